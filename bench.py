@@ -17,7 +17,17 @@ after the last step and compared with the generator's values.
 Inputs are drawn on the device by the package's own generator kernels (ansx_generate_dev, the reference's
 distributions: src/generate_inputs.cpp, include/zipf_dist.hpp); seeds are in the JSON line.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if given and prints the line; everything
+below (per-kernel timing, CPU baselines, the other configurations, the side file of details) runs only with --full
+and is null on the line otherwise.
+
+--dump-outputs DIR writes what the last timed step computed, as float64 arrays (exact for every uint32 value):
+  decoded.npy          the decoded list at 2^21 fixed positions (seeded, sorted), i.e. what decode hands its caller
+  container.npy        the container bytes at 2^21 fixed fractions of its length (seeded), i.e. what encode hands its caller
+  container_bytes.npy  the container's length in bytes (one element)
+  (at N > 1, rank 0's own list and container)
+
+Extra objects on the JSON line (--full):
   roofline       dominant kernel: algorithmic bytes (encode 4+c, decode c+4 bytes/int) / its
                  average launch duration (hipEvents inside libansx on the launch stream), against the
                  8 TB/s HBM peak; `traffic` is replayed from the committed PMC summary (traffic_source)
@@ -523,6 +533,27 @@ def bwtmtf_ranks(max_words=8 * (1 << 20)):
                    "then torch), tools/generate_bwtmtf.x" % total)
 
 
+DUMP_SAMPLE = 1 << 21
+
+
+def dump_outputs(torch, out_dir, d_cont, nb, d_back):
+    """The last timed step's outputs, sampled at seeded positions that depend only on the list's and the container's
+    lengths, as float64 (at most 32 MB in all)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+    n = d_back.numel()
+    pos = np.unique(rng.integers(0, n, size=min(n, DUMP_SAMPLE), dtype=np.int64)) if n > DUMP_SAMPLE else np.arange(n)
+    dec = d_back[torch.from_numpy(pos).to(d_back.device)].cpu().numpy().view("uint32")
+    frac = np.sort(rng.random(DUMP_SAMPLE))
+    cpos = np.minimum((frac * nb).astype(np.int64), max(nb - 1, 0)) if nb > DUMP_SAMPLE else np.arange(nb)
+    cont = d_cont[torch.from_numpy(cpos).to(d_cont.device)].cpu().numpy()
+    np.save(os.path.join(out_dir, "decoded.npy"), dec.astype(np.float64))
+    np.save(os.path.join(out_dir, "container.npy"), cont.astype(np.float64))
+    np.save(os.path.join(out_dir, "container_bytes.npy"), np.array([nb], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -536,6 +567,13 @@ def main():
     ap.add_argument("--dist", default="zipf20s1.2", help="zipf<log2 n>[s<q>] | uniform<lo>-<hi> | uniform256 | geom<p>")
     ap.add_argument("--block", type=int, default=0, help="ints per block (0 = library default)")
     ap.add_argument("--ckpt", type=int, default=0, help="restart interval (0 = library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel pass, CPU baselines, extra configurations, frontier and the details side file "
+                         "(a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last step's outputs to DIR/<name>.npy")
+    ap.add_argument("--details", metavar="FILE", default=os.path.join("bench_out", "bench_details.json"),
+                    help="--full: side file of per-kernel tables and extra rows (relative paths: from the repository root)")
     ap.add_argument("--cpu-sample", type=int, default=64 * (1 << 20))
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
@@ -556,6 +594,8 @@ def main():
                     help="N > 1 control-flow rehearsal on ONE GPU: gloo backend, every rank on cuda:0, "
                          "containers gathered through host copies (not a measurement)")
     args = ap.parse_args()
+    if not args.full:  # a plain run does only what its headline figure needs
+        args.no_cpu = args.no_profile = args.no_extra = True
 
     import torch
 
@@ -771,6 +811,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, outs[(state["k"] - 1) % DEPTH], nb, d_back)
     ok = bool(torch.equal(d_back, d_in))
     merged_ok = None
     if dist is not None:
@@ -923,14 +965,15 @@ def main():
                    "single_stream": single_stream, "first_call": first_call, "gpu_rates": gpu_rates, "cpu_baseline_full": cpu,
                    "roofline_full": roofline, "workspace_mb": ctx.workspace_bytes() / 1e6}
         details_path = None
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            details_path = os.path.join("gpurun_out", "bench_details.json")
-            with open(os.path.join(ROOT, details_path), "w") as fh:
-                json.dump(details, fh, indent=1)
-        except OSError:
-            details_path = None
-        print(json.dumps({"bench_details": details}), file=sys.stderr)
+        if args.full:
+            try:
+                details_path = args.details
+                os.makedirs(os.path.dirname(os.path.join(ROOT, details_path)), exist_ok=True)
+                with open(os.path.join(ROOT, details_path), "w") as fh:
+                    json.dump(details, fh, indent=1)
+            except OSError:
+                details_path = None
+            print(json.dumps({"bench_details": details}), file=sys.stderr)
         if roofline:  # (the sources are sentences: the side file has them)
             roofline = {k: v for k, v in roofline.items() if k not in ("traffic_source", "issue_floor_source")}
         line = {

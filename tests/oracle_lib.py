@@ -6,6 +6,8 @@
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module.
 """
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -145,6 +147,26 @@ def ref(name="libans_ref.so"):
 
 def have_ref():
     return ref() is not None
+
+
+_ref_checks = None
+
+
+def ref_checks(name):
+    """The reference's answers recorded by tests/golden/make_ref_checks_golden.py (tests/golden/ref_checks.json)."""
+    global _ref_checks
+    if _ref_checks is None:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_checks.json")) as fh:
+            _ref_checks = json.load(fh)
+    return _ref_checks[name]
+
+
+def sha256_of(*arrays):
+    """sha256 hex digest of the arrays' bytes, one after the other."""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
 
 
 # ---------------------------------------------------------------- convenience wrappers

@@ -24,6 +24,9 @@ def test_every_declared_symbol_is_exported(A):
     hdr = open(os.path.join(ROOT, "include", "ansx.h")).read()
     declared = sorted(set(re.findall(r"\b(ansx_[a-z0-9_]+)\s*\(", hdr)))
     assert len(declared) >= 16
+    # the package's loader first: it binds libansx to torch's HIP runtime; a bare dlopen as the first load would pull
+    # in a second runtime, and every later ansx_init of the same process (the GPU tests of a whole-suite run) fails
+    A.lib()
     lib = C.CDLL(os.path.join(ROOT, "ans_large_alphabet_amd", "libansx.so"))
     for name in declared:
         assert hasattr(lib, name), name

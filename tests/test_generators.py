@@ -65,15 +65,45 @@ def test_zipf_map_equals_the_reference_class_on_its_own_uniforms():
     assert total >= 10000
 
 
+ZIPF_LIVE = ((1 << 20, 1.2, 77), (1 << 24, 1.2, 78), (1 << 16, 1.0, 79))
+
+
+def mt19937_canonical(seed, m):
+    """The first m doubles std::generate_canonical<double, 53> draws from std::mt19937(seed) (libstdc++: two 32-bit words
+    a, b per double, (a + b 2^32) / 2^64 in double arithmetic).  numpy's MT19937 seeds as std::mt19937 does under its
+    legacy seeding."""
+    bg = np.random.MT19937(0)
+    bg._legacy_seeding(seed)
+    r = bg.random_raw(2 * m)
+    u = (r[0::2].astype(np.float64) + r[1::2].astype(np.float64) * 4294967296.0) / 18446744073709551616.0
+    return np.where(u >= 1.0, np.nextafter(1.0, 0.0), u)
+
+
 def test_zipf_map_equals_the_compiled_reference_live(oracle_built):
-    """The same comparison on fresh draws when oracle/_ref is present (authoring container and GPU box)."""
+    """The same comparison on 20 000 fresh draws per case: the reference's uniforms are regenerated here, and its values and
+    draws per value are pinned by tests/golden/ref_checks.json (make_ref_checks_golden.py); where oracle/_ref is built
+    they are also drawn live."""
     import oracle_lib as ol
 
-    if not ol.have_ref() or not hasattr(ol.ref(), "ref_zipf_trace"):
-        pytest.skip("oracle/_ref not built")
-    for n, q, seed in ((1 << 20, 1.2, 77), (1 << 24, 1.2, 78), (1 << 16, 1.0, 79)):
-        vals, nd, u = ol.ref_zipf_trace(n, q, seed, 20000)
-        _check_zipf_map(n, q, [int(x) for x in vals], [int(x) for x in nd], [float(x) for x in u])
+    want = {(c["n"], c["q"], c["seed"]): c for c in ol.ref_checks("zipf_live")}
+    for n, q, seed in ZIPF_LIVE:
+        w = want[(n, q, seed)]
+        u = mt19937_canonical(seed, w["uniforms"])
+        assert ol.sha256_of(u) == w["u01_sha256"], (n, q, seed)
+        vals, draws, d = [], [], 0
+        for x in u:
+            k, acc = A.zipf_from_uniform(n, q, float(x))
+            d += 1
+            if acc:
+                vals.append(k)
+                draws.append(d)
+                d = 0
+        assert d == 0 and len(vals) == w["count"], (n, q, seed)
+        assert ol.sha256_of(np.array(vals, dtype=np.uint32)) == w["values_sha256"], (n, q, seed)
+        assert ol.sha256_of(np.array(draws, dtype=np.uint32)) == w["draws_sha256"], (n, q, seed)
+        if ol.have_ref() and hasattr(ol.ref(), "ref_zipf_trace"):
+            vals, nd, u = ol.ref_zipf_trace(n, q, seed, 20000)
+            _check_zipf_map(n, q, [int(x) for x in vals], [int(x) for x in nd], [float(x) for x in u])
 
 
 def test_generators_are_pure_functions_of_seed_and_index():

@@ -117,26 +117,43 @@ def test_golden_large(fixture):
 
 
 # ---------------------------------------------------------------- against the real reference
+#
+# Every test here computes the restatement's answers on fixed inputs and compares them with the reference's answers on the
+# same inputs: as recorded in tests/golden/ref_checks.json (make_ref_checks_golden.py, from oracle/_ref) and, where
+# oracle/_ref is built, also computed live.  The ref_* helpers are the reference's side; the maker records their results.
 
-needs_ref = pytest.mark.skipif(not ol.have_ref(), reason="oracle/_ref not built")
+sha = ol.sha256_of
 
 
-@needs_ref
-@pytest.mark.parametrize("f", [1, 2, 3, 5, 7])
-def test_fold_unfold_vs_reference(f):
+def fold_unfold_inputs(f):
     rng = np.random.default_rng(f)
     xs = np.concatenate([np.arange(0, 70000, dtype=np.uint64),
                          rng.integers(0, 1 << 32, size=20000, dtype=np.uint64)]).astype(np.uint32)
+    return xs[::7]
+
+
+def ref_fold_unfold(f, xs):
+    """Rows: the reference's fold mapping of every x, its exception bytes and the undo mapping of the folded symbol."""
+    r = ol.ref()
+    s = [r.ref_fold_mapping(f, int(x)) for x in xs]
+    return np.array([s, [r.ref_fold_exception_bytes(f, v) for v in s], [r.ref_fold_undo_mapping(f, v) for v in s]],
+                    dtype=np.uint32)
+
+
+@pytest.mark.parametrize("f", [1, 2, 3, 5, 7])
+def test_fold_unfold_vs_reference(f):
+    xs = fold_unfold_inputs(f)
+    got = np.zeros((3, xs.size), dtype=np.uint32)
     k = C.c_uint32(0)
-    for x in xs[::7]:
+    for i, x in enumerate(xs):
         s = ol.oracle().ans_oracle_fold(f, int(x), C.byref(k))
-        assert s == ol.ref().ref_fold_mapping(f, int(x))
-        assert k.value == ol.ref().ref_fold_exception_bytes(f, s)
-        assert ol.oracle().ans_oracle_unfold(f, s, None) == ol.ref().ref_fold_undo_mapping(f, s)
+        got[:, i] = (s, k.value, ol.oracle().ans_oracle_unfold(f, s, None))
+    assert sha(got) == ol.ref_checks("fold_unfold")[str(f)]
+    if ol.have_ref():
+        assert np.array_equal(got, ref_fold_unfold(f, xs))
 
 
-@needs_ref
-def test_adjust_freqs_vs_reference():
+def adjust_freqs_cases():
     rng = np.random.default_rng(5)
     for f in (1, 3, 5):
         nf = 1 << (f + 9)
@@ -156,15 +173,29 @@ def test_adjust_freqs_vs_reference():
             if freqs.sum() == 0:
                 freqs[0] = 3
             largest = int(np.nonzero(freqs)[0].max())
-            a = np.zeros(largest + 1, dtype=np.uint32)
-            b = np.zeros(largest + 1, dtype=np.uint32)
-            Ma = ol.oracle().ans_oracle_adjust_freqs(freqs, nf, largest, a)
-            Mb = ol.ref().ref_adjust_freqs(freqs, nf, largest, b)
+            yield f, trial, freqs, nf, largest
+
+
+def ref_adjust_freqs(freqs, nf, largest):
+    b = np.zeros(largest + 1, dtype=np.uint32)
+    return ol.ref().ref_adjust_freqs(freqs, nf, largest, b), b
+
+
+def test_adjust_freqs_vs_reference():
+    want = ol.ref_checks("adjust_freqs")
+    i = 0
+    for f, trial, freqs, nf, largest in adjust_freqs_cases():
+        a = np.zeros(largest + 1, dtype=np.uint32)
+        Ma = ol.oracle().ans_oracle_adjust_freqs(freqs, nf, largest, a)
+        assert sha(np.uint64(Ma), a) == want[i], (f, trial)
+        if ol.have_ref():
+            Mb, b = ref_adjust_freqs(freqs, nf, largest)
             assert Ma == Mb and np.array_equal(a, b), (f, trial)
+        i += 1
+    assert i == len(want)
 
 
-@needs_ref
-def test_prelude_vs_reference():
+def prelude_cases():
     rng = np.random.default_rng(11)
     for trial in range(60):
         nsyms = int(rng.integers(1, 3000))
@@ -173,42 +204,88 @@ def test_prelude_vs_reference():
         # random composition of M into nsyms parts (zeros allowed)
         cuts = np.sort(rng.integers(0, M + 1, size=nsyms - 1))
         nf = np.diff(np.concatenate([[0], cuts, [M]])).astype(np.uint32)
+        yield trial, nf, nsyms, M
+
+
+def ref_prelude(nf, nsyms, M, valid_bits):
+    """The reference's prelude bytes with the bits past `valid_bits` of the last word zeroed."""
+    b = np.zeros(8 * nsyms + 64, dtype=np.uint8)
+    nb = ol.ref().ref_serialize_prelude(nf, nsyms, M, b)
+    vb = valid_bits % 32
+    if vb:
+        w = int.from_bytes(b[nb - 4:nb].tobytes(), "little") & ((1 << vb) - 1)
+        b[nb - 4:nb] = np.frombuffer(w.to_bytes(4, "little"), dtype=np.uint8)
+    return b[:nb].copy()
+
+
+def ref_load_prelude(a, nsyms):
+    back = np.zeros(nsyms, dtype=np.uint32)
+    return ol.ref().ref_load_prelude(a, back), back
+
+
+def test_prelude_vs_reference():
+    want = ol.ref_checks("prelude")
+    assert len(want) == 60
+    for trial, nf, nsyms, M in prelude_cases():
         a = np.zeros(8 * nsyms + 64, dtype=np.uint8)
-        b = np.zeros(8 * nsyms + 64, dtype=np.uint8)
         bits = C.c_uint32(0)
         na = ol.oracle().ans_oracle_write_prelude(nf, nsyms, M, a, C.byref(bits))
-        nb = ol.ref().ref_serialize_prelude(nf, nsyms, M, b)
-        assert na == nb
-        vb = bits.value % 32
-        if vb:
-            w = int.from_bytes(b[nb - 4:nb].tobytes(), "little") & ((1 << vb) - 1)
-            b[nb - 4:nb] = np.frombuffer(w.to_bytes(4, "little"), dtype=np.uint8)
-        assert np.array_equal(a[:na], b[:nb]), trial
-        back = np.zeros(nsyms, dtype=np.uint32)
-        assert ol.ref().ref_load_prelude(a, back) == nsyms
-        assert np.array_equal(back, nf)
+        w = want[trial]
+        assert na == w["bytes"] and sha(a[:na]) == w["sha256"], trial
+        # what the reference's loader read back from these bytes
+        assert w["loaded"] == nsyms and w["loaded_sha256"] == sha(nf), trial
+        if ol.have_ref():
+            assert np.array_equal(a[:na], ref_prelude(nf, nsyms, M, bits.value)), trial
+            got, back = ref_load_prelude(a, nsyms)
+            assert got == nsyms and np.array_equal(back, nf)
 
 
-@needs_ref
-@pytest.mark.parametrize("kind", [ol.FOLD, ol.RFOLD])
-@pytest.mark.parametrize("f", [1, 3, 5])
-def test_streams_vs_reference(kind, f):
+REF_LIBS = ("libans_ref.so", "libans_ref_pattern.so")
+
+
+def ref_stream(kind, f, d, info):
+    """The reference's stream of `d` from both builds (zero- and pattern-initialised stack), padding bits zeroed as the
+    restatement's `info` says, and the reference decoder's output on it: {"bytes", "sha256": [per build], "decoded"}."""
+    rs = [ol.canonicalize(ol.ref_encode(kind, f, d, lib), info) for lib in REF_LIBS]
+    return {"bytes": int(rs[0].size), "sha256": [sha(r) for r in rs], "decoded": sha(ol.ref_decode(kind, f, rs[0], d.size))}
+
+
+def check_stream(w, s, expect_decoded, tag):
+    assert len(s) == w["bytes"], tag
+    for lib, h in zip(REF_LIBS, w["sha256"]):
+        assert sha(s) == h, tag + (lib,)
+    assert sha(expect_decoded) == w["decoded"], tag
+
+
+def stream_cases(kind, f):
     for fam in ["uniform256", "uniform20", "geom0.01", "zipf20s1.2", "sparse_large", "boundaries"]:
         for n in (1, 4, 6, 999, 20000):
             d = ol.gen_inputs(fam, n, seed=77 * f + n)
             if kind == ol.RFOLD:
                 d = d % np.uint32(1 << 20)
-            s, info, _, _ = ol.oracle_encode(kind, f, d)
-            for libname in ("libans_ref.so", "libans_ref_pattern.so"):
-                r = ol.ref_encode(kind, f, d, libname)
-                assert len(r) == len(s)
-                assert np.array_equal(ol.canonicalize(r, info), s), (fam, n, libname)
-            back = ol.ref_decode(kind, f, s, n)
-            if kind == ol.RFOLD and info.reorder_flag == 0:
-                # the reference decoder subtracts T unconditionally
-                assert np.array_equal(back, ol.oracle_decode(kind, f, s, n, ref_f3_compat=True))
-            else:
-                assert np.array_equal(back, d)
+            yield fam, n, d
+
+
+@pytest.mark.parametrize("kind", [ol.FOLD, ol.RFOLD])
+@pytest.mark.parametrize("f", [1, 3, 5])
+def test_streams_vs_reference(kind, f):
+    want = ol.ref_checks("streams")["%d-%d" % (kind, f)]
+    i = 0
+    for fam, n, d in stream_cases(kind, f):
+        s, info, _, _ = ol.oracle_encode(kind, f, d)
+        f3 = kind == ol.RFOLD and info.reorder_flag == 0
+        # SURVEY F3: the reference decoder subtracts T unconditionally
+        expect = ol.oracle_decode(kind, f, s, n, ref_f3_compat=True) if f3 else d
+        check_stream(want[i], s, expect, (fam, n))
+        i += 1
+        if not ol.have_ref():
+            continue
+        for libname in REF_LIBS:
+            r = ol.ref_encode(kind, f, d, libname)
+            assert len(r) == len(s)
+            assert np.array_equal(ol.canonicalize(r, info), s), (fam, n, libname)
+        assert np.array_equal(ol.ref_decode(kind, f, s, n), expect)
+    assert i == len(want)
 
 
 # ---------------------------------------------------------------- properties
@@ -265,64 +342,97 @@ def test_checkpoints_restart_points():
     assert np.array_equal(tail + np.uint64(16 * M), np.array(list(info.final_states), dtype=np.uint64))
 
 
-needs_ref2 = pytest.mark.skipif(not ol.have_ref(), reason="oracle/_ref not built")
+MSB_EDGE = np.array([0, 255, 256, 257, 65535, 65536, 65537, (1 << 24) - 1, 1 << 24, (1 << 24) + 1, (1 << 30) - 1],
+                    dtype=np.uint32)
 
 
-@needs_ref2
-def test_msb_streams_vs_reference():
-    """ANSmsb (include/ans_msb.hpp, methods.hpp:499-515): restatement vs the compiled reference."""
-    edge = np.array([0, 255, 256, 257, 65535, 65536, 65537, (1 << 24) - 1, 1 << 24, (1 << 24) + 1,
-                     (1 << 30) - 1], dtype=np.uint32)
+def msb_cases():
     for fam in ["uniform256", "uniform20", "geom0.01", "zipf20s1.2", "sparse_large", "boundaries"]:
         for n in (1, 4, 6, 999, 20000):
             d = ol.gen_inputs(fam, n, seed=5 + n)
             if n >= 999:
-                d[:edge.size] = edge
-            s, info, _, _ = ol.oracle_encode(ol.MSB, 0, d)
-            for libname in ("libans_ref.so", "libans_ref_pattern.so"):
+                d[:MSB_EDGE.size] = MSB_EDGE
+            yield fam, n, d
+
+
+def test_msb_streams_vs_reference():
+    """ANSmsb (include/ans_msb.hpp, methods.hpp:499-515): restatement vs the compiled reference."""
+    want = ol.ref_checks("msb")
+    i = 0
+    for fam, n, d in msb_cases():
+        s, info, _, _ = ol.oracle_encode(ol.MSB, 0, d)
+        check_stream(want[i], s, d, (fam, n))
+        i += 1
+        if ol.have_ref():
+            for libname in REF_LIBS:
                 r = ol.ref_encode(ol.MSB, 0, d, libname)
                 assert len(r) == len(s) and np.array_equal(ol.canonicalize(r, info), s), (fam, n, libname)
             assert np.array_equal(ol.ref_decode(ol.MSB, 0, s, n), d)
-            assert np.array_equal(ol.oracle_decode(ol.MSB, 0, s, n), d)
+        assert np.array_equal(ol.oracle_decode(ol.MSB, 0, s, n), d)
+    assert i == len(want)
 
 
 # ---------------------------------------------------------------- ANSint and pseudo_adaptive blocks
 
-@needs_ref
+def ansint_cases():
+    rng = np.random.default_rng(3)
+    return [ol.gen_inputs("uniform256", 5000, 1), ol.gen_inputs("geom0.01", 20000, 2), ol.gen_inputs("geom0.4", 7, 3),
+            np.minimum(ol.gen_inputs("zipf20s1.2", 30000, 4), 30000).astype(np.uint32),
+            np.concatenate([np.ones(299990, dtype=np.uint32), np.arange(2, 12, dtype=np.uint32)]),  # frame above 2^16
+            np.array([3] * 4000 + [1], dtype=np.uint32), np.array([5, 1], dtype=np.uint32),
+            rng.integers(1, 2000, 2001).astype(np.uint32)]
+
+
 def test_ansint_matches_reference():
     """ANSint (ans_int.hpp, methods.hpp:484-497): identity symbols, 32-bit frequencies, no u16 exit."""
-    rng = np.random.default_rng(3)
-    cases = [ol.gen_inputs("uniform256", 5000, 1), ol.gen_inputs("geom0.01", 20000, 2), ol.gen_inputs("geom0.4", 7, 3),
-             np.minimum(ol.gen_inputs("zipf20s1.2", 30000, 4), 30000).astype(np.uint32),
-             np.concatenate([np.ones(299990, dtype=np.uint32), np.arange(2, 12, dtype=np.uint32)]),  # frame above 2^16
-             np.array([3] * 4000 + [1], dtype=np.uint32), np.array([5, 1], dtype=np.uint32),
-             rng.integers(1, 2000, 2001).astype(np.uint32)]
+    want = ol.ref_checks("ansint")
+    cases = ansint_cases()
+    assert len(cases) == len(want)
     big = 0
-    for d in cases:
+    for d, w in zip(cases, want):
         s, info, _, _ = ol.oracle_encode(ol.INT, 0, d)
-        r = ol.ref_encode(ol.INT, 0, d)
-        assert np.array_equal(ol.canonicalize(r, info), s), d[:8]
+        assert len(s) == w["bytes"] and sha(s) == w["sha256"][0], d[:8]
+        assert sha(d) == w["decoded"], d[:8]  # the reference decoder returned the input
+        if ol.have_ref():
+            r = ol.ref_encode(ol.INT, 0, d)
+            assert np.array_equal(ol.canonicalize(r, info), s), d[:8]
+            assert np.array_equal(ol.ref_decode(ol.INT, 0, s, d.size), d)
         assert np.array_equal(ol.oracle_decode(ol.INT, 0, s, d.size), d)
-        assert np.array_equal(ol.ref_decode(ol.INT, 0, s, d.size), d)
         big += info.log2_frame > 16
     assert big >= 1  # the wide-frequency regime is covered
 
 
-@needs_ref
-@pytest.mark.parametrize("kind,f", [(ol.MSB, 0), (ol.INT, 0), (ol.FOLD, 1), (ol.FOLD, 3)])
-def test_pseudo_adaptive_block_matches_reference(kind, f):
-    """One block of src/pseudo_adaptive.cpp:85-130: alphabet header + codec stream of the rank-remapped block."""
+def pa_cases():
     for fam, n in (("zipf20s1.2", 16384), ("uniform256", 4096), ("geom0.01", 8192), ("sparse_large", 3000),
                    ("constant", 1000), ("boundaries", 513), ("uniform20", 2048), ("zipf20s1.2", 3)):
         d = ol.gen_inputs(fam, n, seed=7)
         if fam == "sparse_large":
             d = d % np.uint32(1 << 20)  # the harness keeps the running sums of distinct values in 32 bits
+        yield fam, n, d
+
+
+def ref_pa_block(kind, f, d, pinfo, info):
+    r, hb = ol.ref_pa_encode(kind, f, d)
+    return {"header_bytes": int(hb), "bytes": int(r.size), "sha256": sha(ol.canonicalize_pa(r, pinfo, info))}
+
+
+@pytest.mark.parametrize("kind,f", [(ol.MSB, 0), (ol.INT, 0), (ol.FOLD, 1), (ol.FOLD, 3)])
+def test_pseudo_adaptive_block_matches_reference(kind, f):
+    """One block of src/pseudo_adaptive.cpp:85-130: alphabet header + codec stream of the rank-remapped block."""
+    want = ol.ref_checks("pa")["%d-%d" % (kind, f)]
+    i = 0
+    for fam, n, d in pa_cases():
         s, pinfo, info, _, _ = ol.oracle_pa_encode(kind, f, d)
-        r, hb = ol.ref_pa_encode(kind, f, d)
-        assert hb == pinfo.header_bytes and r.size == s.size, (fam, n)
-        assert np.array_equal(ol.canonicalize_pa(r, pinfo, info), s), (fam, n)
+        w = want[i]
+        i += 1
+        assert w["header_bytes"] == pinfo.header_bytes and w["bytes"] == s.size and w["sha256"] == sha(s), (fam, n)
+        if ol.have_ref():
+            r, hb = ol.ref_pa_encode(kind, f, d)
+            assert hb == pinfo.header_bytes and r.size == s.size, (fam, n)
+            assert np.array_equal(ol.canonicalize_pa(r, pinfo, info), s), (fam, n)
         assert np.array_equal(ol.oracle_pa_decode(kind, f, s, n), d), (fam, n)
         assert pinfo.sigma == np.unique(d).size
+    assert i == len(want)
 
 
 def test_golden_compaction_and_ansint():
