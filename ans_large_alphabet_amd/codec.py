@@ -142,6 +142,20 @@ class _Codec:
         if st != L.OK:
             raise L.AnsxError(st, self.name() + ".decode_dev")
 
+    def decode_ranges_dev(self, in_ptr, in_bytes, first, count, out_ptr, out_capacity, stream=None):
+        """Random access: ints [first[i], first[i] + count[i]) of the container at in_ptr, range after range, to
+        out_ptr (out_capacity ints); decodes only the blocks the ranges touch.  first / count: anything numpy turns
+        into uint64 / uint32 arrays of one length.  Returns sum(count)."""
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+        count = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
+        if first.size != count.size:
+            raise ValueError("first and count differ in length (%d, %d)" % (first.size, count.size))
+        st = L.lib().ansx_decode_ranges_dev(self._ctx().handle, self.KIND, self.f, in_ptr, in_bytes, first.ctypes.data,
+                                            count.ctypes.data, first.size, out_ptr, out_capacity, stream)
+        if st != L.OK:
+            raise L.AnsxError(st, self.name() + ".decode_ranges_dev")
+        return int(count.sum(dtype=np.uint64))
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <set>
 #include <string>
@@ -26,6 +27,7 @@
 #include "ansx_gen.h"
 #include "ansx_pa.h"
 #include "ansx_intsparse.h"
+#include "ansx_ranges.h"
 
 namespace {
 
@@ -57,6 +59,9 @@ struct ansx_ctx {
     DevBuf pre_work;  // f = 6, 7: off[] and bit buffer of the generic prelude writer
     DevBuf hist, hterm, sortF, sortSym, attS, prevS, attMeta, blk, table, tab32, scratch, misc, mapped, mostfreq,
         stage_in, stage_out, dec_s2s, dec_cum, dec_info, plain, rf_tmp, log2lut, pa_alpha, pa_info, pairs, lg2i, sizes, nearlist, force;
+    DevBuf rng_plan, rng_cont, rng_list;  // ansx_decode_ranges_dev: flags + block list + range pieces, sub-container, its ints
+    u8* rng_pin = nullptr;                // ... and the pinned host image of rng_plan (an asynchronous upload from
+    size_t rng_pin_cap = 0;               //     pageable memory is staged by the runtime: 0.666 -> 0.618 ms at 4096 ranges)
     u32* h_pin = nullptr;  // pinned: [0..3] gflags, [4..7] result (2 x u64), [8..] header scratch
     // Largest alphabet (max_sym + 1) seen per (kind, fidelity, block_ints): sizes the LDS of the fused
     // model kernel and of the LDS-table encoder without a mid-call round trip (see encode_dev).
@@ -1484,8 +1489,46 @@ int parse_header(const u8* h, size_t bytes, ansx_container_header* out)
     return ANSX_OK;
 }
 
+// The options a container's header stands for
+ansx_opts container_opts(const ansx_container_header& H)
+{
+    ansx_opts o;
+    o.block_ints = H.block_ints;
+    o.ckpt_interval = H.ckpt_interval ? H.ckpt_interval : ANSX_NO_CHECKPOINTS;
+    o.flags = (H.kind & 0x100u) ? ANSX_FLAG_COMPACT_ALPHABET : 0;
+    o.reserved = 0;
+    return o;
+}
+
+// The checks every reader of a container applies to its header before it touches anything behind it: the codec the
+// caller names, the layout the header's own geometry implies, every section inside the input, sane model bounds.
+// P: the container's plan (the container, not the caller's options, defines the geometry).
+int container_plan(const ansx_container_header& H, u32 kind, u32 f, size_t in_bytes, Plan* P)
+{
+    if ((H.kind & 0xFFu) != kind || H.fidelity != f) return ANSX_ERR_FORMAT;
+    const ansx_opts o = container_opts(H);
+    if (H.block_ints == ANSX_SINGLE_STREAM) return ANSX_ERR_FORMAT;
+    if (make_plan((int)(H.kind & 0xFFu), (int)f, (size_t)H.n, &o, P)) return ANSX_ERR_FORMAT;
+    set_restart_format(P, (H.kind & ANSX_KIND_WIDE_RESTART) != 0);
+    if (P->g.nblocks != H.nblocks || P->g.nckf != H.ckpts_per_block || P->g.ckpt != H.ckpt_interval
+        || P->lay.payload_off != H.payload_offset)
+        return ANSX_ERR_FORMAT;
+    // (written so that a crafted payload_bytes near 2^64 cannot wrap the sum; payload_offset covers
+    // the index and the restart-point area, so this also places those inside the input)
+    if (H.payload_offset > in_bytes || H.payload_bytes > in_bytes - H.payload_offset) return ANSX_ERR_FORMAT;
+    // every block stream has a minimum length (index_entry_ok): a payload shorter than that for all blocks is malformed
+    // whatever the index says (in particular payload_bytes == 0, which no parser may take for "no index")
+    if (H.payload_bytes < (u64)P->g.nblocks * (P->g.pa ? 8u : 38u)) return ANSX_ERR_FORMAT;
+    // (with compaction a list whose blocks all hold a single distinct value has no model at all)
+    if (H.max_log2_frame > 31 || (H.max_nsyms == 0 && !P->g.pa) || H.max_nsyms > P->NSP) return ANSX_ERR_FORMAT;
+    return ANSX_OK;
+}
+
+// remember = false: the header is not stored in hdr_cache (ansx_decode_ranges_dev's sub-containers must not stand in
+// for the containers of ordinary calls of the same shape).  epilogue: enqueued behind the decode's kernels and before
+// its status read-back (ansx_decode_ranges_dev's gather: one host round trip less); given the device flags.
 int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u32* d_out,
-    hipStream_t s, bool allow_spec = true)
+    hipStream_t s, bool allow_spec = true, bool remember = true, const std::function<int(const u32*)>* epilogue = nullptr)
 {
     Plan P = Pin;
     bool spec = false;
@@ -1576,27 +1619,8 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
             HIPCHK(c, hipStreamSynchronize(s));
         }
         if ((rc = parse_header(hp, in_bytes, &H))) return rc;
-        if ((H.kind & 0xFFu) != P.g.kind || H.fidelity != f || H.n != P.g.n) return ANSX_ERR_FORMAT;
-        // the container, not the caller's options, defines the geometry
-        ansx_opts o;
-        o.block_ints = H.block_ints;
-        o.ckpt_interval = H.ckpt_interval ? H.ckpt_interval : ANSX_NO_CHECKPOINTS;
-        o.flags = (H.kind & 0x100u) ? ANSX_FLAG_COMPACT_ALPHABET : 0;
-        o.reserved = 0;
-        if (H.block_ints == ANSX_SINGLE_STREAM) return ANSX_ERR_FORMAT;
-        if ((rc = make_plan((int)(H.kind & 0xFFu), (int)f, (size_t)H.n, &o, &P))) return ANSX_ERR_FORMAT;
-        set_restart_format(&P, (H.kind & ANSX_KIND_WIDE_RESTART) != 0);
-        if (P.g.nblocks != H.nblocks || P.g.nckf != H.ckpts_per_block || P.g.ckpt != H.ckpt_interval
-            || P.lay.payload_off != H.payload_offset)
-            return ANSX_ERR_FORMAT;
-        // (written so that a crafted payload_bytes near 2^64 cannot wrap the sum; payload_offset covers
-        // the index and the restart-point area, so this also places those inside the input)
-        if (H.payload_offset > in_bytes || H.payload_bytes > in_bytes - H.payload_offset) return ANSX_ERR_FORMAT;
-        // every block stream has a minimum length (index_entry_ok): a payload shorter than that for all blocks is malformed
-        // whatever the index says (in particular payload_bytes == 0, which no parser may take for "no index")
-        if (H.payload_bytes < (u64)P.g.nblocks * (P.g.pa ? 8u : 38u)) return ANSX_ERR_FORMAT;
-        // (with compaction a list whose blocks all hold a single distinct value has no model at all)
-        if (H.max_log2_frame > 31 || (H.max_nsyms == 0 && !P.g.pa) || H.max_nsyms > P.NSP) return ANSX_ERR_FORMAT;
+        if (H.n != P.g.n) return ANSX_ERR_FORMAT;
+        if ((rc = container_plan(H, P.g.kind, f, in_bytes, &P))) return rc;
         maxM = 1u << H.max_log2_frame;
         max_ns = H.max_nsyms ? H.max_nsyms : 1u;
         max_ep = std::min<u32>(max_ns, (u32)H.max_present_m1 + 1u);
@@ -1661,6 +1685,7 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
     if (P.g.pa)
         LAUNCH(c, "k_pa_unmap", k_pa_unmap, P.g.nblocks, 256, 0, s, P.g, (const u32*)c->pa_alpha.p, pa_info, d_out, gflags);
     if (spec) LAUNCH(c, "k_check_header", k_check_header, 1, 64, 0, s, d_in, Hspec, gflags);
+    if (epilogue && (rc = (*epilogue)(gflags))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_pin, c->misc.p, 64, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (spec && (c->h_pin[ANSX_G_ERR] & (1u << ANSX_G_HDR_BIT))) {
@@ -1668,7 +1693,7 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
         return decode_dev(c, Pin, d_in, in_bytes, d_out, s, false);
     }
     const int st = flags_to_status(c->h_pin[ANSX_G_ERR]);
-    if (!P.plain && !spec && st == ANSX_OK) {
+    if (!P.plain && !spec && st == ANSX_OK && remember) {
         ansx_container_header Hc;
         memcpy(&Hc, (u8*)c->h_pin + 64, sizeof(Hc));
         if (c->hdr_cache.find(hkey) == c->hdr_cache.end()) {
@@ -1683,6 +1708,139 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
         c->hdr_cache[hkey] = Hc;
     }
     return st;
+}
+
+// --------------------------------------------------------------------------------- random access
+// ansx_decode_ranges_dev: host plan -> k_range_index + k_range_copy build a container of the
+// touched blocks only -> decode_dev on it (no cached header in or out) -> k_range_gather into the caller's buffer.
+int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* first, const u32* count,
+    size_t nranges, u32* d_out, size_t cap, hipStream_t s)
+{
+    int rc;
+    if (in_bytes < sizeof(ansx_container_header)) return ANSX_ERR_FORMAT;
+    u8* hp = (u8*)c->h_pin + 64;
+    HIPCHK(c, hipMemcpyAsync(hp, d_in, sizeof(ansx_container_header), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    ansx_container_header H;
+    if ((rc = parse_header(hp, in_bytes, &H))) return rc;  // (a single-stream stream has no magic: ANSX_ERR_FORMAT)
+    Plan P;
+    if ((rc = container_plan(H, (u32)kind, (u32)f, in_bytes, &P))) return rc;
+    P.g.payload_bytes = H.payload_bytes;  // (index_entry_ok on the source's entries)
+    const u64 n = H.n, bi = P.g.block_ints;
+
+    // ranges -> block spans; their union as sorted runs of consecutive blocks, each numbered from its first touched block
+    u64 total = 0;
+    std::vector<std::pair<u64, u64>> span;  // [first block, last block] of every non-empty range
+    span.reserve(nranges);
+    for (size_t i = 0; i < nranges; i++) {
+        if (first[i] > n || (u64)count[i] > n - first[i]) return ANSX_ERR_ARG;
+        if (!count[i]) continue;
+        span.push_back({ first[i] / bi, (first[i] + count[i] - 1) / bi });
+        total += count[i];  // (at most 2^32 - 1 per range: no wrap below 2^32 ranges)
+    }
+    if (total > cap) return ANSX_ERR_CAPACITY;
+    if (total == 0) return ANSX_OK;
+    std::sort(span.begin(), span.end());
+    struct Run {
+        u64 b0, b1, k0;  // blocks b0..b1 are touched blocks k0.. of the sub-container
+    };
+    std::vector<Run> runs;
+    u64 T = 0;
+    for (const auto& sp : span) {
+        if (!runs.empty() && sp.first <= runs.back().b1 + 1) {
+            if (sp.second > runs.back().b1) {
+                T += sp.second - runs.back().b1;
+                runs.back().b1 = sp.second;
+            }
+            continue;
+        }
+        runs.push_back({ sp.first, sp.second, T });
+        T += sp.second - sp.first + 1;
+    }
+    const u64 last_b = runs.back().b1;
+    const u64 n_sub = (T - 1) * bi + std::min<u64>(bi, n - last_b * bi);  // (only the source's last block can be short: it sorts last)
+
+    // the sub-container's plan: make_plan's layout for n_sub ints, the source's restart-point format
+    const ansx_opts o = container_opts(H);
+    Plan Ps;
+    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
+    set_restart_format(&Ps, P.g.ckw != 0);
+    if (Ps.g.nblocks != T || Ps.g.nckf != P.g.nckf) return ANSX_ERR_FORMAT;
+    // (max_present_m1, max_nsyms, max_log2_frame are bounds over the blocks: they hold for any subset)
+    ansx_container_header Hs = H;
+    Hs.n = n_sub;
+    Hs.nblocks = (u32)T;
+    Hs.payload_bytes = 0;  // (k_range_index writes the sum of the touched blocks' stream lengths)
+    Hs.payload_offset = Ps.lay.payload_off;
+    const u64 cap_pay = std::min<u64>(H.payload_bytes, T * (u64)block_bound(kind, (u32)f, P.g.block_ints, P.g.pa != 0));
+    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
+
+    // the plan on the device, one upload: flags[4] | touched blocks u32[T] | range pieces | first piece per range u32[nr + 1]
+    std::vector<ansx_range_piece> pieces;
+    pieces.reserve(span.size());
+    std::vector<u32> pstart;
+    pstart.reserve(span.size() + 1);
+    u64 npieces = 0, dst = 0;
+    for (size_t i = 0; i < nranges; i++) {
+        if (!count[i]) continue;
+        const u64 b0 = first[i] / bi;
+        auto it = std::upper_bound(runs.begin(), runs.end(), b0, [](u64 v, const Run& r) { return v < r.b0; });
+        const Run& r = *(it - 1);
+        pieces.push_back({ (r.k0 + (b0 - r.b0)) * bi + (first[i] - b0 * bi), dst, (u64)count[i] });
+        pstart.push_back((u32)npieces);
+        dst += count[i];
+        npieces += (count[i] + ANSX_RANGE_CHUNK - 1) / ANSX_RANGE_CHUNK;
+    }
+    if (npieces > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    pstart.push_back((u32)npieces);
+    const u32 nr = (u32)pieces.size();
+    const size_t o_tb = 16, o_pc = rup(o_tb + 4 * T, 16), o_ps = rup(o_pc + sizeof(ansx_range_piece) * nr, 16);
+    const size_t plan_bytes = o_ps + 4 * ((size_t)nr + 1);
+    if (plan_bytes > c->rng_pin_cap) {
+        if (c->rng_pin) HIPCHK(c, hipHostFree(c->rng_pin));
+        c->rng_pin = nullptr;
+        c->rng_pin_cap = 0;
+        const size_t want = plan_bytes + (plan_bytes >> 3) + 4096;
+        HIPCHK(c, hipHostMalloc((void**)&c->rng_pin, want, hipHostMallocDefault));
+        c->rng_pin_cap = want;
+    }
+    {
+        u8* hb = c->rng_pin;  // (no copy out of it is pending: every call ends in a synchronisation)
+        memset(hb, 0, o_tb);
+        u32* tb = (u32*)(hb + o_tb);
+        for (const Run& r : runs)
+            for (u64 b = r.b0; b <= r.b1; b++) *tb++ = (u32)b;
+        memcpy(hb + o_pc, pieces.data(), sizeof(ansx_range_piece) * nr);
+        memcpy(hb + o_ps, pstart.data(), 4 * ((size_t)nr + 1));
+    }
+    if ((rc = ensure(c, c->rng_plan, plan_bytes))) return rc;
+    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
+    if ((rc = ensure(c, c->rng_list, 4 * n_sub + 64))) return rc;
+    u8* dplan = (u8*)c->rng_plan.p;
+    u32* dflags = (u32*)dplan;
+    const u32* dtb = (const u32*)(dplan + o_tb);
+    u8* sub = (u8*)c->rng_cont.p;
+    u32* list = (u32*)c->rng_list.p;
+    HIPCHK(c, hipMemcpyAsync(dplan, c->rng_pin, plan_bytes, hipMemcpyHostToDevice, s));
+
+    const ansx_range_lay sl = { P.lay.ckoff_off, P.lay.ckstate_off, P.lay.hint_off, P.lay.payload_off };
+    const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
+    LAUNCH(c, "k_range_index", k_range_index, 1, 1024, 0, s, d_in, P.g, dtb, (u32)T, Hs, sub, cap_pay, dflags);
+    LAUNCH(c, "k_range_copy", k_range_copy, (u32)T, 256, 0, s, d_in, P.g, sl, dl, dtb, sub, cap_pay, dflags);
+    // the gather and the read-back of this call's own flags ride on the decode's final read-back (the gather skips
+    // when the decode flagged an error)
+    u32* hflag = c->h_pin + 512;  // (bytes 2048.. of the pinned page: clear of the header scratch decode_dev uses)
+    *hflag = 0;
+    const std::function<int(const u32*)> gather = [&](const u32* gflags) -> int {
+        const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
+        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, (const ansx_range_piece*)(dplan + o_pc),
+            (const u32*)(dplan + o_ps), nr, (u32)npieces, d_out, gflags);
+        HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
+        return ANSX_OK;
+    };
+    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, false, false, &gather);
+    if (*hflag) return ANSX_ERR_FORMAT;  // an index entry of a touched block was invalid
+    return rc;
 }
 
 }  // namespace
@@ -1866,7 +2024,8 @@ void ansx_destroy(ansx_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
-        &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->log2lut, &c->pa_alpha, &c->pa_info, &c->pairs, &c->lg2i, &c->sizes, &c->nearlist, &c->force, &c->geo_big };
+        &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->log2lut, &c->pa_alpha, &c->pa_info, &c->pairs, &c->lg2i, &c->sizes, &c->nearlist, &c->force, &c->geo_big,
+        &c->rng_plan, &c->rng_cont, &c->rng_list };
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& kv : c->geo)
@@ -1876,6 +2035,7 @@ void ansx_destroy(ansx_ctx* c)
         (void)hipEventDestroy(r.e1);
     }
     if (c->h_pin) (void)hipHostFree(c->h_pin);
+    if (c->rng_pin) (void)hipHostFree(c->rng_pin);
     (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1937,6 +2097,19 @@ int ansx_decode_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     return decode_dev(c, P, d_in, in_bytes, d_out, s);
+}
+
+int ansx_decode_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, const uint64_t* first,
+    const uint32_t* count, size_t nranges, uint32_t* d_out, size_t out_capacity_ints, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!first || !count)) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    if (nranges == 0) return ANSX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return decode_ranges(c, kind, f, d_in, in_bytes, (const u64*)first, count, nranges, d_out, out_capacity_ints, s);
 }
 
 int ansx_encode(ansx_ctx* c, int kind, int f, const uint32_t* in, size_t n, uint8_t* out, size_t cap,
@@ -2216,7 +2389,8 @@ size_t ansx_workspace_bytes(const ansx_ctx* c)
     if (!c) return 0;
     const DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
-        &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->pa_alpha, &c->pa_info, &c->pairs, &c->sizes };
+        &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->pa_alpha, &c->pa_info, &c->pairs, &c->sizes,
+        &c->rng_plan, &c->rng_cont, &c->rng_list };
     size_t t = 0;
     for (const DevBuf* b : bufs) t += b->cap;
     return t;

@@ -161,6 +161,27 @@ int ansx_encode_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t* d_in,
 int ansx_decode_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in, size_t in_bytes,
     uint32_t* d_out, size_t n, const ansx_opts* opts, void* stream);
 
+/* Random access: decode `nranges` ranges [first[i], first[i] + count[i]) of the list held in a CONTAINER (not a
+ * single-stream reference stream) without decoding the blocks no range touches.  first / count are HOST arrays;
+ * d_in (16-byte aligned) and d_out (4-byte aligned) are device memory.  Range i is written to
+ * d_out[sum_{j<i} count[j] ...]; ranges may overlap, repeat, be unsorted, or have count 0.  The output is
+ * bit-identical to concatenating full[first[i] : first[i] + count[i]], where full is what ansx_decode_dev returns for
+ * the same container.  Every container form the library writes is accepted (any codec, compaction, either
+ * restart-point format, no restart points, any block_ints, merged containers); the container's header defines n.
+ * Errors: ANSX_ERR_ARG for a null ctx / d_in / d_out, a null first or count with nranges > 0, a misaligned pointer,
+ * or any first[i] + count[i] > n (checked on the host against the header, before anything is launched);
+ * ANSX_ERR_CAPACITY when sum(count) > out_capacity_ints; ANSX_ERR_FORMAT when kind / fidelity differ from the header,
+ * the input is not a container, or an index entry of a touched block is invalid.  nranges == 0 or all counts 0:
+ * ANSX_OK with nothing launched.
+ * Selectivity: of an untouched block nothing is read -- stream, restart points, parse hints, index entries -- and no
+ * kernel's grid grows with the container's block count: the touched blocks are copied into a workspace container
+ * (header + their index entries, rebased), which the ordinary decode path decodes, and the ranges are gathered from
+ * it.  The call leaves no trace in the context that later ansx_decode_dev / ansx_encode_dev calls would see (no
+ * remembered header, no per-geometry hint).  Returns after the status has been read back, like ansx_decode_dev. */
+int ansx_decode_ranges_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in, size_t in_bytes,
+    const uint64_t* first, const uint32_t* count, size_t nranges, uint32_t* d_out, size_t out_capacity_ints,
+    void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
