@@ -156,6 +156,26 @@ class _Codec:
             raise L.AnsxError(st, self.name() + ".decode_ranges_dev")
         return int(count.sum(dtype=np.uint64))
 
+    def decode_device_ranges_dev(self, in_ptr, in_bytes, first_ptr, count_ptr, nranges, out_ptr, out_capacity,
+                                 offsets_ptr=None, stream=None):
+        """Random access with the ranges in device memory: first_ptr -> nranges uint64 firsts, count_ptr -> nranges
+        uint32 counts, both device pointers read on `stream` (e.g. an int64 / int32 tensor's data_ptr()).  Writes the
+        ranges back to back to out_ptr (out_capacity ints) and, if offsets_ptr is given, the nranges + 1 exclusive
+        prefix sums of count there.  Returns sum(count); ANSX_ERR_CAPACITY raises AnsxError with .needed = sum(count)."""
+        for name, v in (("nranges", nranges), ("out_capacity", out_capacity), ("in_bytes", in_bytes)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        total = C.c_uint64(0)
+        st = L.lib().ansx_decode_device_ranges_dev(self._ctx().handle, self.KIND, self.f, in_ptr, int(in_bytes),
+                                                   first_ptr, count_ptr, int(nranges), out_ptr, int(out_capacity),
+                                                   offsets_ptr, C.byref(total), stream)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".decode_device_ranges_dev")
+            if st == L.ERR_CAPACITY:
+                err.needed = int(total.value)
+            raise err
+        return int(total.value)
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

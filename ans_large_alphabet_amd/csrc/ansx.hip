@@ -60,6 +60,7 @@ struct ansx_ctx {
     DevBuf hist, hterm, sortF, sortSym, attS, prevS, attMeta, blk, table, tab32, scratch, misc, mapped, mostfreq,
         stage_in, stage_out, dec_s2s, dec_cum, dec_info, plain, rf_tmp, log2lut, pa_alpha, pa_info, pairs, lg2i, sizes, nearlist, force;
     DevBuf rng_plan, rng_cont, rng_list;  // ansx_decode_ranges_dev: flags + block list + range pieces, sub-container, its ints
+    DevBuf rng_dev;                       // ansx_decode_device_ranges_dev: the device planner's workspace
     u8* rng_pin = nullptr;                // ... and the pinned host image of rng_plan (an asynchronous upload from
     size_t rng_pin_cap = 0;               //     pageable memory is staged by the runtime: 0.666 -> 0.618 ms at 4096 ranges)
     u32* h_pin = nullptr;  // pinned: [0..3] gflags, [4..7] result (2 x u64), [8..] header scratch
@@ -1711,21 +1712,81 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
 }
 
 // --------------------------------------------------------------------------------- random access
-// ansx_decode_ranges_dev: host plan -> k_range_index + k_range_copy build a container of the
-// touched blocks only -> decode_dev on it (no cached header in or out) -> k_range_gather into the caller's buffer.
-int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* first, const u32* count,
-    size_t nranges, u32* d_out, size_t cap, hipStream_t s)
+// ansx_decode_ranges_dev / ansx_decode_device_ranges_dev: a plan (host- or device-built) ->
+// k_range_index + k_range_copy build a container of the touched blocks only -> decode_dev on it (no cached header in
+// or out) -> k_range_gather into the caller's buffer.
+
+// The source container's header, checked as decode_dev checks it, and its plan
+int range_source(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, hipStream_t s, ansx_container_header* H,
+    Plan* P)
 {
     int rc;
     if (in_bytes < sizeof(ansx_container_header)) return ANSX_ERR_FORMAT;
     u8* hp = (u8*)c->h_pin + 64;
     HIPCHK(c, hipMemcpyAsync(hp, d_in, sizeof(ansx_container_header), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    if ((rc = parse_header(hp, in_bytes, H))) return rc;  // (a single-stream stream has no magic: ANSX_ERR_FORMAT)
+    if ((rc = container_plan(*H, (u32)kind, (u32)f, in_bytes, P))) return rc;
+    P->g.payload_bytes = H->payload_bytes;  // (index_entry_ok on the source's entries)
+    return ANSX_OK;
+}
+
+// The tail both fronts share, from the plan on the device: tb[T] the touched blocks (ascending, unique; last_b the
+// last), R the pieces of the nr non-empty ranges, pstart[nr + 1] their first gather pieces; dflags: a zeroed word.
+int range_tail(ansx_ctx* c, int kind, int f, const u8* d_in, const ansx_container_header& H, const Plan& P, u64 T,
+    u64 last_b, const u32* dtb, const ansx_range_piece* R, const u32* pstart, u32 nr, u64 npieces, u32* dflags,
+    u32* d_out, hipStream_t s)
+{
+    int rc;
+    const u64 n = H.n, bi = P.g.block_ints;
+    const u64 n_sub = (T - 1) * bi + std::min<u64>(bi, n - last_b * bi);  // (only the source's last block can be short: it sorts last)
+
+    // the sub-container's plan: make_plan's layout for n_sub ints, the source's restart-point format
+    const ansx_opts o = container_opts(H);
+    Plan Ps;
+    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
+    set_restart_format(&Ps, P.g.ckw != 0);
+    if (Ps.g.nblocks != T || Ps.g.nckf != P.g.nckf) return ANSX_ERR_FORMAT;
+    // (max_present_m1, max_nsyms, max_log2_frame are bounds over the blocks: they hold for any subset)
+    ansx_container_header Hs = H;
+    Hs.n = n_sub;
+    Hs.nblocks = (u32)T;
+    Hs.payload_bytes = 0;  // (k_range_index writes the sum of the touched blocks' stream lengths)
+    Hs.payload_offset = Ps.lay.payload_off;
+    const u64 cap_pay = std::min<u64>(H.payload_bytes, T * (u64)block_bound(kind, (u32)f, P.g.block_ints, P.g.pa != 0));
+    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
+    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
+    if ((rc = ensure(c, c->rng_list, 4 * n_sub + 64))) return rc;
+    u8* sub = (u8*)c->rng_cont.p;
+    u32* list = (u32*)c->rng_list.p;
+
+    const ansx_range_lay sl = { P.lay.ckoff_off, P.lay.ckstate_off, P.lay.hint_off, P.lay.payload_off };
+    const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
+    LAUNCH(c, "k_range_index", k_range_index, 1, 1024, 0, s, d_in, P.g, dtb, (u32)T, Hs, sub, cap_pay, dflags);
+    LAUNCH(c, "k_range_copy", k_range_copy, (u32)T, 256, 0, s, d_in, P.g, sl, dl, dtb, sub, cap_pay, dflags);
+    // the gather and the read-back of this call's own flags ride on the decode's final read-back (the gather skips
+    // when the decode flagged an error)
+    u32* hflag = c->h_pin + 512;  // (bytes 2048.. of the pinned page: clear of the header scratch decode_dev uses)
+    *hflag = 0;
+    const std::function<int(const u32*)> gather = [&](const u32* gflags) -> int {
+        const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
+        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, R, pstart, nr, (u32)npieces, d_out, gflags);
+        HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
+        return ANSX_OK;
+    };
+    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, false, false, &gather);
+    if (*hflag) return ANSX_ERR_FORMAT;  // an index entry of a touched block was invalid
+    return rc;
+}
+
+// ansx_decode_ranges_dev: the plan built on the host from host arrays, uploaded in one copy
+int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* first, const u32* count,
+    size_t nranges, u32* d_out, size_t cap, hipStream_t s)
+{
+    int rc;
     ansx_container_header H;
-    if ((rc = parse_header(hp, in_bytes, &H))) return rc;  // (a single-stream stream has no magic: ANSX_ERR_FORMAT)
     Plan P;
-    if ((rc = container_plan(H, (u32)kind, (u32)f, in_bytes, &P))) return rc;
-    P.g.payload_bytes = H.payload_bytes;  // (index_entry_ok on the source's entries)
+    if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &H, &P))) return rc;
     const u64 n = H.n, bi = P.g.block_ints;
 
     // ranges -> block spans; their union as sorted runs of consecutive blocks, each numbered from its first touched block
@@ -1757,23 +1818,6 @@ int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes,
         runs.push_back({ sp.first, sp.second, T });
         T += sp.second - sp.first + 1;
     }
-    const u64 last_b = runs.back().b1;
-    const u64 n_sub = (T - 1) * bi + std::min<u64>(bi, n - last_b * bi);  // (only the source's last block can be short: it sorts last)
-
-    // the sub-container's plan: make_plan's layout for n_sub ints, the source's restart-point format
-    const ansx_opts o = container_opts(H);
-    Plan Ps;
-    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
-    set_restart_format(&Ps, P.g.ckw != 0);
-    if (Ps.g.nblocks != T || Ps.g.nckf != P.g.nckf) return ANSX_ERR_FORMAT;
-    // (max_present_m1, max_nsyms, max_log2_frame are bounds over the blocks: they hold for any subset)
-    ansx_container_header Hs = H;
-    Hs.n = n_sub;
-    Hs.nblocks = (u32)T;
-    Hs.payload_bytes = 0;  // (k_range_index writes the sum of the touched blocks' stream lengths)
-    Hs.payload_offset = Ps.lay.payload_off;
-    const u64 cap_pay = std::min<u64>(H.payload_bytes, T * (u64)block_bound(kind, (u32)f, P.g.block_ints, P.g.pa != 0));
-    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
 
     // the plan on the device, one upload: flags[4] | touched blocks u32[T] | range pieces | first piece per range u32[nr + 1]
     std::vector<ansx_range_piece> pieces;
@@ -1814,33 +1858,85 @@ int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes,
         memcpy(hb + o_ps, pstart.data(), 4 * ((size_t)nr + 1));
     }
     if ((rc = ensure(c, c->rng_plan, plan_bytes))) return rc;
-    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
-    if ((rc = ensure(c, c->rng_list, 4 * n_sub + 64))) return rc;
     u8* dplan = (u8*)c->rng_plan.p;
-    u32* dflags = (u32*)dplan;
-    const u32* dtb = (const u32*)(dplan + o_tb);
-    u8* sub = (u8*)c->rng_cont.p;
-    u32* list = (u32*)c->rng_list.p;
     HIPCHK(c, hipMemcpyAsync(dplan, c->rng_pin, plan_bytes, hipMemcpyHostToDevice, s));
+    return range_tail(c, kind, f, d_in, H, P, T, runs.back().b1, (const u32*)(dplan + o_tb),
+        (const ansx_range_piece*)(dplan + o_pc), (const u32*)(dplan + o_ps), nr, npieces, (u32*)dplan, d_out, s);
+}
 
-    const ansx_range_lay sl = { P.lay.ckoff_off, P.lay.ckstate_off, P.lay.hint_off, P.lay.payload_off };
-    const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
-    LAUNCH(c, "k_range_index", k_range_index, 1, 1024, 0, s, d_in, P.g, dtb, (u32)T, Hs, sub, cap_pay, dflags);
-    LAUNCH(c, "k_range_copy", k_range_copy, (u32)T, 256, 0, s, d_in, P.g, sl, dl, dtb, sub, cap_pay, dflags);
-    // the gather and the read-back of this call's own flags ride on the decode's final read-back (the gather skips
-    // when the decode flagged an error)
-    u32* hflag = c->h_pin + 512;  // (bytes 2048.. of the pinned page: clear of the header scratch decode_dev uses)
-    *hflag = 0;
-    const std::function<int(const u32*)> gather = [&](const u32* gflags) -> int {
-        const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
-        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, (const ansx_range_piece*)(dplan + o_pc),
-            (const u32*)(dplan + o_ps), nr, (u32)npieces, d_out, gflags);
-        HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
-        return ANSX_OK;
-    };
-    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, false, false, &gather);
-    if (*hflag) return ANSX_ERR_FORMAT;  // an index entry of a touched block was invalid
-    return rc;
+// ansx_decode_device_ranges_dev: the plan built on the device from first / count in device memory (ansx_ranges.h,
+// "device plan"); one read-back of its scalars decides the errors and sizes the tail, no O(nranges) copy either way.
+int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
+    const u32* d_count, size_t nranges, u32* d_out, size_t cap, u64* d_offsets, u64* total_ints, hipStream_t s)
+{
+    int rc;
+    ansx_container_header H;
+    Plan P;
+    if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &H, &P))) return rc;
+    const u64 n = H.n, bi = P.g.block_ints, nr = nranges, nb = P.g.nblocks;
+    u32 kb = 0;  // key bits of a block id
+    while ((1ull << kb) < nb) kb++;
+    const u64 nt = (nr + ANSX_DR_TILE - 1) / ANSX_DR_TILE;
+
+    // workspace: scalars u64[8] | per-tile partials u64[6 nt] | radix histogram u32[16 nt] | pieces[nr] |
+    // pstart u32[nr + 1] | spans (b0, b1 + 1) twice over u32[4 nr] | tb u32[nblocks]
+    const size_t o_pt = 64, o_h = o_pt + 48 * nt, o_pc = rup(o_h + 64 * nt, 16), o_ps = o_pc + sizeof(ansx_range_piece) * nr;
+    const size_t o_sp = rup(o_ps + 4 * (nr + 1), 16), o_tb = o_sp + 16 * nr, bytes = o_tb + 4 * nb;
+    if ((rc = ensure(c, c->rng_dev, bytes))) return rc;
+    u8* w = (u8*)c->rng_dev.p;
+    u64* sc = (u64*)w;
+    u64* part = (u64*)(w + o_pt);
+    u64* partm = part + 4 * nt;
+    u64* parta = part + 5 * nt;
+    u32* hist = (u32*)(w + o_h);
+    ansx_range_piece* R = (ansx_range_piece*)(w + o_pc);
+    u32* pstart = (u32*)(w + o_ps);
+    u32* kv[4] = { (u32*)(w + o_sp), (u32*)(w + o_sp) + nr, (u32*)(w + o_sp) + 2 * nr, (u32*)(w + o_sp) + 3 * nr };
+    u32* tb = (u32*)(w + o_tb);
+    u32 cur = 0;  // the sorted spans are kv[cur], kv[cur + 1]; the union goes to the other pair
+    if (nr <= ANSX_DR_TILE) {
+        LAUNCH(c, "k_dr_plan_small", k_dr_plan_small, 1, ANSX_DR_NT, 0, s, d_first, d_count, (u32)nr, n, bi, kb, d_offsets,
+            R, pstart, kv[2], kv[3], parta, sc);
+    } else {
+        const u32 g = (u32)nt;
+        LAUNCH(c, "k_dr_spans", k_dr_spans, g, ANSX_DR_NT, 0, s, d_first, d_count, nr, n, part);
+        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, part, nt, 4u, nt, sc, (u32*)&sc[ANSX_DR_FLAGS]);
+        LAUNCH(c, "k_dr_compact", k_dr_compact, g, ANSX_DR_NT, 0, s, d_first, d_count, nr, n, bi, (const u64*)part,
+            (const u64*)sc, d_offsets, kv[0], kv[1], R, pstart);
+        for (u32 sh = 0; sh < kb; sh += 4) {
+            LAUNCH(c, "k_dr_digit_count", k_dr_digit_count, g, ANSX_DR_NT, 0, s, kv[cur], (const u64*)sc, sh, hist);
+            LAUNCH(c, "k_dr_scan", (k_dr_scan<u32, false>), 1, ANSX_DR_NT, 0, s, hist, 16 * nt, 1u, 0ull, (u64*)nullptr,
+                (u32*)nullptr);
+            LAUNCH(c, "k_dr_digit_scatter", k_dr_digit_scatter, g, ANSX_DR_NT, 0, s, kv[cur], kv[cur + 1], kv[2 - cur],
+                kv[3 - cur], (const u64*)sc, sh, (const u32*)hist);
+            cur = 2 - cur;
+        }
+        LAUNCH(c, "k_dr_tile_max", k_dr_tile_max, g, ANSX_DR_NT, 0, s, kv[cur + 1], (const u64*)sc, partm);
+        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, true>), 1, ANSX_DR_NT, 0, s, partm, nt, 1u, 0ull, sc + ANSX_DR_LASTB1,
+            (u32*)nullptr);
+        LAUNCH(c, "k_dr_adds", k_dr_adds, g, ANSX_DR_NT, 0, s, kv[cur], kv[cur + 1], (const u64*)sc, (const u64*)partm,
+            kv[2 - cur], kv[3 - cur], parta);
+        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, parta, nt, 1u, 0ull, sc + ANSX_DR_T,
+            (u32*)nullptr);
+        LAUNCH(c, "k_dr_pieces", k_dr_pieces, (u32)((nr + ANSX_DR_NT - 1) / ANSX_DR_NT), ANSX_DR_NT, 0, s, R,
+            (const u64*)sc, bi, kv[2 - cur], kv[3 - cur], (const u64*)parta);
+    }
+    const u32* S = kv[2 - cur];
+    const u32* offl = kv[3 - cur];
+    u64* hs = (u64*)((u8*)c->h_pin + 3072);  // (clear of decode_dev's header scratch and range_tail's flag word)
+    HIPCHK(c, hipMemcpyAsync(hs, sc, 64, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (hs[ANSX_DR_BAD]) return ANSX_ERR_ARG;
+    const u64 total = hs[ANSX_DR_TOTAL], nne = hs[ANSX_DR_NNE], npieces = hs[ANSX_DR_NPIECES], T = hs[ANSX_DR_T];
+    if (total_ints) *total_ints = total;
+    if (total > cap) return ANSX_ERR_CAPACITY;
+    if (total == 0) return ANSX_OK;
+    if (npieces > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (T == 0 || T > nb || nne == 0 || hs[ANSX_DR_LASTB1] == 0) return ANSX_ERR_HIP;  // (cannot happen: a planner fault)
+    LAUNCH(c, "k_dr_blocks", k_dr_blocks, (u32)((T + ANSX_DR_NT - 1) / ANSX_DR_NT), ANSX_DR_NT, 0, s, tb, (u32)T, (u32)nne,
+        S, offl, (const u64*)parta);
+    return range_tail(c, kind, f, d_in, H, P, T, hs[ANSX_DR_LASTB1] - 1, tb, R, pstart, (u32)nne, npieces,
+        (u32*)&sc[ANSX_DR_FLAGS], d_out, s);
 }
 
 }  // namespace
@@ -2025,7 +2121,7 @@ void ansx_destroy(ansx_ctx* c)
     DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->log2lut, &c->pa_alpha, &c->pa_info, &c->pairs, &c->lg2i, &c->sizes, &c->nearlist, &c->force, &c->geo_big,
-        &c->rng_plan, &c->rng_cont, &c->rng_list };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev };
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& kv : c->geo)
@@ -2110,6 +2206,27 @@ int ansx_decode_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, si
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     return decode_ranges(c, kind, f, d_in, in_bytes, (const u64*)first, count, nranges, d_out, out_capacity_ints, s);
+}
+
+int ansx_decode_device_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes,
+    const uint64_t* d_first, const uint32_t* d_count, size_t nranges, uint32_t* d_out, size_t out_capacity_ints,
+    uint64_t* d_offsets, uint64_t* total_ints, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!d_first || !d_count)) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u) || ((uintptr_t)d_first & 7u) || ((uintptr_t)d_count & 3u)
+        || ((uintptr_t)d_offsets & 7u))
+        return ANSX_ERR_ARG;
+    if (nranges > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (nranges == 0) {
+        if (total_ints) *total_ints = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return decode_device_ranges(c, kind, f, d_in, in_bytes, (const u64*)d_first, d_count, nranges, d_out,
+        out_capacity_ints, (u64*)d_offsets, (u64*)total_ints, s);
 }
 
 int ansx_encode(ansx_ctx* c, int kind, int f, const uint32_t* in, size_t n, uint8_t* out, size_t cap,
@@ -2390,7 +2507,7 @@ size_t ansx_workspace_bytes(const ansx_ctx* c)
     const DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->pa_alpha, &c->pa_info, &c->pairs, &c->sizes,
-        &c->rng_plan, &c->rng_cont, &c->rng_list };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev };
     size_t t = 0;
     for (const DevBuf* b : bufs) t += b->cap;
     return t;

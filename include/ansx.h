@@ -182,6 +182,26 @@ int ansx_decode_ranges_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t*
     const uint64_t* first, const uint32_t* count, size_t nranges, uint32_t* d_out, size_t out_capacity_ints,
     void* stream);
 
+/* Random access with the ranges in DEVICE memory: as ansx_decode_ranges_dev, except that d_first (8-byte aligned) and
+ * d_count (4-byte aligned) are device arrays, read on `stream` (a kernel that wrote them earlier on that stream is
+ * ordered before), and the plan -- touched blocks, range positions -- is built on the device: no copy of O(nranges)
+ * bytes in either direction.  Output, selectivity, the accepted forms and the promise to leave no trace in the context
+ * are those of ansx_decode_ranges_dev; no kernel's grid grows with the container's block count (grids scale with
+ * nranges or with the number of touched blocks).
+ * d_offsets (optional, 8-byte aligned device array of nranges + 1 u64): the exclusive prefix sum of count -- where
+ * range i starts in d_out -- and the total; written on ANSX_OK and ANSX_ERR_CAPACITY, unspecified after other errors.
+ * *total_ints (optional, host): sum(count), set on ANSX_OK and ANSX_ERR_CAPACITY (the size of a retry).
+ * Errors decided on the host, before anything is launched: ANSX_ERR_ARG for a null ctx / d_in / d_out, a null d_first
+ * or d_count with nranges > 0, a misaligned pointer (d_in 16, d_out 4, d_first 8, d_count 4, d_offsets 8 bytes), or
+ * nranges > UINT32_MAX; ANSX_ERR_FORMAT as for ansx_decode_ranges_dev (kind / fidelity differ from the header, not a
+ * container).  nranges == 0: ANSX_OK, *total_ints = 0, nothing launched.
+ * Errors decided on the device, read back before any byte of d_out is written: ANSX_ERR_ARG if any
+ * first[i] + count[i] > n, ANSX_ERR_CAPACITY if sum(count) > out_capacity_ints (ANSX_ERR_ARG wins when both hold);
+ * ANSX_ERR_FORMAT for an invalid index entry of a touched block.  Returns after the status has been read back. */
+int ansx_decode_device_ranges_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in, size_t in_bytes,
+    const uint64_t* d_first, const uint32_t* d_count, size_t nranges, uint32_t* d_out, size_t out_capacity_ints,
+    uint64_t* d_offsets, uint64_t* total_ints, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
