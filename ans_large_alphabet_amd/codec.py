@@ -176,6 +176,36 @@ class _Codec:
             raise err
         return int(total.value)
 
+    def decode_batch_dev(self, in_ptrs, in_bytes, out_ptr, out_capacity, stream=None):
+        """A batch of containers in one call: in_ptrs / in_bytes (sequences or numpy arrays of ints) are the device
+        addresses (16-byte aligned) and sizes of the containers; container i decodes to ints [offsets[i],
+        offsets[i + 1]) of out_ptr (out_capacity ints).  Returns offsets, np.uint64 of len(in_ptrs) + 1 (the last is the
+        total).  out_ptr=None with out_capacity=0 is a size query: it decodes nothing and returns the offsets.
+        ERR_CAPACITY raises AnsxError with .needed = the total (and .offsets); a host-side ERR_FORMAT carries .index,
+        the first container that failed its checks, one found on the device .index = None."""
+        ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
+        if ptrs.size != sizes.size:
+            raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
+        count = ptrs.size
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        bad = C.c_size_t(count)
+        st = L.lib().ansx_decode_batch_dev(self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if count else None,
+                                           sizes.ctypes.data if count else None, count, out_ptr, int(out_capacity),
+                                           offsets.ctypes.data, C.byref(total), C.byref(bad), stream)
+        if st == L.ERR_CAPACITY and out_ptr is None and int(out_capacity) == 0:
+            return offsets
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".decode_batch_dev")
+            if st == L.ERR_CAPACITY:
+                err.needed = int(total.value)
+                err.offsets = offsets
+            if st == L.ERR_FORMAT:
+                err.index = int(bad.value) if bad.value < count else None
+            raise err
+        return offsets
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

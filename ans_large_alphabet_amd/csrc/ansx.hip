@@ -28,6 +28,7 @@
 #include "ansx_pa.h"
 #include "ansx_intsparse.h"
 #include "ansx_ranges.h"
+#include "ansx_batch.h"
 
 namespace {
 
@@ -61,6 +62,7 @@ struct ansx_ctx {
         stage_in, stage_out, dec_s2s, dec_cum, dec_info, plain, rf_tmp, log2lut, pa_alpha, pa_info, pairs, lg2i, sizes, nearlist, force;
     DevBuf rng_plan, rng_cont, rng_list;  // ansx_decode_ranges_dev: flags + block list + range pieces, sub-container, its ints
     DevBuf rng_dev;                       // ansx_decode_device_ranges_dev: the device planner's workspace
+    DevBuf bat_hdr;                       // ansx_decode_batch_dev: input addresses and headers of the batch
     u8* rng_pin = nullptr;                // ... and the pinned host image of rng_plan (an asynchronous upload from
     size_t rng_pin_cap = 0;               //     pageable memory is staged by the runtime: 0.666 -> 0.618 ms at 4096 ranges)
     u32* h_pin = nullptr;  // pinned: [0..3] gflags, [4..7] result (2 x u64), [8..] header scratch
@@ -128,6 +130,7 @@ struct ansx_ctx {
         bool near_flip = false;       // ANSX_TEST_NEAR_FLIP: the device decides close calls the wrong way (tests: the host must fix them)
         u32 cand_chains = 0;          // ANSX_CAND_CHAINS: 1 | 2 recurrences per lane in k_candidates (0 = by the call's size)
         double fast_guard = ANSX_FAST_GUARD;  // ANSX_FAST_GUARD: relative guard band of the fast model path's stop rule (tests widen it)
+        u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
     } dbg;
 };
 
@@ -206,6 +209,10 @@ struct Plan {
     bool plain;
     Layout lay;
     u32 NSP;
+    // decode of a batch pass (ansx_batch.h): the per-block table decode_dev puts into g after the header's checks
+    // (make_plan has no part in it), and the ints of the output it lays out
+    const ansx_blk_out* bout = nullptr;
+    u64 bout_ints = 0;
 };
 
 Layout layout_of(const ansx_geo& g, bool plain)
@@ -278,6 +285,7 @@ int make_plan(int kind, int f, size_t n, const ansx_opts* opts, Plan* P)
     g.payload_bytes = 0;  // (set by decode_dev from the container header)
     g.trusted_index = 0;  // (set by decode_dev on the single-stream path only, where the host writes the two entries)
     g.pad_ = 0;
+    g.bout = nullptr;     // (set by decode_dev on a batch pass only)
     g.map = kind == ANSX_MSB ? map_msb() : (kind == ANSX_INT ? map_int() : map_fold((u32)f));
     P->g = g;
     // symbol-array stride: the reference's MAX_SIGMA (ans_fold.hpp:70; ans_msb.hpp:28 has 1280)
@@ -1632,6 +1640,7 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
         payload_off = H.payload_offset;
         in_bytes_payload = H.payload_bytes;
         P.g.payload_bytes = H.payload_bytes;  // every parser validates the two index entries of its own block (index_entry_ok)
+        P.g.bout = Pin.bout;                  // (container_plan -> make_plan has reset it)
         // The ring decoder needs nothing else from the index: no validation kernel, no read-back.  The staged /
         // straight-from-HBM forms size their LDS from the largest block stream, which only the index knows.
         const size_t rs_probe = rup((size_t)(maxM >= 32 ? maxM / 32 : 1) * 8, 16) + 2 * rup((size_t)max_ep * 4, 16) + ANSX_DEC_SCRATCH;
@@ -1656,8 +1665,10 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
     }
     const u32* hints = P.plain ? nullptr : (const u32*)(d_in + P.lay.hint_off);
     const uint4* pa_info = nullptr;
+    // alpha scratch: laid out like the output (geo_block_out)
+    const size_t alpha_bytes = 4 * (P.g.bout ? (size_t)Pin.bout_ints : (size_t)P.g.nblocks * P.g.block_ints);
     if (P.g.pa) {  // alphabet headers first: they tell where every block's codec stream starts
-        if ((rc = ensure(c, c->pa_alpha, (size_t)P.g.nblocks * P.g.block_ints * 4))) return rc;
+        if ((rc = ensure(c, c->pa_alpha, alpha_bytes))) return rc;
         if ((rc = ensure(c, c->pa_info, (size_t)P.g.nblocks * 16))) return rc;
         LAUNCH(c, "k_pa_parse", k_pa_parse, (P.g.nblocks + 63) / 64, 64, 0, s, cont, P.g, boff, payload_off,
             (u32*)c->pa_alpha.p, (uint4*)c->pa_info.p, gflags);
@@ -1667,7 +1678,7 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
     if (int_sparse) {
         // plain ANSint: the prelude ranges over the VALUES (any max_sym); its present symbols become the block's ranks
         // (ansx_intsparse.h) -- whichever model the encoder ran, the stream is the reference's
-        if ((rc = ensure(c, c->pa_alpha, (size_t)P.g.nblocks * P.g.block_ints * 4))) return rc;
+        if ((rc = ensure(c, c->pa_alpha, alpha_bytes))) return rc;
         if ((rc = ensure(c, c->pa_info, (size_t)P.g.nblocks * 16))) return rc;
         if ((rc = ensure(c, c->dec_cum, (size_t)P.g.nblocks * (P.NSP + 8) * 4))) return rc;
         if ((rc = ensure(c, c->dec_info, (size_t)P.g.nblocks * 16))) return rc;
@@ -1715,6 +1726,19 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
 // ansx_decode_ranges_dev / ansx_decode_device_ranges_dev: a plan (host- or device-built) ->
 // k_range_index + k_range_copy build a container of the touched blocks only -> decode_dev on it (no cached header in
 // or out) -> k_range_gather into the caller's buffer.
+
+// rng_pin holds at least `bytes` (its content is not kept)
+int ensure_pin(ansx_ctx* c, size_t bytes)
+{
+    if (bytes <= c->rng_pin_cap) return ANSX_OK;
+    if (c->rng_pin) HIPCHK(c, hipHostFree(c->rng_pin));
+    c->rng_pin = nullptr;
+    c->rng_pin_cap = 0;
+    const size_t want = bytes + (bytes >> 3) + 4096;
+    HIPCHK(c, hipHostMalloc((void**)&c->rng_pin, want, hipHostMallocDefault));
+    c->rng_pin_cap = want;
+    return ANSX_OK;
+}
 
 // The source container's header, checked as decode_dev checks it, and its plan
 int range_source(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, hipStream_t s, ansx_container_header* H,
@@ -1840,14 +1864,7 @@ int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes,
     const u32 nr = (u32)pieces.size();
     const size_t o_tb = 16, o_pc = rup(o_tb + 4 * T, 16), o_ps = rup(o_pc + sizeof(ansx_range_piece) * nr, 16);
     const size_t plan_bytes = o_ps + 4 * ((size_t)nr + 1);
-    if (plan_bytes > c->rng_pin_cap) {
-        if (c->rng_pin) HIPCHK(c, hipHostFree(c->rng_pin));
-        c->rng_pin = nullptr;
-        c->rng_pin_cap = 0;
-        const size_t want = plan_bytes + (plan_bytes >> 3) + 4096;
-        HIPCHK(c, hipHostMalloc((void**)&c->rng_pin, want, hipHostMallocDefault));
-        c->rng_pin_cap = want;
-    }
+    if ((rc = ensure_pin(c, plan_bytes))) return rc;
     {
         u8* hb = c->rng_pin;  // (no copy out of it is pending: every call ends in a synchronisation)
         memset(hb, 0, o_tb);
@@ -1939,6 +1956,184 @@ int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in
         (u32*)&sc[ANSX_DR_FLAGS], d_out, s);
 }
 
+// --------------------------------------------------------------------------------- batches of containers
+// ansx_decode_batch_dev: every header in one round trip -> the host's checks, offsets and
+// capacity -> per geometry, passes of at most P blocks: k_batch_index + k_batch_copy build a sub-container of the
+// pass's blocks -> decode_dev on it with the per-block table (no cached header in or out) -> k_range_gather into the
+// caller's buffer.
+#define ANSX_BATCH_PASS_DEFAULT 16384u  // blocks per pass: the block count of the headline container
+
+struct BatchSrc {  // a container of the batch, checked
+    ansx_container_header H;
+    Layout lay;
+    u64 base;
+    u32 nblocks;
+};
+
+// One pass over containers ids[*ci..] of one geometry, from block *b0 of the first, up to PB blocks; moves *ci / *b0
+// past them.  Every buffer it uses is bounded by the pass: its blocks, their ints and their bytes.
+int batch_pass(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& src, const std::vector<u64>& off,
+    const std::vector<u32>& ids, size_t* ci, u32* b0, u32 PB, u32* d_out, hipStream_t s)
+{
+    int rc;
+    const ansx_container_header& H0 = src[ids[*ci]].H;
+    const u64 bi = H0.block_ints;
+    const u64 bbound = block_bound(kind, (u32)f, (size_t)bi, (H0.kind & 0x100u) != 0);
+    std::vector<ansx_batch_src> S;
+    std::vector<ansx_batch_blk> B;
+    std::vector<ansx_blk_out> O;  // the decoders' table: every container's blocks back to back, from a multiple of 4 ints
+    std::vector<ansx_range_piece> R;
+    std::vector<u32> pstart;
+    u64 wl = 0, cap_pay = 0, npieces = 0;  // work-list ints, sub-container payload bound, gather pieces
+    ansx_container_header Hs = H0;
+    Hs.max_nsyms = 0, Hs.max_log2_frame = 0, Hs.max_present_m1 = 0;  // (the maxima over the pass's sources)
+    while (*ci < ids.size() && B.size() < PB) {
+        const u32 i = ids[*ci];
+        const BatchSrc& cs = src[i];
+        const u32 take = (u32)std::min<u64>(cs.nblocks - *b0, PB - B.size());
+        const u32 si = (u32)S.size();
+        S.push_back({ cs.base, cs.lay.ckoff_off, cs.lay.ckstate_off, cs.lay.hint_off, cs.lay.payload_off,
+            cs.H.payload_bytes, cs.nblocks, 0 });
+        u64 ints = 0;
+        for (u32 k = 0; k < take; k++) {
+            const u64 b = (u64)*b0 + k;
+            const u32 nbk = (u32)std::min<u64>(bi, cs.H.n - b * bi);
+            B.push_back({ si, (u32)b });
+            O.push_back({ wl + k * bi, nbk, 0 });
+            ints += nbk;
+        }
+        R.push_back({ wl, off[i] + (u64)*b0 * bi, ints });
+        pstart.push_back((u32)npieces);
+        npieces += (ints + ANSX_RANGE_CHUNK - 1) / ANSX_RANGE_CHUNK;
+        wl += rup(ints, 4);
+        cap_pay += std::min<u64>(cs.H.payload_bytes, (u64)take * bbound);
+        Hs.max_nsyms = std::max(Hs.max_nsyms, cs.H.max_nsyms);
+        Hs.max_log2_frame = std::max(Hs.max_log2_frame, cs.H.max_log2_frame);
+        Hs.max_present_m1 = std::max(Hs.max_present_m1, cs.H.max_present_m1);
+        *b0 += take;
+        if (*b0 == cs.nblocks) (*ci)++, *b0 = 0;
+    }
+    if (npieces > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    pstart.push_back((u32)npieces);
+    const u32 T = (u32)B.size(), nr = (u32)R.size();
+
+    // the sub-container's plan: any n that makes make_plan lay out exactly T blocks (the table says how long each is)
+    const u64 n_sub = (u64)(T - 1) * bi + O.back().n;
+    const ansx_opts o = container_opts(H0);
+    Plan Ps;
+    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
+    set_restart_format(&Ps, (H0.kind & ANSX_KIND_WIDE_RESTART) != 0);
+    if (Ps.g.nblocks != T) return ANSX_ERR_FORMAT;
+    Hs.n = n_sub;
+    Hs.nblocks = T;
+    Hs.payload_bytes = 0;  // (k_batch_index writes the sum of the blocks' stream lengths)
+    Hs.payload_offset = Ps.lay.payload_off;
+
+    // the pass's plan, one upload: flags[4] | sources | blocks | table | gather pieces | first piece per source
+    const size_t o_s = 16, o_b = rup(o_s + sizeof(ansx_batch_src) * nr, 16), o_o = rup(o_b + sizeof(ansx_batch_blk) * T, 16);
+    const size_t o_r = rup(o_o + sizeof(ansx_blk_out) * T, 16), o_p = rup(o_r + sizeof(ansx_range_piece) * nr, 16);
+    const size_t plan_bytes = o_p + 4 * ((size_t)nr + 1);
+    if ((rc = ensure_pin(c, plan_bytes))) return rc;
+    u8* hb = c->rng_pin;  // (no copy out of it is pending: the previous pass ended in a synchronisation)
+    memset(hb, 0, o_s);
+    memcpy(hb + o_s, S.data(), sizeof(ansx_batch_src) * nr);
+    memcpy(hb + o_b, B.data(), sizeof(ansx_batch_blk) * T);
+    memcpy(hb + o_o, O.data(), sizeof(ansx_blk_out) * T);
+    memcpy(hb + o_r, R.data(), sizeof(ansx_range_piece) * nr);
+    memcpy(hb + o_p, pstart.data(), 4 * ((size_t)nr + 1));
+    if ((rc = ensure(c, c->rng_plan, plan_bytes))) return rc;
+    u8* dplan = (u8*)c->rng_plan.p;
+    HIPCHK(c, hipMemcpyAsync(dplan, hb, plan_bytes, hipMemcpyHostToDevice, s));
+    u32* dflags = (u32*)dplan;
+    const ansx_batch_src* dS = (const ansx_batch_src*)(dplan + o_s);
+    const ansx_batch_blk* dB = (const ansx_batch_blk*)(dplan + o_b);
+    const ansx_range_piece* dR = (const ansx_range_piece*)(dplan + o_r);
+    const u32* dP = (const u32*)(dplan + o_p);
+
+    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
+    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
+    if ((rc = ensure(c, c->rng_list, 4 * wl + 64))) return rc;
+    u8* sub = (u8*)c->rng_cont.p;
+    u32* list = (u32*)c->rng_list.p;
+    const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
+    LAUNCH(c, "k_batch_index", k_batch_index, 1, 1024, 0, s, dS, dB, Ps.g, T, Hs, sub, cap_pay, dflags);
+    LAUNCH(c, "k_batch_copy", k_batch_copy, T, 256, 0, s, dS, dB, Ps.g, dl, sub, cap_pay, dflags);
+    // as in range_tail: the gather and the read-back of this pass's own flags ride on the decode's final read-back
+    u32* hflag = c->h_pin + 512;
+    *hflag = 0;
+    const std::function<int(const u32*)> gather = [&](const u32* gflags) -> int {
+        const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
+        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, dR, dP, nr, (u32)npieces, d_out, gflags);
+        HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
+        return ANSX_OK;
+    };
+    Ps.bout = (const ansx_blk_out*)(dplan + o_o);
+    Ps.bout_ints = wl;
+    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, false, false, &gather);
+    if (*hflag) return ANSX_ERR_FORMAT;  // an index entry of a pass block was invalid
+    return rc;
+}
+
+int decode_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
+    u32* d_out, size_t cap, u64* offsets, u64* total_ints, size_t* bad_index, hipStream_t s)
+{
+    int rc;
+    // every header in one round trip: the input addresses up (0 for an input too short to hold one), the headers back
+    const size_t o_h = rup(8 * count, 16), bytes = o_h + 64 * count;
+    if ((rc = ensure_pin(c, bytes))) return rc;
+    if ((rc = ensure(c, c->bat_hdr, bytes))) return rc;
+    u64* hp = (u64*)c->rng_pin;
+    for (size_t i = 0; i < count; i++) hp[i] = in_bytes[i] >= sizeof(ansx_container_header) ? (u64)(uintptr_t)d_ins[i] : 0;
+    u8* dw = (u8*)c->bat_hdr.p;
+    HIPCHK(c, hipMemcpyAsync(dw, hp, 8 * count, hipMemcpyHostToDevice, s));
+    LAUNCH(c, "k_batch_headers", k_batch_headers, (u32)((4 * (u64)count + 255) / 256), 256, 0, s, (const u64*)dw,
+        (u64)count, (uint4*)(dw + o_h));
+    HIPCHK(c, hipMemcpyAsync(c->rng_pin + o_h, dw + o_h, 64 * count, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+
+    // decode_dev's checks on every header, in batch order; the offsets and the total
+    std::vector<BatchSrc> src(count);
+    std::vector<u64> off(count + 1);
+    u64 total = 0;
+    for (size_t i = 0; i < count; i++) {
+        BatchSrc& b = src[i];
+        Plan P;
+        if (in_bytes[i] < sizeof(ansx_container_header) || parse_header(c->rng_pin + o_h + 64 * i, in_bytes[i], &b.H)
+            || container_plan(b.H, (u32)kind, (u32)f, in_bytes[i], &P)) {  // (a single-stream stream has no magic)
+            if (bad_index) *bad_index = i;
+            return ANSX_ERR_FORMAT;
+        }
+        b.lay = P.lay;
+        b.base = (u64)(uintptr_t)d_ins[i];
+        b.nblocks = P.g.nblocks;
+        off[i] = total;
+        total = b.H.n > ~0ull - total ? ~0ull : total + b.H.n;  // (saturated: no buffer holds that many)
+    }
+    off[count] = total;
+    if (offsets) memcpy(offsets, off.data(), 8 * (count + 1));
+    if (total_ints) *total_ints = total;
+    if (total > cap) return ANSX_ERR_CAPACITY;
+
+    // groups of one geometry (block_ints, restart interval, compaction, restart-point format), batch order inside each
+    std::map<std::array<u32, 4>, std::vector<u32>> groups;
+    for (size_t i = 0; i < count; i++) {
+        const ansx_container_header& H = src[i].H;
+        groups[{ H.block_ints, H.ckpt_interval, (H.kind >> 8) & 1u, (H.kind >> 9) & 1u }].push_back((u32)i);
+    }
+    const u32 PB = c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT;
+    for (const auto& gr : groups) {
+        size_t ci = 0;
+        u32 b0 = 0;
+        while (ci < gr.second.size()) {
+            if ((rc = batch_pass(c, kind, f, src, off, gr.second, &ci, &b0, PB, d_out, s))) {
+                if (rc == ANSX_ERR_FORMAT && bad_index) *bad_index = count;  // (found on the device: which one is not known)
+                return rc;
+            }
+        }
+    }
+    return ANSX_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -2001,7 +2196,8 @@ int ansx_init(int device, ansx_ctx** out)
         return ANSX_ERR_HIP;
     }
     static const char* const names[] = { "ANSX_TEST_TABLE16_FIXUP", "ANSX_ENCODE_GTAB16", "ANSX_PARSE_GENERIC", "ANSX_PARSE_WIN", "ANSX_PARSE_FAST",
-        "ANSX_DECODE_TABLE", "ANSX_NO_STREAM_LDS", "ANSX_DECODE_MODE", "ANSX_PARSE_STAGE_WORDS", "ANSX_MODEL_FUSED", "ANSX_MODEL_SYNC", "ANSX_NS_HINT", "ANSX_T_HINT", "ANSX_NO_FAST_MODEL", "ANSX_FAST_GUARD", "ANSX_CAND_CHAINS", "ANSX_NEAR_BAND", "ANSX_TEST_NEAR_FLIP", "ANSX_WIDE_RESTART", "ANSX_TEST_WIDE_AT" };
+        "ANSX_DECODE_TABLE", "ANSX_NO_STREAM_LDS", "ANSX_DECODE_MODE", "ANSX_PARSE_STAGE_WORDS", "ANSX_MODEL_FUSED", "ANSX_MODEL_SYNC", "ANSX_NS_HINT", "ANSX_T_HINT", "ANSX_NO_FAST_MODEL", "ANSX_FAST_GUARD", "ANSX_CAND_CHAINS", "ANSX_NEAR_BAND", "ANSX_TEST_NEAR_FLIP", "ANSX_WIDE_RESTART", "ANSX_TEST_WIDE_AT",
+        "ANSX_BATCH_PASS_BLOCKS" };
     for (const char* nm : names)
         if (const char* v = getenv(nm)) (void)ansx_debug_set(c, nm, v);
     *out = c;
@@ -2104,6 +2300,7 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
     }
     else if (!strcmp(name, "ANSX_NEAR_BAND")) c->dbg.near_band = (value && value[0]) ? strtod(value, nullptr) : ANSX_NEAR_BAND;
     else if (!strcmp(name, "ANSX_TEST_NEAR_FLIP")) c->dbg.near_flip = on;
+    else if (!strcmp(name, "ANSX_BATCH_PASS_BLOCKS")) c->dbg.batch_pass_blocks = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_CAND_CHAINS")) {
         const u32 v = value ? (u32)strtoul(value, nullptr, 10) : 0u;
         if (v > 2) return ANSX_ERR_ARG;
@@ -2121,7 +2318,7 @@ void ansx_destroy(ansx_ctx* c)
     DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->log2lut, &c->pa_alpha, &c->pa_info, &c->pairs, &c->lg2i, &c->sizes, &c->nearlist, &c->force, &c->geo_big,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr };
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& kv : c->geo)
@@ -2227,6 +2424,26 @@ int ansx_decode_device_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* d
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     return decode_device_ranges(c, kind, f, d_in, in_bytes, (const u64*)d_first, d_count, nranges, d_out,
         out_capacity_ints, (u64*)d_offsets, (u64*)total_ints, s);
+}
+
+int ansx_decode_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count,
+    uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_index, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || count > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (count > 0 && (!d_ins || !in_bytes)) return ANSX_ERR_ARG;
+    if ((!d_out && out_capacity_ints > 0) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    for (size_t i = 0; i < count; i++)
+        if (!d_ins[i] || ((uintptr_t)d_ins[i] & 15u)) return ANSX_ERR_ARG;
+    if (count == 0) {
+        if (offsets) offsets[0] = 0;
+        if (total_ints) *total_ints = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return decode_batch(c, kind, f, d_ins, in_bytes, count, d_out, out_capacity_ints, (u64*)offsets, (u64*)total_ints,
+        bad_index, s);
 }
 
 int ansx_encode(ansx_ctx* c, int kind, int f, const uint32_t* in, size_t n, uint8_t* out, size_t cap,
@@ -2507,7 +2724,7 @@ size_t ansx_workspace_bytes(const ansx_ctx* c)
     const DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->pa_alpha, &c->pa_info, &c->pairs, &c->sizes,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr };
     size_t t = 0;
     for (const DevBuf* b : bufs) t += b->cap;
     return t;

@@ -317,6 +317,16 @@ struct ansx_geo {
                         // plain reference stream has no index); 0 = they come from the container and every parser checks
                         // the pair of its own block (index_entry_ok).  Never derived from a container field.
     u32 pad_;
+    const struct ansx_blk_out* bout;  // decode: per-block lengths and output offsets (a pass of ansx_decode_batch_dev,
+                                      // ansx_batch.h); null everywhere else: block b then has geo_block_n ints at b * block_ints
+};
+
+// One block of a batch pass: its ints and where they start in the pass's output.  Blocks of many containers share one
+// sub-container there, so any of them may be short and the output of block b does not start at b * block_ints.
+struct ansx_blk_out {
+    u64 off;  // first int in the output (a multiple of 4: the decoders' 16-byte stores)
+    u32 n;    // ints
+    u32 pad_;
 };
 
 // Restart points in the container index.  A state is below 2^36 M and a cursor below the block's
@@ -356,10 +366,13 @@ ANSX_HD bool index_entry_ok(const ansx_geo& g, u32 b, u64 a, u64 e)
 
 ANSX_HD u32 geo_block_n(const ansx_geo& g, u32 b)
 {
+    if (g.bout) return g.bout[b].n;
     u64 start = (u64)b * g.block_ints;
     u64 rem = g.n - start;
     return (u32)(rem < g.block_ints ? rem : g.block_ints);
 }
+// first output int of block b (decode side)
+ANSX_HD u64 geo_block_out(const ansx_geo& g, u32 b) { return g.bout ? g.bout[b].off : (u64)b * g.block_ints; }
 // decoder segments of a block with nb ints
 ANSX_HD u32 geo_nseg(u32 nb, u32 ckpt)
 {

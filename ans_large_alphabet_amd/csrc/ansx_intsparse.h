@@ -211,11 +211,14 @@ __global__ __launch_bounds__(64) void k_int_sparse_parse(const u8* __restrict__ 
     u32 sigma = 0;
     if (!err) {
         const u32 M = 1u << logM;
-        const u32 cap = g.block_ints < ANSX_SP_MAX_SIGMA ? g.block_ints : ANSX_SP_MAX_SIGMA;  // a block has at most block_ints distinct values
+        // a block has at most block_ints distinct values; a block of a batch pass at most its own ints (its alpha
+        // scratch is no longer than that)
+        const u32 bmax = g.bout ? geo_block_n(g, b) : g.block_ints;
+        const u32 cap = bmax < ANSX_SP_MAX_SIGMA ? bmax : ANSX_SP_MAX_SIGMA;
         const u8* bp = H.stream + H.pos;
         const u32 avail = H.sbytes - H.pos;
         u32* cum = g_cum + (u64)b * (NSP + 8);
-        u32* al = alpha + (u64)b * g.block_ints;
+        u32* al = alpha + geo_block_out(g, b);
         u64 w0 = ld_u64_unaligned(bp), w1 = ld_u64_unaligned(bp + 8);  // (a stream has at least 38 bytes: parse_header)
         u32 consumed = 0, next_byte = 16, total_bits = 0;
         const u32 maxbits = avail * 8;
@@ -314,8 +317,8 @@ __global__ __launch_bounds__(256) void k_int_unmap(ansx_geo g, const u32* __rest
     const uint4 pi = sp_info[b];
     if (pi.z) return;
     const u32 nb = geo_block_n(g, b);
-    const u32* al = alpha + (u64)b * g.block_ints;
-    u32* o = out + (u64)b * g.block_ints;
+    const u32* al = alpha + geo_block_out(g, b);
+    u32* o = out + geo_block_out(g, b);
     const u32 sigma = pi.x;
     u32 bad = 0;
     for (u32 i0 = threadIdx.x; i0 < nb; i0 += 256 * 8) {

@@ -4099,7 +4099,7 @@ __global__ void k_decode_rank(const u8* __restrict__ cont, ansx_geo g, u32 NSP,
     dec_lut_rank lut;
     lut.bwp = bwp;
     lut.ep = ep;
-    u32* o = outp + (u64)b * g.block_ints;
+    u32* o = outp + geo_block_out(g, b);
     if (use_ring) {
         // rings start at the next 16-byte boundary of the LDS address space (the host adds the slack)
         const u32 labs = (u32)(size_t)(__attribute__((address_space(3))) void*)lds_stream;
@@ -4367,8 +4367,8 @@ __global__ __launch_bounds__(256) void k_decode_rank2(const u8* __restrict__ con
         __syncthreads();
         okB = dec_build_rank_tables<RFOLD, 4, 2>(g, bw, epB, sh_scan, &sh_bad, gcB, curB, prvB, biB.x, MB, WB, max_ns, biB.z, streamB, tid, nt, gflags);
     }
-    u32* oA = outp + (u64)bA * g.block_ints;
-    u32* oB = outp + (u64)bBs * g.block_ints;
+    u32* oA = outp + geo_block_out(g, bA);
+    u32* oB = outp + geo_block_out(g, bBs);
     dec_lut_rank2<0> lutA;
     dec_lut_rank2<8> lutB;
     if (okA && ringA && okB && ringB) {
@@ -4554,7 +4554,7 @@ __global__ void k_decode(const u8* __restrict__ cont, ansx_geo g, u32 NSP,
     lut.f = f;
     lut.T = T;
     lut.mf = (RFOLD && rflag) ? mfl : nullptr;
-    u32* o = outp + (u64)b * g.block_ints;
+    u32* o = outp + geo_block_out(g, b);
     if (st_lds)
         dec_segments<true>(g, b, nb, sbytes, tid, nt, logM, lut, stream, lds_stream, ckpt_state, ckpt_off, o);
     else

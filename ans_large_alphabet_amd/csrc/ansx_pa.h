@@ -288,7 +288,7 @@ __global__ __launch_bounds__(64) void k_pa_parse(const u8* __restrict__ cont, an
     const u32 sbytes = (u32)(block_off[b + 1] - boff);
     const u32 nb = geo_block_n(g, b);
     u32 err = 0, sigma = 0, hb = 0;
-    u32* out = alpha + (u64)b * g.block_ints;
+    u32* out = alpha + geo_block_out(g, b);
     if (sbytes < 8) err = 1;
     if (!err) {
         sigma = ld_u32_unaligned(stream);
@@ -410,8 +410,8 @@ __global__ __launch_bounds__(256) void k_pa_unmap(ansx_geo g, const u32* __restr
     const uint4 pi = pa_info[b];
     if (pi.z) return;
     const u32 nb = geo_block_n(g, b);
-    const u32* al = alpha + (u64)b * g.block_ints;
-    u32* o = out + (u64)b * g.block_ints;
+    const u32* al = alpha + geo_block_out(g, b);
+    u32* o = out + geo_block_out(g, b);
     const u32 sigma = pi.x;
     u32 bad = 0;
     if (sigma == 1) {

@@ -33,26 +33,26 @@ __device__ __forceinline__ u64 range_block_len(const ansx_geo& g, const u64* __r
 
 // One workgroup: exclusive scan of the touched blocks' stream lengths into the sub-container's index (the pattern of
 // k_scan_sizes: every wave owns a contiguous range of entries, its lanes on consecutive ones), then the header --
-// the host's image with the payload size filled in.
-__global__ __launch_bounds__(1024) void k_range_index(const u8* __restrict__ src, ansx_geo g,
-    const u32* __restrict__ tb, u32 T, ansx_container_header hsub, u8* __restrict__ dst, u64 cap_pay,
-    u32* __restrict__ flags)
+// the host's image with the payload size filled in.  len(i): the stream length of the sub-container's block i, 0 for an
+// invalid one (flagged by len itself).
+template <class Len>
+__device__ __forceinline__ void range_index_body(u32 T, Len len, const ansx_container_header& hsub, u8* __restrict__ dst,
+    u64 cap_pay, u32* __restrict__ flags)
 {
     __shared__ u64 part[20];
     const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u64* boff = (const u64*)(src + 64);
     u64* sboff = (u64*)(dst + 64);
     const u32 per = ((T + 15) / 16 + 63) & ~63u;  // entries per wave, a multiple of 64
     const u32 lo = wave * per < T ? wave * per : T, hi = (lo + per) < T ? (lo + per) : T;
     u64 sum = 0;
-    for (u32 i = lo + lane; i < hi; i += 64) sum += range_block_len(g, boff, tb[i], flags);
+    for (u32 i = lo + lane; i < hi; i += 64) sum += len(i);
     sum = wave_sum(sum);
     u64 total;
     u64 run = block_excl_scan<u64>(lane == 63 ? sum : 0ull, part, tid, 1024, &total);
     run = wave_last(run);
     for (u32 i0 = lo; i0 < hi; i0 += 64) {
         const u32 i = i0 + lane;
-        const u64 v = i < hi ? range_block_len(g, boff, tb[i], flags) : 0ull;
+        const u64 v = i < hi ? len(i) : 0ull;
         const u64 incl = wave_incl_scan(v);
         if (i < hi) sboff[i] = run + incl - v;
         run += wave_last(incl);
@@ -68,6 +68,14 @@ __global__ __launch_bounds__(1024) void k_range_index(const u8* __restrict__ src
         if (tid == 13) v = (u32)(total >> 32);
         ((u32*)dst)[tid] = v;
     }
+}
+
+__global__ __launch_bounds__(1024) void k_range_index(const u8* __restrict__ src, ansx_geo g,
+    const u32* __restrict__ tb, u32 T, ansx_container_header hsub, u8* __restrict__ dst, u64 cap_pay,
+    u32* __restrict__ flags)
+{
+    const u64* boff = (const u64*)(src + 64);
+    range_index_body(T, [&](u32 i) { return range_block_len(g, boff, tb[i], flags); }, hsub, dst, cap_pay, flags);
 }
 
 // dst[0..n) = src[0..n): 16-byte stores on dst's aligned body, fed by 16-byte loads where src is aligned alike and by
@@ -112,11 +120,10 @@ __device__ __forceinline__ void range_copy_bytes(u8* __restrict__ dst, const u8*
 
 // One workgroup per touched block (k-th of the sorted list, block b of the source): its restart points, parse hints
 // and stream to their places in the sub-container.  Runs after k_range_index, whose index it reads.
-__global__ __launch_bounds__(256) void k_range_copy(const u8* __restrict__ src, ansx_geo g, ansx_range_lay sl,
-    ansx_range_lay dl, const u32* __restrict__ tb, u8* __restrict__ dst, u64 cap_pay, u32* __restrict__ flags)
+__device__ __forceinline__ void range_copy_block(const u8* __restrict__ src, const ansx_geo& g, const ansx_range_lay& sl,
+    const ansx_range_lay& dl, u32 k, u32 b, u8* __restrict__ dst, u64 cap_pay, u32* __restrict__ flags)
 {
-    const u32 k = blockIdx.x, tid = threadIdx.x;
-    const u32 b = tb[k];
+    const u32 tid = threadIdx.x;
     const u64* sboff = (const u64*)(dst + 64);
     const u64 d0 = sboff[k], d1 = sboff[k + 1];
     if (d1 <= d0 || d1 > cap_pay) {  // an invalid entry (flagged by k_range_index) or a sum past the workspace
@@ -133,6 +140,12 @@ __global__ __launch_bounds__(256) void k_range_copy(const u8* __restrict__ src, 
     if (tid < 8) ((u32*)(dst + dl.hint_off + 32ull * k))[tid] = ((const u32*)(src + sl.hint_off + 32ull * b))[tid];
     const u64* boff = (const u64*)(src + 64);
     range_copy_bytes(dst + dl.payload_off + d0, src + sl.payload_off + boff[b], d1 - d0, tid, 256);
+}
+
+__global__ __launch_bounds__(256) void k_range_copy(const u8* __restrict__ src, ansx_geo g, ansx_range_lay sl,
+    ansx_range_lay dl, const u32* __restrict__ tb, u8* __restrict__ dst, u64 cap_pay, u32* __restrict__ flags)
+{
+    range_copy_block(src, g, sl, dl, blockIdx.x, tb[blockIdx.x], dst, cap_pay, flags);
 }
 
 // out[p.dst + i] = sub[p.src + i] for every range piece, nothing if the decode flagged an error: workgroup w takes ints

@@ -202,6 +202,33 @@ int ansx_decode_device_ranges_dev(ansx_ctx* ctx, int kind, int fidelity, const u
     const uint64_t* d_first, const uint32_t* d_count, size_t nranges, uint32_t* d_out, size_t out_capacity_ints,
     uint64_t* d_offsets, uint64_t* total_ints, void* stream);
 
+/* A batch of containers in one call (posting lists, column chunks: one container per term or chunk).  d_ins[i]
+ * (16-byte aligned DEVICE pointers, HOST array) are `count` containers of the codec (kind, fidelity), in_bytes[i]
+ * bounding each; container i decodes to d_out[offsets[i] .. offsets[i] + n_i), n_i from its own header, in batch order
+ * and back to back -- bit-identical to ansx_decode_dev on each in turn, outputs concatenated.  Every container form
+ * ansx_decode_dev reads is accepted, and the containers may differ in geometry (block_ints, ckpt_interval, compaction,
+ * restart-point format); the same pointer may appear more than once, in any order.  d_out: 4-byte aligned.
+ * offsets (optional, HOST array of count + 1): the exclusive prefix sums of the n_i, and the total; *total_ints
+ * (optional): sum(n_i).  Both are written on ANSX_OK and ANSX_ERR_CAPACITY, so d_out = NULL, out_capacity_ints = 0
+ * is a size query.
+ * Errors decided before the context is touched: ANSX_ERR_ARG for a null ctx, a null d_ins or in_bytes with count > 0,
+ * a null d_ins[i], a misaligned pointer, d_out == NULL with out_capacity_ints > 0, or count > UINT32_MAX.
+ * count == 0: ANSX_OK, total 0, nothing launched.
+ * Errors decided on the host, before any byte of d_out is written (all headers come back in one round trip):
+ * ANSX_ERR_FORMAT if in_bytes[i] < 64, input i is a single-stream stream (no header), its kind or fidelity is not the
+ * call's, or any other check of ansx_decode_dev on its header fails -- *bad_index (optional) is then i, the first such
+ * container; ANSX_ERR_CAPACITY if sum(n_i) > out_capacity_ints.
+ * Errors decided on the device (an invalid index entry or block stream): ANSX_ERR_FORMAT with *bad_index = count --
+ * unlike the range entries, d_out is then unspecified (earlier passes may have written their containers) and the
+ * failing container is not known.
+ * The context stays usable after any error, and the call leaves no trace in it (nothing enters the cached headers of
+ * ansx_decode_dev, no per-geometry hint changes).  Synchronous, like ansx_decode_dev; the inputs are read on
+ * `stream`.  Work is done in passes of at most 16384 blocks per geometry (ANSX_BATCH_PASS_BLOCKS), and the
+ * workspace is bounded by one pass, not by the batch. */
+int ansx_decode_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    size_t count, uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_index,
+    void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
