@@ -48,6 +48,20 @@ struct Layout {  // container layout, a pure function of the geometry (restart-p
 
 }  // namespace
 
+// Block-range pipeline of the model kernels (encode_general; measurements: DESIGN.md section 6)
+#define ANSX_PIPE_NEVER (-1)
+#define ANSX_PIPE_ALWAYS (-2)
+#define ANSX_PIPE_MAX_RANGES 64
+// A call pipelines by itself from ANSX_PIPE_MIN_BLOCKS blocks and ANSX_PIPE_MIN_INTS ints on, in ANSX_PIPE_RANGES ranges.
+// Measured on MI355X (encode call, serial -> pipelined): 16384 blocks of 16 Ki ints ANSfold-1 1.226 -> 1.173 ms with 2, 3 or
+// 5 ranges, 1.213 with 6, 1.261 with 8 (k_sort_entropy and k_candidates have latency floors that every range pays again);
+// 8192 blocks break even for ANSfold-1 and gain for ANSfold-5 (2.91 -> 2.70 ms); 4096 blocks and fewer lose 0.003-0.07 ms
+// to the cross-stream waits.  Two ranges were never slower than the serial form on any list of that size, three lost
+// their gain on uniform data.
+#define ANSX_PIPE_RANGES 2u
+#define ANSX_PIPE_MIN_BLOCKS 8192u
+#define ANSX_PIPE_MIN_INTS ((u64)1 << 27)
+
 struct ansx_ctx {
     u32 num_cus = 256;
     int device = 0;
@@ -92,6 +106,10 @@ struct ansx_ctx {
     u32 sp_retries = 0;             // (tests) calls repeated with the full-size arrays
     bool sp_full_lds = false;       // ... and its prelude writer runs with the full-size LDS arrays (a block's code outgrew the hint-sized ones)
     ansx_encode_stats last = {};
+    // Block-range pipeline of the fast model path (encode_general): two side streams and the events of its fork and join,
+    // created by the first call that needs them (pipeline_prepare) and destroyed with the context, never per call.
+    hipStream_t pipe_stream[2] = { nullptr, nullptr };
+    std::vector<hipEvent_t> pipe_ev;  // [0], [1]: a side stream has finished its ranges; [2 + k]: the histogram of range k is done
     // Path-selection overrides for tests and experiments (every path must give identical bytes).
     // Taken from the environment ONCE in ansx_init, changed afterwards only through ansx_debug_set;
     // the per-call hot path never looks at the environment.
@@ -130,6 +148,7 @@ struct ansx_ctx {
         bool near_flip = false;       // ANSX_TEST_NEAR_FLIP: the device decides close calls the wrong way (tests: the host must fix them)
         u32 cand_chains = 0;          // ANSX_CAND_CHAINS: 1 | 2 recurrences per lane in k_candidates (0 = by the call's size)
         double fast_guard = ANSX_FAST_GUARD;  // ANSX_FAST_GUARD: relative guard band of the fast model path's stop rule (tests widen it)
+        int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
         u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
     } dbg;
 };
@@ -192,6 +211,27 @@ void prof_end(ansx_ctx* c, hipStream_t s)
     } while (0)
 
 inline size_t rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// status of a stream / event call of the block-range pipeline (no early return: its caller still has to join)
+int pipe_hip(ansx_ctx* c, hipError_t e)
+{
+    if (e == hipSuccess) return ANSX_OK;
+    c->last_hip = (int)e;
+    return ANSX_ERR_HIP;
+}
+// the side streams and events of a pipelined call of `nranges` ranges: made once per context, more events only when a
+// later call has more ranges
+int pipeline_prepare(ansx_ctx* c, u32 nranges)
+{
+    for (hipStream_t& st : c->pipe_stream)
+        if (!st) HIPCHK(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    while (c->pipe_ev.size() < 2 + (size_t)nranges) {
+        hipEvent_t e;
+        HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->pipe_ev.push_back(e);
+    }
+    return ANSX_OK;
+}
 
 // worst-case bytes of one block's reference stream
 size_t codec_nsp(int kind, u32 f) { return kind == ANSX_MSB ? 2048u : (kind == ANSX_INT ? 16384u : fold_NSP(f)); }
@@ -656,19 +696,6 @@ int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_
     }
     // (fast path: H is a tree sum in registers, no LDS row of terms)
     const size_t hist_lds = !h_in_hist ? (size_t)NSP * 4 : (size_t)4 * (NSP + ANSX_HCOPY_PAD) * 4 + (fast ? 0 : (size_t)NSP * 8 + 80);
-    if (NSP >= 8192u) {  // f >= 4: 16-bit counters, two per LDS word (a chunk holds at most 16384 values): half the LDS, twice the workgroups per CU
-        const size_t packed_lds = (size_t)NSP * 2;
-        if (packed_lds > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_fold_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)packed_lds));
-        // (sum_mode bit 1: on the fast model path H is the workgroup's tree sum and there is no hterm array to write)
-        LAUNCH(c, "k_fold_hist", k_fold_hist<true>, (size_t)NB * cpb, 256, packed_lds, s, src, g, chunk, cpb, NSP, hist, hterm,
-            fast ? 2u : 0u, blk, gflags, (g.kind == ANSX_INT && !g.pa) ? NSP : (1u << 30));
-    } else {
-        if (hist_lds > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_fold_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds));
-        LAUNCH(c, "k_fold_hist", k_fold_hist<false>, (size_t)NB * cpb, 256, hist_lds, s, src, g, chunk, cpb, NSP, hist, hterm,
-            (h_in_hist ? 1u : 0u) | (fast ? 2u : 0u), blk, gflags, (g.kind == ANSX_INT && !g.pa) ? NSP : (1u << 30));
-    }
     // K2.  "big" symbols have freq >= ANSX_VMAX, so a block holds at most block_ints/ANSX_VMAX
     const u32 nbig_cap = (u32)std::min<size_t>(NSP, (size_t)g.block_ints / ANSX_VMAX + 2);
     // (optimistic calls with whole-block histograms: the staged row is as long as the alphabet hint, see the kernel)
@@ -677,22 +704,6 @@ int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_
     size_t k2a_lds = (size_t)nbig_cap * 8 + (size_t)sort_cap * (sort16 ? 2 : 4) + (h_deferred ? 0 : 512 * 8);
     const bool sort_staged = k2a_lds <= 150 * 1024;  // (f = 6, 7 with 32-bit counts: the row stays in HBM)
     if (!sort_staged) k2a_lds = (size_t)nbig_cap * 8 + (h_deferred ? 0 : 512 * 8);
-    if (k2a_lds > 32 * 1024) {
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_sort_entropy<u16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k2a_lds));
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_sort_entropy<u32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k2a_lds));
-    }
-    if ((size_t)NSP * 8 + 64 > 48 * 1024 && (size_t)NSP * 8 + 64 <= 150 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_write_prelude<0>,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NSP * 8 + 64)));
-    if (!sort_staged)
-        LAUNCH(c, "k_sort_entropy", (k_sort_entropy<u32, false>), NB, 64, k2a_lds, s, g, NSP, nbig_cap, h_deferred ? 1u : 0u, hist,
-            (u32*)c->sortF.p, (u16*)c->sortSym.p, blk, sort_cap, fast ? (uint2*)c->pairs.p : (uint2*)nullptr, gflags);
-    else if (sort16)
-        LAUNCH(c, "k_sort_entropy", k_sort_entropy<u16>, NB, 64, k2a_lds, s, g, NSP, nbig_cap, h_deferred ? 1u : 0u, hist,
-            (u32*)c->sortF.p, (u16*)c->sortSym.p, blk, sort_cap, fast ? (uint2*)c->pairs.p : (uint2*)nullptr, gflags);
-    else
-        LAUNCH(c, "k_sort_entropy", k_sort_entropy<u32>, NB, 64, k2a_lds, s, g, NSP, nbig_cap, h_deferred ? 1u : 0u, hist,
-            (u32*)c->sortF.p, (u16*)c->sortSym.p, blk, sort_cap, fast ? (uint2*)c->pairs.p : (uint2*)nullptr, gflags);
     // Frame sizes M0*2^t are tried ANSX_ATTEMPTS at a time.  Almost every block settles in the
     // first batch; the count of undecided blocks comes back with the words the encoder launch
     // needs anyway (largest alphabet / frame), so further batches are launched only on demand.
@@ -706,19 +717,115 @@ int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_
     // (plain ANSint: no parse hints -- its decoder walks the value-range prelude sparsely, and the container must not depend on
     // which of the two models, dense or rank space, wrote it)
     u32* hints = (P.plain || (g.kind == ANSX_INT && !g.pa)) ? nullptr : (u32*)(d_out + P.lay.hint_off);
+    // fast model path: lanes / chains of k_candidates, LDS of k_model_finish
+    const u32 bpw = fast ? 64u / NT : 1u;
+    // chains per lane: one while that leaves at most one wave per SIMD, else two (see k_candidates); per launch, by its blocks
+    auto cand_chains = [&](u32 nblk) -> u32 {
+        return c->dbg.cand_chains ? c->dbg.cand_chains : (((nblk + bpw - 1) / bpw <= 4u * c->num_cus) ? 1u : 2u);
+    };
+    const u32 fcap = std::min<u32>(NSP, std::max<u32>(64u, (ns_cap + 15u) & ~15u));
+    const bool fin_generic = NSP > 4096;  // (loop-based form: inc[] in the block's histogram row, two LDS arrays)
+    const size_t fl = (size_t)fcap * (fin_generic ? 8 : 12) + 64;
+
+    // Block-range pipeline of the fast model path: the call's blocks in `nranges` contiguous ranges,
+    // the histograms one after the other on the caller's stream, and k_sort_entropy -> k_candidates -> k_model_finish of
+    // every range but the last on one of the context's two side streams (alternating) behind that range's histogram -- a
+    // memory-bound kernel beside a VALU-bound one beside a latency chain.  The ranges meet in no workspace byte (every
+    // array is indexed by the absolute block number) and in `gflags` only through order-independent atomics.  Everything
+    // joins on the caller's stream in front of the encoder.  nranges == 0: one launch of each kernel over all blocks on
+    // the caller's stream.
+    u32 range_blocks = NB, nranges = 0;
+    if (fast && !c->profile && c->dbg.model_pipeline != ANSX_PIPE_NEVER) {
+        // (profile mode: the event pairs of LAUNCH would time overlapped kernels -- serial there)
+        const int mode = c->dbg.model_pipeline;
+        u32 want = mode > 0 ? (u32)mode : ((mode == ANSX_PIPE_ALWAYS || (NB >= ANSX_PIPE_MIN_BLOCKS && g.n >= ANSX_PIPE_MIN_INTS)) ? ANSX_PIPE_RANGES : 0u);
+        if (want) {
+            // (a captured graph with parallel branches: the call stays one chain of launches under capture)
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) want = 0;
+        }
+        if (want) {
+            range_blocks = (u32)rup(((size_t)NB + want - 1) / want, 64);  // range boundaries: multiples of 64 blocks
+            nranges = (NB + range_blocks - 1) / range_blocks;
+            if ((rc = pipeline_prepare(c, nranges))) return rc;
+        }
+    }
+
+    // ---- every function attribute of the phase, in front of the first launch (nothing but launches, event records and
+    // stream waits between the pipeline's fork and its join)
+    const bool hist_packed = NSP >= 8192u;  // f >= 4: 16-bit counters, two per LDS word (a chunk holds at most 16384 values): half the LDS, twice the workgroups per CU
+    const size_t packed_lds = (size_t)NSP * 2;
+    if (hist_packed) {
+        if (packed_lds > 48 * 1024)
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_fold_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)packed_lds));
+    } else if (hist_lds > 48 * 1024)
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_fold_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds));
+    if (k2a_lds > 32 * 1024) {
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_sort_entropy<u16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k2a_lds));
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_sort_entropy<u32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k2a_lds));
+    }
+    if ((size_t)NSP * 8 + 64 > 48 * 1024 && (size_t)NSP * 8 + 64 <= 150 * 1024)
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_write_prelude<0>,
+                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NSP * 8 + 64)));
     if (fast) {
-        const u32 bpw = 64u / NT;
-        // chains per lane: one while that leaves at most one wave per SIMD, else two (see k_candidates)
-        const u32 nch = c->dbg.cand_chains ? c->dbg.cand_chains : (((NB + bpw - 1) / bpw <= 4u * c->num_cus) ? 1u : 2u);
+        // k_candidates: the chain counts its launches will use (a full range and the last, shorter one)
+        const u32 last_blocks = nranges ? NB - (nranges - 1) * range_blocks : NB;
+        const u32 chain_set = (1u << cand_chains(nranges ? range_blocks : NB)) | (1u << cand_chains(last_blocks));
+        for (u32 nch = 1; nch <= 2; nch++) {
+            const size_t cl = (size_t)ANSX_CAND_WAVES * nch * bpw * ANSX_CAND_ROW * 16;
+            if (!(chain_set & (1u << nch)) || cl <= 48 * 1024) continue;
+            const void* fn = nullptr;
+            switch (NT) {
+            case 4: fn = nch == 1 ? (const void*)k_candidates<4, 1> : (const void*)k_candidates<4, 2>; break;
+            case 5: fn = nch == 1 ? (const void*)k_candidates<5, 1> : (const void*)k_candidates<5, 2>; break;
+            case 6: fn = nch == 1 ? (const void*)k_candidates<6, 1> : (const void*)k_candidates<6, 2>; break;
+            case 7: fn = nch == 1 ? (const void*)k_candidates<7, 1> : (const void*)k_candidates<7, 2>; break;
+            default: fn = nch == 1 ? (const void*)k_candidates<8, 1> : (const void*)k_candidates<8, 2>; break;
+            }
+            HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cl));
+        }
+        if (fl > 48 * 1024 && !(NSP <= 1024 && c->dbg.fin_one_wave)) {
+            const void* fn = NSP <= 1024 ? (const void*)k_model_finish<4, 8>
+                : NSP > 4096 ? (NT <= 5 ? (const void*)k_model_finish<0, 5> : (const void*)k_model_finish<0, 8>)
+                             : (NT <= 5 ? (const void*)k_model_finish<16, 5> : (const void*)k_model_finish<16, 8>);
+            HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl));
+        }
+    }
+
+    // ---- the four launches for the blocks [b0, be) on stream st
+    // K1
+    auto launch_hist = [&](hipStream_t st, u32 b0, u32 be) -> int {
+        const size_t grid = (size_t)(be - b0) * cpb;
+        if (hist_packed) {
+            // (sum_mode bit 1: on the fast model path H is the workgroup's tree sum and there is no hterm array to write)
+            LAUNCH(c, "k_fold_hist", k_fold_hist<true>, grid, 256, packed_lds, st, src, g, chunk, cpb, NSP, hist, hterm,
+                fast ? 2u : 0u, blk, gflags, (g.kind == ANSX_INT && !g.pa) ? NSP : (1u << 30), b0, be);
+        } else {
+            LAUNCH(c, "k_fold_hist", k_fold_hist<false>, grid, 256, hist_lds, st, src, g, chunk, cpb, NSP, hist, hterm,
+                (h_in_hist ? 1u : 0u) | (fast ? 2u : 0u), blk, gflags, (g.kind == ANSX_INT && !g.pa) ? NSP : (1u << 30), b0, be);
+        }
+        return ANSX_OK;
+    };
+    // K2
+    auto launch_sort = [&](hipStream_t st, u32 b0, u32 be) -> int {
+        if (!sort_staged)
+            LAUNCH(c, "k_sort_entropy", (k_sort_entropy<u32, false>), be - b0, 64, k2a_lds, st, g, NSP, nbig_cap, h_deferred ? 1u : 0u, hist,
+                (u32*)c->sortF.p, (u16*)c->sortSym.p, blk, sort_cap, fast ? (uint2*)c->pairs.p : (uint2*)nullptr, gflags, b0, be);
+        else if (sort16)
+            LAUNCH(c, "k_sort_entropy", k_sort_entropy<u16>, be - b0, 64, k2a_lds, st, g, NSP, nbig_cap, h_deferred ? 1u : 0u, hist,
+                (u32*)c->sortF.p, (u16*)c->sortSym.p, blk, sort_cap, fast ? (uint2*)c->pairs.p : (uint2*)nullptr, gflags, b0, be);
+        else
+            LAUNCH(c, "k_sort_entropy", k_sort_entropy<u32>, be - b0, 64, k2a_lds, st, g, NSP, nbig_cap, h_deferred ? 1u : 0u, hist,
+                (u32*)c->sortF.p, (u16*)c->sortSym.p, blk, sort_cap, fast ? (uint2*)c->pairs.p : (uint2*)nullptr, gflags, b0, be);
+        return ANSX_OK;
+    };
+    auto launch_cand = [&](hipStream_t st, u32 b0, u32 be) -> int {
+        const u32 nch = cand_chains(be - b0);
         const size_t cl = (size_t)ANSX_CAND_WAVES * nch * bpw * ANSX_CAND_ROW * 16;
-        const u32 cwaves = (NB + nch * bpw - 1) / (nch * bpw);
+        const u32 cwaves = (be - b0 + nch * bpw - 1) / (nch * bpw);
 #define ANSX_LAUNCH_CAND2(NT_, NCH_)                                                                                    \
-    do {                                                                                                            \
-        if (cl > 48 * 1024)                                                                                         \
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_candidates<NT_, NCH_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cl)); \
-        LAUNCH(c, "k_candidates", (k_candidates<NT_, NCH_>), (cwaves + ANSX_CAND_WAVES - 1) / ANSX_CAND_WAVES, 64 * ANSX_CAND_WAVES, cl, s, g, NSP, \
-            (const uint2*)c->pairs.p, (const ansx_blk*)blk, (uint4*)c->attS.p, (u32*)c->attMeta.p);               \
-    } while (0)
+        LAUNCH(c, "k_candidates", (k_candidates<NT_, NCH_>), (cwaves + ANSX_CAND_WAVES - 1) / ANSX_CAND_WAVES, 64 * ANSX_CAND_WAVES, cl, st, g, NSP, \
+            (const uint2*)c->pairs.p, (const ansx_blk*)blk, (uint4*)c->attS.p, (u32*)c->attMeta.p, b0, be)
 #define ANSX_LAUNCH_CAND(NT_)                                                                                           \
     do {                                                                                                            \
         if (nch == 1) ANSX_LAUNCH_CAND2(NT_, 1);                                                                    \
@@ -733,38 +840,71 @@ int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_
         }
 #undef ANSX_LAUNCH_CAND
 #undef ANSX_LAUNCH_CAND2
-        const u32 fcap = std::min<u32>(NSP, std::max<u32>(64u, (ns_cap + 15u) & ~15u));
-        const bool fin_generic = NSP > 4096;  // (loop-based form: inc[] in the block's histogram row, two LDS arrays)
-        const size_t fl = (size_t)fcap * (fin_generic ? 8 : 12) + 64;
-#define ANSX_LAUNCH_FIN(IPT_, NTC_)                                                                                    \
-    do {                                                                                                            \
-        if (fl > 48 * 1024)                                                                                         \
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_model_finish<IPT_, NTC_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl)); \
-        LAUNCH(c, "k_model_finish", (k_model_finish<IPT_, NTC_>), NB, 256, fl, s, g, NSP, NT, (const uint2*)c->pairs.p, (const uint4*)c->attS.p, \
+        return ANSX_OK;
+    };
+    auto launch_fin = [&](hipStream_t st, u32 b0, u32 be) -> int {
+#define ANSX_LAUNCH_FIN(IPT_, NTC_, NTH_)                                                                              \
+        LAUNCH(c, "k_model_finish", (k_model_finish<IPT_, NTC_, NTH_>), be - b0, NTH_, fl, st, g, NSP, NT, (const uint2*)c->pairs.p, (const uint4*)c->attS.p, \
             (const u32*)c->attMeta.p, blk, (u32*)c->tab32.p, (u8*)c->scratch.p, (u64)scr_stride, mostfreq, hints, gflags, fcap, c->dbg.fast_guard, (const double*)c->lg2i.p, geo, \
-            fin_generic ? hist : (u32*)nullptr); \
-    } while (0)
+            (fin_generic && (NTH_) == 256) ? hist : (u32*)nullptr, b0, be)
         if (NSP <= 1024 && c->dbg.fin_one_wave) {
             // one wave per block (16 slots per lane, every candidate in every lane, no workgroup barriers): four times the blocks in flight
-            if (NT <= 5) {
-                LAUNCH(c, "k_model_finish", (k_model_finish<16, 5, 64>), NB, 64, fl, s, g, NSP, NT, (const uint2*)c->pairs.p, (const uint4*)c->attS.p,
-                    (const u32*)c->attMeta.p, blk, (u32*)c->tab32.p, (u8*)c->scratch.p, (u64)scr_stride, mostfreq, hints, gflags, fcap, c->dbg.fast_guard, (const double*)c->lg2i.p, geo,
-                    (u32*)nullptr);
-            } else {
-                LAUNCH(c, "k_model_finish", (k_model_finish<16, 8, 64>), NB, 64, fl, s, g, NSP, NT, (const uint2*)c->pairs.p, (const uint4*)c->attS.p,
-                    (const u32*)c->attMeta.p, blk, (u32*)c->tab32.p, (u8*)c->scratch.p, (u64)scr_stride, mostfreq, hints, gflags, fcap, c->dbg.fast_guard, (const double*)c->lg2i.p, geo,
-                    (u32*)nullptr);
-            }
+            if (NT <= 5) ANSX_LAUNCH_FIN(16, 5, 64);
+            else ANSX_LAUNCH_FIN(16, 8, 64);
         } else if (NSP <= 1024) {
-            ANSX_LAUNCH_FIN(4, 8);  // (wave-per-candidate form: NTC is not used)
+            ANSX_LAUNCH_FIN(4, 8, 256);  // (wave-per-candidate form: NTC is not used)
         } else if (NSP > 4096) {
-            if (NT <= 5) ANSX_LAUNCH_FIN(0, 5);
-            else ANSX_LAUNCH_FIN(0, 8);
+            if (NT <= 5) ANSX_LAUNCH_FIN(0, 5, 256);
+            else ANSX_LAUNCH_FIN(0, 8, 256);
         } else {
-            if (NT <= 5) ANSX_LAUNCH_FIN(16, 5);
-            else ANSX_LAUNCH_FIN(16, 8);
+            if (NT <= 5) ANSX_LAUNCH_FIN(16, 5, 256);
+            else ANSX_LAUNCH_FIN(16, 8, 256);
         }
 #undef ANSX_LAUNCH_FIN
+        return ANSX_OK;
+    };
+    if (nranges == 0) {
+        if ((rc = launch_hist(s, 0, NB))) return rc;
+        if ((rc = launch_sort(s, 0, NB))) return rc;
+        if (fast) {
+            if ((rc = launch_cand(s, 0, NB))) return rc;
+            if ((rc = launch_fin(s, 0, NB))) return rc;
+        }
+    } else {
+        // fork: a range's model kernels wait for the event recorded on the caller's stream behind its histogram -- and with
+        // it for everything the call, and the call before it, put on that stream (k_begin_encode, the remap, the previous
+        // encoder's last read of the shared workspace)
+        u32 used = 0;  // side streams with work of this call
+        rc = ANSX_OK;
+        for (u32 k = 0; k < nranges && !rc; k++) {
+            const u32 b0 = k * range_blocks, be = std::min<u32>(NB, b0 + range_blocks);
+            if ((rc = launch_hist(s, b0, be))) break;
+            hipStream_t st = s;
+            if (k + 1 < nranges) {
+                const u32 side = k & 1u;
+                st = c->pipe_stream[side];
+                if ((rc = pipe_hip(c, hipEventRecord(c->pipe_ev[2 + k], s)))) break;
+                if ((rc = pipe_hip(c, hipStreamWaitEvent(st, c->pipe_ev[2 + k], 0)))) break;
+                used |= 1u << side;
+            }  // (the last range stays on the caller's stream behind its histogram: nothing is left to overlap it with there,
+               // and the encoder follows it without a cross-stream wait)
+            if ((rc = launch_sort(st, b0, be))) break;
+            if ((rc = launch_cand(st, b0, be))) break;
+            rc = launch_fin(st, b0, be);
+        }
+        // join: always, whatever happened above -- when the call returns, all its work is ordered on the caller's stream
+        for (u32 side = 0; side < 2; side++) {
+            if (!(used & (1u << side))) continue;
+            int rj = pipe_hip(c, hipEventRecord(c->pipe_ev[side], c->pipe_stream[side]));
+            if (!rj) rj = pipe_hip(c, hipStreamWaitEvent(s, c->pipe_ev[side], 0));
+            if (rj) {  // (the runtime refused the record or the wait: the host waits instead, so the promise still holds)
+                (void)hipStreamSynchronize(c->pipe_stream[side]);
+                if (!rc) rc = rj;
+            }
+        }
+        if (rc) return rc;
+    }
+    if (fast) {
         max_logM = 16;
         max_ns = ns_cap;
     }
@@ -2197,7 +2337,7 @@ int ansx_init(int device, ansx_ctx** out)
     }
     static const char* const names[] = { "ANSX_TEST_TABLE16_FIXUP", "ANSX_ENCODE_GTAB16", "ANSX_PARSE_GENERIC", "ANSX_PARSE_WIN", "ANSX_PARSE_FAST",
         "ANSX_DECODE_TABLE", "ANSX_NO_STREAM_LDS", "ANSX_DECODE_MODE", "ANSX_PARSE_STAGE_WORDS", "ANSX_MODEL_FUSED", "ANSX_MODEL_SYNC", "ANSX_NS_HINT", "ANSX_T_HINT", "ANSX_NO_FAST_MODEL", "ANSX_FAST_GUARD", "ANSX_CAND_CHAINS", "ANSX_NEAR_BAND", "ANSX_TEST_NEAR_FLIP", "ANSX_WIDE_RESTART", "ANSX_TEST_WIDE_AT",
-        "ANSX_BATCH_PASS_BLOCKS" };
+        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE" };
     for (const char* nm : names)
         if (const char* v = getenv(nm)) (void)ansx_debug_set(c, nm, v);
     *out = c;
@@ -2301,6 +2441,17 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
     else if (!strcmp(name, "ANSX_NEAR_BAND")) c->dbg.near_band = (value && value[0]) ? strtod(value, nullptr) : ANSX_NEAR_BAND;
     else if (!strcmp(name, "ANSX_TEST_NEAR_FLIP")) c->dbg.near_flip = on;
     else if (!strcmp(name, "ANSX_BATCH_PASS_BLOCKS")) c->dbg.batch_pass_blocks = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
+    else if (!strcmp(name, "ANSX_MODEL_PIPELINE")) {
+        if (!value || !value[0] || !strcmp(value, "0")) c->dbg.model_pipeline = 0;
+        else if (!strcmp(value, "never")) c->dbg.model_pipeline = ANSX_PIPE_NEVER;
+        else if (!strcmp(value, "always")) c->dbg.model_pipeline = ANSX_PIPE_ALWAYS;
+        else {
+            char* end = nullptr;
+            const unsigned long v = strtoul(value, &end, 10);
+            if (value[0] < '0' || value[0] > '9' || *end != 0 || v < 1 || v > ANSX_PIPE_MAX_RANGES) return ANSX_ERR_ARG;
+            c->dbg.model_pipeline = (int)v;
+        }
+    }
     else if (!strcmp(name, "ANSX_CAND_CHAINS")) {
         const u32 v = value ? (u32)strtoul(value, nullptr, 10) : 0u;
         if (v > 2) return ANSX_ERR_ARG;
@@ -2315,6 +2466,11 @@ void ansx_destroy(ansx_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    for (hipStream_t st : c->pipe_stream)  // (idle unless a call failed in the middle: drained before anything is freed)
+        if (st) (void)hipStreamSynchronize(st);
+    for (hipEvent_t e : c->pipe_ev) (void)hipEventDestroy(e);
+    for (hipStream_t st : c->pipe_stream)
+        if (st) (void)hipStreamDestroy(st);
     DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->log2lut, &c->pa_alpha, &c->pa_info, &c->pairs, &c->lg2i, &c->sizes, &c->nearlist, &c->force, &c->geo_big,

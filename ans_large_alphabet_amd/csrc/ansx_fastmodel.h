@@ -68,16 +68,18 @@ template <u32 NT, u32 NCH>  // compile-time: every staging load of a stage must 
                    // hipcc gives each load its own basic block and a full wait: 7 us per stage instead of one round trip)
 __global__ __launch_bounds__(64 * ANSX_CAND_WAVES) void k_candidates(ansx_geo g, u32 NSP,
     const uint2* __restrict__ pairs, const ansx_blk* __restrict__ blk, uint4* __restrict__ srank,
-    u32* __restrict__ attMeta)
+    u32* __restrict__ attMeta, u32 b0, u32 bend)
 {
+    // b0, bend: the launch covers the blocks [b0, bend) of the call; its waves count from b0 and touch no row outside
+
     extern __shared__ double2 cand_lds_all[];  // per wave: [2 BPW][ANSX_CAND_ROW] { freq, reciprocal of fs_rem }
     const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     constexpr u32 BPW = 64u / NT;
     constexpr u32 rows = NCH * BPW;
     double2* const cand_lds = cand_lds_all + wv * rows * ANSX_CAND_ROW;
     const u32 bl = lane / NT, t = lane - bl * NT;
-    const u32 wb0 = (u32)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * ANSX_CAND_WAVES + wv) * rows));
-    if (wb0 >= g.nblocks) return;
+    const u32 wb0 = (u32)__builtin_amdgcn_readfirstlane((int)(b0 + (blockIdx.x * ANSX_CAND_WAVES + wv) * rows));
+    if (wb0 >= bend) return;
     u32 bb[NCH], sigma[NCH], sh[NCH];
     bool live[NCH];
     double Md[NCH], fsd[NCH], mx[NCH];
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(64 * ANSX_CAND_WAVES) void k_candidates(ansx_geo g,
 #pragma unroll
     for (u32 c = 0; c < NCH; c++) {
         bb[c] = wb0 + c * BPW + bl;
-        live[c] = bl < BPW && bb[c] < g.nblocks;
+        live[c] = bl < BPW && bb[c] < bend;
         sigma[c] = 0, sh[c] = 0;
         double nd = 1.0;
         if (live[c]) {
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(64 * ANSX_CAND_WAVES) void k_candidates(ansx_geo g,
     // recurrence and turn fs_rem into its reciprocal on the way into LDS
     constexpr u32 NITER = rows * (ANSX_CAND_SL / 64u);
     uint2 nxt[NITER];
-    const u32 last_b = g.nblocks - 1u;
+    const u32 last_b = bend - 1u;
     auto fetch = [&](u32 c0) {
 #pragma unroll
         for (u32 k = 0; k < NITER; k++) {
@@ -271,7 +273,7 @@ __global__ __launch_bounds__(NTH) void k_model_finish(ansx_geo g, u32 NSP, u32 N
     const uint4* __restrict__ srank, const u32* __restrict__ attMeta, ansx_blk* __restrict__ blk,
     u32* __restrict__ tab32, u8* __restrict__ scratch, u64 scr_stride, const u32* __restrict__ mostfreq,
     u32* __restrict__ hints, u32* __restrict__ gflags, u32 cap, double guard, const double* __restrict__ lg2i,
-    const uint2* __restrict__ geo, u32* __restrict__ incbuf = nullptr)
+    const uint2* __restrict__ geo, u32* __restrict__ incbuf, u32 b0, u32 bend)
 {
     static_assert(IPT % 4 == 0, "table rows are written 16 bytes at a time");
     static_assert(ANSX_FIN_LUT == 512 && (NTH == 256 || NTH == 64), "two table entries per thread (eight in the one-wave form)");
@@ -283,7 +285,8 @@ __global__ __launch_bounds__(NTH) void k_model_finish(ansx_geo g, u32 NSP, u32 N
     __shared__ double wpart[ANSX_ATTEMPTS][4];  // per candidate and wave: partial sum of F log2 S (one wave: column 0)
     __shared__ double wsum[ANSX_ATTEMPTS];      // XH of every candidate
     const u32 tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    const u32 b = blockIdx.x;
+    const u32 b = b0 + blockIdx.x;  // the launch covers the blocks [b0, bend) of the call
+    if (b >= bend) return;
     ansx_blk* B = &blk[b];
     u32* off = lds32;             // [cap]
     u32* bits = lds32 + cap;      // bit buffer; until the prelude is written: the chosen frequencies by symbol

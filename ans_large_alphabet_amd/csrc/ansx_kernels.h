@@ -127,8 +127,10 @@ __device__ __forceinline__ uint4 ld16_stream(const uint4* p)
 template <bool PACKED>
 __global__ __launch_bounds__(256) void k_fold_hist(const u32* __restrict__ in, ansx_geo g,
     u32 chunk, u32 cpb, u32 NSP, u32* __restrict__ hist, double* __restrict__ hterm, u32 sum_mode,
-    ansx_blk* __restrict__ blk, u32* __restrict__ gflags, u32 value_limit)
+    ansx_blk* __restrict__ blk, u32* __restrict__ gflags, u32 value_limit, u32 b0, u32 bend)
 {
+    // b0, bend: the launch covers the blocks [b0, bend) of the call (0, g.nblocks: all of them); every index below is
+    // the absolute block number
     // sum_mode bit 0: four histogram copies, entropy terms kept in LDS (alphabets <= 2048 slots);
     //          bit 1: the fast model path -- H is the workgroup's tree sum of the terms instead of the reference's
     //                 left-to-right sum (within ~1e-13 of it; the stop rule of that path keeps a 1e-9 guard band
@@ -137,7 +139,8 @@ __global__ __launch_bounds__(256) void k_fold_hist(const u32* __restrict__ in, a
     const bool tree_sum = (sum_mode & 2u) != 0;
     extern __shared__ u32 lds_hist[];
     const u32 tid = threadIdx.x;
-    const u32 b = blockIdx.x / cpb, c = blockIdx.x % cpb;
+    const u32 b = b0 + blockIdx.x / cpb, c = blockIdx.x % cpb;
+    if (b >= bend) return;
     const u32 nb = geo_block_n(g, b);
     const u64 start = (u64)c * chunk;
     if (start >= nb) return;
@@ -324,8 +327,9 @@ __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcn
 template <typename HT, bool STAGED = true>
 __global__ __launch_bounds__(64) void k_sort_entropy(ansx_geo g, u32 NSP, u32 nbig_cap, u32 h_deferred,
     const u32* __restrict__ hist, u32* __restrict__ sortF, u16* __restrict__ sortSym,
-    ansx_blk* __restrict__ blk, u32 cap, uint2* __restrict__ pairs, u32* __restrict__ gflags)
+    ansx_blk* __restrict__ blk, u32 cap, uint2* __restrict__ pairs, u32* __restrict__ gflags, u32 b0, u32 bend)
 {
+    // b0, bend: the launch covers the blocks [b0, bend) of the call
     extern __shared__ u64 lds_k2a[];  // [nbig_cap] big keys (freq << 16 | sym), then the staged row
     __shared__ u32 cnt[ANSX_VMAX];
     __shared__ u16 cnt0[ANSX_VMAX];  // number of symbols per frequency value (before the scan)
@@ -336,7 +340,8 @@ __global__ __launch_bounds__(64) void k_sort_entropy(ansx_geo g, u32 NSP, u32 nb
     HT* hrow = (HT*)(lds_k2a + nbig_cap);  // [cap] this block's histogram row
     double* terms = (double*)(hrow + (STAGED ? cap : 0u));   // [512], only allocated when the entropy is summed here
     const u32 lane = threadIdx.x;
-    const u32 b = blockIdx.x;
+    const u32 b = b0 + blockIdx.x;
+    if (b >= bend) return;
     const u32* h = hist + (u64)b * NSP;
     // stage the histogram row once: its first 640 entries are requested together with the alphabet size they are
     // then cut to (a row has NSP entries whatever the block's alphabet) -- one round trip instead of two or more

@@ -321,7 +321,12 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
  * learns; too small a value only costs a repeat on the general path), ANSX_T_HINT (number: candidate frame sizes per
  * block of the fast model path), ANSX_NO_FAST_MODEL, ANSX_FAST_GUARD / ANSX_NEAR_BAND (numbers: relative bands around
  * the stop-rule threshold inside which the fast path repeats on the exact one / the host re-decides),
- * ANSX_TEST_NEAR_FLIP (the device decides close calls the wrong way), ANSX_CAND_CHAINS (1 | 2), ANSX_WIDE_RESTART
+ * ANSX_TEST_NEAR_FLIP (the device decides close calls the wrong way), ANSX_CAND_CHAINS (1 | 2), ANSX_MODEL_PIPELINE
+ * ("never" | "always" | a range count 1 .. 64; ""/"0"/NULL: by the call's size; anything else: ANSX_ERR_ARG -- the
+ * block-range pipeline of the fast model path: the call's blocks in contiguous ranges, their histograms one after the
+ * other on the caller's stream, the model kernels of every range but the last on two side streams of the context, all
+ * joined on the caller's stream in front of the encoder; "always" / a number pipeline any list that takes the fast model
+ * path, however short, except in per-kernel profile mode and on a stream that is being captured), ANSX_WIDE_RESTART
  * (wide restart points in every container -- the one switch here that changes the output: the index, not the block
  * streams), ANSX_TEST_WIDE_AT (number <= 16: frames above 2^this count as too large for packed restart points);
  * through this call only (round 4): ANSX_NO_PC / ANSX_FORCE_PC / ANSX_NO_PC_AUTO / ANSX_PC_B_PAIRS (the producer /
