@@ -48,7 +48,7 @@ struct Layout {  // container layout, a pure function of the geometry (restart-p
 
 }  // namespace
 
-// Block-range pipeline of the model kernels (encode_general; measurements: DESIGN.md section 6)
+// Block-range pipeline of the model kernels (model_fast; measurements: DESIGN.md section 6)
 #define ANSX_PIPE_NEVER (-1)
 #define ANSX_PIPE_ALWAYS (-2)
 #define ANSX_PIPE_MAX_RANGES 64
@@ -94,19 +94,9 @@ struct ansx_ctx {
     int last_gather_ranks = 0;   // ranks of the communicator the last ansx_gather_containers call ran on (ncclCommCount)
     std::set<u64> wide_hint;     // geometries that met a frame above 2^16: wide restart points from the start
     std::map<u64, u32> t_hint;   // largest chosen candidate index t (frame M0 * 2^t) + 1 seen per geometry: lanes per block of k_candidates
-    const u32* cur_force = nullptr;  // per-block frames decided by the host (resolve_near), device array, for the repeat of a call
-    const u32* cur_src = nullptr;    // set by encode_general: the ints the model kernels saw (the input, or its remapped form)
-    bool used_pc = false;        // set by launch_lds_encoder: the producer / consumer encoder kernel ran in the call
-    bool used_fast = false;      // set by encode_general: the call's model came from k_candidates / k_model_finish
-    u32 cur_nt = 0;              // set by encode_dev: candidates per block for the fast model path of this call (0 = exact path)
-    u32 cur_rf_slots = 0;        // set by encode_dev for the optimistic attempt of the current call
-    u32 cur_pa_distinct = 0;     // the same for the compaction layer's k_pa_remap (the hint itself)
     std::set<u64> int_sparse_hint;  // plain-ANSint geometries whose values outgrew the dense 16384-symbol model: rank space from the start
-    bool cur_int_sparse = false;    // this call models its blocks in rank space (ansx_intsparse.h)
-    u32 sp_retries = 0;             // (tests) calls repeated with the full-size arrays
-    bool sp_full_lds = false;       // ... and its prelude writer runs with the full-size LDS arrays (a block's code outgrew the hint-sized ones)
     ansx_encode_stats last = {};
-    // Block-range pipeline of the fast model path (encode_general): two side streams and the events of its fork and join,
+    // Block-range pipeline of the fast model path (model_fast): two side streams and the events of its fork and join,
     // created by the first call that needs them (pipeline_prepare) and destroyed with the context, never per call.
     hipStream_t pipe_stream[2] = { nullptr, nullptr };
     std::vector<hipEvent_t> pipe_ev;  // [0], [1]: a side stream has finished its ranges; [2 + k]: the histogram of range k is done
@@ -450,24 +440,14 @@ constexpr int ANSX_RETRY_WIDE = -2;     // internal: a frame above 2^16 in a cal
 //                 last workgroup pads itself with neutral steps (blocks that do not exist, the partial last block)
 //   k_encode<1>   one wave per 16 blocks, 4-byte LDS entries: geometries the pair kernel does not take
 //   k_encode<2>   compact tables in HBM with the hottest 1151 symbols per block in LDS: alphabets that fit neither
-template <bool POW2, int S>
-static int launch_pc(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u32* src, u32 ns_entries, u32 rowwords, u32 pairs, u32 wgs,
-    size_t lds, ansx_blk* blk, u64 scr_stride, u64* ck_state, u32* ck_off, u32* enc_sizes, unsigned long long* enc_gsums, hipStream_t s)
-{
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_encode_pc<POW2, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    LAUNCH(c, "k_encode", (k_encode_pc<POW2, S>), wgs, 128 * pairs, lds, s, src, g, NSP, (const u32*)c->tab32.p, ns_entries, rowwords, blk,
-        (u8*)c->scratch.p, scr_stride, ck_state, ck_off, enc_sizes, enc_gsums);
-    return ANSX_OK;
-}
 static int launch_f64_encoder(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u32* src, u32 ns_entries, ansx_blk* blk, u64 scr_stride,
-    u64* ck_state, u32* ck_off, u32* enc_sizes, unsigned long long* enc_gsums, u32 NB, hipStream_t s)
+    u64* ck_state, u32* ck_off, u32* enc_sizes, unsigned long long* enc_gsums, u32 NB, hipStream_t s, bool* used_pc)
 {
-    c->used_pc = false;
+    *used_pc = false;  // (true below, once the pair kernel has taken blocks of this call)
     const u32 lds_stride = ns_entries | 1u;  // odd stride spreads the 16 tables over the banks
     const size_t enc_lds = (size_t)16 * lds_stride * 4;
     const bool mode1 = enc_lds <= 40 * 1024 && !c->dbg.encode_mode2;
     const bool pow2 = map_is_pow2(g.map);
-    int rc;
     u32 first = 0;
     // ---- producer / consumer pairs
     const u32 rowwords = ((ns_entries + 2u) / 2u) | 1u;  // ns_entries + 1 running sums of 16 bits, an odd number of words per row
@@ -489,13 +469,12 @@ static int launch_f64_encoder(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u32
     if (pairs && (g.ckpt == 0 || g.ckpt % (4u * S) == 0)) {
         const u32 wgs = (NB + 16 * pairs - 1) / (16 * pairs);
         const size_t lds = pc_lds(pairs, S);
-        if (pow2) rc = S == 8 ? launch_pc<true, 8>(c, g, NSP, src, ns_entries, rowwords, pairs, wgs, lds, blk, scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, s)
-                              : launch_pc<true, 4>(c, g, NSP, src, ns_entries, rowwords, pairs, wgs, lds, blk, scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, s);
-        else rc = S == 8 ? launch_pc<false, 8>(c, g, NSP, src, ns_entries, rowwords, pairs, wgs, lds, blk, scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, s)
-                         : launch_pc<false, 4>(c, g, NSP, src, ns_entries, rowwords, pairs, wgs, lds, blk, scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, s);
-        if (rc) return rc;
+        const auto kern = pow2 ? (S == 8 ? k_encode_pc<true, 8> : k_encode_pc<true, 4>) : (S == 8 ? k_encode_pc<false, 8> : k_encode_pc<false, 4>);
+        HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        LAUNCH(c, "k_encode", kern, wgs, 128 * pairs, lds, s, src, g, NSP, (const u32*)c->tab32.p, ns_entries, rowwords, blk,
+            (u8*)c->scratch.p, scr_stride, ck_state, ck_off, enc_sizes, enc_gsums);
         first = wgs * 16 * pairs;
-        c->used_pc = true;
+        *used_pc = true;
         if (first >= NB) return ANSX_OK;
     }
     const u32 enc_waves = (NB - first + 15) / 16;
@@ -505,18 +484,12 @@ static int launch_f64_encoder(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u32
     if (mode1) {
         // ---- one wave per 16 blocks.  Waves of one workgroup run the main loop in step (a barrier per super-batch): up to four
         // waves per workgroup -- one per SIMD of a CU -- as soon as there are that many waves per CU (see k_encode)
-        if (wpw * enc_lds > 48 * 1024) {
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_encode<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wpw * enc_lds)));
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_encode<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wpw * enc_lds)));
-        }
-        if (pow2)
-            LAUNCH(c, first ? "k_encode_rest" : "k_encode", (k_encode<1, true>), enc_grid, 64 * wpw, wpw * enc_lds, s, src, g, NSP,
-                (const ansx_enc_entry*)nullptr, (const u32*)c->tab32.p, lds_stride, blk, (u8*)c->scratch.p,
-                (u64)scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, first);
-        else
-            LAUNCH(c, first ? "k_encode_rest" : "k_encode", (k_encode<1, false>), enc_grid, 64 * wpw, wpw * enc_lds, s, src, g, NSP,
-                (const ansx_enc_entry*)nullptr, (const u32*)c->tab32.p, lds_stride, blk, (u8*)c->scratch.p,
-                (u64)scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, first);
+        const auto kern = pow2 ? k_encode<1, true> : k_encode<1, false>;
+        if (wpw * enc_lds > 48 * 1024)
+            HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wpw * enc_lds)));
+        LAUNCH(c, first ? "k_encode_rest" : "k_encode", kern, enc_grid, 64 * wpw, wpw * enc_lds, s, src, g, NSP,
+            (const ansx_enc_entry*)nullptr, (const u32*)c->tab32.p, lds_stride, blk, (u8*)c->scratch.p,
+            (u64)scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, first);
         return ANSX_OK;
     }
     // ---- alphabets too large for LDS: compact table entries from HBM, same branch-free f64 step
@@ -529,20 +502,78 @@ static int launch_f64_encoder(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u32
     return ANSX_OK;
 }
 
-// ns_cap == 0: discovery mode -- the largest alphabet / frame of the call are read back between the
-// model kernels and the encoder launch (one host round trip per candidate batch).
-// ns_cap != 0: optimistic mode -- the caller has seen this geometry before (alphabet hint): the first
-// candidate batch is assumed to settle every block, frames are assumed to stay within 2^16 and alphabets
-// within ns_cap, so everything is launched back to back; the assumptions are checked on the words that
-// come back with the output size anyway, and a miss returns ANSX_RETRY_GENERAL.
-int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t cap,
-    size_t* out_bytes, hipStream_t s, u32* seen_ns, u32 ns_cap)
+// One attempt of an encode call: what it may assume.  The retry ladder (encode_dev -> encode_dev_once -> resolve_near)
+// builds the attempts; inside an attempt the value is constant, and no function of the encode path learns a per-call
+// fact from the context.
+struct EncodeAttempt {
+    // ns_cap == 0: discovery -- the largest alphabet / frame of the call are read back between the model kernels and
+    // the encoder launch (one host round trip per candidate batch).
+    // ns_cap != 0: optimistic -- the caller has seen this geometry before (alphabet hint): the first candidate batch is
+    // assumed to settle every block, frames are assumed to stay within 2^16 and alphabets within ns_cap, so everything
+    // is launched back to back; the assumptions are checked on the words that come back with the output size anyway,
+    // and a miss returns ANSX_RETRY_GENERAL.  nt, rf_slots and pa_distinct are nonzero in optimistic attempts only.
+    u32 ns_cap = 0;
+    u32 nt = 0;                  // candidates per block of the fast model path (4 .. 8), 0 = the exact model kernels
+    u32 rf_slots = 0;            // ANSrfold: optimistic hash-table size (rf_opt_slots), 0 = the full-size table
+    u32 pa_distinct = 0;         // compaction layer: the geometry's distinct-value hint (sizes k_pa_remap2), 0 = full size
+    bool int_sparse = false;     // plain ANSint modelled in rank space (ansx_intsparse.h)
+    bool sp_full_lds = false;    // ... and its prelude writer runs with the full-size LDS arrays (a block's code outgrew the hint-sized ones)
+    const u32* force = nullptr;  // per-block frames decided by the host (resolve_near), device array
+};
+// ... and what it found.  Every attempt starts it afresh, except sp_repeated, which only ever becomes true: a ladder
+// that hands one outcome to all its attempts reads there whether any of them, at any depth, was repeated.
+struct EncodeOutcome {
+    u32 flags[16] = {};        // the words read back from `misc` (gflags, result): a copy, the pinned page is free again
+    const u32* src = nullptr;  // the ints the model kernels saw (the input, or its remapped form)
+    bool used_fast = false;    // the model came from k_candidates / k_model_finish
+    bool used_pc = false;      // the producer / consumer encoder kernel ran
+    bool sp_repeated = false;  // a rank-space attempt was repeated with the full-size prelude writer
+};
+
+// What the phases of one attempt share: the call's arguments and the workspace pointers encode_begin carves.
+struct EncodeWs {
+    const Plan* P;  // (the first seven: set by the attempt's driver, the rest start as zero)
+    const EncodeAttempt* a;
+    EncodeOutcome* out;
+    const u32* d_in;
+    u8* d_out;
+    size_t cap;
+    hipStream_t s;
+    u64 scr_stride;                 // bytes per block of the stream scratch
+    u32 *gflags, *hist, *enc_sizes;
+    u64 *result, *boff_ws;
+    unsigned long long* enc_gsums;  // stream sizes summed per 64 blocks
+    ansx_blk* blk;
+    u32* hints;                     // the container's parse hints, or null
+    const uint2* geo;               // tabulated tree nodes of the prelude's interpolative code, or null
+    double* hterm;                  // entropy terms through HBM (model_prepare), or null
+    const u32 *src, *mostfreq;      // encode_remap: the ints the model kernels and the encoder read; ANSrfold's selection
+    u32 max_logM, max_ns;           // the model phase: largest frame / alphabet the later launches are sized for
+};
+
+u64 scratch_stride(const ansx_geo& g) { return rup(block_bound(g.kind, g.f, g.block_ints, g.pa != 0) + 16, 256); }
+
+// the flag words (and the result behind them), read back into the attempt's outcome: a host wait
+int read_flags(ansx_ctx* c, const EncodeWs& W, u32 words)
 {
-    const bool optimistic = ns_cap != 0;
+    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->misc.p, (size_t)words * 4, hipMemcpyDeviceToHost, W.s));
+    HIPCHK(c, hipStreamSynchronize(W.s));
+    memcpy(W.out->flags, c->h_pin, (size_t)words * 4);
+    return ANSX_OK;
+}
+
+// Phase 1: the workspace (grown on demand, kept by the context), the one-time tables, and k_begin_encode.
+int encode_begin(ansx_ctx* c, EncodeWs& W)
+{
+    const Plan& P = *W.P;
     const ansx_geo& g = P.g;
-    const u32 NB = g.nblocks, NSP = P.NSP, f = g.f;
-    const size_t scr_stride = rup(block_bound(g.kind, f, g.block_ints, g.pa != 0) + 16, 256);
-    if (!P.plain && cap < P.lay.payload_off) return ANSX_ERR_CAPACITY;
+    const u32 NB = g.nblocks, NSP = P.NSP;
+    hipStream_t s = W.s;
+    const bool sp = W.out->sp_repeated;
+    *W.out = EncodeOutcome();
+    W.out->sp_repeated = sp;
+    W.scr_stride = scratch_stride(g);
+    if (!P.plain && W.cap < P.lay.payload_off) return ANSX_ERR_CAPACITY;
     int rc;
     if ((rc = ensure(c, c->hist, (size_t)NB * NSP * 4))) return rc;
     if ((rc = ensure(c, c->sortF, (size_t)NB * NSP * 4))) return rc;
@@ -555,69 +586,76 @@ int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_
         if ((rc = ensure(c, c->log2lut, (size_t)65536 * sizeof(ansx_log2_ent)))) return rc;
         LAUNCH(c, "k_build_log2_lut", k_build_log2_lut, 256, 256, 0, s, (ansx_log2_ent*)c->log2lut.p);
     }
-    const uint2* geo = nullptr;
     if (NSP <= 4096) {  // tree nodes of the prelude's interpolative code for every alphabet size up to NSP, once per context
         DevBuf& gb = c->geo[NSP];
         if (!gb.p) {
             if ((rc = ensure(c, gb, ((size_t)NSP * (NSP + 1) / 2 + 8) * 8))) return rc;
             LAUNCH(c, "k_build_interp_geo", k_build_interp_geo, NSP, 256, 0, s, NSP, (uint2*)gb.p);
         }
-        geo = (const uint2*)gb.p;
+        W.geo = (const uint2*)gb.p;
     }
     if ((rc = ensure(c, c->blk, (size_t)NB * sizeof(ansx_blk)))) return rc;
     if ((rc = ensure(c, c->table, (size_t)NB * NSP * sizeof(ansx_enc_entry)))) return rc;
     if ((rc = ensure(c, c->tab32, (size_t)NB * NSP * 4))) return rc;
-    if ((rc = ensure(c, c->scratch, (size_t)NB * scr_stride))) return rc;
+    if ((rc = ensure(c, c->scratch, (size_t)NB * W.scr_stride))) return rc;
     if ((rc = ensure(c, c->misc, 64 + 8 * ((size_t)NB + 1)))) return rc;
     // per-block stream sizes + their sums per 64 blocks, published by the encoder for k_assemble
     const size_t ngroups = (((size_t)NB + 63) / 64 + 1) & ~(size_t)1;  // (an even count: the sums end on a 16-byte boundary)
     if ((rc = ensure(c, c->sizes, ngroups * 8 + (size_t)NB * 4))) return rc;
-    unsigned long long* enc_gsums = (unsigned long long*)c->sizes.p;
-    u32* enc_sizes = (u32*)((u8*)c->sizes.p + ngroups * 8);
-    u32* gflags = (u32*)c->misc.p;
-    u64* result = (u64*)((u8*)c->misc.p + 16);
-    u64* boff_ws = (u64*)((u8*)c->misc.p + 64);
-    ansx_blk* blk = (ansx_blk*)c->blk.p;
-    u32* hist = (u32*)c->hist.p;
+    W.enc_gsums = (unsigned long long*)c->sizes.p;
+    W.enc_sizes = (u32*)((u8*)c->sizes.p + ngroups * 8);
+    W.gflags = (u32*)c->misc.p;
+    W.result = (u64*)((u8*)c->misc.p + 16);
+    W.boff_ws = (u64*)((u8*)c->misc.p + 64);
+    W.blk = (ansx_blk*)c->blk.p;
+    W.hist = (u32*)c->hist.p;
+    // (plain ANSint: no parse hints -- its decoder walks the value-range prelude sparsely, and the container must not depend on
+    // which of the two models, dense or rank space, wrote it)
+    W.hints = (P.plain || (g.kind == ANSX_INT && !g.pa)) ? nullptr : (u32*)(W.d_out + P.lay.hint_off);
+    W.src = W.d_in;
 
-    {
-        // flag words, size sums, block metadata, and the container's header / index / restart-point area: unused
-        // slots (short last block) and alignment padding are defined to be zero, so equal inputs give
-        // byte-identical containers
-        static_assert(sizeof(ansx_blk) % 16 == 0, "zeroed 16 bytes at a time");
-        ansx_zero4 Z;
-        Z.p[0] = (uint4*)c->misc.p, Z.n16[0] = 4;
-        Z.p[1] = (uint4*)enc_gsums, Z.n16[1] = ngroups / 2;
-        Z.p[2] = (uint4*)blk, Z.n16[2] = (u64)NB * (sizeof(ansx_blk) / 16);
-        Z.p[3] = (uint4*)d_out, Z.n16[3] = P.plain ? 0 : (u64)P.lay.payload_off / 16;
-        const u64 tot = Z.n16[0] + Z.n16[1] + Z.n16[2] + Z.n16[3];
-        LAUNCH(c, "k_begin_encode", k_begin_encode, (u32)std::min<u64>(2048, (tot + 255) / 256), 256, 0, s, Z);
-    }
+    // flag words, size sums, block metadata, and the container's header / index / restart-point area: unused slots (short
+    // last block) and alignment padding are defined to be zero, so equal inputs give byte-identical containers
+    static_assert(sizeof(ansx_blk) % 16 == 0, "zeroed 16 bytes at a time");
+    ansx_zero4 Z;
+    Z.p[0] = (uint4*)c->misc.p, Z.n16[0] = 4;
+    Z.p[1] = (uint4*)W.enc_gsums, Z.n16[1] = ngroups / 2;
+    Z.p[2] = (uint4*)W.blk, Z.n16[2] = (u64)NB * (sizeof(ansx_blk) / 16);
+    Z.p[3] = (uint4*)W.d_out, Z.n16[3] = P.plain ? 0 : (u64)P.lay.payload_off / 16;
+    const u64 tot = Z.n16[0] + Z.n16[1] + Z.n16[2] + Z.n16[3];
+    LAUNCH(c, "k_begin_encode", k_begin_encode, (u32)std::min<u64>(2048, (tot + 255) / 256), 256, 0, s, Z);
+    return ensure(c, c->nearlist, (size_t)ANSX_NEAR_CAP * 4);
+}
 
-    if ((rc = ensure(c, c->nearlist, (size_t)ANSX_NEAR_CAP * 4))) return rc;
-    const u32* src = d_in;
-    const u32* mostfreq = nullptr;
+// Phase 2, the remap front: ANSrfold's most-frequent-value remap, the compaction layer, rank-space ANSint.  Leaves the
+// ints the codec runs on in W.src (W.d_in itself where no front applies).
+int encode_remap(ansx_ctx* c, EncodeWs& W)
+{
+    const ansx_geo& g = W.P->g;
+    const EncodeAttempt& a = *W.a;
+    const u32 NB = g.nblocks;
+    hipStream_t s = W.s;
+    int rc;
     if (g.kind == ANSX_RFOLD) {
-        const u32 T = fold_T(f);
         if ((rc = ensure(c, c->mapped, (size_t)g.n * 4))) return rc;
-        if ((rc = ensure(c, c->mostfreq, (size_t)NB * T * 4))) return rc;
-        rc = rfold_remap(c, P.g, d_in, (u32*)c->mapped.p, (u32*)c->mostfreq.p, blk, gflags, s, optimistic ? c->cur_rf_slots : 0u);
-        if (rc) return rc;
-        src = (const u32*)c->mapped.p;
-        mostfreq = (const u32*)c->mostfreq.p;
+        if ((rc = ensure(c, c->mostfreq, (size_t)NB * fold_T(g.f) * 4))) return rc;
+        if ((rc = rfold_remap(c, g, W.d_in, (u32*)c->mapped.p, (u32*)c->mostfreq.p, W.blk, W.gflags, s, a.rf_slots))) return rc;
+        W.src = (const u32*)c->mapped.p;
+        W.mostfreq = (const u32*)c->mostfreq.p;
     }
-
-    if (g.pa) {
-        // per-block alphabet compaction (src/pseudo_adaptive.cpp:85-130): alphabet header into the block's
-        // scratch slot, the codec then runs on the 1-based ranks
+    if (g.pa || a.int_sparse) {
         if ((rc = ensure(c, c->mapped, (size_t)NB * g.block_ints * 4))) return rc;
         if ((rc = ensure(c, c->pa_alpha, (size_t)NB * g.block_ints * 4))) return rc;
-        // sizes from the geometry's distinct-value hint (optimistic calls only): hash set 2.5 x, value list the next
+        W.src = (const u32*)c->mapped.p;
+    }
+    if (g.pa) {
+        // per-block alphabet compaction (src/pseudo_adaptive.cpp:85-130): alphabet header into the block's scratch slot, the
+        // codec then runs on the 1-based ranks.  Sizes from the geometry's distinct-value hint (optimistic calls only): hash set 2.5 x, value list the next
         // power of two above 1.25 x; both workgroups of a CU must fit its LDS
         u32 pa_slots = ANSX_PA_SLOTS, pa_uqcap = ANSX_PA_MAX_BLOCK;
         bool pa_small = false;
-        if (optimistic && c->cur_pa_distinct != 0) {
-            const u32 d = c->cur_pa_distinct;
+        if (a.pa_distinct != 0) {
+            const u32 d = a.pa_distinct;
             const u32 sl = (2 * d + d / 2 + 64 + 255) & ~255u;
             u32 uc = 1024;
             while (uc < d + d / 4 + 16) uc <<= 1;
@@ -626,405 +664,438 @@ int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_
         const size_t lds1 = ((size_t)pa_slots + pa_uqcap) * 4;
         if (pa_small) {
             HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-            LAUNCH(c, "k_pa_remap", k_pa_remap2, NB, 1024, lds1, s, d_in, g, pa_slots, pa_uqcap, (u32*)c->mapped.p,
-                (u32*)c->pa_alpha.p, blk, gflags, 1u << 30);
+            LAUNCH(c, "k_pa_remap", k_pa_remap2, NB, 1024, lds1, s, W.d_in, g, pa_slots, pa_uqcap, (u32*)c->mapped.p,
+                (u32*)c->pa_alpha.p, W.blk, W.gflags, 1u << 30);
         } else {
             HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-            LAUNCH(c, "k_pa_remap", k_pa_remap, NB, 1024, lds1, s, d_in, g, pa_slots, pa_uqcap, (u32*)c->mapped.p,
-                (u32*)c->pa_alpha.p, blk, gflags, 1u << 30, 0u);
+            LAUNCH(c, "k_pa_remap", k_pa_remap, NB, 1024, lds1, s, W.d_in, g, pa_slots, pa_uqcap, (u32*)c->mapped.p,
+                (u32*)c->pa_alpha.p, W.blk, W.gflags, 1u << 30, 0u);
         }
         const size_t lds2 = pa_small ? ((size_t)3 * pa_uqcap + 32) * 4 : ((size_t)2 * ANSX_PA_MAX_BLOCK + 16) * 4;
         HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_header, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        LAUNCH(c, "k_pa_header", k_pa_header, NB, 256, lds2, s, g, (const u32*)c->pa_alpha.p, blk, (u8*)c->scratch.p,
-            (u64)scr_stride, pa_small ? pa_uqcap : (u32)ANSX_PA_MAX_BLOCK);
-        src = (const u32*)c->mapped.p;
+        LAUNCH(c, "k_pa_header", k_pa_header, NB, 256, lds2, s, g, (const u32*)c->pa_alpha.p, W.blk, (u8*)c->scratch.p,
+            W.scr_stride, pa_small ? pa_uqcap : (u32)ANSX_PA_MAX_BLOCK);
     }
-    const bool sparse = c->cur_int_sparse;
-    if (sparse) {
+    if (a.int_sparse) {
         // plain ANSint on values beyond the dense model (ansx_intsparse.h): the codec runs on every block's 0-based ranks
-        if ((rc = ensure(c, c->mapped, (size_t)NB * g.block_ints * 4))) return rc;
-        if ((rc = ensure(c, c->pa_alpha, (size_t)NB * g.block_ints * 4))) return rc;
         const size_t lds1 = ((size_t)ANSX_PA_SLOTS + ANSX_PA_MAX_BLOCK) * 4;
         HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        LAUNCH(c, "k_pa_remap", k_pa_remap, NB, 1024, lds1, s, d_in, g, (u32)ANSX_PA_SLOTS, (u32)ANSX_PA_MAX_BLOCK, (u32*)c->mapped.p,
-            (u32*)c->pa_alpha.p, blk, gflags, (u32)ANSX_SP_VALUE_LIMIT, 1u);
-        src = (const u32*)c->mapped.p;
+        LAUNCH(c, "k_pa_remap", k_pa_remap, NB, 1024, lds1, s, W.d_in, g, (u32)ANSX_PA_SLOTS, (u32)ANSX_PA_MAX_BLOCK, (u32*)c->mapped.p,
+            (u32*)c->pa_alpha.p, W.blk, W.gflags, (u32)ANSX_SP_VALUE_LIMIT, 1u);
     }
-    c->cur_src = src;
-    // K1
-    u32 chunk = g.block_ints < 16384u ? g.block_ints : 16384u;
-    if (chunk & 3u) chunk = (chunk + 3u) & ~3u;
-    const u32 cpb = (g.block_ints + chunk - 1) / chunk;
-    if (cpb > 1) HIPCHK(c, hipMemsetAsync(hist, 0, (size_t)NB * NSP * 4, s));
-    // blocks that fit one histogram workgroup (the normal case) get their entropy terms from K1
-    // and the in-order sum from K2b; longer blocks keep both in K2a
-    const bool h_deferred = (cpb == 1);
-    // entropy terms are evaluated by the histogram kernel when it sees whole blocks; alphabets up
-    // to 2048 slots are also summed there (terms in LDS), larger ones through HBM in K2b
-    const bool h_in_hist = h_deferred && NSP <= 2048;
-    // Fast model path (ansx_fastmodel.h): geometries seen before, whole-block histograms, 16-bit frequencies,
-    // compact tables; every assumption is checked on the device and a miss repeats the call on the exact path.
-    const u32 NT = optimistic ? c->cur_nt : 0u;
+    W.out->src = W.src;
+    return ANSX_OK;
+}
+
+// Launch shapes of the model kernels: a pure function of the geometry, the attempt and the debug switches.
+struct ModelShape {
+    u32 chunk, cpb;    // K1: ints per histogram workgroup, workgroups per block
+    bool h_deferred;   // blocks that fit one histogram workgroup (the normal case): entropy terms from K1, in-order sum from K2b (else both in K2a)
+    bool h_in_hist;    // ... and alphabets up to 2048 slots are also summed in K1 (terms in LDS), larger ones through HBM in K2b
+    bool fast;         // fast model path (ansx_fastmodel.h): k_candidates / k_model_finish instead of the candidate batches
+    bool hist_packed;  // f >= 4: 16-bit counters, two per LDS word (a chunk holds at most 16384 values): half the LDS, twice the workgroups per CU
+    size_t hist_lds;
+    u32 nbig_cap, sort_cap;  // K2: "big" symbols have freq >= ANSX_VMAX; length of the staged row
+    bool sort16, sort_staged;
+    size_t k2a_lds;
+    u32 always16;      // the 16-byte table entries have a certain consumer before the frames are known
+    // fast model path: lanes of k_candidates, LDS of k_model_finish
+    u32 bpw, fcap;
+    size_t fin_lds;
+};
+ModelShape model_shape(const ansx_ctx* c, const EncodeWs& W)
+{
+    const ansx_geo& g = W.P->g;
+    const EncodeAttempt& a = *W.a;
+    const u32 NSP = W.P->NSP;
+    ModelShape M;
+    M.chunk = g.block_ints < 16384u ? g.block_ints : 16384u;
+    if (M.chunk & 3u) M.chunk = (M.chunk + 3u) & ~3u;
+    M.cpb = (g.block_ints + M.chunk - 1) / M.chunk;
+    M.h_deferred = (M.cpb == 1);
+    M.h_in_hist = M.h_deferred && NSP <= 2048;
+    // Fast model path: geometries seen before, whole-block histograms, 16-bit frequencies, compact tables; every
+    // assumption is checked on the device and a miss repeats the call on the exact path.
     // (alphabets above 4096 slots -- f = 4, 5 -- take the generic form of k_model_finish as long as its three LDS arrays,
     // sized from the alphabet hint, fit a CU; ANSint has no u16 rule and 32-bit frequencies: exact path)
-    const u32 fcap_probe = std::min<u32>(NSP, std::max<u32>(64u, (ns_cap + 15u) & ~15u));
-    const bool fast = NT != 0 && !g.pa && h_deferred && g.block_ints <= 65535u && NSP <= 16384 && g.kind != ANSX_INT
-        && (NSP <= 4096 || (size_t)fcap_probe * 8 + 64 <= 150 * 1024) && !c->dbg.table16_fixup
-        && !c->dbg.encode_gtab16 && (u64)scr_stride * 16 < 0x7FFFFF00ull;
-    c->used_fast = fast;
-    if (fast && NSP > 4096 && !c->dbg.no_big_geo) {
-        // k_model_finish<0>: a 14-level tree descent per item was two thirds of its prelude writer; the nodes of every alphabet
-        // size up to the hint come from a table here too (built once per context, rebuilt when the hint grows)
-        if (c->geo_big_cap < fcap_probe) {
-            if ((rc = ensure(c, c->geo_big, ((size_t)fcap_probe * (fcap_probe + 1) / 2 + 8) * 8))) return rc;
-            LAUNCH(c, "k_build_interp_geo", k_build_interp_geo, fcap_probe, 256, 0, s, fcap_probe, (uint2*)c->geo_big.p);
-            c->geo_big_cap = fcap_probe;
-        }
-        geo = (const uint2*)c->geo_big.p;
-    }
-    if (fast) {
-        if ((rc = ensure(c, c->pairs, (size_t)NB * NSP * 8))) return rc;
-        if (!c->lg2i.p) {  // log2 of the integers below 2^16, once per context (512 KB)
-            if ((rc = ensure(c, c->lg2i, (size_t)65536 * 8))) return rc;
-            LAUNCH(c, "k_build_log2i_lut", k_build_log2i_lut, 256, 256, 0, s, (double*)c->lg2i.p);
-        }
-    }
-    double* hterm = nullptr;
-    if (h_deferred && !h_in_hist && !fast) {
-        if ((rc = ensure(c, c->hterm, (size_t)NB * NSP * 8))) return rc;
-        hterm = (double*)c->hterm.p;
-    }
+    M.fcap = std::min<u32>(NSP, std::max<u32>(64u, (a.ns_cap + 15u) & ~15u));
+    M.fast = a.nt != 0 && !g.pa && M.h_deferred && g.block_ints <= 65535u && NSP <= 16384 && g.kind != ANSX_INT
+        && (NSP <= 4096 || (size_t)M.fcap * 8 + 64 <= 150 * 1024) && !c->dbg.table16_fixup
+        && !c->dbg.encode_gtab16 && W.scr_stride * 16 < 0x7FFFFF00ull;
+    M.hist_packed = NSP >= 8192u;
     // (fast path: H is a tree sum in registers, no LDS row of terms)
-    const size_t hist_lds = !h_in_hist ? (size_t)NSP * 4 : (size_t)4 * (NSP + ANSX_HCOPY_PAD) * 4 + (fast ? 0 : (size_t)NSP * 8 + 80);
-    // K2.  "big" symbols have freq >= ANSX_VMAX, so a block holds at most block_ints/ANSX_VMAX
-    const u32 nbig_cap = (u32)std::min<size_t>(NSP, (size_t)g.block_ints / ANSX_VMAX + 2);
+    M.hist_lds = M.hist_packed ? (size_t)NSP * 2
+        : !M.h_in_hist       ? (size_t)NSP * 4
+                             : (size_t)4 * (NSP + ANSX_HCOPY_PAD) * 4 + (M.fast ? 0 : (size_t)NSP * 8 + 80);
+    M.nbig_cap = (u32)std::min<size_t>(NSP, (size_t)g.block_ints / ANSX_VMAX + 2);
     // (optimistic calls with whole-block histograms: the staged row is as long as the alphabet hint, see the kernel)
-    const u32 sort_cap = (optimistic && h_deferred) ? std::min<u32>(NSP, std::max<u32>(64u, (ns_cap + 7u) & ~7u)) : NSP;
-    const bool sort16 = g.block_ints <= 65535u;  // (a count fits 16 bits: half the staged row)
-    size_t k2a_lds = (size_t)nbig_cap * 8 + (size_t)sort_cap * (sort16 ? 2 : 4) + (h_deferred ? 0 : 512 * 8);
-    const bool sort_staged = k2a_lds <= 150 * 1024;  // (f = 6, 7 with 32-bit counts: the row stays in HBM)
-    if (!sort_staged) k2a_lds = (size_t)nbig_cap * 8 + (h_deferred ? 0 : 512 * 8);
-    // Frame sizes M0*2^t are tried ANSX_ATTEMPTS at a time.  Almost every block settles in the
-    // first batch; the count of undecided blocks comes back with the words the encoder launch
-    // needs anyway (largest alphabet / frame), so further batches are launched only on demand.
+    M.sort_cap = (a.ns_cap != 0 && M.h_deferred) ? std::min<u32>(NSP, std::max<u32>(64u, (a.ns_cap + 7u) & ~7u)) : NSP;
+    M.sort16 = g.block_ints <= 65535u;  // (a count fits 16 bits: half the staged row)
+    M.k2a_lds = (size_t)M.nbig_cap * 8 + (size_t)M.sort_cap * (M.sort16 ? 2 : 4) + (M.h_deferred ? 0 : 512 * 8);
+    M.sort_staged = M.k2a_lds <= 150 * 1024;  // (f = 6, 7 with 32-bit counts: the row stays in HBM)
+    if (!M.sort_staged) M.k2a_lds = (size_t)M.nbig_cap * 8 + (M.h_deferred ? 0 : 512 * 8);
+    // consumers of the 16-byte table entries that are certain before the frames are known: the generic prelude writer (alphabets above
+    // 4096 slots) and the integer-state encoder (forced, or scratch slots too far apart for the f64 encoder's 31-bit buffer offsets)
+    M.always16 = (!c->dbg.table16_fixup && (NSP > 4096 || W.scr_stride * 16 >= 0x7FFFFF00ull || c->dbg.encode_gtab16)) ? 1u : 0u;
+    M.bpw = M.fast ? 64u / a.nt : 1u;
+    M.fin_lds = (size_t)M.fcap * (NSP > 4096 ? 8 : 12) + 64;  // (above 4096 slots: inc[] in the block's histogram row, two LDS arrays)
+    return M;
+}
+
+// ---- one dispatch per templated model kernel: the attribute call and the launch name the instantiation through it
+using hist_kernel_t = decltype(&k_fold_hist<false>);
+using sort_kernel_t = decltype(&k_sort_entropy<u16>);
+using cand_kernel_t = decltype(&k_candidates<4, 1>);
+using fin_kernel_t = decltype(&k_model_finish<4, 8>);
+hist_kernel_t hist_kernel(const ModelShape& M) { return M.hist_packed ? k_fold_hist<true> : k_fold_hist<false>; }
+sort_kernel_t sort_kernel(const ModelShape& M)
+{
+    return !M.sort_staged ? k_sort_entropy<u32, false> : (M.sort16 ? k_sort_entropy<u16> : k_sort_entropy<u32>);
+}
+cand_kernel_t cand_kernel(u32 NT, u32 nch)
+{
+    switch (NT) {
+    case 4: return nch == 1 ? k_candidates<4, 1> : k_candidates<4, 2>;
+    case 5: return nch == 1 ? k_candidates<5, 1> : k_candidates<5, 2>;
+    case 6: return nch == 1 ? k_candidates<6, 1> : k_candidates<6, 2>;
+    case 7: return nch == 1 ? k_candidates<7, 1> : k_candidates<7, 2>;
+    default: return nch == 1 ? k_candidates<8, 1> : k_candidates<8, 2>;
+    }
+}
+struct FinKernel { fin_kernel_t kern; u32 threads; };  // (its NTH is also the launch's workgroup size)
+FinKernel fin_kernel(const ansx_ctx* c, u32 NSP, u32 NT)
+{
+    // one wave per block (16 slots per lane, every candidate in every lane, no workgroup barriers): four times the blocks in flight
+    if (NSP <= 1024 && c->dbg.fin_one_wave) return { NT <= 5 ? k_model_finish<16, 5, 64> : k_model_finish<16, 8, 64>, 64 };
+    if (NSP <= 1024) return { k_model_finish<4, 8, 256>, 256 };  // (wave-per-candidate form: NTC is not used)
+    if (NSP > 4096) return { NT <= 5 ? k_model_finish<0, 5, 256> : k_model_finish<0, 8, 256>, 256 };
+    return { NT <= 5 ? k_model_finish<16, 5, 256> : k_model_finish<16, 8, 256>, 256 };
+}
+template <class K>
+int raise_lds(ansx_ctx* c, K kern, size_t lds)
+{
+    HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return ANSX_OK;
+}
+// chains per lane of k_candidates: one while that leaves at most one wave per SIMD, else two (see the kernel); per launch, by its blocks
+u32 cand_chains(const ansx_ctx* c, const ModelShape& M, u32 nblk)
+{
+    return c->dbg.cand_chains ? c->dbg.cand_chains : (((nblk + M.bpw - 1) / M.bpw <= 4u * c->num_cus) ? 1u : 2u);
+}
+size_t cand_lds(const ModelShape& M, u32 nch) { return (size_t)ANSX_CAND_WAVES * nch * M.bpw * ANSX_CAND_ROW * 16; }
+
+// ---- the launches of the model phase for the blocks [b0, be) on stream st
+// K1
+int launch_hist(ansx_ctx* c, const EncodeWs& W, const ModelShape& M, hipStream_t st, u32 b0, u32 be)
+{
+    const ansx_geo& g = W.P->g;
+    const u32 NSP = W.P->NSP;
+    // (sum_mode bit 1: on the fast model path H is the workgroup's tree sum and there is no hterm array to write)
+    LAUNCH(c, "k_fold_hist", hist_kernel(M), (size_t)(be - b0) * M.cpb, 256, M.hist_lds, st, W.src, g, M.chunk, M.cpb, NSP, W.hist, W.hterm,
+        (M.h_in_hist ? 1u : 0u) | (M.fast ? 2u : 0u), W.blk, W.gflags, (g.kind == ANSX_INT && !g.pa) ? NSP : (1u << 30), b0, be);
+    return ANSX_OK;
+}
+// K2
+int launch_sort(ansx_ctx* c, const EncodeWs& W, const ModelShape& M, hipStream_t st, u32 b0, u32 be)
+{
+    LAUNCH(c, "k_sort_entropy", sort_kernel(M), be - b0, 64, M.k2a_lds, st, W.P->g, W.P->NSP, M.nbig_cap, M.h_deferred ? 1u : 0u, W.hist,
+        (u32*)c->sortF.p, (u16*)c->sortSym.p, W.blk, M.sort_cap, M.fast ? (uint2*)c->pairs.p : (uint2*)nullptr, W.gflags, b0, be);
+    return ANSX_OK;
+}
+// K2 and the two kernels of the fast model path behind it
+int launch_fast_model(ansx_ctx* c, const EncodeWs& W, const ModelShape& M, hipStream_t st, u32 b0, u32 be)
+{
+    const ansx_geo& g = W.P->g;
+    const u32 NSP = W.P->NSP, NT = W.a->nt;
+    int rc;
+    if ((rc = launch_sort(c, W, M, st, b0, be))) return rc;
+    const u32 nch = cand_chains(c, M, be - b0);
+    const u32 cwaves = (be - b0 + nch * M.bpw - 1) / (nch * M.bpw);
+    LAUNCH(c, "k_candidates", cand_kernel(NT, nch), (cwaves + ANSX_CAND_WAVES - 1) / ANSX_CAND_WAVES, 64 * ANSX_CAND_WAVES, cand_lds(M, nch), st,
+        g, NSP, (const uint2*)c->pairs.p, (const ansx_blk*)W.blk, (uint4*)c->attS.p, (u32*)c->attMeta.p, b0, be);
+    const FinKernel fin = fin_kernel(c, NSP, NT);
+    LAUNCH(c, "k_model_finish", fin.kern, be - b0, fin.threads, M.fin_lds, st, g, NSP, NT, (const uint2*)c->pairs.p, (const uint4*)c->attS.p,
+        (const u32*)c->attMeta.p, W.blk, (u32*)c->tab32.p, (u8*)c->scratch.p, W.scr_stride, W.mostfreq, W.hints, W.gflags, M.fcap,
+        c->dbg.fast_guard, (const double*)c->lg2i.p, W.geo, NSP > 4096 ? W.hist : (u32*)nullptr, b0, be);
+    return ANSX_OK;
+}
+
+// Phase 3a: what K1 and K2 need whichever model form follows
+int model_prepare(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
+{
+    const size_t NB = W.P->g.nblocks, NSP = W.P->NSP;
+    int rc;
+    if (M.cpb > 1) HIPCHK(c, hipMemsetAsync(W.hist, 0, NB * NSP * 4, W.s));
+    if (M.h_deferred && !M.h_in_hist && !M.fast) {
+        if ((rc = ensure(c, c->hterm, NB * NSP * 8))) return rc;
+        W.hterm = (double*)c->hterm.p;
+    }
+    if (M.hist_lds > 48 * 1024 && (rc = raise_lds(c, hist_kernel(M), M.hist_lds))) return rc;
+    if (M.k2a_lds > 32 * 1024 && (rc = raise_lds(c, sort_kernel(M), M.k2a_lds))) return rc;
+    return ANSX_OK;
+}
+
+// Phase 3b, the model in its exact form: K1, K2, then frame sizes M0 * 2^t tried ANSX_ATTEMPTS at a time.  Almost every
+// block settles in the first batch; the count of undecided blocks comes back with the words the encoder launch
+// needs anyway (largest alphabet / frame), so further batches are launched only on demand.
+int model_exact(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
+{
+    const ansx_geo& g = W.P->g;
+    const u32 NB = g.nblocks, NSP = W.P->NSP;
     const u32 nbatch = 24 / ANSX_ATTEMPTS;  // t < 24 (t <= 16 suffices)
-    u32 max_logM = 0, max_ns = 0;
-    // consumers of the 16-byte table entries that are certain before the frames are known: the
-    // generic prelude writer (alphabets above 4096 slots) and the integer-state encoder (forced, or
-    // scratch slots too far apart for the f64 encoder's 31-bit buffer offsets)
-    const bool test_fixup = c->dbg.table16_fixup;  // tests: integer-state encoder fed by k_table16_from32
-    const u32 always16 = (!test_fixup && (NSP > 4096 || (u64)scr_stride * 16 >= 0x7FFFFF00ull || c->dbg.encode_gtab16)) ? 1u : 0u;
-    // (plain ANSint: no parse hints -- its decoder walks the value-range prelude sparsely, and the container must not depend on
-    // which of the two models, dense or rank space, wrote it)
-    u32* hints = (P.plain || (g.kind == ANSX_INT && !g.pa)) ? nullptr : (u32*)(d_out + P.lay.hint_off);
-    // fast model path: lanes / chains of k_candidates, LDS of k_model_finish
-    const u32 bpw = fast ? 64u / NT : 1u;
-    // chains per lane: one while that leaves at most one wave per SIMD, else two (see k_candidates); per launch, by its blocks
-    auto cand_chains = [&](u32 nblk) -> u32 {
-        return c->dbg.cand_chains ? c->dbg.cand_chains : (((nblk + bpw - 1) / bpw <= 4u * c->num_cus) ? 1u : 2u);
-    };
-    const u32 fcap = std::min<u32>(NSP, std::max<u32>(64u, (ns_cap + 15u) & ~15u));
-    const bool fin_generic = NSP > 4096;  // (loop-based form: inc[] in the block's histogram row, two LDS arrays)
-    const size_t fl = (size_t)fcap * (fin_generic ? 8 : 12) + 64;
-
-    // Block-range pipeline of the fast model path: the call's blocks in `nranges` contiguous ranges,
-    // the histograms one after the other on the caller's stream, and k_sort_entropy -> k_candidates -> k_model_finish of
-    // every range but the last on one of the context's two side streams (alternating) behind that range's histogram -- a
-    // memory-bound kernel beside a VALU-bound one beside a latency chain.  The ranges meet in no workspace byte (every
-    // array is indexed by the absolute block number) and in `gflags` only through order-independent atomics.  Everything
-    // joins on the caller's stream in front of the encoder.  nranges == 0: one launch of each kernel over all blocks on
-    // the caller's stream.
-    u32 range_blocks = NB, nranges = 0;
-    if (fast && !c->profile && c->dbg.model_pipeline != ANSX_PIPE_NEVER) {
-        // (profile mode: the event pairs of LAUNCH would time overlapped kernels -- serial there)
-        const int mode = c->dbg.model_pipeline;
-        u32 want = mode > 0 ? (u32)mode : ((mode == ANSX_PIPE_ALWAYS || (NB >= ANSX_PIPE_MIN_BLOCKS && g.n >= ANSX_PIPE_MIN_INTS)) ? ANSX_PIPE_RANGES : 0u);
-        if (want) {
-            // (a captured graph with parallel branches: the call stays one chain of launches under capture)
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) want = 0;
-        }
-        if (want) {
-            range_blocks = (u32)rup(((size_t)NB + want - 1) / want, 64);  // range boundaries: multiples of 64 blocks
-            nranges = (NB + range_blocks - 1) / range_blocks;
-            if ((rc = pipeline_prepare(c, nranges))) return rc;
-        }
-    }
-
-    // ---- every function attribute of the phase, in front of the first launch (nothing but launches, event records and
-    // stream waits between the pipeline's fork and its join)
-    const bool hist_packed = NSP >= 8192u;  // f >= 4: 16-bit counters, two per LDS word (a chunk holds at most 16384 values): half the LDS, twice the workgroups per CU
-    const size_t packed_lds = (size_t)NSP * 2;
-    if (hist_packed) {
-        if (packed_lds > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_fold_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)packed_lds));
-    } else if (hist_lds > 48 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_fold_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds));
-    if (k2a_lds > 32 * 1024) {
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_sort_entropy<u16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k2a_lds));
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_sort_entropy<u32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k2a_lds));
-    }
-    if ((size_t)NSP * 8 + 64 > 48 * 1024 && (size_t)NSP * 8 + 64 <= 150 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_write_prelude<0>,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NSP * 8 + 64)));
-    if (fast) {
-        // k_candidates: the chain counts its launches will use (a full range and the last, shorter one)
-        const u32 last_blocks = nranges ? NB - (nranges - 1) * range_blocks : NB;
-        const u32 chain_set = (1u << cand_chains(nranges ? range_blocks : NB)) | (1u << cand_chains(last_blocks));
-        for (u32 nch = 1; nch <= 2; nch++) {
-            const size_t cl = (size_t)ANSX_CAND_WAVES * nch * bpw * ANSX_CAND_ROW * 16;
-            if (!(chain_set & (1u << nch)) || cl <= 48 * 1024) continue;
-            const void* fn = nullptr;
-            switch (NT) {
-            case 4: fn = nch == 1 ? (const void*)k_candidates<4, 1> : (const void*)k_candidates<4, 2>; break;
-            case 5: fn = nch == 1 ? (const void*)k_candidates<5, 1> : (const void*)k_candidates<5, 2>; break;
-            case 6: fn = nch == 1 ? (const void*)k_candidates<6, 1> : (const void*)k_candidates<6, 2>; break;
-            case 7: fn = nch == 1 ? (const void*)k_candidates<7, 1> : (const void*)k_candidates<7, 2>; break;
-            default: fn = nch == 1 ? (const void*)k_candidates<8, 1> : (const void*)k_candidates<8, 2>; break;
-            }
-            HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cl));
-        }
-        if (fl > 48 * 1024 && !(NSP <= 1024 && c->dbg.fin_one_wave)) {
-            const void* fn = NSP <= 1024 ? (const void*)k_model_finish<4, 8>
-                : NSP > 4096 ? (NT <= 5 ? (const void*)k_model_finish<0, 5> : (const void*)k_model_finish<0, 8>)
-                             : (NT <= 5 ? (const void*)k_model_finish<16, 5> : (const void*)k_model_finish<16, 8>);
-            HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl));
-        }
-    }
-
-    // ---- the four launches for the blocks [b0, be) on stream st
-    // K1
-    auto launch_hist = [&](hipStream_t st, u32 b0, u32 be) -> int {
-        const size_t grid = (size_t)(be - b0) * cpb;
-        if (hist_packed) {
-            // (sum_mode bit 1: on the fast model path H is the workgroup's tree sum and there is no hterm array to write)
-            LAUNCH(c, "k_fold_hist", k_fold_hist<true>, grid, 256, packed_lds, st, src, g, chunk, cpb, NSP, hist, hterm,
-                fast ? 2u : 0u, blk, gflags, (g.kind == ANSX_INT && !g.pa) ? NSP : (1u << 30), b0, be);
-        } else {
-            LAUNCH(c, "k_fold_hist", k_fold_hist<false>, grid, 256, hist_lds, st, src, g, chunk, cpb, NSP, hist, hterm,
-                (h_in_hist ? 1u : 0u) | (fast ? 2u : 0u), blk, gflags, (g.kind == ANSX_INT && !g.pa) ? NSP : (1u << 30), b0, be);
-        }
-        return ANSX_OK;
-    };
-    // K2
-    auto launch_sort = [&](hipStream_t st, u32 b0, u32 be) -> int {
-        if (!sort_staged)
-            LAUNCH(c, "k_sort_entropy", (k_sort_entropy<u32, false>), be - b0, 64, k2a_lds, st, g, NSP, nbig_cap, h_deferred ? 1u : 0u, hist,
-                (u32*)c->sortF.p, (u16*)c->sortSym.p, blk, sort_cap, fast ? (uint2*)c->pairs.p : (uint2*)nullptr, gflags, b0, be);
-        else if (sort16)
-            LAUNCH(c, "k_sort_entropy", k_sort_entropy<u16>, be - b0, 64, k2a_lds, st, g, NSP, nbig_cap, h_deferred ? 1u : 0u, hist,
-                (u32*)c->sortF.p, (u16*)c->sortSym.p, blk, sort_cap, fast ? (uint2*)c->pairs.p : (uint2*)nullptr, gflags, b0, be);
-        else
-            LAUNCH(c, "k_sort_entropy", k_sort_entropy<u32>, be - b0, 64, k2a_lds, st, g, NSP, nbig_cap, h_deferred ? 1u : 0u, hist,
-                (u32*)c->sortF.p, (u16*)c->sortSym.p, blk, sort_cap, fast ? (uint2*)c->pairs.p : (uint2*)nullptr, gflags, b0, be);
-        return ANSX_OK;
-    };
-    auto launch_cand = [&](hipStream_t st, u32 b0, u32 be) -> int {
-        const u32 nch = cand_chains(be - b0);
-        const size_t cl = (size_t)ANSX_CAND_WAVES * nch * bpw * ANSX_CAND_ROW * 16;
-        const u32 cwaves = (be - b0 + nch * bpw - 1) / (nch * bpw);
-#define ANSX_LAUNCH_CAND2(NT_, NCH_)                                                                                    \
-        LAUNCH(c, "k_candidates", (k_candidates<NT_, NCH_>), (cwaves + ANSX_CAND_WAVES - 1) / ANSX_CAND_WAVES, 64 * ANSX_CAND_WAVES, cl, st, g, NSP, \
-            (const uint2*)c->pairs.p, (const ansx_blk*)blk, (uint4*)c->attS.p, (u32*)c->attMeta.p, b0, be)
-#define ANSX_LAUNCH_CAND(NT_)                                                                                           \
-    do {                                                                                                            \
-        if (nch == 1) ANSX_LAUNCH_CAND2(NT_, 1);                                                                    \
-        else ANSX_LAUNCH_CAND2(NT_, 2);                                                                             \
-    } while (0)
-        switch (NT) {
-        case 4: ANSX_LAUNCH_CAND(4); break;
-        case 5: ANSX_LAUNCH_CAND(5); break;
-        case 6: ANSX_LAUNCH_CAND(6); break;
-        case 7: ANSX_LAUNCH_CAND(7); break;
-        default: ANSX_LAUNCH_CAND(8); break;
-        }
-#undef ANSX_LAUNCH_CAND
-#undef ANSX_LAUNCH_CAND2
-        return ANSX_OK;
-    };
-    auto launch_fin = [&](hipStream_t st, u32 b0, u32 be) -> int {
-#define ANSX_LAUNCH_FIN(IPT_, NTC_, NTH_)                                                                              \
-        LAUNCH(c, "k_model_finish", (k_model_finish<IPT_, NTC_, NTH_>), be - b0, NTH_, fl, st, g, NSP, NT, (const uint2*)c->pairs.p, (const uint4*)c->attS.p, \
-            (const u32*)c->attMeta.p, blk, (u32*)c->tab32.p, (u8*)c->scratch.p, (u64)scr_stride, mostfreq, hints, gflags, fcap, c->dbg.fast_guard, (const double*)c->lg2i.p, geo, \
-            (fin_generic && (NTH_) == 256) ? hist : (u32*)nullptr, b0, be)
-        if (NSP <= 1024 && c->dbg.fin_one_wave) {
-            // one wave per block (16 slots per lane, every candidate in every lane, no workgroup barriers): four times the blocks in flight
-            if (NT <= 5) ANSX_LAUNCH_FIN(16, 5, 64);
-            else ANSX_LAUNCH_FIN(16, 8, 64);
-        } else if (NSP <= 1024) {
-            ANSX_LAUNCH_FIN(4, 8, 256);  // (wave-per-candidate form: NTC is not used)
-        } else if (NSP > 4096) {
-            if (NT <= 5) ANSX_LAUNCH_FIN(0, 5, 256);
-            else ANSX_LAUNCH_FIN(0, 8, 256);
-        } else {
-            if (NT <= 5) ANSX_LAUNCH_FIN(16, 5, 256);
-            else ANSX_LAUNCH_FIN(16, 8, 256);
-        }
-#undef ANSX_LAUNCH_FIN
-        return ANSX_OK;
-    };
-    if (nranges == 0) {
-        if ((rc = launch_hist(s, 0, NB))) return rc;
-        if ((rc = launch_sort(s, 0, NB))) return rc;
-        if (fast) {
-            if ((rc = launch_cand(s, 0, NB))) return rc;
-            if ((rc = launch_fin(s, 0, NB))) return rc;
-        }
-    } else {
-        // fork: a range's model kernels wait for the event recorded on the caller's stream behind its histogram -- and with
-        // it for everything the call, and the call before it, put on that stream (k_begin_encode, the remap, the previous
-        // encoder's last read of the shared workspace)
-        u32 used = 0;  // side streams with work of this call
-        rc = ANSX_OK;
-        for (u32 k = 0; k < nranges && !rc; k++) {
-            const u32 b0 = k * range_blocks, be = std::min<u32>(NB, b0 + range_blocks);
-            if ((rc = launch_hist(s, b0, be))) break;
-            hipStream_t st = s;
-            if (k + 1 < nranges) {
-                const u32 side = k & 1u;
-                st = c->pipe_stream[side];
-                if ((rc = pipe_hip(c, hipEventRecord(c->pipe_ev[2 + k], s)))) break;
-                if ((rc = pipe_hip(c, hipStreamWaitEvent(st, c->pipe_ev[2 + k], 0)))) break;
-                used |= 1u << side;
-            }  // (the last range stays on the caller's stream behind its histogram: nothing is left to overlap it with there,
-               // and the encoder follows it without a cross-stream wait)
-            if ((rc = launch_sort(st, b0, be))) break;
-            if ((rc = launch_cand(st, b0, be))) break;
-            rc = launch_fin(st, b0, be);
-        }
-        // join: always, whatever happened above -- when the call returns, all its work is ordered on the caller's stream
-        for (u32 side = 0; side < 2; side++) {
-            if (!(used & (1u << side))) continue;
-            int rj = pipe_hip(c, hipEventRecord(c->pipe_ev[side], c->pipe_stream[side]));
-            if (!rj) rj = pipe_hip(c, hipStreamWaitEvent(s, c->pipe_ev[side], 0));
-            if (rj) {  // (the runtime refused the record or the wait: the host waits instead, so the promise still holds)
-                (void)hipStreamSynchronize(c->pipe_stream[side]);
-                if (!rc) rc = rj;
-            }
-        }
-        if (rc) return rc;
-    }
-    if (fast) {
-        max_logM = 16;
-        max_ns = ns_cap;
-    }
-    for (u32 batch = 0; batch < (fast ? 0u : nbatch); batch++) {
-        if (batch) HIPCHK(c, hipMemsetAsync(&gflags[ANSX_G_PAD], 0, 4, s));
+    hipStream_t s = W.s;
+    int rc;
+    if ((rc = launch_hist(c, W, M, s, 0, NB))) return rc;
+    if ((rc = launch_sort(c, W, M, s, 0, NB))) return rc;
+    for (u32 batch = 0; batch < nbatch; batch++) {
+        if (batch) HIPCHK(c, hipMemsetAsync(&W.gflags[ANSX_G_PAD], 0, 4, s));
         LAUNCH(c, "k_scale_attempts", k_scale_attempts, ((size_t)NB * ANSX_ATTEMPTS + 255) / 256, 256,
-            0, s, g, NSP, batch, hist, (const u32*)c->sortF.p, (const u16*)c->sortSym.p, blk,
-            (u16*)c->attS.p, (u32*)c->attMeta.p, (const double*)hterm, (const ansx_log2_ent*)c->log2lut.p,
+            0, s, g, NSP, batch, W.hist, (const u32*)c->sortF.p, (const u16*)c->sortSym.p, W.blk,
+            (u16*)c->attS.p, (u32*)c->attMeta.p, (const double*)W.hterm, (const ansx_log2_ent*)c->log2lut.p,
             g.block_ints <= 65535u ? 1u : 0u);
-        LAUNCH(c, "k_select_model", k_select_model, NB, 64, 0, s, g, NSP, batch, hist,
-            (const u16*)c->attS.p, (const u32*)c->attMeta.p, (u16*)c->prevS.p, blk,
-            (ansx_enc_entry*)c->table.p, (u32*)c->tab32.p, gflags, batch == nbatch - 1 ? 1u : 0u, always16,
-            (u32*)c->nearlist.p, c->cur_force, c->dbg.near_band, c->dbg.near_flip ? 1u : 0u);
-        if (optimistic) {  // checked after the fact (blocks left undecided carry no model and are skipped)
-            max_logM = 16;
-            max_ns = ns_cap;
+        LAUNCH(c, "k_select_model", k_select_model, NB, 64, 0, s, g, NSP, batch, W.hist,
+            (const u16*)c->attS.p, (const u32*)c->attMeta.p, (u16*)c->prevS.p, W.blk,
+            (ansx_enc_entry*)c->table.p, (u32*)c->tab32.p, W.gflags, batch == nbatch - 1 ? 1u : 0u, M.always16,
+            (u32*)c->nearlist.p, W.a->force, c->dbg.near_band, c->dbg.near_flip ? 1u : 0u);
+        if (W.a->ns_cap != 0) {  // checked after the fact (blocks left undecided carry no model and are skipped)
+            W.max_logM = 16;
+            W.max_ns = W.a->ns_cap;
             break;
         }
-        HIPCHK(c, hipMemcpyAsync(c->h_pin, c->misc.p, 16, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        int st0 = flags_to_status(c->h_pin[ANSX_G_ERR]);
-        if (st0) return st0;
-        max_logM = c->h_pin[ANSX_G_MAXLOGM];
-        max_ns = c->h_pin[ANSX_G_MAXNSYMS];
-        if (c->h_pin[ANSX_G_PAD] == 0) break;
+        if ((rc = read_flags(c, W, 4))) return rc;
+        const u32* fl = W.out->flags;
+        if ((rc = flags_to_status(fl[ANSX_G_ERR]))) return rc;
+        W.max_logM = fl[ANSX_G_MAXLOGM];
+        W.max_ns = fl[ANSX_G_MAXNSYMS];
+        if (fl[ANSX_G_PAD] == 0) break;
     }
-    if (!P.plain && !g.ckw && g.nckf != 0 && max_logM > c->dbg.wide_at) return ANSX_RETRY_WIDE;  // (discovery path: known before anything is encoded)
-    if (!always16 && (max_logM > 16 || test_fixup))  // mixed call: a frame above 2^16 sends every block to the integer-state encoder
-        LAUNCH(c, "k_table16_from32", k_table16_from32, NB, 256, 0, s, g, NSP, (const ansx_blk*)blk,
-            (const u32*)c->tab32.p, (ansx_enc_entry*)c->table.p);
-    // K3 (also fills the container's parse hints)
-    // LDS arrays of the prelude writer: as long as the call's largest alphabet (known here on the discovery path,
-    // assumed = the hint on the optimistic one), not as its slot count
-    u32 pre_cap = optimistic ? ns_cap : max_ns;
-    pre_cap = std::min<u32>(NSP, std::max<u32>(64u, (pre_cap + 7u) & ~7u));
-    if (fast) {
-        // (k_model_finish wrote the preludes)
-    } else if (NSP <= 1024 && max_logM <= 16) {
-        LAUNCH(c, "k_write_prelude", (k_write_prelude<4>), NB, 256, (size_t)pre_cap * 12 + 64, s, g, NSP,
-            (const ansx_enc_entry*)c->table.p, (const u32*)c->tab32.p, hist, blk, (u8*)c->scratch.p,
-            (u64)scr_stride, mostfreq, hints, pre_cap, geo);
-    } else if (NSP <= 4096 && max_logM <= 16) {
+    return ANSX_OK;
+}
+
+// Block-range pipeline of the fast model path: the call's blocks in `nranges` contiguous ranges,
+// the histograms one after the other on the caller's stream, and k_sort_entropy -> k_candidates -> k_model_finish of
+// every range but the last on one of the context's two side streams (alternating) behind that range's histogram -- a
+// memory-bound kernel beside a VALU-bound one beside a latency chain.  The ranges meet in no workspace byte (every
+// array is indexed by the absolute block number) and in `gflags` only through order-independent atomics.  Everything
+// joins on the caller's stream in front of the encoder.  *nranges == 0: one launch of each kernel over all blocks on
+// the caller's stream.
+int pipeline_plan(ansx_ctx* c, const EncodeWs& W, u32* range_blocks, u32* nranges)
+{
+    const ansx_geo& g = W.P->g;
+    const u32 NB = g.nblocks;
+    const int mode = c->dbg.model_pipeline;
+    *range_blocks = NB, *nranges = 0;
+    // (profile mode: the event pairs of LAUNCH would time overlapped kernels -- serial there)
+    if (c->profile || mode == ANSX_PIPE_NEVER) return ANSX_OK;
+    const u32 want = mode > 0 ? (u32)mode : ((mode == ANSX_PIPE_ALWAYS || (NB >= ANSX_PIPE_MIN_BLOCKS && g.n >= ANSX_PIPE_MIN_INTS)) ? ANSX_PIPE_RANGES : 0u);
+    if (!want) return ANSX_OK;
+    // (a captured graph with parallel branches: the call stays one chain of launches under capture)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(W.s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return ANSX_OK;
+    *range_blocks = (u32)rup(((size_t)NB + want - 1) / want, 64);  // range boundaries: multiples of 64 blocks
+    *nranges = (NB + *range_blocks - 1) / *range_blocks;
+    return pipeline_prepare(c, *nranges);
+}
+
+// Phase 3b, the model in its fast form: K1, K2, k_candidates, k_model_finish (which also writes the preludes), serial
+// or as the block-range pipeline.  Everything that is not a launch, an event record or a stream wait -- buffers, the
+// one-time tables, the side streams, every function attribute -- comes first.
+int model_fast(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
+{
+    const u32 NB = W.P->g.nblocks, NSP = W.P->NSP;
+    hipStream_t s = W.s;
+    int rc;
+    if (NSP > 4096 && !c->dbg.no_big_geo) {
+        // k_model_finish<0>: a 14-level tree descent per item was two thirds of its prelude writer; the nodes of every alphabet
+        // size up to the hint come from a table here too (built once per context, rebuilt when the hint grows)
+        if (c->geo_big_cap < M.fcap) {
+            if ((rc = ensure(c, c->geo_big, ((size_t)M.fcap * (M.fcap + 1) / 2 + 8) * 8))) return rc;
+            LAUNCH(c, "k_build_interp_geo", k_build_interp_geo, M.fcap, 256, 0, s, M.fcap, (uint2*)c->geo_big.p);
+            c->geo_big_cap = M.fcap;
+        }
+        W.geo = (const uint2*)c->geo_big.p;
+    }
+    if ((rc = ensure(c, c->pairs, (size_t)NB * NSP * 8))) return rc;
+    if (!c->lg2i.p) {  // log2 of the integers below 2^16, once per context (512 KB)
+        if ((rc = ensure(c, c->lg2i, (size_t)65536 * 8))) return rc;
+        LAUNCH(c, "k_build_log2i_lut", k_build_log2i_lut, 256, 256, 0, s, (double*)c->lg2i.p);
+    }
+    u32 range_blocks, nranges;
+    if ((rc = pipeline_plan(c, W, &range_blocks, &nranges))) return rc;
+    // k_candidates: the chain counts its launches will use (a full range and the last, shorter one)
+    const u32 last_blocks = nranges ? NB - (nranges - 1) * range_blocks : NB;
+    const u32 chain_set = (1u << cand_chains(c, M, range_blocks)) | (1u << cand_chains(c, M, last_blocks));
+    for (u32 nch = 1; nch <= 2; nch++)
+        if ((chain_set & (1u << nch)) && cand_lds(M, nch) > 48 * 1024 && (rc = raise_lds(c, cand_kernel(W.a->nt, nch), cand_lds(M, nch)))) return rc;
+    if (M.fin_lds > 48 * 1024 && (rc = raise_lds(c, fin_kernel(c, NSP, W.a->nt).kern, M.fin_lds))) return rc;
+
+    W.max_logM = 16;
+    W.max_ns = W.a->ns_cap;
+    if (nranges == 0) {
+        if ((rc = launch_hist(c, W, M, s, 0, NB))) return rc;
+        return launch_fast_model(c, W, M, s, 0, NB);
+    }
+    // fork: a range's model kernels wait for the event recorded on the caller's stream behind its histogram -- and with
+    // it for everything the call, and the call before it, put on that stream (k_begin_encode, the remap, the previous
+    // encoder's last read of the shared workspace)
+    u32 used = 0;  // side streams with work of this call
+    rc = ANSX_OK;
+    for (u32 k = 0; k < nranges && !rc; k++) {
+        const u32 b0 = k * range_blocks, be = std::min<u32>(NB, b0 + range_blocks);
+        if ((rc = launch_hist(c, W, M, s, b0, be))) break;
+        hipStream_t st = s;
+        if (k + 1 < nranges) {
+            const u32 side = k & 1u;
+            st = c->pipe_stream[side];
+            if ((rc = pipe_hip(c, hipEventRecord(c->pipe_ev[2 + k], s)))) break;
+            if ((rc = pipe_hip(c, hipStreamWaitEvent(st, c->pipe_ev[2 + k], 0)))) break;
+            used |= 1u << side;
+        }  // (the last range stays on the caller's stream behind its histogram: nothing is left to overlap it with there,
+           // and the encoder follows it without a cross-stream wait)
+        rc = launch_fast_model(c, W, M, st, b0, be);
+    }
+    // join: always, whatever happened above -- when the call returns, all its work is ordered on the caller's stream
+    for (u32 side = 0; side < 2; side++) {
+        if (!(used & (1u << side))) continue;
+        int rj = pipe_hip(c, hipEventRecord(c->pipe_ev[side], c->pipe_stream[side]));
+        if (!rj) rj = pipe_hip(c, hipStreamWaitEvent(s, c->pipe_ev[side], 0));
+        if (rj) {  // (the runtime refused the record or the wait: the host waits instead, so the promise still holds)
+            (void)hipStreamSynchronize(c->pipe_stream[side]);
+            if (!rc) rc = rj;
+        }
+    }
+    return rc;
+}
+
+// Phase 4, the exact form's prelude writers (K3; they also fill the container's parse hints).  Their LDS arrays are as
+// long as the call's largest alphabet (known here on the discovery path, assumed = the hint on the optimistic one), not
+// as its slot count: workgroups per CU.
+int write_preludes(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
+{
+    const ansx_geo& g = W.P->g;
+    const u32 NB = g.nblocks, NSP = W.P->NSP;
+    hipStream_t s = W.s;
+    const ansx_enc_entry* table = (const ansx_enc_entry*)c->table.p;
+    const u32* tab32 = (const u32*)c->tab32.p;
+    u8* scratch = (u8*)c->scratch.p;
+    if (!M.always16 && (W.max_logM > 16 || c->dbg.table16_fixup))  // mixed call: a frame above 2^16 sends every block to the integer-state encoder
+        LAUNCH(c, "k_table16_from32", k_table16_from32, NB, 256, 0, s, g, NSP, (const ansx_blk*)W.blk, tab32, (ansx_enc_entry*)c->table.p);
+    const u32 pre_cap = std::min<u32>(NSP, std::max<u32>(64u, ((W.a->ns_cap ? W.a->ns_cap : W.max_ns) + 7u) & ~7u));
+    if (NSP <= 1024 && W.max_logM <= 16) {
+        LAUNCH(c, "k_write_prelude", (k_write_prelude<4>), NB, 256, (size_t)pre_cap * 12 + 64, s, g, NSP, table, tab32, W.hist, W.blk, scratch,
+            W.scr_stride, W.mostfreq, W.hints, pre_cap, W.geo);
+    } else if (NSP <= 4096 && W.max_logM <= 16) {
         HIPCHK(c, hipFuncSetAttribute((const void*)k_write_prelude<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                       (int)((size_t)pre_cap * 12 + 64)));
-        LAUNCH(c, "k_write_prelude", (k_write_prelude<16>), NB, 256, (size_t)pre_cap * 12 + 64, s, g, NSP,
-            (const ansx_enc_entry*)c->table.p, (const u32*)c->tab32.p, hist, blk, (u8*)c->scratch.p,
-            (u64)scr_stride, mostfreq, hints, pre_cap, geo);
-    } else if (sparse) {
+        LAUNCH(c, "k_write_prelude", (k_write_prelude<16>), NB, 256, (size_t)pre_cap * 12 + 64, s, g, NSP, table, tab32, W.hist, W.blk, scratch,
+            W.scr_stride, W.mostfreq, W.hints, pre_cap, W.geo);
+    } else if (W.a->int_sparse) {
         // the reference's prelude over the VALUE range, from the rank-space model (16-byte entries: always16) and the block's values
-        // LDS from the call's most distinct values per block (max_ns: read back above, the discovery path) unless a block's code
-        // outgrew three words per value on the first attempt
-        const u32 sp_cap = c->sp_full_lds ? (u32)ANSX_SP_MAX_SIGMA : std::min<u32>(ANSX_SP_MAX_SIGMA, (std::max<u32>(max_ns, 64u) + 63u) & ~63u);
-        const u32 sp_bits = c->sp_full_lds ? (u32)ANSX_SP_MAX_SIGMA
-                                           : (c->dbg.test_sp_bits ? c->dbg.test_sp_bits : std::min<u32>(ANSX_SP_MAX_SIGMA, 2u * sp_cap + 64u));
+        // LDS from the call's most distinct values per block (max_ns: read back by model_exact, the discovery path) unless a block's
+        // code outgrew three words per value on the first attempt
+        const bool full = W.a->sp_full_lds;
+        const u32 sp_cap = full ? (u32)ANSX_SP_MAX_SIGMA : std::min<u32>(ANSX_SP_MAX_SIGMA, (std::max<u32>(W.max_ns, 64u) + 63u) & ~63u);
+        const u32 sp_bits = full ? (u32)ANSX_SP_MAX_SIGMA
+                                 : (c->dbg.test_sp_bits ? c->dbg.test_sp_bits : std::min<u32>(ANSX_SP_MAX_SIGMA, 2u * sp_cap + 64u));
         const size_t sp_lds = (size_t)(sp_cap + sp_bits + 2) * 4;
         HIPCHK(c, hipFuncSetAttribute((const void*)k_int_sparse_prelude, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp_lds));
-        LAUNCH(c, "k_int_sparse_prelude", k_int_sparse_prelude, NB, 256, sp_lds, s, g, NSP, (const u32*)c->pa_alpha.p,
-            (const ansx_enc_entry*)c->table.p, blk, (u8*)c->scratch.p, (u64)scr_stride, sp_cap, sp_bits, (u32)(4 * NSP), gflags);
+        LAUNCH(c, "k_int_sparse_prelude", k_int_sparse_prelude, NB, 256, sp_lds, s, g, NSP, (const u32*)c->pa_alpha.p, table, W.blk, scratch,
+            W.scr_stride, sp_cap, sp_bits, (u32)(4 * NSP), W.gflags);
     } else {
-        const size_t gen_lds = (size_t)pre_cap * 8 + 64;  // (as long as the call's largest alphabet, not as its slot count: workgroups per CU)
+        size_t gen_lds = (size_t)pre_cap * 8 + 64;
+        u32* g_work = nullptr;
         if (gen_lds > 150 * 1024) {  // f = 6, 7: the writer's two arrays in HBM
+            int rc;
             if ((rc = ensure(c, c->pre_work, (size_t)NB * (2 * (size_t)pre_cap + 16) * 4))) return rc;
-            LAUNCH(c, "k_write_prelude", (k_write_prelude<0>), NB, 256, 64, s, g, NSP,
-                (const ansx_enc_entry*)c->table.p, (const u32*)c->tab32.p, hist, blk, (u8*)c->scratch.p,
-                (u64)scr_stride, mostfreq, hints, pre_cap, (const uint2*)nullptr, (u32*)c->pre_work.p);
-        } else
-        LAUNCH(c, "k_write_prelude", (k_write_prelude<0>), NB, 256, gen_lds, s, g, NSP,
-            (const ansx_enc_entry*)c->table.p, (const u32*)c->tab32.p, hist, blk, (u8*)c->scratch.p,
-            (u64)scr_stride, mostfreq, hints, pre_cap, (const uint2*)nullptr, (u32*)nullptr);
+            g_work = (u32*)c->pre_work.p;
+            gen_lds = 64;
+        } else if (gen_lds > 48 * 1024)
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_write_prelude<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds));
+        LAUNCH(c, "k_write_prelude", (k_write_prelude<0>), NB, 256, gen_lds, s, g, NSP, table, tab32, W.hist, W.blk, scratch,
+            W.scr_stride, W.mostfreq, W.hints, pre_cap, (const uint2*)nullptr, g_work);
     }
-    // K5.  The encoder keeps its 16 per-wave tables in LDS when they fit (sized from the largest
-    // alphabet / frame actually produced, read back above).
-    u64* ck_state = P.plain ? nullptr : (u64*)(d_out + P.lay.ckstate_off);
-    u32* ck_off = P.plain ? nullptr : (u32*)(d_out + P.lay.ckoff_off);
-    // (its emitted-byte stores go through a buffer descriptor spanning the wave's 16 scratch slots:
-    // 31-bit offsets)
-    const bool f64_ok = max_logM <= 16 && (u64)scr_stride * 16 < 0x7FFFFF00ull && !test_fixup;
-    if (f64_ok && !c->dbg.encode_gtab16) {
-        if ((rc = launch_f64_encoder(c, g, NSP, src, max_ns, blk, (u64)scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, NB, s))) return rc;
-    } else {
-        LAUNCH(c, "k_encode_gtab", (k_encode<0>), ((size_t)NB * 4 + 63) / 64, 64, 0, s, src, g, NSP,
-            (const ansx_enc_entry*)c->table.p, (const u32*)c->tab32.p, 0u, blk, (u8*)c->scratch.p,
-            (u64)scr_stride, ck_state, ck_off, enc_sizes, enc_gsums);
-    }
-    // K6
-    u64* boff = P.plain ? boff_ws : (u64*)(d_out + P.lay.index_off);
+    return ANSX_OK;
+}
+
+// Phase 5, the encoder (K5).  The f64-state forms keep their per-wave tables in LDS when they fit (sized from the
+// largest alphabet / frame of the model phase); their emitted-byte stores go through a buffer descriptor spanning the
+// wave's 16 scratch slots: 31-bit offsets.
+int launch_encoder(ansx_ctx* c, EncodeWs& W)
+{
+    const Plan& P = *W.P;
+    const u32 NB = P.g.nblocks;
+    u64* ck_state = P.plain ? nullptr : (u64*)(W.d_out + P.lay.ckstate_off);
+    u32* ck_off = P.plain ? nullptr : (u32*)(W.d_out + P.lay.ckoff_off);
+    const bool f64_ok = W.max_logM <= 16 && W.scr_stride * 16 < 0x7FFFFF00ull && !c->dbg.table16_fixup;
+    if (f64_ok && !c->dbg.encode_gtab16)
+        return launch_f64_encoder(c, P.g, P.NSP, W.src, W.max_ns, W.blk, W.scr_stride, ck_state, ck_off, W.enc_sizes, W.enc_gsums, NB, W.s,
+            &W.out->used_pc);
+    LAUNCH(c, "k_encode_gtab", (k_encode<0>), ((size_t)NB * 4 + 63) / 64, 64, 0, W.s, W.src, P.g, P.NSP,
+        (const ansx_enc_entry*)c->table.p, (const u32*)c->tab32.p, 0u, W.blk, (u8*)c->scratch.p,
+        W.scr_stride, ck_state, ck_off, W.enc_sizes, W.enc_gsums);
+    return ANSX_OK;
+}
+
+// Phase 6: assembly (K6), the attempt's one read-back of the flag words behind it, and their status.
+int encode_finish(ansx_ctx* c, EncodeWs& W, size_t* out_bytes)
+{
+    const Plan& P = *W.P;
+    const ansx_geo& g = P.g;
+    const u32 NB = g.nblocks;
+    hipStream_t s = W.s;
+    u64* boff = P.plain ? W.boff_ws : (u64*)(W.d_out + P.lay.index_off);
     if (NB <= 65536u) {
-        LAUNCH(c, "k_assemble", k_assemble, NB, 256, 0, s, g, (const u32*)enc_sizes, (const unsigned long long*)enc_gsums, boff, result,
-            (const u8*)c->scratch.p, (u64)scr_stride, d_out, (u64)P.lay.payload_off, (u64)cap, gflags, P.plain ? 0u : 1u);
+        LAUNCH(c, "k_assemble", k_assemble, NB, 256, 0, s, g, (const u32*)W.enc_sizes, (const unsigned long long*)W.enc_gsums, boff, W.result,
+            (const u8*)c->scratch.p, W.scr_stride, W.d_out, (u64)P.lay.payload_off, (u64)W.cap, W.gflags, P.plain ? 0u : 1u);
     } else {
-        LAUNCH(c, "k_scan_sizes", k_scan_sizes, 1, 1024, 0, s, g, blk, boff, result, P.lay.payload_off,
-            (u64)cap, gflags);
-        LAUNCH(c, "k_compact", k_compact, NB, 256, 0, s, g, blk, boff, (const u8*)c->scratch.p,
-            (u64)scr_stride, d_out + P.lay.payload_off, gflags);
+        LAUNCH(c, "k_scan_sizes", k_scan_sizes, 1, 1024, 0, s, g, W.blk, boff, W.result, P.lay.payload_off,
+            (u64)W.cap, W.gflags);
+        LAUNCH(c, "k_compact", k_compact, NB, 256, 0, s, g, W.blk, boff, (const u8*)c->scratch.p,
+            W.scr_stride, W.d_out + P.lay.payload_off, W.gflags);
         if (!P.plain)
-            LAUNCH(c, "k_write_header", k_write_header, 1, 64, 0, s, g, d_out, gflags, result, P.lay.payload_off);
+            LAUNCH(c, "k_write_header", k_write_header, 1, 64, 0, s, g, W.d_out, W.gflags, W.result, P.lay.payload_off);
     }
-    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->misc.p, 64, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (optimistic) {
-        if (c->h_pin[ANSX_G_ERR] & (1u << 6)) return ANSX_ERR_DOMAIN;
-        if (c->h_pin[ANSX_G_ERR] & (1u << ANSX_G_VIOL_BIT)) return ANSX_RETRY_GENERAL;  // (rfold: optimistic hash table too small)
-        if (c->h_pin[ANSX_G_PAD] != 0 || c->h_pin[ANSX_G_MAXLOGM] > 16 || c->h_pin[ANSX_G_MAXNSYMS] > ns_cap)
-            return ANSX_RETRY_GENERAL;
-        if (!g.ckw && g.nckf != 0 && c->h_pin[ANSX_G_MAXLOGM] > c->dbg.wide_at) return ANSX_RETRY_GENERAL;  // (tests only: wide_at < 16)
+    int rc;
+    if ((rc = read_flags(c, W, 16))) return rc;
+    const u32* fl = W.out->flags;
+    if (W.a->ns_cap != 0) {
+        if (fl[ANSX_G_ERR] & (1u << 6)) return ANSX_ERR_DOMAIN;
+        if (fl[ANSX_G_ERR] & (1u << ANSX_G_VIOL_BIT)) return ANSX_RETRY_GENERAL;  // (rfold: optimistic hash table too small; the fused model: any assumption)
+        if (fl[ANSX_G_PAD] != 0 || fl[ANSX_G_MAXLOGM] > 16 || fl[ANSX_G_MAXNSYMS] > W.a->ns_cap) return ANSX_RETRY_GENERAL;
+        if (!g.ckw && g.nckf != 0 && fl[ANSX_G_MAXLOGM] > c->dbg.wide_at) return ANSX_RETRY_GENERAL;  // (tests only: wide_at < 16)
     }
-    int st = flags_to_status(c->h_pin[ANSX_G_ERR]);
-    if (st) return st;
-    if (sparse && !c->sp_full_lds && (c->h_pin[ANSX_G_ERR] & (1u << ANSX_G_VIOL_BIT))) {
-        c->sp_full_lds = true;  // (the value-range prelude of some block needs more than two words per distinct value)
-        c->sp_retries++;
-        const int rc2 = encode_general(c, P, d_in, d_out, cap, out_bytes, s, seen_ns, ns_cap);
-        c->sp_full_lds = false;
-        return rc2;
-    }
-    *seen_ns = c->h_pin[ANSX_G_MAXNSYMS];
+    if ((rc = flags_to_status(fl[ANSX_G_ERR]))) return rc;
     u64 payload;
-    memcpy(&payload, (u8*)c->h_pin + 16, 8);
+    memcpy(&payload, &fl[4], 8);
     *out_bytes = (size_t)(P.lay.payload_off + payload);
     return ANSX_OK;
+}
+
+// One attempt on the tailored model kernels: the phases in the order of DESIGN.md section 5.
+int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t cap, size_t* out_bytes, hipStream_t s,
+    const EncodeAttempt& a, EncodeOutcome* out)
+{
+    const ansx_geo& g = P.g;
+    EncodeWs W = { &P, &a, out, d_in, d_out, cap, s };
+    int rc;
+    if ((rc = encode_begin(c, W))) return rc;                                  // workspace, k_begin_encode
+    if ((rc = encode_remap(c, W))) return rc;                                  // rfold / compaction / rank-space ANSint
+    const ModelShape M = model_shape(c, W);
+    out->used_fast = M.fast;
+    if ((rc = model_prepare(c, W, M))) return rc;
+    if ((rc = M.fast ? model_fast(c, W, M) : model_exact(c, W, M))) return rc;  // K1 .. K4
+    if (!P.plain && !g.ckw && g.nckf != 0 && W.max_logM > c->dbg.wide_at) return ANSX_RETRY_WIDE;  // (discovery path: known before anything is encoded)
+    if (!M.fast && (rc = write_preludes(c, W, M))) return rc;                  // (k_model_finish wrote them)
+    if ((rc = launch_encoder(c, W))) return rc;
+    if ((rc = encode_finish(c, W, out_bytes))) return rc;
+    if (a.int_sparse && !a.sp_full_lds && (out->flags[ANSX_G_ERR] & (1u << ANSX_G_VIOL_BIT))) {
+        // (the value-range prelude of some block needs more than two words per distinct value)
+        EncodeAttempt full = a;
+        full.sp_full_lds = true;
+        rc = encode_general(c, P, d_in, d_out, cap, out_bytes, s, full, out);
+        out->sp_repeated = true;
+    }
+    return rc;
 }
 
 // LDS carve of k_model_fused for `cap` symbols (a multiple of 8), see ansx_model.h
@@ -1068,92 +1139,26 @@ ansx_model_lds model_layout(u32 cap)
     return L;
 }
 
-// Optimistic encode, fused form: ONE model kernel per block with everything in LDS (sized from the context's
-// alphabet hint), no host round trip before the final size read-back.  Any block that does not fit the
-// assumptions (alphabet above the hint, frame above 2^16) raises the violation flag and the caller
-// repeats the call on the general path.
-int encode_fast(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t cap, size_t* out_bytes,
-    hipStream_t s, u32 ns_cap, u32* seen_ns)
+// Optimistic attempt, fused form (opt-in): ONE model kernel per block with everything in LDS (sized from the
+// alphabet hint) between the shared front and tail.  Any block that does not fit the assumptions (alphabet above the
+// hint, frame above 2^16) raises the violation flag and the caller repeats the call on the general path.
+int encode_fast(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t cap, size_t* out_bytes, hipStream_t s,
+    const EncodeAttempt& a, EncodeOutcome* out)
 {
-    const ansx_geo& g = P.g;
-    const u32 NB = g.nblocks, NSP = P.NSP, f = g.f;
-    const size_t scr_stride = rup(block_bound(g.kind, f, g.block_ints) + 16, 256);
-    if (cap < P.lay.payload_off) return ANSX_ERR_CAPACITY;
-    if ((u64)scr_stride * 16 >= 0x7FFFFF00ull) return ANSX_RETRY_GENERAL;
-    const ansx_model_lds ML = model_layout(ns_cap);
-    if (ML.total > 150 * 1024) return ANSX_RETRY_GENERAL;
+    const ansx_model_lds ML = model_layout(a.ns_cap);
+    if (scratch_stride(P.g) * 16 >= 0x7FFFFF00ull || ML.total > 150 * 1024) return ANSX_RETRY_GENERAL;
+    EncodeWs W = { &P, &a, out, d_in, d_out, cap, s };
     int rc;
-    if (!c->log2lut.p) {  // stage-1 table of the portable log2, once per context (1.5 MB)
-        if ((rc = ensure(c, c->log2lut, (size_t)65536 * sizeof(ansx_log2_ent)))) return rc;
-        LAUNCH(c, "k_build_log2_lut", k_build_log2_lut, 256, 256, 0, s, (ansx_log2_ent*)c->log2lut.p);
-    }
-    if ((rc = ensure(c, c->blk, (size_t)NB * sizeof(ansx_blk)))) return rc;
-    if ((rc = ensure(c, c->tab32, (size_t)NB * NSP * 4))) return rc;
-    if ((rc = ensure(c, c->scratch, (size_t)NB * scr_stride))) return rc;
-    if ((rc = ensure(c, c->misc, 64 + 8 * ((size_t)NB + 1)))) return rc;
-    const size_t ngroups = (((size_t)NB + 63) / 64 + 1) & ~(size_t)1;
-    if ((rc = ensure(c, c->sizes, ngroups * 8 + (size_t)NB * 4))) return rc;
-    unsigned long long* enc_gsums = (unsigned long long*)c->sizes.p;
-    u32* enc_sizes = (u32*)((u8*)c->sizes.p + ngroups * 8);
-    HIPCHK(c, hipMemsetAsync(enc_gsums, 0, ngroups * 8, s));
-    u32* gflags = (u32*)c->misc.p;
-    u64* result = (u64*)((u8*)c->misc.p + 16);
-    ansx_blk* blk = (ansx_blk*)c->blk.p;
-    HIPCHK(c, hipMemsetAsync(c->misc.p, 0, 64, s));
-    HIPCHK(c, hipMemsetAsync(blk, 0, (size_t)NB * sizeof(ansx_blk), s));
-    HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)P.lay.payload_off, s));
-    const u32* src = d_in;
-    const u32* mostfreq = nullptr;
-    if (g.kind == ANSX_RFOLD) {
-        const u32 T = fold_T(f);
-        if ((rc = ensure(c, c->mapped, (size_t)g.n * 4))) return rc;
-        if ((rc = ensure(c, c->mostfreq, (size_t)NB * T * 4))) return rc;
-        rc = rfold_remap(c, P.g, d_in, (u32*)c->mapped.p, (u32*)c->mostfreq.p, blk, gflags, s, c->cur_rf_slots);
-        if (rc) return rc;
-        src = (const u32*)c->mapped.p;
-        mostfreq = (const u32*)c->mostfreq.p;
-    }
-    if (ns_cap <= 1024) {
-        if (ML.total > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_model_fused<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ML.total));
-        LAUNCH(c, "k_model_fused", (k_model_fused<4>), NB, 256, ML.total, s, src, g, NSP, ML,
-            (const ansx_log2_ent*)c->log2lut.p, blk, (u32*)c->tab32.p, (u8*)c->scratch.p, (u64)scr_stride, mostfreq,
-            gflags, 1u << 30, (u32*)(d_out + P.lay.hint_off));
-    } else {
-        if (ML.total > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_model_fused<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ML.total));
-        LAUNCH(c, "k_model_fused", (k_model_fused<16>), NB, 256, ML.total, s, src, g, NSP, ML,
-            (const ansx_log2_ent*)c->log2lut.p, blk, (u32*)c->tab32.p, (u8*)c->scratch.p, (u64)scr_stride, mostfreq,
-            gflags, 1u << 30, (u32*)(d_out + P.lay.hint_off));
-    }
-    u64* ck_state = (u64*)(d_out + P.lay.ckstate_off);
-    u32* ck_off = (u32*)(d_out + P.lay.ckoff_off);
-    {
-        int rcl;
-        if ((rcl = launch_f64_encoder(c, g, NSP, src, ns_cap, blk, (u64)scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, NB, s))) return rcl;
-    }
-    u64* boff = (u64*)(d_out + P.lay.index_off);
-    if (NB <= 65536u) {
-        LAUNCH(c, "k_assemble", k_assemble, NB, 256, 0, s, g, (const u32*)enc_sizes, (const unsigned long long*)enc_gsums, boff, result,
-            (const u8*)c->scratch.p, (u64)scr_stride, d_out, (u64)P.lay.payload_off, (u64)cap, gflags, 1u);
-    } else {
-        LAUNCH(c, "k_scan_sizes", k_scan_sizes, 1, 1024, 0, s, g, blk, boff, result, P.lay.payload_off, (u64)cap, gflags);
-        LAUNCH(c, "k_compact", k_compact, NB, 256, 0, s, g, blk, boff, (const u8*)c->scratch.p, (u64)scr_stride,
-            d_out + P.lay.payload_off, gflags);
-        LAUNCH(c, "k_write_header", k_write_header, 1, 64, 0, s, g, d_out, gflags, result, P.lay.payload_off);
-    }
-    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->misc.p, 64, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    const u32 fl = c->h_pin[ANSX_G_ERR];
-    if (fl & (1u << 6)) return ANSX_ERR_DOMAIN;
-    if (fl & (1u << ANSX_G_VIOL_BIT)) return ANSX_RETRY_GENERAL;
-    int st = flags_to_status(fl);
-    if (st) return st;
-    *seen_ns = c->h_pin[ANSX_G_MAXNSYMS];
-    u64 payload;
-    memcpy(&payload, (u8*)c->h_pin + 16, 8);
-    *out_bytes = (size_t)(P.lay.payload_off + payload);
-    return ANSX_OK;
+    if ((rc = encode_begin(c, W))) return rc;
+    if ((rc = encode_remap(c, W))) return rc;
+    const auto kern = a.ns_cap <= 1024 ? k_model_fused<4> : k_model_fused<16>;
+    if (ML.total > 48 * 1024 && (rc = raise_lds(c, kern, ML.total))) return rc;
+    LAUNCH(c, "k_model_fused", kern, P.g.nblocks, 256, ML.total, s, W.src, P.g, P.NSP, ML, (const ansx_log2_ent*)c->log2lut.p, W.blk,
+        (u32*)c->tab32.p, (u8*)c->scratch.p, W.scr_stride, W.mostfreq, W.gflags, 1u << 30, W.hints);
+    W.max_logM = 16;
+    W.max_ns = a.ns_cap;
+    if ((rc = launch_encoder(c, W))) return rc;
+    return encode_finish(c, W, out_bytes);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1233,14 +1238,13 @@ int host_adjust_freqs(const std::vector<u32>& freqs, u32 largest_sym, bool requi
     return -1;
 }
 
-int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t cap, size_t* out_bytes, hipStream_t s,
-    u32* seen_ns, u32 ns_cap);
-
+// `last`: the attempt whose container stands in d_out, `out` its outcome.  A forced repeat assumes nothing but what
+// the host decided, keeps the model space of that attempt, and leaves its own outcome in `out`.
 int resolve_near(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t cap, size_t* out_bytes, hipStream_t s,
-    u32* seen_ns, u32* redecided)
+    const EncodeAttempt& last, EncodeOutcome* out, u32* redecided)
 {
     const ansx_geo& g = P.g;
-    const u32 nn = c->h_pin[ANSX_G_NEAR];
+    const u32 nn = out->flags[ANSX_G_NEAR];
     std::vector<u32> list;
     if (nn <= ANSX_NEAR_CAP) {
         list.resize(nn);
@@ -1250,15 +1254,14 @@ int resolve_near(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t 
         list.resize(g.nblocks);
         for (u32 b = 0; b < g.nblocks; b++) list[b] = b;
     }
-    std::vector<u32> hin, hist;
-    std::vector<u32> force;
+    std::vector<u32> hin, hist, force;
     u32 nre = 0;
     for (const u32 b : list) {
         if (b >= g.nblocks) continue;
         const u32 nb = geo_block_n(g, b);
         ansx_blk hb;
         hin.resize(nb);
-        HIPCHK(c, hipMemcpyAsync(hin.data(), c->cur_src + (u64)b * g.block_ints, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(hin.data(), out->src + (u64)b * g.block_ints, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(&hb, (const ansx_blk*)c->blk.p + b, sizeof(hb), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         if (hb.pa_sigma == 1) continue;  // (compaction: a one-value block has no model)
@@ -1286,92 +1289,89 @@ int resolve_near(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t 
     if ((rc = ensure(c, c->force, (size_t)g.nblocks * 4))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->force.p, force.data(), (size_t)g.nblocks * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipStreamSynchronize(s));  // (force is a local)
-    c->cur_force = (const u32*)c->force.p;
-    c->cur_rf_slots = 0;
-    c->cur_pa_distinct = 0;
-    rc = encode_general(c, P, d_in, d_out, cap, out_bytes, s, seen_ns, 0);
-    c->cur_force = nullptr;
-    return rc;
+    EncodeAttempt forced;
+    forced.int_sparse = last.int_sparse;
+    forced.force = (const u32*)c->force.p;
+    return encode_general(c, P, d_in, d_out, cap, out_bytes, s, forced, out);
 }
+
+// (pa, kind, fidelity, block_ints): the key of the per-geometry hint maps
+u64 geo_key(const ansx_geo& g) { return ((u64)g.pa << 48) | ((u64)g.kind << 40) | ((u64)g.f << 32) | g.block_ints; }
 
 int encode_dev_once(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t cap, size_t* out_bytes,
     hipStream_t s)
 {
     // The first call of a geometry discovers its alphabet size with a mid-call read-back; later calls
     // are launched back to back on that hint and repeat (rarely) if the input outgrew it.
-    const u64 key = ((u64)P.g.pa << 48) | ((u64)P.g.kind << 40) | ((u64)P.g.f << 32) | P.g.block_ints;
-    u32 seen = 0;
-    int rc = ANSX_RETRY_GENERAL;
+    const u64 key = geo_key(P.g);
     const bool int_plain = P.g.kind == ANSX_INT && !P.g.pa;
-    c->cur_int_sparse = int_plain && c->int_sparse_hint.count(key) != 0;
     const auto it = c->ns_hint.find(key);
     const u32 hint = c->dbg.ns_hint ? c->dbg.ns_hint : (it != c->ns_hint.end() ? it->second : 0u);
     const bool eligible = !P.plain && hint != 0 && (P.NSP <= 4096 || (P.NSP <= 16384 && P.g.kind != ANSX_INT && !P.g.pa)) && !c->dbg.encode_gtab16 && !c->dbg.table16_fixup
         && !c->dbg.model_sync;  // (with compaction too: the hint then describes the alphabets of the rank-remapped blocks)
-    const auto rit = c->rf_hint.find(key);
-    c->cur_rf_slots = (eligible && P.g.kind == ANSX_RFOLD && rit != c->rf_hint.end()) ? rf_opt_slots(rit->second, fold_T(P.g.f)) : 0u;
-    c->cur_pa_distinct = (eligible && P.g.pa && rit != c->rf_hint.end()) ? rit->second : 0u;
-    // candidates per block for the fast model path: one more than the largest index chosen so far, 4..8 lanes
-    // (fewer than 4 would leave the wave's lanes to more blocks than its LDS rows); above 8 the exact path stays
-    const auto tit = c->t_hint.find(key);
-    const u32 tcount = c->dbg.t_hint ? c->dbg.t_hint : (tit != c->t_hint.end() ? tit->second : 0u);
-    c->cur_nt = (eligible && !c->dbg.no_fast_model && tcount != 0 && tcount <= 8) ? std::max<u32>(4u, tcount) : 0u;
+    // (k_model_fused: the LDS-resident single-kernel model, measured slower than the five tailored
+    // kernels -- DESIGN.md section 6 -- and therefore opt-in)
+    const bool fused = eligible && c->dbg.model_fused && P.g.block_ints <= ANSX_MODEL_MAX_BLOCK && !P.g.pa;
+    EncodeAttempt exact;  // discovery: nothing assumed
+    exact.int_sparse = int_plain && c->int_sparse_hint.count(key) != 0;
+    EncodeAttempt hinted = exact;  // ... and what the geometry's hints allow
     if (eligible) {
-        u32 ns_cap = (hint + 7u) & ~7u;
-        if (ns_cap < 64) ns_cap = 64;
-        if (ns_cap > P.NSP) ns_cap = P.NSP;
-        // (k_model_fused: the LDS-resident single-kernel model, measured slower than the five tailored
-        // kernels -- DESIGN.md section 6 -- and therefore opt-in)
-        if (c->dbg.model_fused && P.g.block_ints <= ANSX_MODEL_MAX_BLOCK && !P.g.pa)
-            rc = encode_fast(c, P, d_in, d_out, cap, out_bytes, s, ns_cap, &seen);
-        else
-            rc = encode_general(c, P, d_in, d_out, cap, out_bytes, s, &seen, ns_cap);
+        hinted.ns_cap = std::min<u32>(P.NSP, std::max<u32>(64u, (hint + 7u) & ~7u));
+        const auto rit = c->rf_hint.find(key);
+        if (P.g.kind == ANSX_RFOLD && rit != c->rf_hint.end()) hinted.rf_slots = rf_opt_slots(rit->second, fold_T(P.g.f));
+        if (P.g.pa && rit != c->rf_hint.end()) hinted.pa_distinct = rit->second;
+        // candidates per block for the fast model path: one more than the largest index chosen so far, 4..8 lanes
+        // (fewer than 4 would leave the wave's lanes to more blocks than its LDS rows); above 8 the exact path stays
+        const auto tit = c->t_hint.find(key);
+        const u32 tcount = c->dbg.t_hint ? c->dbg.t_hint : (tit != c->t_hint.end() ? tit->second : 0u);
+        if (!c->dbg.no_fast_model && tcount != 0 && tcount <= 8) hinted.nt = std::max<u32>(4u, tcount);
     }
-    bool missed = false;
-    u32 path = !eligible ? 0u : (c->dbg.model_fused && P.g.block_ints <= ANSX_MODEL_MAX_BLOCK && !P.g.pa ? 2u : (c->used_fast ? 5u : 1u));
+    EncodeOutcome o;
+    int rc = ANSX_RETRY_GENERAL;
+    if (eligible) rc = (fused ? encode_fast : encode_general)(c, P, d_in, d_out, cap, out_bytes, s, hinted, &o);
+    u32 path = !eligible ? 0u : (fused ? 2u : (o.used_fast ? 5u : 1u));
+    const bool missed = eligible && rc == ANSX_RETRY_GENERAL;
     if (rc == ANSX_RETRY_GENERAL) {
-        missed = eligible;
-        c->cur_rf_slots = 0;
-        c->cur_pa_distinct = 0;
         path = eligible ? path | 16u : 0u;
-        rc = encode_general(c, P, d_in, d_out, cap, out_bytes, s, &seen, 0);
+        rc = encode_general(c, P, d_in, d_out, cap, out_bytes, s, exact, &o);
     }
     // Plain ANSint: the dense model takes values below 16384; a call with larger ones is repeated in rank space, and so is
     // every later call of the geometry from the start -- unless its values turn out small, where the dense form (whose
     // containers carry parse hints) is the one a fresh context would have written: equal inputs, equal bytes.
-    if (int_plain && !c->cur_int_sparse && rc == ANSX_ERR_DOMAIN) {
-        c->cur_int_sparse = true;
+    if (int_plain && !exact.int_sparse && rc == ANSX_ERR_DOMAIN) {
+        exact.int_sparse = true;
         c->int_sparse_hint.insert(key);
-        rc = encode_general(c, P, d_in, d_out, cap, out_bytes, s, &seen, 0);
-    } else if (int_plain && c->cur_int_sparse && rc == ANSX_OK && c->h_pin[ANSX_G_VMAX] < P.NSP) {
-        c->cur_int_sparse = false;
+        rc = encode_general(c, P, d_in, d_out, cap, out_bytes, s, exact, &o);
+    } else if (int_plain && exact.int_sparse && rc == ANSX_OK && o.flags[ANSX_G_VMAX] < P.NSP) {
+        exact.int_sparse = false;
         c->int_sparse_hint.erase(key);
-        rc = encode_general(c, P, d_in, d_out, cap, out_bytes, s, &seen, 0);
+        rc = encode_general(c, P, d_in, d_out, cap, out_bytes, s, exact, &o);
     }
-    if (c->cur_int_sparse) path |= 256u;  // plain ANSint modelled in rank space
-    if (c->sp_retries) path |= 512u, c->sp_retries = 0;  // ... and repeated with the full-size prelude writer
-    if (rc == ANSX_RETRY_WIDE) return rc;
+    if (exact.int_sparse) path |= 256u;  // plain ANSint modelled in rank space
     // close calls of the stop rule (counted by the exact kernels only; the fast path repeats on them): the host decides
     u32 redecided = 0;
-    const u32 near_blocks = c->h_pin[ANSX_G_NEAR];  // (a forced repeat skips the rule for the blocks it forces)
-    if (rc == ANSX_OK && near_blocks != 0) rc = resolve_near(c, P, d_in, d_out, cap, out_bytes, s, &seen, &redecided);
+    const u32 near_blocks = o.flags[ANSX_G_NEAR];  // (a forced repeat skips the rule for the blocks it forces)
+    if (rc == ANSX_OK && near_blocks != 0) rc = resolve_near(c, P, d_in, d_out, cap, out_bytes, s, exact, &o, &redecided);
     if (rc == ANSX_RETRY_WIDE) return rc;
+    if (o.sp_repeated) path |= 512u;  // ... and repeated with the full-size prelude writer
+    // (from here on `o` is the outcome of the attempt whose container is returned)
     c->last.host_redecided = redecided;
-    c->last.path = path | (c->used_pc ? 128u : 0u);
-    c->last.max_nsyms = c->h_pin[ANSX_G_MAXNSYMS];
-    c->last.max_log2_frame = c->h_pin[ANSX_G_MAXLOGM];
+    c->last.path = path | (o.used_pc ? 128u : 0u);
+    c->last.max_nsyms = o.flags[ANSX_G_MAXNSYMS];
+    c->last.max_log2_frame = o.flags[ANSX_G_MAXLOGM];
     c->last.near_threshold_decisions = near_blocks;
     if (rc == ANSX_OK && !P.plain) {
         // a miss raises the hint past what was seen, so inputs whose alphabets creep upwards do not
         // miss on every call
+        const u32 seen = o.flags[ANSX_G_MAXNSYMS];
         const u32 want = missed ? seen + seen / 8 + 8 : seen;
         u32& h = c->ns_hint[key];
         if (want > h) h = want;
         u32& th = c->t_hint[key];
-        const u32 wantt = c->h_pin[ANSX_G_MAXT] + 1u + (missed ? 1u : 0u);
+        const u32 wantt = o.flags[ANSX_G_MAXT] + 1u + (missed ? 1u : 0u);
         if (wantt > th) th = wantt;
         if (P.g.kind == ANSX_RFOLD || P.g.pa) {
-            const u32 d = c->h_pin[ANSX_G_RFDIST];
+            const u32 d = o.flags[ANSX_G_RFDIST];
             u32& r = c->rf_hint[key];
             const u32 wantd = missed ? d + d / 8 + 8 : d;
             if (wantd > r) r = wantd;
@@ -1386,7 +1386,7 @@ int encode_dev(ansx_ctx* c, const Plan& P0, const u32* d_in, u8* d_out, size_t c
 {
     Plan P = P0;
     if (!P.plain) {
-        const u64 key = ((u64)P.g.pa << 48) | ((u64)P.g.kind << 40) | ((u64)P.g.f << 32) | P.g.block_ints;
+        const u64 key = geo_key(P.g);
         const size_t stream_bound = block_bound(P.g.kind, P.g.f, P.g.block_ints, P.g.pa != 0) + 16;
         const bool must = P.g.kind == ANSX_INT || stream_bound >= ((size_t)1 << ANSX_CK_CURSOR_BITS) || c->dbg.wide_restart;
         // The hint only picks which attempt runs FIRST; the format that is returned is a function of the input and the
