@@ -27,7 +27,7 @@ EXPORTS = [
     "ansx_workspace_bytes", "ansx_host_log2", "ansx_selftest_log2", "ansx_selftest_div", "ansx_debug_set",
     "ansx_generate_dev", "ansx_generate_host", "ansx_last_encode_stats", "ansx_merge_containers_dev",
     "ansx_zipf_from_uniform", "ansx_gather_containers", "ansx_last_gather_ranks", "ansx_decode_ranges_dev",
-    "ansx_decode_device_ranges_dev", "ansx_decode_batch_dev",
+    "ansx_decode_device_ranges_dev", "ansx_decode_batch_dev", "ansx_encode_batch_dev",
 ]
 
 
@@ -123,6 +123,9 @@ def lib():
     L.ansx_decode_batch_dev.restype = C.c_int
     L.ansx_decode_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, sz, vp, C.POINTER(C.c_uint64),
                                         C.POINTER(sz), vp]
+    L.ansx_encode_batch_dev.restype = C.c_int
+    L.ansx_encode_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz),
+                                        C.POINTER(Opts), vp]
     L.ansx_container_info.restype = C.c_int
     L.ansx_container_info.argtypes = [vp, sz, C.POINTER(ContainerHeader)]
     L.ansx_profile_enable.restype = C.c_int

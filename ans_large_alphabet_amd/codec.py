@@ -206,6 +206,32 @@ class _Codec:
             raise err
         return offsets
 
+    def encode_batch_dev(self, in_ptr, offsets, out_ptr, out_capacity, stream=None):
+        """A batch of lists in one call: list i is ints [offsets[i], offsets[i + 1]) of the device array at in_ptr
+        (offsets: len(lists) + 1 non-decreasing ints, the layout decode_batch_dev returns; no list may be empty).
+        Container i -- byte for byte what encode_dev writes for list i -- goes to out_ptr + out_offsets[i] (16-byte
+        aligned, back to back, zero padding in between) with out_bytes[i] bytes; sum(rup16(bound(n_i))) is always enough
+        out_capacity.  Returns (out_offsets, out_bytes): np.uint64 of len(lists) + 1 (the last is the total) and of
+        len(lists).  An AnsxError carries .index: the list an argument check or a per-list encode refused, None when
+        the error was found on the device in a pass over many lists."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise ValueError("offsets needs at least one entry (count + 1)")
+        count = offsets.size - 1
+        out_offsets = np.zeros(count + 1, dtype=np.uint64)
+        out_bytes = np.zeros(count, dtype=np.uint64)
+        total = C.c_size_t(0)
+        bad = C.c_size_t(count)
+        st = L.lib().ansx_encode_batch_dev(self._ctx().handle, self.KIND, self.f, in_ptr, offsets.ctypes.data, count, out_ptr,
+                                           int(out_capacity), out_offsets.ctypes.data,
+                                           out_bytes.ctypes.data if count else None, C.byref(total), C.byref(bad),
+                                           C.byref(self.opts), stream)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".encode_batch_dev")
+            err.index = int(bad.value) if bad.value < count else None
+            raise err
+        return out_offsets, out_bytes
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

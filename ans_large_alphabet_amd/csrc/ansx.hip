@@ -29,6 +29,7 @@
 #include "ansx_intsparse.h"
 #include "ansx_ranges.h"
 #include "ansx_batch.h"
+#include "ansx_encbatch.h"
 
 namespace {
 
@@ -77,6 +78,7 @@ struct ansx_ctx {
     DevBuf rng_plan, rng_cont, rng_list;  // ansx_decode_ranges_dev: flags + block list + range pieces, sub-container, its ints
     DevBuf rng_dev;                       // ansx_decode_device_ranges_dev: the device planner's workspace
     DevBuf bat_hdr;                       // ansx_decode_batch_dev: input addresses and headers of the batch
+    DevBuf enb_plan, enb_wc;              // ansx_encode_batch_dev: a pass's plan and results; its restart points and hints (work area)
     u8* rng_pin = nullptr;                // ... and the pinned host image of rng_plan (an asynchronous upload from
     size_t rng_pin_cap = 0;               //     pageable memory is staged by the runtime: 0.666 -> 0.618 ms at 4096 ranges)
     u32* h_pin = nullptr;  // pinned: [0..3] gflags, [4..7] result (2 x u64), [8..] header scratch
@@ -95,6 +97,12 @@ struct ansx_ctx {
     std::set<u64> wide_hint;     // geometries that met a frame above 2^16: wide restart points from the start
     std::map<u64, u32> t_hint;   // largest chosen candidate index t (frame M0 * 2^t) + 1 seen per geometry: lanes per block of k_candidates
     std::set<u64> int_sparse_hint;  // plain-ANSint geometries whose values outgrew the dense 16384-symbol model: rank space from the start
+    // ansx_encode_batch_dev learns in a slot of its own: the five hint sets above are exchanged with these for the
+    // length of a batch call (EncBatchHints), so nothing a batch sees reaches a later ansx_encode_dev and vice versa
+    struct {
+        std::map<u64, u32> ns_hint, rf_hint, t_hint;
+        std::set<u64> wide_hint, int_sparse_hint;
+    } bat;
     ansx_encode_stats last = {};
     // Block-range pipeline of the fast model path (model_fast): two side streams and the events of its fork and join,
     // created by the first call that needs them (pipeline_prepare) and destroyed with the context, never per call.
@@ -139,7 +147,7 @@ struct ansx_ctx {
         u32 cand_chains = 0;          // ANSX_CAND_CHAINS: 1 | 2 recurrences per lane in k_candidates (0 = by the call's size)
         double fast_guard = ANSX_FAST_GUARD;  // ANSX_FAST_GUARD: relative guard band of the fast model path's stop rule (tests widen it)
         int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
-        u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
+        u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
     } dbg;
 };
 
@@ -243,6 +251,8 @@ struct Plan {
     // (make_plan has no part in it), and the ints of the output it lays out
     const ansx_blk_out* bout = nullptr;
     u64 bout_ints = 0;
+    // encode of a batch pass (ansx_encbatch.h): the pass's work list and where its containers go; null everywhere else
+    const struct EncBatchPass* bat = nullptr;
 };
 
 Layout layout_of(const ansx_geo& g, bool plain)
@@ -316,6 +326,7 @@ int make_plan(int kind, int f, size_t n, const ansx_opts* opts, Plan* P)
     g.trusted_index = 0;  // (set by decode_dev on the single-stream path only, where the host writes the two entries)
     g.pad_ = 0;
     g.bout = nullptr;     // (set by decode_dev on a batch pass only)
+    g.bin = nullptr;      // (set by encode_batch_pass only)
     g.map = kind == ANSX_MSB ? map_msb() : (kind == ANSX_INT ? map_int() : map_fold((u32)f));
     P->g = g;
     // symbol-array stride: the reference's MAX_SIGMA (ans_fold.hpp:70; ans_msb.hpp:28 has 1280)
@@ -456,7 +467,8 @@ static int launch_f64_encoder(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u32
     auto pc_lds = [&](u32 pairs, u32 S) { return (size_t)pairs * 16 * rowwords * 4 + (size_t)pairs * (2 * S * 1024 + (S == 8 ? 16 * 144 : 0)); };
     u32 pairs = 0, S = 0;
     // (block_ints <= 2^22: the stand-in for a neutral step of a 2^16 frame lets the state creep by 2^-16 per step, see the kernel)
-    const bool pc_geo = !c->dbg.no_pc && g.block_ints % 128u == 0 && g.block_ints <= (1u << 22) && (u64)scr_stride * 16 < 0x40000000ull;
+    // (a batch pass: its blocks are not block_ints apart in the input -- k_encode<MODE> reads them through the per-block table)
+    const bool pc_geo = !c->dbg.no_pc && !g.bin && g.block_ints % 128u == 0 && g.block_ints <= (1u << 22) && (u64)scr_stride * 16 < 0x40000000ull;
     if (pc_geo && (!c->dbg.no_pc_auto || c->dbg.use_pc || c->dbg.force_pc) && mode1 && pc_lds(4, 8) <= 160 * 1024
         && (((NB + 63) / 64) * 2 >= (u32)c->num_cus || c->dbg.force_pc))
         pairs = 4, S = 8;  // (A) the chip-filling form: 0.66 against k_encode<1>'s 0.71 ms on the headline workload since the producer
@@ -553,6 +565,15 @@ struct EncodeWs {
 
 u64 scratch_stride(const ansx_geo& g) { return rup(block_bound(g.kind, g.f, g.block_ints, g.pa != 0) + 16, 256); }
 
+// A pass of ansx_encode_batch_dev (encode_batch_pass builds it; the phases reach it through Plan::bat)
+struct EncBatchPass {
+    const ansx_blk_in* hblk;  // the work list on the host (resolve_near reads a block back through it)
+    u32 longest;              // ints of the pass's longest block: sizes the stream scratch stride
+    ansx_encb_args A;         // device pointers of the plan, the results and the work area
+    u8* d_out;                // the caller's buffer
+    const ansx_encb_res* hres;  // pinned: the results, read back with the attempt's flag words
+};
+
 // the flag words (and the result behind them), read back into the attempt's outcome: a host wait
 int read_flags(ansx_ctx* c, const EncodeWs& W, u32 words)
 {
@@ -572,7 +593,8 @@ int encode_begin(ansx_ctx* c, EncodeWs& W)
     const bool sp = W.out->sp_repeated;
     *W.out = EncodeOutcome();
     W.out->sp_repeated = sp;
-    W.scr_stride = scratch_stride(g);
+    // (a batch pass: slots as long as its longest block needs, not as block_ints would)
+    W.scr_stride = P.bat ? rup(block_bound(g.kind, g.f, P.bat->longest, g.pa != 0) + 16, 256) : scratch_stride(g);
     if (!P.plain && W.cap < P.lay.payload_off) return ANSX_ERR_CAPACITY;
     int rc;
     if ((rc = ensure(c, c->hist, (size_t)NB * NSP * 4))) return rc;
@@ -1044,7 +1066,19 @@ int encode_finish(ansx_ctx* c, EncodeWs& W, size_t* out_bytes)
     const u32 NB = g.nblocks;
     hipStream_t s = W.s;
     u64* boff = P.plain ? W.boff_ws : (u64*)(W.d_out + P.lay.index_off);
-    if (NB <= 65536u) {
+    if (P.bat) {
+        // a batch pass: every list's container straight from the stream scratch into the caller's buffer (ansx_encbatch.h);
+        // the results ride on the read-back of the flag words
+        ansx_encb_args A = P.bat->A;
+        A.ns_cap = W.a->ns_cap;
+        A.forced = W.a->force != nullptr ? 1u : 0u;
+        // (the lists' maxima are gathered with atomics: every attempt of the pass starts them afresh)
+        HIPCHK(c, hipMemsetAsync(A.mx, 0, sizeof(ansx_encb_max) * (size_t)A.nl, s));
+        LAUNCH(c, "k_encb_scan", k_encb_scan, 1, 1024, 0, s, g, A, (const ansx_blk*)W.blk, (const u32*)W.enc_sizes, W.result, W.gflags);
+        LAUNCH(c, "k_encb_write", k_encb_write, NB, 256, 0, s, g, A, (const u32*)W.enc_sizes, (const u8*)c->scratch.p, W.scr_stride,
+            P.bat->d_out);
+        HIPCHK(c, hipMemcpyAsync((void*)P.bat->hres, A.res, sizeof(ansx_encb_res) * ((size_t)A.nl + 1), hipMemcpyDeviceToHost, s));
+    } else if (NB <= 65536u) {
         LAUNCH(c, "k_assemble", k_assemble, NB, 256, 0, s, g, (const u32*)W.enc_sizes, (const unsigned long long*)W.enc_gsums, boff, W.result,
             (const u8*)c->scratch.p, W.scr_stride, W.d_out, (u64)P.lay.payload_off, (u64)W.cap, W.gflags, P.plain ? 0u : 1u);
     } else {
@@ -1258,10 +1292,12 @@ int resolve_near(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t 
     u32 nre = 0;
     for (const u32 b : list) {
         if (b >= g.nblocks) continue;
-        const u32 nb = geo_block_n(g, b);
+        // (g.bin is a device table: a batch pass keeps the host's copy)
+        const u32 nb = P.bat ? P.bat->hblk[b].n : geo_block_n(g, b);
+        const u64 first = P.bat ? P.bat->hblk[b].off : (u64)b * g.block_ints;
         ansx_blk hb;
         hin.resize(nb);
-        HIPCHK(c, hipMemcpyAsync(hin.data(), out->src + (u64)b * g.block_ints, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(hin.data(), out->src + first, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(&hb, (const ansx_blk*)c->blk.p + b, sizeof(hb), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         if (hb.pa_sigma == 1) continue;  // (compaction: a one-value block has no model)
@@ -1284,7 +1320,10 @@ int resolve_near(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t 
         }
     }
     *redecided = nre;
-    if (nre == 0) return ANSX_OK;
+    // (a batch pass with close calls has written nothing yet -- k_encb_scan holds such an attempt back, so that a repeat
+    // with other sizes leaves no stale byte behind the total: it is always repeated, with whatever the host decided)
+    if (nre == 0 && !P.bat) return ANSX_OK;
+    if (force.empty()) force.assign(g.nblocks, 0u);
     int rc;
     if ((rc = ensure(c, c->force, (size_t)g.nblocks * 4))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->force.p, force.data(), (size_t)g.nblocks * 4, hipMemcpyHostToDevice, s));
@@ -1311,7 +1350,7 @@ int encode_dev_once(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size
         && !c->dbg.model_sync;  // (with compaction too: the hint then describes the alphabets of the rank-remapped blocks)
     // (k_model_fused: the LDS-resident single-kernel model, measured slower than the five tailored
     // kernels -- DESIGN.md section 6 -- and therefore opt-in)
-    const bool fused = eligible && c->dbg.model_fused && P.g.block_ints <= ANSX_MODEL_MAX_BLOCK && !P.g.pa;
+    const bool fused = eligible && c->dbg.model_fused && P.g.block_ints <= ANSX_MODEL_MAX_BLOCK && !P.g.pa && !P.bat;
     EncodeAttempt exact;  // discovery: nothing assumed
     exact.int_sparse = int_plain && c->int_sparse_hint.count(key) != 0;
     EncodeAttempt hinted = exact;  // ... and what the geometry's hints allow
@@ -2274,6 +2313,180 @@ int decode_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const siz
     return ANSX_OK;
 }
 
+// --------------------------------------------------------------------------------- batch encode
+// ansx_encode_batch_dev: the batch in order, cut at list boundaries into passes of at most P
+// blocks -> per pass one plan upload, the ordinary encode phases over its work list (ansx_geo::bin), k_encb_scan +
+// k_encb_write assemble every list's container in place, one read-back.  A list of more than P blocks, and every list
+// of a form without a batched path, goes through encode_dev into its place.
+
+// For the length of a batch call the context's hint sets are the batch's own, and what ansx_last_encode_stats reports is
+// put back: a later ansx_encode_dev finds the context as it left it.
+struct EncBatchHints {
+    ansx_ctx* c;
+    ansx_encode_stats last;
+    explicit EncBatchHints(ansx_ctx* c_) : c(c_), last(c_->last) { swap(); }
+    ~EncBatchHints()
+    {
+        swap();
+        c->last = last;
+    }
+    void swap()
+    {
+        std::swap(c->ns_hint, c->bat.ns_hint);
+        std::swap(c->rf_hint, c->bat.rf_hint);
+        std::swap(c->t_hint, c->bat.t_hint);
+        std::swap(c->wide_hint, c->bat.wide_hint);
+        std::swap(c->int_sparse_hint, c->bat.int_sparse_hint);
+    }
+};
+
+// A list with this many full blocks amortises its own launches and read-back, and the ordinary path gives it the
+// encoder forms a pass cannot take (the buffer-view pipeline of k_encode<1>, k_encode_pc): the (C) criterion of
+// launch_f64_encoder.  Such a list goes through encode_dev into its place.
+#define ANSX_ENCB_LONG_BLOCKS 16u
+
+// geometries the batched path takes: the LDS-model codecs without compaction
+bool encode_batch_form(const ansx_geo& g)
+{
+    return !g.pa && (g.kind == ANSX_MSB || (g.kind == ANSX_FOLD && g.f <= 5));
+}
+
+// One pass: lists [l0, l1) of the batch, NB blocks in all, containers from byte `base` of d_out on.  Writes their
+// offsets and sizes and returns the pass's bytes (a multiple of 16) in *pass_bytes.
+int encode_batch_pass(ansx_ctx* c, const Plan& P0, const u32* d_in, const u64* offsets, size_t l0, size_t l1, u32 NB,
+    u8* d_out, size_t cap, u64 base, u64* out_off, u64* out_bytes, u64* pass_bytes, hipStream_t s)
+{
+    int rc;
+    const u64 bi = P0.g.block_ints;
+    const u32 nl = (u32)(l1 - l0);
+    // the plan, one upload from pinned memory: blocks | lists; behind it on the device: maxima | results | block sums
+    const size_t o_l = sizeof(ansx_blk_in) * (size_t)NB, o_m = o_l + sizeof(ansx_encb_list) * ((size_t)nl + 1);
+    const size_t o_r = o_m + sizeof(ansx_encb_max) * (size_t)nl, o_s = o_r + sizeof(ansx_encb_res) * ((size_t)nl + 1);
+    const size_t plan_bytes = o_s + 8 * ((size_t)NB + 1);
+    const size_t res_bytes = sizeof(ansx_encb_res) * ((size_t)nl + 1);
+    if ((rc = ensure_pin(c, o_m + res_bytes))) return rc;
+    u8* hb = c->rng_pin;  // (nothing is pending on it: every call that uses it ends in a synchronisation)
+    ansx_blk_in* hblk = (ansx_blk_in*)hb;
+    ansx_encb_list* hl = (ansx_encb_list*)(hb + o_l);
+    u32 k = 0, longest = 0;
+    for (size_t i = l0; i < l1; i++) {
+        const u64 n = offsets[i + 1] - offsets[i];
+        hl[i - l0] = { n, k, 0 };
+        for (u64 at = 0; at < n; at += bi, k++) {
+            const u32 nb = (u32)std::min<u64>(bi, n - at);
+            hblk[k] = { offsets[i] + at, nb, (u32)(i - l0) };
+            longest = std::max(longest, nb);
+        }
+    }
+    hl[nl] = { 0, k, 0 };
+    if (k != NB) return ANSX_ERR_ARG;  // (cannot happen: the caller counted the same blocks)
+    if ((rc = ensure(c, c->enb_plan, plan_bytes))) return rc;
+    u8* dp = (u8*)c->enb_plan.p;
+    HIPCHK(c, hipMemcpyAsync(dp, hb, o_m, hipMemcpyHostToDevice, s));
+
+    // the pass's plan: any n that makes make_plan lay out exactly NB blocks (the table says how long each is); its
+    // restart points and hints go to the work area in the wide form, whatever the lists will need
+    // g.n is not the pass's ints.  What reads it: the block-range pipeline's size rule (pipeline_plan: a pass of 8192 and
+    // more blocks forks its model kernels as a list of that many full blocks would -- the ranges are block ranges, so
+    // that holds for short blocks too; not measured on a pass); k_encode's wg_sync and buffer view and k_encode_pc,
+    // all switched off by g.bin.  model_shape sizes by block_ints and the hints, not by g.n.
+    Plan P = P0;
+    P.g.n = (u64)(NB - 1) * bi + 1;
+    P.g.nblocks = NB;
+    P.g.bin = (const ansx_blk_in*)dp;
+    set_restart_format(&P, true);
+    if ((rc = ensure(c, c->enb_wc, (size_t)P.lay.payload_off + 64))) return rc;
+    u8* wc = (u8*)c->enb_wc.p;
+    const size_t stream_bound = block_bound(P.g.kind, P.g.f, P.g.block_ints, false) + 16;
+    EncBatchPass B;
+    B.hblk = hblk;
+    B.longest = longest;
+    B.A.bin = P.g.bin;
+    B.A.lists = (const ansx_encb_list*)(dp + o_l);
+    B.A.mx = (ansx_encb_max*)(dp + o_m);
+    B.A.res = (ansx_encb_res*)(dp + o_r);
+    B.A.bsum = (u64*)(dp + o_s);
+    B.A.nl = nl;
+    B.A.ns_cap = 0;
+    B.A.forced = 0;
+    // (encode_dev's rule: wide where a cursor may pass 24 bits or on request; ANSint never comes here)
+    B.A.must_wide = (stream_bound >= ((size_t)1 << ANSX_CK_CURSOR_BITS) || c->dbg.wide_restart) ? 1u : 0u;
+    B.A.wide_at = c->dbg.wide_at;
+    B.A.base = base;
+    B.A.cap = cap;
+    B.A.w_ckoff = (const u32*)(wc + P.lay.ckoff_off);
+    B.A.w_ckstate = (const u64*)(wc + P.lay.ckstate_off);
+    B.A.w_hints = (const u32*)(wc + P.lay.hint_off);
+    B.d_out = d_out;
+    B.hres = (const ansx_encb_res*)(hb + o_m);
+    P.bat = &B;
+    size_t work_bytes = 0;
+    // (the work area has no payload: its capacity is never the limit, the caller's is checked by k_encb_scan)
+    if ((rc = encode_dev_once(c, P, d_in, wc, ~(size_t)0 >> 1, &work_bytes, s))) return rc;
+    if (B.hres[nl].off != 1) return ANSX_ERR_HIP;  // (cannot happen: the host accepted an attempt the device refused)
+    for (u32 i = 0; i < nl; i++) {
+        out_off[l0 + i] = B.hres[i].off;
+        out_bytes[l0 + i] = B.hres[i].bytes;
+    }
+    *pass_bytes = B.hres[nl].bytes;
+    return ANSX_OK;
+}
+
+int encode_batch(ansx_ctx* c, const Plan& P0, const ansx_opts* opts, const u32* d_in, const u64* offsets, size_t count,
+    u8* d_out, size_t cap, u64* out_offsets, u64* out_bytes, size_t* total_bytes, size_t* bad_index, hipStream_t s)
+{
+    int rc;
+    EncBatchHints slot(c);
+    const u64 bi = P0.g.block_ints;
+    const u32 PB = c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT;
+    const bool batched = encode_batch_form(P0.g);
+    std::vector<u64> oo(count + 1), ob(count);
+    u64 cur = 0;
+    if (bad_index) *bad_index = count;
+    size_t i = 0;
+    while (i < count) {
+        const u64 n = offsets[i + 1] - offsets[i];
+        const u64 nbk = (n + bi - 1) / bi;
+        if (!batched || nbk > PB || n / bi >= ANSX_ENCB_LONG_BLOCKS) {
+            // the ordinary path, straight into the list's place
+            Plan P;
+            if (make_plan((int)P0.g.kind, (int)P0.g.f, (size_t)n, opts, &P)) return ANSX_ERR_ARG;  // (checked by the entry point)
+            size_t bytes = 0;
+            if (cur > cap) return ANSX_ERR_CAPACITY;
+            if ((rc = encode_dev(c, P, d_in + offsets[i], d_out + cur, cap - cur, &bytes, s))) {
+                if (bad_index && rc != ANSX_ERR_HIP) *bad_index = i;
+                return rc;
+            }
+            const u64 r16 = rup(bytes, 16);
+            if (cur + r16 > cap) return ANSX_ERR_CAPACITY;
+            if (r16 != bytes) HIPCHK(c, hipMemsetAsync(d_out + cur + bytes, 0, r16 - bytes, s));
+            oo[i] = cur, ob[i] = bytes;
+            cur += r16;
+            i++;
+            continue;
+        }
+        size_t j = i;
+        u64 blocks = 0;
+        while (j < count) {
+            const u64 nj = (offsets[j + 1] - offsets[j] + bi - 1) / bi;
+            if (blocks + nj > PB || (offsets[j + 1] - offsets[j]) / bi >= ANSX_ENCB_LONG_BLOCKS) break;
+            blocks += nj;
+            j++;
+        }
+        u64 pass_bytes = 0;
+        if ((rc = encode_batch_pass(c, P0, d_in, offsets, i, j, (u32)blocks, d_out, cap, cur, oo.data(), ob.data(), &pass_bytes, s)))
+            return rc;
+        cur += pass_bytes;
+        i = j;
+    }
+    HIPCHK(c, hipStreamSynchronize(s));  // (the padding behind a list of the ordinary path)
+    oo[count] = cur;
+    if (out_offsets) memcpy(out_offsets, oo.data(), 8 * (count + 1));
+    if (out_bytes) memcpy(out_bytes, ob.data(), 8 * count);
+    if (total_bytes) *total_bytes = (size_t)cur;
+    return ANSX_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -2430,6 +2643,7 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         c->rf_hint.clear();
         c->t_hint.clear();
         c->wide_hint.clear();
+        c->bat.ns_hint.clear(), c->bat.rf_hint.clear(), c->bat.t_hint.clear(), c->bat.wide_hint.clear(), c->bat.int_sparse_hint.clear();
         c->hdr_cache.clear();
         c->hdr_order.clear();
     }
@@ -2474,7 +2688,7 @@ void ansx_destroy(ansx_ctx* c)
     DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->log2lut, &c->pa_alpha, &c->pa_info, &c->pairs, &c->lg2i, &c->sizes, &c->nearlist, &c->force, &c->geo_big,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc };
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& kv : c->geo)
@@ -2600,6 +2814,42 @@ int ansx_decode_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     return decode_batch(c, kind, f, d_ins, in_bytes, count, d_out, out_capacity_ints, (u64*)offsets, (u64*)total_ints,
         bad_index, s);
+}
+
+int ansx_encode_batch_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,
+    uint8_t* d_out, size_t out_capacity, uint64_t* out_offsets, uint64_t* out_bytes, size_t* total_bytes, size_t* bad_index,
+    const ansx_opts* opts, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || count > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (count > 0 && (!d_in || !offsets || !d_out)) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_in & 3u)) return ANSX_ERR_ARG;
+    if (opts && opts->block_ints == ANSX_SINGLE_STREAM) return ANSX_ERR_ARG;  // (a batch yields containers)
+    Plan P0;
+    int rc = make_plan(kind, f, 1, opts, &P0);  // kind, fidelity and options, as for any list
+    if (rc) return rc;
+    for (size_t i = 0; i < count; i++) {
+        Plan P;
+        if (offsets[i + 1] < offsets[i]) return ANSX_ERR_ARG;
+        if (offsets[i + 1] == offsets[i] || make_plan(kind, f, (size_t)(offsets[i + 1] - offsets[i]), opts, &P)) {
+            if (bad_index) *bad_index = i;  // an empty list (or one no container can hold), as ansx_encode_dev refuses n == 0
+            return ANSX_ERR_ARG;
+        }
+    }
+    if (count == 0) {
+        if (out_offsets) out_offsets[0] = 0;
+        if (total_bytes) *total_bytes = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    try {
+        return encode_batch(c, P0, opts, d_in, (const u64*)offsets, count, d_out, out_capacity, (u64*)out_offsets,
+            (u64*)out_bytes, total_bytes, bad_index, s);
+    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge batch)
+        c->last_hip = (int)hipErrorOutOfMemory;
+        return ANSX_ERR_HIP;
+    }
 }
 
 int ansx_encode(ansx_ctx* c, int kind, int f, const uint32_t* in, size_t n, uint8_t* out, size_t cap,
@@ -2880,7 +3130,7 @@ size_t ansx_workspace_bytes(const ansx_ctx* c)
     const DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->pa_alpha, &c->pa_info, &c->pairs, &c->sizes,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc };
     size_t t = 0;
     for (const DevBuf* b : bufs) t += b->cap;
     return t;

@@ -319,6 +319,8 @@ struct ansx_geo {
     u32 pad_;
     const struct ansx_blk_out* bout;  // decode: per-block lengths and output offsets (a pass of ansx_decode_batch_dev,
                                       // ansx_batch.h); null everywhere else: block b then has geo_block_n ints at b * block_ints
+    const struct ansx_blk_in* bin;    // encode: per-block lengths and input offsets (a pass of ansx_encode_batch_dev,
+                                      // ansx_encbatch.h); null everywhere else
 };
 
 // One block of a batch pass: its ints and where they start in the pass's output.  Blocks of many containers share one
@@ -364,15 +366,26 @@ ANSX_HD bool index_entry_ok(const ansx_geo& g, u32 b, u64 a, u64 e)
     return !bad;
 }
 
+// One block of an encode batch pass: its ints and where they start in the caller's input.  Blocks of many lists share
+// one work list there; a list may start at any int, so nothing about the alignment of `off` is promised.
+struct ansx_blk_in {
+    u64 off;   // first int in the input
+    u32 n;     // ints
+    u32 list;  // the list of the pass it belongs to
+};
+
 ANSX_HD u32 geo_block_n(const ansx_geo& g, u32 b)
 {
     if (g.bout) return g.bout[b].n;
+    if (g.bin) return g.bin[b].n;
     u64 start = (u64)b * g.block_ints;
     u64 rem = g.n - start;
     return (u32)(rem < g.block_ints ? rem : g.block_ints);
 }
 // first output int of block b (decode side)
 ANSX_HD u64 geo_block_out(const ansx_geo& g, u32 b) { return g.bout ? g.bout[b].off : (u64)b * g.block_ints; }
+// first input int of block b (encode side)
+ANSX_HD u64 geo_block_in(const ansx_geo& g, u32 b) { return g.bin ? g.bin[b].off : (u64)b * g.block_ints; }
 // decoder segments of a block with nb ints
 ANSX_HD u32 geo_nseg(u32 nb, u32 ckpt)
 {

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void k_fold_hist(const u32* __restrict__ in, a
     const u64 start = (u64)c * chunk;
     if (start >= nb) return;
     const u32 len = (u32)((nb - start) < chunk ? (nb - start) : chunk);
-    const u32* src = in + (u64)b * g.block_ints + start;
+    const u32* src = in + geo_block_in(g, b) + start;
     // sum_here (alphabets <= 2048 slots): 4 histogram copies, lane l counts into copy l & 3.  With
     // skewed data a dozen lanes of every ds_add hit the hottest bin and the LDS unit serialises
     // them; copies are ANSX_HCOPY_PAD words apart modulo the 32 banks so the same symbol's four
@@ -1801,7 +1801,7 @@ __global__ __launch_bounds__(256) void k_encode(const u32* __restrict__ in, ansx
         return;
     }
     const u32 nb = geo_block_n(g, b);
-    const u32* src = in + (u64)b * g.block_ints;
+    const u32* src = in + geo_block_in(g, b);
     enc_tab<F64> tab;
     if constexpr (MODE == 1) tab.t = wtab + (lane >> 2) * lds_stride;
     else if constexpr (MODE == 2) {
@@ -1895,7 +1895,7 @@ __global__ __launch_bounds__(256) void k_encode(const u32* __restrict__ in, ansx
         }
         bool piped = false;
         if constexpr (MODE == 1) {
-            if (ck_per_batch) {
+            if (ck_per_batch && !g.bin) {  // (a batch pass: the wave's 16 blocks are not block_ints apart -- the per-lane loads below)
                 piped = true;
                 // Inputs come through a buffer view of the wave's 16 blocks, one load per step straight into the
                 // registers a sub-batch of 8 steps just released: they are first read 21 steps (>= 84 vector-memory
@@ -2101,7 +2101,7 @@ __global__ __launch_bounds__(256) void k_encode(const u32* __restrict__ in, ansx
             for (int j = 0; j < ANSX_ENC_U; j++) raw1[j] = tab.fetchp(f, xa[j], raw1l[j]);
         }
         // (waves of one workgroup stay in step, see the scheduled loop above)
-        const bool wg_sync2 = blockDim.x > 64 && ((u64)first_block + (u64)(blockIdx.x + 1) * (blockDim.x >> 2)) * g.block_ints <= g.n;
+        const bool wg_sync2 = blockDim.x > 64 && !g.bin && ((u64)first_block + (u64)(blockIdx.x + 1) * (blockDim.x >> 2)) * g.block_ints <= g.n;
         while (gi) {
             if (wg_sync2) __syncthreads();
             const u32 top = gi;  // this super-batch encodes groups top-1 ... top-XB

@@ -229,6 +229,43 @@ int ansx_decode_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* 
     size_t count, uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_index,
     void* stream);
 
+/* A batch of lists in one call: the writer's side of ansx_decode_batch_dev (posting lists, column chunks).  List i is
+ * d_in[offsets[i] .. offsets[i + 1]); offsets is a HOST array of count + 1 non-decreasing int offsets -- the layout
+ * ansx_decode_batch_dev returns -- and d_in is 4-byte aligned device memory: a list may start at any int.  Container i
+ * is written to d_out + out_offsets[i] (d_out: 16-byte aligned): out_offsets[i] is a multiple of 16, the containers
+ * stand in batch order, back to back, out_bytes[i] is container i's exact size, and the padding bytes in between are
+ * zero; out_offsets[count] and *total_bytes are the end of the last container rounded up to 16.  out_offsets (count + 1)
+ * and out_bytes (count) are optional HOST arrays; d_out + out_offsets[i] with out_bytes[i] feed ansx_decode_batch_dev
+ * directly.  Container i is byte for byte what ansx_encode_dev(kind, fidelity, list i, opts) writes from a fresh
+ * context: header (max_nsyms, max_present_m1 and max_log2_frame are maxima over that list's own blocks), index,
+ * restart points, parse hints and payload; its restart points are wide exactly when that list alone would have had
+ * wide ones, so two lists of one batch may differ in form.
+ * Capacity: sum_i rup16(ansx_bound(kind, fidelity, n_i, opts)), rup16 = rounded up to a multiple of 16, is always
+ * enough.
+ * Errors decided before the context is touched (ANSX_ERR_ARG): a null ctx; a null d_in, offsets or d_out with
+ * count > 0; a misaligned pointer; count > UINT32_MAX; decreasing offsets; an empty list -- *bad_index (optional) is
+ * then the first empty list, as ansx_encode_dev refuses n == 0; a bad kind, fidelity or options, as for
+ * ansx_encode_dev; opts->block_ints == ANSX_SINGLE_STREAM (a batch yields containers).  count == 0: ANSX_OK, total 0,
+ * nothing launched.
+ * Errors found on the device: ANSX_ERR_DOMAIN, ANSX_ERR_MODEL, ANSX_ERR_CAPACITY, with *bad_index = count unless the
+ * list is known (one that was encoded on its own, see below).  d_out is then unspecified, but nothing is ever written
+ * at or beyond d_out + out_capacity.  The context stays usable after any error.
+ * How the work is done.  ANSX_FOLD with fidelity 1..5 and ANSX_MSB, without compaction, take the batched path: the
+ * lists are grouped, in batch order and cut at list boundaries only, into passes of at most 16384 blocks
+ * (ANSX_BATCH_PASS_BLOCKS, the key ansx_decode_batch_dev uses); the model, prelude and encoder kernels run once per
+ * pass over all its blocks, one kernel pair assembles every container of the pass in place, and one read-back per pass
+ * returns its status, offsets and sizes.  A list of 16 or more full blocks (or of more than one pass's blocks) is
+ * encoded by the ordinary path into its place: it amortises its own overheads, at the cost of a call of ansx_encode_dev.  ANSX_RFOLD, ANSX_INT, compaction and fidelity 6, 7 have NO batched
+ * path yet: they are accepted and bit-identical, but every list is encoded on its own inside the call, at the cost
+ * of a loop of ansx_encode_dev.  Workspace: bounded by one pass (or the largest single list), not by the batch.
+ * No trace: the call keeps the alphabet and frame hints it learns in a slot of its own and puts
+ * ansx_last_encode_stats back, so a later ansx_encode_dev behaves -- path and bytes -- as if the batch call had not
+ * happened; a batch of short lists does not teach the context a small alphabet.  Synchronous, like ansx_encode_dev;
+ * the input is read on `stream`. */
+int ansx_encode_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t* d_in, const uint64_t* offsets, size_t count,
+    uint8_t* d_out, size_t out_capacity, uint64_t* out_offsets, uint64_t* out_bytes, size_t* total_bytes, size_t* bad_index,
+    const ansx_opts* opts, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
