@@ -28,6 +28,7 @@ EXPORTS = [
     "ansx_generate_dev", "ansx_generate_host", "ansx_last_encode_stats", "ansx_merge_containers_dev",
     "ansx_zipf_from_uniform", "ansx_gather_containers", "ansx_last_gather_ranks", "ansx_decode_ranges_dev",
     "ansx_decode_device_ranges_dev", "ansx_decode_batch_dev", "ansx_encode_batch_dev",
+    "ansx_decode_batch_ranges_dev",
 ]
 
 
@@ -123,6 +124,9 @@ def lib():
     L.ansx_decode_batch_dev.restype = C.c_int
     L.ansx_decode_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, sz, vp, C.POINTER(C.c_uint64),
                                         C.POINTER(sz), vp]
+    L.ansx_decode_batch_ranges_dev.restype = C.c_int
+    L.ansx_decode_batch_ranges_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp,
+                                               C.POINTER(C.c_uint64), C.POINTER(sz), C.POINTER(sz), vp]
     L.ansx_encode_batch_dev.restype = C.c_int
     L.ansx_encode_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz),
                                         C.POINTER(Opts), vp]

@@ -206,6 +206,44 @@ class _Codec:
             raise err
         return offsets
 
+    def decode_batch_ranges_dev(self, in_ptrs, in_bytes, src, first, count, out_ptr, out_capacity, stream=None):
+        """Ranges of a batch of containers in one call: range i is ints [first[i], first[i] + count[i]) of container
+        src[i] of the batch in_ptrs / in_bytes (as decode_batch_dev; a container no range names is not looked at, its
+        pointer may be 0) and goes to ints [offsets[i], offsets[i + 1]) of out_ptr (out_capacity ints).  Decodes only
+        the blocks the ranges touch.  Returns offsets, np.uint64 of len(src) + 1 (the last is the total).  out_ptr=None
+        with out_capacity=0 is a size query.  An AnsxError carries .bad_container / .bad_range where the call set
+        them (None otherwise; a format error found on the device has .bad_container = len(in_ptrs)); ERR_CAPACITY
+        also .needed = the total and .offsets."""
+        ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
+        if ptrs.size != sizes.size:
+            raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
+        src = np.ascontiguousarray(src, dtype=np.uint32).reshape(-1)
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+        count = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
+        if not src.size == first.size == count.size:
+            raise ValueError("src, first and count differ in length (%d, %d, %d)" % (src.size, first.size, count.size))
+        nc, nr = ptrs.size, src.size
+        offsets = np.zeros(nr + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c, bad_r = C.c_size_t(unset), C.c_size_t(unset)
+        st = L.lib().ansx_decode_batch_ranges_dev(
+            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None, nc,
+            src.ctypes.data if nr else None, first.ctypes.data if nr else None, count.ctypes.data if nr else None, nr,
+            out_ptr, int(out_capacity), offsets.ctypes.data, C.byref(total), C.byref(bad_c), C.byref(bad_r), stream)
+        if st == L.ERR_CAPACITY and out_ptr is None and int(out_capacity) == 0:
+            return offsets
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".decode_batch_ranges_dev")
+            err.bad_container = int(bad_c.value) if bad_c.value != unset else None
+            err.bad_range = int(bad_r.value) if bad_r.value != unset else None
+            if st == L.ERR_CAPACITY:
+                err.needed = int(total.value)
+                err.offsets = offsets
+            raise err
+        return offsets
+
     def encode_batch_dev(self, in_ptr, offsets, out_ptr, out_capacity, stream=None):
         """A batch of lists in one call: list i is ints [offsets[i], offsets[i + 1]) of the device array at in_ptr
         (offsets: len(lists) + 1 non-decreasing ints, the layout decode_batch_dev returns; no list may be empty).

@@ -29,6 +29,7 @@
 #include "ansx_intsparse.h"
 #include "ansx_ranges.h"
 #include "ansx_batch.h"
+#include "ansx_batchranges.h"
 #include "ansx_encbatch.h"
 
 namespace {
@@ -147,7 +148,7 @@ struct ansx_ctx {
         u32 cand_chains = 0;          // ANSX_CAND_CHAINS: 1 | 2 recurrences per lane in k_candidates (0 = by the call's size)
         double fast_guard = ANSX_FAST_GUARD;  // ANSX_FAST_GUARD: relative guard band of the fast model path's stop rule (tests widen it)
         int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
-        u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
+        u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev, ansx_decode_batch_ranges_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
     } dbg;
 };
 
@@ -2149,12 +2150,89 @@ struct BatchSrc {  // a container of the batch, checked
     u32 nblocks;
 };
 
+// What a pass hands to its gather: two sections of the plan upload, behind the sources, blocks and table
+struct PassTail {
+    const void* a;  // the gather's pieces: ansx_range_piece per source (batch_pass), ansx_piece per piece (batch_ranges_group)
+    size_t a_bytes;
+    const void* b;  // the index over them: u32 pstart per source + 1 (batch_pass), u64 wpos per piece + 1 (batch_ranges_group)
+    size_t b_bytes;
+};
+// the pass's gather: enqueues the copy from the decoded work list to the caller's buffer (da, db: the tail's sections a
+// and b on the device, 16-byte aligned; the decode's flags)
+typedef std::function<int(const u32* list, const u8* da, const u8* db, const u32* gflags)> PassGather;
+
+// The part every pass shares (ansx_decode_batch_dev, ansx_decode_batch_ranges_dev): S, B, O -- the pass's sources, its
+// T blocks and the decoders' table over a work list of wl ints -- and the tail go up in one copy; k_batch_index and
+// k_batch_copy build the sub-container (H0: a header of the pass's geometry, Hs: the sub-container's, the maxima over
+// the sources filled in), decode_dev decodes it with the gather riding on its final read-back.  Every buffer is bounded
+// by the pass: its blocks, their ints and their bytes, and the tail.
+int pass_decode(ansx_ctx* c, int kind, int f, const ansx_container_header& H0, ansx_container_header Hs,
+    const std::vector<ansx_batch_src>& S, const std::vector<ansx_batch_blk>& B, const std::vector<ansx_blk_out>& O, u64 wl,
+    u64 cap_pay, const PassTail& tail, const PassGather& pass_gather, hipStream_t s)
+{
+    int rc;
+    const u64 bi = H0.block_ints;
+    const u32 T = (u32)B.size(), nr = (u32)S.size();
+
+    // the sub-container's plan: any n that makes make_plan lay out exactly T blocks (the table says how long each is)
+    const u64 n_sub = (u64)(T - 1) * bi + O.back().n;
+    const ansx_opts o = container_opts(H0);
+    Plan Ps;
+    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
+    set_restart_format(&Ps, (H0.kind & ANSX_KIND_WIDE_RESTART) != 0);
+    if (Ps.g.nblocks != T) return ANSX_ERR_FORMAT;
+    Hs.n = n_sub;
+    Hs.nblocks = T;
+    Hs.payload_bytes = 0;  // (k_batch_index writes the sum of the blocks' stream lengths)
+    Hs.payload_offset = Ps.lay.payload_off;
+
+    // the pass's plan, one upload: flags[4] | sources | blocks | table | the tail's two sections
+    const size_t o_s = 16, o_b = rup(o_s + sizeof(ansx_batch_src) * nr, 16), o_o = rup(o_b + sizeof(ansx_batch_blk) * T, 16);
+    const size_t o_r = rup(o_o + sizeof(ansx_blk_out) * T, 16), o_p = rup(o_r + tail.a_bytes, 16);
+    const size_t plan_bytes = o_p + tail.b_bytes;
+    if ((rc = ensure_pin(c, plan_bytes))) return rc;
+    u8* hb = c->rng_pin;  // (no copy out of it is pending: the previous pass ended in a synchronisation)
+    memset(hb, 0, o_s);
+    memcpy(hb + o_s, S.data(), sizeof(ansx_batch_src) * nr);
+    memcpy(hb + o_b, B.data(), sizeof(ansx_batch_blk) * T);
+    memcpy(hb + o_o, O.data(), sizeof(ansx_blk_out) * T);
+    memcpy(hb + o_r, tail.a, tail.a_bytes);
+    memcpy(hb + o_p, tail.b, tail.b_bytes);
+    if ((rc = ensure(c, c->rng_plan, plan_bytes))) return rc;
+    u8* dplan = (u8*)c->rng_plan.p;
+    HIPCHK(c, hipMemcpyAsync(dplan, hb, plan_bytes, hipMemcpyHostToDevice, s));
+    u32* dflags = (u32*)dplan;
+    const ansx_batch_src* dS = (const ansx_batch_src*)(dplan + o_s);
+    const ansx_batch_blk* dB = (const ansx_batch_blk*)(dplan + o_b);
+
+    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
+    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
+    if ((rc = ensure(c, c->rng_list, 4 * wl + 64))) return rc;
+    u8* sub = (u8*)c->rng_cont.p;
+    u32* list = (u32*)c->rng_list.p;
+    const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
+    LAUNCH(c, "k_batch_index", k_batch_index, 1, 1024, 0, s, dS, dB, Ps.g, T, Hs, sub, cap_pay, dflags);
+    LAUNCH(c, "k_batch_copy", k_batch_copy, T, 256, 0, s, dS, dB, Ps.g, dl, sub, cap_pay, dflags);
+    // as in range_tail: the gather and the read-back of this pass's own flags ride on the decode's final read-back
+    u32* hflag = c->h_pin + 512;
+    *hflag = 0;
+    const std::function<int(const u32*)> gather = [&](const u32* gflags) -> int {
+        if ((rc = pass_gather(list, dplan + o_r, dplan + o_p, gflags))) return rc;
+        HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
+        return ANSX_OK;
+    };
+    Ps.bout = (const ansx_blk_out*)(dplan + o_o);
+    Ps.bout_ints = wl;
+    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, false, false, &gather);
+    if (*hflag) return ANSX_ERR_FORMAT;  // an index entry of a pass block was invalid
+    return rc;
+}
+
 // One pass over containers ids[*ci..] of one geometry, from block *b0 of the first, up to PB blocks; moves *ci / *b0
-// past them.  Every buffer it uses is bounded by the pass: its blocks, their ints and their bytes.
+// past them.
 int batch_pass(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& src, const std::vector<u64>& off,
     const std::vector<u32>& ids, size_t* ci, u32* b0, u32 PB, u32* d_out, hipStream_t s)
 {
-    int rc;
     const ansx_container_header& H0 = src[ids[*ci]].H;
     const u64 bi = H0.block_ints;
     const u64 bbound = block_bound(kind, (u32)f, (size_t)bi, (H0.kind & 0x100u) != 0);
@@ -2194,63 +2272,16 @@ int batch_pass(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& src, c
     }
     if (npieces > 0xFFFFFFFFull) return ANSX_ERR_ARG;
     pstart.push_back((u32)npieces);
-    const u32 T = (u32)B.size(), nr = (u32)R.size();
-
-    // the sub-container's plan: any n that makes make_plan lay out exactly T blocks (the table says how long each is)
-    const u64 n_sub = (u64)(T - 1) * bi + O.back().n;
-    const ansx_opts o = container_opts(H0);
-    Plan Ps;
-    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
-    set_restart_format(&Ps, (H0.kind & ANSX_KIND_WIDE_RESTART) != 0);
-    if (Ps.g.nblocks != T) return ANSX_ERR_FORMAT;
-    Hs.n = n_sub;
-    Hs.nblocks = T;
-    Hs.payload_bytes = 0;  // (k_batch_index writes the sum of the blocks' stream lengths)
-    Hs.payload_offset = Ps.lay.payload_off;
-
-    // the pass's plan, one upload: flags[4] | sources | blocks | table | gather pieces | first piece per source
-    const size_t o_s = 16, o_b = rup(o_s + sizeof(ansx_batch_src) * nr, 16), o_o = rup(o_b + sizeof(ansx_batch_blk) * T, 16);
-    const size_t o_r = rup(o_o + sizeof(ansx_blk_out) * T, 16), o_p = rup(o_r + sizeof(ansx_range_piece) * nr, 16);
-    const size_t plan_bytes = o_p + 4 * ((size_t)nr + 1);
-    if ((rc = ensure_pin(c, plan_bytes))) return rc;
-    u8* hb = c->rng_pin;  // (no copy out of it is pending: the previous pass ended in a synchronisation)
-    memset(hb, 0, o_s);
-    memcpy(hb + o_s, S.data(), sizeof(ansx_batch_src) * nr);
-    memcpy(hb + o_b, B.data(), sizeof(ansx_batch_blk) * T);
-    memcpy(hb + o_o, O.data(), sizeof(ansx_blk_out) * T);
-    memcpy(hb + o_r, R.data(), sizeof(ansx_range_piece) * nr);
-    memcpy(hb + o_p, pstart.data(), 4 * ((size_t)nr + 1));
-    if ((rc = ensure(c, c->rng_plan, plan_bytes))) return rc;
-    u8* dplan = (u8*)c->rng_plan.p;
-    HIPCHK(c, hipMemcpyAsync(dplan, hb, plan_bytes, hipMemcpyHostToDevice, s));
-    u32* dflags = (u32*)dplan;
-    const ansx_batch_src* dS = (const ansx_batch_src*)(dplan + o_s);
-    const ansx_batch_blk* dB = (const ansx_batch_blk*)(dplan + o_b);
-    const ansx_range_piece* dR = (const ansx_range_piece*)(dplan + o_r);
-    const u32* dP = (const u32*)(dplan + o_p);
-
-    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
-    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
-    if ((rc = ensure(c, c->rng_list, 4 * wl + 64))) return rc;
-    u8* sub = (u8*)c->rng_cont.p;
-    u32* list = (u32*)c->rng_list.p;
-    const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
-    LAUNCH(c, "k_batch_index", k_batch_index, 1, 1024, 0, s, dS, dB, Ps.g, T, Hs, sub, cap_pay, dflags);
-    LAUNCH(c, "k_batch_copy", k_batch_copy, T, 256, 0, s, dS, dB, Ps.g, dl, sub, cap_pay, dflags);
-    // as in range_tail: the gather and the read-back of this pass's own flags ride on the decode's final read-back
-    u32* hflag = c->h_pin + 512;
-    *hflag = 0;
-    const std::function<int(const u32*)> gather = [&](const u32* gflags) -> int {
+    const u32 nr = (u32)R.size();
+    // the tail: gather pieces | first piece per source
+    const PassTail tail = { R.data(), sizeof(ansx_range_piece) * nr, pstart.data(), 4 * ((size_t)nr + 1) };
+    const PassGather gather = [&](const u32* list, const u8* da, const u8* db, const u32* gflags) -> int {
         const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
-        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, dR, dP, nr, (u32)npieces, d_out, gflags);
-        HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
+        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, (const ansx_range_piece*)da, (const u32*)db, nr,
+            (u32)npieces, d_out, gflags);
         return ANSX_OK;
     };
-    Ps.bout = (const ansx_blk_out*)(dplan + o_o);
-    Ps.bout_ints = wl;
-    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, false, false, &gather);
-    if (*hflag) return ANSX_ERR_FORMAT;  // an index entry of a pass block was invalid
-    return rc;
+    return pass_decode(c, kind, f, H0, Hs, S, B, O, wl, cap_pay, tail, gather, s);
 }
 
 int decode_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
@@ -2308,6 +2339,280 @@ int decode_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const siz
                 if (rc == ANSX_ERR_FORMAT && bad_index) *bad_index = count;  // (found on the device: which one is not known)
                 return rc;
             }
+        }
+    }
+    return ANSX_OK;
+}
+
+// --------------------------------------------------------------------------------- ranges of a batch
+// ansx_decode_batch_ranges_dev: the headers of the REFERENCED containers in one round trip -> the
+// host's checks, offsets and capacity -> per geometry, the touched (container, block) pairs, sorted and unique, in
+// passes of at most P: pass_decode on them as on a pass of ansx_decode_batch_dev, with k_piece_gather as the way out.
+
+struct BrRun {     // consecutive touched blocks b0..b1 of referenced container r, inside one pass
+    u32 r, b0, b1, pass;
+    u64 wl;        // its first int in the pass's work list (a multiple of 4)
+};
+struct BrPiece {   // a range, or the part of one that lies in one run
+    u32 pass;
+    u64 src, dst, count;
+};
+
+// The union of one container's block spans sp[0..m) (first block << 32 | last block) as ascending stretches of
+// consecutive blocks with a gap between any two, appended to out.  More spans than the container has blocks (point
+// lookups) are counted into a difference array over its blocks; fewer are sorted.
+void br_union(u64* sp, size_t m, u32 nblocks, std::vector<u32>& diff, std::vector<std::pair<u32, u32>>& out)
+{
+    if (m > nblocks) {
+        diff.assign((size_t)nblocks + 1, 0);
+        for (size_t i = 0; i < m; i++) diff[sp[i] >> 32]++, diff[(u32)sp[i] + 1]--;
+        u32 depth = 0, b0 = 0;
+        for (u32 b = 0; b <= nblocks; b++) {
+            const u32 d = depth + diff[b];  // (spans that cover block b; 0 at b = nblocks)
+            if (!depth && d) b0 = b;
+            if (depth && !d) out.push_back({ b0, b - 1 });
+            depth = d;
+        }
+        return;
+    }
+    std::sort(sp, sp + m);
+    u32 b0 = (u32)(sp[0] >> 32), e = (u32)sp[0];
+    for (size_t i = 1; i < m; i++) {
+        const u32 f = (u32)(sp[i] >> 32), l = (u32)sp[i];
+        if (f <= e + 1) {
+            e = std::max(e, l);
+            continue;
+        }
+        out.push_back({ b0, e });
+        b0 = f, e = l;
+    }
+    out.push_back({ b0, e });
+}
+
+// The touched blocks of the ranges `ids` (non-empty, of one geometry: bi ints per block) as runs, sorted by
+// (container, block) and cut where a pass holds PB blocks.  A run's ints start at a multiple of 4 in its pass's work list.
+void br_runs(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, const u64* first, const u32* cnt,
+    const std::vector<u32>& ids, u64 bi, u32 PB, std::vector<BrRun>* runs)
+{
+    // the spans bucketed by container (a counting sort over the referenced containers)
+    std::vector<size_t> at(rs.size() + 1, 0);
+    for (const u32 i : ids) at[rid[i] + 1]++;
+    for (size_t r = 0; r < rs.size(); r++) at[r + 1] += at[r];
+    std::vector<u64> span(ids.size());
+    {
+        std::vector<size_t> put(at.begin(), at.end() - 1);
+        for (const u32 i : ids) span[put[rid[i]]++] = (first[i] / bi) << 32 | ((first[i] + cnt[i] - 1) / bi);
+    }
+    u32 pass = 0, pb = 0;  // the pass being filled, its blocks so far
+    u64 wl = 0;            // ... and its work-list ints
+    std::vector<u32> diff;
+    std::vector<std::pair<u32, u32>> stretch;
+    for (size_t r = 0; r < rs.size(); r++) {
+        if (at[r] == at[r + 1]) continue;
+        stretch.clear();
+        br_union(span.data() + at[r], at[r + 1] - at[r], rs[r].nblocks, diff, stretch);
+        const u64 n = rs[r].H.n;
+        for (const auto& st : stretch)
+            for (u32 b = st.first; b <= st.second;) {
+                const u32 take = (u32)std::min<u64>((u64)st.second - b + 1, PB - pb);
+                runs->push_back({ (u32)r, b, b + take - 1, pass, wl });
+                wl += rup(std::min<u64>(n, ((u64)b + take) * bi) - (u64)b * bi, 4);
+                pb += take;
+                b += take;
+                if (pb == PB) pass++, pb = 0, wl = 0;
+            }
+    }
+}
+
+// Every range's pieces, one per run it crosses (runs cut from one stretch of blocks follow each other), bucketed by
+// pass in range order: pieces PP and their counts PC, pass p's from pfirst[p] to pfirst[p + 1].
+void br_pieces(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, const u64* first, const u32* cnt,
+    const std::vector<u64>& off, const std::vector<u32>& ids, u64 bi, const std::vector<BrRun>& runs,
+    std::vector<ansx_piece>* PP, std::vector<u64>* PC, std::vector<u64>* pfirst)
+{
+    const u32 npass = runs.back().pass + 1;
+    std::vector<BrPiece> pieces;
+    pieces.reserve(ids.size());
+    pfirst->assign((size_t)npass + 1, 0);
+    for (const u32 i : ids) {
+        const u32 r = rid[i], b0 = (u32)(first[i] / bi);
+        const u64 n = rs[r].H.n;
+        auto it = std::upper_bound(runs.begin(), runs.end(), b0,
+            [r](u32 v, const BrRun& x) { return x.r != r ? r < x.r : v < x.b0; });
+        size_t k = (size_t)(it - runs.begin()) - 1;
+        u64 pos = first[i], left = cnt[i], dst = off[i];
+        for (; left; k++) {
+            const BrRun& rn = runs[k];
+            const u64 take = std::min<u64>(left, std::min<u64>(n, ((u64)rn.b1 + 1) * bi) - pos);
+            pieces.push_back({ rn.pass, rn.wl + (pos - (u64)rn.b0 * bi), dst, take });
+            (*pfirst)[rn.pass + 1]++;
+            pos += take, dst += take, left -= take;
+        }
+    }
+    for (u32 p = 0; p < npass; p++) (*pfirst)[p + 1] += (*pfirst)[p];
+    PP->resize(pieces.size());
+    PC->resize(pieces.size());
+    std::vector<u64> put(pfirst->begin(), pfirst->end() - 1);
+    for (const BrPiece& q : pieces) {  // (stable: range order inside a pass)
+        (*PP)[put[q.pass]] = { q.src, q.dst };
+        (*PC)[put[q.pass]++] = q.count;
+    }
+}
+
+// The ranges `ids` (non-empty, in range order) of one geometry; rs: the referenced containers, rid[i] / off[i]: range
+// i's container among them and its place in d_out.
+int batch_ranges_group(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& rs, const std::vector<u32>& rid,
+    const u64* first, const u32* cnt, const std::vector<u64>& off, const std::vector<u32>& ids, u32 PB, u32* d_out,
+    hipStream_t s)
+{
+    int rc;
+    const ansx_container_header& H0 = rs[rid[ids[0]]].H;
+    const u64 bi = H0.block_ints;
+    const u64 bbound = block_bound(kind, (u32)f, (size_t)bi, (H0.kind & 0x100u) != 0);
+    std::vector<BrRun> runs;
+    br_runs(rs, rid, first, cnt, ids, bi, PB, &runs);
+    std::vector<ansx_piece> PP;
+    std::vector<u64> PC, pfirst;
+    br_pieces(rs, rid, first, cnt, off, ids, bi, runs, &PP, &PC, &pfirst);
+    const u32 npass = runs.back().pass + 1;
+
+    std::vector<ansx_batch_src> S;
+    std::vector<ansx_batch_blk> B;
+    std::vector<ansx_blk_out> O;
+    std::vector<u64> wpos;
+    size_t k = 0;
+    for (u32 p = 0; p < npass; p++) {
+        // the pass's sources (one per container), blocks and table, as batch_pass builds them
+        S.clear(), B.clear(), O.clear();
+        u64 cap_pay = 0, wl_pass = 0;
+        u32 sblocks = 0;  // blocks of the source being filled
+        ansx_container_header Hs = H0;
+        Hs.max_nsyms = 0, Hs.max_log2_frame = 0, Hs.max_present_m1 = 0;  // (the maxima over the pass's sources)
+        const auto close_source = [&]() {
+            if (!S.empty()) cap_pay += std::min<u64>(S.back().payload_bytes, (u64)sblocks * bbound);
+            sblocks = 0;
+        };
+        for (u32 last_r = 0; k < runs.size() && runs[k].pass == p; k++) {
+            const BrRun& rn = runs[k];
+            const BatchSrc& cs = rs[rn.r];
+            if (S.empty() || rn.r != last_r) {
+                close_source();
+                S.push_back({ cs.base, cs.lay.ckoff_off, cs.lay.ckstate_off, cs.lay.hint_off, cs.lay.payload_off,
+                    cs.H.payload_bytes, cs.nblocks, 0 });
+                Hs.max_nsyms = std::max(Hs.max_nsyms, cs.H.max_nsyms);
+                Hs.max_log2_frame = std::max(Hs.max_log2_frame, cs.H.max_log2_frame);
+                Hs.max_present_m1 = std::max(Hs.max_present_m1, cs.H.max_present_m1);
+                last_r = rn.r;
+            }
+            for (u32 b = rn.b0; b <= rn.b1; b++) {
+                B.push_back({ (u32)S.size() - 1, b });
+                O.push_back({ rn.wl + (u64)(b - rn.b0) * bi, (u32)std::min<u64>(bi, cs.H.n - (u64)b * bi), 0 });
+            }
+            sblocks += rn.b1 - rn.b0 + 1;
+            wl_pass = rn.wl + rup(std::min<u64>(cs.H.n, ((u64)rn.b1 + 1) * bi) - (u64)rn.b0 * bi, 4);
+        }
+        close_source();
+        const u64 np = pfirst[p + 1] - pfirst[p];
+        if (np > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+        wpos.resize(np + 1);
+        u64 ints = 0;
+        for (u64 q = 0; q < np; q++) wpos[q] = ints, ints += PC[pfirst[p] + q];
+        wpos[np] = ints;
+        // the tail: pieces | their exclusive prefix over the pass
+        const PassTail tail = { PP.data() + pfirst[p], sizeof(ansx_piece) * np, wpos.data(), 8 * (np + 1) };
+        const PassGather gather = [&](const u32* list, const u8* da, const u8* db, const u32* gflags) -> int {
+            const u32 grid = (u32)std::min<u64>((ints + ANSX_PIECE_CHUNK - 1) / ANSX_PIECE_CHUNK, 1u << 20);
+            LAUNCH(c, "k_piece_gather", k_piece_gather, grid, 256, 0, s, list, (const ansx_piece*)da, (const u64*)db, (u32)np,
+                ints, d_out, gflags);
+            return ANSX_OK;
+        };
+        if ((rc = pass_decode(c, kind, f, H0, Hs, S, B, O, wl_pass, cap_pay, tail, gather, s))) return rc;
+    }
+    return ANSX_OK;
+}
+
+int decode_batch_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
+    const u32* src, const u64* first, const u32* cnt, size_t nranges, u32* d_out, size_t cap, u64* offsets, u64* total_ints,
+    size_t* bad_container, size_t* bad_range, hipStream_t s)
+{
+    int rc;
+    // the referenced containers, in batch order, and every range's place among them (rid); nothing below looks at any
+    // other container.  A batch that is not much larger than the query is marked in an array over its positions, a
+    // larger one is found by sorting the names.
+    std::vector<u32> ref, rid(nranges);
+    if (count <= 4 * nranges + 1024) {
+        std::vector<u32> slot(count, 0);
+        for (size_t i = 0; i < nranges; i++) slot[src[i]] = 1;
+        for (size_t j = 0; j < count; j++)
+            if (slot[j]) slot[j] = (u32)ref.size(), ref.push_back((u32)j);
+        for (size_t i = 0; i < nranges; i++) rid[i] = slot[src[i]];
+    } else {
+        ref.assign(src, src + nranges);
+        std::sort(ref.begin(), ref.end());
+        ref.erase(std::unique(ref.begin(), ref.end()), ref.end());
+        for (size_t i = 0; i < nranges; i++) rid[i] = (u32)(std::lower_bound(ref.begin(), ref.end(), src[i]) - ref.begin());
+    }
+    const size_t nref = ref.size();
+
+    // their headers in one round trip: the addresses up (0 for an input too short to hold one), the headers back
+    const size_t o_h = rup(8 * nref, 16), bytes = o_h + 64 * nref;
+    if ((rc = ensure_pin(c, bytes))) return rc;
+    if ((rc = ensure(c, c->bat_hdr, bytes))) return rc;
+    u64* hp = (u64*)c->rng_pin;
+    for (size_t j = 0; j < nref; j++)
+        hp[j] = in_bytes[ref[j]] >= sizeof(ansx_container_header) ? (u64)(uintptr_t)d_ins[ref[j]] : 0;
+    u8* dw = (u8*)c->bat_hdr.p;
+    HIPCHK(c, hipMemcpyAsync(dw, hp, 8 * nref, hipMemcpyHostToDevice, s));
+    LAUNCH(c, "k_batch_headers", k_batch_headers, (u32)((4 * (u64)nref + 255) / 256), 256, 0, s, (const u64*)dw, (u64)nref,
+        (uint4*)(dw + o_h));
+    HIPCHK(c, hipMemcpyAsync(c->rng_pin + o_h, dw + o_h, 64 * nref, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+
+    // decode_batch's checks on every one of them, in batch order
+    std::vector<BatchSrc> rs(nref);
+    for (size_t j = 0; j < nref; j++) {
+        BatchSrc& b = rs[j];
+        const size_t nb = in_bytes[ref[j]];
+        Plan P;
+        if (nb < sizeof(ansx_container_header) || parse_header(c->rng_pin + o_h + 64 * j, nb, &b.H)
+            || container_plan(b.H, (u32)kind, (u32)f, nb, &P)) {  // (a single-stream stream has no magic)
+            if (bad_container) *bad_container = ref[j];
+            return ANSX_ERR_FORMAT;
+        }
+        b.lay = P.lay;
+        b.base = (u64)(uintptr_t)d_ins[ref[j]];
+        b.nblocks = P.g.nblocks;
+    }
+    // every range against its own container's n; the offsets and the total
+    std::vector<u64> off(nranges + 1);
+    u64 total = 0;
+    for (size_t i = 0; i < nranges; i++) {
+        const u64 n = rs[rid[i]].H.n;
+        if (first[i] > n || (u64)cnt[i] > n - first[i]) {
+            if (bad_range) *bad_range = i;
+            return ANSX_ERR_ARG;
+        }
+        off[i] = total;
+        total += cnt[i];  // (at most 2^32 - 1 per range, at most 2^32 - 1 ranges: no wrap)
+    }
+    off[nranges] = total;
+    if (offsets) memcpy(offsets, off.data(), 8 * (nranges + 1));
+    if (total_ints) *total_ints = total;
+    if (total > cap) return ANSX_ERR_CAPACITY;
+    if (total == 0) return ANSX_OK;
+
+    // the non-empty ranges by geometry (block_ints, restart interval, compaction, restart-point format), range order inside
+    std::map<std::array<u32, 4>, std::vector<u32>> groups;
+    for (size_t i = 0; i < nranges; i++) {
+        if (!cnt[i]) continue;
+        const ansx_container_header& H = rs[rid[i]].H;
+        groups[{ H.block_ints, H.ckpt_interval, (H.kind >> 8) & 1u, (H.kind >> 9) & 1u }].push_back((u32)i);
+    }
+    const u32 PB = c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT;
+    for (const auto& gr : groups) {
+        if ((rc = batch_ranges_group(c, kind, f, rs, rid, first, cnt, off, gr.second, PB, d_out, s))) {
+            if (rc == ANSX_ERR_FORMAT && bad_container) *bad_container = count;  // (found on the device: which one is not known)
+            return rc;
         }
     }
     return ANSX_OK;
@@ -2814,6 +3119,35 @@ int ansx_decode_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     return decode_batch(c, kind, f, d_ins, in_bytes, count, d_out, out_capacity_ints, (u64*)offsets, (u64*)total_ints,
         bad_index, s);
+}
+
+int ansx_decode_batch_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    size_t count, const uint32_t* src, const uint64_t* first, const uint32_t* cnt, size_t nranges, uint32_t* d_out,
+    size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_container, size_t* bad_range, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || count > 0xFFFFFFFFull || nranges > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!src || !first || !cnt || !d_ins || !in_bytes)) return ANSX_ERR_ARG;
+    if ((!d_out && out_capacity_ints > 0) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    for (size_t i = 0; i < nranges; i++)
+        if (src[i] >= count) {
+            if (bad_range) *bad_range = i;
+            return ANSX_ERR_ARG;
+        }
+    for (size_t i = 0; i < nranges; i++)  // (only the containers some range names are looked at)
+        if (!d_ins[src[i]] || ((uintptr_t)d_ins[src[i]] & 15u)) {
+            if (bad_range) *bad_range = i;
+            return ANSX_ERR_ARG;
+        }
+    if (nranges == 0) {
+        if (offsets) offsets[0] = 0;
+        if (total_ints) *total_ints = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return decode_batch_ranges(c, kind, f, d_ins, in_bytes, count, src, (const u64*)first, cnt, nranges, d_out,
+        out_capacity_ints, (u64*)offsets, (u64*)total_ints, bad_container, bad_range, s);
 }
 
 int ansx_encode_batch_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,

@@ -229,6 +229,43 @@ int ansx_decode_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* 
     size_t count, uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_index,
     void* stream);
 
+/* Ranges of a batch of containers in one call: the product of ansx_decode_ranges_dev and ansx_decode_batch_dev (a few
+ * ranges out of each of many posting lists or column chunks).  d_ins / in_bytes / count: the batch, as for
+ * ansx_decode_batch_dev.  src, first, cnt: HOST arrays of nranges; range i is ints [first[i], first[i] + cnt[i]) of
+ * container src[i], written to d_out[offsets[i] ..): the ranges in order and back to back.  offsets (optional, HOST
+ * array of nranges + 1): the exclusive prefix sums of cnt, and the total; *total_ints (optional): sum(cnt).  The output
+ * is bit-identical to slicing what ansx_decode_dev returns for each container.  Ranges may overlap, repeat, be unsorted,
+ * have count 0 and name containers in any order; the same pointer may stand at several batch positions (they are then
+ * distinct sources); every container form ansx_decode_dev reads is accepted, and the containers of one call may differ
+ * in geometry.  d_out: 4-byte aligned.
+ * Selectivity: a container is REFERENCED when some range names it (count 0 included).  Of an unreferenced container
+ * nothing is read, not even its header, and d_ins[i] / in_bytes[i] are not examined (null is allowed).  Of a referenced
+ * container only the header, the index entries of touched blocks and the bytes of touched blocks are read.  No kernel's
+ * grid grows with count or with any container's block count: grids grow with the referenced containers, the touched
+ * blocks and the ints asked for.
+ * Errors decided before the context is touched (ANSX_ERR_ARG): a null ctx; a null src, first, cnt, d_ins or in_bytes
+ * with nranges > 0; count or nranges > UINT32_MAX; d_out misaligned, or NULL with out_capacity_ints > 0;
+ * src[i] >= count -- *bad_range (optional) is then i, the first such range; a null or not 16-byte aligned pointer of a
+ * referenced container -- *bad_range is then the first range naming it.  nranges == 0: ANSX_OK, total 0,
+ * offsets[0] = 0, nothing launched, whatever count is.
+ * Errors decided on the host, before any byte of d_out is written (the headers of the referenced containers come back in
+ * one round trip), in this order: ANSX_ERR_FORMAT under exactly ansx_decode_batch_dev's header checks --
+ * *bad_container (optional) is then the first failing container in batch order; ANSX_ERR_ARG if first[i] > n or
+ * cnt[i] > n - first[i] against the named container's own n -- *bad_range is then the first such range;
+ * ANSX_ERR_CAPACITY if sum(cnt) > out_capacity_ints.  offsets and *total_ints are written on ANSX_OK and
+ * ANSX_ERR_CAPACITY, so d_out = NULL, out_capacity_ints = 0 is a size query.
+ * Errors found on the device (an invalid index entry or stream of a touched block): ANSX_ERR_FORMAT with
+ * *bad_container = count; d_out is then unspecified, as for ansx_decode_batch_dev, but nothing is ever written at or
+ * beyond d_out + out_capacity_ints.
+ * The context stays usable after any error, and the call leaves no trace in it (no cached header, no per-geometry
+ * hint).  Synchronous; the inputs are read on `stream`.  Work is done per geometry in passes of at most 16384 touched
+ * blocks (ANSX_BATCH_PASS_BLOCKS); device workspace is bounded by one pass and the plan of its pieces, plus 72 bytes per
+ * referenced container. */
+int ansx_decode_batch_ranges_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    size_t count, const uint32_t* src, const uint64_t* first, const uint32_t* cnt, size_t nranges, uint32_t* d_out,
+    size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_container, size_t* bad_range,
+    void* stream);
+
 /* A batch of lists in one call: the writer's side of ansx_decode_batch_dev (posting lists, column chunks).  List i is
  * d_in[offsets[i] .. offsets[i + 1]); offsets is a HOST array of count + 1 non-decreasing int offsets -- the layout
  * ansx_decode_batch_dev returns -- and d_in is 4-byte aligned device memory: a list may start at any int.  Container i
