@@ -374,10 +374,13 @@ u32 rf_opt_slots(u32 distinct, u32 T)
     return lds <= 78 * 1024 ? slots : 0u;
 }
 // opt_slots != 0: optimistic table size for the LDS form (see k_rfold_remap_hash), from rf_opt_slots()
+// ids != null (a batch pass, LDS form only): the nids blocks of the pass listed there, addressed through g.bin
 int rfold_remap(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u32* mostfreq,
-    ansx_blk* blk, u32* gflags, hipStream_t s, u32 opt_slots = 0)
+    ansx_blk* blk, u32* gflags, hipStream_t s, u32 opt_slots = 0, const u32* ids = nullptr, u32 nids = 0)
 {
     const u32 T = fold_T(g.f);
+    const u32 grid = ids ? nids : g.nblocks;
+    if (ids && (g.block_ints > 16384u || T > 4096u)) return ANSX_ERR_ARG;  // (encode_batch_form keeps these off a pass)
     if (g.block_ints > 16384u || T > 4096u) {  // (T > 4096: f = 6, 7 -- the selection buffer alone is 64 / 128 KB)
         // large blocks (incl. whole-list single-stream mode): hash table in HBM
         u32 slots = 2;
@@ -410,8 +413,8 @@ int rfold_remap(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u3
             { static unsigned long long z[3] = { 0, 0, 0 }; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, 24, 4101 * 8); }
             hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, s);
 #endif
-            LAUNCH(c, "k_rfold_remap", k_rfold_remap_hash2, g.nblocks, 1024, lds, s, d_in, g, opt_slots, mapped,
-                mostfreq, blk, gflags);
+            LAUNCH(c, "k_rfold_remap", k_rfold_remap_hash2, grid, 1024, lds, s, d_in, g, opt_slots, mapped,
+                mostfreq, blk, gflags, ids);
 #ifdef ANSX_STAMPS_RF
             {
                 (void)hipEventRecord(e1, s); (void)hipStreamSynchronize(s);
@@ -425,8 +428,8 @@ int rfold_remap(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u3
         const size_t lds = 6 * (size_t)ANSX_RF_SLOTS + sel_bytes;
         HIPCHK(c, hipFuncSetAttribute((const void*)k_rfold_remap_hash,
                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(c, "k_rfold_remap", k_rfold_remap_hash, g.nblocks, 1024, lds, s, d_in, g, (u32)ANSX_RF_SLOTS, mapped,
-            mostfreq, blk, gflags);
+        LAUNCH(c, "k_rfold_remap", k_rfold_remap_hash, grid, 1024, lds, s, d_in, g, (u32)ANSX_RF_SLOTS, mapped,
+            mostfreq, blk, gflags, ids);
         return ANSX_OK;
     }
     u32 N2 = 2;
@@ -437,6 +440,25 @@ int rfold_remap(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u3
                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     LAUNCH(c, "k_rfold_remap_sort", k_rfold_remap, g.nblocks, 256, lds, s, d_in, g, N2, mapped, mostfreq,
         blk, gflags);
+    return ANSX_OK;
+}
+
+// The remap of a batch pass (ansx_rfold.h): one launch per class of blocks that has any, over that class's block ids.
+// `in` and `mapped` are addressed through g.bin, so both are pointers to where int 0 of the caller's input would be.
+int rfold_remap_pass(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u32* mostfreq, ansx_blk* blk,
+    u32* gflags, hipStream_t s, u32 opt_slots, const u32* ids, const u32 ncls[3])
+{
+    const u32 n_id = ncls[0], n_small = ncls[1], n_large = ncls[2];
+    if (n_id)
+        LAUNCH(c, "k_rfold_remap_identity", k_rfold_remap_identity, std::min<u32>(2048u, (n_id + 3) / 4), 256, 0, s, d_in, g, ids,
+            n_id, mapped, blk, gflags);
+    if (n_small) {
+        const size_t lds = 4 * (size_t)ANSX_RF_SMALL_LDS;  // two workgroups share a CU's 160 KB
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_rfold_remap_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        LAUNCH(c, "k_rfold_remap_small", k_rfold_remap_small, (n_small + 3) / 4, 256, lds, s, d_in, g, ids + n_id, n_small,
+            mapped, mostfreq, blk, gflags);
+    }
+    if (n_large) return rfold_remap(c, g, d_in, mapped, mostfreq, blk, gflags, s, opt_slots, ids + n_id + n_small, n_large);
     return ANSX_OK;
 }
 
@@ -571,6 +593,9 @@ struct EncBatchPass {
     const ansx_blk_in* hblk;  // the work list on the host (resolve_near reads a block back through it)
     u32 longest;              // ints of the pass's longest block: sizes the stream scratch stride
     ansx_encb_args A;         // device pointers of the plan, the results and the work area
+    u64 in_base, in_ints;     // the pass's lists are ints [in_base, in_base + in_ints) of the caller's input
+    const u32* rf_ids;        // ANSrfold: block ids by remap class (identity | small | large), device; rf_ncls: how many of each
+    u32 rf_ncls[3];
     u8* d_out;                // the caller's buffer
     const ansx_encb_res* hres;  // pinned: the results, read back with the attempt's flag words
 };
@@ -659,7 +684,19 @@ int encode_remap(ansx_ctx* c, EncodeWs& W)
     const u32 NB = g.nblocks;
     hipStream_t s = W.s;
     int rc;
-    if (g.kind == ANSX_RFOLD) {
+    if (g.kind == ANSX_RFOLD && W.P->bat) {
+        // a batch pass (g.n is not its ints): `mapped` holds the pass's own stretch of the input's index space, and the
+        // pointer handed on is biased by the stretch's start, so that the one work list g.bin addresses d_in and mapped
+        // alike -- for the model kernels, the encoder and resolve_near's read-back
+        const EncBatchPass& B = *W.P->bat;
+        if ((rc = ensure(c, c->mapped, (size_t)std::max<u64>(B.in_ints, 1) * 4))) return rc;
+        if ((rc = ensure(c, c->mostfreq, (size_t)NB * fold_T(g.f) * 4))) return rc;
+        u32* biased = (u32*)((uintptr_t)c->mapped.p - (uintptr_t)B.in_base * 4);
+        if ((rc = rfold_remap_pass(c, g, W.d_in, biased, (u32*)c->mostfreq.p, W.blk, W.gflags, s, a.rf_slots, B.rf_ids, B.rf_ncls)))
+            return rc;
+        W.src = biased;
+        W.mostfreq = (const u32*)c->mostfreq.p;
+    } else if (g.kind == ANSX_RFOLD) {
         if ((rc = ensure(c, c->mapped, (size_t)g.n * 4))) return rc;
         if ((rc = ensure(c, c->mostfreq, (size_t)NB * fold_T(g.f) * 4))) return rc;
         if ((rc = rfold_remap(c, g, W.d_in, (u32*)c->mapped.p, (u32*)c->mostfreq.p, W.blk, W.gflags, s, a.rf_slots))) return rc;
@@ -2653,7 +2690,9 @@ struct EncBatchHints {
 // geometries the batched path takes: the LDS-model codecs without compaction
 bool encode_batch_form(const ansx_geo& g)
 {
-    return !g.pa && (g.kind == ANSX_MSB || (g.kind == ANSX_FOLD && g.f <= 5));
+    if (g.pa) return false;
+    // (ANSrfold: the remap of a pass has the LDS forms only, ansx_rfold.h)
+    return g.kind == ANSX_MSB || (g.kind == ANSX_FOLD && g.f <= 5) || (g.kind == ANSX_RFOLD && g.f <= 5 && g.block_ints <= 16384u);
 }
 
 // One pass: lists [l0, l1) of the batch, NB blocks in all, containers from byte `base` of d_out on.  Writes their
@@ -2664,8 +2703,11 @@ int encode_batch_pass(ansx_ctx* c, const Plan& P0, const u32* d_in, const u64* o
     int rc;
     const u64 bi = P0.g.block_ints;
     const u32 nl = (u32)(l1 - l0);
-    // the plan, one upload from pinned memory: blocks | lists; behind it on the device: maxima | results | block sums
-    const size_t o_l = sizeof(ansx_blk_in) * (size_t)NB, o_m = o_l + sizeof(ansx_encb_list) * ((size_t)nl + 1);
+    // the plan, one upload from pinned memory: blocks | lists | ANSrfold's block ids by remap class; behind it on the
+    // device: maxima | results | block sums
+    const bool rf = P0.g.kind == ANSX_RFOLD;
+    const size_t o_l = sizeof(ansx_blk_in) * (size_t)NB, o_i = o_l + sizeof(ansx_encb_list) * ((size_t)nl + 1);
+    const size_t o_m = o_i + (rf ? rup(4 * (size_t)NB, 16) : 0);
     const size_t o_r = o_m + sizeof(ansx_encb_max) * (size_t)nl, o_s = o_r + sizeof(ansx_encb_res) * ((size_t)nl + 1);
     const size_t plan_bytes = o_s + 8 * ((size_t)NB + 1);
     const size_t res_bytes = sizeof(ansx_encb_res) * ((size_t)nl + 1);
@@ -2685,6 +2727,15 @@ int encode_batch_pass(ansx_ctx* c, const Plan& P0, const u32* d_in, const u64* o
     }
     hl[nl] = { 0, k, 0 };
     if (k != NB) return ANSX_ERR_ARG;  // (cannot happen: the caller counted the same blocks)
+    u32 ncls[3] = { 0, 0, 0 };
+    if (rf) {  // the remap classes (ansx_rfold.h), by block length: counted, then every class's ids in block order
+        const u32 T = fold_T(P0.g.f);
+        auto cls = [&](u32 nb) { return nb < T ? 0u : (nb <= ANSX_RF_SMALL_INTS ? 1u : 2u); };
+        for (u32 b = 0; b < NB; b++) ncls[cls(hblk[b].n)]++;
+        u32* hid = (u32*)(hb + o_i);
+        u32 at[3] = { 0, ncls[0], ncls[0] + ncls[1] };
+        for (u32 b = 0; b < NB; b++) hid[at[cls(hblk[b].n)]++] = b;
+    }
     if ((rc = ensure(c, c->enb_plan, plan_bytes))) return rc;
     u8* dp = (u8*)c->enb_plan.p;
     HIPCHK(c, hipMemcpyAsync(dp, hb, o_m, hipMemcpyHostToDevice, s));
@@ -2706,6 +2757,10 @@ int encode_batch_pass(ansx_ctx* c, const Plan& P0, const u32* d_in, const u64* o
     EncBatchPass B;
     B.hblk = hblk;
     B.longest = longest;
+    B.in_base = offsets[l0];
+    B.in_ints = offsets[l1] - offsets[l0];
+    B.rf_ids = rf ? (const u32*)(dp + o_i) : nullptr;
+    memcpy(B.rf_ncls, ncls, sizeof(ncls));
     B.A.bin = P.g.bin;
     B.A.lists = (const ansx_encb_list*)(dp + o_l);
     B.A.mx = (ansx_encb_max*)(dp + o_m);

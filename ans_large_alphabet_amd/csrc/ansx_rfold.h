@@ -191,23 +191,25 @@ __device__ __forceinline__ u32 rf_slot(u32 v, u32 slots) { return (u32)(((u64)(v
 // geometry before and sizes the table for 1.5 x the most distinct values a block of it ever had, so that two
 // workgroups share a CU (k_rfold_remap_hash2: 64 registers) and every pass is that much shorter; a block that
 // does not fit raises the violation flag, writes zeros, and the caller repeats the call with the full table.
+// `ids` (a pass of ansx_encode_batch_dev): workgroup w takes block ids[w] of the pass, and block b's ints lie where the
+// work list g.bin says, in the input and in `mapped` alike; null: block blockIdx.x, at b * block_ints.
 __device__ __forceinline__ void rfold_remap_hash_body(const u32* __restrict__ in, const ansx_geo& g, u32 slots,
     u32* __restrict__ mapped, u32* __restrict__ mostfreq, ansx_blk* __restrict__ blk,
-    u32* __restrict__ gflags)
+    u32* __restrict__ gflags, const u32* __restrict__ ids)
 {
     extern __shared__ u8 smem_rh[];
     __shared__ u32 sh_cnt;
     __shared__ u32 sh_max;
     __shared__ u32 sh_ovf;
     const u32 tid = threadIdx.x, nt = blockDim.x;
-    const u32 b = blockIdx.x;
+    const u32 b = ids ? ids[blockIdx.x] : blockIdx.x;
     const u32 nb = geo_block_n(g, b);
     const u32 T = fold_T(g.f);
     u32* keys = (u32*)smem_rh;                                      // [SLOTS]
     u32* cnt32 = (u32*)(smem_rh + 4 * (size_t)slots);              // [slots/2], two u16 counters each
     u64* sel = (u64*)(smem_rh + 6 * (size_t)slots);                // [T]  (slots is a multiple of 4)
-    const u32* src = in + (u64)b * g.block_ints;
-    u32* dst = mapped + (u64)b * g.block_ints;
+    const u32* src = in + geo_block_in(g, b);
+    u32* dst = mapped + geo_block_in(g, b);
     STAMP_RF(0);
 #ifdef ANSX_STAMPS_RF
     const unsigned long long rf_t0 = wall_clock64();
@@ -493,9 +495,10 @@ __device__ __forceinline__ void rfold_remap_hash_body(const u32* __restrict__ in
 
 
 __global__ __launch_bounds__(1024) void k_rfold_remap_hash(const u32* __restrict__ in, ansx_geo g, u32 slots,
-    u32* __restrict__ mapped, u32* __restrict__ mostfreq, ansx_blk* __restrict__ blk, u32* __restrict__ gflags)
+    u32* __restrict__ mapped, u32* __restrict__ mostfreq, ansx_blk* __restrict__ blk, u32* __restrict__ gflags,
+    const u32* __restrict__ ids)
 {
-    rfold_remap_hash_body(in, g, slots, mapped, mostfreq, blk, gflags);
+    rfold_remap_hash_body(in, g, slots, mapped, mostfreq, blk, gflags, ids);
 }
 // two workgroups per CU: 32 waves, 64 registers each
 #ifdef RF_NO_WPE
@@ -505,9 +508,189 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 #endif
 
     const u32* __restrict__ in, ansx_geo g, u32 slots, u32* __restrict__ mapped, u32* __restrict__ mostfreq,
+    ansx_blk* __restrict__ blk, u32* __restrict__ gflags, const u32* __restrict__ ids)
+{
+    rfold_remap_hash_body(in, g, slots, mapped, mostfreq, blk, gflags, ids);
+}
+
+// ------------------------------------------------------------------------------------------
+// K9 for a pass of ansx_encode_batch_dev: the host sorts the pass's blocks into three classes
+// by their length nb and hands every class the list of its block ids.
+//   nb < T                        k_rfold_remap_identity: fewer than T ints are fewer than T distinct values
+//   T <= nb <= ANSX_RF_SMALL_INTS k_rfold_remap_small:    one wave per block
+//   longer                        k_rfold_remap_hash / k_rfold_remap_hash2 over the class's ids
+// ------------------------------------------------------------------------------------------
+#define ANSX_RF_SMALL_INTS 1024u
+#define ANSX_RF_SMALL_SLOTS 2048u  // 2 x the most values a block of the class has
+// per wave: the (count, value) pairs of the block's distinct values | keys | counts, then ranks (two u16 per word)
+#define ANSX_RF_SMALL_LDS (8u * ANSX_RF_SMALL_INTS + 6u * ANSX_RF_SMALL_SLOTS)
+
+// ans_reorder_fold.hpp:94-97 for blocks that cannot have T distinct values: the ints as they are, flag 0.  One wave per
+// block, grid stride over the class.
+__global__ __launch_bounds__(256) void k_rfold_remap_identity(const u32* __restrict__ in, ansx_geo g,
+    const u32* __restrict__ ids, u32 count, u32* __restrict__ mapped, ansx_blk* __restrict__ blk, u32* __restrict__ gflags)
+{
+    const u32 lane = threadIdx.x & 63u, nw = gridDim.x * 4u;
+    u32 vmax = 0;
+    for (u32 i = blockIdx.x * 4u + (threadIdx.x >> 6); i < count; i += nw) {
+        const u32 b = ids[i];
+        const u32 nb = geo_block_n(g, b);
+        const u64 at = geo_block_in(g, b);
+        for (u32 j = lane; j < nb; j += 64) {
+            const u32 v = in[at + j];
+            mapped[at + j] = v;
+            vmax = v > vmax ? v : vmax;
+        }
+        if (lane == 0) blk[b].flag = 0;
+    }
+    vmax = wave_max(vmax);
+    if (lane == 0 && vmax >= (1u << 30)) atomicOr(&gflags[ANSX_G_ERR], 1u << 6);
+}
+
+// One wave per block of T..ANSX_RF_SMALL_INTS ints, four blocks per workgroup; the waves share nothing and never wait
+// for each other (no workgroup barrier: a wave's own LDS traffic is ordered by wave_lds_sync).  The result is that of
+// rfold_remap_hash_body.  A lane holds 16 of the block's values and the table slots they went to; the lane whose insert
+// claimed a slot owns that distinct value.  With at most 1024 distinct values there is no threshold search: all
+// (-count, value) pairs are sorted, 16 per lane in registers (bitonic: partner distances below 16 inside the lane, the
+// others one shuffle away), and the first T are the selection in rank order (ans_reorder_fold.hpp:79-85).  The T
+// selected values are probed once more (bounded) to leave their ranks in the table; the remap of the block's ints then
+// reads the slot each lane remembered from its insert, without a probe.
+__global__ __launch_bounds__(256) void k_rfold_remap_small(const u32* __restrict__ in, ansx_geo g,
+    const u32* __restrict__ ids, u32 count, u32* __restrict__ mapped, u32* __restrict__ mostfreq,
     ansx_blk* __restrict__ blk, u32* __restrict__ gflags)
 {
-    rfold_remap_hash_body(in, g, slots, mapped, mostfreq, blk, gflags);
+    extern __shared__ u8 smem_rs[];
+    constexpr u32 SLOTS = ANSX_RF_SMALL_SLOTS, VPT = ANSX_RF_SMALL_INTS / 64u;
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const u32 idx = blockIdx.x * 4u + wv;
+    if (idx >= count) return;
+    const u32 b = ids[idx];
+    u32 nb = geo_block_n(g, b);
+    nb = nb < ANSX_RF_SMALL_INTS ? nb : ANSX_RF_SMALL_INTS;  // (the class's bound: what the registers and the table hold)
+    const u32 T = fold_T(g.f);
+    u8* base = smem_rs + (size_t)wv * ANSX_RF_SMALL_LDS;
+    u64* sel = (u64*)base;                                         // [ANSX_RF_SMALL_INTS]
+    u32* keys = (u32*)(base + 8u * ANSX_RF_SMALL_INTS);            // [SLOTS]
+    u32* cnt32 = keys + SLOTS;                                     // [SLOTS / 2], two u16 counters each
+    u16* rank16 = (u16*)cnt32;                                     // ... later a rank per slot
+    const u32* src = in + geo_block_in(g, b);
+    u32* dst = mapped + geo_block_in(g, b);
+    for (u32 i = lane; i < SLOTS; i += 64) keys[i] = ANSX_RF_EMPTY;
+    for (u32 i = lane; i < SLOTS / 2; i += 64) cnt32[i] = 0;
+    u32 vals[VPT], slot[VPT];
+#pragma unroll
+    for (u32 q = 0; q < VPT; q++) vals[q] = lane + 64 * q < nb ? src[lane + 64 * q] : 0u;
+    wave_lds_sync();
+    // ---- insert: value -> count (counts <= 1024 fit 16 bits)
+    u32 own = 0, lmax = 0;
+#pragma unroll
+    for (u32 q = 0; q < VPT; q++) {
+        slot[q] = SLOTS;  // none
+        if (lane + 64 * q < nb) {
+            const u32 v = vals[q];
+            lmax = v > lmax ? v : lmax;
+            u32 s = rf_slot(v, SLOTS);
+            // (the table is never more than half full; the bound only matters if the caller's buffer changes under us)
+            for (u32 probes = 0; probes < SLOTS; probes++) {
+                const u32 old = atomicCAS(&keys[s], ANSX_RF_EMPTY, v);
+                if (old == ANSX_RF_EMPTY) own |= 1u << q;
+                if (old == ANSX_RF_EMPTY || old == v) {
+                    slot[q] = s;
+                    break;
+                }
+                s = (s + 1) & (SLOTS - 1);
+            }
+            if (slot[q] < SLOTS) atomicAdd(&cnt32[slot[q] >> 1], 1u << (16 * (slot[q] & 1)));
+        }
+    }
+    wave_lds_sync();
+    const u32 mine = (u32)__builtin_popcount(own);
+    const u32 incl = wave_incl_scan(mine);
+    const u32 sigma = wave_last(incl);
+    const u32 vmax = wave_max(lmax);
+    if (lane == 0 && sigma > gflags[ANSX_G_RFDIST]) atomicMax(&gflags[ANSX_G_RFDIST], sigma);
+    if (sigma < T) {  // ans_reorder_fold.hpp:94-97: identity mapping, flag 0
+#pragma unroll
+        for (u32 q = 0; q < VPT; q++)
+            if (lane + 64 * q < nb) dst[lane + 64 * q] = vals[q];
+        if (lane == 0) {
+            blk[b].flag = 0;
+            if (vmax >= (1u << 30)) atomicOr(&gflags[ANSX_G_ERR], 1u << 6);
+        }
+        return;
+    }
+    if (lane == 0 && (u64)vmax + T >= (1u << 30)) atomicOr(&gflags[ANSX_G_ERR], 1u << 6);
+    // ---- the distinct values' (-count, value) pairs, behind each other in LDS; the rest of the 1024 sorts last
+    {
+        u32 pos = incl - mine;
+#pragma unroll
+        for (u32 q = 0; q < VPT; q++)
+            if ((own >> q) & 1u) {
+                const u32 c = (cnt32[slot[q] >> 1] >> (16 * (slot[q] & 1))) & 0xFFFFu;
+                if (pos < ANSX_RF_SMALL_INTS) sel[pos] = ((u64)(0xFFFFFFFFu - c) << 32) | (u64)vals[q];
+                pos++;
+            }
+        for (u32 i = sigma + lane; i < ANSX_RF_SMALL_INTS; i += 64) sel[i] = ~0ull;
+    }
+    wave_lds_sync();
+    // ---- sort: register q of a lane is element lane * 16 + q (which pair starts where does not matter)
+    u64 key[VPT];
+#pragma unroll
+    for (u32 q = 0; q < VPT; q++) key[q] = sel[q * 64 + lane];
+    for (u32 k = 2; k <= ANSX_RF_SMALL_INTS; k <<= 1) {
+        const bool asc_lane = ((lane * VPT) & k) == 0;  // (k >= 32: the same for the lane's 16 elements)
+        for (u32 j = k >> 1; j >= VPT; j >>= 1) {
+            const u32 m = j / VPT;
+            const bool keep_min = asc_lane == ((lane & m) == 0);
+#pragma unroll
+            for (u32 q = 0; q < VPT; q++) {
+                const u32 lo = (u32)__shfl_xor((int)(u32)key[q], (int)m);
+                const u32 hi = (u32)__shfl_xor((int)(u32)(key[q] >> 32), (int)m);
+                const u64 other = ((u64)hi << 32) | lo;
+                key[q] = keep_min ? (key[q] < other ? key[q] : other) : (key[q] < other ? other : key[q]);
+            }
+        }
+#pragma unroll
+        for (u32 j = VPT / 2; j > 0; j >>= 1) {
+            if (j < k) {
+#pragma unroll
+                for (u32 q = 0; q < VPT; q++)
+                    if ((q & j) == 0) {
+                        const bool asc = ((lane * VPT + q) & k) == 0;
+                        const u64 x = key[q], y = key[q | j];
+                        const bool sw = (x > y) == asc;
+                        key[q] = sw ? y : x;
+                        key[q | j] = sw ? x : y;
+                    }
+            }
+        }
+    }
+    // ---- ranks of the T selected values into the table (0xFFFF = not selected), and the block's mostfreq row
+    for (u32 i = lane; i < SLOTS / 2; i += 64) cnt32[i] = 0xFFFFFFFFu;
+    wave_lds_sync();
+    u32* mf = mostfreq + (u64)b * T;
+#pragma unroll
+    for (u32 q = 0; q < VPT; q++) {
+        const u32 r = lane * VPT + q;
+        if (r < T) {
+            const u32 v = (u32)key[q];
+            mf[r] = v;  // ans_reorder_fold.hpp:104-105
+            u32 s = rf_slot(v, SLOTS), probes = 0;
+            while (keys[s] != v && probes < SLOTS) {
+                s = (s + 1) & (SLOTS - 1);
+                probes++;
+            }
+            if (probes < SLOTS) rank16[s] = (u16)r;
+        }
+    }
+    wave_lds_sync();
+#pragma unroll
+    for (u32 q = 0; q < VPT; q++)
+        if (lane + 64 * q < nb) {
+            const u32 r = slot[q] < SLOTS ? (u32)rank16[slot[q]] : 0xFFFFu;
+            dst[lane + 64 * q] = (r != 0xFFFFu) ? r : vals[q] + T;  // :99-103
+        }
+    if (lane == 0) blk[b].flag = 1;
 }
 
 // ------------------------------------------------------------------------------------------
