@@ -235,6 +235,29 @@ int pipeline_prepare(ansx_ctx* c, u32 nranges)
 // worst-case bytes of one block's reference stream
 size_t codec_nsp(int kind, u32 f) { return kind == ANSX_MSB ? 2048u : (kind == ANSX_INT ? 16384u : fold_NSP(f)); }
 
+// Remap classes of a pass's blocks, by block length: ANSrfold's (ansx_rfold.h) and the compaction layer's (ansx_pa.h)
+enum { RF_CLS_IDENTITY = 0, RF_CLS_SMALL = 1, RF_CLS_LARGE = 2 };
+enum { PA_CLS_SMALL = 0, PA_CLS_LARGE = 1 };
+
+// The shortest symbol-row stride (Plan::NSP) the encode kernels take when no int they see exceeds `vmax` (a compacted
+// block's ranks: at most its length).  What a row must hold beyond the largest symbol `top` of 1..vmax, in one place:
+//   - top + 1 entries, the block's alphabet;
+//   - 8 more: k_scale_attempts and k_fold_hist read rows in chunks of 8 entries (ns rounded up to 8, plus a prefetch
+//     that is clamped to stride - 8), and rows must start on 16-byte boundaries (u16 rows: a multiple of 8 entries);
+//   - at least 64 entries: the floor of pre_cap, fcap and sort_cap (model_shape, write_preludes), which are then cut
+//     to min(stride, ...), and one full wave pass of k_sort_entropy / k_select_model;
+//   - a power of two, as every codec's own stride is (ANSX_HCOPY_PAD's bank argument, hist_packed's NSP / 2 words).
+// The stride selects launch shapes (model_shape, write_preludes) exactly as a codec's own slot count does, keys the
+// interp-geo tables (ansx_ctx::geo, one per distinct stride) and is no part of any stream.
+u32 min_row_stride(const ansx_map& m, u32 vmax)
+{
+    u32 top = 0;
+    for (u32 x = 1; x <= vmax; x++) top = std::max(top, map_sym(m, x, map_nbytes(m, x)));
+    u32 stride = 64;
+    while (stride < top + 1u + 8u) stride <<= 1;
+    return stride;
+}
+
 size_t block_bound(int kind, u32 f, size_t nb, bool pa = false)
 {
     size_t hdr = kind == ANSX_RFOLD ? 4 + 4 * (size_t)fold_T(f) : 0;
@@ -448,7 +471,7 @@ int rfold_remap(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u3
 int rfold_remap_pass(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u32* mostfreq, ansx_blk* blk,
     u32* gflags, hipStream_t s, u32 opt_slots, const u32* ids, const u32 ncls[3])
 {
-    const u32 n_id = ncls[0], n_small = ncls[1], n_large = ncls[2];
+    const u32 n_id = ncls[RF_CLS_IDENTITY], n_small = ncls[RF_CLS_SMALL], n_large = ncls[RF_CLS_LARGE];
     if (n_id)
         LAUNCH(c, "k_rfold_remap_identity", k_rfold_remap_identity, std::min<u32>(2048u, (n_id + 3) / 4), 256, 0, s, d_in, g, ids,
             n_id, mapped, blk, gflags);
@@ -594,8 +617,8 @@ struct EncBatchPass {
     u32 longest;              // ints of the pass's longest block: sizes the stream scratch stride
     ansx_encb_args A;         // device pointers of the plan, the results and the work area
     u64 in_base, in_ints;     // the pass's lists are ints [in_base, in_base + in_ints) of the caller's input
-    const u32* rf_ids;        // ANSrfold: block ids by remap class (identity | small | large), device; rf_ncls: how many of each
-    u32 rf_ncls[3];
+    const u32* remap_ids;     // block ids by remap class, device, class after class in the order of the form's enum below
+    u32 remap_ncls[3];        // (null where the form has no remap front); remap_ncls: how many blocks each class has
     u8* d_out;                // the caller's buffer
     const ansx_encb_res* hres;  // pinned: the results, read back with the attempt's flag words
 };
@@ -692,7 +715,7 @@ int encode_remap(ansx_ctx* c, EncodeWs& W)
         if ((rc = ensure(c, c->mapped, (size_t)std::max<u64>(B.in_ints, 1) * 4))) return rc;
         if ((rc = ensure(c, c->mostfreq, (size_t)NB * fold_T(g.f) * 4))) return rc;
         u32* biased = (u32*)((uintptr_t)c->mapped.p - (uintptr_t)B.in_base * 4);
-        if ((rc = rfold_remap_pass(c, g, W.d_in, biased, (u32*)c->mostfreq.p, W.blk, W.gflags, s, a.rf_slots, B.rf_ids, B.rf_ncls)))
+        if ((rc = rfold_remap_pass(c, g, W.d_in, biased, (u32*)c->mostfreq.p, W.blk, W.gflags, s, a.rf_slots, B.remap_ids, B.remap_ncls)))
             return rc;
         W.src = biased;
         W.mostfreq = (const u32*)c->mostfreq.p;
@@ -703,12 +726,37 @@ int encode_remap(ansx_ctx* c, EncodeWs& W)
         W.src = (const u32*)c->mapped.p;
         W.mostfreq = (const u32*)c->mostfreq.p;
     }
+    u32 *pa_mapped = nullptr, *pa_alpha = nullptr;  // ranks and running sums of the compaction layer / rank-space ANSint
     if (g.pa || a.int_sparse) {
-        if ((rc = ensure(c, c->mapped, (size_t)NB * g.block_ints * 4))) return rc;
-        if ((rc = ensure(c, c->pa_alpha, (size_t)NB * g.block_ints * 4))) return rc;
-        W.src = (const u32*)c->mapped.p;
+        // (a batch pass: both in the input's own index space, biased like ANSrfold's `mapped` above -- the one work list
+        // serves d_in, the ranks and the alphabets, and a block's alphabet, at most its ints, fits its own stretch)
+        const EncBatchPass* B = W.P->bat;
+        const size_t ints = B ? (size_t)std::max<u64>(B->in_ints, 1) : (size_t)NB * g.block_ints;
+        const uintptr_t bias = B ? (uintptr_t)B->in_base * 4 : 0;
+        if ((rc = ensure(c, c->mapped, ints * 4))) return rc;
+        if ((rc = ensure(c, c->pa_alpha, ints * 4))) return rc;
+        pa_mapped = (u32*)((uintptr_t)c->mapped.p - bias);
+        pa_alpha = (u32*)((uintptr_t)c->pa_alpha.p - bias);
+        W.src = pa_mapped;
     }
-    if (g.pa) {
+    // the blocks k_pa_remap / k_pa_header take: all of them, or the large class of a batch pass through its ids
+    const u32* pa_ids = nullptr;
+    u32 pa_large = NB;
+    if (g.pa && W.P->bat) {
+        // a batch pass: one launch pair per class of blocks that has any (ansx_pa.h); no table, no sizes for the small one
+        const EncBatchPass& B = *W.P->bat;
+        const u32 n_small = B.remap_ncls[PA_CLS_SMALL];
+        if (n_small) {
+            LAUNCH(c, "k_pa_remap_small", k_pa_remap_small, std::min<u32>(2048u, (n_small + 3) / 4), 256, 0, s, W.d_in, g, B.remap_ids,
+                n_small, pa_mapped, pa_alpha, W.blk, W.gflags, 1u << 30);
+            const u32 cap = ANSX_PA_SMALL_INTS;
+            LAUNCH(c, "k_pa_header", k_pa_header, n_small, 256, ((size_t)3 * cap + 32) * 4, s, g, (const u32*)pa_alpha, W.blk,
+                (u8*)c->scratch.p, W.scr_stride, cap, B.remap_ids);
+        }
+        pa_ids = B.remap_ids + n_small;
+        pa_large = B.remap_ncls[PA_CLS_LARGE];
+    }
+    if (g.pa && pa_large) {
         // per-block alphabet compaction (src/pseudo_adaptive.cpp:85-130): alphabet header into the block's scratch slot, the
         // codec then runs on the 1-based ranks.  Sizes from the geometry's distinct-value hint (optimistic calls only): hash set 2.5 x, value list the next
         // power of two above 1.25 x; both workgroups of a CU must fit its LDS
@@ -724,24 +772,24 @@ int encode_remap(ansx_ctx* c, EncodeWs& W)
         const size_t lds1 = ((size_t)pa_slots + pa_uqcap) * 4;
         if (pa_small) {
             HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-            LAUNCH(c, "k_pa_remap", k_pa_remap2, NB, 1024, lds1, s, W.d_in, g, pa_slots, pa_uqcap, (u32*)c->mapped.p,
-                (u32*)c->pa_alpha.p, W.blk, W.gflags, 1u << 30);
+            LAUNCH(c, "k_pa_remap", k_pa_remap2, pa_large, 1024, lds1, s, W.d_in, g, pa_slots, pa_uqcap, pa_mapped, pa_alpha, W.blk,
+                W.gflags, 1u << 30, pa_ids);
         } else {
             HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-            LAUNCH(c, "k_pa_remap", k_pa_remap, NB, 1024, lds1, s, W.d_in, g, pa_slots, pa_uqcap, (u32*)c->mapped.p,
-                (u32*)c->pa_alpha.p, W.blk, W.gflags, 1u << 30, 0u);
+            LAUNCH(c, "k_pa_remap", k_pa_remap, pa_large, 1024, lds1, s, W.d_in, g, pa_slots, pa_uqcap, pa_mapped, pa_alpha, W.blk,
+                W.gflags, 1u << 30, 0u, pa_ids);
         }
         const size_t lds2 = pa_small ? ((size_t)3 * pa_uqcap + 32) * 4 : ((size_t)2 * ANSX_PA_MAX_BLOCK + 16) * 4;
         HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_header, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        LAUNCH(c, "k_pa_header", k_pa_header, NB, 256, lds2, s, g, (const u32*)c->pa_alpha.p, W.blk, (u8*)c->scratch.p,
-            W.scr_stride, pa_small ? pa_uqcap : (u32)ANSX_PA_MAX_BLOCK);
+        LAUNCH(c, "k_pa_header", k_pa_header, pa_large, 256, lds2, s, g, (const u32*)pa_alpha, W.blk, (u8*)c->scratch.p,
+            W.scr_stride, pa_small ? pa_uqcap : (u32)ANSX_PA_MAX_BLOCK, pa_ids);
     }
     if (a.int_sparse) {
         // plain ANSint on values beyond the dense model (ansx_intsparse.h): the codec runs on every block's 0-based ranks
         const size_t lds1 = ((size_t)ANSX_PA_SLOTS + ANSX_PA_MAX_BLOCK) * 4;
         HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        LAUNCH(c, "k_pa_remap", k_pa_remap, NB, 1024, lds1, s, W.d_in, g, (u32)ANSX_PA_SLOTS, (u32)ANSX_PA_MAX_BLOCK, (u32*)c->mapped.p,
-            (u32*)c->pa_alpha.p, W.blk, W.gflags, (u32)ANSX_SP_VALUE_LIMIT, 1u);
+        LAUNCH(c, "k_pa_remap", k_pa_remap, NB, 1024, lds1, s, W.d_in, g, (u32)ANSX_PA_SLOTS, (u32)ANSX_PA_MAX_BLOCK, pa_mapped,
+            pa_alpha, W.blk, W.gflags, (u32)ANSX_SP_VALUE_LIMIT, 1u, (const u32*)nullptr);
     }
     W.out->src = W.src;
     return ANSX_OK;
@@ -2687,10 +2735,11 @@ struct EncBatchHints {
 // launch_f64_encoder.  Such a list goes through encode_dev into its place.
 #define ANSX_ENCB_LONG_BLOCKS 16u
 
-// geometries the batched path takes: the LDS-model codecs without compaction
+// geometries the batched path takes: the LDS-model codecs, ANSfold and ANSmsb also with compaction (whose blocks are at
+// most 16384 ints: make_plan); ANSint has none
 bool encode_batch_form(const ansx_geo& g)
 {
-    if (g.pa) return false;
+    if (g.pa) return g.kind == ANSX_MSB || (g.kind == ANSX_FOLD && g.f <= 5);
     // (ANSrfold: the remap of a pass has the LDS forms only, ansx_rfold.h)
     return g.kind == ANSX_MSB || (g.kind == ANSX_FOLD && g.f <= 5) || (g.kind == ANSX_RFOLD && g.f <= 5 && g.block_ints <= 16384u);
 }
@@ -2703,11 +2752,11 @@ int encode_batch_pass(ansx_ctx* c, const Plan& P0, const u32* d_in, const u64* o
     int rc;
     const u64 bi = P0.g.block_ints;
     const u32 nl = (u32)(l1 - l0);
-    // the plan, one upload from pinned memory: blocks | lists | ANSrfold's block ids by remap class; behind it on the
-    // device: maxima | results | block sums
-    const bool rf = P0.g.kind == ANSX_RFOLD;
+    // the plan, one upload from pinned memory: blocks | lists | the block ids by remap class of ANSrfold or the compaction
+    // layer; behind it on the device: maxima | results | block sums
+    const bool rf = P0.g.kind == ANSX_RFOLD, pa = P0.g.pa != 0;
     const size_t o_l = sizeof(ansx_blk_in) * (size_t)NB, o_i = o_l + sizeof(ansx_encb_list) * ((size_t)nl + 1);
-    const size_t o_m = o_i + (rf ? rup(4 * (size_t)NB, 16) : 0);
+    const size_t o_m = o_i + (rf || pa ? rup(4 * (size_t)NB, 16) : 0);
     const size_t o_r = o_m + sizeof(ansx_encb_max) * (size_t)nl, o_s = o_r + sizeof(ansx_encb_res) * ((size_t)nl + 1);
     const size_t plan_bytes = o_s + 8 * ((size_t)NB + 1);
     const size_t res_bytes = sizeof(ansx_encb_res) * ((size_t)nl + 1);
@@ -2728,9 +2777,12 @@ int encode_batch_pass(ansx_ctx* c, const Plan& P0, const u32* d_in, const u64* o
     hl[nl] = { 0, k, 0 };
     if (k != NB) return ANSX_ERR_ARG;  // (cannot happen: the caller counted the same blocks)
     u32 ncls[3] = { 0, 0, 0 };
-    if (rf) {  // the remap classes (ansx_rfold.h), by block length: counted, then every class's ids in block order
+    if (rf || pa) {  // the remap classes (ansx_rfold.h, ansx_pa.h), by block length: counted, then every class's ids in block order
         const u32 T = fold_T(P0.g.f);
-        auto cls = [&](u32 nb) { return nb < T ? 0u : (nb <= ANSX_RF_SMALL_INTS ? 1u : 2u); };
+        auto cls = [&](u32 nb) -> u32 {
+            if (pa) return nb <= ANSX_PA_SMALL_INTS ? PA_CLS_SMALL : PA_CLS_LARGE;
+            return nb < T ? RF_CLS_IDENTITY : (nb <= ANSX_RF_SMALL_INTS ? RF_CLS_SMALL : RF_CLS_LARGE);
+        };
         for (u32 b = 0; b < NB; b++) ncls[cls(hblk[b].n)]++;
         u32* hid = (u32*)(hb + o_i);
         u32 at[3] = { 0, ncls[0], ncls[0] + ncls[1] };
@@ -2750,17 +2802,20 @@ int encode_batch_pass(ansx_ctx* c, const Plan& P0, const u32* d_in, const u64* o
     P.g.n = (u64)(NB - 1) * bi + 1;
     P.g.nblocks = NB;
     P.g.bin = (const ansx_blk_in*)dp;
+    // (the ints the codec sees are ranks of at most the block's length: 770 MiB of model arrays for 16384 ten-int lists
+    // with the codec's own 1024 slots per row)
+    if (pa) P.NSP = std::min(P.NSP, min_row_stride(P.g.map, longest));
     set_restart_format(&P, true);
     if ((rc = ensure(c, c->enb_wc, (size_t)P.lay.payload_off + 64))) return rc;
     u8* wc = (u8*)c->enb_wc.p;
-    const size_t stream_bound = block_bound(P.g.kind, P.g.f, P.g.block_ints, false) + 16;
+    const size_t stream_bound = block_bound(P.g.kind, P.g.f, P.g.block_ints, pa) + 16;
     EncBatchPass B;
     B.hblk = hblk;
     B.longest = longest;
     B.in_base = offsets[l0];
     B.in_ints = offsets[l1] - offsets[l0];
-    B.rf_ids = rf ? (const u32*)(dp + o_i) : nullptr;
-    memcpy(B.rf_ncls, ncls, sizeof(ncls));
+    B.remap_ids = rf || pa ? (const u32*)(dp + o_i) : nullptr;
+    memcpy(B.remap_ncls, ncls, sizeof(ncls));
     B.A.bin = P.g.bin;
     B.A.lists = (const ansx_encb_list*)(dp + o_l);
     B.A.mx = (ansx_encb_max*)(dp + o_m);

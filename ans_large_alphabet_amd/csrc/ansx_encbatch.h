@@ -82,7 +82,9 @@ __global__ __launch_bounds__(1024) void k_encb_scan(ansx_geo g, ansx_encb_args A
         if (b < NB) {
             v = sizes[b];
             const ansx_blk* B = &blk[b];
-            if (!B->status && B->resolved) {
+            // (a one-value block of the compaction layer is marked resolved but has no model: as in the call's own maxima,
+            // k_select_model, it does not count)
+            if (!B->status && B->resolved && B->pa_sigma != 1) {
                 ansx_encb_max* m = &A.mx[A.bin[b].list];
                 atomicMax(&m->logM, B->logM);
                 atomicMax(&m->ns, B->max_sym + 1u);

@@ -9,6 +9,7 @@
 // block's distinct values must stay below 2^32 - 1 (ANSX_ERR_DOMAIN otherwise).
 //
 //   encode: k_pa_remap   distinct values (LDS hash set), sorted, ranks by binary search; running sums
+//                        (k_pa_remap_small for the blocks of up to 1024 ints of a batch pass: one wave per block)
 //           k_pa_header  interpolative code of the running sums (the prelude writer's machinery)
 //           ... then the codec's kernels on the remapped block ...
 //   decode: k_pa_parse   alphabet header -> values, one lane per block
@@ -31,9 +32,11 @@ __device__ __forceinline__ u32 pa_slot(u32 v, u32 slots) { return (u32)(((u64)(v
 // values a block of the geometry had so far (as k_rfold_remap_hash: two workgroups per CU on the 64-register build
 // k_pa_remap2; a block that does not fit raises the violation flag, leaves a valid one-value block, and the call is
 // repeated with the full sizes).
+// ids != null (a batch pass): workgroup i takes block ids[i].  A block's ints, its ranks and its running sums all start
+// at geo_block_in(g, b) of their array: where the work list g.bin says, or at b * block_ints without one.
 __device__ __forceinline__ void pa_remap_body(const u32* __restrict__ in, const ansx_geo& g, u32 slots, u32 uqcap,
     u32* __restrict__ mapped, u32* __restrict__ alpha_sum, ansx_blk* __restrict__ blk, u32* __restrict__ gflags,
-    u32 value_limit, u32 mode = 0)
+    u32 value_limit, const u32* __restrict__ ids, u32 mode = 0)
 {
     // mode 1 (plain ANSint in rank space, ansx_intsparse.h): alpha_sum receives the distinct VALUES (not their running
     // sums: no 32-bit sum to overflow), ranks are 0-based, the count goes to blk[].sp_sigma -- a one-value block keeps its
@@ -44,10 +47,11 @@ __device__ __forceinline__ void pa_remap_body(const u32* __restrict__ in, const 
     u32* keys = pa_lds;                  // [slots]
     u32* uq = pa_lds + slots;            // [uqcap] distinct values (uqcap: a power of two >= 1024)
     const u32 tid = threadIdx.x, nt = 1024;
-    const u32 b = blockIdx.x;
+    const u32 b = ids ? ids[blockIdx.x] : blockIdx.x;
     const u32 nb = geo_block_n(g, b);
-    const u32* src = in + (u64)b * g.block_ints;
-    u32* dst = mapped + (u64)b * g.block_ints;
+    const u64 at = geo_block_in(g, b);
+    const u32* src = in + at;
+    u32* dst = mapped + at;
     for (u32 i = tid; i < slots; i += nt) keys[i] = ANSX_PA_EMPTY;
     if (tid == 0) {
         sh_cnt = 0;
@@ -96,7 +100,7 @@ __device__ __forceinline__ void pa_remap_body(const u32* __restrict__ in, const 
     if (mode == 1 && (sh_ovf || sh_cnt > uqcap)) {  // more distinct values than the rank-space model has symbols: ANSX_ERR_DOMAIN
         for (u32 i = tid; i < nb; i += nt) dst[i] = 0;
         if (tid == 0) {
-            alpha_sum[(u64)b * g.block_ints] = 0;
+            alpha_sum[at] = 0;
             blk[b].sp_sigma = 1;
             atomicOr(&gflags[ANSX_G_ERR], 1u << 6);
         }
@@ -105,7 +109,7 @@ __device__ __forceinline__ void pa_remap_body(const u32* __restrict__ in, const 
     if (sh_ovf || sh_cnt > uqcap) {  // optimistic sizes too small: a valid one-value block, and the call is repeated
         for (u32 i = tid; i < nb; i += nt) dst[i] = 1;
         if (tid == 0) {
-            alpha_sum[(u64)b * g.block_ints] = 0;
+            alpha_sum[at] = 0;
             blk[b].pa_sigma = 1;
             atomicOr(&gflags[ANSX_G_ERR], 1u << ANSX_G_VIOL_BIT);
             atomicMax(&gflags[ANSX_G_RFDIST], sh_cnt > slots ? sh_cnt : slots);
@@ -179,7 +183,7 @@ __device__ __forceinline__ void pa_remap_body(const u32* __restrict__ in, const 
     default: sort_regs(std::integral_constant<u32, 16>{}); break;
     }
     if (mode == 1) {
-        u32* as = alpha_sum + (u64)b * g.block_ints;
+        u32* as = alpha_sum + at;
         for (u32 j = tid; j < sigma; j += nt) as[j] = uq[j];
         if (tid == 0) blk[b].sp_sigma = sigma;
     } else
@@ -191,7 +195,7 @@ __device__ __forceinline__ void pa_remap_body(const u32* __restrict__ in, const 
         for (u32 j = lo; j < hi; j++) sum += uq[j];
         u64 total;
         u64 run = block_excl_scan<u64>(sum, sh_part64, tid, nt, &total);
-        u32* as = alpha_sum + (u64)b * g.block_ints;
+        u32* as = alpha_sum + at;
         for (u32 j = lo; j < hi; j++) {
             run += uq[j];
             as[j] = (u32)run;
@@ -228,31 +232,153 @@ __device__ __forceinline__ void pa_remap_body(const u32* __restrict__ in, const 
 
 __global__ __launch_bounds__(1024) void k_pa_remap(const u32* __restrict__ in, ansx_geo g, u32 slots, u32 uqcap,
     u32* __restrict__ mapped, u32* __restrict__ alpha_sum, ansx_blk* __restrict__ blk, u32* __restrict__ gflags, u32 value_limit,
-    u32 mode)
+    u32 mode, const u32* __restrict__ ids)
 {
-    pa_remap_body(in, g, slots, uqcap, mapped, alpha_sum, blk, gflags, value_limit, mode);
+    pa_remap_body(in, g, slots, uqcap, mapped, alpha_sum, blk, gflags, value_limit, ids, mode);
 }
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_pa_remap2(const u32* __restrict__ in,
     ansx_geo g, u32 slots, u32 uqcap, u32* __restrict__ mapped, u32* __restrict__ alpha_sum, ansx_blk* __restrict__ blk,
-    u32* __restrict__ gflags, u32 value_limit)
+    u32* __restrict__ gflags, u32 value_limit, const u32* __restrict__ ids)
 {
-    pa_remap_body(in, g, slots, uqcap, mapped, alpha_sum, blk, gflags, value_limit);
+    pa_remap_body(in, g, slots, uqcap, mapped, alpha_sum, blk, gflags, value_limit, ids);
+}
+
+// The blocks of at most ANSX_PA_SMALL_INTS ints of a batch pass (ansx_encode_batch_dev): one wave
+// per block, four per workgroup, grid stride over the class's block ids; the waves share nothing and never wait for
+// each other (no workgroup barrier: a wave's own LDS traffic is ordered by wave_lds_sync).  What it writes is what
+// pa_remap_body writes in mode 0.  No hash set: a lane holds 16 of the block's values, the wave sorts all of them in
+// registers (the bitonic network of k_rfold_remap_small: partner distances below 16 inside the lane, the others one
+// shuffle away), a value that differs from its predecessor is a distinct one, a wave scan of their counts gives sigma and
+// packs them, ascending, into the wave's 4 KB of LDS; the ranks are lower bounds over that array, as in the workgroup
+// kernel.  Nothing here can overflow, so there is no optimistic size and no repeat.
+#define ANSX_PA_SMALL_INTS 1024u
+__global__ __launch_bounds__(256) void k_pa_remap_small(const u32* __restrict__ in, ansx_geo g,
+    const u32* __restrict__ ids, u32 count, u32* __restrict__ mapped, u32* __restrict__ alpha_sum,
+    ansx_blk* __restrict__ blk, u32* __restrict__ gflags, u32 value_limit)
+{
+    constexpr u32 VPT = ANSX_PA_SMALL_INTS / 64u;
+    __shared__ u32 uq_all[4][ANSX_PA_SMALL_INTS];
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    u32* uq = uq_all[wv];  // the block's distinct values, ascending, padded to a power of two
+    for (u32 idx = blockIdx.x * 4u + wv; idx < count; idx += gridDim.x * 4u) {
+        const u32 b = ids[idx];
+        u32 nb = geo_block_n(g, b);
+        nb = nb < ANSX_PA_SMALL_INTS ? nb : ANSX_PA_SMALL_INTS;  // (the class's bound: what the registers hold)
+        const u64 at = geo_block_in(g, b);
+        const u32* src = in + at;
+        u32* dst = mapped + at;
+        u32* as = alpha_sum + at;
+        // the ints beyond the block sort last (an int of that value is beyond the limit anyway: the call fails)
+        u32 vals[VPT], key[VPT];
+        u32 lmax = 0;
+#pragma unroll
+        for (u32 q = 0; q < VPT; q++) {
+            const bool have = lane + 64 * q < nb;
+            vals[q] = have ? src[lane + 64 * q] : 0xFFFFFFFFu;
+            lmax = have && vals[q] > lmax ? vals[q] : lmax;
+            key[q] = vals[q];
+        }
+        // ---- sort: register q of a lane is element lane * 16 + q (which int starts where does not matter)
+        for (u32 k = 2; k <= ANSX_PA_SMALL_INTS; k <<= 1) {
+            const bool asc_lane = ((lane * VPT) & k) == 0;  // (k >= 32: the same for the lane's 16 elements)
+            for (u32 j = k >> 1; j >= VPT; j >>= 1) {
+                const u32 m = j / VPT;
+                const bool keep_min = asc_lane == ((lane & m) == 0);
+#pragma unroll
+                for (u32 q = 0; q < VPT; q++) {
+                    const u32 other = (u32)__shfl_xor((int)key[q], (int)m);
+                    key[q] = keep_min ? (key[q] < other ? key[q] : other) : (key[q] < other ? other : key[q]);
+                }
+            }
+#pragma unroll
+            for (u32 j = VPT / 2; j > 0; j >>= 1) {
+                if (j < k) {
+#pragma unroll
+                    for (u32 q = 0; q < VPT; q++)
+                        if ((q & j) == 0) {
+                            const bool asc = ((lane * VPT + q) & k) == 0;
+                            const u32 x = key[q], y = key[q | j];
+                            const bool sw = (x > y) == asc;
+                            key[q] = sw ? y : x;
+                            key[q | j] = sw ? x : y;
+                        }
+                }
+            }
+        }
+        // ---- the distinct values: the first of every run among the block's own nb elements; their running sums
+        // (pseudo_adaptive.cpp:103-105, u32 there: the exact sum must fit)
+        const u32 before = (u32)__shfl_up((int)key[VPT - 1], 1);
+        u32 heads = 0;
+        u64 lsum = 0;
+#pragma unroll
+        for (u32 q = 0; q < VPT; q++) {
+            const u32 e = lane * VPT + q;
+            const u32 prev = q ? key[q - 1] : before;
+            const bool head = e < nb && (e == 0 || key[q] != prev);
+            heads |= head ? 1u << q : 0u;
+            lsum += head ? (u64)key[q] : 0ull;
+        }
+        const u32 mine = (u32)__builtin_popcount(heads);
+        const u32 incl = wave_incl_scan(mine);
+        const u32 sigma = wave_last(incl);
+        const u64 sincl = wave_incl_scan(lsum);
+        const u64 total = wave_last(sincl);
+        const u32 vmax = wave_max(lmax);
+        u32 N2 = 1;
+        while (N2 < sigma) N2 <<= 1;
+        wave_lds_sync();  // (the previous block's searches have read uq)
+        {
+            u32 pos = incl - mine;
+            u64 run = sincl - lsum;
+#pragma unroll
+            for (u32 q = 0; q < VPT; q++)
+                if ((heads >> q) & 1u) {
+                    run += key[q];
+                    uq[pos] = key[q];  // (pos < sigma <= nb)
+                    as[pos] = (u32)run;
+                    pos++;
+                }
+            for (u32 i = sigma + lane; i < N2; i += 64) uq[i] = 0xFFFFFFFFu;
+        }
+        if (lane == 0) {
+            if (vmax >= value_limit || total >= 0xFFFFFFFFull) atomicOr(&gflags[ANSX_G_ERR], 1u << 6 /* ANSX_ERR_DOMAIN */);
+            blk[b].pa_sigma = sigma;
+            if (sigma > gflags[ANSX_G_RFDIST]) atomicMax(&gflags[ANSX_G_RFDIST], sigma);
+        }
+        wave_lds_sync();
+        // ---- 1-based rank of every int (:91-103): branch-free lower bound, the lane's 16 searches advancing together
+        u32 lo[VPT];
+#pragma unroll
+        for (u32 q = 0; q < VPT; q++) lo[q] = 0;
+        for (u32 st = N2 >> 1; st > 0; st >>= 1) {
+            u32 probe[VPT];
+#pragma unroll
+            for (u32 q = 0; q < VPT; q++) probe[q] = uq[lo[q] + st - 1];
+#pragma unroll
+            for (u32 q = 0; q < VPT; q++) lo[q] += probe[q] < vals[q] ? st : 0u;
+        }
+#pragma unroll
+        for (u32 q = 0; q < VPT; q++)
+            if (lane + 64 * q < nb) dst[lane + 64 * q] = lo[q] + 1u;
+    }
 }
 
 // Alphabet header: one workgroup of 256 threads per block (the prelude writer's generic path).  `cap` = words per
 // LDS array: ANSX_PA_MAX_BLOCK (offsets + bit buffer = 128 KB: one workgroup per CU, the running sums read from
 // HBM), or the value-list capacity k_pa_remap ran with on an optimistic call (a few thousand: three arrays --
 // the running sums are staged too -- and three workgroups per CU; a block k_pa_remap gave up on has sigma = 1).
+// ids != null (a batch pass): workgroup i takes block ids[i], and cap is that of the class (1024 for the blocks of
+// k_pa_remap_small: 12 KB of LDS).
 __global__ __launch_bounds__(256) void k_pa_header(ansx_geo g, const u32* __restrict__ alpha_sum,
-    ansx_blk* __restrict__ blk, u8* __restrict__ scratch, u64 scr_stride, u32 cap)
+    ansx_blk* __restrict__ blk, u8* __restrict__ scratch, u64 scr_stride, u32 cap, const u32* __restrict__ ids)
 {
     extern __shared__ u32 lds32[];
     __shared__ u32 sh_part[8];
     const u32 tid = threadIdx.x;
-    const u32 b = blockIdx.x;
+    const u32 b = ids ? ids[blockIdx.x] : blockIdx.x;
     ansx_blk* B = &blk[b];
     const u32 sigma = B->pa_sigma;
-    const u32* as = alpha_sum + (u64)b * g.block_ints;
+    const u32* as = alpha_sum + geo_block_in(g, b);
     u32* off = lds32;           // [sigma]
     u32* bits = lds32 + cap;    // bit buffer (the code of sigma ascending values below 2^32 takes at most sigma words)
     const u32* inc = as;

@@ -285,11 +285,12 @@ int ansx_decode_batch_ranges_dev(ansx_ctx* ctx, int kind, int fidelity, const ui
  * ansx_encode_dev; opts->block_ints == ANSX_SINGLE_STREAM (a batch yields containers).  count == 0: ANSX_OK, total 0,
  * nothing launched.
  * Errors found on the device: ANSX_ERR_DOMAIN, ANSX_ERR_MODEL, ANSX_ERR_CAPACITY, with *bad_index = count unless the
- * list is known (one that was encoded on its own, see below; lists of ANSX_RFOLD with fidelity 1..5 run in passes and
- * are among those not named).  d_out is then unspecified, but nothing is ever written
+ * list is known (one that was encoded on its own, see below; lists of ANSX_RFOLD with fidelity 1..5 and compacted lists
+ * of ANSX_FOLD with fidelity 1..5 and of ANSX_MSB run in passes and are among those not named).  d_out is then
+ * unspecified, but nothing is ever written
  * at or beyond d_out + out_capacity.  The context stays usable after any error.
- * How the work is done.  ANSX_FOLD and ANSX_RFOLD (block_ints <= 16384) with fidelity 1..5 and ANSX_MSB, without
- * compaction, take the batched path: the
+ * How the work is done.  ANSX_FOLD and ANSX_RFOLD (block_ints <= 16384) with fidelity 1..5 and ANSX_MSB take the batched
+ * path, ANSX_FOLD and ANSX_MSB also with ANSX_FLAG_COMPACT_ALPHABET: the
  * lists are grouped, in batch order and cut at list boundaries only, into passes of at most 16384 blocks
  * (ANSX_BATCH_PASS_BLOCKS, the key ansx_decode_batch_dev uses); the model, prelude and encoder kernels run once per
  * pass over all its blocks, one kernel pair assembles every container of the pass in place, and one read-back per pass
@@ -298,11 +299,16 @@ int ansx_decode_batch_ranges_dev(ansx_ctx* ctx, int kind, int fidelity, const ui
  * ANSX_RFOLD's remap of a pass runs one kernel per class of blocks: blocks of fewer than T = 2^(fidelity + 7) ints are
  * copied (they cannot have T distinct values), blocks of T..1024 ints take a kernel with one wave per block, longer
  * blocks the hash-table kernel of ansx_encode_dev; a table that the batch's own hint sized too small repeats the pass,
- * not the batch.  ANSX_INT, compaction and fidelity 6, 7 have NO batched
+ * not the batch.  With compaction the remap of a pass has two classes: blocks of up to 1024 ints take a kernel with
+ * one wave per block that sorts the block (no table, nothing to size or repeat), longer blocks the hash-set kernel of
+ * ansx_encode_dev, sized from the batch's own hint; a set that is too small repeats the pass.  ANSX_INT (with and
+ * without compaction) and fidelity 6, 7 have NO batched
  * path yet: they are accepted and bit-identical, but every list is encoded on its own inside the call, at the cost
  * of a loop of ansx_encode_dev.  Workspace: bounded by one pass (or the largest single list), not by the batch; for
  * ANSX_RFOLD it includes the pass's remapped ints and T * 4 bytes per block of the pass for the selected values
- * (256 MiB for a full pass of 16384 blocks at fidelity 5).
+ * (256 MiB for a full pass of 16384 blocks at fidelity 5), with compaction 8 bytes per int of the pass (ranks and
+ * alphabets), and the model arrays' rows of a compacted pass are as long as the ranks of its longest block need, not
+ * as the codec's alphabet.
  * No trace: the call keeps the alphabet and frame hints it learns in a slot of its own and puts
  * ansx_last_encode_stats back, so a later ansx_encode_dev behaves -- path and bytes -- as if the batch call had not
  * happened; a batch of short lists does not teach the context a small alphabet.  Synchronous, like ansx_encode_dev;
