@@ -135,6 +135,7 @@ struct ansx_ctx {
         bool force_pc = false;        // ANSX_FORCE_PC: the pair kernel for every workgroup of 64 full blocks, however few (tests)
         bool no_pc = false;           // ANSX_NO_PC: the LDS-table encoder as one wave per 16 blocks everywhere (k_encode<1>), no producer / consumer pairs
         int decode_small_ring = 0;    // ANSX_DECODE_SMALL_RING: "never" / "always" (default: by the container's bytes per int)
+        bool setup_old = false;       // ANSX_DECODE_SETUP=old: windowed subtrees in k_parse_prelude_par, scan form of the decoder's table build
         int decode_pair = 0;          // ANSX_DECODE_PAIR: "0"/unset auto, "never", "always" (k_decode_rank2: two blocks per workgroup)
         u32 pair_lds_limit = 0;       // ANSX_DECODE_PAIR_LDS: auto uses the pair kernel up to this many bytes of LDS per workgroup (0: never --
                                       // measured SLOWER than one block per workgroup, 0.77-0.79 vs 0.72 ms on the headline workload)
@@ -1540,6 +1541,18 @@ int encode_dev(ansx_ctx* c, const Plan& P0, const u32* d_in, u8* d_out, size_t c
 }
 
 // --------------------------------------------------------------------------------- decode
+// Which subtree form k_parse_prelude_par runs, from header fields only: a depth-3 subtree has at most max_ns >> 3
+// items; its value array (two sentinels more) and ANSX_PAR_STK stack rows must fit the 48 rows behind the staged words.
+// 1: u16 elements (every value fits: frame + alphabet + 3 <= 65535), 2: u32 elements, 0: the windowed form.
+static int ansx_par_form(u32 max_ns, u32 maxM)
+{
+    const size_t room = (size_t)(48 - ANSX_PAR_STK) * 64 * 4;
+    const size_t elems = (size_t)(max_ns >> 3) + 2;
+    if ((u64)maxM + max_ns + 3 <= 65535u && elems * 64 * 2 <= room) return 1;
+    if (elems * 64 * 4 <= room) return 2;
+    return 0;
+}
+
 template <bool RF>
 int launch_decode(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u8* cont, const u64* boff,
     const u64* ck_state, const u32* ck_off, u64 payload_off, u32* d_out, u32 maxM, u32 max_ns,
@@ -1568,17 +1581,29 @@ int launch_decode(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u8* cont, const
         LAUNCH(c, "k_parse_prelude", (k_parse_prelude<RF>), (g.nblocks + 63) / 64, 64, 0, s, cont, g, NSP,
             boff, payload_off, max_ns, maxM, (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, gflags, pa_info);
     } else if (hints != nullptr && !c->dbg.parse_win && !c->dbg.parse_fast) {
+        // Subtree form: value arrays (u16 / u32 elements) where a depth-3 subtree's array fits the slice the windowed
+        // form needs anyway, from header fields only; otherwise, or with ANSX_DECODE_SETUP=old, the windowed form.
+        const int form = c->dbg.setup_old ? 0 : ansx_par_form(max_ns, maxM);
         // Waves per workgroup (each wave works alone on its own LDS slice): measured on MI355X at 16384 blocks,
-        // 530-symbol tables 1/2/3/4 waves -> 0.161/0.162/0.109/0.122 ms, 2300-symbol tables 0.275/0.273/0.286/0.252.
+        // windowed form: 530-symbol tables 1/2/3/4 waves -> 0.161/0.162/0.109/0.122 ms, 2300-symbol tables
+        // 0.275/0.273/0.286/0.252; value-array form (event-timed, so ~0.005 above the kernel's own time): 526-symbol
+        // tables 0.062/0.062/0.068/0.056, 257-symbol tables 0.045/0.042/0.048/0.039.
         const u32 par_waves = (g.nblocks + 7) / 8;
-        const u32 pw_max = max_ns <= 1024 ? 3u : 4u;
+        const u32 pw_max = (form != 0 || max_ns > 1024) ? 4u : 3u;
         const u32 pw = std::min<u32>(pw_max, std::max<u32>(1u, (par_waves + c->num_cus - 1) / c->num_cus));
         const u32 par_grid = (par_waves + pw - 1) / pw;
-        const size_t lds = (size_t)pw * (32 + 48) * 64 * 4;
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_parse_prelude_par<RF, 32>,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(c, "k_parse_prelude", (k_parse_prelude_par<RF, 32>), par_grid, 64 * pw, lds, s, cont, g, NSP, boff,
-            payload_off, max_ns, maxM, hints, (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, gflags, pa_info);
+        const size_t lds = (size_t)pw * ANSX_PAR_SLICE_WORDS * 4;
+#define ANSX_LAUNCH_PAR(FORM, label)                                                                                        \
+    do {                                                                                                                    \
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_parse_prelude_par<RF, ANSX_PAR_SW, FORM>,                              \
+                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                               \
+        LAUNCH(c, label, (k_parse_prelude_par<RF, ANSX_PAR_SW, FORM>), par_grid, 64 * pw, lds, s, cont, g, NSP, boff,       \
+            payload_off, max_ns, maxM, hints, (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, gflags, pa_info);                  \
+    } while (0)
+        if (form == 1) ANSX_LAUNCH_PAR(1, "k_parse_prelude_arr");
+        else if (form == 2) ANSX_LAUNCH_PAR(2, "k_parse_prelude_arr");
+        else ANSX_LAUNCH_PAR(0, "k_parse_prelude");
+#undef ANSX_LAUNCH_PAR
     } else if (c->dbg.parse_fast && (u64)maxM + max_ns + 3 <= 65535u && pf_lds <= 150 * 1024) {
         HIPCHK(c, hipFuncSetAttribute((const void*)k_parse_prelude_fast<RF>,
                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)pf_lds));
@@ -1604,6 +1629,7 @@ int launch_decode(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u8* cont, const
     const size_t mfb = RF ? (size_t)T * 4 : 0;
     const size_t want_stream = rup((size_t)max_block_bytes + 32, 16);
     const size_t LDS_LIMIT = 150 * 1024;
+    const u32 setup_old = c->dbg.setup_old ? 1u : 0u;  // the scan form of dec_build_rank_tables
     // normal path: rank/select tables (frames up to 2^16), staged stream while >= 3 WGs/CU still fit
     const size_t rs_tables = rup((size_t)(maxM >= 32 ? maxM / 32 : 1) * 8, 16) + 2 * rup((size_t)max_ep * 4, 16) + ANSX_DEC_SCRATCH;
     if (maxM <= 65536u && rs_tables <= LDS_LIMIT && !c->dbg.decode_table) {
@@ -1633,7 +1659,7 @@ int launch_decode(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u8* cont, const
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
                 LAUNCH(c, "k_decode", (k_decode_rank2<RF>), (g.nblocks + 1) / 2, threads, lds2, s, cont, g, NSP, boff,
                     ck_state, ck_off, payload_off, d_out, maxM, max_ep, (u64)cont_bytes, (const u32*)c->dec_cum.p,
-                    (const uint4*)c->dec_info.p, gflags);
+                    (const uint4*)c->dec_info.p, gflags, setup_old);
                 return ANSX_OK;
             }
             // Streams of a few bytes per step (the container's bytes per int, header fields only): the 256-byte speculative
@@ -1647,7 +1673,7 @@ int launch_decode(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u8* cont, const
                     HIPCHK(c, hipFuncSetAttribute((const void*)k_decode_rank<RF, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldss));
                 LAUNCH(c, "k_decode", (k_decode_rank<RF, 2>), g.nblocks, threads, ldss, s, cont, g, NSP, boff,
                     ck_state, ck_off, payload_off, d_out, maxM, max_ep, (u64)cont_bytes, (const u32*)c->dec_cum.p,
-                    (const uint4*)c->dec_info.p, gflags);
+                    (const uint4*)c->dec_info.p, gflags, setup_old);
                 return ANSX_OK;
             }
             const size_t lds = rs_tables + ring_lds;
@@ -1656,7 +1682,7 @@ int launch_decode(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u8* cont, const
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             LAUNCH(c, "k_decode", (k_decode_rank<RF, 1>), g.nblocks, threads, lds, s, cont, g, NSP, boff,
                 ck_state, ck_off, payload_off, d_out, maxM, max_ep, (u64)cont_bytes, (const u32*)c->dec_cum.p,
-                (const uint4*)c->dec_info.p, gflags);
+                (const uint4*)c->dec_info.p, gflags, setup_old);
             return ANSX_OK;
         }
         size_t lds = rs_tables;
@@ -1670,7 +1696,7 @@ int launch_decode(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u8* cont, const
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         LAUNCH(c, "k_decode", (k_decode_rank<RF, 0>), g.nblocks, threads, lds, s, cont, g, NSP, boff, ck_state,
             ck_off, payload_off, d_out, maxM, max_ep, (u64)stream_cap, (const u32*)c->dec_cum.p,
-            (const uint4*)c->dec_info.p, gflags);
+            (const uint4*)c->dec_info.p, gflags, setup_old);
         return ANSX_OK;
     }
     // frames above 2^16 (or forced): slot -> symbol table form, in LDS if it fits, else in HBM
@@ -2965,7 +2991,7 @@ int ansx_init(int device, ansx_ctx** out)
     }
     static const char* const names[] = { "ANSX_TEST_TABLE16_FIXUP", "ANSX_ENCODE_GTAB16", "ANSX_PARSE_GENERIC", "ANSX_PARSE_WIN", "ANSX_PARSE_FAST",
         "ANSX_DECODE_TABLE", "ANSX_NO_STREAM_LDS", "ANSX_DECODE_MODE", "ANSX_PARSE_STAGE_WORDS", "ANSX_MODEL_FUSED", "ANSX_MODEL_SYNC", "ANSX_NS_HINT", "ANSX_T_HINT", "ANSX_NO_FAST_MODEL", "ANSX_FAST_GUARD", "ANSX_CAND_CHAINS", "ANSX_NEAR_BAND", "ANSX_TEST_NEAR_FLIP", "ANSX_WIDE_RESTART", "ANSX_TEST_WIDE_AT",
-        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE" };
+        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP" };
     for (const char* nm : names)
         if (const char* v = getenv(nm)) (void)ansx_debug_set(c, nm, v);
     *out = c;
@@ -3052,6 +3078,11 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         c->dbg.decode_small_ring = !value ? 0 : !strcmp(value, "never") ? 1 : !strcmp(value, "always") ? 2 : 0;
     else if (!strcmp(name, "ANSX_DECODE_PAIR"))
         c->dbg.decode_pair = !value ? 0 : !strcmp(value, "never") ? 1 : !strcmp(value, "always") ? 2 : 0;
+    else if (!strcmp(name, "ANSX_DECODE_SETUP")) {
+        if (!value || !value[0] || !strcmp(value, "0")) c->dbg.setup_old = false;
+        else if (!strcmp(value, "old")) c->dbg.setup_old = true;
+        else return ANSX_ERR_ARG;
+    }
     else if (!strcmp(name, "ANSX_DECODE_PAIR_LDS")) c->dbg.pair_lds_limit = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_FORGET_HINTS")) {  // the next call of every geometry is a first call again (bench.py: first_call_ms)
         c->ns_hint.clear();

@@ -3174,6 +3174,102 @@ __device__ __forceinline__ u32 parse_subtree_win(u32 (*stage)[64], u32 (*stkA)[6
     return err;
 }
 
+// ---- K7, value-array form of one subtree (the parallel kernel's default where the array fits its LDS slice).
+// The item loop of k_parse_prelude_fast on a lane's own subtree: the decoded values of items [a0, a0 + n0) live in an
+// LDS array E, [element][lane], indexed relative to the subtree -- E[i] is item a0 + i - 1, E[0] = low0 - 1 and
+// E[n0 + 1] = high0 + 1 are the bounds handed down by the levels above -- so a node's bounds are looked up
+// (low = E[a] + 1, high = E[a + n + 1] - 1) instead of travelling on the stack, which holds just start << 16 | size
+// in one row per level, and the loop body is one basic block without ballots.  The bits come from SW words staged once
+// per lane, from the word of its first bit on; a lane that gets within two words of their end (or a malformed one)
+// only sets `stop` and keeps going with a frozen bit position.  When the loop is done a lane without `stop` writes
+// its values to cum[a0 + 1 .. a0 + n0]: 16-byte stores where the address allows, dwords at the ragged ends (the
+// windowed form stores one dword per item in tree order).  A stopped lane has written nothing.
+// Bounds: every LDS and global index below is data independent.  The walk (a, n, the stack) is a function of n0
+// alone, n0 <= NE by the header check ns <= max_ns (a depth-3 subtree has at most max_ns >> 3 items) and the host
+// launches this form only when NE + 2 elements and STK rows fit the slice; the stage index is clamped to SW - 2; the
+// global stores cover exactly the lane's own item range of the block's row.  Decoded values only ever land IN the
+// arrays, never in an index.  ET: u16 where every value fits (frame + alphabet + 3 <= 65535, the fast kernel's rule),
+// else u32.  Returns the lane's error flag; slow = 1: the lane ran out of staged words and has to be parsed again.
+template <u32 SW, u32 STK, typename ET>
+__device__ __forceinline__ u32 parse_subtree_arr(u32 (*stage)[64], u32 (*stack)[64], ET (*E)[64], u32 lane,
+    const u8* __restrict__ bp, u32 avail_words, u32 u, u32 a0, u32 n0, u32 low0, u32 high0, u32 bit0, u32 err,
+    u32* __restrict__ cum, u32& slow)
+{
+    const u32 cnt = err ? 0u : n0;  // items of this lane
+    const u32 base_w = bit0 >> 5;   // stream word held in stage[0][lane]
+#pragma unroll 8
+    for (u32 j = 0; j < SW / 2; j++) {
+        const u32 w = base_w + 2 * j;
+        u64 v = 0;
+        if (cnt && w + 2 <= avail_words) v = ld_u64_unaligned(bp + 4 * (u64)w);
+        else if (cnt && w < avail_words) v = ld_u32_unaligned(bp + 4 * (u64)w);
+        stage[2 * j][lane] = (u32)v;
+        stage[2 * j + 1][lane] = (u32)(v >> 32);
+    }
+    // bit positions are relative to word base_w; bit0 <= 32 avail_words was checked by the caller for lanes with items
+    const u32 maxbits = cnt ? avail_words * 32 - base_w * 32 : 0u;
+    E[0][lane] = (ET)(low0 - 1);
+    E[cnt + 1][lane] = (ET)(high0 + 1);
+    stack[0][lane] = 0;  // row 0 is read speculatively while the stack is empty
+    u32 a = 0, n = cnt, low = low0, high = high0, bitpos = bit0 & 31u, sp = 0, stop = 0;
+    for (u32 it = 0; it < cnt; it++) {
+        const u32 h = (n + 1) >> 1;
+        const u32 n1 = h - 1, n2 = n - h, pe = a + h;
+        // next node (data independent): left child, else right child, else the pending one
+        const bool caseA = n1 != 0, caseB = !caseA && n2 != 0, caseC = !caseA && !caseB;
+        const u32 pc = stack[sp ? sp - 1 : 0][lane];
+        u32 wi = bitpos >> 5;
+        wi = wi < SW - 2 ? wi : SW - 2;
+        const u32 w0 = stage[wi][lane], w1 = stage[wi + 1][lane];
+        const u32 pa = pc >> 16, pn = pc & 0xFFFFu;
+        const u32 Ea = E[pa][lane], Eb = E[pa + pn + 1][lane];
+        const bool push = caseA && n2 != 0;
+        stack[push ? sp : STK - 1][lane] = (pe << 16) | n2;  // row STK - 1 = dump
+        // this item (read_center_mid, interp.hpp:47-63)
+        const u32 U = high - n2 - low - n1 + 1;
+        const u32 win = __builtin_amdgcn_alignbit(w1, w0, bitpos & 31u);
+        const u32 Um1 = U - 1;
+        const u32 bb = 32 - __clz(Um1 | 1u) - (Um1 == 0 ? 1u : 0u);  // hi(U-1)+1; 0 for U == 1
+        const u32 lb = bb ? bb - 1 : 0;                               // bits of the first read (<= 31)
+        const u32 m = (u32)((1ull << bb) - U);
+        const u32 dh = U - ((1u << lb) & (bb ? ~0u : 0u));
+        u32 val = (win & ((1u << lb) - 1u)) + 1;
+        const bool big = (U != 1) && (val > m);
+        val = big ? (2 * val + ((win >> lb) & 1u)) - m - 1 : val;
+        val += dh;
+        if (val > U) val -= U;
+        if (U == 1) val = 1;
+        const u32 v = low + n1 - 1 + val;
+        const u32 len = (U == 1) ? 0u : lb + (big ? 1u : 0u);
+        // (the windowed form's conditions; v <= high <= u + 1 follows from them, so v fits ET)
+        const bool bad = (U == 0) || (U > u + 1) || (bitpos + len > maxbits);
+        const u32 now = (bitpos + 64 > SW * 32) ? 2u : (bad ? 1u : 0u);
+        stop = stop ? stop : now;
+        bitpos += stop ? 0u : len;
+        E[pe][lane] = (ET)v;
+        // descend
+        const u32 na = caseA ? a : (caseB ? pe : pa);
+        const u32 nn = caseA ? n1 : (caseB ? n2 : pn);
+        const u32 nlow = caseA ? low : (caseB ? v + 1 : Ea + 1);
+        const u32 nhigh = caseA ? v - 1 : (caseB ? high : Eb - 1);
+        sp = sp + (push ? 1u : 0u) - ((caseC && sp) ? 1u : 0u);
+        a = na, n = nn, low = nlow, high = nhigh;
+    }
+    if (cnt && !stop) {  // the lane's slice of the row: inc[i - 1] = value - 1
+        u32* dst = cum + a0 + 1;
+        u32 head = (4u - (u32)(((size_t)dst >> 2) & 3u)) & 3u;  // dwords up to the next 16-byte boundary
+        head = head < cnt ? head : cnt;
+        u32 i = 0;
+        for (; i < head; i++) dst[i] = (u32)E[i + 1][lane] - 1u;
+        for (; i + 4 <= cnt; i += 4)
+            *(ansx_u32x4*)(dst + i) = ansx_u32x4{ (u32)E[i + 1][lane] - 1u, (u32)E[i + 2][lane] - 1u,
+                (u32)E[i + 3][lane] - 1u, (u32)E[i + 4][lane] - 1u };
+        for (; i < cnt; i++) dst[i] = (u32)E[i + 1][lane] - 1u;
+    }
+    slow = stop == 2 ? 1u : 0u;
+    return stop == 1 ? 1u : err;
+}
+
 // one lane per block (ANSX_PARSE_WIN; default for containers without usable parse hints)
 template <bool RFOLD, u32 SW>
 __global__ __launch_bounds__(64) void k_parse_prelude_win(const u8* __restrict__ cont, ansx_geo g, u32 NSP,
@@ -3208,17 +3304,23 @@ __global__ __launch_bounds__(64) void k_parse_prelude_win(const u8* __restrict__
 // the right subtrees of the code's top seven nodes begin (written by the prelude writer, which has every
 // item's offset anyway).  Eight lanes per block: the top three levels are decoded
 // level by level (a node needs its parent's value for its bounds; left children follow their parent in
-// the stream, right children sit at the hinted offsets), then every lane runs parse_subtree_win on one of
-// the eight depth-3 subtrees -- an eighth of the serial chain.  Hints are untrusted input like the
+// the stream, right children sit at the hinted offsets), then every lane parses one of the eight depth-3
+// subtrees -- an eighth of the serial chain -- with parse_subtree_arr where its value array fits the wave's
+// LDS slice (FORM 1 / 2) and with parse_subtree_win otherwise (FORM 0).  Hints are untrusted input like the
 // payload: offsets are bounds-checked, and a wrong one yields a table that fails the decoder's
 // consistency checks or decodes to garbage, never an out-of-range access.
-template <bool RFOLD, u32 SW>
+#define ANSX_PAR_SW 32u            // staged words per lane
+#define ANSX_PAR_STK 11u           // stack rows of the value-array form: depth <= 10 (subtrees of <= 1023 items) + dump
+#define ANSX_PAR_SLICE_WORDS ((ANSX_PAR_SW + 48u) * 64u)  // a wave's LDS slice: stage + the windowed form's 3 x 16 stack rows
+// FORM: 0 = windowed subtrees (any alphabet), 1 / 2 = value-array subtrees with u16 / u32 elements (the host checks
+// that the array fits the slice: ansx_par_form)
+template <bool RFOLD, u32 SW, int FORM>
 __global__ __launch_bounds__(256) void k_parse_prelude_par(const u8* __restrict__ cont, ansx_geo g, u32 NSP,
     const u64* __restrict__ block_off, u64 payload_off, u32 max_ns, u32 maxM, const u32* __restrict__ hints,
     u32* __restrict__ g_cum, uint4* __restrict__ binfo, u32* __restrict__ gflags, const uint4* __restrict__ pa_info)
 {
     // SW staged words per lane (a subtree's share of a prelude is ~35 bytes at 530 symbols, ~130 at 2300); the host
-    // launches SW = 32.  The kernel is VALU-issue bound machine-wide (~125 instructions per item).
+    // launches SW = 32.  The kernel is VALU-issue bound machine-wide (~125 instructions per item in the windowed form).
     // Up to four waves per workgroup, each on its own slice of the dynamic LDS and never synchronised with the
     // others: like the encoder's, single-wave workgroups pile up unevenly on a CU's SIMDs once a CU holds more
     // than two of them (0.036 ms up to 2 per CU, 0.103 at 4, 0.168 at 8); see the launch site for the sweep.
@@ -3294,8 +3396,24 @@ __global__ __launch_bounds__(256) void k_parse_prelude_par(const u8* __restrict_
         }
     }
     // ---- the eight depth-3 subtrees
-    err = parse_subtree_win<SW, 16>(stage, stkA, stkL, stkH, lane, bp, avail_words, u, a, n, low, high, bit,
-        herr ? herr : err, cum);
+    if constexpr (FORM == 0) {
+        err = parse_subtree_win<SW, 16>(stage, stkA, stkL, stkH, lane, bp, avail_words, u, a, n, low, high, bit,
+            herr ? herr : err, cum);
+    } else {
+        // the array and its stack share the windowed form's stack rows: that form runs afterwards, and only for
+        // the lanes (if any) whose code outgrew the staged words -- from the subtree's start, the other lanes idle
+        typedef typename std::conditional<FORM == 1, u16, u32>::type ET;
+        u32 slow = 0;
+        const u32 e0 = herr ? herr : err;
+        err = parse_subtree_arr<SW, ANSX_PAR_STK, ET>(stage, stkA, (ET (*)[64])(stkA + ANSX_PAR_STK), lane, bp,
+            avail_words, u, a, n, low, high, bit, e0, cum, slow);
+        if (__builtin_amdgcn_ballot_w64(slow != 0) != 0) {
+            wave_lds_sync();
+            const u32 e1 = parse_subtree_win<SW, 16>(stage, stkA, stkL, stkH, lane, bp, avail_words, u, a,
+                slow ? n : 0u, low, high, bit, e0, cum);
+            if (slow) err = e1;
+        }
+    }
     // block verdict: any lane of the group
     u32 e = err;
     e |= (u32)__shfl_xor((int)e, 1);
@@ -3928,7 +4046,7 @@ __device__ __forceinline__ void dec_stage_stream(u32* lds_stream, const u8* __re
 // addressed by the same register with an immediate offset (k_decode_rank2).  The caller has zeroed the .x words and
 // sh_bad and synchronised.  Returns false (after a workgroup barrier) if the row is not a valid table.
 template <bool RFOLD, u32 WSTRIDE, u32 WOFF>
-__device__ __forceinline__ bool dec_build_rank_tables(const ansx_geo& g, u32* bw, uint2* ep, u64* sh_scan, u32* sh_bad,
+__device__ __forceinline__ bool dec_build_rank_tables_scan(const ansx_geo& g, u32* bw, uint2* ep, u64* sh_scan, u32* sh_bad,
     const u32* __restrict__ gc, u32 (&cur4)[4], u32 (&prv4)[4], u32 ns, u32 M, u32 W, u32 max_ns, u32 rflag,
     const u8* __restrict__ stream, u32 tid, u32 nt, u32* __restrict__ gflags)
 {
@@ -4018,6 +4136,126 @@ __device__ __forceinline__ bool dec_build_rank_tables(const ansx_geo& g, u32* bw
     return true;
 }
 
+// The same tables without the prefix scans (the default up to 12 nt symbols; the scan form above stays for larger
+// alphabets and behind ANSX_DECODE_SETUP=old for the cross-check).  The parsed row is already cumulative -- inc[s] =
+// (sum of the frequencies up to s) + s -- so a symbol's base needs no sum: base(s) = gc[s] - (s - 1) for s >= 1,
+// base(0) = 0, and its rank among the present symbols is the number of start bits up to its own, which is what the
+// decoder's lookup computes from the bitmap.  Three passes:
+//  1. per symbol: frequency and base from the row (the same checks as the scan form), start bit into the bitmap;
+//  2. running popcounts: the biased prefix word of every bitmap entry (as in the scan form);
+//  3. per present symbol: r = prefix + popcount(word up to the bit) - bias -- the expression dec_lut_rank::get
+//     evaluates, so the entry lands where the decoder looks for it by construction -- and ep[r] = {base << 16 | fr, pv}.
+// A thread keeps the packed (base, fr) of its up to twelve symbols in registers between passes 1 and 3.  Reading the
+// row a second time instead (any alphabet) was measured: one more chain of L2 round trips per block, 0.045 ms slower
+// than the scans on 2300-symbol tables and 0.27 ms on 8400-symbol ones (256 Mi ints, one wave per block) -- hence the
+// bound, and the scan form beyond it.
+// Rejected rows are exactly those the scan form rejects.  If any symbol fails its own check (c < p, fr > M,
+// fr > 0xFFFF) both forms reject; if none does, the identity is exact (the sum telescopes, nothing wraps), so the
+// per-symbol base checks see the same numbers, `base + fr` of the last symbol is the scan's total (!= M rejects), and
+// the number of start bits is the number of present symbols: more than max_ns of them means some r >= max_ns, which
+// pass 3 rejects before it stores.  Two present symbols cannot collide on a start bit: bases are strictly increasing
+// where fr > 0.  Every LDS index is checked against M (bitmap) or max_ns (entries) before use, whatever the row holds.
+template <bool RFOLD, u32 WSTRIDE, u32 WOFF>
+__device__ __forceinline__ bool dec_build_rank_tables(const ansx_geo& g, u32* bw, uint2* ep, u64* sh_scan, u32* sh_bad,
+    const u32* __restrict__ gc, u32 (&cur4)[4], u32 (&prv4)[4], u32 ns, u32 M, u32 W, u32 max_ns, u32 rflag,
+    const u8* __restrict__ stream, u32 tid, u32 nt, u32* __restrict__ gflags, bool scan_form)
+{
+    if (scan_form || ns > 12 * nt)  // (uniform)
+        return dec_build_rank_tables_scan<RFOLD, WSTRIDE, WOFF>(g, bw, ep, sh_scan, sh_bad, gc, cur4, prv4, ns, M, W, max_ns, rflag, stream, tid, nt, gflags);
+    const ansx_map f = g.map;
+    const u32 T = fold_T(g.f);
+    u32 bad = ns == 0 ? 1u : 0u;
+    // symbol s from c = gc[s + 1], pg = gc[s]: base << 16 | fr (base < M <= 2^16, 0 < fr <= 0xFFFF), 0 if absent or invalid
+    auto entry = [&](u32 c, u32 pg, u32 s) -> u32 {
+        const u32 p = s ? pg + 1u : 0u;
+        const u32 fr = c - p;
+        if (c < p || fr > M || fr > 0xFFFFu) {  // entries hold 16-bit freq and base
+            bad = 1;
+            return 0u;
+        }
+        const u32 base = s ? pg - (s - 1u) : 0u;  // (a row that is not cumulative wraps to a value the checks below refuse)
+        if (s == ns - 1 && (u64)base + fr != M) bad = 1;  // the sum of the frequencies
+        if (!fr) return 0u;
+        if (!(base < M && base + fr <= M)) {
+            bad = 1;
+            return 0u;
+        }
+        return (base << 16) | fr;
+    };
+    u32 keep[12];  // symbol q * nt + tid
+#pragma unroll
+    for (u32 q = 0; q < 12; q++) keep[q] = 0u;
+#pragma unroll
+    for (u32 ch = 0; ch < 3; ch++) {
+        const u32 c0 = ch * 4 * nt;
+        if (c0 >= ns) break;  // uniform
+        // this chunk's values were requested one chunk ago (the first: at kernel start); request the next
+        u32 nx4[4] = {}, np4[4] = {};
+        if (ch < 2 && c0 + 4 * nt < ns) {
+#pragma unroll
+            for (u32 q = 0; q < 4; q++) {
+                const u32 s = c0 + 4 * nt + q * nt + tid;
+                nx4[q] = s < ns ? gc[s + 1] : 0u;
+                np4[q] = s < ns ? gc[s] : 0u;
+            }
+        }
+#pragma unroll
+        for (u32 q = 0; q < 4; q++) {
+            const u32 s = c0 + q * nt + tid;
+            if (s < ns) {
+                const u32 pk = entry(cur4[q], prv4[q], s);
+                if (pk) atomicOr(&bw[(pk >> 21) * WSTRIDE + WOFF], 1u << ((pk >> 16) & 31u));
+                keep[4 * ch + q] = pk;
+            }
+        }
+#pragma unroll
+        for (u32 q = 0; q < 4; q++) {
+            cur4[q] = nx4[q];
+            prv4[q] = np4[q];
+        }
+    }
+    __syncthreads();
+    if (tid < 64) {  // running popcount before every bitmap word
+        const u32 per = (W + 63) / 64;
+        const u32 lo = tid * per;
+        u32 loc = 0;
+        for (u32 i = 0; i < per; i++)
+            if (lo + i < W) loc += (u32)__builtin_popcount(bw[(lo + i) * WSTRIDE + WOFF]);
+        const u32 incl = wave_incl_scan(loc);
+        // (the second word of a bitmap entry: set bits before it - 1 + (LDS byte address of ep) / 8, see dec_lut_rank)
+        u32 run = incl - loc + ((u32)(size_t)(__attribute__((address_space(3))) const void*)ep / 8u - 1u);
+        for (u32 i = 0; i < per; i++)
+            if (lo + i < W) {
+                bw[(lo + i) * WSTRIDE + WOFF + 1] = run;
+                run += (u32)__builtin_popcount(bw[(lo + i) * WSTRIDE + WOFF]);
+            }
+    }
+    __syncthreads();
+    const u32 ep8 = (u32)(size_t)(__attribute__((address_space(3))) const void*)ep / 8u;
+#pragma unroll
+    for (u32 q = 0; q < 12; q++) {
+        const u32 pk = keep[q], s = q * nt + tid;
+        if (!pk) continue;
+        const u32 base = pk >> 16;
+        const u32 wd = bw[(base >> 5) * WSTRIDE + WOFF], pf = bw[(base >> 5) * WSTRIDE + WOFF + 1];
+        const u32 r = (u32)__builtin_popcount(wd << (~base & 31u)) + pf - ep8;  // dec_lut_rank::get's r8, unbiased
+        if (r < max_ns) {  // (max_ns here: the header's bound on symbols PRESENT in a block, i.e. the entries ep[] holds; untrusted like the rest)
+            // ANSrfold: the most-frequent values follow the 4-byte flag word (ans_reorder_fold.hpp:132-154)
+            u32 mfv = 0;
+            if (RFOLD && rflag && s < T) mfv = ld_u32_unaligned(stream + 4 + 4 * (u64)s);
+            ep[r] = make_uint2(pk, dec_make_pv(f, s, RFOLD && rflag, T, mfv));
+        } else {
+            bad = 1;
+        }
+    }
+    if (bad) {
+        *sh_bad = 1;
+        atomicOr(&gflags[ANSX_G_ERR], 1u << 3);
+    }
+    __syncthreads();
+    return *sh_bad == 0;
+}
+
 // ---- K8: one workgroup per block.  Builds the decoder tables, then one quad of lanes per segment
 // decodes forward from its restart point, reading the stream through per-quad LDS rings (RING),
 // a staged copy of the whole block stream, or straight from HBM (partial block / no room).
@@ -4033,7 +4271,7 @@ __global__ void k_decode_rank(const u8* __restrict__ cont, ansx_geo g, u32 NSP,
     const u64* __restrict__ block_off, const u64* __restrict__ ckpt_state,
     const u32* __restrict__ ckpt_off, u64 payload_off, u32* __restrict__ outp, u32 maxM,
     u32 max_ns, u64 stream_cap, const u32* __restrict__ g_cum, const uint4* __restrict__ binfo,
-    u32* __restrict__ gflags)
+    u32* __restrict__ gflags, u32 setup_old)
 {
     // (no static LDS in this kernel: the bitmap table sits at LDS address 0, so its reads need no base added)
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
@@ -4097,7 +4335,7 @@ __global__ void k_decode_rank(const u8* __restrict__ cont, ansx_geo g, u32 NSP,
     const bool st_lds = !RING && (sbytes + 24 <= stream_cap);
     if (st_lds) dec_stage_stream(lds_stream, stream, sbytes, tid, nt);
     __syncthreads();
-    if (!dec_build_rank_tables<RFOLD, 2, 0>(g, (u32*)bwp, ep, sh_scan, &sh_bad, gc, cur4, prv4, ns, M, W, max_ns, rflag, stream, tid, nt, gflags)) {
+    if (!dec_build_rank_tables<RFOLD, 2, 0>(g, (u32*)bwp, ep, sh_scan, &sh_bad, gc, cur4, prv4, ns, M, W, max_ns, rflag, stream, tid, nt, gflags, setup_old != 0)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the prefetched window is still on its way)
         return;
     }
@@ -4285,7 +4523,7 @@ __global__ __launch_bounds__(256) void k_decode_rank2(const u8* __restrict__ con
     const u64* __restrict__ block_off, const u64* __restrict__ ckpt_state,
     const u32* __restrict__ ckpt_off, u64 payload_off, u32* __restrict__ outp, u32 maxM,
     u32 max_ns, u64 cont_bytes, const u32* __restrict__ g_cum, const uint4* __restrict__ binfo,
-    u32* __restrict__ gflags)
+    u32* __restrict__ gflags, u32 setup_old)
 {
     // (no static LDS in this kernel: the interleaved bitmap table sits at LDS address 0)
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
@@ -4326,7 +4564,8 @@ __global__ __launch_bounds__(256) void k_decode_rank2(const u8* __restrict__ con
     uint2* epB = (uint2*)(smem + off);
     off += epb;
     u64* sh_scan = (u64*)(smem + off);
-    u32& sh_bad = *(u32*)(smem + off + 80);
+    u32& sh_bad = *(u32*)(smem + off + 80);   // block A's error flag
+    u32& sh_badB = *(u32*)(smem + off + 84);  // block B's: its own word, so that no wave still reading A's verdict sees it reset
     off += ANSX_DEC_SCRATCH;
     u32* lds_rest = (u32*)(smem + off);
     const u32 labs = (u32)(size_t)(__attribute__((address_space(3))) void*)lds_rest;
@@ -4362,16 +4601,14 @@ __global__ __launch_bounds__(256) void k_decode_rank2(const u8* __restrict__ con
     }
     if (tid == 0) {
         sh_bad = 0;
+        sh_badB = 0;
         if ((u32)(size_t)(__attribute__((address_space(3))) void*)bw != 0u) atomicOr(&gflags[ANSX_G_ERR], 1u << 3);
     }
     __syncthreads();
     if (okA)
-        okA = dec_build_rank_tables<RFOLD, 4, 0>(g, bw, epA, sh_scan, &sh_bad, gcA, curA, prvA, biA.x, MA, WA, max_ns, biA.z, streamA, tid, nt, gflags);
-    if (okB) {
-        if (tid == 0) sh_bad = 0;
-        __syncthreads();
-        okB = dec_build_rank_tables<RFOLD, 4, 2>(g, bw, epB, sh_scan, &sh_bad, gcB, curB, prvB, biB.x, MB, WB, max_ns, biB.z, streamB, tid, nt, gflags);
-    }
+        okA = dec_build_rank_tables<RFOLD, 4, 0>(g, bw, epA, sh_scan, &sh_bad, gcA, curA, prvA, biA.x, MA, WA, max_ns, biA.z, streamA, tid, nt, gflags, setup_old != 0);
+    if (okB)
+        okB = dec_build_rank_tables<RFOLD, 4, 2>(g, bw, epB, sh_scan, &sh_badB, gcB, curB, prvB, biB.x, MB, WB, max_ns, biB.z, streamB, tid, nt, gflags, setup_old != 0);
     u32* oA = outp + geo_block_out(g, bA);
     u32* oB = outp + geo_block_out(g, bBs);
     dec_lut_rank2<0> lutA;

@@ -417,7 +417,11 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
  * joined on the caller's stream in front of the encoder; "always" / a number pipeline any list that takes the fast model
  * path, however short, except in per-kernel profile mode and on a stream that is being captured), ANSX_WIDE_RESTART
  * (wide restart points in every container -- the one switch here that changes the output: the index, not the block
- * streams), ANSX_TEST_WIDE_AT (number <= 16: frames above 2^this count as too large for packed restart points);
+ * streams), ANSX_TEST_WIDE_AT (number <= 16: frames above 2^this count as too large for packed restart points),
+ * ANSX_DECODE_SETUP ("old"; ""/"0"/NULL: the default; anything else: ANSX_ERR_ARG -- the per-block setup of a decode
+ * call as it was before the value-array subtree parser and the scan-free table build: windowed subtrees in
+ * k_parse_prelude_par whatever the alphabet, one prefix scan per round of symbols in the decoder's table build; for the
+ * cross-check test and the paired timing of tests/tools/bench_decode_setup.py);
  * through this call only (round 4): ANSX_NO_PC / ANSX_FORCE_PC / ANSX_NO_PC_AUTO / ANSX_PC_B_PAIRS (the producer /
  * consumer encoder never / whatever the list length / only on request; pairs per workgroup of its two-round shape),
  * ANSX_ENCODE_MODE2, ANSX_DECODE_PAIR, ANSX_DECODE_SMALL_RING (1 never | 2 always), ANSX_FORGET_HINTS, ANSX_NO_BIG_GEO,
