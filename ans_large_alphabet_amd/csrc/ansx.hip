@@ -64,6 +64,55 @@ struct Layout {  // container layout, a pure function of the geometry (restart-p
 #define ANSX_PIPE_MIN_BLOCKS 8192u
 #define ANSX_PIPE_MIN_INTS ((u64)1 << 27)
 
+// Header of the last container decoded per shape (kind, fidelity, n, bytes): the next decode of that shape is launched
+// on it without waiting for the header to come back, and a one-thread kernel compares it with the real one
+// (k_check_header).  64 shapes; the OLDEST remembered one (insertion order) makes room, never the one being stored.
+struct HeaderCache {
+    typedef std::array<u64, 4> Key;
+    const ansx_container_header* find(const Key& k) const { return map.count(k) ? &map.find(k)->second : nullptr; }
+    void forget(const Key& k) { map.erase(k); }  // (its place in `order` lingers: remember() drops it)
+    void remember(const Key& k, const ansx_container_header& H)
+    {
+        if (!map.count(k)) {
+            order.erase(std::remove(order.begin(), order.end(), k), order.end());
+            order.push_back(k);
+            for (; order.size() > 64; order.pop_front()) map.erase(order.front());
+        }
+        map[k] = H;
+    }
+    void clear() { map.clear(), order.clear(); }
+
+private:
+    std::map<Key, ansx_container_header> map;
+    std::deque<Key> order;  // keys of map, oldest first
+};
+
+// The pinned page every read-back of a few words lands in (ansx_ctx::pin).  The flag words serve every call; behind them
+// each entry point has its own fields, at offsets that keep the fields of one call apart.
+struct PinPage {
+    u32 flags[16];  // bytes 0..63: the device's flag words (ANSX_G_*) with the result, a 64-bit payload size, in words 4, 5
+    union {
+        struct {  // a decode call
+            union {
+                ansx_container_header hdr;  // 64: the container's header (fetched or remembered; range_source: the source's)
+                struct {     // 64: a single reference stream: its first bytes, those behind a most-frequent table,
+                    u8 peek[16], peek_rf[16];  // and the two index entries of its one block (an upload)
+                    u64 index[2];
+                } plain;
+            };
+            u8 pad0[2048 - 64 - 64];
+            u32 caller_flag;  // 2048: the flag word of decode_dev's caller (decode_sub), read back by its epilogue
+            u8 pad1[1024 - 4];
+            u64 planner[8];  // 3072: the scalars of the device planner (decode_device_ranges)
+        };
+        u8 part_hdr[63][64];                       // 64: ansx_merge_containers_dev, the headers of up to 63 parts
+        u64 rank_sizes[2 * ANSX_MERGE_MAX_PARTS];  // 64: ansx_gather_containers, (bytes, slot_bytes) of every rank
+    };
+};
+static_assert(sizeof(PinPage) == 4096 && offsetof(PinPage, plain.index) == 96 && offsetof(PinPage, caller_flag) == 2048
+        && offsetof(PinPage, planner) == 3072,
+    "the pinned page is one 4096-byte allocation (ansx_init) and its fields keep their places");
+
 struct ansx_ctx {
     u32 num_cus = 256;
     int device = 0;
@@ -82,15 +131,12 @@ struct ansx_ctx {
     DevBuf enb_plan, enb_wc;              // ansx_encode_batch_dev: a pass's plan and results; its restart points and hints (work area)
     u8* rng_pin = nullptr;                // ... and the pinned host image of rng_plan (an asynchronous upload from
     size_t rng_pin_cap = 0;               //     pageable memory is staged by the runtime: 0.666 -> 0.618 ms at 4096 ranges)
-    u32* h_pin = nullptr;  // pinned: [0..3] gflags, [4..7] result (2 x u64), [8..] header scratch
+    PinPage* pin = nullptr;
     // Largest alphabet (max_sym + 1) seen per (kind, fidelity, block_ints): sizes the LDS of the fused
     // model kernel and of the LDS-table encoder without a mid-call round trip (see encode_dev).
     std::map<u64, u32> ns_hint;
     std::map<u64, u32> rf_hint;  // rfold: most distinct values per block seen per geometry (optimistic hash-table size)
-    // header of the last container decoded per (kind, fidelity, n, bytes): the next decode of that shape is launched
-    // on it without waiting for the header to come back, and a one-thread kernel compares it with the real one
-    std::map<std::array<u64, 4>, ansx_container_header> hdr_cache;
-    std::deque<std::array<u64, 4>> hdr_order;  // keys of hdr_cache, oldest first (an erased key may linger: erase is idempotent)
+    HeaderCache hdrs;
     std::map<u32, DevBuf> geo;   // tree nodes of the interpolative code per alphabet size, tabulated per symbol-array size (<= 4096)
     DevBuf geo_big;              // the same for alphabets up to geo_big_cap symbols (symbol arrays above 4096 slots, fast model path:
     u32 geo_big_cap = 0;         //   sized from the geometry's alphabet hint, cap^2 * 4 bytes -- 284 MB for fidelity 5 on 2^20-valued lists)
@@ -112,7 +158,7 @@ struct ansx_ctx {
     // Path-selection overrides for tests and experiments (every path must give identical bytes).
     // Taken from the environment ONCE in ansx_init, changed afterwards only through ansx_debug_set;
     // the per-call hot path never looks at the environment.
-    struct {
+    struct Dbg {
         bool table16_fixup = false;   // ANSX_TEST_TABLE16_FIXUP: integer-state encoder fed by k_table16_from32
         bool encode_gtab16 = false;   // ANSX_ENCODE_GTAB16: force the 16-byte-entry integer-state encoder
         bool parse_generic = false;   // ANSX_PARSE_GENERIC: generic prelude parser kernel
@@ -152,6 +198,7 @@ struct ansx_ctx {
         u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev, ansx_decode_batch_ranges_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
     } dbg;
 };
+typedef ansx_ctx::Dbg DebugOpts;
 
 namespace {
 
@@ -627,9 +674,9 @@ struct EncBatchPass {
 // the flag words (and the result behind them), read back into the attempt's outcome: a host wait
 int read_flags(ansx_ctx* c, const EncodeWs& W, u32 words)
 {
-    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->misc.p, (size_t)words * 4, hipMemcpyDeviceToHost, W.s));
+    HIPCHK(c, hipMemcpyAsync(c->pin->flags, c->misc.p, (size_t)words * 4, hipMemcpyDeviceToHost, W.s));
     HIPCHK(c, hipStreamSynchronize(W.s));
-    memcpy(W.out->flags, c->h_pin, (size_t)words * 4);
+    memcpy(W.out->flags, c->pin->flags, (size_t)words * 4);
     return ANSX_OK;
 }
 
@@ -1553,186 +1600,219 @@ static int ansx_par_form(u32 max_ns, u32 maxM)
     return 0;
 }
 
-template <bool RF>
-int launch_decode(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u8* cont, const u64* boff,
-    const u64* ck_state, const u32* ck_off, u64 payload_off, u32* d_out, u32 maxM, u32 max_ns,
-    u32 max_block_bytes, u64 cont_bytes, u32* gflags, hipStream_t s, const uint4* pa_info, const u32* hints, u32 max_ep,
-    bool parsed = false)
+// What the form of a decode depends on besides the geometry and the debug overrides: bounds from the container's header
+// (for a single reference stream: from the peek at its first bytes).
+struct DecodeBounds {
+    u32 maxM, max_ns;     // the largest frame; the bound on a block's symbol indices
+    u32 max_ep;           // the bound on the symbols PRESENT in a block (<= max_ns): the rank / select decoder keeps one
+                          // 8-byte entry per present symbol, so this -- not max_ns -- sizes its LDS
+    bool hinted;          // the container carries parse hints (a single stream has none)
+    u64 payload_bytes;    // bytes of all block streams (per int of the list: how lean the streams are)
+    u32 max_block_bytes;  // the largest block stream -- only the index knows it (k_validate_index) -- or 0: not looked up
+};
+
+enum { PARSE_DONE, PARSE_GENERIC, PARSE_PAR, PARSE_FAST, PARSE_WIN };  // PARSE_DONE: k_int_sparse_parse has filled the tables
+// the k_decode_rank family (in the order of its RING parameter, then the pair kernel) and the two table forms of k_decode
+enum { DEC_STAGED, DEC_RING, DEC_SMALL_RING, DEC_PAIR, DEC_TABLE, DEC_GTAB };  // DEC_GTAB: needs the HBM slot table (dec_s2s)
+struct LaunchShape {
+    u32 grid, threads;
+    size_t lds;
+};
+struct DecodeForm {
+    bool needs_index;  // the decoder hangs on the largest block stream and the bounds do not have it: only the parser is
+                       // filled in, ask again with max_block_bytes measured
+    int parser;        // K7 ...
+    u32 p_variant;     // ... PARSE_PAR: the subtree form (ansx_par_form), PARSE_WIN: staged words per lane, PARSE_FAST: stage_words
+    int decoder;       // K8
+    LaunchShape p, d;
+    u32 stream_cap;  // DEC_STAGED and the table forms: bytes of LDS a block's stream is staged in, 0 = read from HBM
+};
+
+// The one place that decides which parser and which decoder a decode call runs, and in what launch shape.  Pure: no HIP
+// call, nothing of the context but its overrides and the chip's CU count.
+DecodeForm choose_decode_form(const ansx_geo& g, const DecodeBounds& B, const DebugOpts& dbg, u32 num_cus)
 {
-    // max_ep: the header's bound on the symbols PRESENT in a block (<= max_ns, its bound on their indices): the
-    // rank / select decoder keeps one 8-byte entry per present symbol, so this -- not max_ns -- sizes its LDS
-    const u32 T = fold_T(g.f);
-    int rc;
-    if ((rc = ensure(c, c->dec_cum, (size_t)g.nblocks * (NSP + 8) * 4))) return rc;
-    if ((rc = ensure(c, c->dec_info, (size_t)g.nblocks * 16))) return rc;
+    DecodeForm F = {};
+    const u32 maxM = B.maxM, max_ns = B.max_ns;
     // K7.  Containers carry parse hints (bit offsets of the top subtrees of every block's interpolative code):
     // eight lanes per block, k_parse_prelude_par.  Without hints (single-stream mode) or on request one lane
     // per block: the windowed parser (any alphabet / frame size; ANSX_PARSE_WIN), the older E-array fast loop
     // (ANSX_PARSE_FAST: 16-bit values, up to ~880 symbols) or the generic kernel (ANSX_PARSE_GENERIC) --
     // all four are cross-checked in the tests.
-    const size_t pf_e = std::max<size_t>(20480, rup(((size_t)max_ns + 2) * 128, 16));
-    const size_t pf_lds = pf_e + (size_t)ANSX_PF_SW * 64 * 4 + 21 * 64 * 4;
-    u32 stage_words = ANSX_PF_SW;
-    if (c->dbg.parse_stage_words >= 2 && c->dbg.parse_stage_words <= ANSX_PF_SW)  // tests: force the fast loop's in-kernel fallback
-        stage_words = c->dbg.parse_stage_words & ~1u;
-    if (parsed) {
-        // (plain ANSint: k_int_sparse_parse has filled dec_cum / dec_info in rank space)
-    } else if (c->dbg.parse_generic) {
-        LAUNCH(c, "k_parse_prelude", (k_parse_prelude<RF>), (g.nblocks + 63) / 64, 64, 0, s, cont, g, NSP,
-            boff, payload_off, max_ns, maxM, (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, gflags, pa_info);
-    } else if (hints != nullptr && !c->dbg.parse_win && !c->dbg.parse_fast) {
+    const size_t pf_lds = std::max<size_t>(20480, rup(((size_t)max_ns + 2) * 128, 16)) + (size_t)ANSX_PF_SW * 64 * 4 + 21 * 64 * 4;
+    F.p = { (g.nblocks + 63) / 64, 64, 0 };
+    if (g.kind == ANSX_INT && !g.pa) {
+        F.parser = PARSE_DONE;
+    } else if (dbg.parse_generic) {
+        F.parser = PARSE_GENERIC;
+    } else if (B.hinted && !dbg.parse_win && !dbg.parse_fast) {
         // Subtree form: value arrays (u16 / u32 elements) where a depth-3 subtree's array fits the slice the windowed
         // form needs anyway, from header fields only; otherwise, or with ANSX_DECODE_SETUP=old, the windowed form.
-        const int form = c->dbg.setup_old ? 0 : ansx_par_form(max_ns, maxM);
+        F.parser = PARSE_PAR;
+        F.p_variant = dbg.setup_old ? 0 : ansx_par_form(max_ns, maxM);
         // Waves per workgroup (each wave works alone on its own LDS slice): measured on MI355X at 16384 blocks,
         // windowed form: 530-symbol tables 1/2/3/4 waves -> 0.161/0.162/0.109/0.122 ms, 2300-symbol tables
         // 0.275/0.273/0.286/0.252; value-array form (event-timed, so ~0.005 above the kernel's own time): 526-symbol
         // tables 0.062/0.062/0.068/0.056, 257-symbol tables 0.045/0.042/0.048/0.039.
         const u32 par_waves = (g.nblocks + 7) / 8;
-        const u32 pw_max = (form != 0 || max_ns > 1024) ? 4u : 3u;
-        const u32 pw = std::min<u32>(pw_max, std::max<u32>(1u, (par_waves + c->num_cus - 1) / c->num_cus));
-        const u32 par_grid = (par_waves + pw - 1) / pw;
-        const size_t lds = (size_t)pw * ANSX_PAR_SLICE_WORDS * 4;
-#define ANSX_LAUNCH_PAR(FORM, label)                                                                                        \
-    do {                                                                                                                    \
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_parse_prelude_par<RF, ANSX_PAR_SW, FORM>,                              \
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                               \
-        LAUNCH(c, label, (k_parse_prelude_par<RF, ANSX_PAR_SW, FORM>), par_grid, 64 * pw, lds, s, cont, g, NSP, boff,       \
-            payload_off, max_ns, maxM, hints, (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, gflags, pa_info);                  \
-    } while (0)
-        if (form == 1) ANSX_LAUNCH_PAR(1, "k_parse_prelude_arr");
-        else if (form == 2) ANSX_LAUNCH_PAR(2, "k_parse_prelude_arr");
-        else ANSX_LAUNCH_PAR(0, "k_parse_prelude");
-#undef ANSX_LAUNCH_PAR
-    } else if (c->dbg.parse_fast && (u64)maxM + max_ns + 3 <= 65535u && pf_lds <= 150 * 1024) {
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_parse_prelude_fast<RF>,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)pf_lds));
-        LAUNCH(c, "k_parse_prelude", (k_parse_prelude_fast<RF>), (g.nblocks + 63) / 64, 64, pf_lds, s, cont, g,
-            NSP, boff, payload_off, max_ns, maxM, (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, gflags, stage_words, pa_info);
-    } else if (max_ns <= 1024) {  // preludes of a few hundred bytes: 128 staged words per lane
-        const size_t lds = (size_t)(128 + 72) * 64 * 4;
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_parse_prelude_win<RF, 128>,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(c, "k_parse_prelude", (k_parse_prelude_win<RF, 128>), (g.nblocks + 63) / 64, 64, lds, s, cont, g,
-            NSP, boff, payload_off, max_ns, maxM, (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, gflags, pa_info);
+        const u32 pw_max = (F.p_variant != 0 || max_ns > 1024) ? 4u : 3u;
+        const u32 pw = std::min<u32>(pw_max, std::max<u32>(1u, (par_waves + num_cus - 1) / num_cus));
+        F.p = { (par_waves + pw - 1) / pw, 64 * pw, (size_t)pw * ANSX_PAR_SLICE_WORDS * 4 };
+    } else if (dbg.parse_fast && (u64)maxM + max_ns + 3 <= 65535u && pf_lds <= 150 * 1024) {
+        F.parser = PARSE_FAST;
+        F.p_variant = ANSX_PF_SW;
+        if (dbg.parse_stage_words >= 2 && dbg.parse_stage_words <= ANSX_PF_SW)  // tests: force the fast loop's in-kernel fallback
+            F.p_variant = dbg.parse_stage_words & ~1u;
+        F.p.lds = pf_lds;
     } else {
-        const size_t lds = (size_t)(256 + 72) * 64 * 4;
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_parse_prelude_win<RF, 256>,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(c, "k_parse_prelude", (k_parse_prelude_win<RF, 256>), (g.nblocks + 63) / 64, 64, lds, s, cont, g,
-            NSP, boff, payload_off, max_ns, maxM, (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, gflags, pa_info);
+        F.parser = PARSE_WIN;
+        F.p_variant = max_ns <= 1024 ? 128 : 256;  // (preludes of a few hundred bytes: 128 staged words per lane)
+        F.p.lds = (size_t)(F.p_variant + 72) * 64 * 4;
     }
     // K8
     const u32 nseg = geo_nseg(g.block_ints, g.ckpt);
-    u32 threads = (u32)rup((size_t)nseg * 4, 64);
-    if (threads > 256) threads = 256;
-    const size_t mfb = RF ? (size_t)T * 4 : 0;
-    const size_t want_stream = rup((size_t)max_block_bytes + 32, 16);
+    F.d.grid = g.nblocks;
+    F.d.threads = std::min<u32>(256u, (u32)rup((size_t)nseg * 4, 64));
     const size_t LDS_LIMIT = 150 * 1024;
-    const u32 setup_old = c->dbg.setup_old ? 1u : 0u;  // the scan form of dec_build_rank_tables
     // normal path: rank/select tables (frames up to 2^16), staged stream while >= 3 WGs/CU still fit
-    const size_t rs_tables = rup((size_t)(maxM >= 32 ? maxM / 32 : 1) * 8, 16) + 2 * rup((size_t)max_ep * 4, 16) + ANSX_DEC_SCRATCH;
-    if (maxM <= 65536u && rs_tables <= LDS_LIMIT && !c->dbg.decode_table) {
-        // per-quad stream rings when every segment of a full block has the same length; the (at
-        // most one) partial block of the container then reads its stream straight from HBM
-        // (measured on MI355X, 256 Mi ints: rings 0.73 vs 0.76 ms at 16 Ki / 1024, 0.73 vs 1.85 ms at
-        // 64 Ki / 1024 where the stream no longer fits; staged 0.60 vs 0.69 ms at 16 Ki / 512 -- the
-        // ring bookkeeping costs ~6 VALU per step, so it only pays when it frees a lot of LDS)
-        const size_t ring_lds = (size_t)(threads / 4) * ANSX_RING_STRIDE + 16;  // + alignment slack
-        const bool staged_fits = rs_tables + want_stream <= 52 * 1024;
-        const bool ring_ok = g.ckpt != 0 && g.block_ints % g.ckpt == 0 && g.ckpt % 4 == 0
-            && rs_tables + ring_lds <= 60 * 1024;
+    const size_t rs_tables = rup((size_t)(maxM >= 32 ? maxM / 32 : 1) * 8, 16) + 2 * rup((size_t)B.max_ep * 4, 16) + ANSX_DEC_SCRATCH;
+    const bool rank_form = maxM <= 65536u && rs_tables <= LDS_LIMIT && !dbg.decode_table;
+    // per-quad stream rings when every segment of a full block has the same length; the (at
+    // most one) partial block of the container then reads its stream straight from HBM
+    // (measured on MI355X, 256 Mi ints: rings 0.73 vs 0.76 ms at 16 Ki / 1024, 0.73 vs 1.85 ms at
+    // 64 Ki / 1024 where the stream no longer fits; staged 0.60 vs 0.69 ms at 16 Ki / 512 -- the
+    // ring bookkeeping costs ~6 VALU per step, so it only pays when it frees a lot of LDS)
+    const size_t ring_lds = (size_t)(F.d.threads / 4) * ANSX_RING_STRIDE + 16;  // + alignment slack
+    const bool ring_ok = g.ckpt != 0 && g.block_ints % g.ckpt == 0 && g.ckpt % 4 == 0 && rs_tables + ring_lds <= 60 * 1024;
+    const int force = dbg.decode_mode;  // tests: 1 "ring" | 2 "staged"
+    // The ring decoder needs nothing from the index, so a container it could decode is never held up for one (no
+    // validation kernel, no read-back): whether rings pay there, and the staging of the staged form if they do not, go
+    // by the codec's worst-case block stream.  Every other form sizes its LDS from the largest block stream.
+    const bool index_free = rank_form && ring_ok && force != 2 && !g.pa;
+    if (!B.max_block_bytes && !index_free) {
+        F.needs_index = true;
+        return F;
+    }
+    const size_t block_bytes = B.max_block_bytes ? B.max_block_bytes
+                                                 : std::min<size_t>(0x7FFFFFFFu, block_bound((int)g.kind, g.f, g.block_ints, false));
+    const size_t want_stream = rup(block_bytes + 32, 16);
+    size_t tables = rs_tables;  // what the form keeps in LDS besides a staged stream
+    if (rank_form) {
         // large tables (alphabets of thousands of symbols: one wave per block, a handful of waves per CU either
         // way): rings, 1.33 vs 2.08 ms on 2300-symbol alphabets -- the staging pass is pure latency there
-        const bool ring_pays = !staged_fits || rs_tables >= 12 * 1024
-            || 10 * (rs_tables + want_stream) > 16 * (rs_tables + ring_lds);
-        const int force = c->dbg.decode_mode;  // tests: 1 "ring" | 2 "staged"
-        const bool use_ring = ring_ok && (force ? force == 1 : ring_pays);
-        if (use_ring) {
+        const bool staged_fits = rs_tables + want_stream <= 52 * 1024;
+        const bool ring_pays = !staged_fits || rs_tables >= 12 * 1024 || 10 * (rs_tables + want_stream) > 16 * (rs_tables + ring_lds);
+        if (ring_ok && (force ? force == 1 : ring_pays)) {
             // two blocks per workgroup, decoded in one instruction stream (k_decode_rank2): as long as four such workgroups
             // still fit a CU's LDS; the container's last one or two blocks take the single-block code inside that kernel
-            const size_t lds2 = rup((size_t)(maxM >= 32 ? maxM / 32 : 1) * 16, 16) + 4 * rup((size_t)max_ep * 4, 16) + ANSX_DEC_SCRATCH + 2 * ring_lds;
-            const int pair = c->dbg.decode_pair;  // tests / experiments: 1 never, 2 always (LDS permitting)
-            if (pair != 1 && g.nblocks >= 2 && (pair == 2 ? lds2 <= 150 * 1024 : lds2 <= c->dbg.pair_lds_limit)) {
-                if (lds2 > 48 * 1024)
-                    HIPCHK(c, hipFuncSetAttribute((const void*)k_decode_rank2<RF>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-                LAUNCH(c, "k_decode", (k_decode_rank2<RF>), (g.nblocks + 1) / 2, threads, lds2, s, cont, g, NSP, boff,
-                    ck_state, ck_off, payload_off, d_out, maxM, max_ep, (u64)cont_bytes, (const u32*)c->dec_cum.p,
-                    (const uint4*)c->dec_info.p, gflags, setup_old);
-                return ANSX_OK;
-            }
+            const size_t lds2 = rup((size_t)(maxM >= 32 ? maxM / 32 : 1) * 16, 16) + 4 * rup((size_t)B.max_ep * 4, 16) + ANSX_DEC_SCRATCH + 2 * ring_lds;
+            const int pair = dbg.decode_pair;  // tests / experiments: 1 never, 2 always (LDS permitting)
             // Streams of a few bytes per step (the container's bytes per int, header fields only): the 256-byte speculative
             // rings -- sixteen instead of ten blocks of the headline workload per CU; an interval that outran its window is
             // decoded again (dec_segments_ring_small), so a wrong guess here costs time, never correctness.
-            const int small = c->dbg.decode_small_ring;  // tests: 1 never, 2 always
-            const bool lean = g.n != 0 && (double)(cont_bytes - payload_off) / (double)g.n <= 2.0 && g.ckpt % 16 == 0;
-            if (small != 1 && (small == 2 || lean)) {
-                const size_t ldss = rs_tables + (size_t)(threads / 4) * ANSX_SRING_STRIDE + 16;
-                if (ldss > 48 * 1024)
-                    HIPCHK(c, hipFuncSetAttribute((const void*)k_decode_rank<RF, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldss));
-                LAUNCH(c, "k_decode", (k_decode_rank<RF, 2>), g.nblocks, threads, ldss, s, cont, g, NSP, boff,
-                    ck_state, ck_off, payload_off, d_out, maxM, max_ep, (u64)cont_bytes, (const u32*)c->dec_cum.p,
-                    (const uint4*)c->dec_info.p, gflags, setup_old);
-                return ANSX_OK;
+            const int small = dbg.decode_small_ring;  // tests: 1 never, 2 always
+            const bool lean = g.n != 0 && (double)B.payload_bytes / (double)g.n <= 2.0 && g.ckpt % 16 == 0;
+            if (pair != 1 && g.nblocks >= 2 && (pair == 2 ? lds2 <= 150 * 1024 : lds2 <= dbg.pair_lds_limit)) {
+                F.decoder = DEC_PAIR;
+                F.d.grid = (g.nblocks + 1) / 2;
+                F.d.lds = lds2;
+            } else if (small != 1 && (small == 2 || lean)) {
+                F.decoder = DEC_SMALL_RING;
+                F.d.lds = rs_tables + (size_t)(F.d.threads / 4) * ANSX_SRING_STRIDE + 16;
+            } else {
+                F.decoder = DEC_RING;
+                F.d.lds = rs_tables + ring_lds;
             }
-            const size_t lds = rs_tables + ring_lds;
-            if (lds > 48 * 1024)
-                HIPCHK(c, hipFuncSetAttribute((const void*)k_decode_rank<RF, 1>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LAUNCH(c, "k_decode", (k_decode_rank<RF, 1>), g.nblocks, threads, lds, s, cont, g, NSP, boff,
-                ck_state, ck_off, payload_off, d_out, maxM, max_ep, (u64)cont_bytes, (const u32*)c->dec_cum.p,
-                (const uint4*)c->dec_info.p, gflags, setup_old);
-            return ANSX_OK;
+            return F;
         }
-        size_t lds = rs_tables;
-        u32 stream_cap = 0;
-        if (staged_fits && !c->dbg.no_stream_lds) {
-            lds += want_stream;
-            stream_cap = (u32)want_stream;
+        F.decoder = DEC_STAGED;
+        if (!staged_fits || dbg.no_stream_lds) {
+            F.d.lds = rs_tables;
+            return F;
         }
-        if (lds > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_decode_rank<RF, 0>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(c, "k_decode", (k_decode_rank<RF, 0>), g.nblocks, threads, lds, s, cont, g, NSP, boff, ck_state,
-            ck_off, payload_off, d_out, maxM, max_ep, (u64)stream_cap, (const u32*)c->dec_cum.p,
-            (const uint4*)c->dec_info.p, gflags, setup_old);
-        return ANSX_OK;
-    }
-    // frames above 2^16 (or forced): slot -> symbol table form, in LDS if it fits, else in HBM
-    const size_t cb = rup(((size_t)max_ns + 2) * 4, 16);
-    const size_t s2sb = rup((size_t)maxM * 2, 16);
-    const size_t tables = cb + s2sb + mfb;
-    if (tables <= LDS_LIMIT) {
-        size_t lds = tables;
-        u32 stream_cap = 0;
-        if (tables + want_stream <= 52 * 1024) {
-            lds += want_stream;
-            stream_cap = (u32)want_stream;
-        }
-        if (lds > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_decode<true, RF>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(c, "k_decode_table", (k_decode<true, RF>), g.nblocks, threads, lds, s, cont, g, NSP, boff,
-            ck_state, ck_off, payload_off, d_out, maxM, max_ns, stream_cap, (u16*)nullptr,
-            (u32*)c->dec_cum.p, (const uint4*)c->dec_info.p, gflags);
     } else {
-        if ((rc = ensure(c, c->dec_s2s, (size_t)g.nblocks * maxM * 2))) return rc;
-        size_t lds = mfb;
-        u32 stream_cap = 0;
-        if (mfb + want_stream <= 52 * 1024) {
-            lds += want_stream;
-            stream_cap = (u32)want_stream;
+        // frames above 2^16 (or forced): slot -> symbol table form, in LDS if it fits, else in HBM
+        const size_t mfb = g.kind == ANSX_RFOLD ? (size_t)fold_T(g.f) * 4 : 0;
+        tables = rup(((size_t)max_ns + 2) * 4, 16) + rup((size_t)maxM * 2, 16) + mfb;
+        F.decoder = tables <= LDS_LIMIT ? DEC_TABLE : DEC_GTAB;
+        if (F.decoder == DEC_GTAB) tables = mfb;
+        if (tables + want_stream > 52 * 1024) {
+            F.d.lds = std::max<size_t>(tables, 16);
+            return F;
         }
-        if (lds < 16) lds = 16;
-        if (lds > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_decode<false, RF>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(c, "k_decode_gtab", (k_decode<false, RF>), g.nblocks, threads, lds, s, cont, g, NSP, boff,
-            ck_state, ck_off, payload_off, d_out, maxM, max_ns, stream_cap, (u16*)c->dec_s2s.p,
-            (u32*)c->dec_cum.p, (const uint4*)c->dec_info.p, gflags);
     }
+    F.d.lds = tables + want_stream;
+    F.stream_cap = (u32)want_stream;
+    return F;
+}
+
+// What the phases of a decode call share: where the pieces of its source are, its plan (the container's own, the
+// caller's per-block table put in) and the bounds its form is chosen from.
+struct DecodeSrc {
+    Plan P;
+    const u8* cont;
+    const u64* boff;
+    const u64* ck_state;
+    const u32* ck_off;
+    u64 payload_off;
+    const u32* hints;  // the container's parse hints, or null
+    DecodeBounds B;
+};
+
+// LAUNCH in the shape L, the kernel's limit on dynamic LDS raised first where the default does not do
+template <class K, class... Args>
+int launch_lds(ansx_ctx* c, const char* label, K kern, const LaunchShape& L, hipStream_t s, Args... args)
+{
+    int rc;
+    if (L.lds > 48 * 1024 && (rc = raise_lds(c, kern, L.lds))) return rc;
+    LAUNCH(c, label, kern, L.grid, L.threads, L.lds, s, args...);
     return ANSX_OK;
+}
+
+typedef void (*lane_parser_t)(const u8*, ansx_geo, u32, const u64*, u64, u32, u32, u32*, uint4*, u32*, const uint4*);
+typedef void (*par_parser_t)(const u8*, ansx_geo, u32, const u64*, u64, u32, u32, const u32*, u32*, uint4*, u32*, const uint4*);
+typedef void (*rank_decoder_t)(const u8*, ansx_geo, u32, const u64*, const u64*, const u32*, u64, u32*, u32, u32, u64,
+    const u32*, const uint4*, u32*, u32);
+
+// K7 and K8 as the form says: the parser fills dec_cum / dec_info, the decoder reads them
+template <bool RF>
+int launch_decode(ansx_ctx* c, const DecodeSrc& S, const DecodeForm& F, u32* d_out, hipStream_t s)
+{
+    const ansx_geo& g = S.P.g;
+    const DecodeBounds& B = S.B;
+    const u32 NSP = S.P.NSP;
+    int rc;
+    if ((rc = ensure(c, c->dec_cum, (size_t)g.nblocks * (NSP + 8) * 4))) return rc;
+    if ((rc = ensure(c, c->dec_info, (size_t)g.nblocks * 16))) return rc;
+    if (F.decoder == DEC_GTAB && (rc = ensure(c, c->dec_s2s, (size_t)g.nblocks * B.maxM * 2))) return rc;
+    u32* cum = (u32*)c->dec_cum.p;
+    uint4* info = (uint4*)c->dec_info.p;
+    u32* gflags = (u32*)c->misc.p;
+    const uint4* pa_info = g.pa ? (const uint4*)c->pa_info.p : nullptr;
+    const par_parser_t par[3] = { k_parse_prelude_par<RF, ANSX_PAR_SW, 0>, k_parse_prelude_par<RF, ANSX_PAR_SW, 1>, k_parse_prelude_par<RF, ANSX_PAR_SW, 2> };
+    const lane_parser_t lane = F.parser == PARSE_GENERIC ? k_parse_prelude<RF> : F.p_variant == 128 ? k_parse_prelude_win<RF, 128> : k_parse_prelude_win<RF, 256>;
+    const rank_decoder_t rank[4] = { k_decode_rank<RF, 0>, k_decode_rank<RF, 1>, k_decode_rank<RF, 2>, k_decode_rank2<RF> };  // by DEC_*
+    if (F.parser == PARSE_PAR)
+        rc = launch_lds(c, F.p_variant ? "k_parse_prelude_arr" : "k_parse_prelude", par[F.p_variant], F.p, s,
+            S.cont, g, NSP, S.boff, S.payload_off, B.max_ns, B.maxM, S.hints, cum, info, gflags, pa_info);
+    else if (F.parser == PARSE_FAST)
+        rc = launch_lds(c, "k_parse_prelude", k_parse_prelude_fast<RF>, F.p, s, S.cont, g, NSP,
+            S.boff, S.payload_off, B.max_ns, B.maxM, cum, info, gflags, F.p_variant, pa_info);
+    else if (F.parser != PARSE_DONE)
+        rc = launch_lds(c, "k_parse_prelude", lane, F.p, s, S.cont, g, NSP, S.boff,
+            S.payload_off, B.max_ns, B.maxM, cum, info, gflags, pa_info);
+    if (rc) return rc;
+    if (F.decoder == DEC_TABLE || F.decoder == DEC_GTAB) {
+        const bool lds_tab = F.decoder == DEC_TABLE;
+        return launch_lds(c, lds_tab ? "k_decode_table" : "k_decode_gtab", lds_tab ? k_decode<true, RF> : k_decode<false, RF>,
+            F.d, s, S.cont, g, NSP, S.boff, S.ck_state, S.ck_off, S.payload_off, d_out, B.maxM,
+            B.max_ns, F.stream_cap, lds_tab ? (u16*)nullptr : (u16*)c->dec_s2s.p, cum, (const uint4*)info, gflags);
+    }
+    // (the ring decoders bound their reads by the container's bytes where the staged one takes its staging size)
+    const u64 cap = F.decoder == DEC_STAGED ? F.stream_cap : S.payload_off + B.payload_bytes;
+    const u32 setup_old = c->dbg.setup_old ? 1u : 0u;  // the scan form of dec_build_rank_tables
+    return launch_lds(c, "k_decode", rank[F.decoder], F.d, s, S.cont, g, NSP, S.boff, S.ck_state,
+        S.ck_off, S.payload_off, d_out, B.maxM, B.max_ep, cap, (const u32*)cum, (const uint4*)info, gflags, setup_old);
 }
 
 __global__ void k_selftest_div(const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out, u64 n)
@@ -1824,193 +1904,161 @@ int container_plan(const ansx_container_header& H, u32 kind, u32 f, size_t in_by
     return ANSX_OK;
 }
 
-// remember = false: the header is not stored in hdr_cache (ansx_decode_ranges_dev's sub-containers must not stand in
-// for the containers of ordinary calls of the same shape).  epilogue: enqueued behind the decode's kernels and before
-// its status read-back (ansx_decode_ranges_dev's gather: one host round trip less); given the device flags.
-int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u32* d_out,
-    hipStream_t s, bool allow_spec = true, bool remember = true, const std::function<int(const u32*)>* epilogue = nullptr)
+// One reference stream as the decoder's source: copied behind a 16-byte guard (the decoder reads 8 bytes below its
+// cursor), max_sym / log2 M peeked on the host, the two index entries of its one block written here.
+int source_plain(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, hipStream_t s, DecodeSrc* S)
 {
-    Plan P = Pin;
-    bool spec = false;
-    ansx_container_header Hspec;
-    const std::array<u64, 4> hkey = { (u64)Pin.g.kind, (u64)Pin.g.f, (u64)Pin.g.n, (u64)in_bytes };
     int rc;
-    if ((rc = ensure(c, c->misc, 64 + 8 * ((size_t)P.g.nblocks + 1)))) return rc;
-    u32* gflags = (u32*)c->misc.p;
-    HIPCHK(c, hipMemsetAsync(c->misc.p, 0, 64, s));
-    const u32 f = P.g.f;
-    const u32 T = fold_T(f);
-    u32 maxM, max_ns, max_block_bytes;
-    u32 max_ep = 0;  // bound on the symbols present in a block (0: as many as max_ns)
-    const u8* cont;
-    const u64* boff;
-    const u64* ck_state = nullptr;
-    const u32* ck_off = nullptr;
-    u64 payload_off;
-    u64 in_bytes_payload = 0;  // bytes of block streams behind payload_off (bounds the ring decoder reads)
-    if (P.plain) {
-        // one reference stream: copy behind a 16-byte guard (the decoder reads 8 bytes below
-        // its cursor) and peek max_sym / log2 M on the host
-        if (in_bytes < 38) return ANSX_ERR_FORMAT;
-        if ((rc = ensure(c, c->plain, in_bytes + 64))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->plain.p, 0, 16, s));
-        HIPCHK(c, hipMemcpyAsync((u8*)c->plain.p + 16, d_in, in_bytes, hipMemcpyDeviceToDevice, s));
-        // ONE host round trip: the first 16 bytes and, for ANSrfold, the 8 bytes behind a most-frequent table (where the
-        // prelude starts if the block was reordered) are requested together
-        size_t peek = in_bytes < 16 ? in_bytes : 16;
-        u8* hp = (u8*)c->h_pin + 64;
-        u8* hp2 = hp + 16;
-        const size_t pos_rf = 4 + 4 * (size_t)T;
-        const bool have_rf = P.g.kind == ANSX_RFOLD && pos_rf + 8 <= in_bytes;
-        HIPCHK(c, hipMemcpyAsync(hp, d_in, peek, hipMemcpyDeviceToHost, s));
-        if (have_rf) HIPCHK(c, hipMemcpyAsync(hp2, d_in + pos_rf, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        size_t pos = 0;
-        if (P.g.kind == ANSX_RFOLD) {
-            u32 flag;
-            memcpy(&flag, hp, 4);
-            if (flag > 1) return ANSX_ERR_FORMAT;
-            pos = 4 + (flag ? 4 * (size_t)T : 0);
-            if (pos + 8 > in_bytes) return ANSX_ERR_FORMAT;
-            if (flag) {
-                hp = hp2;
-                pos = 0;
-            }
-        }
-        u32 ms = 0, sh = 0;
-        for (int i = 0; i < 5; i++) {
-            u8 cb = hp[pos++];
-            ms += (u32)(cb & 127) << sh;
-            if (!(cb & 128)) break;
-            sh += 7;
-        }
-        u32 lg = hp[pos];
-        const bool int_sp = P.g.kind == ANSX_INT && !P.g.pa;  // (any max_sym below 2^30: the model is parsed in rank space)
-        if ((int_sp ? ms >= ANSX_SP_VALUE_LIMIT : ms >= P.NSP) || lg > 31) return ANSX_ERR_FORMAT;
-        maxM = 1u << lg;
-        max_ns = ms + 1 < P.NSP ? ms + 1 : P.NSP;
-        // (the two index entries of the one block go up from pinned memory: no wait -- the page is next written by
-        // this call's final read-back, which the stream orders behind this copy)
-        u64* hb = (u64*)((u8*)c->h_pin + 64 + 32);
-        hb[0] = 0, hb[1] = (u64)in_bytes;
-        P.g.trusted_index = 1;  // the index of this one block is the pair written here, not container bytes
-        u64* boff_ws = (u64*)((u8*)c->misc.p + 64);
-        HIPCHK(c, hipMemcpyAsync(boff_ws, hb, 16, hipMemcpyHostToDevice, s));
-        cont = (const u8*)c->plain.p;
-        boff = boff_ws;
-        payload_off = 16;
-        max_block_bytes = (u32)in_bytes;
-        in_bytes_payload = in_bytes;
-    } else {
-        u8* hp = (u8*)c->h_pin + 64;
-        if (in_bytes < sizeof(ansx_container_header)) return ANSX_ERR_FORMAT;
-        ansx_container_header H;
-        const auto hit = c->hdr_cache.find(hkey);
-        if (allow_spec && hit != c->hdr_cache.end()) {
-            // Same shape as a container decoded before: launch on that header now, verify it on the device
-            // (k_check_header); a different header repeats the call the slow way.  Every kernel treats header-derived
-            // sizes as untrusted anyway (index entries, restart points and hints are bounds-checked against them).
-            H = hit->second;
-            memcpy(hp, &H, sizeof(H));
-            spec = true;
-            Hspec = H;
-        } else {
-            HIPCHK(c, hipMemcpyAsync(hp, d_in, sizeof(ansx_container_header), hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-        }
-        if ((rc = parse_header(hp, in_bytes, &H))) return rc;
-        if (H.n != P.g.n) return ANSX_ERR_FORMAT;
-        if ((rc = container_plan(H, P.g.kind, f, in_bytes, &P))) return rc;
-        maxM = 1u << H.max_log2_frame;
-        max_ns = H.max_nsyms ? H.max_nsyms : 1u;
-        max_ep = std::min<u32>(max_ns, (u32)H.max_present_m1 + 1u);
-        cont = d_in;
-        boff = (const u64*)(d_in + P.lay.index_off);
-        ck_state = (const u64*)(d_in + P.lay.ckstate_off);
-        ck_off = (const u32*)(d_in + P.lay.ckoff_off);
-        payload_off = H.payload_offset;
-        in_bytes_payload = H.payload_bytes;
-        P.g.payload_bytes = H.payload_bytes;  // every parser validates the two index entries of its own block (index_entry_ok)
-        P.g.bout = Pin.bout;                  // (container_plan -> make_plan has reset it)
-        // The ring decoder needs nothing else from the index: no validation kernel, no read-back.  The staged /
-        // straight-from-HBM forms size their LDS from the largest block stream, which only the index knows.
-        const size_t rs_probe = rup((size_t)(maxM >= 32 ? maxM / 32 : 1) * 8, 16) + 2 * rup((size_t)max_ep * 4, 16) + ANSX_DEC_SCRATCH;
-        const bool ring_certain = !P.g.pa && maxM <= 65536u && P.g.ckpt != 0 && P.g.block_ints % P.g.ckpt == 0 && P.g.ckpt % 4 == 0
-            && c->dbg.decode_mode != 2 && !c->dbg.decode_table
-            && rs_probe + (size_t)(std::min<u32>(256u, (u32)rup((size_t)geo_nseg(P.g.block_ints, P.g.ckpt) * 4, 64)) / 4) * ANSX_RING_STRIDE + 16 <= 60 * 1024;
-        if (spec && !ring_certain) {  // (a read-back follows anyway: nothing to gain from the cached header)
-            c->hdr_cache.erase(hkey);
-            return decode_dev(c, Pin, d_in, in_bytes, d_out, s, false);
-        }
-        if (ring_certain) {
-            max_block_bytes = (u32)std::min<size_t>(0x7FFFFFFFu, block_bound((int)P.g.kind, f, P.g.block_ints, false));  // (=> never "staged fits")
-        } else {
-            LAUNCH(c, "k_validate_index", k_validate_index, (P.g.nblocks + 255) / 256, 256, 0, s, P.g, boff,
-                H.payload_bytes, gflags);
-            // the index must be sane before any block is touched
-            HIPCHK(c, hipMemcpyAsync(c->h_pin, c->misc.p, 16, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-            if (c->h_pin[ANSX_G_ERR]) return flags_to_status(c->h_pin[ANSX_G_ERR]);
-            max_block_bytes = c->h_pin[ANSX_G_PAD];
-        }
-    }
-    const u32* hints = P.plain ? nullptr : (const u32*)(d_in + P.lay.hint_off);
-    const uint4* pa_info = nullptr;
-    // alpha scratch: laid out like the output (geo_block_out)
-    const size_t alpha_bytes = 4 * (P.g.bout ? (size_t)Pin.bout_ints : (size_t)P.g.nblocks * P.g.block_ints);
-    if (P.g.pa) {  // alphabet headers first: they tell where every block's codec stream starts
-        if ((rc = ensure(c, c->pa_alpha, alpha_bytes))) return rc;
-        if ((rc = ensure(c, c->pa_info, (size_t)P.g.nblocks * 16))) return rc;
-        LAUNCH(c, "k_pa_parse", k_pa_parse, (P.g.nblocks + 63) / 64, 64, 0, s, cont, P.g, boff, payload_off,
-            (u32*)c->pa_alpha.p, (uint4*)c->pa_info.p, gflags);
-        pa_info = (const uint4*)c->pa_info.p;
-    }
-    const bool int_sparse = P.g.kind == ANSX_INT && !P.g.pa;
-    if (int_sparse) {
-        // plain ANSint: the prelude ranges over the VALUES (any max_sym); its present symbols become the block's ranks
-        // (ansx_intsparse.h) -- whichever model the encoder ran, the stream is the reference's
-        if ((rc = ensure(c, c->pa_alpha, alpha_bytes))) return rc;
-        if ((rc = ensure(c, c->pa_info, (size_t)P.g.nblocks * 16))) return rc;
-        if ((rc = ensure(c, c->dec_cum, (size_t)P.g.nblocks * (P.NSP + 8) * 4))) return rc;
-        if ((rc = ensure(c, c->dec_info, (size_t)P.g.nblocks * 16))) return rc;
-        LAUNCH(c, "k_parse_prelude", k_int_sparse_parse, (P.g.nblocks + 63) / 64, 64, 0, s, cont, P.g, P.NSP, boff, payload_off, maxM,
-            (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, (u32*)c->pa_alpha.p, (uint4*)c->pa_info.p, gflags);
-    }
-    if (P.g.kind == ANSX_RFOLD)
-        rc = launch_decode<true>(c, P.g, P.NSP, cont, boff, ck_state, ck_off, payload_off, d_out, maxM,
-            max_ns, max_block_bytes, (u64)payload_off + in_bytes_payload, gflags, s, pa_info, hints, max_ep ? max_ep : max_ns);
-    else
-        rc = launch_decode<false>(c, P.g, P.NSP, cont, boff, ck_state, ck_off, payload_off, d_out, maxM,
-            max_ns, max_block_bytes, (u64)payload_off + in_bytes_payload, gflags, s, pa_info, hints, max_ep ? max_ep : max_ns, int_sparse);
-    if (rc) return rc;
-    if (int_sparse)
-        LAUNCH(c, "k_int_unmap", k_int_unmap, P.g.nblocks, 256, 0, s, P.g, (const u32*)c->pa_alpha.p, (const uint4*)c->pa_info.p, d_out, gflags);
-    if (P.g.pa)
-        LAUNCH(c, "k_pa_unmap", k_pa_unmap, P.g.nblocks, 256, 0, s, P.g, (const u32*)c->pa_alpha.p, pa_info, d_out, gflags);
-    if (spec) LAUNCH(c, "k_check_header", k_check_header, 1, 64, 0, s, d_in, Hspec, gflags);
-    if (epilogue && (rc = (*epilogue)(gflags))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->misc.p, 64, hipMemcpyDeviceToHost, s));
+    Plan P = Pin;
+    if (in_bytes < 38) return ANSX_ERR_FORMAT;
+    if ((rc = ensure(c, c->plain, in_bytes + 64))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->plain.p, 0, 16, s));
+    HIPCHK(c, hipMemcpyAsync((u8*)c->plain.p + 16, d_in, in_bytes, hipMemcpyDeviceToDevice, s));
+    // ONE host round trip: the first 16 bytes and, for ANSrfold, the 8 bytes behind a most-frequent table (where the
+    // prelude starts if the block was reordered) are requested together
+    const u8* hp = c->pin->plain.peek;
+    const size_t pos_rf = 4 + 4 * (size_t)fold_T(P.g.f);
+    HIPCHK(c, hipMemcpyAsync(c->pin->plain.peek, d_in, 16, hipMemcpyDeviceToHost, s));
+    if (P.g.kind == ANSX_RFOLD && pos_rf + 8 <= in_bytes)
+        HIPCHK(c, hipMemcpyAsync(c->pin->plain.peek_rf, d_in + pos_rf, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (spec && (c->h_pin[ANSX_G_ERR] & (1u << ANSX_G_HDR_BIT))) {
-        c->hdr_cache.erase(hkey);
-        return decode_dev(c, Pin, d_in, in_bytes, d_out, s, false);
-    }
-    const int st = flags_to_status(c->h_pin[ANSX_G_ERR]);
-    if (!P.plain && !spec && st == ANSX_OK && remember) {
-        ansx_container_header Hc;
-        memcpy(&Hc, (u8*)c->h_pin + 64, sizeof(Hc));
-        if (c->hdr_cache.find(hkey) == c->hdr_cache.end()) {
-            // evict the OLDEST remembered shape (insertion order), never the one being stored
-            c->hdr_order.erase(std::remove(c->hdr_order.begin(), c->hdr_order.end(), hkey), c->hdr_order.end());  // (left behind by a mismatch)
-            c->hdr_order.push_back(hkey);
-            while (c->hdr_order.size() > 64) {
-                c->hdr_cache.erase(c->hdr_order.front());
-                c->hdr_order.pop_front();
-            }
+    size_t pos = 0;
+    if (P.g.kind == ANSX_RFOLD) {
+        u32 flag;
+        memcpy(&flag, hp, 4);
+        if (flag > 1) return ANSX_ERR_FORMAT;
+        pos = flag ? pos_rf : 4;
+        if (pos + 8 > in_bytes) return ANSX_ERR_FORMAT;
+        if (flag) {
+            hp = c->pin->plain.peek_rf;
+            pos = 0;
         }
-        c->hdr_cache[hkey] = Hc;
     }
-    return st;
+    u32 ms = 0, sh = 0;
+    for (int i = 0; i < 5; i++) {
+        u8 cb = hp[pos++];
+        ms += (u32)(cb & 127) << sh;
+        if (!(cb & 128)) break;
+        sh += 7;
+    }
+    const u32 lg = hp[pos];
+    const bool int_sp = P.g.kind == ANSX_INT && !P.g.pa;  // (any max_sym below 2^30: the model is parsed in rank space)
+    if ((int_sp ? ms >= ANSX_SP_VALUE_LIMIT : ms >= P.NSP) || lg > 31) return ANSX_ERR_FORMAT;
+    // (the two index entries of the one block go up from pinned memory: no wait -- the page is next written by
+    // this call's final read-back, which the stream orders behind this copy)
+    u64* hb = c->pin->plain.index;
+    hb[0] = 0, hb[1] = (u64)in_bytes;
+    P.g.trusted_index = 1;  // the index of this one block is the pair written here, not container bytes
+    u64* boff_ws = (u64*)((u8*)c->misc.p + 64);
+    HIPCHK(c, hipMemcpyAsync(boff_ws, hb, 16, hipMemcpyHostToDevice, s));
+    const u32 max_ns = std::min(ms + 1, P.NSP);
+    *S = { P, (const u8*)c->plain.p, boff_ws, nullptr, nullptr, 16, nullptr, { 1u << lg, max_ns, max_ns, false, in_bytes, (u32)in_bytes } };
+    return ANSX_OK;
+}
+
+// A container as the decoder's source: its header -- `spec` if given, else fetched (one host round trip) -- checked, the
+// plan it implies and the bounds it states.  Every kernel treats header-derived sizes as untrusted anyway (index entries,
+// restart points and hints are bounds-checked against them): that is what lets a call run on a remembered header.
+int source_container(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, const ansx_container_header* spec,
+    hipStream_t s, DecodeSrc* S)
+{
+    int rc;
+    Plan P = Pin;
+    if (in_bytes < sizeof(ansx_container_header)) return ANSX_ERR_FORMAT;
+    if (spec) {
+        c->pin->hdr = *spec;
+    } else {
+        HIPCHK(c, hipMemcpyAsync(&c->pin->hdr, d_in, sizeof(ansx_container_header), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    ansx_container_header H;
+    if ((rc = parse_header((const u8*)&c->pin->hdr, in_bytes, &H))) return rc;
+    if (H.n != P.g.n) return ANSX_ERR_FORMAT;
+    if ((rc = container_plan(H, P.g.kind, P.g.f, in_bytes, &P))) return rc;
+    P.g.payload_bytes = H.payload_bytes;  // every parser validates the two index entries of its own block (index_entry_ok)
+    P.g.bout = Pin.bout;                  // (container_plan -> make_plan has reset it)
+    const u32 max_ns = H.max_nsyms ? H.max_nsyms : 1u;
+    *S = { P, d_in, (const u64*)(d_in + P.lay.index_off), (const u64*)(d_in + P.lay.ckstate_off), (const u32*)(d_in + P.lay.ckoff_off),
+        H.payload_offset, (const u32*)(d_in + P.lay.hint_off),
+        { 1u << H.max_log2_frame, max_ns, std::min<u32>(max_ns, (u32)H.max_present_m1 + 1u), true, H.payload_bytes, 0 } };
+    return ANSX_OK;
+}
+
+// The steps ahead of the parser where the codec ran on a block's ranks (k_pa_unmap / k_int_unmap put the values back).
+int decode_premap(ansx_ctx* c, const DecodeSrc& S, hipStream_t s)
+{
+    const Plan& P = S.P;
+    const bool int_sparse = P.g.kind == ANSX_INT && !P.g.pa;
+    if (!P.g.pa && !int_sparse) return ANSX_OK;
+    int rc;
+    u32* gflags = (u32*)c->misc.p;
+    // alpha scratch: laid out like the output (geo_block_out)
+    if ((rc = ensure(c, c->pa_alpha, 4 * (P.g.bout ? (size_t)P.bout_ints : (size_t)P.g.nblocks * P.g.block_ints)))) return rc;
+    if ((rc = ensure(c, c->pa_info, (size_t)P.g.nblocks * 16))) return rc;
+    if (P.g.pa) {  // alphabet headers first: they tell where every block's codec stream starts
+        LAUNCH(c, "k_pa_parse", k_pa_parse, (P.g.nblocks + 63) / 64, 64, 0, s, S.cont, P.g, S.boff, S.payload_off,
+            (u32*)c->pa_alpha.p, (uint4*)c->pa_info.p, gflags);
+        return ANSX_OK;
+    }
+    // plain ANSint: the prelude ranges over the VALUES (any max_sym); its present symbols become the block's ranks
+    // (ansx_intsparse.h) -- whichever model the encoder ran, the stream is the reference's
+    if ((rc = ensure(c, c->dec_cum, (size_t)P.g.nblocks * (P.NSP + 8) * 4))) return rc;
+    if ((rc = ensure(c, c->dec_info, (size_t)P.g.nblocks * 16))) return rc;
+    LAUNCH(c, "k_parse_prelude", k_int_sparse_parse, (P.g.nblocks + 63) / 64, 64, 0, s, S.cont, P.g, P.NSP, S.boff, S.payload_off, S.B.maxM,
+        (u32*)c->dec_cum.p, (uint4*)c->dec_info.p, (u32*)c->pa_alpha.p, (uint4*)c->pa_info.p, gflags);
+    return ANSX_OK;
+}
+
+struct DecodeOpts {
+    bool speculate = true;  // launch on the header remembered for the container's shape, if there is one
+    bool remember = true;   // false: a sub-container must not stand in for the containers of ordinary calls of its shape
+    // enqueued behind the decode's kernels and before its status read-back (the caller's gather: one host round trip less)
+    const std::function<int(const u32* gflags)>* epilogue = nullptr;
+};
+
+// A decode call.  Where the call may (O.speculate) and a header is remembered for the container's shape, the first attempt
+// runs on that header, `spec`, without waiting for the container's own; an attempt in vain is repeated once without.
+int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u32* d_out, hipStream_t s,
+    const DecodeOpts& O = DecodeOpts())
+{
+    const HeaderCache::Key key = { (u64)Pin.g.kind, (u64)Pin.g.f, (u64)Pin.g.n, (u64)in_bytes };
+    const ansx_container_header* spec = !Pin.plain && O.speculate ? c->hdrs.find(key) : nullptr;
+    for (;; c->hdrs.forget(key), spec = nullptr) {  // (at most twice: only an attempt on `spec` is repeated)
+        int rc;
+        if ((rc = ensure(c, c->misc, 64 + 8 * ((size_t)Pin.g.nblocks + 1)))) return rc;
+        u32* gflags = (u32*)c->misc.p;
+        HIPCHK(c, hipMemsetAsync(c->misc.p, 0, 64, s));
+        DecodeSrc S;
+        if ((rc = Pin.plain ? source_plain(c, Pin, d_in, in_bytes, s, &S) : source_container(c, Pin, d_in, in_bytes, spec, s, &S)))
+            return rc;
+        const ansx_geo& g = S.P.g;
+        DecodeForm F = choose_decode_form(g, S.B, c->dbg, c->num_cus);
+        if (F.needs_index) {
+            if (spec) continue;  // (a read-back follows anyway: nothing to gain from the remembered header)
+            LAUNCH(c, "k_validate_index", k_validate_index, (g.nblocks + 255) / 256, 256, 0, s, g, S.boff, S.B.payload_bytes, gflags);
+            // the index must be sane before any block is touched
+            HIPCHK(c, hipMemcpyAsync(c->pin->flags, c->misc.p, 16, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            if (c->pin->flags[ANSX_G_ERR]) return flags_to_status(c->pin->flags[ANSX_G_ERR]);
+            S.B.max_block_bytes = c->pin->flags[ANSX_G_PAD];
+            F = choose_decode_form(g, S.B, c->dbg, c->num_cus);
+        }
+        if ((rc = decode_premap(c, S, s))) return rc;
+        if ((rc = g.kind == ANSX_RFOLD ? launch_decode<true>(c, S, F, d_out, s) : launch_decode<false>(c, S, F, d_out, s))) return rc;
+        if (g.kind == ANSX_INT && !g.pa)
+            LAUNCH(c, "k_int_unmap", k_int_unmap, g.nblocks, 256, 0, s, g, (const u32*)c->pa_alpha.p, (const uint4*)c->pa_info.p, d_out, gflags);
+        if (g.pa)
+            LAUNCH(c, "k_pa_unmap", k_pa_unmap, g.nblocks, 256, 0, s, g, (const u32*)c->pa_alpha.p, (const uint4*)c->pa_info.p, d_out, gflags);
+        // the finish: the header the call ran on against the real one, the caller's epilogue, ONE read-back, the status
+        if (spec) LAUNCH(c, "k_check_header", k_check_header, 1, 64, 0, s, d_in, *spec, gflags);
+        if (O.epilogue && (rc = (*O.epilogue)(gflags))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->pin->flags, c->misc.p, 64, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (spec && (c->pin->flags[ANSX_G_ERR] & (1u << ANSX_G_HDR_BIT))) continue;  // another header: the slow way
+        const int st = flags_to_status(c->pin->flags[ANSX_G_ERR]);
+        if (!Pin.plain && !spec && st == ANSX_OK && O.remember) c->hdrs.remember(key, c->pin->hdr);
+        return st;
+    }
 }
 
 // --------------------------------------------------------------------------------- random access
@@ -2037,13 +2085,52 @@ int range_source(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, 
 {
     int rc;
     if (in_bytes < sizeof(ansx_container_header)) return ANSX_ERR_FORMAT;
-    u8* hp = (u8*)c->h_pin + 64;
-    HIPCHK(c, hipMemcpyAsync(hp, d_in, sizeof(ansx_container_header), hipMemcpyDeviceToHost, s));
+    const u8* hp = (const u8*)&c->pin->hdr;
+    HIPCHK(c, hipMemcpyAsync(&c->pin->hdr, d_in, sizeof(ansx_container_header), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if ((rc = parse_header(hp, in_bytes, H))) return rc;  // (a single-stream stream has no magic: ANSX_ERR_FORMAT)
     if ((rc = container_plan(*H, (u32)kind, (u32)f, in_bytes, P))) return rc;
     P->g.payload_bytes = H->payload_bytes;  // (index_entry_ok on the source's entries)
     return ANSX_OK;
+}
+
+// What the ranges and batch entries share: a container built on the device from blocks of other containers, decoded to
+// a work list the caller gathers from.  The sub-container has T blocks and n_sub ints in the geometry of header H (any
+// n_sub that makes make_plan lay out exactly T blocks; bout / list_ints: the decoders' table over a list of so many ints,
+// or null / n_sub) and a payload of at most cap_pay bytes.  `build` enqueues the kernels that write it (its plan, its
+// header -- payload_bytes is theirs to fill in -- and where it goes), decode_dev decodes it (no remembered header in or
+// out), `gather` enqueues the copy out of the list (given the decode's flags: it skips when they hold an error).  The
+// gather and the read-back of dflags, the caller's own flag word, ride on the decode's final read-back.
+typedef std::function<int(const Plan& Ps, const ansx_container_header& Hs, u8* sub)> SubBuild;
+typedef std::function<int(const u32* list, const u32* gflags)> SubGather;
+int decode_sub(ansx_ctx* c, int kind, int f, ansx_container_header H, u64 n_sub, u32 T, u64 cap_pay, u64 list_ints,
+    const ansx_blk_out* bout, const u32* dflags, const SubBuild& build, const SubGather& gather, hipStream_t s)
+{
+    int rc;
+    Plan Ps;
+    const ansx_opts o = container_opts(H);
+    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
+    set_restart_format(&Ps, (H.kind & ANSX_KIND_WIDE_RESTART) != 0);
+    if (Ps.g.nblocks != T || Ps.g.nckf != H.ckpts_per_block) return ANSX_ERR_FORMAT;
+    Ps.bout = bout, Ps.bout_ints = list_ints;
+    H.n = n_sub, H.nblocks = T, H.payload_bytes = 0, H.payload_offset = Ps.lay.payload_off;
+    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
+    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
+    if ((rc = ensure(c, c->rng_list, 4 * list_ints + 64))) return rc;
+    u8* sub = (u8*)c->rng_cont.p;
+    u32* list = (u32*)c->rng_list.p;
+    if ((rc = build(Ps, H, sub))) return rc;
+    u32* hflag = &c->pin->caller_flag;
+    *hflag = 0;
+    const std::function<int(const u32*)> epilogue = [&](const u32* gflags) -> int {
+        if ((rc = gather(list, gflags))) return rc;
+        HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
+        return ANSX_OK;
+    };
+    DecodeOpts O;
+    O.speculate = O.remember = false, O.epilogue = &epilogue;
+    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, O);
+    return *hflag ? ANSX_ERR_FORMAT : rc;  // (the flag: an index entry of one of its blocks was invalid)
 }
 
 // The tail both fronts share, from the plan on the device: tb[T] the touched blocks (ascending, unique; last_b the
@@ -2052,46 +2139,23 @@ int range_tail(ansx_ctx* c, int kind, int f, const u8* d_in, const ansx_containe
     u64 last_b, const u32* dtb, const ansx_range_piece* R, const u32* pstart, u32 nr, u64 npieces, u32* dflags,
     u32* d_out, hipStream_t s)
 {
-    int rc;
     const u64 n = H.n, bi = P.g.block_ints;
     const u64 n_sub = (T - 1) * bi + std::min<u64>(bi, n - last_b * bi);  // (only the source's last block can be short: it sorts last)
-
-    // the sub-container's plan: make_plan's layout for n_sub ints, the source's restart-point format
-    const ansx_opts o = container_opts(H);
-    Plan Ps;
-    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
-    set_restart_format(&Ps, P.g.ckw != 0);
-    if (Ps.g.nblocks != T || Ps.g.nckf != P.g.nckf) return ANSX_ERR_FORMAT;
     // (max_present_m1, max_nsyms, max_log2_frame are bounds over the blocks: they hold for any subset)
-    ansx_container_header Hs = H;
-    Hs.n = n_sub;
-    Hs.nblocks = (u32)T;
-    Hs.payload_bytes = 0;  // (k_range_index writes the sum of the touched blocks' stream lengths)
-    Hs.payload_offset = Ps.lay.payload_off;
     const u64 cap_pay = std::min<u64>(H.payload_bytes, T * (u64)block_bound(kind, (u32)f, P.g.block_ints, P.g.pa != 0));
-    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
-    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
-    if ((rc = ensure(c, c->rng_list, 4 * n_sub + 64))) return rc;
-    u8* sub = (u8*)c->rng_cont.p;
-    u32* list = (u32*)c->rng_list.p;
-
-    const ansx_range_lay sl = { P.lay.ckoff_off, P.lay.ckstate_off, P.lay.hint_off, P.lay.payload_off };
-    const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
-    LAUNCH(c, "k_range_index", k_range_index, 1, 1024, 0, s, d_in, P.g, dtb, (u32)T, Hs, sub, cap_pay, dflags);
-    LAUNCH(c, "k_range_copy", k_range_copy, (u32)T, 256, 0, s, d_in, P.g, sl, dl, dtb, sub, cap_pay, dflags);
-    // the gather and the read-back of this call's own flags ride on the decode's final read-back (the gather skips
-    // when the decode flagged an error)
-    u32* hflag = c->h_pin + 512;  // (bytes 2048.. of the pinned page: clear of the header scratch decode_dev uses)
-    *hflag = 0;
-    const std::function<int(const u32*)> gather = [&](const u32* gflags) -> int {
-        const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
-        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, R, pstart, nr, (u32)npieces, d_out, gflags);
-        HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
+    const SubBuild build = [&](const Plan& Ps, const ansx_container_header& Hs, u8* sub) -> int {
+        const ansx_range_lay sl = { P.lay.ckoff_off, P.lay.ckstate_off, P.lay.hint_off, P.lay.payload_off };
+        const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
+        LAUNCH(c, "k_range_index", k_range_index, 1, 1024, 0, s, d_in, P.g, dtb, (u32)T, Hs, sub, cap_pay, dflags);
+        LAUNCH(c, "k_range_copy", k_range_copy, (u32)T, 256, 0, s, d_in, P.g, sl, dl, dtb, sub, cap_pay, dflags);
         return ANSX_OK;
     };
-    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, false, false, &gather);
-    if (*hflag) return ANSX_ERR_FORMAT;  // an index entry of a touched block was invalid
-    return rc;
+    const SubGather gather = [&](const u32* list, const u32* gflags) -> int {
+        const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
+        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, R, pstart, nr, (u32)npieces, d_out, gflags);
+        return ANSX_OK;
+    };
+    return decode_sub(c, kind, f, H, n_sub, (u32)T, cap_pay, n_sub, nullptr, dflags, build, gather, s);
 }
 
 // ansx_decode_ranges_dev: the plan built on the host from host arrays, uploaded in one copy
@@ -2231,7 +2295,7 @@ int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in
     }
     const u32* S = kv[2 - cur];
     const u32* offl = kv[3 - cur];
-    u64* hs = (u64*)((u8*)c->h_pin + 3072);  // (clear of decode_dev's header scratch and range_tail's flag word)
+    u64* hs = c->pin->planner;
     HIPCHK(c, hipMemcpyAsync(hs, sc, 64, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (hs[ANSX_DR_BAD]) return ANSX_ERR_ARG;
@@ -2282,21 +2346,7 @@ int pass_decode(ansx_ctx* c, int kind, int f, const ansx_container_header& H0, a
     u64 cap_pay, const PassTail& tail, const PassGather& pass_gather, hipStream_t s)
 {
     int rc;
-    const u64 bi = H0.block_ints;
     const u32 T = (u32)B.size(), nr = (u32)S.size();
-
-    // the sub-container's plan: any n that makes make_plan lay out exactly T blocks (the table says how long each is)
-    const u64 n_sub = (u64)(T - 1) * bi + O.back().n;
-    const ansx_opts o = container_opts(H0);
-    Plan Ps;
-    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
-    set_restart_format(&Ps, (H0.kind & ANSX_KIND_WIDE_RESTART) != 0);
-    if (Ps.g.nblocks != T) return ANSX_ERR_FORMAT;
-    Hs.n = n_sub;
-    Hs.nblocks = T;
-    Hs.payload_bytes = 0;  // (k_batch_index writes the sum of the blocks' stream lengths)
-    Hs.payload_offset = Ps.lay.payload_off;
-
     // the pass's plan, one upload: flags[4] | sources | blocks | table | the tail's two sections
     const size_t o_s = 16, o_b = rup(o_s + sizeof(ansx_batch_src) * nr, 16), o_o = rup(o_b + sizeof(ansx_batch_blk) * T, 16);
     const size_t o_r = rup(o_o + sizeof(ansx_blk_out) * T, 16), o_p = rup(o_r + tail.a_bytes, 16);
@@ -2313,30 +2363,20 @@ int pass_decode(ansx_ctx* c, int kind, int f, const ansx_container_header& H0, a
     u8* dplan = (u8*)c->rng_plan.p;
     HIPCHK(c, hipMemcpyAsync(dplan, hb, plan_bytes, hipMemcpyHostToDevice, s));
     u32* dflags = (u32*)dplan;
-    const ansx_batch_src* dS = (const ansx_batch_src*)(dplan + o_s);
-    const ansx_batch_blk* dB = (const ansx_batch_blk*)(dplan + o_b);
-
-    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
-    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
-    if ((rc = ensure(c, c->rng_list, 4 * wl + 64))) return rc;
-    u8* sub = (u8*)c->rng_cont.p;
-    u32* list = (u32*)c->rng_list.p;
-    const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
-    LAUNCH(c, "k_batch_index", k_batch_index, 1, 1024, 0, s, dS, dB, Ps.g, T, Hs, sub, cap_pay, dflags);
-    LAUNCH(c, "k_batch_copy", k_batch_copy, T, 256, 0, s, dS, dB, Ps.g, dl, sub, cap_pay, dflags);
-    // as in range_tail: the gather and the read-back of this pass's own flags ride on the decode's final read-back
-    u32* hflag = c->h_pin + 512;
-    *hflag = 0;
-    const std::function<int(const u32*)> gather = [&](const u32* gflags) -> int {
-        if ((rc = pass_gather(list, dplan + o_r, dplan + o_p, gflags))) return rc;
-        HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
+    const SubBuild build = [&](const Plan& Ps, const ansx_container_header& Hs, u8* sub) -> int {
+        const ansx_batch_src* dS = (const ansx_batch_src*)(dplan + o_s);
+        const ansx_batch_blk* dB = (const ansx_batch_blk*)(dplan + o_b);
+        const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
+        LAUNCH(c, "k_batch_index", k_batch_index, 1, 1024, 0, s, dS, dB, Ps.g, T, Hs, sub, cap_pay, dflags);
+        LAUNCH(c, "k_batch_copy", k_batch_copy, T, 256, 0, s, dS, dB, Ps.g, dl, sub, cap_pay, dflags);
         return ANSX_OK;
     };
-    Ps.bout = (const ansx_blk_out*)(dplan + o_o);
-    Ps.bout_ints = wl;
-    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, false, false, &gather);
-    if (*hflag) return ANSX_ERR_FORMAT;  // an index entry of a pass block was invalid
-    return rc;
+    const SubGather gather = [&](const u32* list, const u32* gflags) -> int {
+        return pass_gather(list, dplan + o_r, dplan + o_p, gflags);
+    };
+    // (any n that makes make_plan lay out exactly T blocks: the table says how long each is)
+    return decode_sub(c, kind, f, Hs, (u64)(T - 1) * H0.block_ints + O.back().n, T, cap_pay, wl, (const ansx_blk_out*)(dplan + o_o),
+        dflags, build, gather, s);
 }
 
 // One pass over containers ids[*ci..] of one geometry, from block *b0 of the first, up to PB blocks; moves *ci / *b0
@@ -2984,7 +3024,7 @@ int ansx_init(int device, ansx_ctx** out)
         delete c;
         return ANSX_ERR_HIP;
     }
-    if (hipHostMalloc((void**)&c->h_pin, 4096, hipHostMallocDefault) != hipSuccess) {
+    if (hipHostMalloc((void**)&c->pin, sizeof(PinPage), hipHostMallocDefault) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;
         return ANSX_ERR_HIP;
@@ -3090,8 +3130,7 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         c->t_hint.clear();
         c->wide_hint.clear();
         c->bat.ns_hint.clear(), c->bat.rf_hint.clear(), c->bat.t_hint.clear(), c->bat.wide_hint.clear(), c->bat.int_sparse_hint.clear();
-        c->hdr_cache.clear();
-        c->hdr_order.clear();
+        c->hdrs.clear();
     }
     else if (!strcmp(name, "ANSX_TEST_WIDE_AT")) {
         const u32 v = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 16u;
@@ -3143,7 +3182,7 @@ void ansx_destroy(ansx_ctx* c)
         (void)hipEventDestroy(r.e0);
         (void)hipEventDestroy(r.e1);
     }
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
+    if (c->pin) (void)hipHostFree(c->pin);
     if (c->rng_pin) (void)hipHostFree(c->rng_pin);
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -3377,7 +3416,7 @@ int ansx_merge_containers_dev(ansx_ctx* c, const uint8_t* const* d_parts, const 
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     // the part headers decide the layout: one small read-back
-    u8* hp = (u8*)c->h_pin + 64;  // 4096-byte pinned page: 63 headers fit behind the first 64 bytes
+    u8* hp = c->pin->part_hdr[0];
     std::vector<ansx_container_header> H((size_t)nparts);
     for (int i = 0; i < nparts; i += 63) {
         const int m = std::min(63, nparts - i);
@@ -3505,7 +3544,7 @@ int ansx_gather_containers(ansx_ctx* c, void* nccl_comm, int rank, int nranks, i
     int rc;
     if ((rc = ensure(c, c->misc, 64 + 8 * (3 * (size_t)ANSX_MERGE_MAX_PARTS + 2)))) return rc;
     u64* d_sizes = (u64*)((u8*)c->misc.p + 64);
-    u64* h_sizes = (u64*)((u8*)c->h_pin + 64);
+    u64* h_sizes = c->pin->rank_sizes;
     const u64 mine[2] = { (u64)bytes, (u64)slot_bytes };
     HIPCHK(c, hipMemcpyAsync(d_sizes + 2 * ANSX_MERGE_MAX_PARTS, mine, 16, hipMemcpyHostToDevice, s));
     if (R.AllGather(d_sizes + 2 * ANSX_MERGE_MAX_PARTS, d_sizes, 2, ncclUint64, comm, s) != ncclSuccess) return ANSX_ERR_HIP;
