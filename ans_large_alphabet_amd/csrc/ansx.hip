@@ -382,6 +382,10 @@ int make_plan(int kind, int f, size_t n, const ansx_opts* opts, Plan* P)
     }
     if (ck & 3u) return ANSX_ERR_ARG;
     if (ck >= bi) ck = 0;
+    // A block's worst-case stream (+ the 16 bytes of slack its scratch slot has) must stay below 2^31 bytes: the index
+    // checks refuse a longer one (index_entry_ok, k_validate_index), and ansx_blk::stream_bytes and the wide restart
+    // cursors are 32-bit.  Single-stream mode: the list is the block.
+    if (block_bound(kind, (u32)f, bi, pa) + 16 >= ((size_t)1 << 31)) return ANSX_ERR_ARG;
     size_t nblocks = (n + bi - 1) / bi;
     if (nblocks > 0x7FFFFFFFull) return ANSX_ERR_ARG;
     ansx_geo g;

@@ -335,7 +335,8 @@ struct ansx_blk_out {
 // stream length, so with frames up to 2^16 and streams below 16 MiB a restart point is 4 x 52 + 24 bits = 29 bytes
 // (container v3, the default): states 0 and 1 as one 104-bit little-endian integer in bytes 0..12 (state 0 in the low
 // 52 bits), states 2 and 3 likewise in bytes 13..25, the cursor in bytes 26..28.  Anything larger (ANSint frames,
-// huge blocks) keeps the v2 arrays -- u32 cursors, then 4 x u64 states -- and says so in the header (kind | 0x200).
+// geometries whose worst-case block stream + 16 reaches 2^24 bytes: encode_dev) keeps the v2 arrays -- u32 cursors, then
+// 4 x u64 states -- and says so in the header (kind | 0x200).
 #define ANSX_CK_RECORD 29u
 #define ANSX_CK_STATE_BITS 52u
 #define ANSX_CK_CURSOR_BITS 24u

@@ -99,7 +99,12 @@ typedef enum {
 #define ANSX_FLAG_COMPACT_ALPHABET 1u
 
 typedef struct {
-    uint32_t block_ints;    /* ints per independent reference stream; 0 = default             */
+    uint32_t block_ints;    /* ints per independent reference stream (a multiple of 4); 0 = default.  A block's
+                               worst-case stream, hdr + 8 + 4 NSP + 7 block_ints + 32 bytes (DESIGN.md section 3;
+                               + 16), must stay below 2^31: block indices, stream sizes and restart cursors are
+                               32-bit and the decoders refuse a longer block stream.  That is block_ints below
+                               about 306.7 million for the fold codecs (ANSX_SINGLE_STREAM: n); beyond it ANSX_ERR_ARG
+                               and ansx_bound() == 0 */
     uint32_t ckpt_interval; /* ints between decoder restart points (multiple of 4); 0 = default */
     uint32_t flags;         /* ANSX_FLAG_* bits                                                */
     uint32_t reserved;
@@ -113,8 +118,8 @@ typedef struct {
                                like every other field: a block with more is a format error)     */
     uint32_t kind;          /* ansx_kind | 0x100 if ANSX_FLAG_COMPACT_ALPHABET | 0x200 if the restart
                                points are in the wide form (u32 cursor + 4 x u64 states: ANSint, frames
-                               above 2^16, block streams of 16 MiB and more) instead of packed 29-byte
-                               records (4 x 52-bit states + 24-bit cursor)                       */
+                               above 2^16, block_ints whose worst-case block stream + 16 reaches 2^24
+                               bytes) instead of packed 29-byte records (4 x 52-bit states + 24-bit cursor) */
     uint32_t fidelity;
     uint64_t n;             /* total ints                                                       */
     uint32_t block_ints;

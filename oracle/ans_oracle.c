@@ -960,6 +960,8 @@ typedef struct {
     size_t n, block_ints, ckpt, nblocks;
     uint32_t *sizes, max_lg, max_ns;
     uint64_t *stream_hash, *ckpt_digest;
+    int compact;                /* blocks go through ans_oracle_pa_encode */
+    uint32_t *present, *hints;  /* optional, per block: symbols present in the model; the 8 parse hints */
     size_t next;
     int bad;
     pthread_mutex_t mu;
@@ -972,7 +974,7 @@ typedef struct {
 static void* blocks_worker(void* arg)
 {
     blocks_job* J = (blocks_job*)arg;
-    const size_t cap = ans_oracle_bound(J->kind, J->f, J->block_ints);
+    const size_t cap = ans_oracle_bound(J->kind, J->f, J->block_ints) + (J->compact ? 8 + 4 * J->block_ints + 8 : 0) + 16;
     const size_t nck_max = J->ckpt ? J->block_ints / J->ckpt + 1 : 1;
     uint8_t* out = (uint8_t*)malloc(cap);
     uint64_t* st = (uint64_t*)malloc(nck_max * 4 * sizeof(uint64_t));
@@ -989,10 +991,23 @@ static void* blocks_worker(void* arg)
             const size_t lo = bb * J->block_ints, cnt = J->n - lo < J->block_ints ? J->n - lo : J->block_ints;
             ans_oracle_info info;
             size_t nck = 0;
-            const size_t nb = ans_oracle_encode(J->kind, J->f, J->in + lo, cnt, out, cap, &info, J->ckpt, st, off, &nck);
+            ans_oracle_pa_info pinfo;
+            memset(&pinfo, 0, sizeof(pinfo));
+            const size_t nb = J->compact
+                ? ans_oracle_pa_encode(J->kind, J->f, J->in + lo, cnt, out, cap - 16, &pinfo, &info, J->ckpt, st, off, &nck)
+                : ans_oracle_encode(J->kind, J->f, J->in + lo, cnt, out, cap - 16, &info, J->ckpt, st, off, &nck);
             if (!nb) {
                 bad = 1;
                 break;
+            }
+            if (J->present) J->present[bb] = info.present_syms;
+            if (J->hints) {
+                /* (a compacted block of one distinct value has no codec stream: its hints are zero) */
+                memset(J->hints + 8 * bb, 0, 8 * sizeof(uint32_t));
+                if (!J->compact || pinfo.sigma != 1) {
+                    memset(out + nb, 0, 16); /* (the reader may look a few bytes past the prelude) */
+                    ans_oracle_prelude_hints(out + pinfo.header_bytes + info.header_bytes, J->hints + 8 * bb);
+                }
             }
             J->sizes[bb] = (uint32_t)nb;
             J->stream_hash[bb] = ans_oracle_hash(out, nb);
@@ -1049,9 +1064,18 @@ static void run_threads(blocks_job* J, int threads, void* (*fn)(void*))
 int ans_oracle_blocks_digest(int kind, uint32_t f, const uint32_t* in, size_t n, size_t block_ints, size_t ckpt_interval,
     int threads, uint32_t* sizes, uint64_t* stream_hash, uint64_t* ckpt_digest, uint32_t* max_log2_frame, uint32_t* max_nsyms)
 {
+    return ans_oracle_blocks_digest_ex(kind, f, in, n, block_ints, ckpt_interval, threads, 0, sizes, stream_hash, ckpt_digest,
+        NULL, NULL, max_log2_frame, max_nsyms);
+}
+
+int ans_oracle_blocks_digest_ex(int kind, uint32_t f, const uint32_t* in, size_t n, size_t block_ints, size_t ckpt_interval,
+    int threads, int compact, uint32_t* sizes, uint64_t* stream_hash, uint64_t* ckpt_digest, uint32_t* present, uint32_t* hints,
+    uint32_t* max_log2_frame, uint32_t* max_nsyms)
+{
     if (!n || !block_ints) return -1;
     blocks_job J;
     memset(&J, 0, sizeof(J));
+    J.compact = compact, J.present = present, J.hints = hints;
     J.kind = kind, J.f = f, J.in = in, J.n = n, J.block_ints = block_ints;
     J.ckpt = ckpt_interval >= block_ints ? 0 : ckpt_interval;
     J.nblocks = (n + block_ints - 1) / block_ints;

@@ -98,6 +98,12 @@ void ans_oracle_prelude_hints(const uint8_t* prelude, uint32_t* hints);
  * header's fields.  Returns 0, or -1 if a block failed. */
 int ans_oracle_blocks_digest(int kind, uint32_t f, const uint32_t* in, size_t n, size_t block_ints, size_t ckpt_interval,
     int threads, uint32_t* sizes, uint64_t* stream_hash, uint64_t* ckpt_digest, uint32_t* max_log2_frame, uint32_t* max_nsyms);
+/* The same with per-block alphabet compaction (compact != 0: every block is one ans_oracle_pa_encode call) and, where the
+ * pointers are not NULL, per block the symbols present in its model (present[b]) and its 8 parse hints (hints[8 b ...];
+ * zero for a compacted block of one distinct value, which has no codec stream). */
+int ans_oracle_blocks_digest_ex(int kind, uint32_t f, const uint32_t* in, size_t n, size_t block_ints, size_t ckpt_interval,
+    int threads, int compact, uint32_t* sizes, uint64_t* stream_hash, uint64_t* ckpt_digest, uint32_t* present, uint32_t* hints,
+    uint32_t* max_log2_frame, uint32_t* max_nsyms);
 /* FNV-1a (64 bit) over 8-byte little-endian words of the span, the tail bytes one by one */
 uint64_t ans_oracle_hash(const uint8_t* p, size_t n);
 /* the same over nspans spans [offs[i], offs[i + 1]) of buf, on `threads` host threads */

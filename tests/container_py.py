@@ -16,6 +16,52 @@ def nseg(nb, ckpt):
     return (nfull + ckpt - 1) // ckpt
 
 
+NSP = {0: lambda f: 1 << (f + 9), 1: lambda f: 1 << (f + 9), 2: lambda f: 2048, 3: lambda f: 16384}  # symbol-row stride per codec
+
+
+def block_bound(kind, f, block, compact=False):
+    """Worst-case bytes of one block stream: hdr + 8 + 4 NSP + 7 block + 32, where ANSrfold's hdr is
+    its most-frequent table, 4 + 4 T with T = 2^(f + 7), and compaction adds the alphabet header, 8 + 4 block + 8."""
+    k = kind & 0xFF
+    hdr = 4 + 4 * (1 << (f + 7)) if k == 1 else 0
+    if compact:
+        hdr += 8 + 4 * block + 8
+    return hdr + 8 + 4 * NSP[k](f) + 7 * block + 32
+
+
+def wide_by_geometry(kind, f, block, compact=False):
+    """The cursor rule: a restart cursor has 24 bits in the packed form, so a geometry whose worst-case block stream
+    (+ 16 bytes of slack) reaches 2^24 takes the wide form -- decided from block_ints alone, never from the streams."""
+    return block_bound(kind, f, block, compact) + 16 >= 1 << 24
+
+
+def scratch_stride(kind, f, block, compact=False):
+    """Bytes between two blocks' slots in the encoder's stream scratch: the bound + 16, rounded up to 256."""
+    return (block_bound(kind, f, block, compact) + 16 + 255) // 256 * 256
+
+
+def first_block_ints(reached, multiple=4):
+    """The smallest block_ints (a multiple of `multiple`) at which the monotone predicate reached(block_ints) holds."""
+    lo, hi = 0, 1 << 31
+    while hi - lo > multiple:
+        mid = (lo + hi) // 2 // multiple * multiple
+        lo, hi = (lo, mid) if reached(mid) else (mid, hi)
+    return hi
+
+
+def layout(nblocks, nckf, wide):
+    """Section offsets of a container: (index, restart cursors / records, wide states, parse hints, payload)."""
+    index_off = 64
+    ckoff_off = index_off + 8 * (nblocks + 1)
+    if wide:
+        ckstate_off = (ckoff_off + 4 * nblocks * nckf + 7) // 8 * 8
+        hint_off = (ckstate_off + 32 * nblocks * nckf + 15) // 16 * 16
+    else:
+        ckstate_off = ckoff_off
+        hint_off = (ckoff_off + 29 * nblocks * nckf + 15) // 16 * 16
+    return index_off, ckoff_off, ckstate_off, hint_off, hint_off + 32 * nblocks
+
+
 def pack_restart_points(states, offs):
     """(n, 4) u64 states + n u32 cursors -> n records of 29 bytes: states 0, 1 as one 104-bit little-endian integer
     (state 0 in the low 52 bits), states 2, 3 likewise, then the cursor in 24 bits."""
@@ -29,7 +75,8 @@ def pack_restart_points(states, offs):
 
 
 def build_container(kind, f, data, block, ckpt, wide=None):
-    """wide: restart-point format; None = what the library picks (wide for ANSint and once a frame exceeds 2^16)."""
+    """wide: restart-point format; None = what the library picks: wide for ANSint, for a geometry whose worst-case block
+    stream reaches 2^24 bytes (wide_by_geometry) and once a frame exceeds 2^16."""
     data = np.ascontiguousarray(data, dtype=np.uint32)
     n = data.size
     if ckpt >= block:
@@ -54,15 +101,8 @@ def build_container(kind, f, data, block, ckpt, wide=None):
         hints = [np.zeros(8, dtype=np.uint32) for _ in hints]
         maxns = maxsig
     if wide is None:
-        wide = (kind & 0xFF) == 3 or maxlg > 16
-    index_off = 64
-    ckoff_off = index_off + 8 * (nblocks + 1)
-    if wide:
-        ckstate_off = (ckoff_off + 4 * nblocks * nckf + 7) // 8 * 8
-        hint_off = (ckstate_off + 32 * nblocks * nckf + 15) // 16 * 16
-    else:
-        hint_off = (ckoff_off + 29 * nblocks * nckf + 15) // 16 * 16
-    payload_off = hint_off + 32 * nblocks
+        wide = (kind & 0xFF) == 3 or wide_by_geometry(kind, f, block, bool(kind & 0x100)) or maxlg > 16
+    index_off, ckoff_off, ckstate_off, hint_off, payload_off = layout(nblocks, nckf, wide)
     sizes = np.array([s.size for s in streams], dtype=np.uint64)
     boff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
     payload = np.concatenate(streams)

@@ -87,6 +87,9 @@ def _load_oracle():
     lib.ans_oracle_blocks_digest.restype = C.c_int
     lib.ans_oracle_blocks_digest.argtypes = [C.c_int, C.c_uint32, _u32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _u32p, _u64p, _u64p,
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.ans_oracle_blocks_digest_ex.restype = C.c_int
+    lib.ans_oracle_blocks_digest_ex.argtypes = [C.c_int, C.c_uint32, _u32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u32p, _u64p,
+                                                _u64p, _u32p, _u32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.ans_oracle_hash_spans.restype = None
     lib.ans_oracle_hash_spans.argtypes = [_u8p, _u64p, C.c_size_t, C.c_int, _u64p]
     return lib
@@ -193,6 +196,22 @@ def oracle_blocks_digest(kind, f, data, block_ints, ckpt_interval, threads=None)
     if rc != 0:
         raise RuntimeError("oracle block pass failed")
     return sizes, sh, cd, lg.value, ns.value
+
+
+def oracle_blocks_full(kind, f, data, block_ints, ckpt_interval, compact=False, threads=None):
+    """oracle_blocks_digest plus what the container's header and index say per block: dict(sizes, hash, ckpt, present
+    u32[nb] -- the symbols present in each block's model --, hints u32[nb, 8], max_lg, max_ns); compact: every block
+    through the compaction layer (ans_oracle_pa_encode)."""
+    data = np.ascontiguousarray(data, dtype=np.uint32)
+    nb = (data.size + block_ints - 1) // block_ints
+    sizes, present, hints = np.zeros(nb, dtype=np.uint32), np.zeros(nb, dtype=np.uint32), np.zeros(8 * nb, dtype=np.uint32)
+    sh, cd = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+    lg, ns = C.c_uint32(0), C.c_uint32(0)
+    rc = oracle().ans_oracle_blocks_digest_ex(kind, f, data, data.size, block_ints, ckpt_interval, threads or host_threads(), int(compact),
+                                              sizes, sh, cd, present, hints, C.byref(lg), C.byref(ns))
+    if rc != 0:
+        raise RuntimeError("oracle block pass failed")
+    return {"sizes": sizes, "hash": sh, "ckpt": cd, "present": present, "hints": hints.reshape(nb, 8), "max_lg": lg.value, "max_ns": ns.value}
 
 
 def hash_spans(buf, offs, threads=None):
