@@ -28,7 +28,8 @@ EXPORTS = [
     "ansx_generate_dev", "ansx_generate_host", "ansx_last_encode_stats", "ansx_merge_containers_dev",
     "ansx_zipf_from_uniform", "ansx_gather_containers", "ansx_last_gather_ranks", "ansx_decode_ranges_dev",
     "ansx_decode_device_ranges_dev", "ansx_decode_batch_dev", "ansx_encode_batch_dev",
-    "ansx_decode_batch_ranges_dev",
+    "ansx_decode_batch_ranges_dev", "ansx_decode_sums_dev", "ansx_decode_batch_sums_dev", "ansx_encode_gaps_dev",
+    "ansx_encode_batch_gaps_dev",
 ]
 
 
@@ -130,6 +131,12 @@ def lib():
     L.ansx_encode_batch_dev.restype = C.c_int
     L.ansx_encode_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz),
                                         C.POINTER(Opts), vp]
+    # running sums and gaps: each takes the arguments of its counterpart
+    for name, like in (("ansx_decode_sums_dev", L.ansx_decode_dev), ("ansx_decode_batch_sums_dev", L.ansx_decode_batch_dev),
+                       ("ansx_encode_gaps_dev", L.ansx_encode_dev), ("ansx_encode_batch_gaps_dev", L.ansx_encode_batch_dev)):
+        fn = getattr(L, name)
+        fn.restype = C.c_int
+        fn.argtypes = list(like.argtypes)
     L.ansx_container_info.restype = C.c_int
     L.ansx_container_info.argtypes = [vp, sz, C.POINTER(ContainerHeader)]
     L.ansx_profile_enable.restype = C.c_int

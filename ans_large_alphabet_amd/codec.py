@@ -270,6 +270,74 @@ class _Codec:
             raise err
         return out_offsets, out_bytes
 
+    # ---- docids: running sums behind the decoders, gaps in front of the encoders (include/ansx.h)
+    def decode_sums_dev(self, in_ptr, in_bytes, out_ptr, n, stream=None):
+        """decode_dev, then the n ints at out_ptr (4-byte aligned) are replaced by their inclusive running sums: gaps
+        in, docids out.  ERR_DOMAIN if a running sum exceeds 2^32 - 1."""
+        st = L.lib().ansx_decode_sums_dev(self._ctx().handle, self.KIND, self.f, in_ptr, in_bytes, out_ptr, n,
+                                          C.byref(self.opts), stream)
+        if st != L.OK:
+            raise L.AnsxError(st, self.name() + ".decode_sums_dev")
+
+    def decode_batch_sums_dev(self, in_ptrs, in_bytes, out_ptr, out_capacity, stream=None):
+        """decode_batch_dev, then every list out[offsets[i] : offsets[i + 1]] is replaced by its own running sums.
+        Arguments, return value and error attributes are those of decode_batch_dev; ERR_DOMAIN (the sum of a list
+        exceeds 2^32 - 1) carries .index, the first such list."""
+        ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
+        if ptrs.size != sizes.size:
+            raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
+        count = ptrs.size
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        bad = C.c_size_t(count)
+        st = L.lib().ansx_decode_batch_sums_dev(self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if count else None,
+                                                sizes.ctypes.data if count else None, count, out_ptr, int(out_capacity),
+                                                offsets.ctypes.data, C.byref(total), C.byref(bad), stream)
+        if st == L.ERR_CAPACITY and out_ptr is None and int(out_capacity) == 0:
+            return offsets
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".decode_batch_sums_dev")
+            if st == L.ERR_CAPACITY:
+                err.needed = int(total.value)
+                err.offsets = offsets
+            if st in (L.ERR_FORMAT, L.ERR_DOMAIN):
+                err.index = int(bad.value) if bad.value < count else None
+            raise err
+        return offsets
+
+    def encode_gaps_dev(self, in_ptr, n, out_ptr, out_capacity, stream=None):
+        """encode_dev of the gaps of the n non-decreasing ids at in_ptr (which is only read) -> bytes written.
+        ERR_DOMAIN if an id is smaller than the one before it."""
+        nb = C.c_size_t(0)
+        st = L.lib().ansx_encode_gaps_dev(self._ctx().handle, self.KIND, self.f, in_ptr, n, out_ptr,
+                                          out_capacity, C.byref(nb), C.byref(self.opts), stream)
+        if st != L.OK:
+            raise L.AnsxError(st, self.name() + ".encode_gaps_dev")
+        return nb.value
+
+    def encode_batch_gaps_dev(self, in_ptr, offsets, out_ptr, out_capacity, stream=None):
+        """encode_batch_dev of the gaps of every list of non-decreasing ids (a list's first gap is its first id).
+        Arguments, return value and .index are those of encode_batch_dev; ERR_DOMAIN for a decrease carries .index,
+        the first list that holds one."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise ValueError("offsets needs at least one entry (count + 1)")
+        count = offsets.size - 1
+        out_offsets = np.zeros(count + 1, dtype=np.uint64)
+        out_bytes = np.zeros(count, dtype=np.uint64)
+        total = C.c_size_t(0)
+        bad = C.c_size_t(count)
+        st = L.lib().ansx_encode_batch_gaps_dev(self._ctx().handle, self.KIND, self.f, in_ptr, offsets.ctypes.data, count,
+                                                out_ptr, int(out_capacity), out_offsets.ctypes.data,
+                                                out_bytes.ctypes.data if count else None, C.byref(total), C.byref(bad),
+                                                C.byref(self.opts), stream)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".encode_batch_gaps_dev")
+            err.index = int(bad.value) if bad.value < count else None
+            raise err
+        return out_offsets, out_bytes
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

@@ -31,6 +31,7 @@
 #include "ansx_batch.h"
 #include "ansx_batchranges.h"
 #include "ansx_encbatch.h"
+#include "ansx_sums.h"
 
 namespace {
 
@@ -129,6 +130,7 @@ struct ansx_ctx {
     DevBuf rng_dev;                       // ansx_decode_device_ranges_dev: the device planner's workspace
     DevBuf bat_hdr;                       // ansx_decode_batch_dev: input addresses and headers of the batch
     DevBuf enb_plan, enb_wc;              // ansx_encode_batch_dev: a pass's plan and results; its restart points and hints (work area)
+    DevBuf sums_plan, sums_ints;          // running sums and gaps: flag word + list starts + tile aggregates and carries; the gaps of a call (4 bytes per int)
     u8* rng_pin = nullptr;                // ... and the pinned host image of rng_plan (an asynchronous upload from
     size_t rng_pin_cap = 0;               //     pageable memory is staged by the runtime: 0.666 -> 0.618 ms at 4096 ranges)
     PinPage* pin = nullptr;
@@ -2972,6 +2974,122 @@ int encode_batch(ansx_ctx* c, const Plan& P0, const ansx_opts* opts, const u32* 
     return ANSX_OK;
 }
 
+// --------------------------------------------------------------------------------- running sums and gaps
+// ansx_decode_sums_dev / ansx_decode_batch_sums_dev / ansx_encode_gaps_dev / ansx_encode_batch_gaps_dev (DESIGN.md
+// section 3e): the ordinary decode, then k_sums_reduce -> k_sums_carry -> k_sums_apply over the flat output; k_gaps into
+// workspace, then the ordinary encode.  A single list is a batch of one.
+
+struct SumsPlan {
+    u32* flag;        // ANSX_SS_NONE, or the first list at fault
+    const u64* offs;  // the list starts, relative to the first
+    u64* agg;         // one aggregate per tile
+    u64* carry;       // ... and the carry into it
+    u32 head;         // ints between the array and the 16-byte boundary below it
+    u32 ntiles;
+};
+
+// The device side of a call over the n ints at `addr` in `count` lists, offs[0 .. count] (host, any base): one upload
+int sums_prepare(ansx_ctx* c, uintptr_t addr, u64 n, const u64* offs, size_t count, hipStream_t s, SumsPlan* S)
+{
+    int rc;
+    S->head = (u32)(addr >> 2) & 3u;
+    const u64 ntiles = (n + S->head + ANSX_SS_TILE - 1) / ANSX_SS_TILE;
+    if (ntiles > 0x7FFFFFFFull) return ANSX_ERR_ARG;
+    S->ntiles = (u32)ntiles;
+    const size_t o_o = 16, o_a = rup(o_o + 8 * (count + 1), 16);
+    if ((rc = ensure_pin(c, o_a))) return rc;
+    if ((rc = ensure(c, c->sums_plan, o_a + 16 * (size_t)ntiles))) return rc;
+    u32* hf = (u32*)c->rng_pin;  // (no copy out of it is pending: every call that uses it ends in a synchronisation)
+    hf[0] = ANSX_SS_NONE, hf[1] = 0, hf[2] = 0, hf[3] = 0;
+    u64* ho = (u64*)(c->rng_pin + o_o);
+    for (size_t i = 0; i <= count; i++) ho[i] = offs[i] - offs[0];
+    u8* d = (u8*)c->sums_plan.p;
+    HIPCHK(c, hipMemcpyAsync(d, c->rng_pin, o_a, hipMemcpyHostToDevice, s));
+    S->flag = (u32*)d;
+    S->offs = (const u64*)(d + o_o);
+    S->agg = (u64*)(d + o_a);
+    S->carry = S->agg + ntiles;
+    return ANSX_OK;
+}
+
+// the flag word back: ANSX_ERR_DOMAIN and the list when a kernel named one
+int sums_finish(ansx_ctx* c, const SumsPlan& S, size_t* bad_index, hipStream_t s)
+{
+    HIPCHK(c, hipMemcpyAsync(c->pin->flags, S.flag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (c->pin->flags[0] == ANSX_SS_NONE) return ANSX_OK;
+    if (bad_index) *bad_index = c->pin->flags[0];
+    return ANSX_ERR_DOMAIN;
+}
+
+// d[offs[i] - offs[0] .. offs[i + 1] - offs[0]) -> its inclusive running sums, for every list, in place
+int sums_run(ansx_ctx* c, u32* d, u64 n, const u64* offs, size_t count, size_t* bad_index, hipStream_t s)
+{
+    int rc;
+    SumsPlan S;
+    if ((rc = sums_prepare(c, (uintptr_t)d, n, offs, count, s, &S))) return rc;
+    u32* base = (u32*)((uintptr_t)d & ~(uintptr_t)15);
+    if (S.ntiles > 1) {
+        LAUNCH(c, "k_sums_reduce", k_sums_reduce, S.ntiles, ANSX_SS_NT, 0, s, (const u32*)base, S.head, n, S.offs, (u32)count, S.agg);
+        LAUNCH(c, "k_sums_carry", k_sums_carry, 1, ANSX_SS_SCAN_NT, 0, s, (const u64*)S.agg, S.carry, (u64)S.ntiles);
+    } else {
+        // one tile: nothing is carried into it -- the zero behind the flag word; its aggregate is not looked at (a list
+        // starts at its first int)
+        S.carry = (u64*)(S.flag + 2);
+    }
+    LAUNCH(c, "k_sums_apply", k_sums_apply, S.ntiles, ANSX_SS_NT, 0, s, base, S.head, n, S.offs, (u32)count, (const u64*)S.agg,
+        (const u64*)S.carry, S.flag);
+    return sums_finish(c, S, bad_index, s);
+}
+
+// The gaps of the lists of d_in (offs as for sums_run) -> *gaps, workspace with d_in's alignment; d_in is only read
+int gaps_run(ansx_ctx* c, const u32* d_in, u64 n, const u64* offs, size_t count, const u32** gaps, size_t* bad_index,
+    hipStream_t s)
+{
+    int rc;
+    SumsPlan S;
+    if ((rc = sums_prepare(c, (uintptr_t)d_in, n, offs, count, s, &S))) return rc;
+    if ((rc = ensure(c, c->sums_ints, 4 * ((size_t)n + 4)))) return rc;
+    const u32* base = (const u32*)((uintptr_t)d_in & ~(uintptr_t)15);
+    u32* base_out = (u32*)c->sums_ints.p;
+    LAUNCH(c, "k_gaps", k_gaps, S.ntiles, ANSX_SS_NT, 0, s, base, base_out, S.head, n, S.offs, (u32)count, S.flag);
+    *gaps = base_out + S.head;
+    return sums_finish(c, S, bad_index, s);
+}
+
+// the argument checks of ansx_decode_batch_dev, everything it decides before the context is touched
+int decode_batch_args(const ansx_ctx* c, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count, const uint32_t* d_out,
+    size_t out_capacity_ints)
+{
+    if (!c || count > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (count > 0 && (!d_ins || !in_bytes)) return ANSX_ERR_ARG;
+    if ((!d_out && out_capacity_ints > 0) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    for (size_t i = 0; i < count; i++)
+        if (!d_ins[i] || ((uintptr_t)d_ins[i] & 15u)) return ANSX_ERR_ARG;
+    return ANSX_OK;
+}
+
+// ... and those of ansx_encode_batch_dev
+int encode_batch_args(const ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,
+    const uint8_t* d_out, size_t* bad_index, const ansx_opts* opts, Plan* P0)
+{
+    if (!c || count > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (count > 0 && (!d_in || !offsets || !d_out)) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_in & 3u)) return ANSX_ERR_ARG;
+    if (opts && opts->block_ints == ANSX_SINGLE_STREAM) return ANSX_ERR_ARG;  // (a batch yields containers)
+    int rc = make_plan(kind, f, 1, opts, P0);  // kind, fidelity and options, as for any list
+    if (rc) return rc;
+    for (size_t i = 0; i < count; i++) {
+        Plan P;
+        if (offsets[i + 1] < offsets[i]) return ANSX_ERR_ARG;
+        if (offsets[i + 1] == offsets[i] || make_plan(kind, f, (size_t)(offsets[i + 1] - offsets[i]), opts, &P)) {
+            if (bad_index) *bad_index = i;  // an empty list (or one no container can hold), as ansx_encode_dev refuses n == 0
+            return ANSX_ERR_ARG;
+        }
+    }
+    return ANSX_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -3177,7 +3295,7 @@ void ansx_destroy(ansx_ctx* c)
     DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->log2lut, &c->pa_alpha, &c->pa_info, &c->pairs, &c->lg2i, &c->sizes, &c->nearlist, &c->force, &c->geo_big,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints };
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& kv : c->geo)
@@ -3364,6 +3482,103 @@ int ansx_encode_batch_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, co
     try {
         return encode_batch(c, P0, opts, d_in, (const u64*)offsets, count, d_out, out_capacity, (u64*)out_offsets,
             (u64*)out_bytes, total_bytes, bad_index, s);
+    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge batch)
+        c->last_hip = (int)hipErrorOutOfMemory;
+        return ANSX_ERR_HIP;
+    }
+}
+
+int ansx_decode_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, uint32_t* d_out, size_t n,
+    const ansx_opts* opts, void* stream)
+{
+    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    Plan P;
+    int rc = make_plan(kind, f, n, opts, &P);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    // the decoders store 16 bytes at a time: an output that is not aligned for them is decoded in workspace and copied
+    u32* dec = d_out;
+    if ((uintptr_t)d_out & 15u) {
+        if ((rc = ensure(c, c->sums_ints, 4 * (n + 4)))) return rc;
+        dec = (u32*)c->sums_ints.p;
+    }
+    if ((rc = decode_dev(c, P, d_in, in_bytes, dec, s))) return rc;
+    if (dec != d_out) HIPCHK(c, hipMemcpyAsync(d_out, dec, 4 * n, hipMemcpyDeviceToDevice, s));
+    const u64 offs[2] = { 0, (u64)n };
+    return sums_run(c, d_out, (u64)n, offs, 1, nullptr, s);
+}
+
+int ansx_decode_batch_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count,
+    uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_index, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    int rc = decode_batch_args(c, d_ins, in_bytes, count, d_out, out_capacity_ints);
+    if (rc) return rc;
+    if (count == 0) {
+        if (offsets) offsets[0] = 0;
+        if (total_ints) *total_ints = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    try {
+        std::vector<u64> off(count + 1);  // (the scan needs the offsets whether the caller asked for them or not)
+        u64 total = 0;
+        rc = decode_batch(c, kind, f, d_ins, in_bytes, count, d_out, out_capacity_ints, off.data(), &total, bad_index, s);
+        if (rc == ANSX_OK || rc == ANSX_ERR_CAPACITY) {
+            if (offsets) memcpy(offsets, off.data(), 8 * (count + 1));
+            if (total_ints) *total_ints = total;
+        }
+        if (rc || total == 0) return rc;
+        // every pass of every geometry group is through: one scan over the whole output
+        return sums_run(c, d_out, total, off.data(), count, bad_index, s);
+    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge batch)
+        c->last_hip = (int)hipErrorOutOfMemory;
+        return ANSX_ERR_HIP;
+    }
+}
+
+int ansx_encode_gaps_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, size_t n, uint8_t* d_out, size_t cap,
+    size_t* out_bytes, const ansx_opts* opts, void* stream)
+{
+    if (!c || !d_in || !d_out || !out_bytes) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_in & 3u)) return ANSX_ERR_ARG;
+    Plan P;
+    int rc = make_plan(kind, f, n, opts, &P);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const u64 offs[2] = { 0, (u64)n };
+    const u32* gaps = nullptr;
+    if ((rc = gaps_run(c, d_in, (u64)n, offs, 1, &gaps, nullptr, s))) return rc;
+    return encode_dev(c, P, gaps, d_out, cap, out_bytes, s);
+}
+
+int ansx_encode_batch_gaps_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,
+    uint8_t* d_out, size_t out_capacity, uint64_t* out_offsets, uint64_t* out_bytes, size_t* total_bytes, size_t* bad_index,
+    const ansx_opts* opts, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    Plan P0;
+    int rc = encode_batch_args(c, kind, f, d_in, offsets, count, d_out, bad_index, opts, &P0);
+    if (rc) return rc;
+    if (count == 0) {
+        if (out_offsets) out_offsets[0] = 0;
+        if (total_bytes) *total_bytes = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    try {
+        const u32* gaps = nullptr;
+        if ((rc = gaps_run(c, d_in + offsets[0], offsets[count] - offsets[0], (const u64*)offsets, count, &gaps, bad_index, s)))
+            return rc;
+        std::vector<u64> off(count + 1);  // the lists' places in the workspace
+        for (size_t i = 0; i <= count; i++) off[i] = offsets[i] - offsets[0];
+        return encode_batch(c, P0, opts, gaps, off.data(), count, d_out, out_capacity, (u64*)out_offsets, (u64*)out_bytes,
+            total_bytes, bad_index, s);
     } catch (const std::bad_alloc&) {  // (the host's arrays of a huge batch)
         c->last_hip = (int)hipErrorOutOfMemory;
         return ANSX_ERR_HIP;
@@ -3648,7 +3863,7 @@ size_t ansx_workspace_bytes(const ansx_ctx* c)
     const DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->pa_alpha, &c->pa_info, &c->pairs, &c->sizes,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints };
     size_t t = 0;
     for (const DevBuf* b : bufs) t += b->cap;
     return t;

@@ -322,6 +322,53 @@ int ansx_encode_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t*
     uint8_t* d_out, size_t out_capacity, uint64_t* out_offsets, uint64_t* out_bytes, size_t* total_bytes, size_t* bad_index,
     const ansx_opts* opts, void* stream);
 
+/* Docids: running sums and gaps.  A posting list is stored as the gaps between its sorted
+ * document ids and read as the ids; these four calls are the two ends.  For a list x the sums are
+ * s[i] = x[0] + ... + x[i] (inclusive); for a list d the gaps are g[0] = d[0], g[i] = d[i] - d[i - 1]; every list of a
+ * batch starts afresh; decode_sums(encode_gaps(d)) == d for every non-decreasing d whose gaps the codec accepts.  Whole
+ * containers and whole batches only (running sums of RANGES would need per-block bases in the container), 32-bit
+ * outputs, no change of the container format: the bytes are those of the ordinary calls on the gaps.
+ *
+ * ansx_decode_sums_dev: the arguments and the behaviour of ansx_decode_dev -- the accepted forms, ANSX_SINGLE_STREAM
+ * included, the remembered headers, the hints, the errors -- then d_out[0 .. n) is replaced in place by its running
+ * sums (three kernels over tiles of the output: per-tile aggregates, one workgroup that scans them, per-tile scan and
+ * store; partial sums are carried in 64 bits).  ANSX_ERR_DOMAIN if any running sum exceeds 2^32 - 1, found on the device
+ * and read back before the call returns; d_out is then unspecified.  Nothing is written outside d_out[0 .. n).  Unlike
+ * ansx_decode_dev, d_out needs only 4-byte alignment (an output that is not 16-byte aligned is decoded in workspace, 4
+ * bytes per int, and copied). */
+int ansx_decode_sums_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in, size_t in_bytes,
+    uint32_t* d_out, size_t n, const ansx_opts* opts, void* stream);
+
+/* ansx_decode_batch_sums_dev: the arguments and the behaviour of ansx_decode_batch_dev -- the same checks in the same
+ * order, the same offsets, the same size query, no trace in the context -- then every list
+ * d_out[offsets[i] .. offsets[i + 1]) is replaced by its own running sums: one segmented scan over the whole output,
+ * after the last pass of the last geometry group, that restarts at every list.  ANSX_ERR_DOMAIN when the sum of some list
+ * exceeds 2^32 - 1; *bad_index (optional) is then the first such list in batch order and d_out is unspecified.  A format
+ * error found on the device is reported as by ansx_decode_batch_dev, and nothing is scanned. */
+int ansx_decode_batch_sums_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    size_t count, uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_index,
+    void* stream);
+
+/* ansx_encode_gaps_dev: the arguments of ansx_encode_dev, d_in holding n non-decreasing ids.  The gaps are written to
+ * workspace of the context (4 bytes per int, grow-only, counted by ansx_workspace_bytes) and encoded by the ordinary
+ * path: the output bytes, *out_bytes, ansx_last_encode_stats and what the context learns are exactly those of
+ * ansx_encode_dev on the gaps; d_in is not modified.  ANSX_ERR_DOMAIN if an id is smaller than the one before it -- decided
+ * by comparing the neighbours, not by the wrapped difference, which can come out below 2^30 -- and nothing is encoded
+ * then; the gaps themselves pass the encoder's own domain checks like any input (a gap of 2^30 or more:
+ * ANSX_ERR_DOMAIN). */
+int ansx_encode_gaps_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t* d_in, size_t n, uint8_t* d_out,
+    size_t out_capacity, size_t* out_bytes, const ansx_opts* opts, void* stream);
+
+/* ansx_encode_batch_gaps_dev: the arguments of ansx_encode_batch_dev, list i holding non-decreasing ids; its first gap
+ * is its own first id, so a list may start below the end of the list before it.  The argument errors decided before the
+ * context is touched are those of ansx_encode_batch_dev, *bad_index included.  ANSX_ERR_DOMAIN with *bad_index = the
+ * first list that holds a decrease, nothing encoded; otherwise the call is byte for byte ansx_encode_batch_dev on the
+ * gaps, its errors, *bad_index and its promise to leave no trace included.  Workspace: 4 bytes per int of the BATCH
+ * for the gaps -- the one place where this call is not bounded by a pass. */
+int ansx_encode_batch_gaps_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t* d_in, const uint64_t* offsets,
+    size_t count, uint8_t* d_out, size_t out_capacity, uint64_t* out_offsets, uint64_t* out_bytes, size_t* total_bytes,
+    size_t* bad_index, const ansx_opts* opts, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
