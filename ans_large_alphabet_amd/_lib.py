@@ -29,7 +29,8 @@ EXPORTS = [
     "ansx_zipf_from_uniform", "ansx_gather_containers", "ansx_last_gather_ranks", "ansx_decode_ranges_dev",
     "ansx_decode_device_ranges_dev", "ansx_decode_batch_dev", "ansx_encode_batch_dev",
     "ansx_decode_batch_ranges_dev", "ansx_decode_sums_dev", "ansx_decode_batch_sums_dev", "ansx_encode_gaps_dev",
-    "ansx_encode_batch_gaps_dev",
+    "ansx_encode_batch_gaps_dev", "ansx_block_bases_dev", "ansx_encode_gaps_bases_dev", "ansx_decode_ranges_sums_dev",
+    "ansx_decode_device_ranges_sums_dev",
 ]
 
 
@@ -137,6 +138,16 @@ def lib():
         fn = getattr(L, name)
         fn.restype = C.c_int
         fn.argtypes = list(like.argtypes)
+    # docids of ranges: block bases beside the container
+    L.ansx_block_bases_dev.restype = C.c_int
+    L.ansx_block_bases_dev.argtypes = [vp, C.c_int, C.c_int, vp, sz, vp, sz, C.POINTER(sz), vp]
+    L.ansx_encode_gaps_bases_dev.restype = C.c_int
+    L.ansx_encode_gaps_bases_dev.argtypes = list(L.ansx_encode_dev.argtypes[:-1]) + [vp, sz, C.POINTER(sz), vp]
+    L.ansx_decode_ranges_sums_dev.restype = C.c_int
+    L.ansx_decode_ranges_sums_dev.argtypes = [vp, C.c_int, C.c_int, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp]
+    L.ansx_decode_device_ranges_sums_dev.restype = C.c_int
+    L.ansx_decode_device_ranges_sums_dev.argtypes = [vp, C.c_int, C.c_int, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp,
+                                                     C.POINTER(C.c_uint64), vp]
     L.ansx_container_info.restype = C.c_int
     L.ansx_container_info.argtypes = [vp, sz, C.POINTER(ContainerHeader)]
     L.ansx_profile_enable.restype = C.c_int

@@ -338,6 +338,72 @@ class _Codec:
             raise err
         return out_offsets, out_bytes
 
+    # ---- docids of ranges: block bases beside the container (include/ansx.h)
+    def block_bases_dev(self, in_ptr, in_bytes, bases_ptr, capacity, stream=None):
+        """The block bases of the container at in_ptr -> the nblocks + 1 uint32 at bases_ptr (capacity entries):
+        bases[b] is the sum of the ints in front of block b.  Returns nbases = nblocks + 1.  bases_ptr=None with
+        capacity=0 is a size query: nothing is decoded.  ERR_CAPACITY raises AnsxError with .needed = nbases;
+        ERR_DOMAIN if the list sums to more than 2^32 - 1."""
+        nb = C.c_size_t(0)
+        st = L.lib().ansx_block_bases_dev(self._ctx().handle, self.KIND, self.f, in_ptr, int(in_bytes), bases_ptr,
+                                          int(capacity), C.byref(nb), stream)
+        if st == L.ERR_CAPACITY and bases_ptr is None and int(capacity) == 0:
+            return int(nb.value)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".block_bases_dev")
+            if st == L.ERR_CAPACITY:
+                err.needed = int(nb.value)
+            raise err
+        return int(nb.value)
+
+    def encode_gaps_bases_dev(self, in_ptr, n, out_ptr, out_capacity, bases_ptr, bases_capacity, stream=None):
+        """encode_gaps_dev that also writes the block bases of its container to bases_ptr (bases_capacity uint32
+        entries) -> (bytes written, nbases).  A bases_capacity below nblocks + 1 raises AnsxError(ERR_CAPACITY) with
+        .needed = nbases before anything is encoded."""
+        nb, nbases = C.c_size_t(0), C.c_size_t(0)
+        st = L.lib().ansx_encode_gaps_bases_dev(self._ctx().handle, self.KIND, self.f, in_ptr, n, out_ptr, out_capacity,
+                                                C.byref(nb), C.byref(self.opts), bases_ptr, int(bases_capacity),
+                                                C.byref(nbases), stream)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".encode_gaps_bases_dev")
+            if st == L.ERR_CAPACITY and nbases.value > int(bases_capacity):
+                err.needed = int(nbases.value)
+            raise err
+        return nb.value, int(nbases.value)
+
+    def decode_ranges_sums_dev(self, in_ptr, in_bytes, bases_ptr, nbases, first, count, out_ptr, out_capacity, stream=None):
+        """decode_ranges_dev returning docids: range i is sums[first[i] : first[i] + count[i]] of the container's
+        running sums, computed from the touched blocks and their entries of the nbases block bases at bases_ptr.
+        ERR_FORMAT if the bases of a touched block are not this container's.  Returns sum(count)."""
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+        count = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
+        if first.size != count.size:
+            raise ValueError("first and count differ in length (%d, %d)" % (first.size, count.size))
+        st = L.lib().ansx_decode_ranges_sums_dev(self._ctx().handle, self.KIND, self.f, in_ptr, in_bytes, bases_ptr,
+                                                 int(nbases), first.ctypes.data, count.ctypes.data, first.size, out_ptr,
+                                                 out_capacity, stream)
+        if st != L.OK:
+            raise L.AnsxError(st, self.name() + ".decode_ranges_sums_dev")
+        return int(count.sum(dtype=np.uint64))
+
+    def decode_device_ranges_sums_dev(self, in_ptr, in_bytes, bases_ptr, nbases, first_ptr, count_ptr, nranges, out_ptr,
+                                      out_capacity, offsets_ptr=None, stream=None):
+        """decode_device_ranges_dev returning docids (see decode_ranges_sums_dev); arguments, return value and
+        .needed on ERR_CAPACITY are those of decode_device_ranges_dev, with bases_ptr, nbases behind in_bytes."""
+        for name, v in (("nranges", nranges), ("out_capacity", out_capacity), ("in_bytes", in_bytes), ("nbases", nbases)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        total = C.c_uint64(0)
+        st = L.lib().ansx_decode_device_ranges_sums_dev(self._ctx().handle, self.KIND, self.f, in_ptr, int(in_bytes),
+                                                        bases_ptr, int(nbases), first_ptr, count_ptr, int(nranges),
+                                                        out_ptr, int(out_capacity), offsets_ptr, C.byref(total), stream)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".decode_device_ranges_sums_dev")
+            if st == L.ERR_CAPACITY:
+                err.needed = int(total.value)
+            raise err
+        return int(total.value)
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

@@ -32,6 +32,7 @@
 #include "ansx_batchranges.h"
 #include "ansx_encbatch.h"
 #include "ansx_sums.h"
+#include "ansx_rangesums.h"
 
 namespace {
 
@@ -198,6 +199,7 @@ struct ansx_ctx {
         double fast_guard = ANSX_FAST_GUARD;  // ANSX_FAST_GUARD: relative guard band of the fast model path's stop rule (tests widen it)
         int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
         u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev, ansx_decode_batch_ranges_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
+        u32 range_sums_wg_max = 0;    // ANSX_RANGE_SUMS_WG_MAX: the largest block the one-kernel scan of the range sums takes (0 = ANSX_RS_WG_MAX; the bench tool measures both sides of the switch)
     } dbg;
 };
 typedef ansx_ctx::Dbg DebugOpts;
@@ -2139,14 +2141,65 @@ int decode_sub(ansx_ctx* c, int kind, int f, ansx_container_header H, u64 n_sub,
     return *hflag ? ANSX_ERR_FORMAT : rc;  // (the flag: an index entry of one of its blocks was invalid)
 }
 
+// The sums variants of the range calls (ansx_rangesums.h): the caller's block bases, nbases of them
+struct RangeBases {
+    const u32* d;
+    size_t n;
+};
+
+// the largest block the one-kernel scan takes
+u64 range_sums_wg_max(const ansx_ctx* c)
+{
+    return std::max<u64>(c->dbg.range_sums_wg_max ? c->dbg.range_sums_wg_max : ANSX_RS_WG_MAX, ANSX_RS_CHUNK);
+}
+
+// the aggregates of the three-phase scan, for the blocks it is used on: one per chunk of every touched block
+int range_sums_workspace(ansx_ctx* c, u64 bi, u64 T, u64** agg)
+{
+    int rc;
+    *agg = nullptr;
+    if (bi <= range_sums_wg_max(c)) return ANSX_OK;
+    const u64 tiles = T * ((bi + ANSX_RS_TILE - 1) / ANSX_RS_TILE);
+    if (tiles > 0x7FFFFFFFull) return ANSX_ERR_ARG;
+    if ((rc = ensure(c, c->sums_plan, 8 * (size_t)tiles * (ANSX_RS_NT / 64u)))) return rc;
+    *agg = (u64*)c->sums_plan.p;
+    return ANSX_OK;
+}
+
+// The work list of T touched blocks (n_sub ints, blocks of bi) -> its running sums from bases[tb[k]], in place, and the
+// check of the bases into gflags.  Enqueued between the decode and the gather; no synchronisation.
+int range_sums_scan(ansx_ctx* c, u32* list, u64 n_sub, u64 bi, u64 T, const u32* dtb, u32 nblocks, const u32* d_bases,
+    u64* agg, u32* gflags, hipStream_t s)
+{
+    if (bi <= ANSX_RS_CHUNK) {
+        LAUNCH(c, "k_rs_scan_small", k_rs_scan_small, (u32)((T + 3) / 4), ANSX_RS_NT, 0, s, list, n_sub, (u32)bi, (u32)T, dtb,
+            nblocks, d_bases, gflags);
+    } else if (bi <= range_sums_wg_max(c)) {
+        LAUNCH(c, "k_rs_scan_block", k_rs_scan_block, (u32)T, ANSX_RS_NT, 0, s, list, n_sub, (u32)bi, dtb, nblocks, d_bases,
+            gflags);
+    } else {
+        const u32 tpb = (u32)((bi + ANSX_RS_TILE - 1) / ANSX_RS_TILE), grid = (u32)(T * tpb);
+        LAUNCH(c, "k_rs_reduce", k_rs_reduce, grid, ANSX_RS_NT, 0, s, (const u32*)list, n_sub, (u32)bi, (u32)T, tpb, agg,
+            (const u32*)gflags);
+        LAUNCH(c, "k_rs_carry", k_rs_carry, (u32)T, ANSX_RS_NT, 0, s, agg, tpb * (ANSX_RS_NT / 64u), dtb, nblocks, d_bases,
+            gflags);
+        LAUNCH(c, "k_rs_apply", k_rs_apply, grid, ANSX_RS_NT, 0, s, list, n_sub, (u32)bi, tpb, (const u64*)agg,
+            (const u32*)gflags);
+    }
+    return ANSX_OK;
+}
+
 // The tail both fronts share, from the plan on the device: tb[T] the touched blocks (ascending, unique; last_b the
 // last), R the pieces of the nr non-empty ranges, pstart[nr + 1] their first gather pieces; dflags: a zeroed word.
 int range_tail(ansx_ctx* c, int kind, int f, const u8* d_in, const ansx_container_header& H, const Plan& P, u64 T,
     u64 last_b, const u32* dtb, const ansx_range_piece* R, const u32* pstart, u32 nr, u64 npieces, u32* dflags,
-    u32* d_out, hipStream_t s)
+    u32* d_out, hipStream_t s, const RangeBases* bases = nullptr)
 {
+    int rc;
     const u64 n = H.n, bi = P.g.block_ints;
     const u64 n_sub = (T - 1) * bi + std::min<u64>(bi, n - last_b * bi);  // (only the source's last block can be short: it sorts last)
+    u64* agg = nullptr;
+    if (bases && (rc = range_sums_workspace(c, bi, T, &agg))) return rc;  // (here: growing it may wait for the device)
     // (max_present_m1, max_nsyms, max_log2_frame are bounds over the blocks: they hold for any subset)
     const u64 cap_pay = std::min<u64>(H.payload_bytes, T * (u64)block_bound(kind, (u32)f, P.g.block_ints, P.g.pa != 0));
     const SubBuild build = [&](const Plan& Ps, const ansx_container_header& Hs, u8* sub) -> int {
@@ -2157,6 +2210,8 @@ int range_tail(ansx_ctx* c, int kind, int f, const u8* d_in, const ansx_containe
         return ANSX_OK;
     };
     const SubGather gather = [&](const u32* list, const u32* gflags) -> int {
+        // (the sums variants: the work list becomes ids first, in place; the scan reports foreign bases in gflags)
+        if (bases && (rc = range_sums_scan(c, (u32*)list, n_sub, bi, T, dtb, P.g.nblocks, bases->d, agg, (u32*)gflags, s))) return rc;
         const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
         LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, R, pstart, nr, (u32)npieces, d_out, gflags);
         return ANSX_OK;
@@ -2166,12 +2221,13 @@ int range_tail(ansx_ctx* c, int kind, int f, const u8* d_in, const ansx_containe
 
 // ansx_decode_ranges_dev: the plan built on the host from host arrays, uploaded in one copy
 int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* first, const u32* count,
-    size_t nranges, u32* d_out, size_t cap, hipStream_t s)
+    size_t nranges, u32* d_out, size_t cap, hipStream_t s, const RangeBases* bases = nullptr)
 {
     int rc;
     ansx_container_header H;
     Plan P;
     if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &H, &P))) return rc;
+    if (bases && bases->n != (size_t)P.g.nblocks + 1) return ANSX_ERR_ARG;
     const u64 n = H.n, bi = P.g.block_ints;
 
     // ranges -> block spans; their union as sorted runs of consecutive blocks, each numbered from its first touched block
@@ -2239,18 +2295,20 @@ int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes,
     u8* dplan = (u8*)c->rng_plan.p;
     HIPCHK(c, hipMemcpyAsync(dplan, c->rng_pin, plan_bytes, hipMemcpyHostToDevice, s));
     return range_tail(c, kind, f, d_in, H, P, T, runs.back().b1, (const u32*)(dplan + o_tb),
-        (const ansx_range_piece*)(dplan + o_pc), (const u32*)(dplan + o_ps), nr, npieces, (u32*)dplan, d_out, s);
+        (const ansx_range_piece*)(dplan + o_pc), (const u32*)(dplan + o_ps), nr, npieces, (u32*)dplan, d_out, s, bases);
 }
 
 // ansx_decode_device_ranges_dev: the plan built on the device from first / count in device memory (ansx_ranges.h,
 // "device plan"); one read-back of its scalars decides the errors and sizes the tail, no O(nranges) copy either way.
 int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
-    const u32* d_count, size_t nranges, u32* d_out, size_t cap, u64* d_offsets, u64* total_ints, hipStream_t s)
+    const u32* d_count, size_t nranges, u32* d_out, size_t cap, u64* d_offsets, u64* total_ints, hipStream_t s,
+    const RangeBases* bases = nullptr)
 {
     int rc;
     ansx_container_header H;
     Plan P;
     if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &H, &P))) return rc;
+    if (bases && bases->n != (size_t)P.g.nblocks + 1) return ANSX_ERR_ARG;
     const u64 n = H.n, bi = P.g.block_ints, nr = nranges, nb = P.g.nblocks;
     u32 kb = 0;  // key bits of a block id
     while ((1ull << kb) < nb) kb++;
@@ -2314,7 +2372,7 @@ int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in
     LAUNCH(c, "k_dr_blocks", k_dr_blocks, (u32)((T + ANSX_DR_NT - 1) / ANSX_DR_NT), ANSX_DR_NT, 0, s, tb, (u32)T, (u32)nne,
         S, offl, (const u64*)parta);
     return range_tail(c, kind, f, d_in, H, P, T, hs[ANSX_DR_LASTB1] - 1, tb, R, pstart, (u32)nne, npieces,
-        (u32*)&sc[ANSX_DR_FLAGS], d_out, s);
+        (u32*)&sc[ANSX_DR_FLAGS], d_out, s, bases);
 }
 
 // --------------------------------------------------------------------------------- batches of containers
@@ -3057,6 +3115,38 @@ int gaps_run(ansx_ctx* c, const u32* d_in, u64 n, const u64* offs, size_t count,
     return sums_finish(c, S, bad_index, s);
 }
 
+// ansx_block_bases_dev: the container decoded into rng_list -- no remembered header in or out --
+// with k_rs_reduce and k_rs_bases riding on the decode's final read-back, which also carries ANSX_ERR_DOMAIN home.
+int block_bases(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, u32* d_bases, size_t cap, size_t* nbases,
+    hipStream_t s)
+{
+    int rc;
+    ansx_container_header H;
+    Plan P;
+    if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &H, &P))) return rc;
+    const u64 n = H.n, bi = P.g.block_ints;
+    const u32 nb = P.g.nblocks;
+    *nbases = (size_t)nb + 1;
+    if (cap < (size_t)nb + 1) return ANSX_ERR_CAPACITY;
+    // a block of at most a chunk is one aggregate, a longer one four per tile
+    const u32 tpb = bi <= ANSX_RS_CHUNK ? 0u : (u32)((bi + ANSX_RS_TILE - 1) / ANSX_RS_TILE);
+    const u32 per = tpb ? tpb * (ANSX_RS_NT / 64u) : 1u;
+    const u64 grid = tpb ? (u64)nb * tpb : ((u64)nb + 3) / 4;
+    if (grid > 0x7FFFFFFFull) return ANSX_ERR_ARG;
+    if ((rc = ensure(c, c->rng_list, 4 * (size_t)n + 64))) return rc;
+    if ((rc = ensure(c, c->sums_plan, 8 * (size_t)nb * per))) return rc;
+    u32* list = (u32*)c->rng_list.p;
+    u64* agg = (u64*)c->sums_plan.p;
+    const std::function<int(const u32*)> epilogue = [&](const u32* gflags) -> int {
+        LAUNCH(c, "k_rs_reduce", k_rs_reduce, (u32)grid, ANSX_RS_NT, 0, s, (const u32*)list, n, (u32)bi, nb, tpb, agg, gflags);
+        LAUNCH(c, "k_rs_bases", k_rs_bases, 1, ANSX_RS_NT, 0, s, (const u64*)agg, per, nb, d_bases, (u32*)gflags);
+        return ANSX_OK;
+    };
+    DecodeOpts O;
+    O.speculate = O.remember = false, O.epilogue = &epilogue;
+    return decode_dev(c, P, d_in, in_bytes, list, s, O);
+}
+
 // the argument checks of ansx_decode_batch_dev, everything it decides before the context is touched
 int decode_batch_args(const ansx_ctx* c, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count, const uint32_t* d_out,
     size_t out_capacity_ints)
@@ -3262,6 +3352,7 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
     else if (!strcmp(name, "ANSX_NEAR_BAND")) c->dbg.near_band = (value && value[0]) ? strtod(value, nullptr) : ANSX_NEAR_BAND;
     else if (!strcmp(name, "ANSX_TEST_NEAR_FLIP")) c->dbg.near_flip = on;
     else if (!strcmp(name, "ANSX_BATCH_PASS_BLOCKS")) c->dbg.batch_pass_blocks = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
+    else if (!strcmp(name, "ANSX_RANGE_SUMS_WG_MAX")) c->dbg.range_sums_wg_max = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_MODEL_PIPELINE")) {
         if (!value || !value[0] || !strcmp(value, "0")) c->dbg.model_pipeline = 0;
         else if (!strcmp(value, "never")) c->dbg.model_pipeline = ANSX_PIPE_NEVER;
@@ -3401,6 +3492,57 @@ int ansx_decode_device_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* d
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     return decode_device_ranges(c, kind, f, d_in, in_bytes, (const u64*)d_first, d_count, nranges, d_out,
         out_capacity_ints, (u64*)d_offsets, (u64*)total_ints, s);
+}
+
+int ansx_decode_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, const uint32_t* d_bases,
+    size_t nbases, const uint64_t* first, const uint32_t* count, size_t nranges, uint32_t* d_out, size_t out_capacity_ints,
+    void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!first || !count)) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!d_bases || ((uintptr_t)d_bases & 3u))) return ANSX_ERR_ARG;
+    if (nranges == 0) return ANSX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const RangeBases bases = { d_bases, nbases };
+    return decode_ranges(c, kind, f, d_in, in_bytes, (const u64*)first, count, nranges, d_out, out_capacity_ints, s, &bases);
+}
+
+int ansx_decode_device_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes,
+    const uint32_t* d_bases, size_t nbases, const uint64_t* d_first, const uint32_t* d_count, size_t nranges, uint32_t* d_out,
+    size_t out_capacity_ints, uint64_t* d_offsets, uint64_t* total_ints, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!d_first || !d_count)) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u) || ((uintptr_t)d_first & 7u) || ((uintptr_t)d_count & 3u)
+        || ((uintptr_t)d_offsets & 7u))
+        return ANSX_ERR_ARG;
+    if (nranges > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!d_bases || ((uintptr_t)d_bases & 3u))) return ANSX_ERR_ARG;
+    if (nranges == 0) {
+        if (total_ints) *total_ints = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const RangeBases bases = { d_bases, nbases };
+    return decode_device_ranges(c, kind, f, d_in, in_bytes, (const u64*)d_first, d_count, nranges, d_out,
+        out_capacity_ints, (u64*)d_offsets, (u64*)total_ints, s, &bases);
+}
+
+int ansx_block_bases_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, uint32_t* d_bases,
+    size_t bases_capacity, size_t* nbases, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || !d_in || !nbases) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_bases & 3u)) return ANSX_ERR_ARG;
+    if (!d_bases && bases_capacity > 0) return ANSX_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return block_bases(c, kind, f, d_in, in_bytes, d_bases, bases_capacity, nbases, s);
 }
 
 int ansx_decode_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count,
@@ -3553,6 +3695,29 @@ int ansx_encode_gaps_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, siz
     const u64 offs[2] = { 0, (u64)n };
     const u32* gaps = nullptr;
     if ((rc = gaps_run(c, d_in, (u64)n, offs, 1, &gaps, nullptr, s))) return rc;
+    return encode_dev(c, P, gaps, d_out, cap, out_bytes, s);
+}
+
+int ansx_encode_gaps_bases_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, size_t n, uint8_t* d_out, size_t cap,
+    size_t* out_bytes, const ansx_opts* opts, uint32_t* d_bases, size_t bases_capacity, size_t* nbases, void* stream)
+{
+    if (!c || !d_in || !d_out || !out_bytes || !nbases) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_in & 3u) || ((uintptr_t)d_bases & 3u)) return ANSX_ERR_ARG;
+    if (!d_bases && bases_capacity > 0) return ANSX_ERR_ARG;
+    if (opts && opts->block_ints == ANSX_SINGLE_STREAM) return ANSX_ERR_ARG;  // (a stream has no blocks)
+    Plan P;
+    int rc = make_plan(kind, f, n, opts, &P);
+    if (rc) return rc;
+    *nbases = (size_t)P.g.nblocks + 1;
+    if (bases_capacity < (size_t)P.g.nblocks + 1) return ANSX_ERR_CAPACITY;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const u64 offs[2] = { 0, (u64)n };
+    const u32* gaps = nullptr;
+    if ((rc = gaps_run(c, d_in, (u64)n, offs, 1, &gaps, nullptr, s))) return rc;
+    // the ids do not decrease: the id in front of a block is the sum of every gap in front of it
+    LAUNCH(c, "k_rs_ids_bases", k_rs_ids_bases, P.g.nblocks / ANSX_RS_NT + 1, ANSX_RS_NT, 0, s, d_in, (u64)n, P.g.block_ints,
+        P.g.nblocks, d_bases);
     return encode_dev(c, P, gaps, d_out, cap, out_bytes, s);
 }
 

@@ -326,7 +326,7 @@ int ansx_encode_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t*
  * document ids and read as the ids; these four calls are the two ends.  For a list x the sums are
  * s[i] = x[0] + ... + x[i] (inclusive); for a list d the gaps are g[0] = d[0], g[i] = d[i] - d[i - 1]; every list of a
  * batch starts afresh; decode_sums(encode_gaps(d)) == d for every non-decreasing d whose gaps the codec accepts.  Whole
- * containers and whole batches only (running sums of RANGES would need per-block bases in the container), 32-bit
+ * containers and whole batches only (running sums of RANGES: the calls with block bases further down), 32-bit
  * outputs, no change of the container format: the bytes are those of the ordinary calls on the gaps.
  *
  * ansx_decode_sums_dev: the arguments and the behaviour of ansx_decode_dev -- the accepted forms, ANSX_SINGLE_STREAM
@@ -368,6 +368,62 @@ int ansx_encode_gaps_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t* 
 int ansx_encode_batch_gaps_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t* d_in, const uint64_t* offsets,
     size_t count, uint8_t* d_out, size_t out_capacity, uint64_t* out_offsets, uint64_t* out_bytes, size_t* total_bytes,
     size_t* bad_index, const ansx_opts* opts, void* stream);
+
+/* Docids of ranges: block bases beside the container.  For a container of n gaps in nblocks
+ * blocks of block_ints ints the bases are nblocks + 1 values of uint32_t in 4-byte aligned DEVICE memory of the caller:
+ * bases[b] is the sum of ints [0, b * block_ints), so bases[0] = 0 and bases[nblocks] is the sum of the whole list, its
+ * last id -- the skip table an inverted index keeps anyway.  Nothing in the container refers to them; the container
+ * format and every other call are as they were.  Two calls produce them, two read them.
+ *
+ * ansx_block_bases_dev: the bases of an existing container.  Every form ansx_decode_dev reads is accepted except a
+ * single-stream stream, which has no blocks (ANSX_ERR_FORMAT, as in the range calls).  The container is decoded into
+ * workspace of the context (4 bytes per int, grow-only, counted by ansx_workspace_bytes), per-block 64-bit sums are
+ * taken, and one workgroup scans them into d_bases.  *nbases = nblocks + 1 is set on ANSX_OK and on ANSX_ERR_CAPACITY
+ * (bases_capacity < nblocks + 1), which is decided from the header before anything is launched: d_bases = NULL,
+ * bases_capacity = 0 is a size query.  ANSX_ERR_DOMAIN if the sum of the list exceeds 2^32 - 1; d_bases is then
+ * unspecified.  The errors of the decode are those of ansx_decode_dev.  Errors decided before the context is touched:
+ * ANSX_ERR_ARG for a null ctx / d_in / nbases, d_in not 16-byte aligned, d_bases not 4-byte aligned, or d_bases == NULL
+ * with bases_capacity > 0.  The call leaves no trace in the context (no remembered header, no per-geometry hint), like
+ * the range calls.  Returns after the status has been read back. */
+int ansx_block_bases_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in, size_t in_bytes, uint32_t* d_bases,
+    size_t bases_capacity, size_t* nbases, void* stream);
+
+/* ansx_encode_gaps_bases_dev: ansx_encode_gaps_dev for the writer who wants the bases as well -- its arguments, then
+ * d_bases, bases_capacity and nbases as above.  The container bytes, *out_bytes, ansx_last_encode_stats and what the
+ * context learns are exactly those of ansx_encode_gaps_dev.  Once the ids have passed the check for decreases, one
+ * kernel reads the bases off them: bases[0] = 0, bases[b] = d_in[b * block_ints - 1], bases[nblocks] = d_in[n - 1],
+ * block_ints being the value opts resolves to.  Decided on the host before anything is launched: ANSX_ERR_ARG as for
+ * ansx_encode_gaps_dev, for a null nbases, a misaligned d_bases, d_bases == NULL with bases_capacity > 0 and for
+ * opts->block_ints == ANSX_SINGLE_STREAM (a stream has no blocks); ANSX_ERR_CAPACITY, with *nbases set, when
+ * bases_capacity < nblocks + 1.  After an error of the encode d_bases is unspecified. */
+int ansx_encode_gaps_bases_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t* d_in, size_t n, uint8_t* d_out,
+    size_t out_capacity, size_t* out_bytes, const ansx_opts* opts, uint32_t* d_bases, size_t bases_capacity,
+    size_t* nbases, void* stream);
+
+/* ansx_decode_ranges_sums_dev: ansx_decode_ranges_dev returning ids.  Range i is s[first[i]] .. s[first[i] + count[i] - 1],
+ * s being what ansx_decode_sums_dev returns for the container; the ranges lie in d_out exactly as ansx_decode_ranges_dev
+ * lays out the gaps.  Everything else is that call's: the accepted forms, what ranges may look like, the errors and
+ * their order, selectivity, no kernel's grid growing with the container's block count, no trace in the context, the
+ * number of host round trips -- the sums add no synchronisation and no read-back of their own.  Between the decode of
+ * the touched blocks and the gather, the work list is scanned in place, restarting at every touched block b from
+ * d_bases[b] (ansx_rangesums.h).  In addition:
+ *   ANSX_ERR_ARG before the context is touched for a null or misaligned (4 bytes) d_bases with nranges > 0;
+ *   ANSX_ERR_ARG on the host, once the header is known and before any launch, if nbases != nblocks + 1;
+ *   of d_bases only entries b and b + 1 of touched blocks b are read;
+ *   every touched block is scanned whole, and d_bases[b] + (the sum of block b, in 64 bits) must equal d_bases[b + 1].
+ *   If it does not, the bases are not this container's: ANSX_ERR_FORMAT, found on the device and reported through the
+ *   flag and the read-back of the decode's own format errors, and like those it leaves d_out unwritten.  Consistent
+ *   bases also prove that no running sum inside a touched block leaves 32 bits, so there is no ANSX_ERR_DOMAIN here. */
+int ansx_decode_ranges_sums_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in, size_t in_bytes,
+    const uint32_t* d_bases, size_t nbases, const uint64_t* first, const uint32_t* count, size_t nranges, uint32_t* d_out,
+    size_t out_capacity_ints, void* stream);
+
+/* ansx_decode_device_ranges_sums_dev: the same over ansx_decode_device_ranges_dev -- its arguments with d_bases, nbases
+ * behind in_bytes, its errors in its order, d_offsets and *total_ints unchanged -- with the additional rules of
+ * ansx_decode_ranges_sums_dev. */
+int ansx_decode_device_ranges_sums_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in, size_t in_bytes,
+    const uint32_t* d_bases, size_t nbases, const uint64_t* d_first, const uint32_t* d_count, size_t nranges,
+    uint32_t* d_out, size_t out_capacity_ints, uint64_t* d_offsets, uint64_t* total_ints, void* stream);
 
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
@@ -478,7 +534,10 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
  * consumer encoder never / whatever the list length / only on request; pairs per workgroup of its two-round shape),
  * ANSX_ENCODE_MODE2, ANSX_DECODE_PAIR, ANSX_DECODE_SMALL_RING (1 never | 2 always), ANSX_FORGET_HINTS, ANSX_NO_BIG_GEO,
  * ANSX_FIN_ONE_WAVE, ANSX_TEST_SP_BITS (number: words of the rank-space ANSint prelude writer's bit buffer on its first
- * attempt)  (flags: "1" on, "0"/""/NULL off).  Unknown name: ANSX_ERR_ARG. */
+ * attempt), ANSX_RANGE_SUMS_WG_MAX (number: the largest block_ints whose touched blocks the sums variants of the range
+ * calls scan in one kernel, a workgroup per block; larger blocks take the three-phase scan; ""/"0"/NULL: 65536 -- for the
+ * paired timing of tests/tools/bench_range_sums.py, the results do not depend on it)  (flags: "1" on, "0"/""/NULL off).
+ * Unknown name: ANSX_ERR_ARG. */
 int ansx_debug_set(ansx_ctx* ctx, const char* name, const char* value);
 
 /* Bytes of device workspace currently held by the context. */
