@@ -19,6 +19,7 @@ DEFAULT_BLOCK_INTS = 16384
 DEFAULT_CKPT_INTERVAL = 1024
 MAX_FIDELITY = 7
 GEN_UNIFORM, GEN_GEOMETRIC, GEN_ZIPF = 0, 1, 2
+NO_ID = 0xFFFFFFFF  # ansx_next_geq_dev: the id of a target above the last id (its position, n, is what decides)
 
 EXPORTS = [
     "ansx_init", "ansx_destroy", "ansx_strerror", "ansx_last_hip_error", "ansx_codec_name",
@@ -30,7 +31,7 @@ EXPORTS = [
     "ansx_decode_device_ranges_dev", "ansx_decode_batch_dev", "ansx_encode_batch_dev",
     "ansx_decode_batch_ranges_dev", "ansx_decode_sums_dev", "ansx_decode_batch_sums_dev", "ansx_encode_gaps_dev",
     "ansx_encode_batch_gaps_dev", "ansx_block_bases_dev", "ansx_encode_gaps_bases_dev", "ansx_decode_ranges_sums_dev",
-    "ansx_decode_device_ranges_sums_dev",
+    "ansx_decode_device_ranges_sums_dev", "ansx_next_geq_dev",
 ]
 
 
@@ -148,6 +149,9 @@ def lib():
     L.ansx_decode_device_ranges_sums_dev.restype = C.c_int
     L.ansx_decode_device_ranges_sums_dev.argtypes = [vp, C.c_int, C.c_int, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp,
                                                      C.POINTER(C.c_uint64), vp]
+    # search by value over the bases: targets -> positions and ids
+    L.ansx_next_geq_dev.restype = C.c_int
+    L.ansx_next_geq_dev.argtypes = [vp, C.c_int, C.c_int, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(C.c_uint64), vp]
     L.ansx_container_info.restype = C.c_int
     L.ansx_container_info.argtypes = [vp, sz, C.POINTER(ContainerHeader)]
     L.ansx_profile_enable.restype = C.c_int

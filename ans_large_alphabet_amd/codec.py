@@ -404,6 +404,24 @@ class _Codec:
             raise err
         return int(total.value)
 
+    # ---- search by value (include/ansx.h)
+    def next_geq_dev(self, in_ptr, in_bytes, bases_ptr, nbases, targets_ptr, ntargets, pos_ptr, ids_ptr, stream=None):
+        """For each of the ntargets uint32 at targets_ptr (device), the first docid >= it of the container at in_ptr:
+        its position -> the uint64 at pos_ptr, the id -> the uint32 at ids_ptr (device arrays of ntargets; either may be
+        None).  A target above the last id gives position n -- the authoritative "not found" -- and id NO_ID.  Only the
+        blocks some target lands in are read, located through the nbases block bases at bases_ptr; ERR_FORMAT if the
+        bases of such a block are not this container's, and then neither array is written.  Returns the number of
+        targets found."""
+        for name, v in (("ntargets", ntargets), ("in_bytes", in_bytes), ("nbases", nbases)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        found = C.c_uint64(0)
+        st = L.lib().ansx_next_geq_dev(self._ctx().handle, self.KIND, self.f, in_ptr, int(in_bytes), bases_ptr, int(nbases),
+                                       targets_ptr, int(ntargets), pos_ptr, ids_ptr, C.byref(found), stream)
+        if st != L.OK:
+            raise L.AnsxError(st, self.name() + ".next_geq_dev")
+        return int(found.value)
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

@@ -33,6 +33,7 @@
 #include "ansx_encbatch.h"
 #include "ansx_sums.h"
 #include "ansx_rangesums.h"
+#include "ansx_nextgeq.h"
 
 namespace {
 
@@ -2189,11 +2190,23 @@ int range_sums_scan(ansx_ctx* c, u32* list, u64 n_sub, u64 bi, u64 T, const u32*
     return ANSX_OK;
 }
 
+// ansx_next_geq_dev (ansx_nextgeq.h): the caller's targets and outputs, and the ranges made of
+// them -- first / count by k_ng_locate, offsets by the planner -- in workspace of the context
+struct NextGeq {
+    const u32* d_targets;
+    u64* d_pos;
+    u32* d_ids;
+    const u64* first;
+    const u32* count;
+    const u64* offsets;
+};
+
 // The tail both fronts share, from the plan on the device: tb[T] the touched blocks (ascending, unique; last_b the
 // last), R the pieces of the nr non-empty ranges, pstart[nr + 1] their first gather pieces; dflags: a zeroed word.
+// ng (with bases; nt targets): k_ng_search over the scanned work list in the place of the gather.
 int range_tail(ansx_ctx* c, int kind, int f, const u8* d_in, const ansx_container_header& H, const Plan& P, u64 T,
     u64 last_b, const u32* dtb, const ansx_range_piece* R, const u32* pstart, u32 nr, u64 npieces, u32* dflags,
-    u32* d_out, hipStream_t s, const RangeBases* bases = nullptr)
+    u32* d_out, hipStream_t s, const RangeBases* bases = nullptr, const NextGeq* ng = nullptr, u32 nt = 0)
 {
     int rc;
     const u64 n = H.n, bi = P.g.block_ints;
@@ -2212,6 +2225,11 @@ int range_tail(ansx_ctx* c, int kind, int f, const u8* d_in, const ansx_containe
     const SubGather gather = [&](const u32* list, const u32* gflags) -> int {
         // (the sums variants: the work list becomes ids first, in place; the scan reports foreign bases in gflags)
         if (bases && (rc = range_sums_scan(c, (u32*)list, n_sub, bi, T, dtb, P.g.nblocks, bases->d, agg, (u32*)gflags, s))) return rc;
+        if (ng) {
+            LAUNCH(c, "k_ng_search", k_ng_search, (nt + ANSX_NG_NT - 1) / ANSX_NG_NT, ANSX_NG_NT, 0, s, list, n_sub, bi, n,
+                ng->d_targets, nt, ng->first, ng->count, ng->offsets, R, ng->d_pos, ng->d_ids, gflags, (const u32*)dflags);
+            return ANSX_OK;
+        }
         const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
         LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, R, pstart, nr, (u32)npieces, d_out, gflags);
         return ANSX_OK;
@@ -2300,9 +2318,12 @@ int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes,
 
 // ansx_decode_device_ranges_dev: the plan built on the device from first / count in device memory (ansx_ranges.h,
 // "device plan"); one read-back of its scalars decides the errors and sizes the tail, no O(nranges) copy either way.
-int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
+// The body serves ansx_next_geq_dev too (ng, with bases; nranges targets): the ranges are then k_ng_locate's, one int at
+// the start of every target's block, made in front of the planner in workspace behind its own; the planner and its
+// read-back are the same, *total_ints is the number of targets found, and the tail searches instead of gathering.
+int device_ranges_body(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
     const u32* d_count, size_t nranges, u32* d_out, size_t cap, u64* d_offsets, u64* total_ints, hipStream_t s,
-    const RangeBases* bases = nullptr)
+    const RangeBases* bases, NextGeq* ng)
 {
     int rc;
     ansx_container_header H;
@@ -2317,9 +2338,19 @@ int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in
     // workspace: scalars u64[8] | per-tile partials u64[6 nt] | radix histogram u32[16 nt] | pieces[nr] |
     // pstart u32[nr + 1] | spans (b0, b1 + 1) twice over u32[4 nr] | tb u32[nblocks]
     const size_t o_pt = 64, o_h = o_pt + 48 * nt, o_pc = rup(o_h + 64 * nt, 16), o_ps = o_pc + sizeof(ansx_range_piece) * nr;
-    const size_t o_sp = rup(o_ps + 4 * (nr + 1), 16), o_tb = o_sp + 16 * nr, bytes = o_tb + 4 * nb;
+    const size_t o_sp = rup(o_ps + 4 * (nr + 1), 16), o_tb = o_sp + 16 * nr;
+    // (ansx_next_geq_dev, behind tb: first u64[nr] | offsets u64[nr + 1] | count u32[nr])
+    const size_t o_nf = rup(o_tb + 4 * nb, 16), o_no = o_nf + 8 * nr, o_nc = o_no + 8 * (nr + 1);
+    const size_t bytes = ng ? o_nc + 4 * nr : o_tb + 4 * nb;
     if ((rc = ensure(c, c->rng_dev, bytes))) return rc;
     u8* w = (u8*)c->rng_dev.p;
+    if (ng) {
+        u64* nf = (u64*)(w + o_nf);
+        u32* nc = (u32*)(w + o_nc);
+        LAUNCH(c, "k_ng_locate", k_ng_locate, (u32)((nr + ANSX_NG_TILE - 1) / ANSX_NG_TILE), ANSX_NG_NT, 0, s, bases->d, (u32)nb,
+            bi, ng->d_targets, (u32)nr, nf, nc);
+        d_first = ng->first = nf, d_count = ng->count = nc, d_offsets = (u64*)(w + o_no), ng->offsets = d_offsets;
+    }
     u64* sc = (u64*)w;
     u64* part = (u64*)(w + o_pt);
     u64* partm = part + 4 * nt;
@@ -2366,13 +2397,28 @@ int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in
     const u64 total = hs[ANSX_DR_TOTAL], nne = hs[ANSX_DR_NNE], npieces = hs[ANSX_DR_NPIECES], T = hs[ANSX_DR_T];
     if (total_ints) *total_ints = total;
     if (total > cap) return ANSX_ERR_CAPACITY;
-    if (total == 0) return ANSX_OK;
+    if (total == 0) {
+        if (ng) {  // (no target found and no tail: the outputs are filled here; the call returns with them written, as ever)
+            LAUNCH(c, "k_ng_none", k_ng_none, (u32)((nr + ANSX_NG_NT - 1) / ANSX_NG_NT), ANSX_NG_NT, 0, s, n, (u32)nr, ng->d_pos,
+                ng->d_ids);
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
+        return ANSX_OK;
+    }
     if (npieces > 0xFFFFFFFFull) return ANSX_ERR_ARG;
     if (T == 0 || T > nb || nne == 0 || hs[ANSX_DR_LASTB1] == 0) return ANSX_ERR_HIP;  // (cannot happen: a planner fault)
     LAUNCH(c, "k_dr_blocks", k_dr_blocks, (u32)((T + ANSX_DR_NT - 1) / ANSX_DR_NT), ANSX_DR_NT, 0, s, tb, (u32)T, (u32)nne,
         S, offl, (const u64*)parta);
     return range_tail(c, kind, f, d_in, H, P, T, hs[ANSX_DR_LASTB1] - 1, tb, R, pstart, (u32)nne, npieces,
-        (u32*)&sc[ANSX_DR_FLAGS], d_out, s, bases);
+        (u32*)&sc[ANSX_DR_FLAGS], d_out, s, bases, ng, (u32)nr);
+}
+
+int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
+    const u32* d_count, size_t nranges, u32* d_out, size_t cap, u64* d_offsets, u64* total_ints, hipStream_t s,
+    const RangeBases* bases = nullptr)
+{
+    return device_ranges_body(c, kind, f, d_in, in_bytes, d_first, d_count, nranges, d_out, cap, d_offsets, total_ints, s,
+        bases, nullptr);
 }
 
 // --------------------------------------------------------------------------------- batches of containers
@@ -3531,6 +3577,31 @@ int ansx_decode_device_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8
     const RangeBases bases = { d_bases, nbases };
     return decode_device_ranges(c, kind, f, d_in, in_bytes, (const u64*)d_first, d_count, nranges, d_out,
         out_capacity_ints, (u64*)d_offsets, (u64*)total_ints, s, &bases);
+}
+
+int ansx_next_geq_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, const uint32_t* d_bases,
+    size_t nbases, const uint32_t* d_targets, size_t ntargets, uint64_t* d_pos, uint32_t* d_ids, uint64_t* found, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || !d_in) return ANSX_ERR_ARG;
+    if (ntargets > 0 && (!d_bases || !d_targets || (!d_pos && !d_ids))) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_bases & 3u) || ((uintptr_t)d_targets & 3u) || ((uintptr_t)d_pos & 7u)
+        || ((uintptr_t)d_ids & 3u))
+        return ANSX_ERR_ARG;
+    if (ntargets > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (ntargets == 0) {
+        if (found) *found = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const RangeBases bases = { d_bases, nbases };
+    NextGeq ng = { d_targets, (u64*)d_pos, d_ids, nullptr, nullptr, nullptr };
+    u64 total = 0;
+    const int rc = device_ranges_body(c, kind, f, d_in, in_bytes, nullptr, nullptr, ntargets, nullptr, ntargets, nullptr,
+        &total, s, &bases, &ng);
+    if (rc == ANSX_OK && found) *found = total;
+    return rc;
 }
 
 int ansx_block_bases_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, uint32_t* d_bases,

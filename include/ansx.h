@@ -425,6 +425,47 @@ int ansx_decode_device_ranges_sums_dev(ansx_ctx* ctx, int kind, int fidelity, co
     const uint32_t* d_bases, size_t nbases, const uint64_t* d_first, const uint32_t* d_count, size_t nranges,
     uint32_t* d_out, size_t out_capacity_ints, uint64_t* d_offsets, uint64_t* total_ints, void* stream);
 
+/* ansx_next_geq_dev: search by value over the bases.  Let s be what ansx_decode_sums_dev returns
+ * for the container, n ids, non-decreasing.  For every target t = d_targets[i]: d_pos[i] = min{ j : s[j] >= t } -- the
+ * lower bound: of equal ids (zero gaps) the first, which may lie in an earlier block than the last -- and
+ * d_ids[i] = s[d_pos[i]].  t = 0 gives position 0.  If t > s[n - 1]: d_pos[i] = n and d_ids[i] = ANSX_NO_ID.  2^32 - 1 can
+ * be a real id, so d_pos[i] == n is the authoritative "not found"; a caller who asks for ids only must keep the last id
+ * below 2^32 - 1 or compare t with bases[nblocks] themselves.  Targets may be unsorted and may repeat.
+ * d_targets: ntargets uint32_t in 4-byte aligned DEVICE memory, read on `stream` (a kernel that wrote them earlier on that
+ * stream is ordered before).  d_pos (8-byte aligned) and d_ids (4-byte aligned): DEVICE arrays of ntargets; either may
+ * be NULL, not both.  *found (optional, host): the number of targets with d_pos[i] < n, set on ANSX_OK.
+ * Accepted forms, header checks, no trace in the context and "returns after the status has been read back" are exactly
+ * those of ansx_decode_device_ranges_sums_dev (every container form the range calls accept; a single-stream stream is
+ * ANSX_ERR_FORMAT), and so are the two host round trips: the header, then the planner's scalars with the status.
+ * One exception: when NO target is found the range path ends at the planner's scalars; the outputs are then filled by
+ * a kernel of their own and the call waits for it, a third host wait, so that it returns with its outputs written as on
+ * every other path.
+ * Errors, in this order:
+ *   before the context is touched, ANSX_ERR_ARG for a null ctx or d_in; a null d_bases or d_targets, or both outputs
+ *   null, with ntargets > 0; a misaligned pointer (d_in 16 bytes, d_bases 4, d_targets 4, d_pos 8, d_ids 4);
+ *   ntargets > UINT32_MAX.  ntargets == 0: ANSX_OK, *found = 0, nothing launched, the context untouched;
+ *   on the host once the header is known, before any launch: ANSX_ERR_FORMAT as in the range calls, then ANSX_ERR_ARG
+ *   if nbases != nblocks + 1;
+ *   on the device: ANSX_ERR_FORMAT for an invalid index entry or stream of a touched block, and for bases that fail
+ *   the check of the sums range calls at a touched block b (d_bases[b] + the block's sum in 64 bits != d_bases[b + 1]),
+ *   through the decode's flag word and its one read-back.  NEITHER output array is written then.
+ * What the bases promise.  The search trusts d_bases to be this container's (non-decreasing, bases[0] = 0, as
+ * ansx_block_bases_dev or ansx_encode_gaps_bases_dev made them) and must not be changed while the call runs.  It verifies
+ * what the sums range calls verify and only at TOUCHED blocks -- the blocks some target was sent to.  A wrong entry
+ * elsewhere can send a target to a block that is not its own WITHOUT DETECTION: the answer is then the lower bound inside
+ * that block, clamped to it.  What holds for any content of d_bases is memory safety: nothing is read outside
+ * d_bases[0 .. nbases), the container and d_targets[0 .. ntargets), nothing is written outside d_pos[0 .. ntargets) and
+ * d_ids[0 .. ntargets), and every search loop ends.
+ * Selectivity: of a block no target lands in, nothing is read -- no stream, restart point, hint or index entry; targets
+ * beyond the last id touch no block; no kernel's grid grows with the container's block count.  Of d_bases the locate
+ * step may read any entry (O(log nblocks) per target, most of them from a copy in LDS) -- the one difference from the
+ * sums range calls, which read entries b and b + 1 only.  Workspace: that of the range calls for the touched blocks plus
+ * 28 bytes per target. */
+#define ANSX_NO_ID 0xFFFFFFFFu
+int ansx_next_geq_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in, size_t in_bytes, const uint32_t* d_bases,
+    size_t nbases, const uint32_t* d_targets, size_t ntargets, uint64_t* d_pos, uint32_t* d_ids, uint64_t* found,
+    void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
