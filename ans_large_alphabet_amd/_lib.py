@@ -31,7 +31,8 @@ EXPORTS = [
     "ansx_decode_device_ranges_dev", "ansx_decode_batch_dev", "ansx_encode_batch_dev",
     "ansx_decode_batch_ranges_dev", "ansx_decode_sums_dev", "ansx_decode_batch_sums_dev", "ansx_encode_gaps_dev",
     "ansx_encode_batch_gaps_dev", "ansx_block_bases_dev", "ansx_encode_gaps_bases_dev", "ansx_decode_ranges_sums_dev",
-    "ansx_decode_device_ranges_sums_dev", "ansx_next_geq_dev",
+    "ansx_decode_device_ranges_sums_dev", "ansx_next_geq_dev", "ansx_encode_batch_gaps_bases_dev",
+    "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev",
 ]
 
 
@@ -152,6 +153,15 @@ def lib():
     # search by value over the bases: targets -> positions and ids
     L.ansx_next_geq_dev.restype = C.c_int
     L.ansx_next_geq_dev.argtypes = [vp, C.c_int, C.c_int, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(C.c_uint64), vp]
+    # batches of gap-coded lists: bases from the writer, ids of ranges, search by value
+    L.ansx_encode_batch_gaps_bases_dev.restype = C.c_int
+    L.ansx_encode_batch_gaps_bases_dev.argtypes = list(L.ansx_encode_batch_dev.argtypes[:-1]) + [vp, sz, vp, C.POINTER(sz), vp]
+    L.ansx_decode_batch_ranges_sums_dev.restype = C.c_int
+    L.ansx_decode_batch_ranges_sums_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp,
+                                                    C.POINTER(C.c_uint64), C.POINTER(sz), C.POINTER(sz), vp]
+    L.ansx_next_geq_batch_dev.restype = C.c_int
+    L.ansx_next_geq_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, sz, vp, vp,
+                                          C.POINTER(C.c_uint64), C.POINTER(sz), C.POINTER(sz), vp]
     L.ansx_container_info.restype = C.c_int
     L.ansx_container_info.argtypes = [vp, sz, C.POINTER(ContainerHeader)]
     L.ansx_profile_enable.restype = C.c_int

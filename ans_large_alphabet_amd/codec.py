@@ -422,6 +422,120 @@ class _Codec:
             raise L.AnsxError(st, self.name() + ".next_geq_dev")
         return int(found.value)
 
+    # ---- batches of gap-coded lists: bases, ids of ranges, search by value (include/ansx.h)
+    def encode_batch_gaps_bases_dev(self, in_ptr, offsets, out_ptr, out_capacity, bases_ptr, bases_capacity, stream=None):
+        """encode_batch_gaps_dev that also writes the block bases of every list: list i's nb_i + 1 bases go to uint32
+        entries [base_offsets[i], base_offsets[i + 1]) of bases_ptr (bases_capacity entries).  Returns (out_offsets,
+        out_bytes, base_offsets), base_offsets np.uint64 of len(lists) + 1 (the last is the total).  bases_ptr=None
+        with bases_capacity=0 is a size query: nothing is encoded and only base_offsets is returned.  A smaller
+        bases_capacity raises AnsxError(ERR_CAPACITY) with .needed = the total and .base_offsets before anything is
+        encoded; .index is that of encode_batch_gaps_dev."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise ValueError("offsets needs at least one entry (count + 1)")
+        count = offsets.size - 1
+        out_offsets = np.zeros(count + 1, dtype=np.uint64)
+        out_bytes = np.zeros(count, dtype=np.uint64)
+        base_offsets = np.zeros(count + 1, dtype=np.uint64)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        total, nbases = C.c_size_t(0), C.c_size_t(unset)
+        bad = C.c_size_t(count)
+        st = L.lib().ansx_encode_batch_gaps_bases_dev(
+            self._ctx().handle, self.KIND, self.f, in_ptr, offsets.ctypes.data, count, out_ptr, int(out_capacity),
+            out_offsets.ctypes.data, out_bytes.ctypes.data if count else None, C.byref(total), C.byref(bad),
+            C.byref(self.opts), bases_ptr, int(bases_capacity), base_offsets.ctypes.data, C.byref(nbases), stream)
+        short = nbases.value != unset and nbases.value > int(bases_capacity)
+        if st == L.ERR_CAPACITY and short and bases_ptr is None and int(bases_capacity) == 0:
+            return base_offsets
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".encode_batch_gaps_bases_dev")
+            err.index = int(bad.value) if bad.value < count else None
+            if st == L.ERR_CAPACITY and short:
+                err.needed = int(nbases.value)
+                err.base_offsets = base_offsets
+            raise err
+        return out_offsets, out_bytes, base_offsets
+
+    @staticmethod
+    def _batch_bases(ptrs, bases_ptrs, nbases):
+        bptrs = np.ascontiguousarray(bases_ptrs, dtype=np.uint64).reshape(-1)
+        nb = np.ascontiguousarray(nbases, dtype=np.uint64).reshape(-1)
+        if not ptrs.size == bptrs.size == nb.size:
+            raise ValueError("in_ptrs, bases_ptrs and nbases differ in length (%d, %d, %d)" % (ptrs.size, bptrs.size, nb.size))
+        return bptrs, nb
+
+    def decode_batch_ranges_sums_dev(self, in_ptrs, in_bytes, bases_ptrs, nbases, src, first, count, out_ptr, out_capacity,
+                                     stream=None):
+        """decode_batch_ranges_dev returning docids: range i is sums[first[i] : first[i] + count[i]] of the running
+        sums of container src[i], computed from the touched blocks and their entries of that container's block bases,
+        the nbases[j] uint32 at bases_ptrs[j] (arrays as long as in_ptrs; those of a container no range names are not
+        looked at).  Arguments, return value and error attributes are otherwise those of decode_batch_ranges_dev;
+        ERR_ARG with .bad_container for an nbases[j] that is not nblocks + 1, ERR_FORMAT with .bad_container =
+        len(in_ptrs) if the bases of a touched block are not its container's.  (.container / .range repeat
+        .bad_container / .bad_range.)"""
+        ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
+        if ptrs.size != sizes.size:
+            raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
+        bptrs, nb = self._batch_bases(ptrs, bases_ptrs, nbases)
+        src = np.ascontiguousarray(src, dtype=np.uint32).reshape(-1)
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+        count = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
+        if not src.size == first.size == count.size:
+            raise ValueError("src, first and count differ in length (%d, %d, %d)" % (src.size, first.size, count.size))
+        nc, nr = ptrs.size, src.size
+        offsets = np.zeros(nr + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c, bad_r = C.c_size_t(unset), C.c_size_t(unset)
+        st = L.lib().ansx_decode_batch_ranges_sums_dev(
+            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None,
+            bptrs.ctypes.data if nc else None, nb.ctypes.data if nc else None, nc,
+            src.ctypes.data if nr else None, first.ctypes.data if nr else None, count.ctypes.data if nr else None, nr,
+            out_ptr, int(out_capacity), offsets.ctypes.data, C.byref(total), C.byref(bad_c), C.byref(bad_r), stream)
+        if st == L.ERR_CAPACITY and out_ptr is None and int(out_capacity) == 0:
+            return offsets
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".decode_batch_ranges_sums_dev")
+            err.bad_container = err.container = int(bad_c.value) if bad_c.value != unset else None
+            err.bad_range = err.range = int(bad_r.value) if bad_r.value != unset else None
+            if st == L.ERR_CAPACITY:
+                err.needed = int(total.value)
+                err.offsets = offsets
+            raise err
+        return offsets
+
+    def next_geq_batch_dev(self, in_ptrs, in_bytes, bases_ptrs, nbases, src, targets_ptr, pos_ptr, ids_ptr, stream=None):
+        """next_geq_dev over a batch: target i, the uint32 at targets_ptr + 4 i (device), is looked up in the list of
+        container src[i] (host array; its length is the number of targets) of the batch in_ptrs / in_bytes /
+        bases_ptrs / nbases (as decode_batch_ranges_sums_dev).  Position -> the uint64 at pos_ptr, id -> the uint32 at
+        ids_ptr (device arrays of len(src); either may be None); a target above its list's last id gives that list's n
+        and NO_ID.  Returns the number of targets found.  An AnsxError carries .bad_container / .bad_target where the
+        call set them (None otherwise; .container / .target repeat them)."""
+        ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
+        if ptrs.size != sizes.size:
+            raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
+        bptrs, nb = self._batch_bases(ptrs, bases_ptrs, nbases)
+        src = np.asarray(src)
+        if src.size and src.dtype.kind not in "ui":
+            raise ValueError("src must hold integers, got dtype %s" % src.dtype)
+        src = np.ascontiguousarray(src, dtype=np.uint32).reshape(-1)
+        nc, nt = ptrs.size, src.size
+        found = C.c_uint64(0)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c, bad_t = C.c_size_t(unset), C.c_size_t(unset)
+        st = L.lib().ansx_next_geq_batch_dev(
+            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None,
+            bptrs.ctypes.data if nc else None, nb.ctypes.data if nc else None, nc, src.ctypes.data if nt else None,
+            targets_ptr, nt, pos_ptr, ids_ptr, C.byref(found), C.byref(bad_c), C.byref(bad_t), stream)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".next_geq_batch_dev")
+            err.bad_container = err.container = int(bad_c.value) if bad_c.value != unset else None
+            err.bad_target = err.target = int(bad_t.value) if bad_t.value != unset else None
+            raise err
+        return int(found.value)
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

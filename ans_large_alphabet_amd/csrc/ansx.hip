@@ -34,6 +34,8 @@
 #include "ansx_sums.h"
 #include "ansx_rangesums.h"
 #include "ansx_nextgeq.h"
+#include "ansx_batchrangesums.h"
+#include "ansx_batchnextgeq.h"
 
 namespace {
 
@@ -2441,10 +2443,20 @@ struct PassTail {
     size_t a_bytes;
     const void* b;  // the index over them: u32 pstart per source + 1 (batch_pass), u64 wpos per piece + 1 (batch_ranges_group)
     size_t b_bytes;
+    const void* c = nullptr;  // the sums calls only: ansx_brs_src per source, the caller's bases;
+    size_t c_bytes = 0;       // no section and no byte of the upload where there is none
+};
+// where a pass's plan lies on the device: its blocks, the decoders' table, the tail's section c and the flag word of
+// k_batch_index / k_batch_copy
+struct PassDev {
+    const ansx_batch_blk* B;
+    const ansx_blk_out* O;
+    const u8* c;
+    const u32* dflags;
 };
 // the pass's gather: enqueues the copy from the decoded work list to the caller's buffer (da, db: the tail's sections a
 // and b on the device, 16-byte aligned; the decode's flags)
-typedef std::function<int(const u32* list, const u8* da, const u8* db, const u32* gflags)> PassGather;
+typedef std::function<int(const u32* list, const u8* da, const u8* db, const u32* gflags, const PassDev& D)> PassGather;
 
 // The part every pass shares (ansx_decode_batch_dev, ansx_decode_batch_ranges_dev): S, B, O -- the pass's sources, its
 // T blocks and the decoders' table over a work list of wl ints -- and the tail go up in one copy; k_batch_index and
@@ -2457,10 +2469,11 @@ int pass_decode(ansx_ctx* c, int kind, int f, const ansx_container_header& H0, a
 {
     int rc;
     const u32 T = (u32)B.size(), nr = (u32)S.size();
-    // the pass's plan, one upload: flags[4] | sources | blocks | table | the tail's two sections
+    // the pass's plan, one upload: flags[4] | sources | blocks | table | the tail's two sections (| its third, if any)
     const size_t o_s = 16, o_b = rup(o_s + sizeof(ansx_batch_src) * nr, 16), o_o = rup(o_b + sizeof(ansx_batch_blk) * T, 16);
     const size_t o_r = rup(o_o + sizeof(ansx_blk_out) * T, 16), o_p = rup(o_r + tail.a_bytes, 16);
-    const size_t plan_bytes = o_p + tail.b_bytes;
+    const size_t o_c = rup(o_p + tail.b_bytes, 16);
+    const size_t plan_bytes = tail.c_bytes ? o_c + tail.c_bytes : o_p + tail.b_bytes;
     if ((rc = ensure_pin(c, plan_bytes))) return rc;
     u8* hb = c->rng_pin;  // (no copy out of it is pending: the previous pass ended in a synchronisation)
     memset(hb, 0, o_s);
@@ -2469,6 +2482,7 @@ int pass_decode(ansx_ctx* c, int kind, int f, const ansx_container_header& H0, a
     memcpy(hb + o_o, O.data(), sizeof(ansx_blk_out) * T);
     memcpy(hb + o_r, tail.a, tail.a_bytes);
     memcpy(hb + o_p, tail.b, tail.b_bytes);
+    if (tail.c_bytes) memcpy(hb + o_c, tail.c, tail.c_bytes);
     if ((rc = ensure(c, c->rng_plan, plan_bytes))) return rc;
     u8* dplan = (u8*)c->rng_plan.p;
     HIPCHK(c, hipMemcpyAsync(dplan, hb, plan_bytes, hipMemcpyHostToDevice, s));
@@ -2482,7 +2496,8 @@ int pass_decode(ansx_ctx* c, int kind, int f, const ansx_container_header& H0, a
         return ANSX_OK;
     };
     const SubGather gather = [&](const u32* list, const u32* gflags) -> int {
-        return pass_gather(list, dplan + o_r, dplan + o_p, gflags);
+        const PassDev D = { (const ansx_batch_blk*)(dplan + o_b), (const ansx_blk_out*)(dplan + o_o), dplan + o_c, dflags };
+        return pass_gather(list, dplan + o_r, dplan + o_p, gflags, D);
     };
     // (any n that makes make_plan lay out exactly T blocks: the table says how long each is)
     return decode_sub(c, kind, f, Hs, (u64)(T - 1) * H0.block_ints + O.back().n, T, cap_pay, wl, (const ansx_blk_out*)(dplan + o_o),
@@ -2536,7 +2551,7 @@ int batch_pass(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& src, c
     const u32 nr = (u32)R.size();
     // the tail: gather pieces | first piece per source
     const PassTail tail = { R.data(), sizeof(ansx_range_piece) * nr, pstart.data(), 4 * ((size_t)nr + 1) };
-    const PassGather gather = [&](const u32* list, const u8* da, const u8* db, const u32* gflags) -> int {
+    const PassGather gather = [&](const u32* list, const u8* da, const u8* db, const u32* gflags, const PassDev&) -> int {
         const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
         LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, (const ansx_range_piece*)da, (const u32*)db, nr,
             (u32)npieces, d_out, gflags);
@@ -2613,10 +2628,12 @@ int decode_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const siz
 struct BrRun {     // consecutive touched blocks b0..b1 of referenced container r, inside one pass
     u32 r, b0, b1, pass;
     u64 wl;        // its first int in the pass's work list (a multiple of 4)
+    u32 k0;        // ... and block b0's number among the pass's blocks
 };
 struct BrPiece {   // a range, or the part of one that lies in one run
     u32 pass;
     u64 src, dst, count;
+    u32 k;         // the block of the pass its first int lies in
 };
 
 // The union of one container's block spans sp[0..m) (first block << 32 | last block) as ascending stretches of
@@ -2676,7 +2693,7 @@ void br_runs(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, const
         for (const auto& st : stretch)
             for (u32 b = st.first; b <= st.second;) {
                 const u32 take = (u32)std::min<u64>((u64)st.second - b + 1, PB - pb);
-                runs->push_back({ (u32)r, b, b + take - 1, pass, wl });
+                runs->push_back({ (u32)r, b, b + take - 1, pass, wl, pb });
                 wl += rup(std::min<u64>(n, ((u64)b + take) * bi) - (u64)b * bi, 4);
                 pb += take;
                 b += take;
@@ -2686,10 +2703,11 @@ void br_runs(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, const
 }
 
 // Every range's pieces, one per run it crosses (runs cut from one stretch of blocks follow each other), bucketed by
-// pass in range order: pieces PP and their counts PC, pass p's from pfirst[p] to pfirst[p + 1].
+// pass in range order: pieces PP and their counts PC, pass p's from pfirst[p] to pfirst[p + 1].  PK (optional): the
+// block of its pass every piece starts in.
 void br_pieces(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, const u64* first, const u32* cnt,
     const std::vector<u64>& off, const std::vector<u32>& ids, u64 bi, const std::vector<BrRun>& runs,
-    std::vector<ansx_piece>* PP, std::vector<u64>* PC, std::vector<u64>* pfirst)
+    std::vector<ansx_piece>* PP, std::vector<u64>* PC, std::vector<u64>* pfirst, std::vector<u32>* PK = nullptr)
 {
     const u32 npass = runs.back().pass + 1;
     std::vector<BrPiece> pieces;
@@ -2705,7 +2723,7 @@ void br_pieces(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, con
         for (; left; k++) {
             const BrRun& rn = runs[k];
             const u64 take = std::min<u64>(left, std::min<u64>(n, ((u64)rn.b1 + 1) * bi) - pos);
-            pieces.push_back({ rn.pass, rn.wl + (pos - (u64)rn.b0 * bi), dst, take });
+            pieces.push_back({ rn.pass, rn.wl + (pos - (u64)rn.b0 * bi), dst, take, rn.k0 + ((u32)(pos / bi) - rn.b0) });
             (*pfirst)[rn.pass + 1]++;
             pos += take, dst += take, left -= take;
         }
@@ -2713,18 +2731,49 @@ void br_pieces(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, con
     for (u32 p = 0; p < npass; p++) (*pfirst)[p + 1] += (*pfirst)[p];
     PP->resize(pieces.size());
     PC->resize(pieces.size());
+    if (PK) PK->resize(pieces.size());
     std::vector<u64> put(pfirst->begin(), pfirst->end() - 1);
     for (const BrPiece& q : pieces) {  // (stable: range order inside a pass)
         (*PP)[put[q.pass]] = { q.src, q.dst };
+        if (PK) (*PK)[put[q.pass]] = q.k;
         (*PC)[put[q.pass]++] = q.count;
     }
 }
 
+// What the sums calls add to a group (ansx_batchrangesums.h): the caller's bases of every
+// referenced container, and for ansx_next_geq_batch_dev the targets and outputs k_ngb_search takes in the gather's place
+struct BrSums {
+    const std::vector<const u32*>* bases;
+    const u32* d_targets;
+    u64* d_pos;
+    u32* d_ids;
+};
+
+// The work list of a pass of T blocks (geometry bi; D: its plan on the device, section c the sources' bases) -> its
+// running sums in place, every block from its own container's base, and the check of the bases into gflags.  Enqueued
+// between the pass's decode and its gather; no synchronisation.  range_sums_scan's shapes and switch.
+int batch_sums_scan(ansx_ctx* c, u32* list, u64 bi, u32 T, const PassDev& D, u64* agg, u32* gflags, hipStream_t s)
+{
+    const ansx_brs_src* SB = (const ansx_brs_src*)D.c;
+    if (bi <= ANSX_RS_CHUNK) {
+        LAUNCH(c, "k_brs_scan_small", k_brs_scan_small, (T + 3) / 4, ANSX_RS_NT, 0, s, list, D.O, D.B, SB, T, gflags);
+    } else if (bi <= range_sums_wg_max(c)) {
+        LAUNCH(c, "k_brs_scan_block", k_brs_scan_block, T, ANSX_RS_NT, 0, s, list, D.O, D.B, SB, gflags);
+    } else {
+        const u32 tpb = (u32)((bi + ANSX_RS_TILE - 1) / ANSX_RS_TILE), grid = T * tpb;
+        LAUNCH(c, "k_brs_reduce", k_brs_reduce, grid, ANSX_RS_NT, 0, s, (const u32*)list, D.O, tpb, agg, (const u32*)gflags);
+        LAUNCH(c, "k_brs_carry", k_brs_carry, T, ANSX_RS_NT, 0, s, agg, tpb * (ANSX_RS_NT / 64u), D.B, SB, gflags);
+        LAUNCH(c, "k_brs_apply", k_brs_apply, grid, ANSX_RS_NT, 0, s, list, D.O, tpb, (const u64*)agg, (const u32*)gflags);
+    }
+    return ANSX_OK;
+}
+
 // The ranges `ids` (non-empty, in range order) of one geometry; rs: the referenced containers, rid[i] / off[i]: range
-// i's container among them and its place in d_out.
+// i's container among them and its place in d_out.  X: the sums calls (the work list scanned in front of the gather; with
+// targets, off[i] is the target's index and k_ngb_search runs in the gather's place).
 int batch_ranges_group(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& rs, const std::vector<u32>& rid,
     const u64* first, const u32* cnt, const std::vector<u64>& off, const std::vector<u32>& ids, u32 PB, u32* d_out,
-    hipStream_t s)
+    hipStream_t s, const BrSums* X = nullptr)
 {
     int rc;
     const ansx_container_header& H0 = rs[rid[ids[0]]].H;
@@ -2734,17 +2783,20 @@ int batch_ranges_group(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>
     br_runs(rs, rid, first, cnt, ids, bi, PB, &runs);
     std::vector<ansx_piece> PP;
     std::vector<u64> PC, pfirst;
-    br_pieces(rs, rid, first, cnt, off, ids, bi, runs, &PP, &PC, &pfirst);
+    std::vector<u32> PK;  // (ansx_next_geq_batch_dev: every piece's block of its pass)
+    const bool search = X && X->d_targets;
+    br_pieces(rs, rid, first, cnt, off, ids, bi, runs, &PP, &PC, &pfirst, search ? &PK : nullptr);
     const u32 npass = runs.back().pass + 1;
 
     std::vector<ansx_batch_src> S;
     std::vector<ansx_batch_blk> B;
     std::vector<ansx_blk_out> O;
     std::vector<u64> wpos;
+    std::vector<ansx_brs_src> SB;  // (the sums calls: the bases of the pass's sources, beside S)
     size_t k = 0;
     for (u32 p = 0; p < npass; p++) {
         // the pass's sources (one per container), blocks and table, as batch_pass builds them
-        S.clear(), B.clear(), O.clear();
+        S.clear(), B.clear(), O.clear(), SB.clear();
         u64 cap_pay = 0, wl_pass = 0;
         u32 sblocks = 0;  // blocks of the source being filled
         ansx_container_header Hs = H0;
@@ -2760,6 +2812,7 @@ int batch_ranges_group(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>
                 close_source();
                 S.push_back({ cs.base, cs.lay.ckoff_off, cs.lay.ckstate_off, cs.lay.hint_off, cs.lay.payload_off,
                     cs.H.payload_bytes, cs.nblocks, 0 });
+                if (X) SB.push_back({ (u64)(uintptr_t)(*X->bases)[rn.r], cs.nblocks, 0 });
                 Hs.max_nsyms = std::max(Hs.max_nsyms, cs.H.max_nsyms);
                 Hs.max_log2_frame = std::max(Hs.max_log2_frame, cs.H.max_log2_frame);
                 Hs.max_present_m1 = std::max(Hs.max_present_m1, cs.H.max_present_m1);
@@ -2780,8 +2833,27 @@ int batch_ranges_group(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>
         for (u64 q = 0; q < np; q++) wpos[q] = ints, ints += PC[pfirst[p] + q];
         wpos[np] = ints;
         // the tail: pieces | their exclusive prefix over the pass
-        const PassTail tail = { PP.data() + pfirst[p], sizeof(ansx_piece) * np, wpos.data(), 8 * (np + 1) };
-        const PassGather gather = [&](const u32* list, const u8* da, const u8* db, const u32* gflags) -> int {
+        PassTail tail = { PP.data() + pfirst[p], sizeof(ansx_piece) * np, wpos.data(), 8 * (np + 1) };
+        const u32 T = (u32)B.size();
+        u64* agg = nullptr;
+        if (X) {
+            tail.c = SB.data(), tail.c_bytes = sizeof(ansx_brs_src) * SB.size();
+            if ((rc = range_sums_workspace(c, bi, T, &agg))) return rc;  // (here: growing it may wait for the device)
+        }
+        if (search) {
+            // a piece is one int at the start of a block of the pass: which block takes the place of the prefix, which
+            // only the gather needs
+            tail.b = PK.data() + pfirst[p], tail.b_bytes = 4 * np;
+        }
+        const PassGather gather = [&](const u32* list, const u8* da, const u8* db, const u32* gflags, const PassDev& D) -> int {
+            // (the sums calls: the work list becomes ids first, in place; the scan reports foreign bases in gflags)
+            if (X && (rc = batch_sums_scan(c, (u32*)list, bi, T, D, agg, (u32*)gflags, s))) return rc;
+            if (search) {
+                LAUNCH(c, "k_ngb_search", k_ngb_search, (u32)((np + ANSX_NGB_NT - 1) / ANSX_NGB_NT), ANSX_NGB_NT, 0, s, list, D.O,
+                    D.B, T, bi, (const ansx_piece*)da, (const u32*)db, (u32)np, X->d_targets, X->d_pos, X->d_ids, gflags,
+                    D.dflags);
+                return ANSX_OK;
+            }
             const u32 grid = (u32)std::min<u64>((ints + ANSX_PIECE_CHUNK - 1) / ANSX_PIECE_CHUNK, 1u << 20);
             LAUNCH(c, "k_piece_gather", k_piece_gather, grid, 256, 0, s, list, (const ansx_piece*)da, (const u64*)db, (u32)np,
                 ints, d_out, gflags);
@@ -2792,15 +2864,23 @@ int batch_ranges_group(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>
     return ANSX_OK;
 }
 
-int decode_batch_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
-    const u32* src, const u64* first, const u32* cnt, size_t nranges, u32* d_out, size_t cap, u64* offsets, u64* total_ints,
-    size_t* bad_container, size_t* bad_range, hipStream_t s)
+// The front half, which ansx_next_geq_batch_dev shares (src: the container every range or target names): the referenced
+// containers `ref`, every range's place among them `rid`, and their checked headers `rs`.  nbases (the sums calls): every
+// referenced container's count of bases against its blocks, behind the header checks.
+struct BrFront {
+    std::vector<u32> ref, rid;
+    std::vector<BatchSrc> rs;
+};
+int batch_ranges_front(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
+    const u32* src, size_t nranges, const size_t* nbases, BrFront* F, size_t* bad_container, hipStream_t s)
 {
     int rc;
     // the referenced containers, in batch order, and every range's place among them (rid); nothing below looks at any
     // other container.  A batch that is not much larger than the query is marked in an array over its positions, a
     // larger one is found by sorting the names.
-    std::vector<u32> ref, rid(nranges);
+    std::vector<u32>& ref = F->ref;
+    std::vector<u32>& rid = F->rid;
+    rid.resize(nranges);
     if (count <= 4 * nranges + 1024) {
         std::vector<u32> slot(count, 0);
         for (size_t i = 0; i < nranges; i++) slot[src[i]] = 1;
@@ -2830,7 +2910,8 @@ int decode_batch_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, co
     HIPCHK(c, hipStreamSynchronize(s));
 
     // decode_batch's checks on every one of them, in batch order
-    std::vector<BatchSrc> rs(nref);
+    std::vector<BatchSrc>& rs = F->rs;
+    rs.resize(nref);
     for (size_t j = 0; j < nref; j++) {
         BatchSrc& b = rs[j];
         const size_t nb = in_bytes[ref[j]];
@@ -2844,6 +2925,38 @@ int decode_batch_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, co
         b.base = (u64)(uintptr_t)d_ins[ref[j]];
         b.nblocks = P.g.nblocks;
     }
+    if (nbases)
+        for (size_t j = 0; j < nref; j++)
+            if (nbases[ref[j]] != (size_t)rs[j].nblocks + 1) {
+                if (bad_container) *bad_container = ref[j];
+                return ANSX_ERR_ARG;
+            }
+    return ANSX_OK;
+}
+
+// the geometry a container's blocks are grouped by: block_ints, restart interval, compaction, restart-point format
+std::array<u32, 4> br_geometry(const ansx_container_header& H)
+{
+    return { H.block_ints, H.ckpt_interval, (H.kind >> 8) & 1u, (H.kind >> 9) & 1u };
+}
+
+// bases (the sums call): d_bases / nbases of every container of the batch, HOST arrays
+struct BatchBases {
+    const u32* const* d;
+    const size_t* n;
+};
+
+int decode_batch_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
+    const u32* src, const u64* first, const u32* cnt, size_t nranges, u32* d_out, size_t cap, u64* offsets, u64* total_ints,
+    size_t* bad_container, size_t* bad_range, hipStream_t s, const BatchBases* bases = nullptr)
+{
+    int rc;
+    BrFront F;
+    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, src, nranges, bases ? bases->n : nullptr, &F,
+             bad_container, s)))
+        return rc;
+    const std::vector<u32>& rid = F.rid;
+    const std::vector<BatchSrc>& rs = F.rs;
     // every range against its own container's n; the offsets and the total
     std::vector<u64> off(nranges + 1);
     u64 total = 0;
@@ -2866,16 +2979,84 @@ int decode_batch_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, co
     std::map<std::array<u32, 4>, std::vector<u32>> groups;
     for (size_t i = 0; i < nranges; i++) {
         if (!cnt[i]) continue;
-        const ansx_container_header& H = rs[rid[i]].H;
-        groups[{ H.block_ints, H.ckpt_interval, (H.kind >> 8) & 1u, (H.kind >> 9) & 1u }].push_back((u32)i);
+        groups[br_geometry(rs[rid[i]].H)].push_back((u32)i);
     }
+    std::vector<const u32*> rbases;  // (the sums call: the bases of the referenced containers)
+    BrSums X = { &rbases, nullptr, nullptr, nullptr };
+    if (bases)
+        for (const u32 j : F.ref) rbases.push_back(bases->d[j]);
     const u32 PB = c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT;
     for (const auto& gr : groups) {
-        if ((rc = batch_ranges_group(c, kind, f, rs, rid, first, cnt, off, gr.second, PB, d_out, s))) {
+        if ((rc = batch_ranges_group(c, kind, f, rs, rid, first, cnt, off, gr.second, PB, d_out, s, bases ? &X : nullptr))) {
             if (rc == ANSX_ERR_FORMAT && bad_container) *bad_container = count;  // (found on the device: which one is not known)
             return rc;
         }
     }
+    return ANSX_OK;
+}
+
+// ansx_next_geq_batch_dev (ansx_batchnextgeq.h): the front half above over the lists the targets
+// name -> k_ngb_locate, a lane per target -> ONE read-back of the located blocks, checked -> the found targets as ranges
+// of one int at the start of their blocks, destination the target's own index -> the passes of the sums call with
+// k_ngb_search in the gather's place.
+int next_geq_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const BatchBases& bases,
+    size_t count, const u32* src, const u32* d_targets, size_t nt, u64* d_pos, u32* d_ids, u64* found, size_t* bad_container,
+    hipStream_t s)
+{
+    int rc;
+    BrFront F;
+    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, src, nt, bases.n, &F, bad_container, s))) return rc;
+    const size_t nref = F.ref.size();
+    // up: the lists | every target's list; down: every target's block.  24 bytes per referenced container and 8 per
+    // target of workspace, the same again pinned on the host.
+    const size_t o_r = rup(sizeof(ansx_ngb_list) * nref, 16), o_b = rup(o_r + 4 * nt, 16), bytes = o_b + 4 * nt;
+    if ((rc = ensure_pin(c, bytes))) return rc;
+    if ((rc = ensure(c, c->rng_dev, bytes))) return rc;
+    u8* hb = c->rng_pin;  // (no copy out of it is pending: the front half ended in a synchronisation)
+    ansx_ngb_list* hl = (ansx_ngb_list*)hb;
+    std::vector<const u32*> rbases(nref);
+    for (size_t j = 0; j < nref; j++) {
+        rbases[j] = bases.d[F.ref[j]];
+        hl[j] = { (u64)(uintptr_t)rbases[j], F.rs[j].H.n, F.rs[j].nblocks, 0 };
+    }
+    memcpy(hb + o_r, F.rid.data(), 4 * nt);
+    u8* w = (u8*)c->rng_dev.p;
+    HIPCHK(c, hipMemcpyAsync(w, hb, o_r + 4 * nt, hipMemcpyHostToDevice, s));
+    LAUNCH(c, "k_ngb_locate", k_ngb_locate, (u32)((nt + ANSX_NGB_NT - 1) / ANSX_NGB_NT), ANSX_NGB_NT, 0, s,
+        (const ansx_ngb_list*)w, (const u32*)(w + o_r), d_targets, (u32)nt, (u32*)(w + o_b), d_pos, d_ids);
+    HIPCHK(c, hipMemcpyAsync(hb + o_b, w + o_b, 4 * nt, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+
+    // every located block against its list; the found targets as ranges, grouped by geometry
+    const u32* blk = (const u32*)(hb + o_b);
+    std::vector<u64> first(nt), off(nt);
+    std::vector<u32> cnt(nt);
+    std::map<std::array<u32, 4>, std::vector<u32>> groups;
+    u64 nfound = 0;
+    for (size_t i = 0; i < nt; i++) {
+        const BatchSrc& cs = F.rs[F.rid[i]];
+        off[i] = i;
+        if (blk[i] == ANSX_NGB_NONE) {
+            first[i] = 0, cnt[i] = 0;
+            continue;
+        }
+        if (blk[i] >= cs.nblocks) {  // (cannot happen: k_ngb_locate's b is an index below nblocks)
+            if (bad_container) *bad_container = count;
+            return ANSX_ERR_FORMAT;
+        }
+        first[i] = (u64)blk[i] * cs.H.block_ints, cnt[i] = 1;
+        groups[br_geometry(cs.H)].push_back((u32)i);
+        nfound++;
+    }
+    const BrSums X = { &rbases, d_targets, d_pos, d_ids };
+    const u32 PB = c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT;
+    for (const auto& gr : groups) {
+        if ((rc = batch_ranges_group(c, kind, f, F.rs, F.rid, first.data(), cnt.data(), off, gr.second, PB, nullptr, s, &X))) {
+            if (rc == ANSX_ERR_FORMAT && bad_container) *bad_container = count;  // (found on the device: which one is not known)
+            return rc;
+        }
+    }
+    if (found) *found = nfound;
     return ANSX_OK;
 }
 
@@ -3147,13 +3328,31 @@ int sums_run(ansx_ctx* c, u32* d, u64 n, const u64* offs, size_t count, size_t* 
 }
 
 // The gaps of the lists of d_in (offs as for sums_run) -> *gaps, workspace with d_in's alignment; d_in is only read
+// side: a second array of count + 1 entries (ansx_encode_batch_gaps_bases_dev: where every list's bases start) that
+// goes up behind the plan, in front of the call's one synchronisation; d_offs / d_side: where the list starts and that
+// array then lie on the device.
+struct GapsSide {
+    const u64* side;
+    const u64* d_offs;
+    const u64* d_side;
+};
 int gaps_run(ansx_ctx* c, const u32* d_in, u64 n, const u64* offs, size_t count, const u32** gaps, size_t* bad_index,
-    hipStream_t s)
+    hipStream_t s, GapsSide* G = nullptr)
 {
     int rc;
     SumsPlan S;
+    const size_t o_g = rup(16 + 8 * (count + 1), 16), side_bytes = 8 * (count + 1);
+    if (G) {  // (both before sums_prepare: it keeps the pinned image it fills, and bat_hdr is no buffer of an encode)
+        if ((rc = ensure_pin(c, o_g + side_bytes))) return rc;
+        if ((rc = ensure(c, c->bat_hdr, side_bytes))) return rc;
+    }
     if ((rc = sums_prepare(c, (uintptr_t)d_in, n, offs, count, s, &S))) return rc;
     if ((rc = ensure(c, c->sums_ints, 4 * ((size_t)n + 4)))) return rc;
+    if (G) {
+        memcpy(c->rng_pin + o_g, G->side, side_bytes);
+        HIPCHK(c, hipMemcpyAsync(c->bat_hdr.p, c->rng_pin + o_g, side_bytes, hipMemcpyHostToDevice, s));
+        G->d_offs = S.offs, G->d_side = (const u64*)c->bat_hdr.p;
+    }
     const u32* base = (const u32*)((uintptr_t)d_in & ~(uintptr_t)15);
     u32* base_out = (u32*)c->sums_ints.p;
     LAUNCH(c, "k_gaps", k_gaps, S.ntiles, ANSX_SS_NT, 0, s, base, base_out, S.head, n, S.offs, (u32)count, S.flag);
@@ -3665,6 +3864,77 @@ int ansx_decode_batch_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* co
         out_capacity_ints, (u64*)offsets, (u64*)total_ints, bad_container, bad_range, s);
 }
 
+int ansx_decode_batch_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint32_t* const* d_bases, const size_t* nbases, size_t count, const uint32_t* src, const uint64_t* first,
+    const uint32_t* cnt, size_t nranges, uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints,
+    size_t* bad_container, size_t* bad_range, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || count > 0xFFFFFFFFull || nranges > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!src || !first || !cnt || !d_ins || !in_bytes || !d_bases || !nbases)) return ANSX_ERR_ARG;
+    if ((!d_out && out_capacity_ints > 0) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    for (size_t i = 0; i < nranges; i++)
+        if (src[i] >= count) {
+            if (bad_range) *bad_range = i;
+            return ANSX_ERR_ARG;
+        }
+    for (size_t i = 0; i < nranges; i++)  // (only the containers some range names are looked at)
+        if (!d_ins[src[i]] || ((uintptr_t)d_ins[src[i]] & 15u) || !d_bases[src[i]] || ((uintptr_t)d_bases[src[i]] & 3u)) {
+            if (bad_range) *bad_range = i;
+            return ANSX_ERR_ARG;
+        }
+    if (nranges == 0) {
+        if (offsets) offsets[0] = 0;
+        if (total_ints) *total_ints = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const BatchBases bases = { d_bases, nbases };
+    try {
+        return decode_batch_ranges(c, kind, f, d_ins, in_bytes, count, src, (const u64*)first, cnt, nranges, d_out,
+            out_capacity_ints, (u64*)offsets, (u64*)total_ints, bad_container, bad_range, s, &bases);
+    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge query)
+        c->last_hip = (int)hipErrorOutOfMemory;
+        return ANSX_ERR_HIP;
+    }
+}
+
+int ansx_next_geq_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint32_t* const* d_bases, const size_t* nbases, size_t count, const uint32_t* src, const uint32_t* d_targets,
+    size_t ntargets, uint64_t* d_pos, uint32_t* d_ids, uint64_t* found, size_t* bad_container, size_t* bad_target, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || count > 0xFFFFFFFFull || ntargets > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (ntargets > 0 && (!src || !d_targets || !d_ins || !in_bytes || !d_bases || !nbases || (!d_pos && !d_ids)))
+        return ANSX_ERR_ARG;
+    if (((uintptr_t)d_targets & 3u) || ((uintptr_t)d_pos & 7u) || ((uintptr_t)d_ids & 3u)) return ANSX_ERR_ARG;
+    for (size_t i = 0; i < ntargets; i++)
+        if (src[i] >= count) {
+            if (bad_target) *bad_target = i;
+            return ANSX_ERR_ARG;
+        }
+    for (size_t i = 0; i < ntargets; i++)  // (only the lists some target names are looked at)
+        if (!d_ins[src[i]] || ((uintptr_t)d_ins[src[i]] & 15u) || !d_bases[src[i]] || ((uintptr_t)d_bases[src[i]] & 3u)) {
+            if (bad_target) *bad_target = i;
+            return ANSX_ERR_ARG;
+        }
+    if (ntargets == 0) {
+        if (found) *found = 0;
+        return ANSX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const BatchBases bases = { d_bases, nbases };
+    try {
+        return next_geq_batch(c, kind, f, d_ins, in_bytes, bases, count, src, d_targets, ntargets, (u64*)d_pos, d_ids,
+            (u64*)found, bad_container, s);
+    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge query)
+        c->last_hip = (int)hipErrorOutOfMemory;
+        return ANSX_ERR_HIP;
+    }
+}
+
 int ansx_encode_batch_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,
     uint8_t* d_out, size_t out_capacity, uint64_t* out_offsets, uint64_t* out_bytes, size_t* total_bytes, size_t* bad_index,
     const ansx_opts* opts, void* stream)
@@ -3811,6 +4081,52 @@ int ansx_encode_batch_gaps_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_i
         const u32* gaps = nullptr;
         if ((rc = gaps_run(c, d_in + offsets[0], offsets[count] - offsets[0], (const u64*)offsets, count, &gaps, bad_index, s)))
             return rc;
+        std::vector<u64> off(count + 1);  // the lists' places in the workspace
+        for (size_t i = 0; i <= count; i++) off[i] = offsets[i] - offsets[0];
+        return encode_batch(c, P0, opts, gaps, off.data(), count, d_out, out_capacity, (u64*)out_offsets, (u64*)out_bytes,
+            total_bytes, bad_index, s);
+    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge batch)
+        c->last_hip = (int)hipErrorOutOfMemory;
+        return ANSX_ERR_HIP;
+    }
+}
+
+int ansx_encode_batch_gaps_bases_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,
+    uint8_t* d_out, size_t out_capacity, uint64_t* out_offsets, uint64_t* out_bytes, size_t* total_bytes, size_t* bad_index,
+    const ansx_opts* opts, uint32_t* d_bases, size_t bases_capacity, uint64_t* base_offsets, size_t* total_bases, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    Plan P0;
+    int rc = encode_batch_args(c, kind, f, d_in, offsets, count, d_out, bad_index, opts, &P0);
+    if (rc) return rc;
+    if (((uintptr_t)d_bases & 3u) || (!d_bases && bases_capacity > 0)) return ANSX_ERR_ARG;
+    try {
+        // where every list's bases start: a pure function of the offsets and the options
+        const u64 bi = P0.g.block_ints;
+        std::vector<u64> boff(count + 1);
+        u64 nbases = 0;
+        for (size_t i = 0; i < count; i++) {
+            boff[i] = nbases;
+            nbases += (offsets[i + 1] - offsets[i] + bi - 1) / bi + 1;
+        }
+        boff[count] = nbases;
+        if (base_offsets) memcpy(base_offsets, boff.data(), 8 * (count + 1));
+        if (total_bases) *total_bases = (size_t)nbases;
+        if (bases_capacity < nbases) return ANSX_ERR_CAPACITY;
+        if (count == 0) {
+            if (out_offsets) out_offsets[0] = 0;
+            if (total_bytes) *total_bytes = 0;
+            return ANSX_OK;
+        }
+        HIPCHK(c, hipSetDevice(c->device));
+        hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+        const u32* gaps = nullptr;
+        GapsSide G = { boff.data(), nullptr, nullptr };
+        if ((rc = gaps_run(c, d_in + offsets[0], offsets[count] - offsets[0], (const u64*)offsets, count, &gaps, bad_index, s, &G)))
+            return rc;
+        // the ids do not decrease: the id in front of a block is the sum of every gap of its list in front of it
+        LAUNCH(c, "k_rs_batch_ids_bases", k_rs_batch_ids_bases, (u32)((nbases + ANSX_RS_NT - 1) / ANSX_RS_NT), ANSX_RS_NT, 0, s,
+            d_in + offsets[0], G.d_offs, G.d_side, (u32)count, (u32)bi, nbases, d_bases);
         std::vector<u64> off(count + 1);  // the lists' places in the workspace
         for (size_t i = 0; i <= count; i++) off[i] = offsets[i] - offsets[0];
         return encode_batch(c, P0, opts, gaps, off.data(), count, d_out, out_capacity, (u64*)out_offsets, (u64*)out_bytes,

@@ -136,18 +136,14 @@ ANSX_D u32 rs_wave_err(const u32* gflags)
     return (u32)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&gflags[ANSX_G_ERR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-// bi <= ANSX_RS_CHUNK: wave w of workgroup g scans block 4 g + w
-__global__ __launch_bounds__(ANSX_RS_NT) void k_rs_scan_small(u32* __restrict__ list, u64 n_sub, u32 bi, u32 T,
-    const u32* __restrict__ tb, u32 nblocks, const u32* __restrict__ bases, u32* __restrict__ gflags)
+// The bodies of the kernels below, by where a block lies: here at k * bi of the list, in ansx_batchrangesums.h wherever
+// a pass's table puts it.  (ok, seed, end): rs_bases_of's verdict on the block.
+
+// a wave scans the block p[0 .. len), len <= ANSX_RS_CHUNK, on its own
+ANSX_D void rs_wave_block(u32* __restrict__ p, u32 len, u32 lane, bool ok, u32 seed, u32 end, u32* __restrict__ gflags)
 {
-    const u32 lane = threadIdx.x & 63u, k = blockIdx.x * (ANSX_RS_NT / 64u) + (threadIdx.x >> 6);
-    if (k >= T || rs_wave_err(gflags)) return;  // (both the same for the whole wave)
-    const u32 len = rs_block_len(n_sub, bi, k);
-    u32* p = list + (u64)k * bi;
     ansx_rs_items t;
     rs_load(p, len, lane, t);
-    u32 seed, end;
-    const bool ok = rs_bases_of(tb, k, nblocks, bases, &seed, &end);
     u64 inc[4];
     const u64 tot = rs_scan(t, inc);
     if (!ok || (u64)seed + tot != (u64)end) {
@@ -157,18 +153,11 @@ __global__ __launch_bounds__(ANSX_RS_NT) void k_rs_scan_small(u32* __restrict__ 
     rs_store(p, len, lane, t, inc, seed);
 }
 
-// ANSX_RS_CHUNK < bi <= ANSX_RS_WG_MAX: workgroup k scans block k, tile after tile
-__global__ __launch_bounds__(ANSX_RS_NT) void k_rs_scan_block(u32* __restrict__ list, u64 n_sub, u32 bi,
-    const u32* __restrict__ tb, u32 nblocks, const u32* __restrict__ bases, u32* __restrict__ gflags)
+// a workgroup scans the block blk[0 .. blen), tile after tile (wtot: two rows of a total per wave)
+ANSX_D void rs_wg_block(u32* __restrict__ blk, u32 blen, u32 tid, bool ok, u32 seed, u32 end, u64 (*wtot)[ANSX_RS_NT / 64u],
+    u32* __restrict__ gflags)
 {
-    __shared__ u64 wtot[2][ANSX_RS_NT / 64u];
-    __shared__ u32 sh_err;
-    const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, k = blockIdx.x;
-    if (rs_wg_err(gflags, &sh_err, tid)) return;
-    const u32 blen = rs_block_len(n_sub, bi, k), ntile = (blen + ANSX_RS_TILE - 1) / ANSX_RS_TILE;
-    u32* blk = list + (u64)k * bi;
-    u32 seed, end;
-    const bool ok = rs_bases_of(tb, k, nblocks, bases, &seed, &end);
+    const u32 lane = tid & 63u, wave = tid >> 6, ntile = (blen + ANSX_RS_TILE - 1) / ANSX_RS_TILE;
     u64 carry = seed;  // the sum in front of the tile at hand
     ansx_rs_items cur, nxt;
     rs_load(blk + wave * ANSX_RS_CHUNK, rs_chunk_len(blen, wave * ANSX_RS_CHUNK), lane, cur);
@@ -190,6 +179,63 @@ __global__ __launch_bounds__(ANSX_RS_NT) void k_rs_scan_block(u32* __restrict__ 
         if (t + 1 < ntile) cur = nxt;
     }
     if (tid == 0 && (!ok || carry != (u64)end)) rs_flag_format(gflags);
+}
+
+// a workgroup scans the `per` aggregates a[] of one block exclusively from its seed, in place, and checks the end
+ANSX_D void rs_carry_block(u64* __restrict__ a, u32 per, u32 tid, bool ok, u32 seed, u32 end, u64* wsum, u32* __restrict__ gflags)
+{
+    u64 carry = seed;
+    for (u32 base = 0; base < per; base += ANSX_RS_NT * 4u) {
+        const u32 i0 = base + tid * 4u;
+        u64 v[4], s = 0, all;
+#pragma unroll
+        for (u32 q = 0; q < 4; q++) {
+            v[q] = i0 + q < per ? a[i0 + q] : 0ull;
+            s += v[q];
+        }
+        u64 run = carry + dr_block_excl(s, wsum, tid, &all, ansx_op_add());
+#pragma unroll
+        for (u32 q = 0; q < 4; q++) {
+            if (i0 + q < per) a[i0 + q] = run;
+            run += v[q];
+        }
+        carry += all;
+    }
+    if (tid == 0 && (!ok || carry != (u64)end)) rs_flag_format(gflags);
+}
+
+// a wave scans the chunk p[0 .. len) from the sum `pre` in front of it
+ANSX_D void rs_apply_chunk(u32* __restrict__ p, u32 len, u32 lane, u32 pre)
+{
+    ansx_rs_items t;
+    rs_load(p, len, lane, t);
+    u64 inc[4];
+    (void)rs_scan(t, inc);
+    rs_store(p, len, lane, t, inc, pre);
+}
+
+// bi <= ANSX_RS_CHUNK: wave w of workgroup g scans block 4 g + w
+__global__ __launch_bounds__(ANSX_RS_NT) void k_rs_scan_small(u32* __restrict__ list, u64 n_sub, u32 bi, u32 T,
+    const u32* __restrict__ tb, u32 nblocks, const u32* __restrict__ bases, u32* __restrict__ gflags)
+{
+    const u32 lane = threadIdx.x & 63u, k = blockIdx.x * (ANSX_RS_NT / 64u) + (threadIdx.x >> 6);
+    if (k >= T || rs_wave_err(gflags)) return;  // (both the same for the whole wave)
+    u32 seed, end;
+    const bool ok = rs_bases_of(tb, k, nblocks, bases, &seed, &end);
+    rs_wave_block(list + (u64)k * bi, rs_block_len(n_sub, bi, k), lane, ok, seed, end, gflags);
+}
+
+// ANSX_RS_CHUNK < bi <= ANSX_RS_WG_MAX: workgroup k scans block k, tile after tile
+__global__ __launch_bounds__(ANSX_RS_NT) void k_rs_scan_block(u32* __restrict__ list, u64 n_sub, u32 bi,
+    const u32* __restrict__ tb, u32 nblocks, const u32* __restrict__ bases, u32* __restrict__ gflags)
+{
+    __shared__ u64 wtot[2][ANSX_RS_NT / 64u];
+    __shared__ u32 sh_err;
+    const u32 tid = threadIdx.x, k = blockIdx.x;
+    if (rs_wg_err(gflags, &sh_err, tid)) return;
+    u32 seed, end;
+    const bool ok = rs_bases_of(tb, k, nblocks, bases, &seed, &end);
+    rs_wg_block(list + (u64)k * bi, rs_block_len(n_sub, bi, k), tid, ok, seed, end, wtot, gflags);
 }
 
 // Phase 1, a wave per chunk: its 64-bit sum -> agg.  per_block == 1 (bi <= ANSX_RS_CHUNK, ansx_block_bases_dev only):
@@ -226,25 +272,7 @@ __global__ __launch_bounds__(ANSX_RS_NT) void k_rs_carry(u64* __restrict__ agg, 
     if (rs_wg_err(gflags, &sh_err, tid)) return;
     u32 seed, end;
     const bool ok = rs_bases_of(tb, k, nblocks, bases, &seed, &end);
-    u64* a = agg + (u64)k * per;
-    u64 carry = seed;
-    for (u32 base = 0; base < per; base += ANSX_RS_NT * 4u) {
-        const u32 i0 = base + tid * 4u;
-        u64 v[4], s = 0, all;
-#pragma unroll
-        for (u32 q = 0; q < 4; q++) {
-            v[q] = i0 + q < per ? a[i0 + q] : 0ull;
-            s += v[q];
-        }
-        u64 run = carry + dr_block_excl(s, wsum, tid, &all, ansx_op_add());
-#pragma unroll
-        for (u32 q = 0; q < 4; q++) {
-            if (i0 + q < per) a[i0 + q] = run;
-            run += v[q];
-        }
-        carry += all;
-    }
-    if (tid == 0 && (!ok || carry != (u64)end)) rs_flag_format(gflags);
+    rs_carry_block(agg + (u64)k * per, per, tid, ok, seed, end, wsum, gflags);
 }
 
 // Phase 3, the geometry of k_rs_reduce's tiles: every chunk scanned from its carry and stored over itself
@@ -257,13 +285,7 @@ __global__ __launch_bounds__(ANSX_RS_NT) void k_rs_apply(u32* __restrict__ list,
     const u64 off = (u64)(blockIdx.x % tpb) * ANSX_RS_TILE + wave * ANSX_RS_CHUNK;
     const u32 len = rs_chunk_len(rs_block_len(n_sub, bi, k), off);
     if (!len) return;
-    u32* p = list + (u64)k * bi + off;
-    ansx_rs_items t;
-    rs_load(p, len, lane, t);
-    const u32 pre = (u32)carry[(u64)blockIdx.x * (ANSX_RS_NT / 64u) + wave];
-    u64 inc[4];
-    (void)rs_scan(t, inc);
-    rs_store(p, len, lane, t, inc, pre);
+    rs_apply_chunk(list + (u64)k * bi + off, len, lane, (u32)carry[(u64)blockIdx.x * (ANSX_RS_NT / 64u) + wave]);
 }
 
 // ansx_block_bases_dev, one workgroup: agg[0 .. nblocks * per) scanned inclusively; where block b ends -- behind its

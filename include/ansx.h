@@ -466,6 +466,83 @@ int ansx_next_geq_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in
     size_t nbases, const uint32_t* d_targets, size_t ntargets, uint64_t* d_pos, uint32_t* d_ids, uint64_t* found,
     void* stream);
 
+/* Batches of gap-coded lists: written with their bases, sliced as ids and searched, one call each (DESIGN.md
+ * section 3h).
+ *
+ * ansx_encode_batch_gaps_bases_dev is ansx_encode_batch_gaps_dev for the writer who also wants the block bases of every
+ * list: that call's arguments, then d_bases (DEVICE, 4-byte aligned, bases_capacity entries), base_offsets (HOST,
+ * count + 1 entries, optional) and total_bases (optional).  List i has nb_i = ceil(n_i / block_ints) blocks, block_ints
+ * the value opts resolves to, and its nb_i + 1 bases stand at d_bases[base_offsets[i] .. base_offsets[i + 1]), back to
+ * back in batch order: bases_i[0] = 0, bases_i[b] = ids_i[b * block_ints - 1], bases_i[nb_i] = ids_i[n_i - 1], what
+ * ansx_block_bases_dev returns for container i.  base_offsets is the exclusive prefix sum of nb_i + 1, a pure function
+ * of offsets and the options, computed on the host before any launch.  The bases are read off the ids by one kernel,
+ * a thread per entry, behind the check for decreases; no host round trip is added.  The containers, out_offsets,
+ * out_bytes, *total_bytes, *bad_index, the errors and the no-trace promise are exactly those of
+ * ansx_encode_batch_gaps_dev.  Additional errors: ANSX_ERR_ARG, before the context is touched, for a misaligned d_bases
+ * or d_bases == NULL with bases_capacity > 0; ANSX_ERR_CAPACITY, on the host before any launch, when bases_capacity <
+ * sum(nb_i + 1) -- base_offsets and *total_bases are written then, so d_bases = NULL, bases_capacity = 0 is a size query.
+ * After an error of the encode d_bases is unspecified. */
+int ansx_encode_batch_gaps_bases_dev(ansx_ctx* ctx, int kind, int fidelity, const uint32_t* d_in, const uint64_t* offsets,
+    size_t count, uint8_t* d_out, size_t out_capacity, uint64_t* out_offsets, uint64_t* out_bytes, size_t* total_bytes,
+    size_t* bad_index, const ansx_opts* opts, uint32_t* d_bases, size_t bases_capacity, uint64_t* base_offsets,
+    size_t* total_bases, void* stream);
+
+/* ansx_decode_batch_ranges_sums_dev: ansx_decode_batch_ranges_dev returning ids.  Range i is s[first[i]] ..
+ * s[first[i] + cnt[i] - 1] of container src[i], s what ansx_decode_sums_dev returns for that container.  d_bases[i]
+ * (HOST array of `count` DEVICE pointers, 4-byte aligned) are the block bases of container i and nbases[i] (HOST) their
+ * number; d_bases + base_offsets[i] of the writer above feeds it directly.  The layout of d_out, offsets, the size
+ * query, what ranges may look like, mixed geometries, one pointer at several batch positions, the errors and their
+ * order, no trace in the context, the passes and the number of host round trips are ansx_decode_batch_ranges_dev's: the
+ * sums add no synchronisation and no read-back.  Between a pass's decode and its gather the pass's work list is scanned
+ * in place, restarting at every touched block from that block's own container's base.
+ * Selectivity: of an unreferenced container neither d_bases[i] nor nbases[i] is examined (null is allowed); of a
+ * referenced one only entries b and b + 1 of touched blocks b are read.
+ * Additional errors: ANSX_ERR_ARG before the context is touched for a null d_bases or nbases array with nranges > 0, or
+ * a null or misaligned d_bases[i] of a referenced container (*bad_range: the first range naming it); ANSX_ERR_ARG on
+ * the host, after the header checks and before the range checks, if nbases[i] != nblocks_i + 1 for a referenced
+ * container (*bad_container: the first such); ANSX_ERR_FORMAT, found on the device, *bad_container = count, if the
+ * bases of a touched block are not the container's: every touched block is scanned whole and bases[b] + (its sum in 64
+ * bits) must be bases[b + 1].  It travels through the pass's flag word and its read-back and that pass's gather writes
+ * nothing; d_out is unspecified, nothing is written at or beyond d_out + out_capacity_ints. */
+int ansx_decode_batch_ranges_sums_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins,
+    const size_t* in_bytes, const uint32_t* const* d_bases, const size_t* nbases, size_t count, const uint32_t* src,
+    const uint64_t* first, const uint32_t* cnt, size_t nranges, uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets,
+    uint64_t* total_ints, size_t* bad_container, size_t* bad_range, void* stream);
+
+/* ansx_next_geq_batch_dev: ansx_next_geq_dev over a batch.  With s the ids of container src[i], n of them:
+ * d_pos[i] = min{ j : s[j] >= d_targets[i] } (the lower bound: of equal ids the first), d_ids[i] = s[d_pos[i]]; beyond
+ * the last id d_pos[i] = n of that container and d_ids[i] = ANSX_NO_ID.  src is a HOST array of ntargets entries,
+ * d_targets DEVICE (4-byte aligned, read on `stream`), d_pos / d_ids DEVICE (8 / 4-byte aligned; either may be NULL,
+ * not both).  *found (optional): the number of targets found, set on ANSX_OK.  Targets may be unsorted, may repeat and
+ * may name the lists in any order.
+ * How it runs: the headers of the referenced containers in one round trip (the front half of
+ * ansx_decode_batch_ranges_dev); k_ngb_locate, a lane per target, finds the smallest block b of its list with
+ * bases[b + 1] >= t and writes n / ANSX_NO_ID where there is none; ONE read-back of the located blocks, 4 bytes per
+ * target -- one host round trip MORE than ansx_decode_batch_ranges_dev; the host checks every value and runs the plan
+ * of the ranges call over the found targets, one int at the start of each one's block; per pass the decode, the scan of
+ * the sums call and a lower bound over the block's scanned ids, clamped to the block's own length.  When no target is
+ * found no pass runs; the outputs are written on return all the same.
+ * Errors, in this order: before the context is touched, ANSX_ERR_ARG for a null ctx, null arrays or both outputs null
+ * with ntargets > 0, a misaligned d_targets / d_pos / d_ids, count or ntargets > UINT32_MAX, src[i] >= count
+ * (*bad_target = i), then a null or misaligned d_ins[src[i]] (16 bytes) or d_bases[src[i]] (4 bytes) (*bad_target: the
+ * first target naming it).  ntargets == 0: ANSX_OK, *found = 0, nothing launched, the context untouched.  Once the
+ * headers are known: ANSX_ERR_FORMAT with *bad_container for a header that fails the checks, then ANSX_ERR_ARG with
+ * *bad_container if nbases[i] != nblocks_i + 1.  On the device: ANSX_ERR_FORMAT with *bad_container = count for a stream
+ * or index entry of a touched block, or bases that are not the container's at a touched block; the outputs are
+ * unspecified then.  Nothing is ever written outside d_pos[0 .. ntargets) and d_ids[0 .. ntargets).
+ * What the bases promise is word for word ansx_next_geq_dev's: verified at touched blocks only, a wrong entry elsewhere
+ * can misdirect a target undetected, memory safety and termination hold for any content.
+ * Selectivity: an unreferenced container is not examined (null d_ins[i] / d_bases[i] allowed); of a block no target
+ * lands in nothing is read; no kernel's grid grows with count or with a container's block count; the locate step may
+ * read any entry of a REFERENCED container's bases.
+ * Workspace: that of one pass (ANSX_BATCH_PASS_BLOCKS blocks) plus 28 bytes per target (its list, its block, its piece
+ * of the plan) and 96 bytes per referenced container (address, header, and the list's entry for the locate step), and
+ * the same again in pinned host memory. */
+int ansx_next_geq_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint32_t* const* d_bases, const size_t* nbases, size_t count, const uint32_t* src, const uint32_t* d_targets,
+    size_t ntargets, uint64_t* d_pos, uint32_t* d_ids, uint64_t* found, size_t* bad_container, size_t* bad_target,
+    void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
