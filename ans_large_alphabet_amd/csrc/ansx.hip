@@ -187,6 +187,7 @@ struct ansx_ctx {
         bool force_pc = false;        // ANSX_FORCE_PC: the pair kernel for every workgroup of 64 full blocks, however few (tests)
         bool no_pc = false;           // ANSX_NO_PC: the LDS-table encoder as one wave per 16 blocks everywhere (k_encode<1>), no producer / consumer pairs
         int decode_small_ring = 0;    // ANSX_DECODE_SMALL_RING: "never" / "always" (default: by the container's bytes per int)
+        bool chain_old = false;       // ANSX_MODEL_CHAIN=old: every block of k_model_finish reads and raises the call's running maxima itself (no k_model_maxima launch)
         bool setup_old = false;       // ANSX_DECODE_SETUP=old: windowed subtrees in k_parse_prelude_par, scan form of the decoder's table build
         int decode_pair = 0;          // ANSX_DECODE_PAIR: "0"/unset auto, "never", "always" (k_decode_rank2: two blocks per workgroup)
         u32 pair_lds_limit = 0;       // ANSX_DECODE_PAIR_LDS: auto uses the pair kernel up to this many bytes of LDS per workgroup (0: never --
@@ -983,7 +984,9 @@ int launch_fast_model(ansx_ctx* c, const EncodeWs& W, const ModelShape& M, hipSt
     const FinKernel fin = fin_kernel(c, NSP, NT);
     LAUNCH(c, "k_model_finish", fin.kern, be - b0, fin.threads, M.fin_lds, st, g, NSP, NT, (const uint2*)c->pairs.p, (const uint4*)c->attS.p,
         (const u32*)c->attMeta.p, W.blk, (u32*)c->tab32.p, (u8*)c->scratch.p, W.scr_stride, W.mostfreq, W.hints, W.gflags, M.fcap,
-        c->dbg.fast_guard, (const double*)c->lg2i.p, W.geo, NSP > 4096 ? W.hist : (u32*)nullptr, b0, be);
+        c->dbg.fast_guard, (const double*)c->lg2i.p, W.geo, NSP > 4096 ? W.hist : (u32*)nullptr, b0, be, c->dbg.chain_old ? 1u : 0u);
+    if (!c->dbg.chain_old)  // (the call's running maxima: no longer every block's own business)
+        LAUNCH(c, "k_model_maxima", k_model_maxima, (be - b0 + 255) / 256, 256, 0, st, (const ansx_blk*)W.blk, W.gflags, b0, be);
     return ANSX_OK;
 }
 
@@ -3488,7 +3491,7 @@ int ansx_init(int device, ansx_ctx** out)
     }
     static const char* const names[] = { "ANSX_TEST_TABLE16_FIXUP", "ANSX_ENCODE_GTAB16", "ANSX_PARSE_GENERIC", "ANSX_PARSE_WIN", "ANSX_PARSE_FAST",
         "ANSX_DECODE_TABLE", "ANSX_NO_STREAM_LDS", "ANSX_DECODE_MODE", "ANSX_PARSE_STAGE_WORDS", "ANSX_MODEL_FUSED", "ANSX_MODEL_SYNC", "ANSX_NS_HINT", "ANSX_T_HINT", "ANSX_NO_FAST_MODEL", "ANSX_FAST_GUARD", "ANSX_CAND_CHAINS", "ANSX_NEAR_BAND", "ANSX_TEST_NEAR_FLIP", "ANSX_WIDE_RESTART", "ANSX_TEST_WIDE_AT",
-        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP" };
+        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP", "ANSX_MODEL_CHAIN" };
     for (const char* nm : names)
         if (const char* v = getenv(nm)) (void)ansx_debug_set(c, nm, v);
     *out = c;
@@ -3578,6 +3581,11 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
     else if (!strcmp(name, "ANSX_DECODE_SETUP")) {
         if (!value || !value[0] || !strcmp(value, "0")) c->dbg.setup_old = false;
         else if (!strcmp(value, "old")) c->dbg.setup_old = true;
+        else return ANSX_ERR_ARG;
+    }
+    else if (!strcmp(name, "ANSX_MODEL_CHAIN")) {
+        if (!value || !value[0] || !strcmp(value, "0")) c->dbg.chain_old = false;
+        else if (!strcmp(value, "old")) c->dbg.chain_old = true;
         else return ANSX_ERR_ARG;
     }
     else if (!strcmp(name, "ANSX_DECODE_PAIR_LDS")) c->dbg.pair_lds_limit = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;

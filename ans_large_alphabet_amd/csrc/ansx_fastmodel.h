@@ -268,12 +268,16 @@ __global__ __launch_bounds__(64 * ANSX_CAND_WAVES) void k_candidates(ansx_geo g,
 // Anything this path does not cover raises the violation flag and leaves the block without a stream; the host
 // repeats the call on the exact path: undecided after NT candidates, the u16 exit with no earlier success, a
 // frame above 2^16, a comparison inside the guard band (`guard`: ANSX_FAST_GUARD; tests widen it to force the repeat).
+// own_maxima (ANSX_MODEL_CHAIN=old, the comparison form): thread 0 of every block reads the call's four running maxima
+// (gflags) and raises those its block exceeds -- four dependent round trips to one cache line for 16 K blocks, on the
+// thread the workgroup's next barrier waits for: 2.2 of a block's 14 us and 0.036 of the kernel's 0.163 ms on the headline
+// workload.  Otherwise the maxima are k_model_maxima's, from what the blocks leave in blk[].
 template <int IPT, int NTC, int NTH = 256>
 __global__ __launch_bounds__(NTH) void k_model_finish(ansx_geo g, u32 NSP, u32 NT, const uint2* __restrict__ pairs,
     const uint4* __restrict__ srank, const u32* __restrict__ attMeta, ansx_blk* __restrict__ blk,
     u32* __restrict__ tab32, u8* __restrict__ scratch, u64 scr_stride, const u32* __restrict__ mostfreq,
     u32* __restrict__ hints, u32* __restrict__ gflags, u32 cap, double guard, const double* __restrict__ lg2i,
-    const uint2* __restrict__ geo, u32* __restrict__ incbuf, u32 b0, u32 bend)
+    const uint2* __restrict__ geo, u32* __restrict__ incbuf, u32 b0, u32 bend, u32 own_maxima)
 {
     static_assert(IPT % 4 == 0, "table rows are written 16 bytes at a time");
     static_assert(ANSX_FIN_LUT == 512 && (NTH == 256 || NTH == 64), "two table entries per thread (eight in the one-wave form)");
@@ -551,15 +555,17 @@ __global__ __launch_bounds__(NTH) void k_model_finish(ansx_geo g, u32 NSP, u32 N
         B->logM = logM;
         B->resolved = 1;
         if (total != (1u << logM)) atomicOr(&gflags[ANSX_G_ERR], 1u << ANSX_G_VIOL_BIT);  // (cannot happen: the candidate summed to M)
-        // same-address atomics serialise in L2 (16 K blocks): only the few blocks that raise a running maximum issue one
-        if (__hip_atomic_load(&gflags[ANSX_G_MAXLOGM], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < logM)
-            atomicMax(&gflags[ANSX_G_MAXLOGM], logM);
-        if (__hip_atomic_load(&gflags[ANSX_G_MAXNSYMS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ns)
-            atomicMax(&gflags[ANSX_G_MAXNSYMS], ns);
-        if (__hip_atomic_load(&gflags[ANSX_G_MAXSIGMA], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < sigma)
-            atomicMax(&gflags[ANSX_G_MAXSIGMA], sigma);
-        if (__hip_atomic_load(&gflags[ANSX_G_MAXT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (u32)chosen)
-            atomicMax(&gflags[ANSX_G_MAXT], (u32)chosen);
+        // (same-address atomics serialise in L2 (16 K blocks): only the few blocks that raise a running maximum issue one)
+        if (own_maxima) {
+            if (__hip_atomic_load(&gflags[ANSX_G_MAXLOGM], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < logM)
+                atomicMax(&gflags[ANSX_G_MAXLOGM], logM);
+            if (__hip_atomic_load(&gflags[ANSX_G_MAXNSYMS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ns)
+                atomicMax(&gflags[ANSX_G_MAXNSYMS], ns);
+            if (__hip_atomic_load(&gflags[ANSX_G_MAXSIGMA], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < sigma)
+                atomicMax(&gflags[ANSX_G_MAXSIGMA], sigma);
+            if (__hip_atomic_load(&gflags[ANSX_G_MAXT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (u32)chosen)
+                atomicMax(&gflags[ANSX_G_MAXT], (u32)chosen);
+        }
     }
     STAMP(8);
     if (inc_hbm) __threadfence_block();  // (inc[] went to HBM: visible to the workgroup behind the barrier)
@@ -570,4 +576,31 @@ __global__ __launch_bounds__(NTH) void k_model_finish(ansx_geo g, u32 NSP, u32 N
     prelude_emit<IPT, false, true, IPT == 0 ? 8 : 0, NTH>(g, B, ns, logM, inc, off, bits, sh_part, scratch + (u64)b * scr_stride, mostfreq, b, tid, 0, hints, geo);  // (logM <= 16)
 #endif
     STAMP(10);
+}
+
+// The call's running maxima (largest frame, alphabet, present symbols, chosen candidate) of the blocks [b0, bend) that
+// k_model_finish has resolved, from their fields in blk[]: one thread per block, a wave's maxima through one lane -- 256
+// waves touch the four words on the headline workload instead of 16384 workgroups.  Counted are exactly the blocks that
+// reached that point of k_model_finish: `resolved` set and no status (k_sort_entropy marks a block that outgrew the
+// alphabet hint resolved with a status; k_model_finish leaves it alone, and so does this kernel).
+__global__ __launch_bounds__(256) void k_model_maxima(const ansx_blk* __restrict__ blk, u32* __restrict__ gflags, u32 b0, u32 bend)
+{
+    const u32 b = b0 + blockIdx.x * 256u + threadIdx.x;
+    u32 lg = 0, ns = 0, sg = 0, t = 0;
+    bool any = false;
+    if (b < bend) {
+        const ansx_blk* B = &blk[b];
+        if (B->resolved && !B->status) {
+            lg = B->logM, ns = B->max_sym + 1u, sg = B->sigma, t = B->logM - B->m0_log2;
+            any = true;
+        }
+    }
+    const bool wany = __builtin_amdgcn_ballot_w64(any) != 0;
+    lg = wave_max(lg), ns = wave_max(ns), sg = wave_max(sg), t = wave_max(t);
+    if ((threadIdx.x & 63u) == 0 && wany) {
+        if (__hip_atomic_load(&gflags[ANSX_G_MAXLOGM], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < lg) atomicMax(&gflags[ANSX_G_MAXLOGM], lg);
+        if (__hip_atomic_load(&gflags[ANSX_G_MAXNSYMS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ns) atomicMax(&gflags[ANSX_G_MAXNSYMS], ns);
+        if (__hip_atomic_load(&gflags[ANSX_G_MAXSIGMA], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < sg) atomicMax(&gflags[ANSX_G_MAXSIGMA], sg);
+        if (__hip_atomic_load(&gflags[ANSX_G_MAXT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < t) atomicMax(&gflags[ANSX_G_MAXT], t);
+    }
 }

@@ -647,7 +647,10 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
  * ANSX_DECODE_SETUP ("old"; ""/"0"/NULL: the default; anything else: ANSX_ERR_ARG -- the per-block setup of a decode
  * call as it was before the value-array subtree parser and the scan-free table build: windowed subtrees in
  * k_parse_prelude_par whatever the alphabet, one prefix scan per round of symbols in the decoder's table build; for the
- * cross-check test and the paired timing of tests/tools/bench_decode_setup.py);
+ * cross-check test and the paired timing of tests/tools/bench_decode_setup.py), ANSX_MODEL_CHAIN ("old"; ""/"0"/NULL:
+ * the default; anything else: ANSX_ERR_ARG -- the fast model path as it was before k_model_maxima: every block of
+ * k_model_finish reads and raises the call's running maxima itself; for the cross-check test and the paired timing of
+ * tests/tools/bench_model_chain.py);
  * through this call only (round 4): ANSX_NO_PC / ANSX_FORCE_PC / ANSX_NO_PC_AUTO / ANSX_PC_B_PAIRS (the producer /
  * consumer encoder never / whatever the list length / only on request; pairs per workgroup of its two-round shape),
  * ANSX_ENCODE_MODE2, ANSX_DECODE_PAIR, ANSX_DECODE_SMALL_RING (1 never | 2 always), ANSX_FORGET_HINTS, ANSX_NO_BIG_GEO,
