@@ -36,6 +36,9 @@
 #include "ansx_nextgeq.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
+#include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
+
+using namespace ansx_plan;
 
 namespace {
 
@@ -47,10 +50,6 @@ struct DevBuf {
 struct ProfRec {
     std::string name;
     hipEvent_t e0, e1;
-};
-
-struct Layout {  // container layout, a pure function of the geometry (restart-point format included)
-    u64 index_off, ckoff_off, ckstate_off, hint_off, payload_off;
 };
 
 }  // namespace
@@ -106,7 +105,7 @@ struct PinPage {
                 } plain;
             };
             u8 pad0[2048 - 64 - 64];
-            u32 caller_flag;  // 2048: the flag word of decode_dev's caller (decode_sub), read back by its epilogue
+            u32 caller_flag;  // 2048: the flag word of decode_dev's caller (sub_decode), read back by its epilogue
             u8 pad1[1024 - 4];
             u64 planner[8];  // 3072: the scalars of the device planner (decode_device_ranges)
         };
@@ -264,8 +263,6 @@ void prof_end(ansx_ctx* c, hipStream_t s)
         prof_end(ctx, strm);                                                                     \
         HIPCHK(ctx, hipGetLastError());                                                          \
     } while (0)
-
-inline size_t rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // status of a stream / event call of the block-range pipeline (no early return: its caller still has to join)
 int pipe_hip(ansx_ctx* c, hipError_t e)
@@ -2076,9 +2073,12 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
 }
 
 // --------------------------------------------------------------------------------- random access
-// ansx_decode_ranges_dev / ansx_decode_device_ranges_dev: a plan (host- or device-built) ->
-// k_range_index + k_range_copy build a container of the touched blocks only -> decode_dev on it (no cached header in
-// or out) -> k_range_gather into the caller's buffer.
+// ansx_decode_ranges_dev / ansx_decode_device_ranges_dev, their ids variants and ansx_next_geq_dev (DESIGN.md sections
+// 3a, 3f, 3g; the host path: section 5): a front builds the plan -- on the host (ansx_plan.h, range_plan; one upload) or
+// on the device (the k_dr_* planner) -- and fills a RangeTail; range_tail prepares a sub-container of the touched blocks
+// only (sub_prepare), builds it with k_range_index + k_range_copy, and decodes it (sub_decode: decode_dev, no cached
+// header in or out) with the call's way out as the one epilogue: k_range_gather into the caller's buffer, the sums
+// scan in front of it, or the scan and k_ng_search (RangeOut).
 
 // rng_pin holds at least `bytes` (its content is not kept)
 int ensure_pin(ansx_ctx* c, size_t bytes)
@@ -2108,49 +2108,92 @@ int range_source(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, 
     return ANSX_OK;
 }
 
-// What the ranges and batch entries share: a container built on the device from blocks of other containers, decoded to
-// a work list the caller gathers from.  The sub-container has T blocks and n_sub ints in the geometry of header H (any
-// n_sub that makes make_plan lay out exactly T blocks; bout / list_ints: the decoders' table over a list of so many ints,
-// or null / n_sub) and a payload of at most cap_pay bytes.  `build` enqueues the kernels that write it (its plan, its
-// header -- payload_bytes is theirs to fill in -- and where it goes), decode_dev decodes it (no remembered header in or
-// out), `gather` enqueues the copy out of the list (given the decode's flags: it skips when they hold an error).  The
-// gather and the read-back of dflags, the caller's own flag word, ride on the decode's final read-back.
-typedef std::function<int(const Plan& Ps, const ansx_container_header& Hs, u8* sub)> SubBuild;
-typedef std::function<int(const u32* list, const u32* gflags)> SubGather;
-int decode_sub(ansx_ctx* c, int kind, int f, ansx_container_header H, u64 n_sub, u32 T, u64 cap_pay, u64 list_ints,
-    const ansx_blk_out* bout, const u32* dflags, const SubBuild& build, const SubGather& gather, hipStream_t s)
+// The layout of a plan upload: 16-byte-aligned sections back to back in the pinned page, which go to the device in one
+// copy.  add() places a section (none of the three a pass may do without: an empty one is nowhere); its handle gives its typed address on either side once upload_room has found room.
+struct Upload {
+    template <class T> struct Sec {
+        size_t off, bytes;
+    };
+    size_t end = 0;
+    u8 *host = nullptr, *devp = nullptr;
+    template <class T> Sec<T> add(size_t n)
+    {
+        const size_t o = n ? rup(end, 16) : end;  // (an empty section takes no room, not even padding)
+        end = o + sizeof(T) * n;
+        return { o, sizeof(T) * n };
+    }
+    template <class T> T* pin(Sec<T> s) const { return (T*)(host + s.off); }
+    template <class T> T* dev(Sec<T> s) const { return (T*)(devp + s.off); }
+    template <class T> void put(Sec<T> s, const T* p) const { memcpy(host + s.off, p, s.bytes); }
+};
+
+// The pinned page and `buf` hold the sections (no copy out of the page is pending: every user ends in a synchronisation)
+int upload_room(ansx_ctx* c, Upload& U, DevBuf& buf)
 {
     int rc;
-    Plan Ps;
+    if ((rc = ensure_pin(c, U.end)) || (rc = ensure(c, buf, U.end))) return rc;
+    U.host = c->rng_pin, U.devp = (u8*)buf.p;
+    return ANSX_OK;
+}
+
+// What the ranges and batch entries share: a container built on the device from blocks of other containers, decoded to
+// a work list the caller's way out reads.  Three steps, the caller's launches between them:
+//   sub_prepare  the sub-container's plan and header, room for it and for the work list.  T blocks and n_sub ints in
+//                the geometry of header H (any n_sub that makes make_plan lay out exactly T blocks; bout / list_ints:
+//                the decoders' table over a list of so many ints, or null / n_sub), a payload of at most cap_pay bytes;
+//   the build    k_range_index + k_range_copy or k_batch_index + k_batch_copy write it (payload_bytes is theirs to
+//                fill in), enqueued by the caller;
+//   sub_decode   decode_dev on it -- no remembered header in or out -- with ONE epilogue: the caller's way out (given
+//                the decode's flags: it skips when they hold an error) and the read-back of dflags, the build's own
+//                flag word, both riding on the decode's final read-back.
+struct Sub {
+    Plan P;
+    ansx_container_header H;
+    u8* cont;
+    u32* list;
+    u64 bytes, cap_pay;
+    ansx_range_lay lay() const { return { P.lay.ckoff_off, P.lay.ckstate_off, P.lay.hint_off, P.lay.payload_off }; }
+};
+
+int sub_prepare(ansx_ctx* c, int kind, int f, const ansx_container_header& H, u64 n_sub, u32 T, u64 cap_pay, u64 list_ints,
+    const ansx_blk_out* bout, Sub* S)
+{
+    int rc;
     const ansx_opts o = container_opts(H);
-    if (make_plan(kind, f, (size_t)n_sub, &o, &Ps)) return ANSX_ERR_FORMAT;
-    set_restart_format(&Ps, (H.kind & ANSX_KIND_WIDE_RESTART) != 0);
-    if (Ps.g.nblocks != T || Ps.g.nckf != H.ckpts_per_block) return ANSX_ERR_FORMAT;
-    Ps.bout = bout, Ps.bout_ints = list_ints;
-    H.n = n_sub, H.nblocks = T, H.payload_bytes = 0, H.payload_offset = Ps.lay.payload_off;
-    const u64 sub_bytes = Ps.lay.payload_off + cap_pay;
-    if ((rc = ensure(c, c->rng_cont, sub_bytes + 64))) return rc;
+    if (make_plan(kind, f, (size_t)n_sub, &o, &S->P)) return ANSX_ERR_FORMAT;
+    set_restart_format(&S->P, (H.kind & ANSX_KIND_WIDE_RESTART) != 0);
+    if (S->P.g.nblocks != T || S->P.g.nckf != H.ckpts_per_block) return ANSX_ERR_FORMAT;
+    S->P.bout = bout, S->P.bout_ints = list_ints;
+    S->H = H;
+    S->H.n = n_sub, S->H.nblocks = T, S->H.payload_bytes = 0, S->H.payload_offset = S->P.lay.payload_off;
+    S->bytes = S->P.lay.payload_off + cap_pay, S->cap_pay = cap_pay;
+    if ((rc = ensure(c, c->rng_cont, S->bytes + 64))) return rc;
     if ((rc = ensure(c, c->rng_list, 4 * list_ints + 64))) return rc;
-    u8* sub = (u8*)c->rng_cont.p;
-    u32* list = (u32*)c->rng_list.p;
-    if ((rc = build(Ps, H, sub))) return rc;
+    S->cont = (u8*)c->rng_cont.p, S->list = (u32*)c->rng_list.p;
+    return ANSX_OK;
+}
+
+template <class WayOut> int sub_decode(ansx_ctx* c, const Sub& S, const u32* dflags, const WayOut& way_out, hipStream_t s)
+{
     u32* hflag = &c->pin->caller_flag;
     *hflag = 0;
     const std::function<int(const u32*)> epilogue = [&](const u32* gflags) -> int {
-        if ((rc = gather(list, gflags))) return rc;
+        int rc;
+        if ((rc = way_out((u32*)gflags))) return rc;
         HIPCHK(c, hipMemcpyAsync(hflag, dflags, 4, hipMemcpyDeviceToHost, s));
         return ANSX_OK;
     };
     DecodeOpts O;
     O.speculate = O.remember = false, O.epilogue = &epilogue;
-    rc = decode_dev(c, Ps, sub, (size_t)sub_bytes, list, s, O);
+    const int rc = decode_dev(c, S.P, S.cont, (size_t)S.bytes, S.list, s, O);
     return *hflag ? ANSX_ERR_FORMAT : rc;  // (the flag: an index entry of one of its blocks was invalid)
 }
 
-// The sums variants of the range calls (ansx_rangesums.h): the caller's block bases, nbases of them
-struct RangeBases {
-    const u32* d;
-    size_t n;
+// What becomes of the decoded work list on a call's way out
+enum WayOutKind {
+    OUT_GATHER,       // its ranges are copied to the caller's buffer
+    OUT_SUMS_GATHER,  // it becomes running sums from the caller's block bases first, in place (DESIGN.md sections 3f, 3h)
+    OUT_SUMS_SEARCH,  // ... and the targets are searched in them, in the gather's place (sections 3g, 3h)
 };
 
 // the largest block the one-kernel scan takes
@@ -2195,147 +2238,112 @@ int range_sums_scan(ansx_ctx* c, u32* list, u64 n_sub, u64 bi, u64 T, const u32*
     return ANSX_OK;
 }
 
-// ansx_next_geq_dev (ansx_nextgeq.h): the caller's targets and outputs, and the ranges made of
-// them -- first / count by k_ng_locate, offsets by the planner -- in workspace of the context
-struct NextGeq {
+// The way out of a call on one container, with what each kind needs: the gathers' destination; for the sums the
+// caller's block bases, nbases of them; for ansx_next_geq_dev (ansx_nextgeq.h) the nt targets and
+// the outputs, and the ranges made of the targets -- first / count by k_ng_locate, offsets by the planner -- which the
+// device front fills in in its own copy.
+struct RangeOut {
+    WayOutKind kind;
+    u32* d_out;
+    const u32* d_bases;
+    size_t nbases;
     const u32* d_targets;
+    u32 nt;
     u64* d_pos;
     u32* d_ids;
-    const u64* first;
+    const u64 *first, *offsets;
     const u32* count;
-    const u64* offsets;
 };
 
-// The tail both fronts share, from the plan on the device: tb[T] the touched blocks (ascending, unique; last_b the
-// last), R the pieces of the nr non-empty ranges, pstart[nr + 1] their first gather pieces; dflags: a zeroed word.
-// ng (with bases; nt targets): k_ng_search over the scanned work list in the place of the gather.
-int range_tail(ansx_ctx* c, int kind, int f, const u8* d_in, const ansx_container_header& H, const Plan& P, u64 T,
-    u64 last_b, const u32* dtb, const ansx_range_piece* R, const u32* pstart, u32 nr, u64 npieces, u32* dflags,
-    u32* d_out, hipStream_t s, const RangeBases* bases = nullptr, const NextGeq* ng = nullptr, u32 nt = 0)
-{
-    int rc;
-    const u64 n = H.n, bi = P.g.block_ints;
-    const u64 n_sub = (T - 1) * bi + std::min<u64>(bi, n - last_b * bi);  // (only the source's last block can be short: it sorts last)
-    u64* agg = nullptr;
-    if (bases && (rc = range_sums_workspace(c, bi, T, &agg))) return rc;  // (here: growing it may wait for the device)
-    // (max_present_m1, max_nsyms, max_log2_frame are bounds over the blocks: they hold for any subset)
-    const u64 cap_pay = std::min<u64>(H.payload_bytes, T * (u64)block_bound(kind, (u32)f, P.g.block_ints, P.g.pa != 0));
-    const SubBuild build = [&](const Plan& Ps, const ansx_container_header& Hs, u8* sub) -> int {
-        const ansx_range_lay sl = { P.lay.ckoff_off, P.lay.ckstate_off, P.lay.hint_off, P.lay.payload_off };
-        const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
-        LAUNCH(c, "k_range_index", k_range_index, 1, 1024, 0, s, d_in, P.g, dtb, (u32)T, Hs, sub, cap_pay, dflags);
-        LAUNCH(c, "k_range_copy", k_range_copy, (u32)T, 256, 0, s, d_in, P.g, sl, dl, dtb, sub, cap_pay, dflags);
-        return ANSX_OK;
-    };
-    const SubGather gather = [&](const u32* list, const u32* gflags) -> int {
-        // (the sums variants: the work list becomes ids first, in place; the scan reports foreign bases in gflags)
-        if (bases && (rc = range_sums_scan(c, (u32*)list, n_sub, bi, T, dtb, P.g.nblocks, bases->d, agg, (u32*)gflags, s))) return rc;
-        if (ng) {
-            LAUNCH(c, "k_ng_search", k_ng_search, (nt + ANSX_NG_NT - 1) / ANSX_NG_NT, ANSX_NG_NT, 0, s, list, n_sub, bi, n,
-                ng->d_targets, nt, ng->first, ng->count, ng->offsets, R, ng->d_pos, ng->d_ids, gflags, (const u32*)dflags);
-            return ANSX_OK;
-        }
-        const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
-        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, R, pstart, nr, (u32)npieces, d_out, gflags);
-        return ANSX_OK;
-    };
-    return decode_sub(c, kind, f, H, n_sub, (u32)T, cap_pay, n_sub, nullptr, dflags, build, gather, s);
-}
-
-// ansx_decode_ranges_dev: the plan built on the host from host arrays, uploaded in one copy
-int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* first, const u32* count,
-    size_t nranges, u32* d_out, size_t cap, hipStream_t s, const RangeBases* bases = nullptr)
-{
-    int rc;
+// What both fronts hand to the tail, the plan on the device: the source container, its header and plan; tb[T] the
+// touched blocks (ascending, unique; last_b the last); R the pieces of the nr non-empty ranges, pstart[nr + 1] their
+// first gather pieces of npieces; dflags: a zeroed word.
+struct RangeTail {
+    const u8* d_in;
     ansx_container_header H;
     Plan P;
-    if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &H, &P))) return rc;
-    if (bases && bases->n != (size_t)P.g.nblocks + 1) return ANSX_ERR_ARG;
-    const u64 n = H.n, bi = P.g.block_ints;
+    u64 T, last_b;
+    const u32 *dtb, *pstart;
+    const ansx_range_piece* R;
+    u32 nr;
+    u64 npieces;
+    u32* dflags;
+};
 
-    // ranges -> block spans; their union as sorted runs of consecutive blocks, each numbered from its first touched block
-    u64 total = 0;
-    std::vector<std::pair<u64, u64>> span;  // [first block, last block] of every non-empty range
-    span.reserve(nranges);
-    for (size_t i = 0; i < nranges; i++) {
-        if (first[i] > n || (u64)count[i] > n - first[i]) return ANSX_ERR_ARG;
-        if (!count[i]) continue;
-        span.push_back({ first[i] / bi, (first[i] + count[i] - 1) / bi });
-        total += count[i];  // (at most 2^32 - 1 per range: no wrap below 2^32 ranges)
-    }
-    if (total > cap) return ANSX_ERR_CAPACITY;
-    if (total == 0) return ANSX_OK;
-    std::sort(span.begin(), span.end());
-    struct Run {
-        u64 b0, b1, k0;  // blocks b0..b1 are touched blocks k0.. of the sub-container
-    };
-    std::vector<Run> runs;
-    u64 T = 0;
-    for (const auto& sp : span) {
-        if (!runs.empty() && sp.first <= runs.back().b1 + 1) {
-            if (sp.second > runs.back().b1) {
-                T += sp.second - runs.back().b1;
-                runs.back().b1 = sp.second;
-            }
-            continue;
+// The tail both fronts share: prepare the sub-container of the touched blocks, build it, decode it, and out
+int range_tail(ansx_ctx* c, int kind, int f, const RangeTail& t, const RangeOut& out, hipStream_t s)
+{
+    int rc;
+    const Plan& P = t.P;
+    const u64 n = t.H.n, bi = P.g.block_ints, T = t.T;
+    const u64 n_sub = (T - 1) * bi + std::min<u64>(bi, n - t.last_b * bi);  // (only the source's last block can be short: it sorts last)
+    u64* agg = nullptr;
+    if (out.kind != OUT_GATHER && (rc = range_sums_workspace(c, bi, T, &agg))) return rc;  // (here: growing it may wait for the device)
+    // (max_present_m1, max_nsyms, max_log2_frame are bounds over the blocks: they hold for any subset)
+    const u64 cap_pay = std::min<u64>(t.H.payload_bytes, T * (u64)block_bound(kind, (u32)f, P.g.block_ints, P.g.pa != 0));
+    Sub sub;
+    if ((rc = sub_prepare(c, kind, f, t.H, n_sub, (u32)T, cap_pay, n_sub, nullptr, &sub))) return rc;
+    const ansx_range_lay sl = { P.lay.ckoff_off, P.lay.ckstate_off, P.lay.hint_off, P.lay.payload_off };
+    LAUNCH(c, "k_range_index", k_range_index, 1, 1024, 0, s, t.d_in, P.g, t.dtb, (u32)T, sub.H, sub.cont, cap_pay, t.dflags);
+    LAUNCH(c, "k_range_copy", k_range_copy, (u32)T, 256, 0, s, t.d_in, P.g, sl, sub.lay(), t.dtb, sub.cont, cap_pay, t.dflags);
+    return sub_decode(c, sub, t.dflags, [&](u32* gflags) -> int {
+        // (the sums: the work list becomes ids first, in place; the scan reports foreign bases in gflags)
+        if (out.kind != OUT_GATHER
+            && (rc = range_sums_scan(c, sub.list, n_sub, bi, T, t.dtb, P.g.nblocks, out.d_bases, agg, gflags, s)))
+            return rc;
+        if (out.kind == OUT_SUMS_SEARCH) {
+            LAUNCH(c, "k_ng_search", k_ng_search, (out.nt + ANSX_NG_NT - 1) / ANSX_NG_NT, ANSX_NG_NT, 0, s, (const u32*)sub.list,
+                n_sub, bi, n, out.d_targets, out.nt, out.first, out.count, out.offsets, t.R, out.d_pos, out.d_ids,
+                (const u32*)gflags, (const u32*)t.dflags);
+            return ANSX_OK;
         }
-        runs.push_back({ sp.first, sp.second, T });
-        T += sp.second - sp.first + 1;
-    }
+        const u32 grid = (u32)std::min<u64>(t.npieces, 1u << 20);
+        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, (const u32*)sub.list, t.R, t.pstart, t.nr, (u32)t.npieces,
+            out.d_out, (const u32*)gflags);
+        return ANSX_OK;
+    }, s);
+}
 
+// ansx_decode_ranges_dev: the plan built on the host from host arrays (ansx_plan.h, range_plan), uploaded in one copy
+int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* first, const u32* count,
+    size_t nranges, size_t cap, const RangeOut& out, hipStream_t s)
+{
+    int rc;
+    RangeTail t = { d_in };
+    if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &t.H, &t.P))) return rc;
+    if (out.kind != OUT_GATHER && out.nbases != (size_t)t.P.g.nblocks + 1) return ANSX_ERR_ARG;
+    RangePlan R;
+    if ((rc = range_plan(t.H.n, t.P.g.block_ints, first, count, nranges, cap, &R))) return rc;
+    if (R.total == 0) return ANSX_OK;
     // the plan on the device, one upload: flags[4] | touched blocks u32[T] | range pieces | first piece per range u32[nr + 1]
-    std::vector<ansx_range_piece> pieces;
-    pieces.reserve(span.size());
-    std::vector<u32> pstart;
-    pstart.reserve(span.size() + 1);
-    u64 npieces = 0, dst = 0;
-    for (size_t i = 0; i < nranges; i++) {
-        if (!count[i]) continue;
-        const u64 b0 = first[i] / bi;
-        auto it = std::upper_bound(runs.begin(), runs.end(), b0, [](u64 v, const Run& r) { return v < r.b0; });
-        const Run& r = *(it - 1);
-        pieces.push_back({ (r.k0 + (b0 - r.b0)) * bi + (first[i] - b0 * bi), dst, (u64)count[i] });
-        pstart.push_back((u32)npieces);
-        dst += count[i];
-        npieces += (count[i] + ANSX_RANGE_CHUNK - 1) / ANSX_RANGE_CHUNK;
-    }
-    if (npieces > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-    pstart.push_back((u32)npieces);
-    const u32 nr = (u32)pieces.size();
-    const size_t o_tb = 16, o_pc = rup(o_tb + 4 * T, 16), o_ps = rup(o_pc + sizeof(ansx_range_piece) * nr, 16);
-    const size_t plan_bytes = o_ps + 4 * ((size_t)nr + 1);
-    if ((rc = ensure_pin(c, plan_bytes))) return rc;
-    {
-        u8* hb = c->rng_pin;  // (no copy out of it is pending: every call ends in a synchronisation)
-        memset(hb, 0, o_tb);
-        u32* tb = (u32*)(hb + o_tb);
-        for (const Run& r : runs)
-            for (u64 b = r.b0; b <= r.b1; b++) *tb++ = (u32)b;
-        memcpy(hb + o_pc, pieces.data(), sizeof(ansx_range_piece) * nr);
-        memcpy(hb + o_ps, pstart.data(), 4 * ((size_t)nr + 1));
-    }
-    if ((rc = ensure(c, c->rng_plan, plan_bytes))) return rc;
-    u8* dplan = (u8*)c->rng_plan.p;
-    HIPCHK(c, hipMemcpyAsync(dplan, c->rng_pin, plan_bytes, hipMemcpyHostToDevice, s));
-    return range_tail(c, kind, f, d_in, H, P, T, runs.back().b1, (const u32*)(dplan + o_tb),
-        (const ansx_range_piece*)(dplan + o_pc), (const u32*)(dplan + o_ps), nr, npieces, (u32*)dplan, d_out, s, bases);
+    Upload U;
+    const auto s_fl = U.add<u32>(4);
+    const auto s_tb = U.add<u32>(R.tb.size());
+    const auto s_pc = U.add<ansx_range_piece>(R.pieces.size());
+    const auto s_ps = U.add<u32>(R.pstart.size());
+    if ((rc = upload_room(c, U, c->rng_plan))) return rc;
+    memset(U.pin(s_fl), 0, s_fl.bytes);
+    U.put(s_tb, R.tb.data()), U.put(s_pc, R.pieces.data()), U.put(s_ps, R.pstart.data());
+    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, U.end, hipMemcpyHostToDevice, s));
+    t.T = R.T, t.last_b = R.last_b, t.dtb = U.dev(s_tb), t.R = U.dev(s_pc), t.pstart = U.dev(s_ps);
+    t.nr = (u32)R.pieces.size(), t.npieces = R.npieces, t.dflags = U.dev(s_fl);
+    return range_tail(c, kind, f, t, out, s);
 }
 
 // ansx_decode_device_ranges_dev: the plan built on the device from first / count in device memory (ansx_ranges.h,
 // "device plan"); one read-back of its scalars decides the errors and sizes the tail, no O(nranges) copy either way.
-// The body serves ansx_next_geq_dev too (ng, with bases; nranges targets): the ranges are then k_ng_locate's, one int at
-// the start of every target's block, made in front of the planner in workspace behind its own; the planner and its
+// The front serves ansx_next_geq_dev too (OUT_SUMS_SEARCH; nranges targets): the ranges are then k_ng_locate's, one int
+// at the start of every target's block, made in front of the planner in workspace behind its own; the planner and its
 // read-back are the same, *total_ints is the number of targets found, and the tail searches instead of gathering.
-int device_ranges_body(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
-    const u32* d_count, size_t nranges, u32* d_out, size_t cap, u64* d_offsets, u64* total_ints, hipStream_t s,
-    const RangeBases* bases, NextGeq* ng)
+int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
+    const u32* d_count, size_t nranges, size_t cap, u64* d_offsets, u64* total_ints, RangeOut out, hipStream_t s)
 {
     int rc;
-    ansx_container_header H;
-    Plan P;
-    if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &H, &P))) return rc;
-    if (bases && bases->n != (size_t)P.g.nblocks + 1) return ANSX_ERR_ARG;
-    const u64 n = H.n, bi = P.g.block_ints, nr = nranges, nb = P.g.nblocks;
+    RangeTail t = { d_in };
+    if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &t.H, &t.P))) return rc;
+    if (out.kind != OUT_GATHER && out.nbases != (size_t)t.P.g.nblocks + 1) return ANSX_ERR_ARG;
+    const bool search = out.kind == OUT_SUMS_SEARCH;
+    const u64 n = t.H.n, bi = t.P.g.block_ints, nr = nranges, nb = t.P.g.nblocks;
     u32 kb = 0;  // key bits of a block id
     while ((1ull << kb) < nb) kb++;
     const u64 nt = (nr + ANSX_DR_TILE - 1) / ANSX_DR_TILE;
@@ -2346,15 +2354,15 @@ int device_ranges_body(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_b
     const size_t o_sp = rup(o_ps + 4 * (nr + 1), 16), o_tb = o_sp + 16 * nr;
     // (ansx_next_geq_dev, behind tb: first u64[nr] | offsets u64[nr + 1] | count u32[nr])
     const size_t o_nf = rup(o_tb + 4 * nb, 16), o_no = o_nf + 8 * nr, o_nc = o_no + 8 * (nr + 1);
-    const size_t bytes = ng ? o_nc + 4 * nr : o_tb + 4 * nb;
+    const size_t bytes = search ? o_nc + 4 * nr : o_tb + 4 * nb;
     if ((rc = ensure(c, c->rng_dev, bytes))) return rc;
     u8* w = (u8*)c->rng_dev.p;
-    if (ng) {
+    if (search) {
         u64* nf = (u64*)(w + o_nf);
         u32* nc = (u32*)(w + o_nc);
-        LAUNCH(c, "k_ng_locate", k_ng_locate, (u32)((nr + ANSX_NG_TILE - 1) / ANSX_NG_TILE), ANSX_NG_NT, 0, s, bases->d, (u32)nb,
-            bi, ng->d_targets, (u32)nr, nf, nc);
-        d_first = ng->first = nf, d_count = ng->count = nc, d_offsets = (u64*)(w + o_no), ng->offsets = d_offsets;
+        LAUNCH(c, "k_ng_locate", k_ng_locate, (u32)((nr + ANSX_NG_TILE - 1) / ANSX_NG_TILE), ANSX_NG_NT, 0, s, out.d_bases, (u32)nb,
+            bi, out.d_targets, (u32)nr, nf, nc);
+        d_first = out.first = nf, d_count = out.count = nc, d_offsets = (u64*)(w + o_no), out.offsets = d_offsets;
     }
     u64* sc = (u64*)w;
     u64* part = (u64*)(w + o_pt);
@@ -2403,9 +2411,9 @@ int device_ranges_body(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_b
     if (total_ints) *total_ints = total;
     if (total > cap) return ANSX_ERR_CAPACITY;
     if (total == 0) {
-        if (ng) {  // (no target found and no tail: the outputs are filled here; the call returns with them written, as ever)
-            LAUNCH(c, "k_ng_none", k_ng_none, (u32)((nr + ANSX_NG_NT - 1) / ANSX_NG_NT), ANSX_NG_NT, 0, s, n, (u32)nr, ng->d_pos,
-                ng->d_ids);
+        if (search) {  // (no target found and no tail: the outputs are filled here; the call returns with them written, as ever)
+            LAUNCH(c, "k_ng_none", k_ng_none, (u32)((nr + ANSX_NG_NT - 1) / ANSX_NG_NT), ANSX_NG_NT, 0, s, n, (u32)nr, out.d_pos,
+                out.d_ids);
             HIPCHK(c, hipStreamSynchronize(s));
         }
         return ANSX_OK;
@@ -2414,97 +2422,101 @@ int device_ranges_body(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_b
     if (T == 0 || T > nb || nne == 0 || hs[ANSX_DR_LASTB1] == 0) return ANSX_ERR_HIP;  // (cannot happen: a planner fault)
     LAUNCH(c, "k_dr_blocks", k_dr_blocks, (u32)((T + ANSX_DR_NT - 1) / ANSX_DR_NT), ANSX_DR_NT, 0, s, tb, (u32)T, (u32)nne,
         S, offl, (const u64*)parta);
-    return range_tail(c, kind, f, d_in, H, P, T, hs[ANSX_DR_LASTB1] - 1, tb, R, pstart, (u32)nne, npieces,
-        (u32*)&sc[ANSX_DR_FLAGS], d_out, s, bases, ng, (u32)nr);
-}
-
-int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
-    const u32* d_count, size_t nranges, u32* d_out, size_t cap, u64* d_offsets, u64* total_ints, hipStream_t s,
-    const RangeBases* bases = nullptr)
-{
-    return device_ranges_body(c, kind, f, d_in, in_bytes, d_first, d_count, nranges, d_out, cap, d_offsets, total_ints, s,
-        bases, nullptr);
+    t.T = T, t.last_b = hs[ANSX_DR_LASTB1] - 1, t.dtb = tb, t.R = R, t.pstart = pstart, t.nr = (u32)nne, t.npieces = npieces;
+    t.dflags = (u32*)&sc[ANSX_DR_FLAGS];
+    return range_tail(c, kind, f, t, out, s);
 }
 
 // --------------------------------------------------------------------------------- batches of containers
-// ansx_decode_batch_dev: every header in one round trip -> the host's checks, offsets and
-// capacity -> per geometry, passes of at most P blocks: k_batch_index + k_batch_copy build a sub-container of the
-// pass's blocks -> decode_dev on it with the per-block table (no cached header in or out) -> k_range_gather into the
-// caller's buffer.
+// ansx_decode_batch_dev: every header in one round trip (batch_headers) -> the host's checks,
+// offsets and capacity -> per geometry, passes of at most P blocks built by ansx_plan::Pass: one upload of the pass's
+// plan, sub_prepare, k_batch_index + k_batch_copy build a sub-container of the pass's blocks, sub_decode on it with the
+// per-block table and k_range_gather into the caller's buffer as the way out.
 #define ANSX_BATCH_PASS_DEFAULT 16384u  // blocks per pass: the block count of the headline container
 
-struct BatchSrc {  // a container of the batch, checked
-    ansx_container_header H;
-    Layout lay;
-    u64 base;
-    u32 nblocks;
-};
+u32 batch_pass_blocks(const ansx_ctx* c) { return c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT; }
 
-// What a pass hands to its gather: two sections of the plan upload, behind the sources, blocks and table
-struct PassTail {
-    const void* a;  // the gather's pieces: ansx_range_piece per source (batch_pass), ansx_piece per piece (batch_ranges_group)
-    size_t a_bytes;
-    const void* b;  // the index over them: u32 pstart per source + 1 (batch_pass), u64 wpos per piece + 1 (batch_ranges_group)
-    size_t b_bytes;
-    const void* c = nullptr;  // the sums calls only: ansx_brs_src per source, the caller's bases;
-    size_t c_bytes = 0;       // no section and no byte of the upload where there is none
-};
-// where a pass's plan lies on the device: its blocks, the decoders' table, the tail's section c and the flag word of
-// k_batch_index / k_batch_copy
-struct PassDev {
-    const ansx_batch_blk* B;
-    const ansx_blk_out* O;
-    const u8* c;
-    const u32* dflags;
-};
-// the pass's gather: enqueues the copy from the decoded work list to the caller's buffer (da, db: the tail's sections a
-// and b on the device, 16-byte aligned; the decode's flags)
-typedef std::function<int(const u32* list, const u8* da, const u8* db, const u32* gflags, const PassDev& D)> PassGather;
-
-// The part every pass shares (ansx_decode_batch_dev, ansx_decode_batch_ranges_dev): S, B, O -- the pass's sources, its
-// T blocks and the decoders' table over a work list of wl ints -- and the tail go up in one copy; k_batch_index and
-// k_batch_copy build the sub-container (H0: a header of the pass's geometry, Hs: the sub-container's, the maxima over
-// the sources filled in), decode_dev decodes it with the gather riding on its final read-back.  Every buffer is bounded
-// by the pass: its blocks, their ints and their bytes, and the tail.
-int pass_decode(ansx_ctx* c, int kind, int f, const ansx_container_header& H0, ansx_container_header Hs,
-    const std::vector<ansx_batch_src>& S, const std::vector<ansx_batch_blk>& B, const std::vector<ansx_blk_out>& O, u64 wl,
-    u64 cap_pay, const PassTail& tail, const PassGather& pass_gather, hipStream_t s)
+// The header round trip of the batch calls, over the m containers pos[0..m) of the batch (pos null: the first m): the
+// addresses up (0 for an input too short to hold a header), k_batch_headers, the headers back; then decode_dev's
+// checks on every one, in that order.  ANSX_ERR_FORMAT with *bad = the first j that fails them.
+int batch_headers(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u32* pos, size_t m,
+    std::vector<BatchSrc>* src, size_t* bad, hipStream_t s)
 {
     int rc;
-    const u32 T = (u32)B.size(), nr = (u32)S.size();
-    // the pass's plan, one upload: flags[4] | sources | blocks | table | the tail's two sections (| its third, if any)
-    const size_t o_s = 16, o_b = rup(o_s + sizeof(ansx_batch_src) * nr, 16), o_o = rup(o_b + sizeof(ansx_batch_blk) * T, 16);
-    const size_t o_r = rup(o_o + sizeof(ansx_blk_out) * T, 16), o_p = rup(o_r + tail.a_bytes, 16);
-    const size_t o_c = rup(o_p + tail.b_bytes, 16);
-    const size_t plan_bytes = tail.c_bytes ? o_c + tail.c_bytes : o_p + tail.b_bytes;
-    if ((rc = ensure_pin(c, plan_bytes))) return rc;
-    u8* hb = c->rng_pin;  // (no copy out of it is pending: the previous pass ended in a synchronisation)
-    memset(hb, 0, o_s);
-    memcpy(hb + o_s, S.data(), sizeof(ansx_batch_src) * nr);
-    memcpy(hb + o_b, B.data(), sizeof(ansx_batch_blk) * T);
-    memcpy(hb + o_o, O.data(), sizeof(ansx_blk_out) * T);
-    memcpy(hb + o_r, tail.a, tail.a_bytes);
-    memcpy(hb + o_p, tail.b, tail.b_bytes);
-    if (tail.c_bytes) memcpy(hb + o_c, tail.c, tail.c_bytes);
-    if ((rc = ensure(c, c->rng_plan, plan_bytes))) return rc;
-    u8* dplan = (u8*)c->rng_plan.p;
-    HIPCHK(c, hipMemcpyAsync(dplan, hb, plan_bytes, hipMemcpyHostToDevice, s));
-    u32* dflags = (u32*)dplan;
-    const SubBuild build = [&](const Plan& Ps, const ansx_container_header& Hs, u8* sub) -> int {
-        const ansx_batch_src* dS = (const ansx_batch_src*)(dplan + o_s);
-        const ansx_batch_blk* dB = (const ansx_batch_blk*)(dplan + o_b);
-        const ansx_range_lay dl = { Ps.lay.ckoff_off, Ps.lay.ckstate_off, Ps.lay.hint_off, Ps.lay.payload_off };
-        LAUNCH(c, "k_batch_index", k_batch_index, 1, 1024, 0, s, dS, dB, Ps.g, T, Hs, sub, cap_pay, dflags);
-        LAUNCH(c, "k_batch_copy", k_batch_copy, T, 256, 0, s, dS, dB, Ps.g, dl, sub, cap_pay, dflags);
-        return ANSX_OK;
-    };
-    const SubGather gather = [&](const u32* list, const u32* gflags) -> int {
-        const PassDev D = { (const ansx_batch_blk*)(dplan + o_b), (const ansx_blk_out*)(dplan + o_o), dplan + o_c, dflags };
-        return pass_gather(list, dplan + o_r, dplan + o_p, gflags, D);
-    };
+    Upload U;
+    const auto s_addr = U.add<u64>(m);
+    const auto s_hdr = U.add<uint4>(4 * m);  // (comes back: only the addresses go up)
+    if ((rc = upload_room(c, U, c->bat_hdr))) return rc;
+    u64* addr = U.pin(s_addr);
+    for (size_t j = 0; j < m; j++) {
+        const size_t i = pos ? pos[j] : j;
+        addr[j] = in_bytes[i] >= sizeof(ansx_container_header) ? (u64)(uintptr_t)d_ins[i] : 0;
+    }
+    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, s_addr.bytes, hipMemcpyHostToDevice, s));
+    LAUNCH(c, "k_batch_headers", k_batch_headers, (u32)((4 * (u64)m + 255) / 256), 256, 0, s, (const u64*)U.dev(s_addr), (u64)m,
+        U.dev(s_hdr));
+    HIPCHK(c, hipMemcpyAsync(U.pin(s_hdr), U.dev(s_hdr), 64 * m, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    src->resize(m);
+    for (size_t j = 0; j < m; j++) {
+        const size_t i = pos ? pos[j] : j;
+        BatchSrc& b = (*src)[j];
+        Plan P;
+        if (in_bytes[i] < sizeof(ansx_container_header) || parse_header((const u8*)U.pin(s_hdr) + 64 * j, in_bytes[i], &b.H)
+            || container_plan(b.H, (u32)kind, (u32)f, in_bytes[i], &P)) {  // (a single-stream stream has no magic)
+            *bad = j;
+            return ANSX_ERR_FORMAT;
+        }
+        b.lay = P.lay;
+        b.base = (u64)(uintptr_t)d_ins[i];
+        b.nblocks = P.g.nblocks;
+    }
+    return ANSX_OK;
+}
+
+// The loop over the geometry groups every batch call ends in: fn on each group's members; a format error from in there
+// was found on the device, which container it was is not known: *bad = count.
+typedef std::map<Geometry, std::vector<u32>> GeometryGroups;
+template <class F> int for_each_group(const GeometryGroups& groups, size_t count, size_t* bad, const F& fn)
+{
+    for (const auto& gr : groups) {
+        const int rc = fn(gr.second);
+        if (rc == ANSX_ERR_FORMAT && bad) *bad = count;
+        if (rc) return rc;
+    }
+    return ANSX_OK;
+}
+
+// A pass's plan on the device, one upload: flags[4] | sources | blocks | table | the caller's own sections behind them
+struct PassUp {
+    Upload U;
+    Upload::Sec<u32> flags = U.add<u32>(4);
+    Upload::Sec<ansx_batch_src> S;
+    Upload::Sec<ansx_batch_blk> B;
+    Upload::Sec<ansx_blk_out> O;
+    explicit PassUp(const Pass& P)
+        : S(U.add<ansx_batch_src>(P.S.size())), B(U.add<ansx_batch_blk>(P.B.size())), O(U.add<ansx_blk_out>(P.O.size())) {}
+};
+
+// The part every pass shares, once the caller has found room for the plan (upload_room) and put its own sections: the
+// plan goes up, the sub-container of the pass's T blocks is prepared and built.  Every buffer is bounded by the pass:
+// its blocks, their ints and their bytes, and the caller's sections.
+int pass_build(ansx_ctx* c, int kind, int f, const Pass& P, const PassUp& D, Sub* sub, hipStream_t s)
+{
+    int rc;
+    const u32 T = (u32)P.B.size();
+    memset(D.U.pin(D.flags), 0, D.flags.bytes);
+    D.U.put(D.S, P.S.data()), D.U.put(D.B, P.B.data()), D.U.put(D.O, P.O.data());
+    HIPCHK(c, hipMemcpyAsync(D.U.devp, D.U.host, D.U.end, hipMemcpyHostToDevice, s));
     // (any n that makes make_plan lay out exactly T blocks: the table says how long each is)
-    return decode_sub(c, kind, f, Hs, (u64)(T - 1) * H0.block_ints + O.back().n, T, cap_pay, wl, (const ansx_blk_out*)(dplan + o_o),
-        dflags, build, gather, s);
+    if ((rc = sub_prepare(c, kind, f, P.Hs, (u64)(T - 1) * P.Hs.block_ints + P.O.back().n, T, P.cap_pay, P.wl, D.U.dev(D.O), sub)))
+        return rc;
+    u32* dflags = D.U.dev(D.flags);
+    LAUNCH(c, "k_batch_index", k_batch_index, 1, 1024, 0, s, (const ansx_batch_src*)D.U.dev(D.S), (const ansx_batch_blk*)D.U.dev(D.B),
+        sub->P.g, T, sub->H, sub->cont, P.cap_pay, dflags);
+    LAUNCH(c, "k_batch_copy", k_batch_copy, T, 256, 0, s, (const ansx_batch_src*)D.U.dev(D.S), (const ansx_batch_blk*)D.U.dev(D.B),
+        sub->P.g, sub->lay(), sub->cont, P.cap_pay, dflags);
+    return ANSX_OK;
 }
 
 // One pass over containers ids[*ci..] of one geometry, from block *b0 of the first, up to PB blocks; moves *ci / *b0
@@ -2512,364 +2524,176 @@ int pass_decode(ansx_ctx* c, int kind, int f, const ansx_container_header& H0, a
 int batch_pass(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& src, const std::vector<u64>& off,
     const std::vector<u32>& ids, size_t* ci, u32* b0, u32 PB, u32* d_out, hipStream_t s)
 {
+    int rc;
     const ansx_container_header& H0 = src[ids[*ci]].H;
-    const u64 bi = H0.block_ints;
-    const u64 bbound = block_bound(kind, (u32)f, (size_t)bi, (H0.kind & 0x100u) != 0);
-    std::vector<ansx_batch_src> S;
-    std::vector<ansx_batch_blk> B;
-    std::vector<ansx_blk_out> O;  // the decoders' table: every container's blocks back to back, from a multiple of 4 ints
+    const u64 bbound = block_bound(kind, (u32)f, (size_t)H0.block_ints, (H0.kind & 0x100u) != 0);
+    Pass P;
     std::vector<ansx_range_piece> R;
     std::vector<u32> pstart;
-    u64 wl = 0, cap_pay = 0, npieces = 0;  // work-list ints, sub-container payload bound, gather pieces
-    ansx_container_header Hs = H0;
-    Hs.max_nsyms = 0, Hs.max_log2_frame = 0, Hs.max_present_m1 = 0;  // (the maxima over the pass's sources)
-    while (*ci < ids.size() && B.size() < PB) {
-        const u32 i = ids[*ci];
-        const BatchSrc& cs = src[i];
-        const u32 take = (u32)std::min<u64>(cs.nblocks - *b0, PB - B.size());
-        const u32 si = (u32)S.size();
-        S.push_back({ cs.base, cs.lay.ckoff_off, cs.lay.ckstate_off, cs.lay.hint_off, cs.lay.payload_off,
-            cs.H.payload_bytes, cs.nblocks, 0 });
-        u64 ints = 0;
-        for (u32 k = 0; k < take; k++) {
-            const u64 b = (u64)*b0 + k;
-            const u32 nbk = (u32)std::min<u64>(bi, cs.H.n - b * bi);
-            B.push_back({ si, (u32)b });
-            O.push_back({ wl + k * bi, nbk, 0 });
-            ints += nbk;
-        }
-        R.push_back({ wl, off[i] + (u64)*b0 * bi, ints });
-        pstart.push_back((u32)npieces);
-        npieces += (ints + ANSX_RANGE_CHUNK - 1) / ANSX_RANGE_CHUNK;
-        wl += rup(ints, 4);
-        cap_pay += std::min<u64>(cs.H.payload_bytes, (u64)take * bbound);
-        Hs.max_nsyms = std::max(Hs.max_nsyms, cs.H.max_nsyms);
-        Hs.max_log2_frame = std::max(Hs.max_log2_frame, cs.H.max_log2_frame);
-        Hs.max_present_m1 = std::max(Hs.max_present_m1, cs.H.max_present_m1);
-        *b0 += take;
-        if (*b0 == cs.nblocks) (*ci)++, *b0 = 0;
-    }
+    const u64 npieces = batch_pass_plan(src, off, ids, ci, b0, PB, bbound, &P, &R, &pstart);
     if (npieces > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-    pstart.push_back((u32)npieces);
     const u32 nr = (u32)R.size();
-    // the tail: gather pieces | first piece per source
-    const PassTail tail = { R.data(), sizeof(ansx_range_piece) * nr, pstart.data(), 4 * ((size_t)nr + 1) };
-    const PassGather gather = [&](const u32* list, const u8* da, const u8* db, const u32* gflags, const PassDev&) -> int {
+    PassUp D(P);
+    const auto s_r = D.U.add<ansx_range_piece>(nr);  // the gather's pieces | first piece per source
+    const auto s_ps = D.U.add<u32>((size_t)nr + 1);
+    if ((rc = upload_room(c, D.U, c->rng_plan))) return rc;
+    D.U.put(s_r, R.data()), D.U.put(s_ps, pstart.data());
+    Sub sub;
+    if ((rc = pass_build(c, kind, f, P, D, &sub, s))) return rc;
+    return sub_decode(c, sub, D.U.dev(D.flags), [&](u32* gflags) -> int {
         const u32 grid = (u32)std::min<u64>(npieces, 1u << 20);
-        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, list, (const ansx_range_piece*)da, (const u32*)db, nr,
-            (u32)npieces, d_out, gflags);
+        LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, (const u32*)sub.list, (const ansx_range_piece*)D.U.dev(s_r),
+            (const u32*)D.U.dev(s_ps), nr, (u32)npieces, d_out, (const u32*)gflags);
         return ANSX_OK;
-    };
-    return pass_decode(c, kind, f, H0, Hs, S, B, O, wl, cap_pay, tail, gather, s);
+    }, s);
 }
 
 int decode_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
     u32* d_out, size_t cap, u64* offsets, u64* total_ints, size_t* bad_index, hipStream_t s)
 {
     int rc;
-    // every header in one round trip: the input addresses up (0 for an input too short to hold one), the headers back
-    const size_t o_h = rup(8 * count, 16), bytes = o_h + 64 * count;
-    if ((rc = ensure_pin(c, bytes))) return rc;
-    if ((rc = ensure(c, c->bat_hdr, bytes))) return rc;
-    u64* hp = (u64*)c->rng_pin;
-    for (size_t i = 0; i < count; i++) hp[i] = in_bytes[i] >= sizeof(ansx_container_header) ? (u64)(uintptr_t)d_ins[i] : 0;
-    u8* dw = (u8*)c->bat_hdr.p;
-    HIPCHK(c, hipMemcpyAsync(dw, hp, 8 * count, hipMemcpyHostToDevice, s));
-    LAUNCH(c, "k_batch_headers", k_batch_headers, (u32)((4 * (u64)count + 255) / 256), 256, 0, s, (const u64*)dw,
-        (u64)count, (uint4*)(dw + o_h));
-    HIPCHK(c, hipMemcpyAsync(c->rng_pin + o_h, dw + o_h, 64 * count, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-
-    // decode_dev's checks on every header, in batch order; the offsets and the total
-    std::vector<BatchSrc> src(count);
+    std::vector<BatchSrc> src;
+    size_t bad = count;
+    if ((rc = batch_headers(c, kind, f, d_ins, in_bytes, nullptr, count, &src, &bad, s))) {
+        if (rc == ANSX_ERR_FORMAT && bad_index) *bad_index = bad;
+        return rc;
+    }
+    // the offsets and the total, in batch order
     std::vector<u64> off(count + 1);
     u64 total = 0;
     for (size_t i = 0; i < count; i++) {
-        BatchSrc& b = src[i];
-        Plan P;
-        if (in_bytes[i] < sizeof(ansx_container_header) || parse_header(c->rng_pin + o_h + 64 * i, in_bytes[i], &b.H)
-            || container_plan(b.H, (u32)kind, (u32)f, in_bytes[i], &P)) {  // (a single-stream stream has no magic)
-            if (bad_index) *bad_index = i;
-            return ANSX_ERR_FORMAT;
-        }
-        b.lay = P.lay;
-        b.base = (u64)(uintptr_t)d_ins[i];
-        b.nblocks = P.g.nblocks;
         off[i] = total;
-        total = b.H.n > ~0ull - total ? ~0ull : total + b.H.n;  // (saturated: no buffer holds that many)
+        total = src[i].H.n > ~0ull - total ? ~0ull : total + src[i].H.n;  // (saturated: no buffer holds that many)
     }
     off[count] = total;
     if (offsets) memcpy(offsets, off.data(), 8 * (count + 1));
     if (total_ints) *total_ints = total;
     if (total > cap) return ANSX_ERR_CAPACITY;
 
-    // groups of one geometry (block_ints, restart interval, compaction, restart-point format), batch order inside each
-    std::map<std::array<u32, 4>, std::vector<u32>> groups;
-    for (size_t i = 0; i < count; i++) {
-        const ansx_container_header& H = src[i].H;
-        groups[{ H.block_ints, H.ckpt_interval, (H.kind >> 8) & 1u, (H.kind >> 9) & 1u }].push_back((u32)i);
-    }
-    const u32 PB = c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT;
-    for (const auto& gr : groups) {
+    // groups of one geometry, batch order inside each
+    GeometryGroups groups;
+    for (size_t i = 0; i < count; i++) groups[br_geometry(src[i].H)].push_back((u32)i);
+    const u32 PB = batch_pass_blocks(c);
+    return for_each_group(groups, count, bad_index, [&](const std::vector<u32>& ids) -> int {
         size_t ci = 0;
         u32 b0 = 0;
-        while (ci < gr.second.size()) {
-            if ((rc = batch_pass(c, kind, f, src, off, gr.second, &ci, &b0, PB, d_out, s))) {
-                if (rc == ANSX_ERR_FORMAT && bad_index) *bad_index = count;  // (found on the device: which one is not known)
-                return rc;
-            }
-        }
-    }
-    return ANSX_OK;
+        while (ci < ids.size())
+            if ((rc = batch_pass(c, kind, f, src, off, ids, &ci, &b0, PB, d_out, s))) return rc;
+        return ANSX_OK;
+    });
 }
 
 // --------------------------------------------------------------------------------- ranges of a batch
-// ansx_decode_batch_ranges_dev: the headers of the REFERENCED containers in one round trip -> the
-// host's checks, offsets and capacity -> per geometry, the touched (container, block) pairs, sorted and unique, in
-// passes of at most P: pass_decode on them as on a pass of ansx_decode_batch_dev, with k_piece_gather as the way out.
+// ansx_decode_batch_ranges_dev: the REFERENCED containers (ansx_plan.h, br_refs) and their
+// headers in one round trip (batch_headers) -> the host's checks, offsets and capacity -> per geometry, the touched
+// (container, block) pairs, sorted and unique, in passes of at most P (br_runs, br_pieces, Pass): each pass as one of
+// ansx_decode_batch_dev, with the way out the call names -- k_piece_gather, the scan in front of it, or the scan and
+// k_ngb_search.
 
-struct BrRun {     // consecutive touched blocks b0..b1 of referenced container r, inside one pass
-    u32 r, b0, b1, pass;
-    u64 wl;        // its first int in the pass's work list (a multiple of 4)
-    u32 k0;        // ... and block b0's number among the pass's blocks
-};
-struct BrPiece {   // a range, or the part of one that lies in one run
-    u32 pass;
-    u64 src, dst, count;
-    u32 k;         // the block of the pass its first int lies in
-};
-
-// The union of one container's block spans sp[0..m) (first block << 32 | last block) as ascending stretches of
-// consecutive blocks with a gap between any two, appended to out.  More spans than the container has blocks (point
-// lookups) are counted into a difference array over its blocks; fewer are sorted.
-void br_union(u64* sp, size_t m, u32 nblocks, std::vector<u32>& diff, std::vector<std::pair<u32, u32>>& out)
-{
-    if (m > nblocks) {
-        diff.assign((size_t)nblocks + 1, 0);
-        for (size_t i = 0; i < m; i++) diff[sp[i] >> 32]++, diff[(u32)sp[i] + 1]--;
-        u32 depth = 0, b0 = 0;
-        for (u32 b = 0; b <= nblocks; b++) {
-            const u32 d = depth + diff[b];  // (spans that cover block b; 0 at b = nblocks)
-            if (!depth && d) b0 = b;
-            if (depth && !d) out.push_back({ b0, b - 1 });
-            depth = d;
-        }
-        return;
-    }
-    std::sort(sp, sp + m);
-    u32 b0 = (u32)(sp[0] >> 32), e = (u32)sp[0];
-    for (size_t i = 1; i < m; i++) {
-        const u32 f = (u32)(sp[i] >> 32), l = (u32)sp[i];
-        if (f <= e + 1) {
-            e = std::max(e, l);
-            continue;
-        }
-        out.push_back({ b0, e });
-        b0 = f, e = l;
-    }
-    out.push_back({ b0, e });
-}
-
-// The touched blocks of the ranges `ids` (non-empty, of one geometry: bi ints per block) as runs, sorted by
-// (container, block) and cut where a pass holds PB blocks.  A run's ints start at a multiple of 4 in its pass's work list.
-void br_runs(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, const u64* first, const u32* cnt,
-    const std::vector<u32>& ids, u64 bi, u32 PB, std::vector<BrRun>* runs)
-{
-    // the spans bucketed by container (a counting sort over the referenced containers)
-    std::vector<size_t> at(rs.size() + 1, 0);
-    for (const u32 i : ids) at[rid[i] + 1]++;
-    for (size_t r = 0; r < rs.size(); r++) at[r + 1] += at[r];
-    std::vector<u64> span(ids.size());
-    {
-        std::vector<size_t> put(at.begin(), at.end() - 1);
-        for (const u32 i : ids) span[put[rid[i]]++] = (first[i] / bi) << 32 | ((first[i] + cnt[i] - 1) / bi);
-    }
-    u32 pass = 0, pb = 0;  // the pass being filled, its blocks so far
-    u64 wl = 0;            // ... and its work-list ints
-    std::vector<u32> diff;
-    std::vector<std::pair<u32, u32>> stretch;
-    for (size_t r = 0; r < rs.size(); r++) {
-        if (at[r] == at[r + 1]) continue;
-        stretch.clear();
-        br_union(span.data() + at[r], at[r + 1] - at[r], rs[r].nblocks, diff, stretch);
-        const u64 n = rs[r].H.n;
-        for (const auto& st : stretch)
-            for (u32 b = st.first; b <= st.second;) {
-                const u32 take = (u32)std::min<u64>((u64)st.second - b + 1, PB - pb);
-                runs->push_back({ (u32)r, b, b + take - 1, pass, wl, pb });
-                wl += rup(std::min<u64>(n, ((u64)b + take) * bi) - (u64)b * bi, 4);
-                pb += take;
-                b += take;
-                if (pb == PB) pass++, pb = 0, wl = 0;
-            }
-    }
-}
-
-// Every range's pieces, one per run it crosses (runs cut from one stretch of blocks follow each other), bucketed by
-// pass in range order: pieces PP and their counts PC, pass p's from pfirst[p] to pfirst[p + 1].  PK (optional): the
-// block of its pass every piece starts in.
-void br_pieces(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, const u64* first, const u32* cnt,
-    const std::vector<u64>& off, const std::vector<u32>& ids, u64 bi, const std::vector<BrRun>& runs,
-    std::vector<ansx_piece>* PP, std::vector<u64>* PC, std::vector<u64>* pfirst, std::vector<u32>* PK = nullptr)
-{
-    const u32 npass = runs.back().pass + 1;
-    std::vector<BrPiece> pieces;
-    pieces.reserve(ids.size());
-    pfirst->assign((size_t)npass + 1, 0);
-    for (const u32 i : ids) {
-        const u32 r = rid[i], b0 = (u32)(first[i] / bi);
-        const u64 n = rs[r].H.n;
-        auto it = std::upper_bound(runs.begin(), runs.end(), b0,
-            [r](u32 v, const BrRun& x) { return x.r != r ? r < x.r : v < x.b0; });
-        size_t k = (size_t)(it - runs.begin()) - 1;
-        u64 pos = first[i], left = cnt[i], dst = off[i];
-        for (; left; k++) {
-            const BrRun& rn = runs[k];
-            const u64 take = std::min<u64>(left, std::min<u64>(n, ((u64)rn.b1 + 1) * bi) - pos);
-            pieces.push_back({ rn.pass, rn.wl + (pos - (u64)rn.b0 * bi), dst, take, rn.k0 + ((u32)(pos / bi) - rn.b0) });
-            (*pfirst)[rn.pass + 1]++;
-            pos += take, dst += take, left -= take;
-        }
-    }
-    for (u32 p = 0; p < npass; p++) (*pfirst)[p + 1] += (*pfirst)[p];
-    PP->resize(pieces.size());
-    PC->resize(pieces.size());
-    if (PK) PK->resize(pieces.size());
-    std::vector<u64> put(pfirst->begin(), pfirst->end() - 1);
-    for (const BrPiece& q : pieces) {  // (stable: range order inside a pass)
-        (*PP)[put[q.pass]] = { q.src, q.dst };
-        if (PK) (*PK)[put[q.pass]] = q.k;
-        (*PC)[put[q.pass]++] = q.count;
-    }
-}
-
-// What the sums calls add to a group (ansx_batchrangesums.h): the caller's bases of every
-// referenced container, and for ansx_next_geq_batch_dev the targets and outputs k_ngb_search takes in the gather's place
-struct BrSums {
-    const std::vector<const u32*>* bases;
+// The way out of a batch call, with what each kind needs: the gather's destination; for the sums (DESIGN.md section
+// 3h, ansx_batchrangesums.h) the caller's bases of every referenced container; for ansx_next_geq_batch_dev the targets
+// and the outputs.
+struct BatchOut {
+    WayOutKind kind;
+    u32* d_out;
+    std::vector<const u32*> bases;
     const u32* d_targets;
     u64* d_pos;
     u32* d_ids;
 };
 
-// The work list of a pass of T blocks (geometry bi; D: its plan on the device, section c the sources' bases) -> its
-// running sums in place, every block from its own container's base, and the check of the bases into gflags.  Enqueued
-// between the pass's decode and its gather; no synchronisation.  range_sums_scan's shapes and switch.
-int batch_sums_scan(ansx_ctx* c, u32* list, u64 bi, u32 T, const PassDev& D, u64* agg, u32* gflags, hipStream_t s)
+// The work list of a pass of T blocks (geometry bi; O, B: its table and blocks on the device, SB: its sources' bases) ->
+// its running sums in place, every block from its own container's base, and the check of the bases into gflags.
+// Enqueued between the pass's decode and its gather; no synchronisation.  range_sums_scan's shapes and switch.
+int batch_sums_scan(ansx_ctx* c, u32* list, u64 bi, u32 T, const ansx_blk_out* O, const ansx_batch_blk* B,
+    const ansx_brs_src* SB, u64* agg, u32* gflags, hipStream_t s)
 {
-    const ansx_brs_src* SB = (const ansx_brs_src*)D.c;
     if (bi <= ANSX_RS_CHUNK) {
-        LAUNCH(c, "k_brs_scan_small", k_brs_scan_small, (T + 3) / 4, ANSX_RS_NT, 0, s, list, D.O, D.B, SB, T, gflags);
+        LAUNCH(c, "k_brs_scan_small", k_brs_scan_small, (T + 3) / 4, ANSX_RS_NT, 0, s, list, O, B, SB, T, gflags);
     } else if (bi <= range_sums_wg_max(c)) {
-        LAUNCH(c, "k_brs_scan_block", k_brs_scan_block, T, ANSX_RS_NT, 0, s, list, D.O, D.B, SB, gflags);
+        LAUNCH(c, "k_brs_scan_block", k_brs_scan_block, T, ANSX_RS_NT, 0, s, list, O, B, SB, gflags);
     } else {
         const u32 tpb = (u32)((bi + ANSX_RS_TILE - 1) / ANSX_RS_TILE), grid = T * tpb;
-        LAUNCH(c, "k_brs_reduce", k_brs_reduce, grid, ANSX_RS_NT, 0, s, (const u32*)list, D.O, tpb, agg, (const u32*)gflags);
-        LAUNCH(c, "k_brs_carry", k_brs_carry, T, ANSX_RS_NT, 0, s, agg, tpb * (ANSX_RS_NT / 64u), D.B, SB, gflags);
-        LAUNCH(c, "k_brs_apply", k_brs_apply, grid, ANSX_RS_NT, 0, s, list, D.O, tpb, (const u64*)agg, (const u32*)gflags);
+        LAUNCH(c, "k_brs_reduce", k_brs_reduce, grid, ANSX_RS_NT, 0, s, (const u32*)list, O, tpb, agg, (const u32*)gflags);
+        LAUNCH(c, "k_brs_carry", k_brs_carry, T, ANSX_RS_NT, 0, s, agg, tpb * (ANSX_RS_NT / 64u), B, SB, gflags);
+        LAUNCH(c, "k_brs_apply", k_brs_apply, grid, ANSX_RS_NT, 0, s, list, O, tpb, (const u64*)agg, (const u32*)gflags);
     }
     return ANSX_OK;
 }
 
 // The ranges `ids` (non-empty, in range order) of one geometry; rs: the referenced containers, rid[i] / off[i]: range
-// i's container among them and its place in d_out.  X: the sums calls (the work list scanned in front of the gather; with
-// targets, off[i] is the target's index and k_ngb_search runs in the gather's place).
+// i's container among them and its place in d_out (OUT_SUMS_SEARCH: the target's index).
 int batch_ranges_group(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& rs, const std::vector<u32>& rid,
-    const u64* first, const u32* cnt, const std::vector<u64>& off, const std::vector<u32>& ids, u32 PB, u32* d_out,
-    hipStream_t s, const BrSums* X = nullptr)
+    const u64* first, const u32* cnt, const std::vector<u64>& off, const std::vector<u32>& ids, u32 PB, const BatchOut& out,
+    hipStream_t s)
 {
     int rc;
     const ansx_container_header& H0 = rs[rid[ids[0]]].H;
     const u64 bi = H0.block_ints;
     const u64 bbound = block_bound(kind, (u32)f, (size_t)bi, (H0.kind & 0x100u) != 0);
+    const bool sums = out.kind != OUT_GATHER, search = out.kind == OUT_SUMS_SEARCH;
     std::vector<BrRun> runs;
     br_runs(rs, rid, first, cnt, ids, bi, PB, &runs);
     std::vector<ansx_piece> PP;
     std::vector<u64> PC, pfirst;
-    std::vector<u32> PK;  // (ansx_next_geq_batch_dev: every piece's block of its pass)
-    const bool search = X && X->d_targets;
+    std::vector<u32> PK;  // (the search: every piece's block of its pass)
     br_pieces(rs, rid, first, cnt, off, ids, bi, runs, &PP, &PC, &pfirst, search ? &PK : nullptr);
     const u32 npass = runs.back().pass + 1;
 
-    std::vector<ansx_batch_src> S;
-    std::vector<ansx_batch_blk> B;
-    std::vector<ansx_blk_out> O;
-    std::vector<u64> wpos;
-    std::vector<ansx_brs_src> SB;  // (the sums calls: the bases of the pass's sources, beside S)
+    Pass P;
     size_t k = 0;
     for (u32 p = 0; p < npass; p++) {
-        // the pass's sources (one per container), blocks and table, as batch_pass builds them
-        S.clear(), B.clear(), O.clear(), SB.clear();
-        u64 cap_pay = 0, wl_pass = 0;
-        u32 sblocks = 0;  // blocks of the source being filled
-        ansx_container_header Hs = H0;
-        Hs.max_nsyms = 0, Hs.max_log2_frame = 0, Hs.max_present_m1 = 0;  // (the maxima over the pass's sources)
-        const auto close_source = [&]() {
-            if (!S.empty()) cap_pay += std::min<u64>(S.back().payload_bytes, (u64)sblocks * bbound);
-            sblocks = 0;
-        };
-        for (u32 last_r = 0; k < runs.size() && runs[k].pass == p; k++) {
-            const BrRun& rn = runs[k];
-            const BatchSrc& cs = rs[rn.r];
-            if (S.empty() || rn.r != last_r) {
-                close_source();
-                S.push_back({ cs.base, cs.lay.ckoff_off, cs.lay.ckstate_off, cs.lay.hint_off, cs.lay.payload_off,
-                    cs.H.payload_bytes, cs.nblocks, 0 });
-                if (X) SB.push_back({ (u64)(uintptr_t)(*X->bases)[rn.r], cs.nblocks, 0 });
-                Hs.max_nsyms = std::max(Hs.max_nsyms, cs.H.max_nsyms);
-                Hs.max_log2_frame = std::max(Hs.max_log2_frame, cs.H.max_log2_frame);
-                Hs.max_present_m1 = std::max(Hs.max_present_m1, cs.H.max_present_m1);
-                last_r = rn.r;
-            }
-            for (u32 b = rn.b0; b <= rn.b1; b++) {
-                B.push_back({ (u32)S.size() - 1, b });
-                O.push_back({ rn.wl + (u64)(b - rn.b0) * bi, (u32)std::min<u64>(bi, cs.H.n - (u64)b * bi), 0 });
-            }
-            sblocks += rn.b1 - rn.b0 + 1;
-            wl_pass = rn.wl + rup(std::min<u64>(cs.H.n, ((u64)rn.b1 + 1) * bi) - (u64)rn.b0 * bi, 4);
-        }
-        close_source();
+        k = P.take_runs(H0, rs, runs, k, p, bi, bbound);
         const u64 np = pfirst[p + 1] - pfirst[p];
         if (np > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-        wpos.resize(np + 1);
-        u64 ints = 0;
-        for (u64 q = 0; q < np; q++) wpos[q] = ints, ints += PC[pfirst[p] + q];
-        wpos[np] = ints;
-        // the tail: pieces | their exclusive prefix over the pass
-        PassTail tail = { PP.data() + pfirst[p], sizeof(ansx_piece) * np, wpos.data(), 8 * (np + 1) };
-        const u32 T = (u32)B.size();
+        const u32 T = (u32)P.B.size();
+        // behind the pass's own sections: pieces | their exclusive prefix over the pass -- or, for the search, where a
+        // piece is one int at the start of a block, that block of the pass in the prefix's place | the sources' bases
+        PassUp D(P);
+        Upload& U = D.U;
+        const auto s_pp = U.add<ansx_piece>(np);
+        const auto s_pk = U.add<u32>(search ? np : 0);
+        const auto s_wp = U.add<u64>(search ? 0 : np + 1);
+        const auto s_sb = U.add<ansx_brs_src>(sums ? P.cont.size() : 0);
         u64* agg = nullptr;
-        if (X) {
-            tail.c = SB.data(), tail.c_bytes = sizeof(ansx_brs_src) * SB.size();
-            if ((rc = range_sums_workspace(c, bi, T, &agg))) return rc;  // (here: growing it may wait for the device)
+        if (sums && (rc = range_sums_workspace(c, bi, T, &agg))) return rc;  // (here: growing it may wait for the device)
+        if ((rc = upload_room(c, U, c->rng_plan))) return rc;
+        U.put(s_pp, PP.data() + pfirst[p]);
+        u64 ints = 0;
+        if (search) U.put(s_pk, PK.data() + pfirst[p]);
+        else {
+            u64* wpos = U.pin(s_wp);
+            for (u64 q = 0; q < np; q++) wpos[q] = ints, ints += PC[pfirst[p] + q];
+            wpos[np] = ints;
         }
-        if (search) {
-            // a piece is one int at the start of a block of the pass: which block takes the place of the prefix, which
-            // only the gather needs
-            tail.b = PK.data() + pfirst[p], tail.b_bytes = 4 * np;
-        }
-        const PassGather gather = [&](const u32* list, const u8* da, const u8* db, const u32* gflags, const PassDev& D) -> int {
-            // (the sums calls: the work list becomes ids first, in place; the scan reports foreign bases in gflags)
-            if (X && (rc = batch_sums_scan(c, (u32*)list, bi, T, D, agg, (u32*)gflags, s))) return rc;
+        for (size_t j = 0; sums && j < P.cont.size(); j++)
+            U.pin(s_sb)[j] = { (u64)(uintptr_t)out.bases[P.cont[j]], rs[P.cont[j]].nblocks, 0 };
+        Sub sub;
+        if ((rc = pass_build(c, kind, f, P, D, &sub, s))) return rc;
+        rc = sub_decode(c, sub, U.dev(D.flags), [&](u32* gflags) -> int {
+            int st;
+            // (the sums: the work list becomes ids first, in place; the scan reports foreign bases in gflags)
+            if (sums && (st = batch_sums_scan(c, sub.list, bi, T, U.dev(D.O), U.dev(D.B), U.dev(s_sb), agg, gflags, s))) return st;
             if (search) {
-                LAUNCH(c, "k_ngb_search", k_ngb_search, (u32)((np + ANSX_NGB_NT - 1) / ANSX_NGB_NT), ANSX_NGB_NT, 0, s, list, D.O,
-                    D.B, T, bi, (const ansx_piece*)da, (const u32*)db, (u32)np, X->d_targets, X->d_pos, X->d_ids, gflags,
-                    D.dflags);
+                LAUNCH(c, "k_ngb_search", k_ngb_search, (u32)((np + ANSX_NGB_NT - 1) / ANSX_NGB_NT), ANSX_NGB_NT, 0, s,
+                    (const u32*)sub.list, (const ansx_blk_out*)U.dev(D.O), (const ansx_batch_blk*)U.dev(D.B), T, bi,
+                    (const ansx_piece*)U.dev(s_pp), (const u32*)U.dev(s_pk), (u32)np, out.d_targets, out.d_pos, out.d_ids,
+                    (const u32*)gflags, (const u32*)U.dev(D.flags));
                 return ANSX_OK;
             }
             const u32 grid = (u32)std::min<u64>((ints + ANSX_PIECE_CHUNK - 1) / ANSX_PIECE_CHUNK, 1u << 20);
-            LAUNCH(c, "k_piece_gather", k_piece_gather, grid, 256, 0, s, list, (const ansx_piece*)da, (const u64*)db, (u32)np,
-                ints, d_out, gflags);
+            LAUNCH(c, "k_piece_gather", k_piece_gather, grid, 256, 0, s, (const u32*)sub.list, (const ansx_piece*)U.dev(s_pp),
+                (const u64*)U.dev(s_wp), (u32)np, ints, out.d_out, (const u32*)gflags);
             return ANSX_OK;
-        };
-        if ((rc = pass_decode(c, kind, f, H0, Hs, S, B, O, wl_pass, cap_pay, tail, gather, s))) return rc;
+        }, s);
+        if (rc) return rc;
     }
     return ANSX_OK;
 }
 
-// The front half, which ansx_next_geq_batch_dev shares (src: the container every range or target names): the referenced
-// containers `ref`, every range's place among them `rid`, and their checked headers `rs`.  nbases (the sums calls): every
-// referenced container's count of bases against its blocks, behind the header checks.
+// The front half every call on ranges of a batch shares (src: the container every range or target names): the
+// referenced containers `ref`, every range's place among them `rid`, and their checked headers `rs`.  nbases (the
+// sums): every referenced container's count of bases against its blocks, behind the header checks.
 struct BrFront {
     std::vector<u32> ref, rid;
     std::vector<BatchSrc> rs;
@@ -2878,86 +2702,30 @@ int batch_ranges_front(ansx_ctx* c, int kind, int f, const u8* const* d_ins, con
     const u32* src, size_t nranges, const size_t* nbases, BrFront* F, size_t* bad_container, hipStream_t s)
 {
     int rc;
-    // the referenced containers, in batch order, and every range's place among them (rid); nothing below looks at any
-    // other container.  A batch that is not much larger than the query is marked in an array over its positions, a
-    // larger one is found by sorting the names.
-    std::vector<u32>& ref = F->ref;
-    std::vector<u32>& rid = F->rid;
-    rid.resize(nranges);
-    if (count <= 4 * nranges + 1024) {
-        std::vector<u32> slot(count, 0);
-        for (size_t i = 0; i < nranges; i++) slot[src[i]] = 1;
-        for (size_t j = 0; j < count; j++)
-            if (slot[j]) slot[j] = (u32)ref.size(), ref.push_back((u32)j);
-        for (size_t i = 0; i < nranges; i++) rid[i] = slot[src[i]];
-    } else {
-        ref.assign(src, src + nranges);
-        std::sort(ref.begin(), ref.end());
-        ref.erase(std::unique(ref.begin(), ref.end()), ref.end());
-        for (size_t i = 0; i < nranges; i++) rid[i] = (u32)(std::lower_bound(ref.begin(), ref.end(), src[i]) - ref.begin());
-    }
-    const size_t nref = ref.size();
-
-    // their headers in one round trip: the addresses up (0 for an input too short to hold one), the headers back
-    const size_t o_h = rup(8 * nref, 16), bytes = o_h + 64 * nref;
-    if ((rc = ensure_pin(c, bytes))) return rc;
-    if ((rc = ensure(c, c->bat_hdr, bytes))) return rc;
-    u64* hp = (u64*)c->rng_pin;
-    for (size_t j = 0; j < nref; j++)
-        hp[j] = in_bytes[ref[j]] >= sizeof(ansx_container_header) ? (u64)(uintptr_t)d_ins[ref[j]] : 0;
-    u8* dw = (u8*)c->bat_hdr.p;
-    HIPCHK(c, hipMemcpyAsync(dw, hp, 8 * nref, hipMemcpyHostToDevice, s));
-    LAUNCH(c, "k_batch_headers", k_batch_headers, (u32)((4 * (u64)nref + 255) / 256), 256, 0, s, (const u64*)dw, (u64)nref,
-        (uint4*)(dw + o_h));
-    HIPCHK(c, hipMemcpyAsync(c->rng_pin + o_h, dw + o_h, 64 * nref, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-
-    // decode_batch's checks on every one of them, in batch order
-    std::vector<BatchSrc>& rs = F->rs;
-    rs.resize(nref);
-    for (size_t j = 0; j < nref; j++) {
-        BatchSrc& b = rs[j];
-        const size_t nb = in_bytes[ref[j]];
-        Plan P;
-        if (nb < sizeof(ansx_container_header) || parse_header(c->rng_pin + o_h + 64 * j, nb, &b.H)
-            || container_plan(b.H, (u32)kind, (u32)f, nb, &P)) {  // (a single-stream stream has no magic)
-            if (bad_container) *bad_container = ref[j];
-            return ANSX_ERR_FORMAT;
-        }
-        b.lay = P.lay;
-        b.base = (u64)(uintptr_t)d_ins[ref[j]];
-        b.nblocks = P.g.nblocks;
+    br_refs(src, nranges, count, &F->ref, &F->rid);  // (nothing below looks at any other container)
+    const std::vector<u32>& ref = F->ref;
+    size_t bad = 0;
+    if ((rc = batch_headers(c, kind, f, d_ins, in_bytes, ref.data(), ref.size(), &F->rs, &bad, s))) {
+        if (rc == ANSX_ERR_FORMAT && bad_container) *bad_container = ref[bad];
+        return rc;
     }
     if (nbases)
-        for (size_t j = 0; j < nref; j++)
-            if (nbases[ref[j]] != (size_t)rs[j].nblocks + 1) {
+        for (size_t j = 0; j < ref.size(); j++)
+            if (nbases[ref[j]] != (size_t)F->rs[j].nblocks + 1) {
                 if (bad_container) *bad_container = ref[j];
                 return ANSX_ERR_ARG;
             }
     return ANSX_OK;
 }
 
-// the geometry a container's blocks are grouped by: block_ints, restart interval, compaction, restart-point format
-std::array<u32, 4> br_geometry(const ansx_container_header& H)
-{
-    return { H.block_ints, H.ckpt_interval, (H.kind >> 8) & 1u, (H.kind >> 9) & 1u };
-}
-
-// bases (the sums call): d_bases / nbases of every container of the batch, HOST arrays
-struct BatchBases {
-    const u32* const* d;
-    const size_t* n;
-};
-
+// d_bases / nbases (the sums): those of every container of the batch, HOST arrays; null for the plain call
 int decode_batch_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
     const u32* src, const u64* first, const u32* cnt, size_t nranges, u32* d_out, size_t cap, u64* offsets, u64* total_ints,
-    size_t* bad_container, size_t* bad_range, hipStream_t s, const BatchBases* bases = nullptr)
+    size_t* bad_container, size_t* bad_range, const u32* const* d_bases, const size_t* nbases, hipStream_t s)
 {
     int rc;
     BrFront F;
-    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, src, nranges, bases ? bases->n : nullptr, &F,
-             bad_container, s)))
-        return rc;
+    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, src, nranges, nbases, &F, bad_container, s))) return rc;
     const std::vector<u32>& rid = F.rid;
     const std::vector<BatchSrc>& rs = F.rs;
     // every range against its own container's n; the offsets and the total
@@ -2978,63 +2746,53 @@ int decode_batch_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, co
     if (total > cap) return ANSX_ERR_CAPACITY;
     if (total == 0) return ANSX_OK;
 
-    // the non-empty ranges by geometry (block_ints, restart interval, compaction, restart-point format), range order inside
-    std::map<std::array<u32, 4>, std::vector<u32>> groups;
-    for (size_t i = 0; i < nranges; i++) {
-        if (!cnt[i]) continue;
-        groups[br_geometry(rs[rid[i]].H)].push_back((u32)i);
-    }
-    std::vector<const u32*> rbases;  // (the sums call: the bases of the referenced containers)
-    BrSums X = { &rbases, nullptr, nullptr, nullptr };
-    if (bases)
-        for (const u32 j : F.ref) rbases.push_back(bases->d[j]);
-    const u32 PB = c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT;
-    for (const auto& gr : groups) {
-        if ((rc = batch_ranges_group(c, kind, f, rs, rid, first, cnt, off, gr.second, PB, d_out, s, bases ? &X : nullptr))) {
-            if (rc == ANSX_ERR_FORMAT && bad_container) *bad_container = count;  // (found on the device: which one is not known)
-            return rc;
-        }
-    }
-    return ANSX_OK;
+    // the non-empty ranges by geometry, range order inside
+    GeometryGroups groups;
+    for (size_t i = 0; i < nranges; i++)
+        if (cnt[i]) groups[br_geometry(rs[rid[i]].H)].push_back((u32)i);
+    BatchOut out = { d_bases ? OUT_SUMS_GATHER : OUT_GATHER, d_out, {}, nullptr, nullptr, nullptr };
+    for (size_t j = 0; d_bases && j < F.ref.size(); j++) out.bases.push_back(d_bases[F.ref[j]]);  // (the referenced containers')
+    const u32 PB = batch_pass_blocks(c);
+    return for_each_group(groups, count, bad_container, [&](const std::vector<u32>& ids) -> int {
+        return batch_ranges_group(c, kind, f, rs, rid, first, cnt, off, ids, PB, out, s);
+    });
 }
 
 // ansx_next_geq_batch_dev (ansx_batchnextgeq.h): the front half above over the lists the targets
 // name -> k_ngb_locate, a lane per target -> ONE read-back of the located blocks, checked -> the found targets as ranges
 // of one int at the start of their blocks, destination the target's own index -> the passes of the sums call with
-// k_ngb_search in the gather's place.
-int next_geq_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const BatchBases& bases,
-    size_t count, const u32* src, const u32* d_targets, size_t nt, u64* d_pos, u32* d_ids, u64* found, size_t* bad_container,
-    hipStream_t s)
+// k_ngb_search as the way out.
+int next_geq_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u32* const* d_bases,
+    const size_t* nbases, size_t count, const u32* src, const u32* d_targets, size_t nt, u64* d_pos, u32* d_ids, u64* found,
+    size_t* bad_container, hipStream_t s)
 {
     int rc;
     BrFront F;
-    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, src, nt, bases.n, &F, bad_container, s))) return rc;
+    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, src, nt, nbases, &F, bad_container, s))) return rc;
     const size_t nref = F.ref.size();
+    BatchOut out = { OUT_SUMS_SEARCH, nullptr, {}, d_targets, d_pos, d_ids };
+    for (const u32 j : F.ref) out.bases.push_back(d_bases[j]);  // (the referenced containers')
     // up: the lists | every target's list; down: every target's block.  24 bytes per referenced container and 8 per
     // target of workspace, the same again pinned on the host.
-    const size_t o_r = rup(sizeof(ansx_ngb_list) * nref, 16), o_b = rup(o_r + 4 * nt, 16), bytes = o_b + 4 * nt;
-    if ((rc = ensure_pin(c, bytes))) return rc;
-    if ((rc = ensure(c, c->rng_dev, bytes))) return rc;
-    u8* hb = c->rng_pin;  // (no copy out of it is pending: the front half ended in a synchronisation)
-    ansx_ngb_list* hl = (ansx_ngb_list*)hb;
-    std::vector<const u32*> rbases(nref);
-    for (size_t j = 0; j < nref; j++) {
-        rbases[j] = bases.d[F.ref[j]];
-        hl[j] = { (u64)(uintptr_t)rbases[j], F.rs[j].H.n, F.rs[j].nblocks, 0 };
-    }
-    memcpy(hb + o_r, F.rid.data(), 4 * nt);
-    u8* w = (u8*)c->rng_dev.p;
-    HIPCHK(c, hipMemcpyAsync(w, hb, o_r + 4 * nt, hipMemcpyHostToDevice, s));
+    Upload U;
+    const auto s_l = U.add<ansx_ngb_list>(nref);
+    const auto s_rid = U.add<u32>(nt);
+    const auto s_blk = U.add<u32>(nt);  // (comes back)
+    if ((rc = upload_room(c, U, c->rng_dev))) return rc;
+    ansx_ngb_list* hl = U.pin(s_l);
+    for (size_t j = 0; j < nref; j++) hl[j] = { (u64)(uintptr_t)out.bases[j], F.rs[j].H.n, F.rs[j].nblocks, 0 };
+    U.put(s_rid, F.rid.data());
+    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, s_rid.off + s_rid.bytes, hipMemcpyHostToDevice, s));
     LAUNCH(c, "k_ngb_locate", k_ngb_locate, (u32)((nt + ANSX_NGB_NT - 1) / ANSX_NGB_NT), ANSX_NGB_NT, 0, s,
-        (const ansx_ngb_list*)w, (const u32*)(w + o_r), d_targets, (u32)nt, (u32*)(w + o_b), d_pos, d_ids);
-    HIPCHK(c, hipMemcpyAsync(hb + o_b, w + o_b, 4 * nt, hipMemcpyDeviceToHost, s));
+        (const ansx_ngb_list*)U.dev(s_l), (const u32*)U.dev(s_rid), d_targets, (u32)nt, U.dev(s_blk), d_pos, d_ids);
+    HIPCHK(c, hipMemcpyAsync(U.pin(s_blk), U.dev(s_blk), 4 * nt, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
 
     // every located block against its list; the found targets as ranges, grouped by geometry
-    const u32* blk = (const u32*)(hb + o_b);
+    const u32* blk = U.pin(s_blk);
     std::vector<u64> first(nt), off(nt);
     std::vector<u32> cnt(nt);
-    std::map<std::array<u32, 4>, std::vector<u32>> groups;
+    GeometryGroups groups;
     u64 nfound = 0;
     for (size_t i = 0; i < nt; i++) {
         const BatchSrc& cs = F.rs[F.rid[i]];
@@ -3051,16 +2809,12 @@ int next_geq_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const s
         groups[br_geometry(cs.H)].push_back((u32)i);
         nfound++;
     }
-    const BrSums X = { &rbases, d_targets, d_pos, d_ids };
-    const u32 PB = c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT;
-    for (const auto& gr : groups) {
-        if ((rc = batch_ranges_group(c, kind, f, F.rs, F.rid, first.data(), cnt.data(), off, gr.second, PB, nullptr, s, &X))) {
-            if (rc == ANSX_ERR_FORMAT && bad_container) *bad_container = count;  // (found on the device: which one is not known)
-            return rc;
-        }
-    }
-    if (found) *found = nfound;
-    return ANSX_OK;
+    const u32 PB = batch_pass_blocks(c);
+    rc = for_each_group(groups, count, bad_container, [&](const std::vector<u32>& ids) -> int {
+        return batch_ranges_group(c, kind, f, F.rs, F.rid, first.data(), cnt.data(), off, ids, PB, out, s);
+    });
+    if (rc == ANSX_OK && found) *found = nfound;
+    return rc;
 }
 
 // --------------------------------------------------------------------------------- batch encode
@@ -3395,7 +3149,72 @@ int block_bases(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, u
     return decode_dev(c, P, d_in, in_bytes, list, s, O);
 }
 
-// the argument checks of ansx_decode_batch_dev, everything it decides before the context is touched
+// The argument checks of the random-access entry points, one per argument shape: everything a call decides before the
+// context is touched.  The plain and the sums entry of a shape share them; what a sums or search entry adds (bases,
+// targets, outputs) it checks itself.
+// ... a container and ranges in host arrays
+int ranges_args(const ansx_ctx* c, const uint8_t* d_in, const uint32_t* d_out, const uint64_t* first, const uint32_t* count,
+    size_t nranges)
+{
+    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!first || !count)) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    return ANSX_OK;
+}
+
+// ... a container and ranges in device arrays
+int device_ranges_args(const ansx_ctx* c, const uint8_t* d_in, const uint32_t* d_out, const uint64_t* d_first,
+    const uint32_t* d_count, size_t nranges, const uint64_t* d_offsets)
+{
+    if (ranges_args(c, d_in, d_out, d_first, d_count, nranges)) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_first & 7u) || ((uintptr_t)d_count & 3u) || ((uintptr_t)d_offsets & 7u)) return ANSX_ERR_ARG;
+    return nranges > 0xFFFFFFFFull ? ANSX_ERR_ARG : ANSX_OK;
+}
+
+// ... a batch and src[0..n), the container every range or target names; with_bases: every named container's bases too.
+// *bad: the first range or target that names no container of the batch, else the first whose container (or bases) is
+// null or misaligned -- only the containers some range names are looked at.
+int batch_src_args(const ansx_ctx* c, const uint8_t* const* d_ins, const size_t* in_bytes, bool with_bases,
+    const uint32_t* const* d_bases, const size_t* nbases, size_t count, const uint32_t* src, size_t n, size_t* bad)
+{
+    if (!c || count > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (n > 0 && (!src || !d_ins || !in_bytes || (with_bases && (!d_bases || !nbases)))) return ANSX_ERR_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (src[i] >= count) {
+            if (bad) *bad = i;
+            return ANSX_ERR_ARG;
+        }
+    for (size_t i = 0; i < n; i++)
+        if (!d_ins[src[i]] || ((uintptr_t)d_ins[src[i]] & 15u)
+            || (with_bases && (!d_bases[src[i]] || ((uintptr_t)d_bases[src[i]] & 3u)))) {
+            if (bad) *bad = i;
+            return ANSX_ERR_ARG;
+        }
+    return ANSX_OK;
+}
+
+// What every entry point of the family does behind its checks: the device, the stream, and the body run where the
+// host's arrays of a huge query or batch may not fit
+template <class F> int run_call(ansx_ctx* c, void* stream, const F& body)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    try {
+        return body(stream ? (hipStream_t)stream : c->stream);
+    } catch (const std::bad_alloc&) {
+        c->last_hip = (int)hipErrorOutOfMemory;
+        return ANSX_ERR_HIP;
+    }
+}
+
+// the call of a batch entry with nothing to do
+int empty_batch(uint64_t* offsets, uint64_t* total_ints)
+{
+    if (offsets) offsets[0] = 0;
+    if (total_ints) *total_ints = 0;
+    return ANSX_OK;
+}
+
+// ... a batch (ansx_decode_batch_dev, ansx_decode_batch_sums_dev)
 int decode_batch_args(const ansx_ctx* c, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count, const uint32_t* d_out,
     size_t out_capacity_ints)
 {
@@ -3717,13 +3536,12 @@ int ansx_decode_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, si
     const uint32_t* count, size_t nranges, uint32_t* d_out, size_t out_capacity_ints, void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
-    if (nranges > 0 && (!first || !count)) return ANSX_ERR_ARG;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    if (ranges_args(c, d_in, d_out, first, count, nranges)) return ANSX_ERR_ARG;
     if (nranges == 0) return ANSX_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return decode_ranges(c, kind, f, d_in, in_bytes, (const u64*)first, count, nranges, d_out, out_capacity_ints, s);
+    const RangeOut out = { OUT_GATHER, d_out };
+    return run_call(c, stream, [&](hipStream_t s) {
+        return decode_ranges(c, kind, f, d_in, in_bytes, (const u64*)first, count, nranges, out_capacity_ints, out, s);
+    });
 }
 
 int ansx_decode_device_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes,
@@ -3731,20 +3549,13 @@ int ansx_decode_device_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* d
     uint64_t* d_offsets, uint64_t* total_ints, void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
-    if (nranges > 0 && (!d_first || !d_count)) return ANSX_ERR_ARG;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u) || ((uintptr_t)d_first & 7u) || ((uintptr_t)d_count & 3u)
-        || ((uintptr_t)d_offsets & 7u))
-        return ANSX_ERR_ARG;
-    if (nranges > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-    if (nranges == 0) {
-        if (total_ints) *total_ints = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return decode_device_ranges(c, kind, f, d_in, in_bytes, (const u64*)d_first, d_count, nranges, d_out,
-        out_capacity_ints, (u64*)d_offsets, (u64*)total_ints, s);
+    if (device_ranges_args(c, d_in, d_out, d_first, d_count, nranges, d_offsets)) return ANSX_ERR_ARG;
+    if (nranges == 0) return empty_batch(nullptr, total_ints);
+    const RangeOut out = { OUT_GATHER, d_out };
+    return run_call(c, stream, [&](hipStream_t s) {
+        return decode_device_ranges(c, kind, f, d_in, in_bytes, (const u64*)d_first, d_count, nranges, out_capacity_ints,
+            (u64*)d_offsets, (u64*)total_ints, out, s);
+    });
 }
 
 int ansx_decode_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, const uint32_t* d_bases,
@@ -3752,15 +3563,13 @@ int ansx_decode_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_i
     void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
-    if (nranges > 0 && (!first || !count)) return ANSX_ERR_ARG;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    if (ranges_args(c, d_in, d_out, first, count, nranges)) return ANSX_ERR_ARG;
     if (nranges > 0 && (!d_bases || ((uintptr_t)d_bases & 3u))) return ANSX_ERR_ARG;
     if (nranges == 0) return ANSX_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const RangeBases bases = { d_bases, nbases };
-    return decode_ranges(c, kind, f, d_in, in_bytes, (const u64*)first, count, nranges, d_out, out_capacity_ints, s, &bases);
+    const RangeOut out = { OUT_SUMS_GATHER, d_out, d_bases, nbases };
+    return run_call(c, stream, [&](hipStream_t s) {
+        return decode_ranges(c, kind, f, d_in, in_bytes, (const u64*)first, count, nranges, out_capacity_ints, out, s);
+    });
 }
 
 int ansx_decode_device_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes,
@@ -3768,22 +3577,14 @@ int ansx_decode_device_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8
     size_t out_capacity_ints, uint64_t* d_offsets, uint64_t* total_ints, void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
-    if (nranges > 0 && (!d_first || !d_count)) return ANSX_ERR_ARG;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u) || ((uintptr_t)d_first & 7u) || ((uintptr_t)d_count & 3u)
-        || ((uintptr_t)d_offsets & 7u))
-        return ANSX_ERR_ARG;
-    if (nranges > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (device_ranges_args(c, d_in, d_out, d_first, d_count, nranges, d_offsets)) return ANSX_ERR_ARG;
     if (nranges > 0 && (!d_bases || ((uintptr_t)d_bases & 3u))) return ANSX_ERR_ARG;
-    if (nranges == 0) {
-        if (total_ints) *total_ints = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const RangeBases bases = { d_bases, nbases };
-    return decode_device_ranges(c, kind, f, d_in, in_bytes, (const u64*)d_first, d_count, nranges, d_out,
-        out_capacity_ints, (u64*)d_offsets, (u64*)total_ints, s, &bases);
+    if (nranges == 0) return empty_batch(nullptr, total_ints);
+    const RangeOut out = { OUT_SUMS_GATHER, d_out, d_bases, nbases };
+    return run_call(c, stream, [&](hipStream_t s) {
+        return decode_device_ranges(c, kind, f, d_in, in_bytes, (const u64*)d_first, d_count, nranges, out_capacity_ints,
+            (u64*)d_offsets, (u64*)total_ints, out, s);
+    });
 }
 
 int ansx_next_geq_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, const uint32_t* d_bases,
@@ -3796,17 +3597,12 @@ int ansx_next_geq_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t 
         || ((uintptr_t)d_ids & 3u))
         return ANSX_ERR_ARG;
     if (ntargets > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-    if (ntargets == 0) {
-        if (found) *found = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const RangeBases bases = { d_bases, nbases };
-    NextGeq ng = { d_targets, (u64*)d_pos, d_ids, nullptr, nullptr, nullptr };
-    u64 total = 0;
-    const int rc = device_ranges_body(c, kind, f, d_in, in_bytes, nullptr, nullptr, ntargets, nullptr, ntargets, nullptr,
-        &total, s, &bases, &ng);
+    if (ntargets == 0) return empty_batch(nullptr, found);
+    const RangeOut out = { OUT_SUMS_SEARCH, nullptr, d_bases, nbases, d_targets, (u32)ntargets, (u64*)d_pos, d_ids };
+    u64 total = 0;  // (the targets found; the ranges are the front's own: no first, count or offsets from here)
+    const int rc = run_call(c, stream, [&](hipStream_t s) {
+        return decode_device_ranges(c, kind, f, d_in, in_bytes, nullptr, nullptr, ntargets, ntargets, nullptr, &total, out, s);
+    });
     if (rc == ANSX_OK && found) *found = total;
     return rc;
 }
@@ -3827,20 +3623,12 @@ int ansx_decode_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_
     uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_index, void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c || count > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-    if (count > 0 && (!d_ins || !in_bytes)) return ANSX_ERR_ARG;
-    if ((!d_out && out_capacity_ints > 0) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
-    for (size_t i = 0; i < count; i++)
-        if (!d_ins[i] || ((uintptr_t)d_ins[i] & 15u)) return ANSX_ERR_ARG;
-    if (count == 0) {
-        if (offsets) offsets[0] = 0;
-        if (total_ints) *total_ints = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return decode_batch(c, kind, f, d_ins, in_bytes, count, d_out, out_capacity_ints, (u64*)offsets, (u64*)total_ints,
-        bad_index, s);
+    if (decode_batch_args(c, d_ins, in_bytes, count, d_out, out_capacity_ints)) return ANSX_ERR_ARG;
+    if (count == 0) return empty_batch(offsets, total_ints);
+    return run_call(c, stream, [&](hipStream_t s) {
+        return decode_batch(c, kind, f, d_ins, in_bytes, count, d_out, out_capacity_ints, (u64*)offsets, (u64*)total_ints,
+            bad_index, s);
+    });
 }
 
 int ansx_decode_batch_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
@@ -3848,28 +3636,14 @@ int ansx_decode_batch_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* co
     size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_container, size_t* bad_range, void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c || count > 0xFFFFFFFFull || nranges > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-    if (nranges > 0 && (!src || !first || !cnt || !d_ins || !in_bytes)) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!first || !cnt)) return ANSX_ERR_ARG;
     if ((!d_out && out_capacity_ints > 0) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
-    for (size_t i = 0; i < nranges; i++)
-        if (src[i] >= count) {
-            if (bad_range) *bad_range = i;
-            return ANSX_ERR_ARG;
-        }
-    for (size_t i = 0; i < nranges; i++)  // (only the containers some range names are looked at)
-        if (!d_ins[src[i]] || ((uintptr_t)d_ins[src[i]] & 15u)) {
-            if (bad_range) *bad_range = i;
-            return ANSX_ERR_ARG;
-        }
-    if (nranges == 0) {
-        if (offsets) offsets[0] = 0;
-        if (total_ints) *total_ints = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return decode_batch_ranges(c, kind, f, d_ins, in_bytes, count, src, (const u64*)first, cnt, nranges, d_out,
-        out_capacity_ints, (u64*)offsets, (u64*)total_ints, bad_container, bad_range, s);
+    if (batch_src_args(c, d_ins, in_bytes, false, nullptr, nullptr, count, src, nranges, bad_range)) return ANSX_ERR_ARG;
+    if (nranges == 0) return empty_batch(offsets, total_ints);
+    return run_call(c, stream, [&](hipStream_t s) {
+        return decode_batch_ranges(c, kind, f, d_ins, in_bytes, count, src, (const u64*)first, cnt, nranges, d_out,
+            out_capacity_ints, (u64*)offsets, (u64*)total_ints, bad_container, bad_range, nullptr, nullptr, s);
+    });
 }
 
 int ansx_decode_batch_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
@@ -3878,34 +3652,14 @@ int ansx_decode_batch_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_
     size_t* bad_container, size_t* bad_range, void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c || count > 0xFFFFFFFFull || nranges > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-    if (nranges > 0 && (!src || !first || !cnt || !d_ins || !in_bytes || !d_bases || !nbases)) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!first || !cnt)) return ANSX_ERR_ARG;
     if ((!d_out && out_capacity_ints > 0) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
-    for (size_t i = 0; i < nranges; i++)
-        if (src[i] >= count) {
-            if (bad_range) *bad_range = i;
-            return ANSX_ERR_ARG;
-        }
-    for (size_t i = 0; i < nranges; i++)  // (only the containers some range names are looked at)
-        if (!d_ins[src[i]] || ((uintptr_t)d_ins[src[i]] & 15u) || !d_bases[src[i]] || ((uintptr_t)d_bases[src[i]] & 3u)) {
-            if (bad_range) *bad_range = i;
-            return ANSX_ERR_ARG;
-        }
-    if (nranges == 0) {
-        if (offsets) offsets[0] = 0;
-        if (total_ints) *total_ints = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const BatchBases bases = { d_bases, nbases };
-    try {
+    if (batch_src_args(c, d_ins, in_bytes, true, d_bases, nbases, count, src, nranges, bad_range)) return ANSX_ERR_ARG;
+    if (nranges == 0) return empty_batch(offsets, total_ints);
+    return run_call(c, stream, [&](hipStream_t s) {
         return decode_batch_ranges(c, kind, f, d_ins, in_bytes, count, src, (const u64*)first, cnt, nranges, d_out,
-            out_capacity_ints, (u64*)offsets, (u64*)total_ints, bad_container, bad_range, s, &bases);
-    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge query)
-        c->last_hip = (int)hipErrorOutOfMemory;
-        return ANSX_ERR_HIP;
-    }
+            out_capacity_ints, (u64*)offsets, (u64*)total_ints, bad_container, bad_range, d_bases, nbases, s);
+    });
 }
 
 int ansx_next_geq_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
@@ -3913,34 +3667,14 @@ int ansx_next_geq_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* 
     size_t ntargets, uint64_t* d_pos, uint32_t* d_ids, uint64_t* found, size_t* bad_container, size_t* bad_target, void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c || count > 0xFFFFFFFFull || ntargets > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-    if (ntargets > 0 && (!src || !d_targets || !d_ins || !in_bytes || !d_bases || !nbases || (!d_pos && !d_ids)))
-        return ANSX_ERR_ARG;
+    if (ntargets > 0 && (!d_targets || (!d_pos && !d_ids))) return ANSX_ERR_ARG;
     if (((uintptr_t)d_targets & 3u) || ((uintptr_t)d_pos & 7u) || ((uintptr_t)d_ids & 3u)) return ANSX_ERR_ARG;
-    for (size_t i = 0; i < ntargets; i++)
-        if (src[i] >= count) {
-            if (bad_target) *bad_target = i;
-            return ANSX_ERR_ARG;
-        }
-    for (size_t i = 0; i < ntargets; i++)  // (only the lists some target names are looked at)
-        if (!d_ins[src[i]] || ((uintptr_t)d_ins[src[i]] & 15u) || !d_bases[src[i]] || ((uintptr_t)d_bases[src[i]] & 3u)) {
-            if (bad_target) *bad_target = i;
-            return ANSX_ERR_ARG;
-        }
-    if (ntargets == 0) {
-        if (found) *found = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const BatchBases bases = { d_bases, nbases };
-    try {
-        return next_geq_batch(c, kind, f, d_ins, in_bytes, bases, count, src, d_targets, ntargets, (u64*)d_pos, d_ids,
+    if (batch_src_args(c, d_ins, in_bytes, true, d_bases, nbases, count, src, ntargets, bad_target)) return ANSX_ERR_ARG;
+    if (ntargets == 0) return empty_batch(nullptr, found);
+    return run_call(c, stream, [&](hipStream_t s) {
+        return next_geq_batch(c, kind, f, d_ins, in_bytes, d_bases, nbases, count, src, d_targets, ntargets, (u64*)d_pos, d_ids,
             (u64*)found, bad_container, s);
-    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge query)
-        c->last_hip = (int)hipErrorOutOfMemory;
-        return ANSX_ERR_HIP;
-    }
+    });
 }
 
 int ansx_encode_batch_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,
@@ -4005,16 +3739,10 @@ int ansx_decode_batch_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* cons
     uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets, uint64_t* total_ints, size_t* bad_index, void* stream)
 {
     // (every argument check comes before the context is touched)
-    int rc = decode_batch_args(c, d_ins, in_bytes, count, d_out, out_capacity_ints);
-    if (rc) return rc;
-    if (count == 0) {
-        if (offsets) offsets[0] = 0;
-        if (total_ints) *total_ints = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    try {
+    int rc;
+    if ((rc = decode_batch_args(c, d_ins, in_bytes, count, d_out, out_capacity_ints))) return rc;
+    if (count == 0) return empty_batch(offsets, total_ints);
+    return run_call(c, stream, [&](hipStream_t s) -> int {
         std::vector<u64> off(count + 1);  // (the scan needs the offsets whether the caller asked for them or not)
         u64 total = 0;
         rc = decode_batch(c, kind, f, d_ins, in_bytes, count, d_out, out_capacity_ints, off.data(), &total, bad_index, s);
@@ -4025,10 +3753,7 @@ int ansx_decode_batch_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* cons
         if (rc || total == 0) return rc;
         // every pass of every geometry group is through: one scan over the whole output
         return sums_run(c, d_out, total, off.data(), count, bad_index, s);
-    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge batch)
-        c->last_hip = (int)hipErrorOutOfMemory;
-        return ANSX_ERR_HIP;
-    }
+    });
 }
 
 int ansx_encode_gaps_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, size_t n, uint8_t* d_out, size_t cap,

@@ -11,17 +11,7 @@
 
 #include "ansx_ranges.h"
 
-struct ansx_batch_src {  // a source container of a pass
-    u64 base;            // its device address
-    u64 ckoff_off, ckstate_off, hint_off, payload_off;  // its layout (make_plan's for its own n)
-    u64 payload_bytes;   // its header's: index_entry_ok on its own entries
-    u32 nblocks;
-    u32 pad_;
-};
-
-struct ansx_batch_blk {  // block k of a pass is block b of source src
-    u32 src, b;
-};
+// (ansx_batch_src, ansx_batch_blk: ansx_plan_types.h)
 
 // hdr[i] = the 64 bytes at ptrs[i], zeros where ptrs[i] is 0 (an input the host has already found too short); four
 // lanes per header, 16 bytes each (every input is 16-byte aligned: checked by the entry point).

@@ -11,11 +11,7 @@
 
 #include "ansx_ranges.h"
 
-struct ansx_piece {  // ints [src, src + count) of the pass's work list go to [dst, dst + count) of the caller's buffer;
-    u64 src, dst;    // count = wpos[i + 1] - wpos[i], wpos the exclusive prefix of the counts over the pass (count > 0)
-};
-
-#define ANSX_PIECE_CHUNK 4096u  // ints per workgroup of k_piece_gather (k_range_gather's chunk)
+// (ansx_piece, ANSX_PIECE_CHUNK: ansx_plan_types.h)
 
 // d[0..m) = s[0..m), m <= ANSX_PIECE_CHUNK, by the 256 threads of the workgroup: the body of k_range_gather's loop --
 // 16-byte accesses where source and destination agree modulo 16 bytes, dwords otherwise.

@@ -1,7 +1,7 @@
 // Docids of ranges of a batch (ansx_decode_batch_ranges_sums_dev), the scan ansx_next_geq_batch_dev shares with it, and
 // the bases of a batch from the writer (ansx_encode_batch_gaps_bases_dev); DESIGN.md section 3h.  gfx950 only.
 //
-// Input.  The work list of a pass (pass_decode in ansx.hip): block k of the pass is the ints [O[k].off, O[k].off + O[k].n)
+// Input.  The work list of a pass (pass_build in ansx.hip): block k of the pass is the ints [O[k].off, O[k].off + O[k].n)
 // of `list`, block B[k].b of source B[k].src; SB[B[k].src] holds that source's bases and its block count.  O[k].off is a
 // multiple of 4 and the list 16-byte aligned, so every block starts on a 16-byte boundary; ANY block may be short (it
 // may be its container's last), and up to 3 padding ints lie between the runs of two containers.  Output: the list in
@@ -22,11 +22,7 @@
 #include "ansx_batch.h"
 #include "ansx_rangesums.h"
 
-struct ansx_brs_src {  // a source of a pass, beside its ansx_batch_src: the caller's bases of that container
-    u64 bases;         // device address of its nblocks + 1 entries (4-byte aligned)
-    u32 nblocks;
-    u32 pad_;
-};
+// (ansx_brs_src: ansx_plan_types.h)
 
 // (seed, end) of block k of the pass: entries b and b + 1 of its source's bases; a block number outside the source (no
 // plan names one) fails the check without a read

@@ -4,14 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ansx_plan_types.h"  // u8 .. i64, and the plain structs the host's plans fill (ansx_blk_out, ...)
+
 #define ANSX_HD __host__ __device__ __forceinline__
 #define ANSX_D __device__ __forceinline__
-
-typedef uint8_t u8;
-typedef uint16_t u16;
-typedef uint32_t u32;
-typedef uint64_t u64;
-typedef int64_t i64;
 
 // ---------------------------------------------------------------------------------------------
 // Constants of the reference codec (include/ans_byte.hpp:24-31 as used by ans_fold.hpp)
@@ -321,14 +317,6 @@ struct ansx_geo {
                                       // ansx_batch.h); null everywhere else: block b then has geo_block_n ints at b * block_ints
     const struct ansx_blk_in* bin;    // encode: per-block lengths and input offsets (a pass of ansx_encode_batch_dev,
                                       // ansx_encbatch.h); null everywhere else
-};
-
-// One block of a batch pass: its ints and where they start in the pass's output.  Blocks of many containers share one
-// sub-container there, so any of them may be short and the output of block b does not start at b * block_ints.
-struct ansx_blk_out {
-    u64 off;  // first int in the output (a multiple of 4: the decoders' 16-byte stores)
-    u32 n;    // ints
-    u32 pad_;
 };
 
 // Restart points in the container index.  A state is below 2^36 M and a cursor below the block's

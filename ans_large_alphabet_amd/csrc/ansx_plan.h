@@ -1,0 +1,336 @@
+// ansx -- the host's plans of the random-access calls ("Host side of the random-access calls"):
+// which blocks a set of ranges touches, where every range's ints lie in the work list those blocks decode to, and the
+// tables a pass over blocks of many containers takes.  Pure host arithmetic: no context, no stream, no device pointer
+// (addresses travel as integers), so it builds with a plain host compiler and is tested on the CPU
+// (tests/tools/plan_check.cpp).  The plain structs the kernels read these plans through are in ansx_plan_types.h,
+// which the kernel headers include.
+#pragma once
+#include "../../include/ansx.h"
+#include "ansx_plan_types.h"
+
+#include <algorithm>
+#include <array>
+#include <utility>
+#include <vector>
+
+namespace ansx_plan {
+
+// (Every function here is static inline: with external linkage the compiler stopped folding the planners into their
+// one caller, and the batch calls over thousands of containers ran 2-5 % longer.)
+
+static inline size_t rup(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+struct Layout {  // container layout, a pure function of the geometry (restart-point format included)
+    u64 index_off, ckoff_off, ckstate_off, hint_off, payload_off;
+};
+
+struct BatchSrc {  // a container of the batch, checked
+    ansx_container_header H;
+    Layout lay;
+    u64 base;
+    u32 nblocks;
+};
+
+// ------------------------------------------------------------------------------- ranges of one container
+// The plan of ansx_decode_ranges_dev: tb, the T touched blocks (ascending, unique; last_b the last); one piece per
+// non-empty range, in range order, src counted in the work list the touched blocks decode to (block tb[k] at k * bi);
+// pstart[nr + 1], every piece's first chunk of ANSX_RANGE_CHUNK ints among the npieces chunks.
+struct RangePlan {
+    u64 T = 0, last_b = 0, npieces = 0, total = 0;
+    std::vector<u32> tb, pstart;
+    std::vector<ansx_range_piece> pieces;
+};
+
+// Ranges [first[i], first[i] + count[i]) of a list of n ints in blocks of bi, for an output of cap ints.  ANSX_ERR_ARG
+// for the first range that leaves the list, then ANSX_ERR_CAPACITY; ANSX_OK with total == 0 (and T == 0) where there is
+// nothing to decode.
+// (Kept out of line, like batch_pass_plan below: folded into their callers by the compiler, the call on 2^20 point
+// ranges ran 7 % longer and the batch call on 4096 containers 3 %.)
+__attribute__((noinline)) static int range_plan(u64 n, u64 bi, const u64* first, const u32* count, size_t nranges, u64 cap, RangePlan* R)
+{
+    // ranges -> block spans; their union as sorted runs of consecutive blocks, each numbered from its first touched block
+    u64 total = 0;
+    std::vector<std::pair<u64, u64>> span;  // [first block, last block] of every non-empty range
+    span.reserve(nranges);
+    for (size_t i = 0; i < nranges; i++) {
+        if (first[i] > n || (u64)count[i] > n - first[i]) return ANSX_ERR_ARG;
+        if (!count[i]) continue;
+        span.push_back({ first[i] / bi, (first[i] + count[i] - 1) / bi });
+        total += count[i];  // (at most 2^32 - 1 per range: no wrap below 2^32 ranges)
+    }
+    if (total > cap) return ANSX_ERR_CAPACITY;
+    if (total == 0) return ANSX_OK;
+    std::sort(span.begin(), span.end());
+    struct Run {
+        u64 b0, b1, k0;  // blocks b0..b1 are touched blocks k0.. of the sub-container
+    };
+    std::vector<Run> runs;
+    u64 T = 0;
+    for (const auto& sp : span) {
+        if (!runs.empty() && sp.first <= runs.back().b1 + 1) {
+            if (sp.second > runs.back().b1) {
+                T += sp.second - runs.back().b1;
+                runs.back().b1 = sp.second;
+            }
+            continue;
+        }
+        runs.push_back({ sp.first, sp.second, T });
+        T += sp.second - sp.first + 1;
+    }
+    R->pieces.reserve(span.size());
+    R->pstart.reserve(span.size() + 1);
+    u64 npieces = 0, dst = 0;
+    for (size_t i = 0; i < nranges; i++) {
+        if (!count[i]) continue;
+        const u64 b0 = first[i] / bi;
+        auto it = std::upper_bound(runs.begin(), runs.end(), b0, [](u64 v, const Run& r) { return v < r.b0; });
+        const Run& r = *(it - 1);
+        R->pieces.push_back({ (r.k0 + (b0 - r.b0)) * bi + (first[i] - b0 * bi), dst, (u64)count[i] });
+        R->pstart.push_back((u32)npieces);
+        dst += count[i];
+        npieces += (count[i] + ANSX_RANGE_CHUNK - 1) / ANSX_RANGE_CHUNK;
+    }
+    if (npieces > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    R->pstart.push_back((u32)npieces);
+    R->tb.reserve(T);
+    for (const Run& r : runs)
+        for (u64 b = r.b0; b <= r.b1; b++) R->tb.push_back((u32)b);
+    R->T = T, R->last_b = runs.back().b1, R->npieces = npieces, R->total = total;
+    return ANSX_OK;
+}
+
+// ------------------------------------------------------------------------------- batches
+// the geometry a container's blocks are grouped by: block_ints, restart interval, compaction, restart-point format
+typedef std::array<u32, 4> Geometry;
+static inline Geometry br_geometry(const ansx_container_header& H)
+{
+    return { H.block_ints, H.ckpt_interval, (H.kind >> 8) & 1u, (H.kind >> 9) & 1u };
+}
+
+// The containers the ranges name (src[i] < count), in batch order, and every range's place among them.  A batch that is
+// not much larger than the query is marked in an array over its positions, a larger one is found by sorting the names.
+static inline void br_refs(const u32* src, size_t nranges, size_t count, std::vector<u32>* ref, std::vector<u32>* rid)
+{
+    ref->clear(), rid->resize(nranges);
+    if (count <= 4 * nranges + 1024) {
+        std::vector<u32> slot(count, 0);
+        for (size_t i = 0; i < nranges; i++) slot[src[i]] = 1;
+        for (size_t j = 0; j < count; j++)
+            if (slot[j]) slot[j] = (u32)ref->size(), ref->push_back((u32)j);
+        for (size_t i = 0; i < nranges; i++) (*rid)[i] = slot[src[i]];
+        return;
+    }
+    ref->assign(src, src + nranges);
+    std::sort(ref->begin(), ref->end());
+    ref->erase(std::unique(ref->begin(), ref->end()), ref->end());
+    for (size_t i = 0; i < nranges; i++) (*rid)[i] = (u32)(std::lower_bound(ref->begin(), ref->end(), src[i]) - ref->begin());
+}
+
+struct BrRun {     // consecutive touched blocks b0..b1 of referenced container r, inside one pass
+    u32 r, b0, b1, pass;
+    u64 wl;        // its first int in the pass's work list (a multiple of 4)
+    u32 k0;        // ... and block b0's number among the pass's blocks
+};
+struct BrPiece {   // a range, or the part of one that lies in one run
+    u32 pass;
+    u64 src, dst, count;
+    u32 k;         // the block of the pass its first int lies in
+};
+
+// The union of one container's block spans sp[0..m) (first block << 32 | last block) as ascending stretches of
+// consecutive blocks with a gap between any two, appended to out.  More spans than the container has blocks (point
+// lookups) are counted into a difference array over its blocks; fewer are sorted.
+static inline void br_union(u64* sp, size_t m, u32 nblocks, std::vector<u32>& diff, std::vector<std::pair<u32, u32>>& out)
+{
+    if (m > nblocks) {
+        diff.assign((size_t)nblocks + 1, 0);
+        for (size_t i = 0; i < m; i++) diff[sp[i] >> 32]++, diff[(u32)sp[i] + 1]--;
+        u32 depth = 0, b0 = 0;
+        for (u32 b = 0; b <= nblocks; b++) {
+            const u32 d = depth + diff[b];  // (spans that cover block b; 0 at b = nblocks)
+            if (!depth && d) b0 = b;
+            if (depth && !d) out.push_back({ b0, b - 1 });
+            depth = d;
+        }
+        return;
+    }
+    std::sort(sp, sp + m);
+    u32 b0 = (u32)(sp[0] >> 32), e = (u32)sp[0];
+    for (size_t i = 1; i < m; i++) {
+        const u32 f = (u32)(sp[i] >> 32), l = (u32)sp[i];
+        if (f <= e + 1) {
+            e = std::max(e, l);
+            continue;
+        }
+        out.push_back({ b0, e });
+        b0 = f, e = l;
+    }
+    out.push_back({ b0, e });
+}
+
+// The touched blocks of the ranges `ids` (non-empty, of one geometry: bi ints per block) as runs, sorted by
+// (container, block) and cut where a pass holds PB blocks.  A run's ints start at a multiple of 4 in its pass's work list.
+static inline void br_runs(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, const u64* first, const u32* cnt,
+    const std::vector<u32>& ids, u64 bi, u32 PB, std::vector<BrRun>* runs)
+{
+    // the spans bucketed by container (a counting sort over the referenced containers)
+    std::vector<size_t> at(rs.size() + 1, 0);
+    for (const u32 i : ids) at[rid[i] + 1]++;
+    for (size_t r = 0; r < rs.size(); r++) at[r + 1] += at[r];
+    std::vector<u64> span(ids.size());
+    {
+        std::vector<size_t> put(at.begin(), at.end() - 1);
+        for (const u32 i : ids) span[put[rid[i]]++] = (first[i] / bi) << 32 | ((first[i] + cnt[i] - 1) / bi);
+    }
+    u32 pass = 0, pb = 0;  // the pass being filled, its blocks so far
+    u64 wl = 0;            // ... and its work-list ints
+    std::vector<u32> diff;
+    std::vector<std::pair<u32, u32>> stretch;
+    for (size_t r = 0; r < rs.size(); r++) {
+        if (at[r] == at[r + 1]) continue;
+        stretch.clear();
+        br_union(span.data() + at[r], at[r + 1] - at[r], rs[r].nblocks, diff, stretch);
+        const u64 n = rs[r].H.n;
+        for (const auto& st : stretch)
+            for (u32 b = st.first; b <= st.second;) {
+                const u32 take = (u32)std::min<u64>((u64)st.second - b + 1, PB - pb);
+                runs->push_back({ (u32)r, b, b + take - 1, pass, wl, pb });
+                wl += rup(std::min<u64>(n, ((u64)b + take) * bi) - (u64)b * bi, 4);
+                pb += take;
+                b += take;
+                if (pb == PB) pass++, pb = 0, wl = 0;
+            }
+    }
+}
+
+// Every range's pieces, one per run it crosses (runs cut from one stretch of blocks follow each other), bucketed by
+// pass in range order: pieces PP and their counts PC, pass p's from pfirst[p] to pfirst[p + 1].  PK (optional): the
+// block of its pass every piece starts in.
+static inline void br_pieces(const std::vector<BatchSrc>& rs, const std::vector<u32>& rid, const u64* first, const u32* cnt,
+    const std::vector<u64>& off, const std::vector<u32>& ids, u64 bi, const std::vector<BrRun>& runs,
+    std::vector<ansx_piece>* PP, std::vector<u64>* PC, std::vector<u64>* pfirst, std::vector<u32>* PK = nullptr)
+{
+    const u32 npass = runs.back().pass + 1;
+    std::vector<BrPiece> pieces;
+    pieces.reserve(ids.size());
+    pfirst->assign((size_t)npass + 1, 0);
+    for (const u32 i : ids) {
+        const u32 r = rid[i], b0 = (u32)(first[i] / bi);
+        const u64 n = rs[r].H.n;
+        auto it = std::upper_bound(runs.begin(), runs.end(), b0,
+            [r](u32 v, const BrRun& x) { return x.r != r ? r < x.r : v < x.b0; });
+        size_t k = (size_t)(it - runs.begin()) - 1;
+        u64 pos = first[i], left = cnt[i], dst = off[i];
+        for (; left; k++) {
+            const BrRun& rn = runs[k];
+            const u64 take = std::min<u64>(left, std::min<u64>(n, ((u64)rn.b1 + 1) * bi) - pos);
+            pieces.push_back({ rn.pass, rn.wl + (pos - (u64)rn.b0 * bi), dst, take, rn.k0 + ((u32)(pos / bi) - rn.b0) });
+            (*pfirst)[rn.pass + 1]++;
+            pos += take, dst += take, left -= take;
+        }
+    }
+    for (u32 p = 0; p < npass; p++) (*pfirst)[p + 1] += (*pfirst)[p];
+    PP->resize(pieces.size());
+    PC->resize(pieces.size());
+    if (PK) PK->resize(pieces.size());
+    std::vector<u64> put(pfirst->begin(), pfirst->end() - 1);
+    for (const BrPiece& q : pieces) {  // (stable: range order inside a pass)
+        (*PP)[put[q.pass]] = { q.src, q.dst };
+        if (PK) (*PK)[put[q.pass]] = q.k;
+        (*PC)[put[q.pass]++] = q.count;
+    }
+}
+
+// A pass over blocks of containers of one geometry: its sources S (one per container, `cont` its number among the
+// caller's), its blocks B, the decoders' table O over the pass's work list of wl ints, the header Hs of the
+// sub-container they make (H0's geometry, the maxima over the sources) and cap_pay, the bound of its payload.
+struct Pass {
+    std::vector<ansx_batch_src> S;
+    std::vector<ansx_batch_blk> B;
+    std::vector<ansx_blk_out> O;
+    std::vector<u32> cont;
+    ansx_container_header Hs;
+    u64 cap_pay, wl;
+    u32 last_blocks;  // blocks of the last source so far: close() adds its share of the payload bound
+
+    void open(const ansx_container_header& H0)
+    {
+        S.clear(), B.clear(), O.clear(), cont.clear();
+        Hs = H0;
+        Hs.max_nsyms = 0, Hs.max_log2_frame = 0, Hs.max_present_m1 = 0;
+        cap_pay = wl = 0, last_blocks = 0;
+    }
+    void close(u64 bbound)
+    {
+        if (!S.empty()) cap_pay += std::min<u64>(S.back().payload_bytes, (u64)last_blocks * bbound);
+        last_blocks = 0;
+    }
+    // Blocks b0..b1 of container r (cs; blocks of bi ints, streams of at most bbound bytes) behind what the pass holds,
+    // their ints from `at` of the work list (a multiple of 4) on: a new source where the container changes.  close()
+    // behind the last.  -> their ints
+    u64 append(const BatchSrc& cs, u32 r, u32 b0, u32 b1, u64 at, u64 bi, u64 bbound)
+    {
+        if (S.empty() || cont.back() != r) {
+            close(bbound);
+            S.push_back({ cs.base, cs.lay.ckoff_off, cs.lay.ckstate_off, cs.lay.hint_off, cs.lay.payload_off,
+                cs.H.payload_bytes, cs.nblocks, 0 });
+            cont.push_back(r);
+            Hs.max_nsyms = std::max(Hs.max_nsyms, cs.H.max_nsyms);
+            Hs.max_log2_frame = std::max(Hs.max_log2_frame, cs.H.max_log2_frame);
+            Hs.max_present_m1 = std::max(Hs.max_present_m1, cs.H.max_present_m1);
+        }
+        for (u32 b = b0; b <= b1; b++) {
+            B.push_back({ (u32)S.size() - 1, b });
+            O.push_back({ at + (u64)(b - b0) * bi, (u32)std::min<u64>(bi, cs.H.n - (u64)b * bi), 0 });
+        }
+        last_blocks += b1 - b0 + 1;
+        const u64 ints = std::min<u64>(cs.H.n, ((u64)b1 + 1) * bi) - (u64)b0 * bi;
+        wl = at + rup(ints, 4);
+        return ints;
+    }
+    // Pass p of br_runs' runs, which start at runs[k], opened on H0 -> the first run behind them.  (B and O get their
+    // room at once: growing them block by block showed in the calls over thousands of containers.)
+    size_t take_runs(const ansx_container_header& H0, const std::vector<BatchSrc>& rs, const std::vector<BrRun>& runs,
+        size_t k, u32 p, u64 bi, u64 bbound)
+    {
+        open(H0);
+        size_t e = k, T = 0;
+        for (; e < runs.size() && runs[e].pass == p; e++) T += runs[e].b1 - runs[e].b0 + 1;
+        B.reserve(T), O.reserve(T);
+        for (; k < e; k++) append(rs[runs[k].r], runs[k].r, runs[k].b0, runs[k].b1, runs[k].wl, bi, bbound);
+        close(bbound);
+        return k;
+    }
+};
+
+// A pass of ansx_decode_batch_dev: whole containers ids[*ci..] of one geometry (src[i] at off[i] of the caller's
+// buffer), from block *b0 of the first, up to PB blocks; moves *ci / *b0 past them.  R, pstart[nr + 1]: one gather
+// piece per source and every piece's first chunk of ANSX_RANGE_CHUNK ints; -> the chunks.
+__attribute__((noinline)) static u64 batch_pass_plan(const std::vector<BatchSrc>& src, const std::vector<u64>& off, const std::vector<u32>& ids,
+    size_t* ci, u32* b0, u32 PB, u64 bbound, Pass* P, std::vector<ansx_range_piece>* R, std::vector<u32>* pstart)
+{
+    const ansx_container_header& H0 = src[ids[*ci]].H;
+    const u64 bi = H0.block_ints;
+    P->open(H0);  // (the table: every container's blocks back to back, from a multiple of 4 ints)
+    R->clear(), pstart->clear();
+    u64 npieces = 0;
+    u64 T = 0;  // (room for the pass's blocks at once, as take_runs finds it)
+    for (size_t j = *ci; j < ids.size() && T < PB; j++) T += src[ids[j]].nblocks;
+    P->B.reserve(std::min<u64>(T, PB)), P->O.reserve(std::min<u64>(T, PB));
+    while (*ci < ids.size() && P->B.size() < PB) {
+        const u32 i = ids[*ci];
+        const BatchSrc& cs = src[i];
+        const u32 take = (u32)std::min<u64>(cs.nblocks - *b0, PB - P->B.size());
+        const u64 at = P->wl, ints = P->append(cs, i, *b0, *b0 + take - 1, at, bi, bbound);
+        R->push_back({ at, off[i] + (u64)*b0 * bi, ints });
+        pstart->push_back((u32)npieces);  // (checked by the caller: npieces stays below 2^32)
+        npieces += (ints + ANSX_RANGE_CHUNK - 1) / ANSX_RANGE_CHUNK;
+        *b0 += take;
+        if (*b0 == cs.nblocks) (*ci)++, *b0 = 0;
+    }
+    P->close(bbound);
+    pstart->push_back((u32)npieces);
+    return npieces;
+}
+
+}  // namespace ansx_plan

@@ -12,11 +12,7 @@ struct ansx_range_lay {  // byte offsets of a container's sections (the index is
     u64 ckoff_off, ckstate_off, hint_off, payload_off;
 };
 
-struct ansx_range_piece {  // one range with count > 0: where its ints sit in the sub-list and in the output
-    u64 src, dst, count;
-};
-
-#define ANSX_RANGE_CHUNK 4096u  // ints per workgroup of k_range_gather
+// (ansx_range_piece, ANSX_RANGE_CHUNK: ansx_plan_types.h)
 
 // Byte length of touched block k's stream (source block b), 0 if its index entries are not those of a well-formed
 // container (index_entry_ok: the checks of k_validate_index): such a block sets the format flag and is not copied.
