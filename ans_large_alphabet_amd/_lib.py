@@ -32,7 +32,7 @@ EXPORTS = [
     "ansx_decode_batch_ranges_dev", "ansx_decode_sums_dev", "ansx_decode_batch_sums_dev", "ansx_encode_gaps_dev",
     "ansx_encode_batch_gaps_dev", "ansx_block_bases_dev", "ansx_encode_gaps_bases_dev", "ansx_decode_ranges_sums_dev",
     "ansx_decode_device_ranges_sums_dev", "ansx_next_geq_dev", "ansx_encode_batch_gaps_bases_dev",
-    "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev",
+    "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
 ]
 
 
@@ -52,6 +52,18 @@ class ContainerHeader(C.Structure):
 class EncodeStats(C.Structure):
     _fields_ = [("max_nsyms", C.c_uint32), ("max_log2_frame", C.c_uint32), ("near_threshold_decisions", C.c_uint32),
                 ("path", C.c_uint32), ("host_redecided", C.c_uint32)]
+
+
+# ansx_decode_stats: the form of the most recent decode (include/ansx.h)
+PARSERS = ("DONE", "GENERIC", "PAR", "FAST", "WIN")
+DECODERS = ("STAGED", "RING", "SMALL_RING", "PAIR", "TABLE", "GTAB")
+DECODE_INDEX_VALIDATED, DECODE_ON_REMEMBERED, DECODE_REPEATED = 1, 2, 4
+
+
+class DecodeStats(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in (
+        "parser", "p_variant", "decoder", "p_grid", "p_threads", "p_lds", "d_grid", "d_threads", "d_lds", "stream_cap",
+        "maxM", "max_ns", "max_ep", "max_block_bytes", "nblocks", "flags")]
 
 
 class KernelTime(C.Structure):
@@ -180,6 +192,8 @@ def lib():
     L.ansx_merge_containers_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.c_int, vp, sz, C.POINTER(sz), vp]
     L.ansx_last_encode_stats.restype = C.c_int
     L.ansx_last_encode_stats.argtypes = [vp, C.POINTER(EncodeStats)]
+    L.ansx_last_decode_stats.restype = C.c_int
+    L.ansx_last_decode_stats.argtypes = [vp, C.POINTER(DecodeStats)]
     L.ansx_last_gather_ranks.restype = C.c_int
     L.ansx_last_gather_ranks.argtypes = [vp]
     L.ansx_debug_set.restype = C.c_int

@@ -61,6 +61,22 @@ class Context:
         L.lib().ansx_last_encode_stats(self._h, C.byref(st))
         return {k: int(getattr(st, k)) for k, _ in L.EncodeStats._fields_}
 
+    def last_decode_stats(self):
+        """The form of the most recent decode as it ran (ansx_decode_stats in include/ansx.h): a dict of the struct's
+        fields as ints, "parser" and "decoder" as names ("PAR", "SMALL_RING", ...; _lib.PARSERS / _lib.DECODERS) and the
+        three flags as bools "index_validated", "on_remembered", "repeated"."""
+        st = L.DecodeStats()
+        rc = L.lib().ansx_last_decode_stats(self._h, C.byref(st))
+        if rc != L.OK:
+            raise L.AnsxError(rc, "ansx_last_decode_stats")
+        d = {k: int(getattr(st, k)) for k, _ in L.DecodeStats._fields_}
+        d["parser"] = L.PARSERS[d["parser"]]
+        d["decoder"] = L.DECODERS[d["decoder"]]
+        d["index_validated"] = bool(d["flags"] & L.DECODE_INDEX_VALIDATED)
+        d["on_remembered"] = bool(d["flags"] & L.DECODE_ON_REMEMBERED)
+        d["repeated"] = bool(d["flags"] & L.DECODE_REPEATED)
+        return d
+
     def debug_set(self, name, value=None):
         """Select one of the equivalent internal code paths (tests / experiments); value None or "" = default."""
         st = L.lib().ansx_debug_set(self._h, name.encode(), None if value is None else str(value).encode())

@@ -37,6 +37,7 @@
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
+#include "ansx_decode_form.h"  // the form of a decode call: parser, decoder, launch shapes
 
 using namespace ansx_plan;
 
@@ -156,6 +157,7 @@ struct ansx_ctx {
         std::set<u64> wide_hint, int_sparse_hint;
     } bat;
     ansx_encode_stats last = {};
+    ansx_decode_stats last_dec = {};  // the form of the most recent decode attempt that ran to its end (ansx_last_decode_stats)
     // Block-range pipeline of the fast model path (model_fast): two side streams and the events of its fork and join,
     // created by the first call that needs them (pipeline_prepare) and destroyed with the context, never per call.
     hipStream_t pipe_stream[2] = { nullptr, nullptr };
@@ -1599,162 +1601,58 @@ int encode_dev(ansx_ctx* c, const Plan& P0, const u32* d_in, u8* d_out, size_t c
 }
 
 // --------------------------------------------------------------------------------- decode
-// Which subtree form k_parse_prelude_par runs, from header fields only: a depth-3 subtree has at most max_ns >> 3
-// items; its value array (two sentinels more) and ANSX_PAR_STK stack rows must fit the 48 rows behind the staged words.
-// 1: u16 elements (every value fits: frame + alphabet + 3 <= 65535), 2: u32 elements, 0: the windowed form.
-static int ansx_par_form(u32 max_ns, u32 maxM)
+// The form of a decode call -- DecodeBounds, DecodeForm, choose_decode_form -- is host-only arithmetic in
+// ansx_decode_form.h (swept on the CPU by tests/tools/decode_form_check.cpp).  Here: what it reads of a plan's geometry
+// and of the context's overrides.
+using ansx_form::DecodeBounds;
+using ansx_form::DecodeForm;
+using ansx_form::LaunchShape;
+using ansx_form::PARSE_DONE;
+using ansx_form::PARSE_GENERIC;
+using ansx_form::PARSE_PAR;
+using ansx_form::PARSE_FAST;
+using ansx_form::PARSE_WIN;
+using ansx_form::DEC_STAGED;
+using ansx_form::DEC_RING;
+using ansx_form::DEC_SMALL_RING;
+using ansx_form::DEC_PAIR;
+using ansx_form::DEC_TABLE;
+using ansx_form::DEC_GTAB;
+
+ansx_form::FormGeo form_geo(const ansx_geo& g)
 {
-    const size_t room = (size_t)(48 - ANSX_PAR_STK) * 64 * 4;
-    const size_t elems = (size_t)(max_ns >> 3) + 2;
-    if ((u64)maxM + max_ns + 3 <= 65535u && elems * 64 * 2 <= room) return 1;
-    if (elems * 64 * 4 <= room) return 2;
-    return 0;
+    return { g.n, g.block_ints, g.nblocks, g.ckpt, g.kind, g.pa, geo_nseg(g.block_ints, g.ckpt),
+        g.kind == ANSX_RFOLD ? fold_T(g.f) * 4u : 0u, block_bound((int)g.kind, g.f, g.block_ints, false) };
 }
 
-// What the form of a decode depends on besides the geometry and the debug overrides: bounds from the container's header
-// (for a single reference stream: from the peek at its first bytes).
-struct DecodeBounds {
-    u32 maxM, max_ns;     // the largest frame; the bound on a block's symbol indices
-    u32 max_ep;           // the bound on the symbols PRESENT in a block (<= max_ns): the rank / select decoder keeps one
-                          // 8-byte entry per present symbol, so this -- not max_ns -- sizes its LDS
-    bool hinted;          // the container carries parse hints (a single stream has none)
-    u64 payload_bytes;    // bytes of all block streams (per int of the list: how lean the streams are)
-    u32 max_block_bytes;  // the largest block stream -- only the index knows it (k_validate_index) -- or 0: not looked up
-};
+ansx_form::FormKeys form_keys(const DebugOpts& d)
+{
+    ansx_form::FormKeys k;
+    k.parse_generic = d.parse_generic, k.parse_win = d.parse_win, k.parse_fast = d.parse_fast;
+    k.parse_stage_words = d.parse_stage_words;
+    k.setup_old = d.setup_old;
+    k.decode_table = d.decode_table, k.no_stream_lds = d.no_stream_lds;
+    k.decode_mode = d.decode_mode, k.decode_pair = d.decode_pair, k.decode_small_ring = d.decode_small_ring;
+    k.pair_lds_limit = d.pair_lds_limit;
+    return k;
+}
 
-enum { PARSE_DONE, PARSE_GENERIC, PARSE_PAR, PARSE_FAST, PARSE_WIN };  // PARSE_DONE: k_int_sparse_parse has filled the tables
-// the k_decode_rank family (in the order of its RING parameter, then the pair kernel) and the two table forms of k_decode
-enum { DEC_STAGED, DEC_RING, DEC_SMALL_RING, DEC_PAIR, DEC_TABLE, DEC_GTAB };  // DEC_GTAB: needs the HBM slot table (dec_s2s)
-struct LaunchShape {
-    u32 grid, threads;
-    size_t lds;
-};
-struct DecodeForm {
-    bool needs_index;  // the decoder hangs on the largest block stream and the bounds do not have it: only the parser is
-                       // filled in, ask again with max_block_bytes measured
-    int parser;        // K7 ...
-    u32 p_variant;     // ... PARSE_PAR: the subtree form (ansx_par_form), PARSE_WIN: staged words per lane, PARSE_FAST: stage_words
-    int decoder;       // K8
-    LaunchShape p, d;
-    u32 stream_cap;  // DEC_STAGED and the table forms: bytes of LDS a block's stream is staged in, 0 = read from HBM
-};
-
-// The one place that decides which parser and which decoder a decode call runs, and in what launch shape.  Pure: no HIP
-// call, nothing of the context but its overrides and the chip's CU count.
 DecodeForm choose_decode_form(const ansx_geo& g, const DecodeBounds& B, const DebugOpts& dbg, u32 num_cus)
 {
-    DecodeForm F = {};
-    const u32 maxM = B.maxM, max_ns = B.max_ns;
-    // K7.  Containers carry parse hints (bit offsets of the top subtrees of every block's interpolative code):
-    // eight lanes per block, k_parse_prelude_par.  Without hints (single-stream mode) or on request one lane
-    // per block: the windowed parser (any alphabet / frame size; ANSX_PARSE_WIN), the older E-array fast loop
-    // (ANSX_PARSE_FAST: 16-bit values, up to ~880 symbols) or the generic kernel (ANSX_PARSE_GENERIC) --
-    // all four are cross-checked in the tests.
-    const size_t pf_lds = std::max<size_t>(20480, rup(((size_t)max_ns + 2) * 128, 16)) + (size_t)ANSX_PF_SW * 64 * 4 + 21 * 64 * 4;
-    F.p = { (g.nblocks + 63) / 64, 64, 0 };
-    if (g.kind == ANSX_INT && !g.pa) {
-        F.parser = PARSE_DONE;
-    } else if (dbg.parse_generic) {
-        F.parser = PARSE_GENERIC;
-    } else if (B.hinted && !dbg.parse_win && !dbg.parse_fast) {
-        // Subtree form: value arrays (u16 / u32 elements) where a depth-3 subtree's array fits the slice the windowed
-        // form needs anyway, from header fields only; otherwise, or with ANSX_DECODE_SETUP=old, the windowed form.
-        F.parser = PARSE_PAR;
-        F.p_variant = dbg.setup_old ? 0 : ansx_par_form(max_ns, maxM);
-        // Waves per workgroup (each wave works alone on its own LDS slice): measured on MI355X at 16384 blocks,
-        // windowed form: 530-symbol tables 1/2/3/4 waves -> 0.161/0.162/0.109/0.122 ms, 2300-symbol tables
-        // 0.275/0.273/0.286/0.252; value-array form (event-timed, so ~0.005 above the kernel's own time): 526-symbol
-        // tables 0.062/0.062/0.068/0.056, 257-symbol tables 0.045/0.042/0.048/0.039.
-        const u32 par_waves = (g.nblocks + 7) / 8;
-        const u32 pw_max = (F.p_variant != 0 || max_ns > 1024) ? 4u : 3u;
-        const u32 pw = std::min<u32>(pw_max, std::max<u32>(1u, (par_waves + num_cus - 1) / num_cus));
-        F.p = { (par_waves + pw - 1) / pw, 64 * pw, (size_t)pw * ANSX_PAR_SLICE_WORDS * 4 };
-    } else if (dbg.parse_fast && (u64)maxM + max_ns + 3 <= 65535u && pf_lds <= 150 * 1024) {
-        F.parser = PARSE_FAST;
-        F.p_variant = ANSX_PF_SW;
-        if (dbg.parse_stage_words >= 2 && dbg.parse_stage_words <= ANSX_PF_SW)  // tests: force the fast loop's in-kernel fallback
-            F.p_variant = dbg.parse_stage_words & ~1u;
-        F.p.lds = pf_lds;
-    } else {
-        F.parser = PARSE_WIN;
-        F.p_variant = max_ns <= 1024 ? 128 : 256;  // (preludes of a few hundred bytes: 128 staged words per lane)
-        F.p.lds = (size_t)(F.p_variant + 72) * 64 * 4;
-    }
-    // K8
-    const u32 nseg = geo_nseg(g.block_ints, g.ckpt);
-    F.d.grid = g.nblocks;
-    F.d.threads = std::min<u32>(256u, (u32)rup((size_t)nseg * 4, 64));
-    const size_t LDS_LIMIT = 150 * 1024;
-    // normal path: rank/select tables (frames up to 2^16), staged stream while >= 3 WGs/CU still fit
-    const size_t rs_tables = rup((size_t)(maxM >= 32 ? maxM / 32 : 1) * 8, 16) + 2 * rup((size_t)B.max_ep * 4, 16) + ANSX_DEC_SCRATCH;
-    const bool rank_form = maxM <= 65536u && rs_tables <= LDS_LIMIT && !dbg.decode_table;
-    // per-quad stream rings when every segment of a full block has the same length; the (at
-    // most one) partial block of the container then reads its stream straight from HBM
-    // (measured on MI355X, 256 Mi ints: rings 0.73 vs 0.76 ms at 16 Ki / 1024, 0.73 vs 1.85 ms at
-    // 64 Ki / 1024 where the stream no longer fits; staged 0.60 vs 0.69 ms at 16 Ki / 512 -- the
-    // ring bookkeeping costs ~6 VALU per step, so it only pays when it frees a lot of LDS)
-    const size_t ring_lds = (size_t)(F.d.threads / 4) * ANSX_RING_STRIDE + 16;  // + alignment slack
-    const bool ring_ok = g.ckpt != 0 && g.block_ints % g.ckpt == 0 && g.ckpt % 4 == 0 && rs_tables + ring_lds <= 60 * 1024;
-    const int force = dbg.decode_mode;  // tests: 1 "ring" | 2 "staged"
-    // The ring decoder needs nothing from the index, so a container it could decode is never held up for one (no
-    // validation kernel, no read-back): whether rings pay there, and the staging of the staged form if they do not, go
-    // by the codec's worst-case block stream.  Every other form sizes its LDS from the largest block stream.
-    const bool index_free = rank_form && ring_ok && force != 2 && !g.pa;
-    if (!B.max_block_bytes && !index_free) {
-        F.needs_index = true;
-        return F;
-    }
-    const size_t block_bytes = B.max_block_bytes ? B.max_block_bytes
-                                                 : std::min<size_t>(0x7FFFFFFFu, block_bound((int)g.kind, g.f, g.block_ints, false));
-    const size_t want_stream = rup(block_bytes + 32, 16);
-    size_t tables = rs_tables;  // what the form keeps in LDS besides a staged stream
-    if (rank_form) {
-        // large tables (alphabets of thousands of symbols: one wave per block, a handful of waves per CU either
-        // way): rings, 1.33 vs 2.08 ms on 2300-symbol alphabets -- the staging pass is pure latency there
-        const bool staged_fits = rs_tables + want_stream <= 52 * 1024;
-        const bool ring_pays = !staged_fits || rs_tables >= 12 * 1024 || 10 * (rs_tables + want_stream) > 16 * (rs_tables + ring_lds);
-        if (ring_ok && (force ? force == 1 : ring_pays)) {
-            // two blocks per workgroup, decoded in one instruction stream (k_decode_rank2): as long as four such workgroups
-            // still fit a CU's LDS; the container's last one or two blocks take the single-block code inside that kernel
-            const size_t lds2 = rup((size_t)(maxM >= 32 ? maxM / 32 : 1) * 16, 16) + 4 * rup((size_t)B.max_ep * 4, 16) + ANSX_DEC_SCRATCH + 2 * ring_lds;
-            const int pair = dbg.decode_pair;  // tests / experiments: 1 never, 2 always (LDS permitting)
-            // Streams of a few bytes per step (the container's bytes per int, header fields only): the 256-byte speculative
-            // rings -- sixteen instead of ten blocks of the headline workload per CU; an interval that outran its window is
-            // decoded again (dec_segments_ring_small), so a wrong guess here costs time, never correctness.
-            const int small = dbg.decode_small_ring;  // tests: 1 never, 2 always
-            const bool lean = g.n != 0 && (double)B.payload_bytes / (double)g.n <= 2.0 && g.ckpt % 16 == 0;
-            if (pair != 1 && g.nblocks >= 2 && (pair == 2 ? lds2 <= 150 * 1024 : lds2 <= dbg.pair_lds_limit)) {
-                F.decoder = DEC_PAIR;
-                F.d.grid = (g.nblocks + 1) / 2;
-                F.d.lds = lds2;
-            } else if (small != 1 && (small == 2 || lean)) {
-                F.decoder = DEC_SMALL_RING;
-                F.d.lds = rs_tables + (size_t)(F.d.threads / 4) * ANSX_SRING_STRIDE + 16;
-            } else {
-                F.decoder = DEC_RING;
-                F.d.lds = rs_tables + ring_lds;
-            }
-            return F;
-        }
-        F.decoder = DEC_STAGED;
-        if (!staged_fits || dbg.no_stream_lds) {
-            F.d.lds = rs_tables;
-            return F;
-        }
-    } else {
-        // frames above 2^16 (or forced): slot -> symbol table form, in LDS if it fits, else in HBM
-        const size_t mfb = g.kind == ANSX_RFOLD ? (size_t)fold_T(g.f) * 4 : 0;
-        tables = rup(((size_t)max_ns + 2) * 4, 16) + rup((size_t)maxM * 2, 16) + mfb;
-        F.decoder = tables <= LDS_LIMIT ? DEC_TABLE : DEC_GTAB;
-        if (F.decoder == DEC_GTAB) tables = mfb;
-        if (tables + want_stream > 52 * 1024) {
-            F.d.lds = std::max<size_t>(tables, 16);
-            return F;
-        }
-    }
-    F.d.lds = tables + want_stream;
-    F.stream_cap = (u32)want_stream;
-    return F;
+    return ansx_form::choose_decode_form(form_geo(g), B, form_keys(dbg), num_cus);
+}
+
+// What ansx_last_decode_stats reports of an attempt: its form, the bounds it was chosen from, how it came about
+void note_decode_form(ansx_ctx* c, const ansx_geo& g, const DecodeBounds& B, const DecodeForm& F, u32 flags)
+{
+    ansx_decode_stats& d = c->last_dec;
+    d.parser = (u32)F.parser, d.p_variant = F.p_variant, d.decoder = (u32)F.decoder;
+    d.p_grid = F.p.grid, d.p_threads = F.p.threads, d.p_lds = (u32)F.p.lds;
+    d.d_grid = F.d.grid, d.d_threads = F.d.threads, d.d_lds = (u32)F.d.lds;
+    d.stream_cap = F.stream_cap;
+    d.maxM = B.maxM, d.max_ns = B.max_ns, d.max_ep = B.max_ep, d.max_block_bytes = B.max_block_bytes;
+    d.nblocks = g.nblocks;
+    d.flags = flags;
 }
 
 // What the phases of a decode call share: where the pieces of its source are, its plan (the container's own, the
@@ -2034,6 +1932,7 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
 {
     const HeaderCache::Key key = { (u64)Pin.g.kind, (u64)Pin.g.f, (u64)Pin.g.n, (u64)in_bytes };
     const ansx_container_header* spec = !Pin.plain && O.speculate ? c->hdrs.find(key) : nullptr;
+    u32 how = 0;  // ANSX_DECODE_* flags of the attempt (ansx_last_decode_stats)
     for (;; c->hdrs.forget(key), spec = nullptr) {  // (at most twice: only an attempt on `spec` is repeated)
         int rc;
         if ((rc = ensure(c, c->misc, 64 + 8 * ((size_t)Pin.g.nblocks + 1)))) return rc;
@@ -2053,7 +1952,9 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
             if (c->pin->flags[ANSX_G_ERR]) return flags_to_status(c->pin->flags[ANSX_G_ERR]);
             S.B.max_block_bytes = c->pin->flags[ANSX_G_PAD];
             F = choose_decode_form(g, S.B, c->dbg, c->num_cus);
+            how |= ANSX_DECODE_INDEX_VALIDATED;
         }
+        note_decode_form(c, g, S.B, F, how | (spec ? ANSX_DECODE_ON_REMEMBERED : 0u));
         if ((rc = decode_premap(c, S, s))) return rc;
         if ((rc = g.kind == ANSX_RFOLD ? launch_decode<true>(c, S, F, d_out, s) : launch_decode<false>(c, S, F, d_out, s))) return rc;
         if (g.kind == ANSX_INT && !g.pa)
@@ -2065,7 +1966,10 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
         if (O.epilogue && (rc = (*O.epilogue)(gflags))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->pin->flags, c->misc.p, 64, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        if (spec && (c->pin->flags[ANSX_G_ERR] & (1u << ANSX_G_HDR_BIT))) continue;  // another header: the slow way
+        if (spec && (c->pin->flags[ANSX_G_ERR] & (1u << ANSX_G_HDR_BIT))) {  // another header: the slow way
+            how = ANSX_DECODE_REPEATED;
+            continue;
+        }
         const int st = flags_to_status(c->pin->flags[ANSX_G_ERR]);
         if (!Pin.plain && !spec && st == ANSX_OK && O.remember) c->hdrs.remember(key, c->pin->hdr);
         return st;
@@ -3312,7 +3216,9 @@ int ansx_init(int device, ansx_ctx** out)
         "ANSX_DECODE_TABLE", "ANSX_NO_STREAM_LDS", "ANSX_DECODE_MODE", "ANSX_PARSE_STAGE_WORDS", "ANSX_MODEL_FUSED", "ANSX_MODEL_SYNC", "ANSX_NS_HINT", "ANSX_T_HINT", "ANSX_NO_FAST_MODEL", "ANSX_FAST_GUARD", "ANSX_CAND_CHAINS", "ANSX_NEAR_BAND", "ANSX_TEST_NEAR_FLIP", "ANSX_WIDE_RESTART", "ANSX_TEST_WIDE_AT",
         "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP", "ANSX_MODEL_CHAIN" };
     for (const char* nm : names)
-        if (const char* v = getenv(nm)) (void)ansx_debug_set(c, nm, v);
+        if (const char* v = getenv(nm))
+            if (ansx_debug_set(c, nm, v) != ANSX_OK)  // (a value the key does not take selects nothing: said, not passed over)
+                fprintf(stderr, "ansx_init: %s=\"%s\" is not a value of that key, ignored\n", nm, v);
     *out = c;
     return ANSX_OK;
 }
@@ -3364,6 +3270,20 @@ int ansx_last_encode_stats(const ansx_ctx* c, ansx_encode_stats* out)
     return ANSX_OK;
 }
 
+int ansx_last_decode_stats(const ansx_ctx* c, ansx_decode_stats* out)
+{
+    if (!c || !out) return ANSX_ERR_ARG;
+    *out = c->last_dec;
+    return ANSX_OK;
+}
+
+// a key that takes one of two words: 0 for ""/"0"/NULL, 1 / 2 for the words, -1 for anything else
+static int debug_word(const char* value, const char* one, const char* two)
+{
+    if (!value || !value[0] || !strcmp(value, "0")) return 0;
+    return !strcmp(value, one) ? 1 : !strcmp(value, two) ? 2 : -1;
+}
+
 int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
 {
     if (!c || !name) return ANSX_ERR_ARG;
@@ -3377,8 +3297,11 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
     else if (!strcmp(name, "ANSX_NO_STREAM_LDS")) c->dbg.no_stream_lds = on;
     else if (!strcmp(name, "ANSX_MODEL_FUSED")) c->dbg.model_fused = on;
     else if (!strcmp(name, "ANSX_MODEL_SYNC")) c->dbg.model_sync = on;
-    else if (!strcmp(name, "ANSX_DECODE_MODE"))
-        c->dbg.decode_mode = !value ? 0 : !strcmp(value, "ring") ? 1 : !strcmp(value, "staged") ? 2 : 0;
+    else if (!strcmp(name, "ANSX_DECODE_MODE")) {
+        const int w = debug_word(value, "ring", "staged");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.decode_mode = w;
+    }
     else if (!strcmp(name, "ANSX_PARSE_STAGE_WORDS")) c->dbg.parse_stage_words = value ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_NS_HINT")) c->dbg.ns_hint = value ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_T_HINT")) c->dbg.t_hint = value ? (u32)strtoul(value, nullptr, 10) : 0u;
@@ -3393,10 +3316,16 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
     else if (!strcmp(name, "ANSX_TEST_SP_BITS")) c->dbg.test_sp_bits = value ? (u32)atoi(value) : 0u;
     else if (!strcmp(name, "ANSX_PC_B_PAIRS")) c->dbg.pc_b_pairs = (value && value[0] == '1') ? 1u : 2u;
     else if (!strcmp(name, "ANSX_ENCODE_MODE2")) c->dbg.encode_mode2 = on;
-    else if (!strcmp(name, "ANSX_DECODE_SMALL_RING"))
-        c->dbg.decode_small_ring = !value ? 0 : !strcmp(value, "never") ? 1 : !strcmp(value, "always") ? 2 : 0;
-    else if (!strcmp(name, "ANSX_DECODE_PAIR"))
-        c->dbg.decode_pair = !value ? 0 : !strcmp(value, "never") ? 1 : !strcmp(value, "always") ? 2 : 0;
+    else if (!strcmp(name, "ANSX_DECODE_SMALL_RING")) {
+        const int w = debug_word(value, "never", "always");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.decode_small_ring = w;
+    }
+    else if (!strcmp(name, "ANSX_DECODE_PAIR")) {
+        const int w = debug_word(value, "never", "always");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.decode_pair = w;
+    }
     else if (!strcmp(name, "ANSX_DECODE_SETUP")) {
         if (!value || !value[0] || !strcmp(value, "0")) c->dbg.setup_old = false;
         else if (!strcmp(value, "old")) c->dbg.setup_old = true;

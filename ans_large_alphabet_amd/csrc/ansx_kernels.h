@@ -2963,7 +2963,7 @@ __global__ __launch_bounds__(64) void k_parse_prelude(const u8* __restrict__ con
 //    <= 31 bits through one 32-bit window (two words + v_alignbit), no refill logic, no 64-bit
 //    shifts, no loads behind the cum[] stores.
 // A lane whose prelude outgrows the staged words falls back to parse_items_generic afterwards.
-#define ANSX_PF_SW 128u
+// (ANSX_PF_SW: ansx_plan_types.h)
 template <bool RFOLD>
 __global__ __launch_bounds__(64) void k_parse_prelude_fast(const u8* __restrict__ cont, ansx_geo g, u32 NSP,
     const u64* __restrict__ block_off, u64 payload_off, u32 max_ns, u32 maxM,
@@ -3309,9 +3309,8 @@ __global__ __launch_bounds__(64) void k_parse_prelude_win(const u8* __restrict__
 // LDS slice (FORM 1 / 2) and with parse_subtree_win otherwise (FORM 0).  Hints are untrusted input like the
 // payload: offsets are bounds-checked, and a wrong one yields a table that fails the decoder's
 // consistency checks or decodes to garbage, never an out-of-range access.
-#define ANSX_PAR_SW 32u            // staged words per lane
-#define ANSX_PAR_STK 11u           // stack rows of the value-array form: depth <= 10 (subtrees of <= 1023 items) + dump
-#define ANSX_PAR_SLICE_WORDS ((ANSX_PAR_SW + 48u) * 64u)  // a wave's LDS slice: stage + the windowed form's 3 x 16 stack rows
+// (ANSX_PAR_SW staged words per lane, ANSX_PAR_STK stack rows of the value-array form, ANSX_PAR_SLICE_WORDS a wave's
+// LDS slice: ansx_plan_types.h)
 // FORM: 0 = windowed subtrees (any alphabet), 1 / 2 = value-array subtrees with u16 / u32 elements (the host checks
 // that the array fits the slice: ansx_par_form)
 template <bool RFOLD, u32 SW, int FORM>
@@ -3429,14 +3428,8 @@ __global__ __launch_bounds__(256) void k_parse_prelude_par(const u8* __restrict_
 // words + v_alignbyte) or straight from global memory (one unaligned 8-byte load)
 // per-quad stream ring of the block decoder: ANSX_RING_CHK steps per refill check, 32 bytes per lane
 // and step of check interval per refill (>= the 28 bytes a quad can consume per step)
-#ifndef ANSX_RING_CHK
-#define ANSX_RING_CHK 4
-#endif
-#define ANSX_DEC_SCRATCH 96u  // k_decode_rank: scan scratch + error flag between the tables and the stream area
-#define ANSX_RING_BYTES (128 * ANSX_RING_CHK)
-#define ANSX_RING_STRIDE (ANSX_RING_BYTES + 16)  // + 8 mirror bytes (ring bytes 0..7 once more) and padding to 16
-#define ANSX_SRING_BYTES 256                       // the speculative small ring (round 4), see dec_segments_ring_small
-#define ANSX_SRING_STRIDE (ANSX_SRING_BYTES + 16)
+// (ANSX_RING_CHK, ANSX_DEC_SCRATCH and the ring sizes ANSX_RING_* / ANSX_SRING_*: ansx_plan_types.h, shared with the
+// host's choice of the decode form)
 // end8 = end - 8: the decoder keeps its cursor biased by 8, so this is what its prefix sum yields
 template <int MODE>
 __device__ __forceinline__ u64 dec_fetch8(const u8* __restrict__ stream, const u32* lds_stream, int end8)

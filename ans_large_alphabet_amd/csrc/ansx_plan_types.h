@@ -42,6 +42,23 @@ struct ansx_piece {  // ints [src, src + count) of the pass's work list go to [d
 
 #define ANSX_PIECE_CHUNK 4096u  // ints per workgroup of k_piece_gather (k_range_gather's chunk)
 
+// LDS geometry of the decode kernels, shared with the host's choice of the decode form (ansx_decode_form.h), which
+// sizes the dynamic LDS the kernels carve.
+#define ANSX_PF_SW 128u            // k_parse_prelude_fast: staged words per lane
+#define ANSX_PAR_SW 32u            // k_parse_prelude_par: staged words per lane
+#define ANSX_PAR_STK 11u           // stack rows of its value-array form: depth <= 10 (subtrees of <= 1023 items) + dump
+#define ANSX_PAR_SLICE_WORDS ((ANSX_PAR_SW + 48u) * 64u)  // a wave's LDS slice: stage + the windowed form's 3 x 16 stack rows
+// per-quad stream ring of the block decoder: ANSX_RING_CHK steps per refill check, 32 bytes per lane and step of check
+// interval per refill (>= the 28 bytes a quad can consume per step)
+#ifndef ANSX_RING_CHK
+#define ANSX_RING_CHK 4
+#endif
+#define ANSX_DEC_SCRATCH 96u  // k_decode_rank: scan scratch + error flag between the tables and the stream area
+#define ANSX_RING_BYTES (128 * ANSX_RING_CHK)
+#define ANSX_RING_STRIDE (ANSX_RING_BYTES + 16)  // + 8 mirror bytes (ring bytes 0..7 once more) and padding to 16
+#define ANSX_SRING_BYTES 256                       // the speculative small ring, see dec_segments_ring_small
+#define ANSX_SRING_STRIDE (ANSX_SRING_BYTES + 16)
+
 struct ansx_brs_src {  // a source of a pass, beside its ansx_batch_src: the caller's bases of that container
     u64 bases;         // device address of its nblocks + 1 entries (4-byte aligned)
     u32 nblocks;

@@ -614,6 +614,55 @@ typedef struct {
 } ansx_encode_stats;
 int ansx_last_encode_stats(const ansx_ctx* ctx, ansx_encode_stats* out);
 
+/* The form of the context's most recent decode, as it ran: which prelude parser and which block decoder, in what
+ * launch shape.  Every read call ends in one decode of a container or of a sub-container built for the call (the range
+ * calls, the batch calls pass by pass, the sums / ids variants, next_geq); the fields describe that decode, for the
+ * attempt whose result was returned, and the last pass of a call wins.  A call that fails before a form is chosen
+ * leaves the previous values.  For tests and logs: no decode path looks at it.
+ *   parser            ANSX_PARSER_DONE     plain ANSint: k_int_sparse_parse has filled the tables, no parser launch
+ *                     ANSX_PARSER_GENERIC  the generic kernel, one lane per block
+ *                     ANSX_PARSER_PAR      eight lanes per block on the container's parse hints (the default);
+ *                                          p_variant 0 windowed subtrees, 1 u16 value arrays, 2 u32 value arrays
+ *                     ANSX_PARSER_FAST     one lane per block, the E-array fast loop; p_variant = staged words
+ *                     ANSX_PARSER_WIN      one lane per block, windowed; p_variant = staged words (128 | 256)
+ *   decoder           ANSX_DECODER_STAGED      rank / select tables, one block per workgroup; stream_cap != 0: the
+ *                                              block's stream staged in LDS, 0: read from HBM
+ *                     ANSX_DECODER_RING        the same with per-quad 512-byte stream rings
+ *                     ANSX_DECODER_SMALL_RING  the same with per-quad 256-byte speculative rings
+ *                     ANSX_DECODER_PAIR        two blocks per workgroup, 512-byte rings
+ *                     ANSX_DECODER_TABLE       slot -> symbol tables in LDS (stream_cap as for STAGED)
+ *                     ANSX_DECODER_GTAB        slot -> symbol tables in HBM (frames above 2^16 that LDS cannot hold)
+ *   p_grid .. d_lds   workgroups, threads per workgroup and bytes of dynamic LDS of the parser's and of the decoder's
+ *                     launch (p_lds 0 and the parser's shape unused under ANSX_PARSER_DONE)
+ *   stream_cap        bytes of LDS a block's stream is staged in (STAGED and the table forms), else 0
+ *   maxM, max_ns, max_ep, max_block_bytes
+ *                     the bounds the form was chosen from: largest frame, bound on a block's symbol indices, bound on
+ *                     the symbols present in a block, largest block stream (0: never looked up -- the ring forms do
+ *                     not need it)
+ *   nblocks           blocks of the container that was decoded (a range call: the touched blocks; a batch call: the
+ *                     blocks of its last pass)
+ *   flags             ANSX_DECODE_INDEX_VALIDATED  k_validate_index ran and its result was read back before the form
+ *                                                  was chosen
+ *                     ANSX_DECODE_ON_REMEMBERED    the attempt ran on the header remembered for the container's shape
+ *                     ANSX_DECODE_REPEATED         an attempt on a remembered header was given up and the call repeated
+ *                                                  on the container's own */
+typedef enum { ANSX_PARSER_DONE = 0, ANSX_PARSER_GENERIC = 1, ANSX_PARSER_PAR = 2, ANSX_PARSER_FAST = 3, ANSX_PARSER_WIN = 4 } ansx_parser;
+typedef enum { ANSX_DECODER_STAGED = 0, ANSX_DECODER_RING = 1, ANSX_DECODER_SMALL_RING = 2, ANSX_DECODER_PAIR = 3,
+    ANSX_DECODER_TABLE = 4, ANSX_DECODER_GTAB = 5 } ansx_decoder;
+#define ANSX_DECODE_INDEX_VALIDATED 1u
+#define ANSX_DECODE_ON_REMEMBERED 2u
+#define ANSX_DECODE_REPEATED 4u
+typedef struct {
+    uint32_t parser, p_variant, decoder;
+    uint32_t p_grid, p_threads, p_lds;
+    uint32_t d_grid, d_threads, d_lds;
+    uint32_t stream_cap;
+    uint32_t maxM, max_ns, max_ep, max_block_bytes;
+    uint32_t nblocks;
+    uint32_t flags;
+} ansx_decode_stats;
+int ansx_last_decode_stats(const ansx_ctx* ctx, ansx_decode_stats* out);
+
 /* Synthetic inputs of the reference's benchmark harness (src/generate_inputs.cpp:94-122, include/
  * zipf_dist.hpp:49-59) as counter-based generators: element i is a pure function of (seed, first_index + i),
  * so a list can be produced in pieces, on any number of GPUs, or on the host, with identical values.
@@ -630,7 +679,8 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
 
 /* Test / experiment hook: select one of the equivalent internal code paths (all must produce identical
  * bytes).  Names are those of the environment variables read once by ansx_init: ANSX_DECODE_MODE
- * ("ring" | "staged" | ""), ANSX_DECODE_TABLE, ANSX_NO_STREAM_LDS, ANSX_PARSE_GENERIC, ANSX_PARSE_WIN, ANSX_PARSE_FAST,
+ * ("ring" | "staged"; ""/"0"/NULL: the default; anything else: ANSX_ERR_ARG), ANSX_DECODE_TABLE,
+ * ANSX_NO_STREAM_LDS, ANSX_PARSE_GENERIC, ANSX_PARSE_WIN, ANSX_PARSE_FAST,
  * ANSX_PARSE_STAGE_WORDS (number), ANSX_ENCODE_GTAB16, ANSX_TEST_TABLE16_FIXUP, ANSX_MODEL_FUSED, ANSX_MODEL_SYNC,
  * ANSX_NS_HINT (number: alphabet-size hint for every call instead of the per-geometry one the context
  * learns; too small a value only costs a repeat on the general path), ANSX_T_HINT (number: candidate frame sizes per
@@ -653,12 +703,14 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
  * tests/tools/bench_model_chain.py);
  * through this call only (round 4): ANSX_NO_PC / ANSX_FORCE_PC / ANSX_NO_PC_AUTO / ANSX_PC_B_PAIRS (the producer /
  * consumer encoder never / whatever the list length / only on request; pairs per workgroup of its two-round shape),
- * ANSX_ENCODE_MODE2, ANSX_DECODE_PAIR, ANSX_DECODE_SMALL_RING (1 never | 2 always), ANSX_FORGET_HINTS, ANSX_NO_BIG_GEO,
+ * ANSX_ENCODE_MODE2, ANSX_DECODE_PAIR, ANSX_DECODE_SMALL_RING ("never" | "always"; ""/"0"/NULL: the default; anything
+ * else: ANSX_ERR_ARG, as for ANSX_DECODE_MODE), ANSX_FORGET_HINTS, ANSX_NO_BIG_GEO,
  * ANSX_FIN_ONE_WAVE, ANSX_TEST_SP_BITS (number: words of the rank-space ANSint prelude writer's bit buffer on its first
  * attempt), ANSX_RANGE_SUMS_WG_MAX (number: the largest block_ints whose touched blocks the sums variants of the range
  * calls scan in one kernel, a workgroup per block; larger blocks take the three-phase scan; ""/"0"/NULL: 65536 -- for the
  * paired timing of tests/tools/bench_range_sums.py, the results do not depend on it)  (flags: "1" on, "0"/""/NULL off).
- * Unknown name: ANSX_ERR_ARG. */
+ * Unknown name: ANSX_ERR_ARG.  ansx_init, which has no way to return such an error, leaves a key whose environment value
+ * is refused at its default and says so in one line on stderr. */
 int ansx_debug_set(ansx_ctx* ctx, const char* name, const char* value);
 
 /* Bytes of device workspace currently held by the context. */

@@ -831,16 +831,29 @@ def test_decoder_stream_modes(A, ctx, kind, f):
     for block, ckpt in ((16384, 1024), (16384, 256), (8192, 2048)):
         codec = codec_for(A, ctx, kind, f, block_ints=block, ckpt_interval=ckpt)
         cont = codec.encode(data)
-        for env in ({}, {"ANSX_DECODE_MODE": "ring"}, {"ANSX_DECODE_MODE": "staged"},
-                    {"ANSX_DECODE_MODE": "staged", "ANSX_NO_STREAM_LDS": "1"}, {"ANSX_DECODE_TABLE": "1"},
-                    # ring decoder: one block per workgroup (k_decode_rank) / two blocks in one instruction stream (k_decode_rank2)
-                    {"ANSX_DECODE_MODE": "ring", "ANSX_DECODE_PAIR": "never"}, {"ANSX_DECODE_MODE": "ring", "ANSX_DECODE_PAIR": "always"},
-                    # 512-byte worst-case rings / 256-byte speculative rings (chosen by the container's bytes per int otherwise)
-                    {"ANSX_DECODE_MODE": "ring", "ANSX_DECODE_SMALL_RING": "never"}, {"ANSX_DECODE_MODE": "ring", "ANSX_DECODE_SMALL_RING": "always"}):
+        # (beside every set of keys: the decoders it may end in, as ansx_last_decode_stats names them -- a forced key
+        # that fell through to another kernel fails here instead of passing on the default one)
+        # Where no key says which rings: the 256-byte ones -- this list takes about 1.2 payload bytes per int -- and
+        # by default rings at all, since the codec's worst-case stream of these blocks does not fit the staged form's 52 KiB.
+        for env, ran in (({}, ("SMALL_RING",)), ({"ANSX_DECODE_MODE": "ring"}, ("SMALL_RING",)),
+                         ({"ANSX_DECODE_MODE": "staged"}, ("STAGED",)),
+                         ({"ANSX_DECODE_MODE": "staged", "ANSX_NO_STREAM_LDS": "1"}, ("STAGED",)), ({"ANSX_DECODE_TABLE": "1"}, ("TABLE",)),
+                         # ring decoder: one block per workgroup (k_decode_rank) / two blocks in one instruction stream (k_decode_rank2)
+                         ({"ANSX_DECODE_MODE": "ring", "ANSX_DECODE_PAIR": "never"}, ("SMALL_RING",)),
+                         ({"ANSX_DECODE_MODE": "ring", "ANSX_DECODE_PAIR": "always"}, ("PAIR",)),
+                         # 512-byte worst-case rings / 256-byte speculative rings (chosen by the container's bytes per int otherwise)
+                         ({"ANSX_DECODE_MODE": "ring", "ANSX_DECODE_SMALL_RING": "never"}, ("RING",)),
+                         ({"ANSX_DECODE_MODE": "ring", "ANSX_DECODE_SMALL_RING": "always"}, ("SMALL_RING",))):
             try:
                 for k, v in env.items():
                     ctx.debug_set(k, v)
                 assert np.array_equal(codec.decode(cont, n), data), (block, ckpt, env)
+                st = ctx.last_decode_stats()
+                assert st["decoder"] in ran, (block, ckpt, env, st)
+                if "ANSX_NO_STREAM_LDS" in env:
+                    assert st["stream_cap"] == 0, (block, ckpt, env, st)
+                elif env.get("ANSX_DECODE_MODE") == "staged":
+                    assert st["stream_cap"] != 0, (block, ckpt, env, st)  # (else the pair of cases is one case twice)
             finally:
                 for k in env:
                     ctx.debug_set(k, None)
@@ -867,6 +880,7 @@ def test_small_ring_decoder_takes_intervals_back(A, ctx):
                 ctx.debug_set("ANSX_DECODE_MODE", "ring")
                 ctx.debug_set("ANSX_DECODE_SMALL_RING", "always")
                 assert np.array_equal(codec.decode(cont, n), d), (kind, f, block, ck)
+                assert ctx.last_decode_stats()["decoder"] == "SMALL_RING", (kind, f, block, ck, ctx.last_decode_stats())
             finally:
                 ctx.debug_set("ANSX_DECODE_MODE", None)
                 ctx.debug_set("ANSX_DECODE_SMALL_RING", None)
