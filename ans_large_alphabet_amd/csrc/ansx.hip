@@ -38,6 +38,7 @@
 #include "ansx_batchnextgeq.h"
 #include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
 #include "ansx_decode_form.h"  // the form of a decode call: parser, decoder, launch shapes
+#include "ansx_encode_form.h"  // the forms of an encode attempt: model, remap, prelude writer, encoder
 
 using namespace ansx_plan;
 
@@ -54,20 +55,6 @@ struct ProfRec {
 };
 
 }  // namespace
-
-// Block-range pipeline of the model kernels (model_fast; measurements: DESIGN.md section 6)
-#define ANSX_PIPE_NEVER (-1)
-#define ANSX_PIPE_ALWAYS (-2)
-#define ANSX_PIPE_MAX_RANGES 64
-// A call pipelines by itself from ANSX_PIPE_MIN_BLOCKS blocks and ANSX_PIPE_MIN_INTS ints on, in ANSX_PIPE_RANGES ranges.
-// Measured on MI355X (encode call, serial -> pipelined): 16384 blocks of 16 Ki ints ANSfold-1 1.226 -> 1.173 ms with 2, 3 or
-// 5 ranges, 1.213 with 6, 1.261 with 8 (k_sort_entropy and k_candidates have latency floors that every range pays again);
-// 8192 blocks break even for ANSfold-1 and gain for ANSfold-5 (2.91 -> 2.70 ms); 4096 blocks and fewer lose 0.003-0.07 ms
-// to the cross-stream waits.  Two ranges were never slower than the serial form on any list of that size, three lost
-// their gain on uniform data.
-#define ANSX_PIPE_RANGES 2u
-#define ANSX_PIPE_MIN_BLOCKS 8192u
-#define ANSX_PIPE_MIN_INTS ((u64)1 << 27)
 
 // Header of the last container decoded per shape (kind, fidelity, n, bytes): the next decode of that shape is launched
 // on it without waiting for the header to come back, and a one-thread kernel compares it with the real one
@@ -183,7 +170,7 @@ struct ansx_ctx {
         u32 test_sp_bits = 0;         // ANSX_TEST_SP_BITS: words of the sparse ANSint prelude writer's bit buffer on the first attempt (tests: forces its repeat)
         bool fin_one_wave = false;    // ANSX_FIN_ONE_WAVE: k_model_finish with one wave per block (alphabets up to 1024 slots)
         bool no_big_geo = false;      // ANSX_NO_BIG_GEO: no tabulated tree geometry for alphabets above 4096 slots
-        bool no_pc_auto = false;      // ANSX_NO_PC_AUTO: never choose the pair kernel by itself (shapes A, B, C of launch_f64_encoder)
+        bool no_pc_auto = false;      // ANSX_NO_PC_AUTO: never choose the pair kernel by itself (criteria A, B, C of choose_encoder_form)
         bool encode_mode2 = false;    // ANSX_ENCODE_MODE2: the compact-table encoder (k_encode<2>) even where the tables fit LDS (tests)
         bool force_pc = false;        // ANSX_FORCE_PC: the pair kernel for every workgroup of 64 full blocks, however few (tests)
         bool no_pc = false;           // ANSX_NO_PC: the LDS-table encoder as one wave per 16 blocks everywhere (k_encode<1>), no producer / consumer pairs
@@ -287,22 +274,18 @@ int pipeline_prepare(ansx_ctx* c, u32 nranges)
     return ANSX_OK;
 }
 
-// worst-case bytes of one block's reference stream
-size_t codec_nsp(int kind, u32 f) { return kind == ANSX_MSB ? 2048u : (kind == ANSX_INT ? 16384u : fold_NSP(f)); }
-
-// Remap classes of a pass's blocks, by block length: ANSrfold's (ansx_rfold.h) and the compaction layer's (ansx_pa.h)
-enum { RF_CLS_IDENTITY = 0, RF_CLS_SMALL = 1, RF_CLS_LARGE = 2 };
-enum { PA_CLS_SMALL = 0, PA_CLS_LARGE = 1 };
+using ansx_enc::block_bound;  // worst-case bytes of one block's reference stream (ansx_encode_form.h)
+using ansx_enc::codec_nsp;
 
 // The shortest symbol-row stride (Plan::NSP) the encode kernels take when no int they see exceeds `vmax` (a compacted
 // block's ranks: at most its length).  What a row must hold beyond the largest symbol `top` of 1..vmax, in one place:
 //   - top + 1 entries, the block's alphabet;
 //   - 8 more: k_scale_attempts and k_fold_hist read rows in chunks of 8 entries (ns rounded up to 8, plus a prefetch
 //     that is clamped to stride - 8), and rows must start on 16-byte boundaries (u16 rows: a multiple of 8 entries);
-//   - at least 64 entries: the floor of pre_cap, fcap and sort_cap (model_shape, write_preludes), which are then cut
+//   - at least 64 entries: the floor of pre_cap, fcap and sort_cap (choose_model_form, choose_prelude_form), which are then cut
 //     to min(stride, ...), and one full wave pass of k_sort_entropy / k_select_model;
 //   - a power of two, as every codec's own stride is (ANSX_HCOPY_PAD's bank argument, hist_packed's NSP / 2 words).
-// The stride selects launch shapes (model_shape, write_preludes) exactly as a codec's own slot count does, keys the
+// The stride selects launch shapes (ansx_encode_form.h) exactly as a codec's own slot count does, keys the
 // interp-geo tables (ansx_ctx::geo, one per distinct stride) and is no part of any stream.
 u32 min_row_stride(const ansx_map& m, u32 vmax)
 {
@@ -311,14 +294,6 @@ u32 min_row_stride(const ansx_map& m, u32 vmax)
     u32 stride = 64;
     while (stride < top + 1u + 8u) stride <<= 1;
     return stride;
-}
-
-size_t block_bound(int kind, u32 f, size_t nb, bool pa = false)
-{
-    size_t hdr = kind == ANSX_RFOLD ? 4 + 4 * (size_t)fold_T(f) : 0;
-    size_t nsp = codec_nsp(kind, f);
-    if (pa) hdr += 8 + 4 * nb + 8;  // alphabet header: at most 32 bits per distinct value
-    return hdr + 8 + 4 * nsp + 7 * nb + 32;
 }
 
 struct Plan {
@@ -443,30 +418,17 @@ int flags_to_status(u32 fl)
 }
 
 // --------------------------------------------------------------------------------- rfold
-// ans_reorder_fold.hpp:70-106 on the device: LDS hash table per block for blocks <= 16384 ints,
-// HBM hash table for longer blocks (incl. whole-list single-stream mode).
-// Optimistic hash-table size for a geometry whose blocks had at most `distinct` different values so far: 1.5 x that,
-// if two such tables (+ selection buffers) share a CU's LDS; 0 = use the full-size table.
-u32 rf_opt_slots(u32 distinct, u32 T)
+// ans_reorder_fold.hpp:70-106 on the device, in the form R names (ansx_enc::choose_remap_form).
+// ids != null (a batch pass, LDS forms only): the nids blocks of the pass listed there, addressed through g.bin
+int rfold_remap(ansx_ctx* c, const ansx_geo& g, const ansx_enc::RemapForm& R, const u32* d_in, u32* mapped, u32* mostfreq,
+    ansx_blk* blk, u32* gflags, hipStream_t s, const u32* ids = nullptr, u32 nids = 0)
 {
-    if (distinct == 0) return 0;
-    u32 slots = (2 * distinct + distinct / 2 + 64 + 255) & ~255u;
-    if (slots < 1024) slots = 1024;
-    const size_t lds = 6 * (size_t)slots + 8 * (size_t)(T < 512 ? 512 : T);
-    return lds <= 78 * 1024 ? slots : 0u;
-}
-// opt_slots != 0: optimistic table size for the LDS form (see k_rfold_remap_hash), from rf_opt_slots()
-// ids != null (a batch pass, LDS form only): the nids blocks of the pass listed there, addressed through g.bin
-int rfold_remap(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u32* mostfreq,
-    ansx_blk* blk, u32* gflags, hipStream_t s, u32 opt_slots = 0, const u32* ids = nullptr, u32 nids = 0)
-{
-    const u32 T = fold_T(g.f);
+    using namespace ansx_enc;
     const u32 grid = ids ? nids : g.nblocks;
-    if (ids && (g.block_ints > 16384u || T > 4096u)) return ANSX_ERR_ARG;  // (encode_batch_form keeps these off a pass)
-    if (g.block_ints > 16384u || T > 4096u) {  // (T > 4096: f = 6, 7 -- the selection buffer alone is 64 / 128 KB)
-        // large blocks (incl. whole-list single-stream mode): hash table in HBM
-        u32 slots = 2;
-        while ((u64)slots < 2ull * g.block_ints && slots < (1u << 31)) slots <<= 1;
+    const Launch& L = R.rf_remap;
+    if (R.rf == RF_HBM_HASH) {
+        if (ids) return ANSX_ERR_ARG;  // (encode_batch_form keeps these off a pass)
+        const u32 slots = R.rf_slots;
         int rc;
         if ((rc = ensure(c, c->rf_tmp, (size_t)g.nblocks * slots * 8 + (size_t)g.nblocks * 16))) return rc;
         u32* keys = (u32*)c->rf_tmp.p;
@@ -476,59 +438,45 @@ int rfold_remap(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u3
         HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)g.nblocks * slots * 4 + (size_t)g.nblocks * 16, s));
         const size_t grid = (g.n + 255) / 256;
         LAUNCH(c, "k_rfg_insert", k_rfg_insert, grid, 256, 0, s, d_in, g, slots, keys, counts, bstat);
-        if ((size_t)T * 8 > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_rfg_select,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)T * 8)));
-        LAUNCH(c, "k_rfg_select", k_rfg_select, g.nblocks, 256, (size_t)T * 8, s, g, slots, (const u32*)keys,
+        if (R.rf_select.raise)
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_rfg_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.rf_select.lds));
+        LAUNCH(c, "k_rfg_select", k_rfg_select, g.nblocks, R.rf_select.threads, R.rf_select.lds, s, g, slots, (const u32*)keys,
             counts, (const u32*)bstat, mostfreq, blk, gflags);
         LAUNCH(c, "k_rfg_map", k_rfg_map, grid, 256, 0, s, d_in, g, slots, (const u32*)keys, (const u32*)counts,
             (const ansx_blk*)blk, mapped);
         return ANSX_OK;
     }
-    if (T <= 4096) {  // hash-table form
-        const size_t sel_bytes = 8 * (size_t)(T < 512 ? 512 : T);  // also holds a 1024-bin histogram
-        if (opt_slots != 0 && opt_slots < ANSX_RF_SLOTS) {
-            const size_t lds = 6 * (size_t)opt_slots + sel_bytes;
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_rfold_remap_hash2,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (R.rf == RF_LDS_OPT) {
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_rfold_remap_hash2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
 #ifdef ANSX_STAMPS_RF
-            { static unsigned long long z[3] = { 0, 0, 0 }; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, 24, 4101 * 8); }
-            hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, s);
+        { static unsigned long long z[3] = { 0, 0, 0 }; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, 24, 4101 * 8); }
+        hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, s);
 #endif
-            LAUNCH(c, "k_rfold_remap", k_rfold_remap_hash2, grid, 1024, lds, s, d_in, g, opt_slots, mapped,
-                mostfreq, blk, gflags, ids);
+        LAUNCH(c, "k_rfold_remap", k_rfold_remap_hash2, grid, L.threads, L.lds, s, d_in, g, R.rf_slots, mapped, mostfreq, blk, gflags, ids);
 #ifdef ANSX_STAMPS_RF
-            {
-                (void)hipEventRecord(e1, s); (void)hipStreamSynchronize(s);
-                float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-                unsigned long long z[3]; (void)hipMemcpyFromSymbol(z, HIP_SYMBOL(g_stamps), 24, 4101 * 8);
-                fprintf(stderr, "[stamps] k_rfold_remap_hash2: events %.3f ms; workgroup lifetimes: max %llu ticks, mean %.0f ticks, %llu above 40 us\n", ms, z[0], (double)z[1] / g.nblocks, z[2]);
-            }
-#endif
-            return ANSX_OK;
+        {
+            (void)hipEventRecord(e1, s); (void)hipStreamSynchronize(s);
+            float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
+            unsigned long long z[3]; (void)hipMemcpyFromSymbol(z, HIP_SYMBOL(g_stamps), 24, 4101 * 8);
+            fprintf(stderr, "[stamps] k_rfold_remap_hash2: events %.3f ms; workgroup lifetimes: max %llu ticks, mean %.0f ticks, %llu above 40 us\n", ms, z[0], (double)z[1] / g.nblocks, z[2]);
         }
-        const size_t lds = 6 * (size_t)ANSX_RF_SLOTS + sel_bytes;
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_rfold_remap_hash,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(c, "k_rfold_remap", k_rfold_remap_hash, grid, 1024, lds, s, d_in, g, (u32)ANSX_RF_SLOTS, mapped,
-            mostfreq, blk, gflags, ids);
+#endif
         return ANSX_OK;
     }
-    u32 N2 = 2;
-    while (N2 < g.block_ints) N2 <<= 1;
-    size_t lds = 6 * (size_t)N2 + 8 * (size_t)T + 16;
-    if (lds > 48 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_rfold_remap,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    LAUNCH(c, "k_rfold_remap_sort", k_rfold_remap, g.nblocks, 256, lds, s, d_in, g, N2, mapped, mostfreq,
-        blk, gflags);
+    if (R.rf == RF_LDS_FULL) {
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_rfold_remap_hash, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+        LAUNCH(c, "k_rfold_remap", k_rfold_remap_hash, grid, L.threads, L.lds, s, d_in, g, R.rf_slots, mapped, mostfreq, blk, gflags, ids);
+        return ANSX_OK;
+    }
+    if (L.raise) HIPCHK(c, hipFuncSetAttribute((const void*)k_rfold_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    LAUNCH(c, "k_rfold_remap_sort", k_rfold_remap, g.nblocks, L.threads, L.lds, s, d_in, g, R.rf_slots, mapped, mostfreq, blk, gflags);
     return ANSX_OK;
 }
 
 // The remap of a batch pass (ansx_rfold.h): one launch per class of blocks that has any, over that class's block ids.
 // `in` and `mapped` are addressed through g.bin, so both are pointers to where int 0 of the caller's input would be.
 int rfold_remap_pass(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mapped, u32* mostfreq, ansx_blk* blk,
-    u32* gflags, hipStream_t s, u32 opt_slots, const u32* ids, const u32 ncls[3])
+    u32* gflags, hipStream_t s, const ansx_enc::RemapForm& R, const u32* ids, const u32 ncls[3])
 {
     const u32 n_id = ncls[RF_CLS_IDENTITY], n_small = ncls[RF_CLS_SMALL], n_large = ncls[RF_CLS_LARGE];
     if (n_id)
@@ -540,7 +488,7 @@ int rfold_remap_pass(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mappe
         LAUNCH(c, "k_rfold_remap_small", k_rfold_remap_small, (n_small + 3) / 4, 256, lds, s, d_in, g, ids + n_id, n_small,
             mapped, mostfreq, blk, gflags);
     }
-    if (n_large) return rfold_remap(c, g, d_in, mapped, mostfreq, blk, gflags, s, opt_slots, ids + n_id + n_small, n_large);
+    if (n_large) return rfold_remap(c, g, R, d_in, mapped, mostfreq, blk, gflags, s, ids + n_id + n_small, n_large);
     return ANSX_OK;
 }
 
@@ -548,93 +496,10 @@ int rfold_remap_pass(ansx_ctx* c, const ansx_geo& g, const u32* d_in, u32* mappe
 constexpr int ANSX_RETRY_GENERAL = -1;  // internal: an optimistic assumption did not hold, repeat without it
 constexpr int ANSX_RETRY_WIDE = -2;     // internal: a frame above 2^16 in a call laid out for packed restart points, repeat with wide ones
 
-// K5, f64-state forms (frames <= 2^16, every block's alphabet <= ns_entries).  Three kernels share the call's blocks:
-//   k_encode_pc   producer / consumer wave pairs, 16 x pairs blocks per workgroup, where that form wins: (A) chip-filling calls
-//                 whose tables fit 64 to a CU (four pairs, S = 8) -- BASELINE config 2; (B) alphabets too large for that whose
-//                 tables fit at 32 (two pairs, S = 4: every entry in LDS, two rounds, each wave alone on its SIMD) -- BASELINE
-//                 config 3; (C) short lists (one pair per workgroup, at most two per CU).  It takes ALL blocks of the call: the
-//                 last workgroup pads itself with neutral steps (blocks that do not exist, the partial last block)
-//   k_encode<1>   one wave per 16 blocks, 4-byte LDS entries: geometries the pair kernel does not take
-//   k_encode<2>   compact tables in HBM with the hottest 1151 symbols per block in LDS: alphabets that fit neither
-static int launch_f64_encoder(ansx_ctx* c, const ansx_geo& g, u32 NSP, const u32* src, u32 ns_entries, ansx_blk* blk, u64 scr_stride,
-    u64* ck_state, u32* ck_off, u32* enc_sizes, unsigned long long* enc_gsums, u32 NB, hipStream_t s, bool* used_pc)
-{
-    *used_pc = false;  // (true below, once the pair kernel has taken blocks of this call)
-    const u32 lds_stride = ns_entries | 1u;  // odd stride spreads the 16 tables over the banks
-    const size_t enc_lds = (size_t)16 * lds_stride * 4;
-    const bool mode1 = enc_lds <= 40 * 1024 && !c->dbg.encode_mode2;
-    const bool pow2 = map_is_pow2(g.map);
-    u32 first = 0;
-    // ---- producer / consumer pairs
-    const u32 rowwords = ((ns_entries + 2u) / 2u) | 1u;  // ns_entries + 1 running sums of 16 bits, an odd number of words per row
-    const u32 full_blocks = (u32)(g.n / g.block_ints);
-    const u32 enc_waves_all = (NB + 15) / 16;
-    auto pc_lds = [&](u32 pairs, u32 S) { return (size_t)pairs * 16 * rowwords * 4 + (size_t)pairs * (2 * S * 1024 + (S == 8 ? 16 * 144 : 0)); };
-    u32 pairs = 0, S = 0;
-    // (block_ints <= 2^22: the stand-in for a neutral step of a 2^16 frame lets the state creep by 2^-16 per step, see the kernel)
-    // (a batch pass: its blocks are not block_ints apart in the input -- k_encode<MODE> reads them through the per-block table)
-    const bool pc_geo = !c->dbg.no_pc && !g.bin && g.block_ints % 128u == 0 && g.block_ints <= (1u << 22) && (u64)scr_stride * 16 < 0x40000000ull;
-    if (pc_geo && (!c->dbg.no_pc_auto || c->dbg.use_pc || c->dbg.force_pc) && mode1 && pc_lds(4, 8) <= 160 * 1024
-        && (((NB + 63) / 64) * 2 >= (u32)c->num_cus || c->dbg.force_pc))
-        pairs = 4, S = 8;  // (A) the chip-filling form: 0.66 against k_encode<1>'s 0.71 ms on the headline workload since the producer
-                           // loads its inputs 16 bytes at a time (equal before that)
-    else if (pc_geo && !mode1 && pc_lds(2, 4) <= 160 * 1024 && (full_blocks >= 32 || c->dbg.force_pc) && !c->dbg.no_pc_auto)
-        pairs = c->dbg.pc_b_pairs, S = 4;                                    // (B) every table entry in LDS, two rounds
-    else if (pc_geo && mode1 && enc_waves_all <= 2u * (u32)c->num_cus && (full_blocks >= 16 || c->dbg.force_pc) && !c->dbg.no_pc_auto)
-        pairs = 1, S = 8;  // (C) short lists: the call waits for one wave's state chain, and the consumer's is 20 % shorter.  (Lists of
-                           // fewer than 16 full blocks stay with k_encode<1>, which walks a short block's own steps only.)
-    if (pairs && (g.ckpt == 0 || g.ckpt % (4u * S) == 0)) {
-        const u32 wgs = (NB + 16 * pairs - 1) / (16 * pairs);
-        const size_t lds = pc_lds(pairs, S);
-        const auto kern = pow2 ? (S == 8 ? k_encode_pc<true, 8> : k_encode_pc<true, 4>) : (S == 8 ? k_encode_pc<false, 8> : k_encode_pc<false, 4>);
-        HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(c, "k_encode", kern, wgs, 128 * pairs, lds, s, src, g, NSP, (const u32*)c->tab32.p, ns_entries, rowwords, blk,
-            (u8*)c->scratch.p, scr_stride, ck_state, ck_off, enc_sizes, enc_gsums);
-        first = wgs * 16 * pairs;
-        *used_pc = true;
-        if (first >= NB) return ANSX_OK;
-    }
-    const u32 enc_waves = (NB - first + 15) / 16;
-    u32 wpw = (enc_waves + c->num_cus - 1) / c->num_cus;
-    wpw = wpw < 1 ? 1 : (wpw > 4 ? 4 : wpw);
-    const size_t enc_grid = (enc_waves + wpw - 1) / wpw;
-    if (mode1) {
-        // ---- one wave per 16 blocks.  Waves of one workgroup run the main loop in step (a barrier per super-batch): up to four
-        // waves per workgroup -- one per SIMD of a CU -- as soon as there are that many waves per CU (see k_encode)
-        const auto kern = pow2 ? k_encode<1, true> : k_encode<1, false>;
-        if (wpw * enc_lds > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wpw * enc_lds)));
-        LAUNCH(c, first ? "k_encode_rest" : "k_encode", kern, enc_grid, 64 * wpw, wpw * enc_lds, s, src, g, NSP,
-            (const ansx_enc_entry*)nullptr, (const u32*)c->tab32.p, lds_stride, blk, (u8*)c->scratch.p,
-            (u64)scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, first);
-        return ANSX_OK;
-    }
-    // ---- alphabets too large for LDS: compact table entries from HBM, same branch-free f64 step
-    const size_t lds2 = (size_t)wpw * 16 * ANSX_ENC_HOT * 4;
-    if (lds2 > 48 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_encode<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-    LAUNCH(c, first ? "k_encode_rest" : "k_encode_gtab", (k_encode<2>), enc_grid, 64 * wpw, lds2, s, src, g, NSP,
-        (const ansx_enc_entry*)nullptr, (const u32*)c->tab32.p, (u32)ANSX_ENC_HOT, blk, (u8*)c->scratch.p,
-        (u64)scr_stride, ck_state, ck_off, enc_sizes, enc_gsums, first);
-    return ANSX_OK;
-}
-
 // One attempt of an encode call: what it may assume.  The retry ladder (encode_dev -> encode_dev_once -> resolve_near)
 // builds the attempts; inside an attempt the value is constant, and no function of the encode path learns a per-call
 // fact from the context.
-struct EncodeAttempt {
-    // ns_cap == 0: discovery -- the largest alphabet / frame of the call are read back between the model kernels and
-    // the encoder launch (one host round trip per candidate batch).
-    // ns_cap != 0: optimistic -- the caller has seen this geometry before (alphabet hint): the first candidate batch is
-    // assumed to settle every block, frames are assumed to stay within 2^16 and alphabets within ns_cap, so everything
-    // is launched back to back; the assumptions are checked on the words that come back with the output size anyway,
-    // and a miss returns ANSX_RETRY_GENERAL.  nt, rf_slots and pa_distinct are nonzero in optimistic attempts only.
-    u32 ns_cap = 0;
-    u32 nt = 0;                  // candidates per block of the fast model path (4 .. 8), 0 = the exact model kernels
-    u32 rf_slots = 0;            // ANSrfold: optimistic hash-table size (rf_opt_slots), 0 = the full-size table
-    u32 pa_distinct = 0;         // compaction layer: the geometry's distinct-value hint (sizes k_pa_remap2), 0 = full size
-    bool int_sparse = false;     // plain ANSint modelled in rank space (ansx_intsparse.h)
-    bool sp_full_lds = false;    // ... and its prelude writer runs with the full-size LDS arrays (a block's code outgrew the hint-sized ones)
+struct EncodeAttempt : ansx_enc::EncAttempt {  // (what it may assume: the part the forms read, ansx_encode_form.h)
     const u32* force = nullptr;  // per-block frames decided by the host (resolve_near), device array
 };
 // ... and what it found.  Every attempt starts it afresh, except sp_repeated, which only ever becomes true: a ladder
@@ -666,9 +531,9 @@ struct EncodeWs {
     double* hterm;                  // entropy terms through HBM (model_prepare), or null
     const u32 *src, *mostfreq;      // encode_remap: the ints the model kernels and the encoder read; ANSrfold's selection
     u32 max_logM, max_ns;           // the model phase: largest frame / alphabet the later launches are sized for
+    ansx_enc::EncGeo G;             // encode_begin: what the forms read of the plan ...
+    ansx_enc::EncKeys K;            // ... and of the context's overrides
 };
-
-u64 scratch_stride(const ansx_geo& g) { return rup(block_bound(g.kind, g.f, g.block_ints, g.pa != 0) + 16, 256); }
 
 // A pass of ansx_encode_batch_dev (encode_batch_pass builds it; the phases reach it through Plan::bat)
 struct EncBatchPass {
@@ -681,6 +546,31 @@ struct EncBatchPass {
     u8* d_out;                // the caller's buffer
     const ansx_encb_res* hres;  // pinned: the results, read back with the attempt's flag words
 };
+
+// The forms of an attempt -- ModelForm, RemapForm, PreludeForm, EncoderForm -- are host-only arithmetic in
+// ansx_encode_form.h (swept on the CPU by tests/tools/encode_form_check.cpp).  Here: what they read of a plan and of
+// the context's overrides.
+using ansx_enc::EncoderForm;
+using ansx_enc::ModelForm;
+using ansx_enc::PreludeForm;
+using ansx_enc::RemapForm;
+
+ansx_enc::EncGeo enc_geo(const Plan& P)
+{
+    const ansx_geo& g = P.g;
+    return { g.n, g.block_ints, g.nblocks, g.ckpt, g.kind, g.f, g.pa, P.NSP, P.plain, P.bat != nullptr, P.bat ? P.bat->longest : 0u,
+        map_is_pow2(g.map) };
+}
+
+ansx_enc::EncKeys enc_keys(const DebugOpts& d)
+{
+    ansx_enc::EncKeys k;
+    k.table16_fixup = d.table16_fixup, k.encode_gtab16 = d.encode_gtab16, k.fin_one_wave = d.fin_one_wave;
+    k.use_pc = d.use_pc, k.no_pc_auto = d.no_pc_auto, k.force_pc = d.force_pc, k.no_pc = d.no_pc, k.encode_mode2 = d.encode_mode2;
+    k.pc_b_pairs = d.pc_b_pairs, k.test_sp_bits = d.test_sp_bits, k.cand_chains = d.cand_chains;
+    k.model_pipeline = d.model_pipeline;
+    return k;
+}
 
 // the flag words (and the result behind them), read back into the attempt's outcome: a host wait
 int read_flags(ansx_ctx* c, const EncodeWs& W, u32 words)
@@ -701,8 +591,9 @@ int encode_begin(ansx_ctx* c, EncodeWs& W)
     const bool sp = W.out->sp_repeated;
     *W.out = EncodeOutcome();
     W.out->sp_repeated = sp;
-    // (a batch pass: slots as long as its longest block needs, not as block_ints would)
-    W.scr_stride = P.bat ? rup(block_bound(g.kind, g.f, P.bat->longest, g.pa != 0) + 16, 256) : scratch_stride(g);
+    W.G = enc_geo(P);
+    W.K = enc_keys(c->dbg);
+    W.scr_stride = ansx_enc::scratch_stride(W.G);
     if (!P.plain && W.cap < P.lay.payload_off) return ANSX_ERR_CAPACITY;
     int rc;
     if ((rc = ensure(c, c->hist, (size_t)NB * NSP * 4))) return rc;
@@ -765,6 +656,7 @@ int encode_remap(ansx_ctx* c, EncodeWs& W)
     const EncodeAttempt& a = *W.a;
     const u32 NB = g.nblocks;
     hipStream_t s = W.s;
+    const RemapForm R = ansx_enc::choose_remap_form(W.G, a);
     int rc;
     if (g.kind == ANSX_RFOLD && W.P->bat) {
         // a batch pass (g.n is not its ints): `mapped` holds the pass's own stretch of the input's index space, and the
@@ -774,14 +666,14 @@ int encode_remap(ansx_ctx* c, EncodeWs& W)
         if ((rc = ensure(c, c->mapped, (size_t)std::max<u64>(B.in_ints, 1) * 4))) return rc;
         if ((rc = ensure(c, c->mostfreq, (size_t)NB * fold_T(g.f) * 4))) return rc;
         u32* biased = (u32*)((uintptr_t)c->mapped.p - (uintptr_t)B.in_base * 4);
-        if ((rc = rfold_remap_pass(c, g, W.d_in, biased, (u32*)c->mostfreq.p, W.blk, W.gflags, s, a.rf_slots, B.remap_ids, B.remap_ncls)))
+        if ((rc = rfold_remap_pass(c, g, W.d_in, biased, (u32*)c->mostfreq.p, W.blk, W.gflags, s, R, B.remap_ids, B.remap_ncls)))
             return rc;
         W.src = biased;
         W.mostfreq = (const u32*)c->mostfreq.p;
     } else if (g.kind == ANSX_RFOLD) {
         if ((rc = ensure(c, c->mapped, (size_t)g.n * 4))) return rc;
         if ((rc = ensure(c, c->mostfreq, (size_t)NB * fold_T(g.f) * 4))) return rc;
-        if ((rc = rfold_remap(c, g, W.d_in, (u32*)c->mapped.p, (u32*)c->mostfreq.p, W.blk, W.gflags, s, a.rf_slots))) return rc;
+        if ((rc = rfold_remap(c, g, R, W.d_in, (u32*)c->mapped.p, (u32*)c->mostfreq.p, W.blk, W.gflags, s))) return rc;
         W.src = (const u32*)c->mapped.p;
         W.mostfreq = (const u32*)c->mostfreq.p;
     }
@@ -817,109 +709,43 @@ int encode_remap(ansx_ctx* c, EncodeWs& W)
     }
     if (g.pa && pa_large) {
         // per-block alphabet compaction (src/pseudo_adaptive.cpp:85-130): alphabet header into the block's scratch slot, the
-        // codec then runs on the 1-based ranks.  Sizes from the geometry's distinct-value hint (optimistic calls only): hash set 2.5 x, value list the next
-        // power of two above 1.25 x; both workgroups of a CU must fit its LDS
-        u32 pa_slots = ANSX_PA_SLOTS, pa_uqcap = ANSX_PA_MAX_BLOCK;
-        bool pa_small = false;
-        if (a.pa_distinct != 0) {
-            const u32 d = a.pa_distinct;
-            const u32 sl = (2 * d + d / 2 + 64 + 255) & ~255u;
-            u32 uc = 1024;
-            while (uc < d + d / 4 + 16) uc <<= 1;
-            if (((size_t)sl + uc) * 4 <= 78 * 1024 && uc <= ANSX_PA_MAX_BLOCK) pa_slots = sl, pa_uqcap = uc, pa_small = true;
-        }
-        const size_t lds1 = ((size_t)pa_slots + pa_uqcap) * 4;
-        if (pa_small) {
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-            LAUNCH(c, "k_pa_remap", k_pa_remap2, pa_large, 1024, lds1, s, W.d_in, g, pa_slots, pa_uqcap, pa_mapped, pa_alpha, W.blk,
-                W.gflags, 1u << 30, pa_ids);
+        // codec then runs on the 1-based ranks.  Hint-sized tables (R.pa_small) have a kernel of their own
+        if (R.pa_small) {
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.pa_remap_lds));
+            LAUNCH(c, "k_pa_remap", k_pa_remap2, pa_large, 1024, R.pa_remap_lds, s, W.d_in, g, R.pa_slots, R.pa_uqcap, pa_mapped, pa_alpha,
+                W.blk, W.gflags, 1u << 30, pa_ids);
         } else {
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-            LAUNCH(c, "k_pa_remap", k_pa_remap, pa_large, 1024, lds1, s, W.d_in, g, pa_slots, pa_uqcap, pa_mapped, pa_alpha, W.blk,
-                W.gflags, 1u << 30, 0u, pa_ids);
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.pa_remap_lds));
+            LAUNCH(c, "k_pa_remap", k_pa_remap, pa_large, 1024, R.pa_remap_lds, s, W.d_in, g, R.pa_slots, R.pa_uqcap, pa_mapped, pa_alpha,
+                W.blk, W.gflags, 1u << 30, 0u, pa_ids);
         }
-        const size_t lds2 = pa_small ? ((size_t)3 * pa_uqcap + 32) * 4 : ((size_t)2 * ANSX_PA_MAX_BLOCK + 16) * 4;
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_header, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        LAUNCH(c, "k_pa_header", k_pa_header, pa_large, 256, lds2, s, g, (const u32*)pa_alpha, W.blk, (u8*)c->scratch.p,
-            W.scr_stride, pa_small ? pa_uqcap : (u32)ANSX_PA_MAX_BLOCK, pa_ids);
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_header, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.pa_hdr_lds));
+        LAUNCH(c, "k_pa_header", k_pa_header, pa_large, 256, R.pa_hdr_lds, s, g, (const u32*)pa_alpha, W.blk, (u8*)c->scratch.p,
+            W.scr_stride, R.pa_hdr_cap, pa_ids);
     }
     if (a.int_sparse) {
         // plain ANSint on values beyond the dense model (ansx_intsparse.h): the codec runs on every block's 0-based ranks
-        const size_t lds1 = ((size_t)ANSX_PA_SLOTS + ANSX_PA_MAX_BLOCK) * 4;
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        LAUNCH(c, "k_pa_remap", k_pa_remap, NB, 1024, lds1, s, W.d_in, g, (u32)ANSX_PA_SLOTS, (u32)ANSX_PA_MAX_BLOCK, pa_mapped,
+        // (never hinted: R has the full-size tables)
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_pa_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.pa_remap_lds));
+        LAUNCH(c, "k_pa_remap", k_pa_remap, NB, 1024, R.pa_remap_lds, s, W.d_in, g, R.pa_slots, R.pa_uqcap, pa_mapped,
             pa_alpha, W.blk, W.gflags, (u32)ANSX_SP_VALUE_LIMIT, 1u, (const u32*)nullptr);
     }
     W.out->src = W.src;
     return ANSX_OK;
 }
 
-// Launch shapes of the model kernels: a pure function of the geometry, the attempt and the debug switches.
-struct ModelShape {
-    u32 chunk, cpb;    // K1: ints per histogram workgroup, workgroups per block
-    bool h_deferred;   // blocks that fit one histogram workgroup (the normal case): entropy terms from K1, in-order sum from K2b (else both in K2a)
-    bool h_in_hist;    // ... and alphabets up to 2048 slots are also summed in K1 (terms in LDS), larger ones through HBM in K2b
-    bool fast;         // fast model path (ansx_fastmodel.h): k_candidates / k_model_finish instead of the candidate batches
-    bool hist_packed;  // f >= 4: 16-bit counters, two per LDS word (a chunk holds at most 16384 values): half the LDS, twice the workgroups per CU
-    size_t hist_lds;
-    u32 nbig_cap, sort_cap;  // K2: "big" symbols have freq >= ANSX_VMAX; length of the staged row
-    bool sort16, sort_staged;
-    size_t k2a_lds;
-    u32 always16;      // the 16-byte table entries have a certain consumer before the frames are known
-    // fast model path: lanes of k_candidates, LDS of k_model_finish
-    u32 bpw, fcap;
-    size_t fin_lds;
-};
-ModelShape model_shape(const ansx_ctx* c, const EncodeWs& W)
-{
-    const ansx_geo& g = W.P->g;
-    const EncodeAttempt& a = *W.a;
-    const u32 NSP = W.P->NSP;
-    ModelShape M;
-    M.chunk = g.block_ints < 16384u ? g.block_ints : 16384u;
-    if (M.chunk & 3u) M.chunk = (M.chunk + 3u) & ~3u;
-    M.cpb = (g.block_ints + M.chunk - 1) / M.chunk;
-    M.h_deferred = (M.cpb == 1);
-    M.h_in_hist = M.h_deferred && NSP <= 2048;
-    // Fast model path: geometries seen before, whole-block histograms, 16-bit frequencies, compact tables; every
-    // assumption is checked on the device and a miss repeats the call on the exact path.
-    // (alphabets above 4096 slots -- f = 4, 5 -- take the generic form of k_model_finish as long as its three LDS arrays,
-    // sized from the alphabet hint, fit a CU; ANSint has no u16 rule and 32-bit frequencies: exact path)
-    M.fcap = std::min<u32>(NSP, std::max<u32>(64u, (a.ns_cap + 15u) & ~15u));
-    M.fast = a.nt != 0 && !g.pa && M.h_deferred && g.block_ints <= 65535u && NSP <= 16384 && g.kind != ANSX_INT
-        && (NSP <= 4096 || (size_t)M.fcap * 8 + 64 <= 150 * 1024) && !c->dbg.table16_fixup
-        && !c->dbg.encode_gtab16 && W.scr_stride * 16 < 0x7FFFFF00ull;
-    M.hist_packed = NSP >= 8192u;
-    // (fast path: H is a tree sum in registers, no LDS row of terms)
-    M.hist_lds = M.hist_packed ? (size_t)NSP * 2
-        : !M.h_in_hist       ? (size_t)NSP * 4
-                             : (size_t)4 * (NSP + ANSX_HCOPY_PAD) * 4 + (M.fast ? 0 : (size_t)NSP * 8 + 80);
-    M.nbig_cap = (u32)std::min<size_t>(NSP, (size_t)g.block_ints / ANSX_VMAX + 2);
-    // (optimistic calls with whole-block histograms: the staged row is as long as the alphabet hint, see the kernel)
-    M.sort_cap = (a.ns_cap != 0 && M.h_deferred) ? std::min<u32>(NSP, std::max<u32>(64u, (a.ns_cap + 7u) & ~7u)) : NSP;
-    M.sort16 = g.block_ints <= 65535u;  // (a count fits 16 bits: half the staged row)
-    M.k2a_lds = (size_t)M.nbig_cap * 8 + (size_t)M.sort_cap * (M.sort16 ? 2 : 4) + (M.h_deferred ? 0 : 512 * 8);
-    M.sort_staged = M.k2a_lds <= 150 * 1024;  // (f = 6, 7 with 32-bit counts: the row stays in HBM)
-    if (!M.sort_staged) M.k2a_lds = (size_t)M.nbig_cap * 8 + (M.h_deferred ? 0 : 512 * 8);
-    // consumers of the 16-byte table entries that are certain before the frames are known: the generic prelude writer (alphabets above
-    // 4096 slots) and the integer-state encoder (forced, or scratch slots too far apart for the f64 encoder's 31-bit buffer offsets)
-    M.always16 = (!c->dbg.table16_fixup && (NSP > 4096 || W.scr_stride * 16 >= 0x7FFFFF00ull || c->dbg.encode_gtab16)) ? 1u : 0u;
-    M.bpw = M.fast ? 64u / a.nt : 1u;
-    M.fin_lds = (size_t)M.fcap * (NSP > 4096 ? 8 : 12) + 64;  // (above 4096 slots: inc[] in the block's histogram row, two LDS arrays)
-    return M;
-}
-
-// ---- one dispatch per templated model kernel: the attribute call and the launch name the instantiation through it
+// ---- a form's variant -> the instantiation: the attribute call and the launch name the kernel through these
 using hist_kernel_t = decltype(&k_fold_hist<false>);
 using sort_kernel_t = decltype(&k_sort_entropy<u16>);
 using cand_kernel_t = decltype(&k_candidates<4, 1>);
 using fin_kernel_t = decltype(&k_model_finish<4, 8>);
-hist_kernel_t hist_kernel(const ModelShape& M) { return M.hist_packed ? k_fold_hist<true> : k_fold_hist<false>; }
-sort_kernel_t sort_kernel(const ModelShape& M)
+hist_kernel_t hist_kernel(const ModelForm& M) { return M.hist.variant == ansx_enc::HIST_PACKED ? k_fold_hist<true> : k_fold_hist<false>; }
+sort_kernel_t sort_kernel(const ModelForm& M)
 {
-    return !M.sort_staged ? k_sort_entropy<u32, false> : (M.sort16 ? k_sort_entropy<u16> : k_sort_entropy<u32>);
+    return M.sort.variant == ansx_enc::SORT_U32_UNSTAGED ? k_sort_entropy<u32, false>
+        : (M.sort.variant == ansx_enc::SORT_U16 ? k_sort_entropy<u16> : k_sort_entropy<u32>);
 }
-cand_kernel_t cand_kernel(u32 NT, u32 nch)
+cand_kernel_t cand_kernel(u32 NT, int nch)
 {
     switch (NT) {
     case 4: return nch == 1 ? k_candidates<4, 1> : k_candidates<4, 2>;
@@ -929,14 +755,17 @@ cand_kernel_t cand_kernel(u32 NT, u32 nch)
     default: return nch == 1 ? k_candidates<8, 1> : k_candidates<8, 2>;
     }
 }
-struct FinKernel { fin_kernel_t kern; u32 threads; };  // (its NTH is also the launch's workgroup size)
-FinKernel fin_kernel(const ansx_ctx* c, u32 NSP, u32 NT)
+fin_kernel_t fin_kernel(const ModelForm& M)  // (its NTH is also the launch's workgroup size)
 {
-    // one wave per block (16 slots per lane, every candidate in every lane, no workgroup barriers): four times the blocks in flight
-    if (NSP <= 1024 && c->dbg.fin_one_wave) return { NT <= 5 ? k_model_finish<16, 5, 64> : k_model_finish<16, 8, 64>, 64 };
-    if (NSP <= 1024) return { k_model_finish<4, 8, 256>, 256 };  // (wave-per-candidate form: NTC is not used)
-    if (NSP > 4096) return { NT <= 5 ? k_model_finish<0, 5, 256> : k_model_finish<0, 8, 256>, 256 };
-    return { NT <= 5 ? k_model_finish<16, 5, 256> : k_model_finish<16, 8, 256>, 256 };
+    switch (M.fin.variant) {
+    case ansx_enc::FIN_ONE_WAVE_5: return k_model_finish<16, 5, 64>;
+    case ansx_enc::FIN_ONE_WAVE_8: return k_model_finish<16, 8, 64>;
+    case ansx_enc::FIN_WAVES: return k_model_finish<4, 8, 256>;
+    case ansx_enc::FIN_GENERIC_5: return k_model_finish<0, 5, 256>;
+    case ansx_enc::FIN_GENERIC_8: return k_model_finish<0, 8, 256>;
+    case ansx_enc::FIN_16_5: return k_model_finish<16, 5, 256>;
+    default: return k_model_finish<16, 8, 256>;
+    }
 }
 template <class K>
 int raise_lds(ansx_ctx* c, K kern, size_t lds)
@@ -944,44 +773,36 @@ int raise_lds(ansx_ctx* c, K kern, size_t lds)
     HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return ANSX_OK;
 }
-// chains per lane of k_candidates: one while that leaves at most one wave per SIMD, else two (see the kernel); per launch, by its blocks
-u32 cand_chains(const ansx_ctx* c, const ModelShape& M, u32 nblk)
-{
-    return c->dbg.cand_chains ? c->dbg.cand_chains : (((nblk + M.bpw - 1) / M.bpw <= 4u * c->num_cus) ? 1u : 2u);
-}
-size_t cand_lds(const ModelShape& M, u32 nch) { return (size_t)ANSX_CAND_WAVES * nch * M.bpw * ANSX_CAND_ROW * 16; }
 
 // ---- the launches of the model phase for the blocks [b0, be) on stream st
 // K1
-int launch_hist(ansx_ctx* c, const EncodeWs& W, const ModelShape& M, hipStream_t st, u32 b0, u32 be)
+int launch_hist(ansx_ctx* c, const EncodeWs& W, const ModelForm& M, hipStream_t st, u32 b0, u32 be)
 {
     const ansx_geo& g = W.P->g;
     const u32 NSP = W.P->NSP;
     // (sum_mode bit 1: on the fast model path H is the workgroup's tree sum and there is no hterm array to write)
-    LAUNCH(c, "k_fold_hist", hist_kernel(M), (size_t)(be - b0) * M.cpb, 256, M.hist_lds, st, W.src, g, M.chunk, M.cpb, NSP, W.hist, W.hterm,
+    LAUNCH(c, "k_fold_hist", hist_kernel(M), (size_t)(be - b0) * M.hist.grid, M.hist.threads, M.hist.lds, st, W.src, g, M.chunk, M.cpb, NSP, W.hist, W.hterm,
         (M.h_in_hist ? 1u : 0u) | (M.fast ? 2u : 0u), W.blk, W.gflags, (g.kind == ANSX_INT && !g.pa) ? NSP : (1u << 30), b0, be);
     return ANSX_OK;
 }
 // K2
-int launch_sort(ansx_ctx* c, const EncodeWs& W, const ModelShape& M, hipStream_t st, u32 b0, u32 be)
+int launch_sort(ansx_ctx* c, const EncodeWs& W, const ModelForm& M, hipStream_t st, u32 b0, u32 be)
 {
-    LAUNCH(c, "k_sort_entropy", sort_kernel(M), be - b0, 64, M.k2a_lds, st, W.P->g, W.P->NSP, M.nbig_cap, M.h_deferred ? 1u : 0u, W.hist,
+    LAUNCH(c, "k_sort_entropy", sort_kernel(M), be - b0, M.sort.threads, M.sort.lds, st, W.P->g, W.P->NSP, M.nbig_cap, M.h_deferred ? 1u : 0u, W.hist,
         (u32*)c->sortF.p, (u16*)c->sortSym.p, W.blk, M.sort_cap, M.fast ? (uint2*)c->pairs.p : (uint2*)nullptr, W.gflags, b0, be);
     return ANSX_OK;
 }
 // K2 and the two kernels of the fast model path behind it
-int launch_fast_model(ansx_ctx* c, const EncodeWs& W, const ModelShape& M, hipStream_t st, u32 b0, u32 be)
+int launch_fast_model(ansx_ctx* c, const EncodeWs& W, const ModelForm& M, hipStream_t st, u32 b0, u32 be)
 {
     const ansx_geo& g = W.P->g;
     const u32 NSP = W.P->NSP, NT = W.a->nt;
     int rc;
     if ((rc = launch_sort(c, W, M, st, b0, be))) return rc;
-    const u32 nch = cand_chains(c, M, be - b0);
-    const u32 cwaves = (be - b0 + nch * M.bpw - 1) / (nch * M.bpw);
-    LAUNCH(c, "k_candidates", cand_kernel(NT, nch), (cwaves + ANSX_CAND_WAVES - 1) / ANSX_CAND_WAVES, 64 * ANSX_CAND_WAVES, cand_lds(M, nch), st,
+    const ansx_enc::Launch cand = ansx_enc::cand_launch(M, be - b0);
+    LAUNCH(c, "k_candidates", cand_kernel(NT, cand.variant), cand.grid, cand.threads, cand.lds, st,
         g, NSP, (const uint2*)c->pairs.p, (const ansx_blk*)W.blk, (uint4*)c->attS.p, (u32*)c->attMeta.p, b0, be);
-    const FinKernel fin = fin_kernel(c, NSP, NT);
-    LAUNCH(c, "k_model_finish", fin.kern, be - b0, fin.threads, M.fin_lds, st, g, NSP, NT, (const uint2*)c->pairs.p, (const uint4*)c->attS.p,
+    LAUNCH(c, "k_model_finish", fin_kernel(M), be - b0, M.fin.threads, M.fin.lds, st, g, NSP, NT, (const uint2*)c->pairs.p, (const uint4*)c->attS.p,
         (const u32*)c->attMeta.p, W.blk, (u32*)c->tab32.p, (u8*)c->scratch.p, W.scr_stride, W.mostfreq, W.hints, W.gflags, M.fcap,
         c->dbg.fast_guard, (const double*)c->lg2i.p, W.geo, NSP > 4096 ? W.hist : (u32*)nullptr, b0, be, c->dbg.chain_old ? 1u : 0u);
     if (!c->dbg.chain_old)  // (the call's running maxima: no longer every block's own business)
@@ -990,7 +811,7 @@ int launch_fast_model(ansx_ctx* c, const EncodeWs& W, const ModelShape& M, hipSt
 }
 
 // Phase 3a: what K1 and K2 need whichever model form follows
-int model_prepare(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
+int model_prepare(ansx_ctx* c, EncodeWs& W, const ModelForm& M)
 {
     const size_t NB = W.P->g.nblocks, NSP = W.P->NSP;
     int rc;
@@ -999,15 +820,15 @@ int model_prepare(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
         if ((rc = ensure(c, c->hterm, NB * NSP * 8))) return rc;
         W.hterm = (double*)c->hterm.p;
     }
-    if (M.hist_lds > 48 * 1024 && (rc = raise_lds(c, hist_kernel(M), M.hist_lds))) return rc;
-    if (M.k2a_lds > 32 * 1024 && (rc = raise_lds(c, sort_kernel(M), M.k2a_lds))) return rc;
+    if (M.hist.raise && (rc = raise_lds(c, hist_kernel(M), M.hist.lds))) return rc;
+    if (M.sort.raise && (rc = raise_lds(c, sort_kernel(M), M.sort.lds))) return rc;
     return ANSX_OK;
 }
 
 // Phase 3b, the model in its exact form: K1, K2, then frame sizes M0 * 2^t tried ANSX_ATTEMPTS at a time.  Almost every
 // block settles in the first batch; the count of undecided blocks comes back with the words the encoder launch
 // needs anyway (largest alphabet / frame), so further batches are launched only on demand.
-int model_exact(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
+int model_exact(ansx_ctx* c, EncodeWs& W, const ModelForm& M)
 {
     const ansx_geo& g = W.P->g;
     const u32 NB = g.nblocks, NSP = W.P->NSP;
@@ -1046,30 +867,12 @@ int model_exact(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
 // every range but the last on one of the context's two side streams (alternating) behind that range's histogram -- a
 // memory-bound kernel beside a VALU-bound one beside a latency chain.  The ranges meet in no workspace byte (every
 // array is indexed by the absolute block number) and in `gflags` only through order-independent atomics.  Everything
-// joins on the caller's stream in front of the encoder.  *nranges == 0: one launch of each kernel over all blocks on
-// the caller's stream.
-int pipeline_plan(ansx_ctx* c, const EncodeWs& W, u32* range_blocks, u32* nranges)
-{
-    const ansx_geo& g = W.P->g;
-    const u32 NB = g.nblocks;
-    const int mode = c->dbg.model_pipeline;
-    *range_blocks = NB, *nranges = 0;
-    // (profile mode: the event pairs of LAUNCH would time overlapped kernels -- serial there)
-    if (c->profile || mode == ANSX_PIPE_NEVER) return ANSX_OK;
-    const u32 want = mode > 0 ? (u32)mode : ((mode == ANSX_PIPE_ALWAYS || (NB >= ANSX_PIPE_MIN_BLOCKS && g.n >= ANSX_PIPE_MIN_INTS)) ? ANSX_PIPE_RANGES : 0u);
-    if (!want) return ANSX_OK;
-    // (a captured graph with parallel branches: the call stays one chain of launches under capture)
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(W.s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return ANSX_OK;
-    *range_blocks = (u32)rup(((size_t)NB + want - 1) / want, 64);  // range boundaries: multiples of 64 blocks
-    *nranges = (NB + *range_blocks - 1) / *range_blocks;
-    return pipeline_prepare(c, *nranges);
-}
-
+// joins on the caller's stream in front of the encoder.  ModelForm::nranges == 0: one launch of each kernel over all
+// blocks on the caller's stream.
 // Phase 3b, the model in its fast form: K1, K2, k_candidates, k_model_finish (which also writes the preludes), serial
 // or as the block-range pipeline.  Everything that is not a launch, an event record or a stream wait -- buffers, the
 // one-time tables, the side streams, every function attribute -- comes first.
-int model_fast(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
+int model_fast(ansx_ctx* c, EncodeWs& W, ModelForm M)
 {
     const u32 NB = W.P->g.nblocks, NSP = W.P->NSP;
     hipStream_t s = W.s;
@@ -1089,14 +892,20 @@ int model_fast(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
         if ((rc = ensure(c, c->lg2i, (size_t)65536 * 8))) return rc;
         LAUNCH(c, "k_build_log2i_lut", k_build_log2i_lut, 256, 256, 0, s, (double*)c->lg2i.p);
     }
-    u32 range_blocks, nranges;
-    if ((rc = pipeline_plan(c, W, &range_blocks, &nranges))) return rc;
+    if (M.nranges) {
+        // (a captured graph with parallel branches: the call stays one chain of launches under capture -- the form again, serial)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) M = ansx_enc::choose_model_form(W.G, *W.a, W.K, c->num_cus, true);
+        else if ((rc = pipeline_prepare(c, M.nranges))) return rc;
+    }
+    const u32 range_blocks = M.range_blocks, nranges = M.nranges;
     // k_candidates: the chain counts its launches will use (a full range and the last, shorter one)
-    const u32 last_blocks = nranges ? NB - (nranges - 1) * range_blocks : NB;
-    const u32 chain_set = (1u << cand_chains(c, M, range_blocks)) | (1u << cand_chains(c, M, last_blocks));
-    for (u32 nch = 1; nch <= 2; nch++)
-        if ((chain_set & (1u << nch)) && cand_lds(M, nch) > 48 * 1024 && (rc = raise_lds(c, cand_kernel(W.a->nt, nch), cand_lds(M, nch)))) return rc;
-    if (M.fin_lds > 48 * 1024 && (rc = raise_lds(c, fin_kernel(c, NSP, W.a->nt).kern, M.fin_lds))) return rc;
+    const ansx_enc::Launch cand[2] = { ansx_enc::cand_launch(M, range_blocks), ansx_enc::cand_launch(M, nranges ? NB - (nranges - 1) * range_blocks : NB) };
+    for (int nch = 1; nch <= 2; nch++) {
+        const ansx_enc::Launch& L = cand[0].variant == nch ? cand[0] : cand[1];
+        if (L.variant == nch && L.raise && (rc = raise_lds(c, cand_kernel(W.a->nt, nch), L.lds))) return rc;
+    }
+    if (M.fin.raise && (rc = raise_lds(c, fin_kernel(M), M.fin.lds))) return rc;
 
     W.max_logM = 16;
     W.max_ns = W.a->ns_cap;
@@ -1139,69 +948,71 @@ int model_fast(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
 // Phase 4, the exact form's prelude writers (K3; they also fill the container's parse hints).  Their LDS arrays are as
 // long as the call's largest alphabet (known here on the discovery path, assumed = the hint on the optimistic one), not
 // as its slot count: workgroups per CU.
-int write_preludes(ansx_ctx* c, EncodeWs& W, const ModelShape& M)
+int write_preludes(ansx_ctx* c, EncodeWs& W, const PreludeForm& F)
 {
+    using namespace ansx_enc;
     const ansx_geo& g = W.P->g;
-    const u32 NB = g.nblocks, NSP = W.P->NSP;
+    const u32 NSP = W.P->NSP;
     hipStream_t s = W.s;
     const ansx_enc_entry* table = (const ansx_enc_entry*)c->table.p;
     const u32* tab32 = (const u32*)c->tab32.p;
     u8* scratch = (u8*)c->scratch.p;
-    if (!M.always16 && (W.max_logM > 16 || c->dbg.table16_fixup))  // mixed call: a frame above 2^16 sends every block to the integer-state encoder
-        LAUNCH(c, "k_table16_from32", k_table16_from32, NB, 256, 0, s, g, NSP, (const ansx_blk*)W.blk, tab32, (ansx_enc_entry*)c->table.p);
-    const u32 pre_cap = std::min<u32>(NSP, std::max<u32>(64u, ((W.a->ns_cap ? W.a->ns_cap : W.max_ns) + 7u) & ~7u));
-    if (NSP <= 1024 && W.max_logM <= 16) {
-        LAUNCH(c, "k_write_prelude", (k_write_prelude<4>), NB, 256, (size_t)pre_cap * 12 + 64, s, g, NSP, table, tab32, W.hist, W.blk, scratch,
-            W.scr_stride, W.mostfreq, W.hints, pre_cap, W.geo);
-    } else if (NSP <= 4096 && W.max_logM <= 16) {
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_write_prelude<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                      (int)((size_t)pre_cap * 12 + 64)));
-        LAUNCH(c, "k_write_prelude", (k_write_prelude<16>), NB, 256, (size_t)pre_cap * 12 + 64, s, g, NSP, table, tab32, W.hist, W.blk, scratch,
-            W.scr_stride, W.mostfreq, W.hints, pre_cap, W.geo);
-    } else if (W.a->int_sparse) {
-        // the reference's prelude over the VALUE range, from the rank-space model (16-byte entries: always16) and the block's values
-        // LDS from the call's most distinct values per block (max_ns: read back by model_exact, the discovery path) unless a block's
-        // code outgrew three words per value on the first attempt
-        const bool full = W.a->sp_full_lds;
-        const u32 sp_cap = full ? (u32)ANSX_SP_MAX_SIGMA : std::min<u32>(ANSX_SP_MAX_SIGMA, (std::max<u32>(W.max_ns, 64u) + 63u) & ~63u);
-        const u32 sp_bits = full ? (u32)ANSX_SP_MAX_SIGMA
-                                 : (c->dbg.test_sp_bits ? c->dbg.test_sp_bits : std::min<u32>(ANSX_SP_MAX_SIGMA, 2u * sp_cap + 64u));
-        const size_t sp_lds = (size_t)(sp_cap + sp_bits + 2) * 4;
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_int_sparse_prelude, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp_lds));
-        LAUNCH(c, "k_int_sparse_prelude", k_int_sparse_prelude, NB, 256, sp_lds, s, g, NSP, (const u32*)c->pa_alpha.p, table, W.blk, scratch,
-            W.scr_stride, sp_cap, sp_bits, (u32)(4 * NSP), W.gflags);
-    } else {
-        size_t gen_lds = (size_t)pre_cap * 8 + 64;
-        u32* g_work = nullptr;
-        if (gen_lds > 150 * 1024) {  // f = 6, 7: the writer's two arrays in HBM
-            int rc;
-            if ((rc = ensure(c, c->pre_work, (size_t)NB * (2 * (size_t)pre_cap + 16) * 4))) return rc;
-            g_work = (u32*)c->pre_work.p;
-            gen_lds = 64;
-        } else if (gen_lds > 48 * 1024)
-            HIPCHK(c, hipFuncSetAttribute((const void*)k_write_prelude<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds));
-        LAUNCH(c, "k_write_prelude", (k_write_prelude<0>), NB, 256, gen_lds, s, g, NSP, table, tab32, W.hist, W.blk, scratch,
-            W.scr_stride, W.mostfreq, W.hints, pre_cap, (const uint2*)nullptr, g_work);
+    const Launch& L = F.w;
+    int rc;
+    if (F.table16_first)
+        LAUNCH(c, "k_table16_from32", k_table16_from32, g.nblocks, 256, 0, s, g, NSP, (const ansx_blk*)W.blk, tab32, (ansx_enc_entry*)c->table.p);
+    if (L.variant == PRE_RANK_SPACE) {
+        if (L.raise && (rc = raise_lds(c, k_int_sparse_prelude, L.lds))) return rc;
+        LAUNCH(c, "k_int_sparse_prelude", k_int_sparse_prelude, L.grid, L.threads, L.lds, s, g, NSP, (const u32*)c->pa_alpha.p, table, W.blk,
+            scratch, W.scr_stride, F.sp_cap, F.sp_bits, (u32)(4 * NSP), W.gflags);
+        return ANSX_OK;
     }
+    const bool generic = L.variant == PRE_GENERIC || L.variant == PRE_GENERIC_HBM;  // (no tabulated tree nodes; HBM: f = 6, 7)
+    u32* g_work = nullptr;
+    if (L.variant == PRE_GENERIC_HBM) {
+        if ((rc = ensure(c, c->pre_work, (size_t)g.nblocks * (2 * (size_t)F.pre_cap + 16) * 4))) return rc;
+        g_work = (u32*)c->pre_work.p;
+    }
+    const auto kern = L.variant == PRE_W4 ? k_write_prelude<4> : (L.variant == PRE_W16 ? k_write_prelude<16> : k_write_prelude<0>);
+    if (L.raise && (rc = raise_lds(c, kern, L.lds))) return rc;
+    LAUNCH(c, "k_write_prelude", kern, L.grid, L.threads, L.lds, s, g, NSP, table, tab32, W.hist, W.blk, scratch, W.scr_stride, W.mostfreq,
+        W.hints, F.pre_cap, generic ? (const uint2*)nullptr : W.geo, g_work);
     return ANSX_OK;
 }
 
-// Phase 5, the encoder (K5).  The f64-state forms keep their per-wave tables in LDS when they fit (sized from the
-// largest alphabet / frame of the model phase); their emitted-byte stores go through a buffer descriptor spanning the
-// wave's 16 scratch slots: 31-bit offsets.
-int launch_encoder(ansx_ctx* c, EncodeWs& W)
+// Phase 5, the encoder (K5) in the form E names.  The f64-state forms keep their per-wave tables in LDS when they fit
+// (sized from the largest alphabet / frame of the model phase); their emitted-byte stores go through a buffer
+// descriptor spanning the wave's 16 scratch slots: 31-bit offsets.
+int launch_encoder(ansx_ctx* c, EncodeWs& W, const EncoderForm& E)
 {
+    using namespace ansx_enc;
     const Plan& P = *W.P;
-    const u32 NB = P.g.nblocks;
+    const ansx_geo& g = P.g;
+    hipStream_t s = W.s;
     u64* ck_state = P.plain ? nullptr : (u64*)(W.d_out + P.lay.ckstate_off);
     u32* ck_off = P.plain ? nullptr : (u32*)(W.d_out + P.lay.ckoff_off);
-    const bool f64_ok = W.max_logM <= 16 && W.scr_stride * 16 < 0x7FFFFF00ull && !c->dbg.table16_fixup;
-    if (f64_ok && !c->dbg.encode_gtab16)
-        return launch_f64_encoder(c, P.g, P.NSP, W.src, W.max_ns, W.blk, W.scr_stride, ck_state, ck_off, W.enc_sizes, W.enc_gsums, NB, W.s,
-            &W.out->used_pc);
-    LAUNCH(c, "k_encode_gtab", (k_encode<0>), ((size_t)NB * 4 + 63) / 64, 64, 0, W.s, W.src, P.g, P.NSP,
-        (const ansx_enc_entry*)c->table.p, (const u32*)c->tab32.p, 0u, W.blk, (u8*)c->scratch.p,
-        W.scr_stride, ck_state, ck_off, W.enc_sizes, W.enc_gsums);
+    const u32* tab32 = (const u32*)c->tab32.p;
+    u8* scratch = (u8*)c->scratch.p;
+    const bool pow2 = W.G.map_pow2;
+    int rc;
+    W.out->used_pc = false;  // (true below, once the pair kernel has taken blocks of this call)
+    if (E.pc.grid) {  // producer / consumer pairs
+        const auto kern = pow2 ? (E.S == 8 ? k_encode_pc<true, 8> : k_encode_pc<true, 4>) : (E.S == 8 ? k_encode_pc<false, 8> : k_encode_pc<false, 4>);
+        if ((rc = raise_lds(c, kern, E.pc.lds))) return rc;
+        LAUNCH(c, "k_encode", kern, E.pc.grid, E.pc.threads, E.pc.lds, s, W.src, g, P.NSP, tab32, W.max_ns, E.rowwords, W.blk, scratch,
+            W.scr_stride, ck_state, ck_off, W.enc_sizes, W.enc_gsums);
+        W.out->used_pc = true;
+    }
+    // one wave per 16 blocks (MODE 1: waves of one workgroup run the main loop in step, a barrier per super-batch), or
+    // the integer-state encoder on the 16-byte entries
+    const Launch& L = E.rest;
+    if (!L.grid) return ANSX_OK;
+    const bool int_state = L.variant == ENC_INT_STATE, mode1 = L.variant == ENC_MODE1;
+    const auto kern = int_state ? k_encode<0> : (mode1 ? (pow2 ? k_encode<1, true> : k_encode<1, false>) : k_encode<2>);
+    if (L.raise && (rc = raise_lds(c, kern, L.lds))) return rc;
+    LAUNCH(c, E.first ? "k_encode_rest" : (mode1 ? "k_encode" : "k_encode_gtab"), kern, L.grid, L.threads, L.lds, s, W.src, g, P.NSP,
+        int_state ? (const ansx_enc_entry*)c->table.p : (const ansx_enc_entry*)nullptr, tab32, E.lds_stride, W.blk, scratch, W.scr_stride,
+        ck_state, ck_off, W.enc_sizes, W.enc_gsums, E.first);
     return ANSX_OK;
 }
 
@@ -1261,13 +1072,14 @@ int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_
     int rc;
     if ((rc = encode_begin(c, W))) return rc;                                  // workspace, k_begin_encode
     if ((rc = encode_remap(c, W))) return rc;                                  // rfold / compaction / rank-space ANSint
-    const ModelShape M = model_shape(c, W);
+    // (profile mode: the event pairs of LAUNCH would time overlapped kernels -- serial there)
+    const ModelForm M = ansx_enc::choose_model_form(W.G, a, W.K, c->num_cus, c->profile);
     out->used_fast = M.fast;
     if ((rc = model_prepare(c, W, M))) return rc;
     if ((rc = M.fast ? model_fast(c, W, M) : model_exact(c, W, M))) return rc;  // K1 .. K4
     if (!P.plain && !g.ckw && g.nckf != 0 && W.max_logM > c->dbg.wide_at) return ANSX_RETRY_WIDE;  // (discovery path: known before anything is encoded)
-    if (!M.fast && (rc = write_preludes(c, W, M))) return rc;                  // (k_model_finish wrote them)
-    if ((rc = launch_encoder(c, W))) return rc;
+    if (!M.fast && (rc = write_preludes(c, W, ansx_enc::choose_prelude_form(W.G, a, W.K, M.always16, W.max_logM, W.max_ns)))) return rc;  // (k_model_finish wrote them)
+    if ((rc = launch_encoder(c, W, ansx_enc::choose_encoder_form(W.G, W.K, c->num_cus, W.max_logM, W.max_ns)))) return rc;
     if ((rc = encode_finish(c, W, out_bytes))) return rc;
     if (a.int_sparse && !a.sp_full_lds && (out->flags[ANSX_G_ERR] & (1u << ANSX_G_VIOL_BIT))) {
         // (the value-range prelude of some block needs more than two words per distinct value)
@@ -1327,18 +1139,18 @@ int encode_fast(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t c
     const EncodeAttempt& a, EncodeOutcome* out)
 {
     const ansx_model_lds ML = model_layout(a.ns_cap);
-    if (scratch_stride(P.g) * 16 >= 0x7FFFFF00ull || ML.total > 150 * 1024) return ANSX_RETRY_GENERAL;
+    if (ansx_enc::scratch_stride(enc_geo(P)) * 16 >= 0x7FFFFF00ull || ML.total > ansx_enc::LDS_BUDGET) return ANSX_RETRY_GENERAL;
     EncodeWs W = { &P, &a, out, d_in, d_out, cap, s };
     int rc;
     if ((rc = encode_begin(c, W))) return rc;
     if ((rc = encode_remap(c, W))) return rc;
     const auto kern = a.ns_cap <= 1024 ? k_model_fused<4> : k_model_fused<16>;
-    if (ML.total > 48 * 1024 && (rc = raise_lds(c, kern, ML.total))) return rc;
+    if (ML.total > ansx_enc::LDS_NO_ATTRIBUTE && (rc = raise_lds(c, kern, ML.total))) return rc;
     LAUNCH(c, "k_model_fused", kern, P.g.nblocks, 256, ML.total, s, W.src, P.g, P.NSP, ML, (const ansx_log2_ent*)c->log2lut.p, W.blk,
         (u32*)c->tab32.p, (u8*)c->scratch.p, W.scr_stride, W.mostfreq, W.gflags, 1u << 30, W.hints);
     W.max_logM = 16;
     W.max_ns = a.ns_cap;
-    if ((rc = launch_encoder(c, W))) return rc;
+    if ((rc = launch_encoder(c, W, ansx_enc::choose_encoder_form(W.G, W.K, c->num_cus, W.max_logM, W.max_ns)))) return rc;
     return encode_finish(c, W, out_bytes);
 }
 
@@ -1504,7 +1316,7 @@ int encode_dev_once(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size
     if (eligible) {
         hinted.ns_cap = std::min<u32>(P.NSP, std::max<u32>(64u, (hint + 7u) & ~7u));
         const auto rit = c->rf_hint.find(key);
-        if (P.g.kind == ANSX_RFOLD && rit != c->rf_hint.end()) hinted.rf_slots = rf_opt_slots(rit->second, fold_T(P.g.f));
+        if (P.g.kind == ANSX_RFOLD && rit != c->rf_hint.end()) hinted.rf_slots = ansx_enc::rf_opt_slots(rit->second, fold_T(P.g.f));
         if (P.g.pa && rit != c->rf_hint.end()) hinted.pa_distinct = rit->second;
         // candidates per block for the fast model path: one more than the largest index chosen so far, 4..8 lanes
         // (fewer than 4 would leave the wave's lanes to more blocks than its LDS rows); above 8 the exact path stays
@@ -2748,11 +2560,6 @@ struct EncBatchHints {
     }
 };
 
-// A list with this many full blocks amortises its own launches and read-back, and the ordinary path gives it the
-// encoder forms a pass cannot take (the buffer-view pipeline of k_encode<1>, k_encode_pc): the (C) criterion of
-// launch_f64_encoder.  Such a list goes through encode_dev into its place.
-#define ANSX_ENCB_LONG_BLOCKS 16u
-
 // geometries the batched path takes: the LDS-model codecs, ANSfold and ANSmsb also with compaction (whose blocks are at
 // most 16384 ints: make_plan); ANSint has none
 bool encode_batch_form(const ansx_geo& g)
@@ -2770,52 +2577,26 @@ int encode_batch_pass(ansx_ctx* c, const Plan& P0, const u32* d_in, const u64* o
     int rc;
     const u64 bi = P0.g.block_ints;
     const u32 nl = (u32)(l1 - l0);
-    // the plan, one upload from pinned memory: blocks | lists | the block ids by remap class of ANSrfold or the compaction
-    // layer; behind it on the device: maxima | results | block sums
+    // the plan (ansx_plan.h): its upload image in pinned memory, the results read back behind it
     const bool rf = P0.g.kind == ANSX_RFOLD, pa = P0.g.pa != 0;
-    const size_t o_l = sizeof(ansx_blk_in) * (size_t)NB, o_i = o_l + sizeof(ansx_encb_list) * ((size_t)nl + 1);
-    const size_t o_m = o_i + (rf || pa ? rup(4 * (size_t)NB, 16) : 0);
-    const size_t o_r = o_m + sizeof(ansx_encb_max) * (size_t)nl, o_s = o_r + sizeof(ansx_encb_res) * ((size_t)nl + 1);
-    const size_t plan_bytes = o_s + 8 * ((size_t)NB + 1);
-    const size_t res_bytes = sizeof(ansx_encb_res) * ((size_t)nl + 1);
-    if ((rc = ensure_pin(c, o_m + res_bytes))) return rc;
+    const EncPassLayout L = encb_layout(NB, nl, rf || pa);
+    const size_t o_l = L.o_l, o_i = L.o_i, o_m = L.o_m, o_r = L.o_r, o_s = L.o_s;
+    if ((rc = ensure_pin(c, o_m + sizeof(ansx_encb_res) * ((size_t)nl + 1)))) return rc;
     u8* hb = c->rng_pin;  // (nothing is pending on it: every call that uses it ends in a synchronisation)
-    ansx_blk_in* hblk = (ansx_blk_in*)hb;
-    ansx_encb_list* hl = (ansx_encb_list*)(hb + o_l);
-    u32 k = 0, longest = 0;
-    for (size_t i = l0; i < l1; i++) {
-        const u64 n = offsets[i + 1] - offsets[i];
-        hl[i - l0] = { n, k, 0 };
-        for (u64 at = 0; at < n; at += bi, k++) {
-            const u32 nb = (u32)std::min<u64>(bi, n - at);
-            hblk[k] = { offsets[i] + at, nb, (u32)(i - l0) };
-            longest = std::max(longest, nb);
-        }
-    }
-    hl[nl] = { 0, k, 0 };
-    if (k != NB) return ANSX_ERR_ARG;  // (cannot happen: the caller counted the same blocks)
-    u32 ncls[3] = { 0, 0, 0 };
-    if (rf || pa) {  // the remap classes (ansx_rfold.h, ansx_pa.h), by block length: counted, then every class's ids in block order
-        const u32 T = fold_T(P0.g.f);
-        auto cls = [&](u32 nb) -> u32 {
-            if (pa) return nb <= ANSX_PA_SMALL_INTS ? PA_CLS_SMALL : PA_CLS_LARGE;
-            return nb < T ? RF_CLS_IDENTITY : (nb <= ANSX_RF_SMALL_INTS ? RF_CLS_SMALL : RF_CLS_LARGE);
-        };
-        for (u32 b = 0; b < NB; b++) ncls[cls(hblk[b].n)]++;
-        u32* hid = (u32*)(hb + o_i);
-        u32 at[3] = { 0, ncls[0], ncls[0] + ncls[1] };
-        for (u32 b = 0; b < NB; b++) hid[at[cls(hblk[b].n)]++] = b;
-    }
-    if ((rc = ensure(c, c->enb_plan, plan_bytes))) return rc;
+    EncPassTables T;
+    if (!encb_pass_tables(offsets, l0, l1, bi, NB, pa ? ENCB_REMAP_PA : (rf ? ENCB_REMAP_RFOLD : ENCB_REMAP_NONE), fold_T(P0.g.f), L, hb, &T))
+        return ANSX_ERR_ARG;  // (cannot happen: the caller counted the same blocks)
+    const u32 longest = T.longest;
+    if ((rc = ensure(c, c->enb_plan, L.plan_bytes))) return rc;
     u8* dp = (u8*)c->enb_plan.p;
     HIPCHK(c, hipMemcpyAsync(dp, hb, o_m, hipMemcpyHostToDevice, s));
 
     // the pass's plan: any n that makes make_plan lay out exactly NB blocks (the table says how long each is); its
     // restart points and hints go to the work area in the wide form, whatever the lists will need
-    // g.n is not the pass's ints.  What reads it: the block-range pipeline's size rule (pipeline_plan: a pass of 8192 and
+    // g.n is not the pass's ints.  What reads it: the block-range pipeline's size rule (choose_model_form: a pass of 8192 and
     // more blocks forks its model kernels as a list of that many full blocks would -- the ranges are block ranges, so
     // that holds for short blocks too; not measured on a pass); k_encode's wg_sync and buffer view and k_encode_pc,
-    // all switched off by g.bin.  model_shape sizes by block_ints and the hints, not by g.n.
+    // all switched off by g.bin.  choose_model_form sizes by block_ints and the hints, not by g.n.
     Plan P = P0;
     P.g.n = (u64)(NB - 1) * bi + 1;
     P.g.nblocks = NB;
@@ -2828,12 +2609,12 @@ int encode_batch_pass(ansx_ctx* c, const Plan& P0, const u32* d_in, const u64* o
     u8* wc = (u8*)c->enb_wc.p;
     const size_t stream_bound = block_bound(P.g.kind, P.g.f, P.g.block_ints, pa) + 16;
     EncBatchPass B;
-    B.hblk = hblk;
+    B.hblk = (const ansx_blk_in*)hb;
     B.longest = longest;
     B.in_base = offsets[l0];
     B.in_ints = offsets[l1] - offsets[l0];
     B.remap_ids = rf || pa ? (const u32*)(dp + o_i) : nullptr;
-    memcpy(B.remap_ncls, ncls, sizeof(ncls));
+    memcpy(B.remap_ncls, T.ncls, sizeof(T.ncls));
     B.A.bin = P.g.bin;
     B.A.lists = (const ansx_encb_list*)(dp + o_l);
     B.A.mx = (ansx_encb_max*)(dp + o_m);
@@ -2871,46 +2652,36 @@ int encode_batch(ansx_ctx* c, const Plan& P0, const ansx_opts* opts, const u32* 
     int rc;
     EncBatchHints slot(c);
     const u64 bi = P0.g.block_ints;
-    const u32 PB = c->dbg.batch_pass_blocks ? c->dbg.batch_pass_blocks : ANSX_BATCH_PASS_DEFAULT;
+    const u32 PB = batch_pass_blocks(c);
     const bool batched = encode_batch_form(P0.g);
     std::vector<u64> oo(count + 1), ob(count);
     u64 cur = 0;
     if (bad_index) *bad_index = count;
-    size_t i = 0;
-    while (i < count) {
-        const u64 n = offsets[i + 1] - offsets[i];
-        const u64 nbk = (n + bi - 1) / bi;
-        if (!batched || nbk > PB || n / bi >= ANSX_ENCB_LONG_BLOCKS) {
-            // the ordinary path, straight into the list's place
-            Plan P;
-            if (make_plan((int)P0.g.kind, (int)P0.g.f, (size_t)n, opts, &P)) return ANSX_ERR_ARG;  // (checked by the entry point)
-            size_t bytes = 0;
-            if (cur > cap) return ANSX_ERR_CAPACITY;
-            if ((rc = encode_dev(c, P, d_in + offsets[i], d_out + cur, cap - cur, &bytes, s))) {
-                if (bad_index && rc != ANSX_ERR_HIP) *bad_index = i;
+    for (size_t i = 0; i < count;) {
+        const EncStep st = encb_step(offsets, count, i, bi, PB, batched);
+        i = st.l1;
+        if (st.NB) {
+            u64 pass_bytes = 0;
+            if ((rc = encode_batch_pass(c, P0, d_in, offsets, st.l0, st.l1, st.NB, d_out, cap, cur, oo.data(), ob.data(), &pass_bytes, s)))
                 return rc;
-            }
-            const u64 r16 = rup(bytes, 16);
-            if (cur + r16 > cap) return ANSX_ERR_CAPACITY;
-            if (r16 != bytes) HIPCHK(c, hipMemsetAsync(d_out + cur + bytes, 0, r16 - bytes, s));
-            oo[i] = cur, ob[i] = bytes;
-            cur += r16;
-            i++;
+            cur += pass_bytes;
             continue;
         }
-        size_t j = i;
-        u64 blocks = 0;
-        while (j < count) {
-            const u64 nj = (offsets[j + 1] - offsets[j] + bi - 1) / bi;
-            if (blocks + nj > PB || (offsets[j + 1] - offsets[j]) / bi >= ANSX_ENCB_LONG_BLOCKS) break;
-            blocks += nj;
-            j++;
-        }
-        u64 pass_bytes = 0;
-        if ((rc = encode_batch_pass(c, P0, d_in, offsets, i, j, (u32)blocks, d_out, cap, cur, oo.data(), ob.data(), &pass_bytes, s)))
+        // the ordinary path, straight into the list's place
+        const size_t l = st.l0;
+        Plan P;
+        if (make_plan((int)P0.g.kind, (int)P0.g.f, (size_t)(offsets[l + 1] - offsets[l]), opts, &P)) return ANSX_ERR_ARG;  // (checked by the entry point)
+        size_t bytes = 0;
+        if (cur > cap) return ANSX_ERR_CAPACITY;
+        if ((rc = encode_dev(c, P, d_in + offsets[l], d_out + cur, cap - cur, &bytes, s))) {
+            if (bad_index && rc != ANSX_ERR_HIP) *bad_index = l;
             return rc;
-        cur += pass_bytes;
-        i = j;
+        }
+        const u64 r16 = rup(bytes, 16);
+        if (cur + r16 > cap) return ANSX_ERR_CAPACITY;
+        if (r16 != bytes) HIPCHK(c, hipMemsetAsync(d_out + cur + bytes, 0, r16 - bytes, s));
+        oo[l] = cur, ob[l] = bytes;
+        cur += r16;
     }
     HIPCHK(c, hipStreamSynchronize(s));  // (the padding behind a list of the ordinary path)
     oo[count] = cur;
@@ -3110,11 +2881,11 @@ template <class F> int run_call(ansx_ctx* c, void* stream, const F& body)
     }
 }
 
-// the call of a batch entry with nothing to do
-int empty_batch(uint64_t* offsets, uint64_t* total_ints)
+// the call of a batch entry with nothing to do (T: the entry's type of a total)
+template <class T> int empty_batch(uint64_t* offsets, T* total)
 {
     if (offsets) offsets[0] = 0;
-    if (total_ints) *total_ints = 0;
+    if (total) *total = 0;
     return ANSX_OK;
 }
 
@@ -3130,7 +2901,16 @@ int decode_batch_args(const ansx_ctx* c, const uint8_t* const* d_ins, const size
     return ANSX_OK;
 }
 
-// ... and those of ansx_encode_batch_dev
+// ... those of the single-list encode entries (ansx_encode_dev and the two gaps variants), with the list's plan
+int encode_args(const ansx_ctx* c, int kind, int f, const uint32_t* d_in, size_t n, const uint8_t* d_out, const size_t* out_bytes,
+    const ansx_opts* opts, Plan* P)
+{
+    if (!c || !d_in || !d_out || !out_bytes) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_in & 3u)) return ANSX_ERR_ARG;
+    return make_plan(kind, f, n, opts, P);
+}
+
+// ... and those of the batch encode entries (ansx_encode_batch_dev and the two gaps variants)
 int encode_batch_args(const ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,
     const uint8_t* d_out, size_t* bad_index, const ansx_opts* opts, Plan* P0)
 {
@@ -3438,14 +3218,10 @@ size_t ansx_bound(int kind, int f, size_t n, const ansx_opts* opts)
 int ansx_encode_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, size_t n, uint8_t* d_out,
     size_t cap, size_t* out_bytes, const ansx_opts* opts, void* stream)
 {
-    if (!c || !d_in || !d_out || !out_bytes) return ANSX_ERR_ARG;
-    if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_in & 3u)) return ANSX_ERR_ARG;
     Plan P;
-    int rc = make_plan(kind, f, n, opts, &P);
+    int rc = encode_args(c, kind, f, d_in, n, d_out, out_bytes, opts, &P);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return encode_dev(c, P, d_in, d_out, cap, out_bytes, s);
+    return run_call(c, stream, [&](hipStream_t s) { return encode_dev(c, P, d_in, d_out, cap, out_bytes, s); });
 }
 
 int ansx_decode_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes,
@@ -3611,35 +3387,14 @@ int ansx_encode_batch_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, co
     const ansx_opts* opts, void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c || count > 0xFFFFFFFFull) return ANSX_ERR_ARG;
-    if (count > 0 && (!d_in || !offsets || !d_out)) return ANSX_ERR_ARG;
-    if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_in & 3u)) return ANSX_ERR_ARG;
-    if (opts && opts->block_ints == ANSX_SINGLE_STREAM) return ANSX_ERR_ARG;  // (a batch yields containers)
     Plan P0;
-    int rc = make_plan(kind, f, 1, opts, &P0);  // kind, fidelity and options, as for any list
+    int rc = encode_batch_args(c, kind, f, d_in, offsets, count, d_out, bad_index, opts, &P0);
     if (rc) return rc;
-    for (size_t i = 0; i < count; i++) {
-        Plan P;
-        if (offsets[i + 1] < offsets[i]) return ANSX_ERR_ARG;
-        if (offsets[i + 1] == offsets[i] || make_plan(kind, f, (size_t)(offsets[i + 1] - offsets[i]), opts, &P)) {
-            if (bad_index) *bad_index = i;  // an empty list (or one no container can hold), as ansx_encode_dev refuses n == 0
-            return ANSX_ERR_ARG;
-        }
-    }
-    if (count == 0) {
-        if (out_offsets) out_offsets[0] = 0;
-        if (total_bytes) *total_bytes = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    try {
-        return encode_batch(c, P0, opts, d_in, (const u64*)offsets, count, d_out, out_capacity, (u64*)out_offsets,
-            (u64*)out_bytes, total_bytes, bad_index, s);
-    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge batch)
-        c->last_hip = (int)hipErrorOutOfMemory;
-        return ANSX_ERR_HIP;
-    }
+    if (count == 0) return empty_batch(out_offsets, total_bytes);
+    return run_call(c, stream, [&](hipStream_t s) {
+        return encode_batch(c, P0, opts, d_in, (const u64*)offsets, count, d_out, out_capacity, (u64*)out_offsets, (u64*)out_bytes,
+            total_bytes, bad_index, s);
+    });
 }
 
 int ansx_decode_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, uint32_t* d_out, size_t n,
@@ -3688,40 +3443,36 @@ int ansx_decode_batch_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* cons
 int ansx_encode_gaps_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, size_t n, uint8_t* d_out, size_t cap,
     size_t* out_bytes, const ansx_opts* opts, void* stream)
 {
-    if (!c || !d_in || !d_out || !out_bytes) return ANSX_ERR_ARG;
-    if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_in & 3u)) return ANSX_ERR_ARG;
     Plan P;
-    int rc = make_plan(kind, f, n, opts, &P);
+    int rc = encode_args(c, kind, f, d_in, n, d_out, out_bytes, opts, &P);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const u64 offs[2] = { 0, (u64)n };
-    const u32* gaps = nullptr;
-    if ((rc = gaps_run(c, d_in, (u64)n, offs, 1, &gaps, nullptr, s))) return rc;
-    return encode_dev(c, P, gaps, d_out, cap, out_bytes, s);
+    return run_call(c, stream, [&](hipStream_t s) -> int {
+        const u64 offs[2] = { 0, (u64)n };
+        const u32* gaps = nullptr;
+        if ((rc = gaps_run(c, d_in, (u64)n, offs, 1, &gaps, nullptr, s))) return rc;
+        return encode_dev(c, P, gaps, d_out, cap, out_bytes, s);
+    });
 }
 
 int ansx_encode_gaps_bases_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, size_t n, uint8_t* d_out, size_t cap,
     size_t* out_bytes, const ansx_opts* opts, uint32_t* d_bases, size_t bases_capacity, size_t* nbases, void* stream)
 {
-    if (!c || !d_in || !d_out || !out_bytes || !nbases) return ANSX_ERR_ARG;
-    if (((uintptr_t)d_out & 15u) || ((uintptr_t)d_in & 3u) || ((uintptr_t)d_bases & 3u)) return ANSX_ERR_ARG;
-    if (!d_bases && bases_capacity > 0) return ANSX_ERR_ARG;
+    if (!nbases || ((uintptr_t)d_bases & 3u) || (!d_bases && bases_capacity > 0)) return ANSX_ERR_ARG;
     if (opts && opts->block_ints == ANSX_SINGLE_STREAM) return ANSX_ERR_ARG;  // (a stream has no blocks)
     Plan P;
-    int rc = make_plan(kind, f, n, opts, &P);
+    int rc = encode_args(c, kind, f, d_in, n, d_out, out_bytes, opts, &P);
     if (rc) return rc;
     *nbases = (size_t)P.g.nblocks + 1;
     if (bases_capacity < (size_t)P.g.nblocks + 1) return ANSX_ERR_CAPACITY;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const u64 offs[2] = { 0, (u64)n };
-    const u32* gaps = nullptr;
-    if ((rc = gaps_run(c, d_in, (u64)n, offs, 1, &gaps, nullptr, s))) return rc;
-    // the ids do not decrease: the id in front of a block is the sum of every gap in front of it
-    LAUNCH(c, "k_rs_ids_bases", k_rs_ids_bases, P.g.nblocks / ANSX_RS_NT + 1, ANSX_RS_NT, 0, s, d_in, (u64)n, P.g.block_ints,
-        P.g.nblocks, d_bases);
-    return encode_dev(c, P, gaps, d_out, cap, out_bytes, s);
+    return run_call(c, stream, [&](hipStream_t s) -> int {
+        const u64 offs[2] = { 0, (u64)n };
+        const u32* gaps = nullptr;
+        if ((rc = gaps_run(c, d_in, (u64)n, offs, 1, &gaps, nullptr, s))) return rc;
+        // the ids do not decrease: the id in front of a block is the sum of every gap in front of it
+        LAUNCH(c, "k_rs_ids_bases", k_rs_ids_bases, P.g.nblocks / ANSX_RS_NT + 1, ANSX_RS_NT, 0, s, d_in, (u64)n, P.g.block_ints,
+            P.g.nblocks, d_bases);
+        return encode_dev(c, P, gaps, d_out, cap, out_bytes, s);
+    });
 }
 
 int ansx_encode_batch_gaps_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,
@@ -3732,14 +3483,8 @@ int ansx_encode_batch_gaps_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_i
     Plan P0;
     int rc = encode_batch_args(c, kind, f, d_in, offsets, count, d_out, bad_index, opts, &P0);
     if (rc) return rc;
-    if (count == 0) {
-        if (out_offsets) out_offsets[0] = 0;
-        if (total_bytes) *total_bytes = 0;
-        return ANSX_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    try {
+    if (count == 0) return empty_batch(out_offsets, total_bytes);
+    return run_call(c, stream, [&](hipStream_t s) -> int {
         const u32* gaps = nullptr;
         if ((rc = gaps_run(c, d_in + offsets[0], offsets[count] - offsets[0], (const u64*)offsets, count, &gaps, bad_index, s)))
             return rc;
@@ -3747,10 +3492,7 @@ int ansx_encode_batch_gaps_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_i
         for (size_t i = 0; i <= count; i++) off[i] = offsets[i] - offsets[0];
         return encode_batch(c, P0, opts, gaps, off.data(), count, d_out, out_capacity, (u64*)out_offsets, (u64*)out_bytes,
             total_bytes, bad_index, s);
-    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge batch)
-        c->last_hip = (int)hipErrorOutOfMemory;
-        return ANSX_ERR_HIP;
-    }
+    });
 }
 
 int ansx_encode_batch_gaps_bases_dev(ansx_ctx* c, int kind, int f, const uint32_t* d_in, const uint64_t* offsets, size_t count,
@@ -3762,26 +3504,25 @@ int ansx_encode_batch_gaps_bases_dev(ansx_ctx* c, int kind, int f, const uint32_
     int rc = encode_batch_args(c, kind, f, d_in, offsets, count, d_out, bad_index, opts, &P0);
     if (rc) return rc;
     if (((uintptr_t)d_bases & 3u) || (!d_bases && bases_capacity > 0)) return ANSX_ERR_ARG;
-    try {
-        // where every list's bases start: a pure function of the offsets and the options
-        const u64 bi = P0.g.block_ints;
-        std::vector<u64> boff(count + 1);
-        u64 nbases = 0;
+    // where every list's bases start: a pure function of the offsets and the options
+    // (a size query allocates nothing: the caller's array, if any, takes them)
+    const u64 bi = P0.g.block_ints;
+    auto bases_offsets = [&](u64* boff) {
+        u64 nb = 0;
         for (size_t i = 0; i < count; i++) {
-            boff[i] = nbases;
-            nbases += (offsets[i + 1] - offsets[i] + bi - 1) / bi + 1;
+            if (boff) boff[i] = nb;
+            nb += (offsets[i + 1] - offsets[i] + bi - 1) / bi + 1;
         }
-        boff[count] = nbases;
-        if (base_offsets) memcpy(base_offsets, boff.data(), 8 * (count + 1));
-        if (total_bases) *total_bases = (size_t)nbases;
-        if (bases_capacity < nbases) return ANSX_ERR_CAPACITY;
-        if (count == 0) {
-            if (out_offsets) out_offsets[0] = 0;
-            if (total_bytes) *total_bytes = 0;
-            return ANSX_OK;
-        }
-        HIPCHK(c, hipSetDevice(c->device));
-        hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+        if (boff) boff[count] = nb;
+        return nb;
+    };
+    const u64 nbases = bases_offsets((u64*)base_offsets);
+    if (total_bases) *total_bases = (size_t)nbases;
+    if (bases_capacity < nbases) return ANSX_ERR_CAPACITY;
+    if (count == 0) return empty_batch(out_offsets, total_bytes);
+    return run_call(c, stream, [&](hipStream_t s) -> int {
+        std::vector<u64> boff(count + 1);
+        bases_offsets(boff.data());
         const u32* gaps = nullptr;
         GapsSide G = { boff.data(), nullptr, nullptr };
         if ((rc = gaps_run(c, d_in + offsets[0], offsets[count] - offsets[0], (const u64*)offsets, count, &gaps, bad_index, s, &G)))
@@ -3793,10 +3534,7 @@ int ansx_encode_batch_gaps_bases_dev(ansx_ctx* c, int kind, int f, const uint32_
         for (size_t i = 0; i <= count; i++) off[i] = offsets[i] - offsets[0];
         return encode_batch(c, P0, opts, gaps, off.data(), count, d_out, out_capacity, (u64*)out_offsets, (u64*)out_bytes,
             total_bytes, bad_index, s);
-    } catch (const std::bad_alloc&) {  // (the host's arrays of a huge batch)
-        c->last_hip = (int)hipErrorOutOfMemory;
-        return ANSX_ERR_HIP;
-    }
+    });
 }
 
 int ansx_encode(ansx_ctx* c, int kind, int f, const uint32_t* in, size_t n, uint8_t* out, size_t cap,

@@ -355,14 +355,6 @@ ANSX_HD bool index_entry_ok(const ansx_geo& g, u32 b, u64 a, u64 e)
     return !bad;
 }
 
-// One block of an encode batch pass: its ints and where they start in the caller's input.  Blocks of many lists share
-// one work list there; a list may start at any int, so nothing about the alignment of `off` is promised.
-struct ansx_blk_in {
-    u64 off;   // first int in the input
-    u32 n;     // ints
-    u32 list;  // the list of the pass it belongs to
-};
-
 ANSX_HD u32 geo_block_n(const ansx_geo& g, u32 b)
 {
     if (g.bout) return g.bout[b].n;

@@ -12,19 +12,8 @@
 
 #include "ansx_kernels.h"
 
-struct ansx_encb_list {  // list i of a pass: blocks [fb, next list's fb); the entry behind the last list closes it
-    u64 n;               // its ints
-    u32 fb;
-    u32 pad_;
-};
-
-struct ansx_encb_max {  // maxima over a list's own blocks (the container header's), and the form of its restart points
-    u32 logM, ns, sigma, wide;
-};
-
-struct ansx_encb_res {  // where container i went (relative to the caller's buffer) and its exact size
-    u64 off, bytes;
-};
+// (ansx_encb_list, ansx_encb_max and ansx_encb_res, the tables of a pass's lists, are in ansx_plan_types.h: the host lays
+// them out in ansx_plan.h)
 
 struct ansx_encb_args {
     const ansx_blk_in* bin;       // the pass's blocks

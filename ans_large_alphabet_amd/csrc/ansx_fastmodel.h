@@ -29,8 +29,7 @@
 #endif
 
 #define ANSX_FAST_GUARD 1e-9
-#define ANSX_CAND_SL 64u         // symbols per LDS stage (NT = 5: 12.5 KB per wave, three 4-wave workgroups per CU)
-#define ANSX_CAND_ROW (ANSX_CAND_SL + 1u)  // entries per block row (odd: rows start in different banks)
+// (ANSX_CAND_SL, ANSX_CAND_ROW and ANSX_CAND_WAVES, the LDS stage of k_candidates: ansx_plan_types.h)
 #define ANSX_CAND_MAXBPW 16u     // blocks per wave (NT >= 4 lanes per block)
 #define ANSX_FIN_LUT 512u        // entries of the log2 table k_model_finish keeps in LDS (larger values: the table in HBM)
 
@@ -63,7 +62,6 @@ ANSX_HD u64 srank_chunk(u32 NSP, u32 NT, u32 b, u32 batch, u32 t) { return ((u64
 // workgroup, each with its own LDS slice and never synchronised (single-wave workgroups pile up unevenly on a CU's
 // SIMDs; waves of one workgroup land one per SIMD).
 // pairs: k_sort_entropy's packed output.  attMeta: {ok, maxS} per (block, t).
-#define ANSX_CAND_WAVES 4u
 template <u32 NT, u32 NCH>  // compile-time: every staging load of a stage must be in flight at once (with a run-time trip count
                    // hipcc gives each load its own basic block and a full wait: 7 us per stage instead of one round trip)
 __global__ __launch_bounds__(64 * ANSX_CAND_WAVES) void k_candidates(ansx_geo g, u32 NSP,

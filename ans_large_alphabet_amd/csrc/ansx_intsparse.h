@@ -28,7 +28,7 @@
 
 #include "ansx_kernels.h"
 
-#define ANSX_SP_MAX_SIGMA 16384u      // distinct values per block (ranks are symbols of the 16384-slot ANSint model)
+// (ANSX_SP_MAX_SIGMA, the distinct values a block may have: ansx_plan_types.h)
 #define ANSX_SP_VALUE_LIMIT (1u << 30)  // values below 2^30: the code's universe M + max_sym + 2 stays below 2^31
 
 // number of values <= t among vals[lo .. hi) (ascending)

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void k_begin_encode(ansx_zero4 Z)
 // K1: folded-symbol histogram.  One workgroup per chunk of a block; LDS bins; coalesced 16 B
 // loads.  Replaces the first pass of ans_fold_encode<f>::create (ans_fold.hpp:74-78).
 // ------------------------------------------------------------------------------------------
-#define ANSX_HCOPY_PAD 8u
+// (ANSX_HCOPY_PAD: ansx_plan_types.h)
 // 16-byte load of data that is read once per pass (global_load_dwordx4 ... nt): measured on MI355X with
 // tests/tools/ubench_read.hip, a 1 GiB read-only stream reaches 6.9 TB/s this way against 6.0-6.5 TB/s plain.
 typedef u32 ansx_u32x4 __attribute__((ext_vector_type(4)));
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void k_fold_hist(const u32* __restrict__ in, a
 // Entropy: p*log2(p) terms lane-parallel, summed serially in index order so that the rounding
 // matches a scalar left-to-right accumulation.
 // ------------------------------------------------------------------------------------------
-#define ANSX_VMAX 256u
+// (ANSX_VMAX: ansx_plan_types.h)
 #define ANSX_MASKV 256u
 
 // Single-wave workgroups: LDS operations of one wave execute in order, so a "barrier" only has
@@ -1697,7 +1697,7 @@ template <int CTRL> __device__ __forceinline__ u32 quad_add_dpp(u32 v)
     return v + (u32)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
 }
 
-#define ANSX_ENC_HOT 577  // MODE 2: words per LDS row = 1152 u16 running sums (1151 hot symbols) + a zero sentinel pair (odd stride; 16 rows = 36.9 KB per wave)
+// (ANSX_ENC_HOT, MODE 2's words per LDS row: ansx_plan_types.h)
 #define ANSX_ENC_U 8    // table entries per lane fetched ahead
 #define ANSX_ENC_XB 32  // inputs per lane fetched ahead (one super-batch)
 

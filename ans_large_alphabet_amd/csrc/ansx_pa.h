@@ -21,9 +21,8 @@
 
 #include <type_traits>
 
-#define ANSX_PA_SLOTS 20480u  // hash set capacity: >= 1.25 x 16384 values per block
+// (ANSX_PA_SLOTS, the hash set's capacity, and ANSX_PA_MAX_BLOCK are in ansx_plan_types.h)
 #define ANSX_PA_EMPTY 0xFFFFFFFFu
-#define ANSX_PA_MAX_BLOCK 16384u
 
 __device__ __forceinline__ u32 pa_slot(u32 v, u32 slots) { return (u32)(((u64)(v * 2654435761u) * slots) >> 32); }
 
@@ -251,7 +250,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 // shuffle away), a value that differs from its predecessor is a distinct one, a wave scan of their counts gives sigma and
 // packs them, ascending, into the wave's 4 KB of LDS; the ranks are lower bounds over that array, as in the workgroup
 // kernel.  Nothing here can overflow, so there is no optimistic size and no repeat.
-#define ANSX_PA_SMALL_INTS 1024u
+// (ANSX_PA_SMALL_INTS, the longest block of the class: ansx_plan_types.h)
 __global__ __launch_bounds__(256) void k_pa_remap_small(const u32* __restrict__ in, ansx_geo g,
     const u32* __restrict__ ids, u32 count, u32* __restrict__ mapped, u32* __restrict__ alpha_sum,
     ansx_blk* __restrict__ blk, u32* __restrict__ gflags, u32 value_limit)

@@ -1,6 +1,7 @@
 // ansx -- the host's plans of the random-access calls ("Host side of the random-access calls"):
 // which blocks a set of ranges touches, where every range's ints lie in the work list those blocks decode to, and the
-// tables a pass over blocks of many containers takes.  Pure host arithmetic: no context, no stream, no device pointer
+// tables a pass over blocks of many containers takes; and the steps and pass tables of a batch of lists to encode
+// (ansx_encode_batch_dev).  Pure host arithmetic: no context, no stream, no device pointer
 // (addresses travel as integers), so it builds with a plain host compiler and is tested on the CPU
 // (tests/tools/plan_check.cpp).  The plain structs the kernels read these plans through are in ansx_plan_types.h,
 // which the kernel headers include.
@@ -331,6 +332,102 @@ __attribute__((noinline)) static u64 batch_pass_plan(const std::vector<BatchSrc>
     P->close(bbound);
     pstart->push_back((u32)npieces);
     return npieces;
+}
+
+// ------------------------------------------------------------------------------- batches of lists to encode
+// ansx_encode_batch_dev cuts its batch, in order and at list boundaries, into steps: a list alone through the ordinary
+// encode, or lists [l0, l1) as one pass of NB blocks.
+
+// A list with this many full blocks amortises its own launches and read-back, and the ordinary path gives it the
+// encoder forms a pass cannot take (the buffer-view pipeline of k_encode<1>, k_encode_pc): the (C) criterion of
+// choose_encoder_form.  Such a list goes alone.
+#define ANSX_ENCB_LONG_BLOCKS 16u
+
+struct EncStep {
+    size_t l0, l1;
+    u32 NB;  // 0: list l0 alone (l1 = l0 + 1)
+};
+// The step that starts at list i (< count) of lists offsets[0 .. count] in blocks of bi ints, for passes of at most PB
+// blocks.  batched: the geometry has a batched form at all.  Alone goes every list of more than PB blocks or of
+// ANSX_ENCB_LONG_BLOCKS full blocks, and a pass ends in front of one.
+static inline EncStep encb_step(const u64* offsets, size_t count, size_t i, u64 bi, u32 PB, bool batched)
+{
+    const u64 n = offsets[i + 1] - offsets[i];
+    if (!batched || (n + bi - 1) / bi > PB || n / bi >= ANSX_ENCB_LONG_BLOCKS) return { i, i + 1, 0 };
+    size_t j = i;
+    u64 blocks = 0;
+    while (j < count) {
+        const u64 nj = (offsets[j + 1] - offsets[j] + bi - 1) / bi;
+        if (blocks + nj > PB || (offsets[j + 1] - offsets[j]) / bi >= ANSX_ENCB_LONG_BLOCKS) break;
+        blocks += nj;
+        j++;
+    }
+    return { i, j, (u32)blocks };
+}
+
+// Remap classes of a pass's blocks, by block length: ANSrfold's (ansx_rfold.h; below T ints a block cannot have T
+// distinct values) and the compaction layer's (ansx_pa.h)
+enum { RF_CLS_IDENTITY = 0, RF_CLS_SMALL = 1, RF_CLS_LARGE = 2 };
+enum { PA_CLS_SMALL = 0, PA_CLS_LARGE = 1 };
+enum { ENCB_REMAP_NONE, ENCB_REMAP_RFOLD, ENCB_REMAP_PA };
+static inline u32 encb_class(int remap, u32 T, u32 nb)
+{
+    if (remap == ENCB_REMAP_PA) return nb <= ANSX_PA_SMALL_INTS ? PA_CLS_SMALL : PA_CLS_LARGE;
+    return nb < T ? RF_CLS_IDENTITY : (nb <= ANSX_RF_SMALL_INTS ? RF_CLS_SMALL : RF_CLS_LARGE);
+}
+
+// The plan of a pass of NB blocks in nl lists, one upload from pinned memory: blocks | lists | the block ids by remap
+// class (where the form has a remap front) -- bytes [0, o_m); behind it on the device: maxima | results | block sums.
+// Every section starts on a 16-byte boundary.
+struct EncPassLayout {
+    size_t o_l, o_i, o_m, o_r, o_s, plan_bytes;
+};
+static inline EncPassLayout encb_layout(u32 NB, u32 nl, bool ids)
+{
+    EncPassLayout L;
+    L.o_l = sizeof(ansx_blk_in) * (size_t)NB;
+    L.o_i = L.o_l + sizeof(ansx_encb_list) * ((size_t)nl + 1);
+    L.o_m = L.o_i + (ids ? rup(4 * (size_t)NB, 16) : 0);
+    L.o_r = L.o_m + sizeof(ansx_encb_max) * (size_t)nl;
+    L.o_s = L.o_r + sizeof(ansx_encb_res) * ((size_t)nl + 1);
+    L.plan_bytes = L.o_s + 8 * ((size_t)NB + 1);
+    return L;
+}
+
+// The tables of the pass over lists [l0, l1), written into the upload image hb (L.o_m bytes): the work list (every
+// list's ints in blocks of bi, in order), the list table and -- remap != ENCB_REMAP_NONE -- the block ids by remap
+// class, every class's in block order, with the classes' counts in ncls.  -> false if the lists do not have NB blocks.
+struct EncPassTables {
+    u32 longest;  // ints of the pass's longest block
+    u32 ncls[3];
+};
+static inline bool encb_pass_tables(const u64* offsets, size_t l0, size_t l1, u64 bi, u32 NB, int remap, u32 T, const EncPassLayout& L,
+    u8* hb, EncPassTables* out)
+{
+    ansx_blk_in* hblk = (ansx_blk_in*)hb;
+    ansx_encb_list* hl = (ansx_encb_list*)(hb + L.o_l);
+    u32 k = 0, longest = 0;
+    for (size_t i = l0; i < l1; i++) {
+        const u64 n = offsets[i + 1] - offsets[i];
+        hl[i - l0] = { n, k, 0 };
+        for (u64 at = 0; at < n; at += bi, k++) {
+            if (k == NB) return false;  // (the image has room for NB blocks)
+            const u32 nb = (u32)std::min<u64>(bi, n - at);
+            hblk[k] = { offsets[i] + at, nb, (u32)(i - l0) };
+            longest = std::max(longest, nb);
+        }
+    }
+    hl[l1 - l0] = { 0, k, 0 };
+    if (k != NB) return false;
+    out->longest = longest;
+    out->ncls[0] = out->ncls[1] = out->ncls[2] = 0;
+    if (remap != ENCB_REMAP_NONE) {  // counted, then every class's ids in block order
+        for (u32 b = 0; b < NB; b++) out->ncls[encb_class(remap, T, hblk[b].n)]++;
+        u32* hid = (u32*)(hb + L.o_i);
+        u32 at[3] = { 0, out->ncls[0], out->ncls[0] + out->ncls[1] };
+        for (u32 b = 0; b < NB; b++) hid[at[encb_class(remap, T, hblk[b].n)]++] = b;
+    }
+    return true;
 }
 
 }  // namespace ansx_plan

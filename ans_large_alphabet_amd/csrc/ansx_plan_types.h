@@ -59,6 +59,61 @@ struct ansx_piece {  // ints [src, src + count) of the pass's work list go to [d
 #define ANSX_SRING_BYTES 256                       // the speculative small ring, see dec_segments_ring_small
 #define ANSX_SRING_STRIDE (ANSX_SRING_BYTES + 16)
 
+// LDS geometry and size rules of the encode kernels, shared with the host's choice of the encode forms
+// (ansx_encode_form.h) and with the pass tables of ansx_encode_batch_dev (ansx_plan.h).
+#define ANSX_HCOPY_PAD 8u          // k_fold_hist: pad between its four histogram copies
+#define ANSX_VMAX 256u             // k_sort_entropy: frequencies below this are binned, the larger ones ranked separately
+#define ANSX_CAND_SL 64u           // k_candidates: symbols per LDS stage (NT = 5: 12.5 KB per wave, three 4-wave workgroups per CU)
+#define ANSX_CAND_ROW (ANSX_CAND_SL + 1u)  // entries per block row (odd: rows start in different banks)
+#define ANSX_CAND_WAVES 4u         // ... and its waves per workgroup, each with its own LDS slice
+#define ANSX_ENC_HOT 577  // MODE 2: words per LDS row = 1152 u16 running sums (1151 hot symbols) + a zero sentinel pair (odd stride; 16 rows = 36.9 KB per wave)
+#define ANSX_RF_SLOTS 20480u       // k_rfold_remap_hash: >= 1.25 x 16384 values per block
+#define ANSX_RF_SMALL_INTS 1024u   // k_rfold_remap_small: the longest block of its class ...
+#define ANSX_RF_SMALL_SLOTS 2048u  // ... 2 x the most values such a block has
+// per wave: the (count, value) pairs of the block's distinct values | keys | counts, then ranks (two u16 per word)
+#define ANSX_RF_SMALL_LDS (8u * ANSX_RF_SMALL_INTS + 6u * ANSX_RF_SMALL_SLOTS)
+#define ANSX_PA_SLOTS 20480u       // k_pa_remap: hash set capacity, >= 1.25 x 16384 values per block
+#define ANSX_PA_MAX_BLOCK 16384u   // the longest block the compaction layer takes
+#define ANSX_PA_SMALL_INTS 1024u   // k_pa_remap_small: the longest block of its class
+#define ANSX_SP_MAX_SIGMA 16384u   // rank-space ANSint: distinct values per block (ranks are symbols of the 16384-slot ANSint model)
+
+// Block-range pipeline of the model kernels (model_fast; measurements: DESIGN.md section 6): the values of
+// ANSX_MODEL_PIPELINE besides a range count, and the size rule.
+#define ANSX_PIPE_NEVER (-1)
+#define ANSX_PIPE_ALWAYS (-2)
+#define ANSX_PIPE_MAX_RANGES 64
+// A call pipelines by itself from ANSX_PIPE_MIN_BLOCKS blocks and ANSX_PIPE_MIN_INTS ints on, in ANSX_PIPE_RANGES ranges.
+// Measured on MI355X (encode call, serial -> pipelined): 16384 blocks of 16 Ki ints ANSfold-1 1.226 -> 1.173 ms with 2, 3 or
+// 5 ranges, 1.213 with 6, 1.261 with 8 (k_sort_entropy and k_candidates have latency floors that every range pays again);
+// 8192 blocks break even for ANSfold-1 and gain for ANSfold-5 (2.91 -> 2.70 ms); 4096 blocks and fewer lose 0.003-0.07 ms
+// to the cross-stream waits.  Two ranges were never slower than the serial form on any list of that size, three lost
+// their gain on uniform data.
+#define ANSX_PIPE_RANGES 2u
+#define ANSX_PIPE_MIN_BLOCKS 8192u
+#define ANSX_PIPE_MIN_INTS ((u64)1 << 27)
+
+// One block of an encode batch pass: its ints and where they start in the caller's input.  Blocks of many lists share
+// one work list there; a list may start at any int, so nothing about the alignment of `off` is promised.
+struct ansx_blk_in {
+    u64 off;   // first int in the input
+    u32 n;     // ints
+    u32 list;  // the list of the pass it belongs to
+};
+
+struct ansx_encb_list {  // list i of a pass: blocks [fb, next list's fb); the entry behind the last list closes it
+    u64 n;               // its ints
+    u32 fb;
+    u32 pad_;
+};
+
+struct ansx_encb_max {  // maxima over a list's own blocks (the container header's), and the form of its restart points
+    u32 logM, ns, sigma, wide;
+};
+
+struct ansx_encb_res {  // where container i went (relative to the caller's buffer) and its exact size
+    u64 off, bytes;
+};
+
 struct ansx_brs_src {  // a source of a pass, beside its ansx_batch_src: the caller's bases of that container
     u64 bases;         // device address of its nblocks + 1 entries (4-byte aligned)
     u32 nblocks;

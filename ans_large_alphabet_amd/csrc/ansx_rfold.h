@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void k_rfold_remap(const u32* __restrict__ in,
 // ans_reorder_fold.hpp:79-85); ranks are written back into the table and every input value is
 // remapped with one probe.
 // ------------------------------------------------------------------------------------------
-#define ANSX_RF_SLOTS 20480u  // >= 1.25 x 16384 values per block
+// (ANSX_RF_SLOTS, the table's slots -- >= 1.25 x 16384 values per block -- is in ansx_plan_types.h)
 #define ANSX_RF_EMPTY 0xFFFFFFFFu
 
 __device__ __forceinline__ u32 rf_slot(u32 v, u32 slots) { return (u32)(((u64)(v * 2654435761u) * slots) >> 32); }
@@ -520,10 +520,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 //   T <= nb <= ANSX_RF_SMALL_INTS k_rfold_remap_small:    one wave per block
 //   longer                        k_rfold_remap_hash / k_rfold_remap_hash2 over the class's ids
 // ------------------------------------------------------------------------------------------
-#define ANSX_RF_SMALL_INTS 1024u
-#define ANSX_RF_SMALL_SLOTS 2048u  // 2 x the most values a block of the class has
-// per wave: the (count, value) pairs of the block's distinct values | keys | counts, then ranks (two u16 per word)
-#define ANSX_RF_SMALL_LDS (8u * ANSX_RF_SMALL_INTS + 6u * ANSX_RF_SMALL_SLOTS)
+// (ANSX_RF_SMALL_INTS, ANSX_RF_SMALL_SLOTS and ANSX_RF_SMALL_LDS, a wave's carve, are in ansx_plan_types.h)
 
 // ans_reorder_fold.hpp:94-97 for blocks that cannot have T distinct values: the ints as they are, flag 0.  One wave per
 // block, grid stride over the class.

@@ -2,6 +2,8 @@
 // identity data: int j of block b of a list is b * bi + j, of container r the pair (r, b * bi + j).  Nothing here
 // restates a planner: a plan is run the way the kernels run it -- work list, pieces, chunks, the decoders' table -- and
 // what comes out is compared with the slices the ranges name; beside that, the invariants the device side relies on.
+// The steps and pass tables of ansx_encode_batch_dev are checked the same way: the steps partition the lists, and a pass's
+// work list is walked block by block against the lists it came from.
 // Built with -fsanitize=address,undefined and run by tests/test_range_plans_cpu.py; exit status 0 and "ok" on success.
 #include "../../ans_large_alphabet_amd/csrc/ansx_plan.h"
 
@@ -458,8 +460,97 @@ static void batches(u64 bi)
     (void)what;
 }
 
+// ------------------------------------------------------------------------------- batches of lists to encode
+// Batches of 0..40 lists with lengths around every threshold (T: below it ANSrfold's remap is the identity; 1024: the
+// small classes; the block; ANSX_ENCB_LONG_BLOCKS blocks), cut for passes of PB blocks.
+static void encode_batches(u64 bi, u32 T)
+{
+    const char* what = "encode batch";
+    const u64 lengths[] = { 1, T - 1, T, 1024, 1025, bi - 1, bi, bi + 1, 15 * bi, 16 * bi, 40 * bi };
+    std::mt19937_64 rng(99 + bi + T);
+    for (const u32 PB : { 1u, 2u, 7u, 16384u })
+        for (size_t count = 0; count <= 40; count++)
+            for (int remap = ENCB_REMAP_NONE; remap <= ENCB_REMAP_PA; remap++) {
+                std::vector<u64> off(count + 1, 5);  // (the first list need not start at int 0)
+                for (size_t i = 0; i < count; i++) off[i + 1] = off[i] + lengths[count == 11 ? i % 11 : rng() % 11];
+                auto blocks_of = [&](size_t i) { return (off[i + 1] - off[i] + bi - 1) / bi; };
+                // the steps partition the lists in order
+                size_t at = 0;
+                while (at < count) {
+                    const EncStep st = encb_step(off.data(), count, at, bi, PB, true);
+                    CHECK(st.l0 == at && st.l1 > st.l0 && st.l1 <= count);
+                    at = st.l1;
+                    const bool first_alone = blocks_of(st.l0) > PB || (off[st.l0 + 1] - off[st.l0]) / bi >= ANSX_ENCB_LONG_BLOCKS;
+                    if (!st.NB) {  // alone: too long for a pass, or long enough to pay for itself
+                        CHECK(st.l1 == st.l0 + 1 && first_alone);
+                        continue;
+                    }
+                    CHECK(!first_alone && st.NB <= PB);
+                    u64 nb = 0;
+                    for (size_t i = st.l0; i < st.l1; i++) {
+                        nb += blocks_of(i);
+                        CHECK(blocks_of(i) <= PB && (off[i + 1] - off[i]) / bi < ANSX_ENCB_LONG_BLOCKS);
+                    }
+                    CHECK(nb == st.NB);
+                    // (the pass is full: the next list would not fit, or goes alone)
+                    if (st.l1 < count) CHECK(nb + blocks_of(st.l1) > PB || (off[st.l1 + 1] - off[st.l1]) / bi >= ANSX_ENCB_LONG_BLOCKS);
+                    // the layout: sections in order, 16-byte aligned, none overlapping; the upload is what the host fills
+                    const u32 nl = (u32)(st.l1 - st.l0);
+                    const EncPassLayout L = encb_layout(st.NB, nl, remap != ENCB_REMAP_NONE);
+                    const size_t sec[7] = { 0, L.o_l, L.o_i, L.o_m, L.o_r, L.o_s, L.plan_bytes };
+                    const size_t need[6] = { sizeof(ansx_blk_in) * st.NB, sizeof(ansx_encb_list) * (nl + 1), remap != ENCB_REMAP_NONE ? 4 * (size_t)st.NB : 0,
+                        sizeof(ansx_encb_max) * nl, sizeof(ansx_encb_res) * (nl + 1), 8 * ((size_t)st.NB + 1) };
+                    for (int k = 0; k < 6; k++) CHECK(sec[k] % 16 == 0 && sec[k] + need[k] <= sec[k + 1]);
+                    // the tables, written into an image of exactly the upload's size (the sanitizer sees any byte beyond it)
+                    std::vector<u8> image(L.o_m);
+                    EncPassTables Tb;
+                    CHECK(encb_pass_tables(off.data(), st.l0, st.l1, bi, st.NB, remap, T, L, image.data(), &Tb));
+                    CHECK(!encb_pass_tables(off.data(), st.l0, st.l1, bi, st.NB - 1, remap, T, L, image.data(), &Tb) || st.NB == 0);
+                    CHECK(encb_pass_tables(off.data(), st.l0, st.l1, bi, st.NB, remap, T, L, image.data(), &Tb));
+                    const ansx_blk_in* blk = (const ansx_blk_in*)image.data();
+                    const ansx_encb_list* lists = (const ansx_encb_list*)(image.data() + L.o_l);
+                    u32 k = 0, longest = 0;
+                    for (size_t i = st.l0; i < st.l1; i++) {  // every int of every list exactly once, in order
+                        CHECK(lists[i - st.l0].n == off[i + 1] - off[i] && lists[i - st.l0].fb == k);
+                        for (u64 pos = off[i]; pos < off[i + 1]; k++) {
+                            CHECK(k < st.NB && blk[k].off == pos && blk[k].list == i - st.l0 && blk[k].n >= 1 && blk[k].n <= bi);
+                            CHECK(blk[k].n == bi || pos + blk[k].n == off[i + 1]);
+                            pos += blk[k].n;
+                            longest = std::max(longest, blk[k].n);
+                        }
+                    }
+                    CHECK(k == st.NB && lists[nl].fb == st.NB && Tb.longest == longest);
+                    if (remap == ENCB_REMAP_NONE) {
+                        CHECK(Tb.ncls[0] + Tb.ncls[1] + Tb.ncls[2] == 0);
+                        continue;
+                    }
+                    // the class ids: a permutation of the blocks, grouped by class, in block order inside a class
+                    const u32* ids = (const u32*)(image.data() + L.o_i);
+                    CHECK(Tb.ncls[0] + Tb.ncls[1] + Tb.ncls[2] == st.NB && (remap != ENCB_REMAP_PA || Tb.ncls[2] == 0));
+                    std::vector<char> seen(st.NB, 0);
+                    u32 j = 0;
+                    for (u32 cls = 0; cls < 3; cls++)
+                        for (u32 e = 0; e < Tb.ncls[cls]; e++, j++) {
+                            const u32 b = ids[j];
+                            CHECK(b < st.NB && !seen[b] && (e == 0 || ids[j - 1] < b));
+                            seen[b] = 1;
+                            const u32 n = blk[b].n;
+                            const u32 want = remap == ENCB_REMAP_PA ? (n <= 1024 ? 0u : 1u) : (n < T ? 0u : (n <= 1024 ? 1u : 2u));
+                            CHECK(want == cls);
+                        }
+                }
+                // no batched form: every list alone
+                for (size_t i = 0; i < count; i++) {
+                    const EncStep st = encb_step(off.data(), count, i, bi, PB, false);
+                    CHECK(st.l0 == i && st.l1 == i + 1 && st.NB == 0);
+                }
+            }
+}
+
 int main()
 {
+    for (const u64 bi : { (u64)4096, (u64)16384 })
+        for (const u32 T : { 256u, 4096u }) encode_batches(bi, T);
     for (const u64 bi : { (u64)4, (u64)4096 }) {
         for (const u64 n : { (u64)1, bi, bi + 1, 3 * bi + 1 }) single_container(bi, n);
         batches(bi);
