@@ -33,6 +33,7 @@ EXPORTS = [
     "ansx_encode_batch_gaps_dev", "ansx_block_bases_dev", "ansx_encode_gaps_bases_dev", "ansx_decode_ranges_sums_dev",
     "ansx_decode_device_ranges_sums_dev", "ansx_next_geq_dev", "ansx_encode_batch_gaps_bases_dev",
     "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
+    "ansx_intersect_ids_dev", "ansx_intersect_dev",
 ]
 
 
@@ -174,6 +175,11 @@ def lib():
     L.ansx_next_geq_batch_dev.restype = C.c_int
     L.ansx_next_geq_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, sz, vp, vp,
                                           C.POINTER(C.c_uint64), C.POINTER(sz), C.POINTER(sz), vp]
+    # intersection: the members of a candidate array in one list; the ids common to several lists
+    L.ansx_intersect_ids_dev.restype = C.c_int
+    L.ansx_intersect_ids_dev.argtypes = [vp, C.c_int, C.c_int, vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, C.POINTER(C.c_uint64), vp]
+    L.ansx_intersect_dev.restype = C.c_int
+    L.ansx_intersect_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, sz, C.POINTER(C.c_uint64), C.POINTER(sz), vp]
     L.ansx_container_info.restype = C.c_int
     L.ansx_container_info.argtypes = [vp, sz, C.POINTER(ContainerHeader)]
     L.ansx_profile_enable.restype = C.c_int

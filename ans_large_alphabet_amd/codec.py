@@ -552,6 +552,57 @@ class _Codec:
             raise err
         return int(found.value)
 
+    # ---- intersection (include/ansx.h)
+    def intersect_ids_dev(self, in_ptr, in_bytes, bases_ptr, nbases, cand_ptr, ncand, out_ids_ptr, out_idx_ptr, out_pos_ptr,
+                          out_capacity, stream=None):
+        """Which of the ncand uint32 at cand_ptr (device, any order, repeats allowed) are docids of the container at
+        in_ptr: the members, in candidate order and back to back, go to the device arrays of out_capacity entries
+        out_ids_ptr (uint32: the value), out_idx_ptr (uint32: its index among the candidates) and out_pos_ptr (uint64:
+        its first position in the list); any may be None, not all.  Returns the number of members; more than
+        out_capacity raises AnsxError(ERR_CAPACITY) with .needed = that number and writes nothing.  ERR_FORMAT if the
+        bases of a block some candidate was sent to are not this container's; nothing is written then either."""
+        for name, v in (("ncand", ncand), ("in_bytes", in_bytes), ("nbases", nbases), ("out_capacity", out_capacity)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        found = C.c_uint64(0)
+        st = L.lib().ansx_intersect_ids_dev(self._ctx().handle, self.KIND, self.f, in_ptr, int(in_bytes), bases_ptr,
+                                            int(nbases), cand_ptr, int(ncand), out_ids_ptr, out_idx_ptr, out_pos_ptr,
+                                            int(out_capacity), C.byref(found), stream)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".intersect_ids_dev")
+            if st == L.ERR_CAPACITY:
+                err.needed = int(found.value)
+            raise err
+        return int(found.value)
+
+    def intersect_dev(self, in_ptrs, in_bytes, bases_ptrs, nbases, out_ids_ptr, out_capacity, stream=None):
+        """The docids common to the lists of the batch in_ptrs / in_bytes / bases_ptrs / nbases (as
+        decode_batch_ranges_sums_dev): those of the shortest list (of equal ones the first) that occur in every other
+        one, ascending, to the uint32 array of out_capacity entries at out_ids_ptr (device).  Returns their number; more
+        than out_capacity raises AnsxError(ERR_CAPACITY) with .needed = that number and writes nothing, so
+        out_ids_ptr=None, out_capacity=0 asks for the size.  An AnsxError carries .bad_container where the call set it
+        (None otherwise)."""
+        ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
+        if ptrs.size != sizes.size:
+            raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
+        bptrs, nb = self._batch_bases(ptrs, bases_ptrs, nbases)
+        nc = ptrs.size
+        found = C.c_uint64(0)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c = C.c_size_t(unset)
+        st = L.lib().ansx_intersect_dev(
+            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None,
+            bptrs.ctypes.data if nc else None, nb.ctypes.data if nc else None, nc, out_ids_ptr, int(out_capacity),
+            C.byref(found), C.byref(bad_c), stream)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".intersect_dev")
+            err.bad_container = err.container = int(bad_c.value) if bad_c.value != unset else None
+            if st == L.ERR_CAPACITY:
+                err.needed = int(found.value)
+            raise err
+        return int(found.value)
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

@@ -34,6 +34,7 @@
 #include "ansx_sums.h"
 #include "ansx_rangesums.h"
 #include "ansx_nextgeq.h"
+#include "ansx_intersect.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
@@ -96,6 +97,8 @@ struct PinPage {
             u32 caller_flag;  // 2048: the flag word of decode_dev's caller (sub_decode), read back by its epilogue
             u8 pad1[1024 - 4];
             u64 planner[8];  // 3072: the scalars of the device planner (decode_device_ranges)
+            u64 isect_total;  // 3136: the members an intersect step found, read back by the decode's epilogue
+            u32 isect_sflag;  // 3144: the flag word of the scan behind a whole-list decode to ids (decode_ids)
         };
         u8 part_hdr[63][64];                       // 64: ansx_merge_containers_dev, the headers of up to 63 parts
         u64 rank_sizes[2 * ANSX_MERGE_MAX_PARTS];  // 64: ansx_gather_containers, (bytes, slot_bytes) of every rank
@@ -121,6 +124,7 @@ struct ansx_ctx {
     DevBuf rng_dev;                       // ansx_decode_device_ranges_dev: the device planner's workspace
     DevBuf bat_hdr;                       // ansx_decode_batch_dev: input addresses and headers of the batch
     DevBuf enb_plan, enb_wc;              // ansx_encode_batch_dev: a pass's plan and results; its restart points and hints (work area)
+    DevBuf isect_ids;                     // ansx_intersect_dev: the driver's ids and the survivors of a step, two arrays of n_driver ints
     DevBuf sums_plan, sums_ints;          // running sums and gaps: flag word + list starts + tile aggregates and carries; the gaps of a call (4 bytes per int)
     u8* rng_pin = nullptr;                // ... and the pinned host image of rng_plan (an asynchronous upload from
     size_t rng_pin_cap = 0;               //     pageable memory is staged by the runtime: 0.666 -> 0.618 ms at 4096 ranges)
@@ -191,6 +195,7 @@ struct ansx_ctx {
         double fast_guard = ANSX_FAST_GUARD;  // ANSX_FAST_GUARD: relative guard band of the fast model path's stop rule (tests widen it)
         int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
         u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev, ansx_decode_batch_ranges_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
+        int intersect_form = 0;       // ANSX_INTERSECT_FORM: 0 by ANSX_ISECT_FULL_PER_BLOCK, 1 "selective", 2 "full" (tests and the bench tool force one)
         u32 range_sums_wg_max = 0;    // ANSX_RANGE_SUMS_WG_MAX: the largest block the one-kernel scan of the range sums takes (0 = ANSX_RS_WG_MAX; the bench tool measures both sides of the switch)
     } dbg;
 };
@@ -1794,7 +1799,8 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
 // on the device (the k_dr_* planner) -- and fills a RangeTail; range_tail prepares a sub-container of the touched blocks
 // only (sub_prepare), builds it with k_range_index + k_range_copy, and decodes it (sub_decode: decode_dev, no cached
 // header in or out) with the call's way out as the one epilogue: k_range_gather into the caller's buffer, the sums
-// scan in front of it, or the scan and k_ng_search (RangeOut).
+// scan in front of it, the scan and k_ng_search, or the scan, k_isect_match and the compaction of an intersect step
+// (RangeOut).
 
 // rng_pin holds at least `bytes` (its content is not kept)
 int ensure_pin(ansx_ctx* c, size_t bytes)
@@ -1910,7 +1916,38 @@ enum WayOutKind {
     OUT_GATHER,       // its ranges are copied to the caller's buffer
     OUT_SUMS_GATHER,  // it becomes running sums from the caller's block bases first, in place (DESIGN.md sections 3f, 3h)
     OUT_SUMS_SEARCH,  // ... and the targets are searched in them, in the gather's place (sections 3g, 3h)
+    OUT_SUMS_MATCH,   // ... or matched against them and the members compacted (section 3i)
 };
+
+// The workspace of an intersect step's match and compaction (ansx_intersect.h) over nc candidates, 16-byte aligned:
+// total u64[2] | tile counts u64[ntiles] | ballots u64[ceil(nc / 64)] | pos u64[nc] when positions are asked for.
+// 8 bytes per 64 candidates, 8 per tile and, with positions, 8 per candidate.
+struct IsectWork {
+    u64 *total, *counts, *ballots, *wpos;
+    u32 ntiles;
+    static size_t bytes(u64 nc, bool pos)
+    {
+        return 16 + 8 * (size_t)((nc + ANSX_ISECT_TILE - 1) / ANSX_ISECT_TILE) + 8 * (size_t)((nc + 63) / 64) + (pos ? 8 * (size_t)nc : 0);
+    }
+    IsectWork() : total(nullptr), counts(nullptr), ballots(nullptr), wpos(nullptr), ntiles(0) {}
+    IsectWork(u8* w, u64 nc, bool pos)
+    {
+        ntiles = (u32)((nc + ANSX_ISECT_TILE - 1) / ANSX_ISECT_TILE);
+        total = (u64*)w, counts = total + 2, ballots = counts + ntiles, wpos = pos ? ballots + (nc + 63) / 64 : nullptr;
+    }
+};
+
+// The outputs of an intersect step: device arrays of cap entries, any but not all of them null
+struct IsectOut {
+    u32 *ids, *idx;
+    u64* pos;
+    u64 cap;
+};
+
+// What both forms of the match end in, enqueued in the decode's epilogue behind k_isect_match / k_isect_match_full:
+// the scan of the tile counts, the compaction, and the total on its way home with the decode's final read-back.
+int isect_compact(ansx_ctx* c, const IsectWork& W, const u32* d_cand, u32 nc, const IsectOut& o, const u32* gflags,
+    const u32* dflags, hipStream_t s);
 
 // the largest block the one-kernel scan takes
 u64 range_sums_wg_max(const ansx_ctx* c)
@@ -1969,6 +2006,8 @@ struct RangeOut {
     u32* d_ids;
     const u64 *first, *offsets;
     const u32* count;
+    IsectOut isect;  // OUT_SUMS_MATCH: the targets are the candidates; d_pos, d_ids are not used
+    IsectWork iw;    // ... and its workspace, the device front's to fill in
 };
 
 // What both fronts hand to the tail, the plan on the device: the source container, its header and plan; tb[T] the
@@ -2013,6 +2052,12 @@ int range_tail(ansx_ctx* c, int kind, int f, const RangeTail& t, const RangeOut&
                 (const u32*)gflags, (const u32*)t.dflags);
             return ANSX_OK;
         }
+        if (out.kind == OUT_SUMS_MATCH) {
+            LAUNCH(c, "k_isect_match", k_isect_match, out.iw.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)sub.list, n_sub, bi,
+                out.d_targets, out.nt, out.first, out.count, out.offsets, t.R, out.iw.ballots, out.iw.counts, out.iw.wpos,
+                (const u32*)gflags, (const u32*)t.dflags);
+            return isect_compact(c, out.iw, out.d_targets, out.nt, out.isect, gflags, t.dflags, s);
+        }
         const u32 grid = (u32)std::min<u64>(t.npieces, 1u << 20);
         LAUNCH(c, "k_range_gather", k_range_gather, grid, 256, 0, s, (const u32*)sub.list, t.R, t.pstart, t.nr, (u32)t.npieces,
             out.d_out, (const u32*)gflags);
@@ -2051,14 +2096,14 @@ int decode_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes,
 // The front serves ansx_next_geq_dev too (OUT_SUMS_SEARCH; nranges targets): the ranges are then k_ng_locate's, one int
 // at the start of every target's block, made in front of the planner in workspace behind its own; the planner and its
 // read-back are the same, *total_ints is the number of targets found, and the tail searches instead of gathering.
-int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
-    const u32* d_count, size_t nranges, size_t cap, u64* d_offsets, u64* total_ints, RangeOut out, hipStream_t s)
+// An intersect step (OUT_SUMS_MATCH, section 3i) is that search with another way out, and its workspace behind.
+// device_ranges_from: the call behind the source's header, for a caller that has it already (t.d_in, t.H, t.P).
+int device_ranges_from(ansx_ctx* c, int kind, int f, RangeTail t, const u64* d_first, const u32* d_count, size_t nranges,
+    size_t cap, u64* d_offsets, u64* total_ints, RangeOut out, hipStream_t s)
 {
     int rc;
-    RangeTail t = { d_in };
-    if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &t.H, &t.P))) return rc;
     if (out.kind != OUT_GATHER && out.nbases != (size_t)t.P.g.nblocks + 1) return ANSX_ERR_ARG;
-    const bool search = out.kind == OUT_SUMS_SEARCH;
+    const bool match = out.kind == OUT_SUMS_MATCH, search = out.kind == OUT_SUMS_SEARCH || match;
     const u64 n = t.H.n, bi = t.P.g.block_ints, nr = nranges, nb = t.P.g.nblocks;
     u32 kb = 0;  // key bits of a block id
     while ((1ull << kb) < nb) kb++;
@@ -2070,9 +2115,11 @@ int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in
     const size_t o_sp = rup(o_ps + 4 * (nr + 1), 16), o_tb = o_sp + 16 * nr;
     // (ansx_next_geq_dev, behind tb: first u64[nr] | offsets u64[nr + 1] | count u32[nr])
     const size_t o_nf = rup(o_tb + 4 * nb, 16), o_no = o_nf + 8 * nr, o_nc = o_no + 8 * (nr + 1);
-    const size_t bytes = search ? o_nc + 4 * nr : o_tb + 4 * nb;
+    const size_t o_iw = rup(o_nc + 4 * nr, 16);  // (an intersect step, behind count: IsectWork)
+    const size_t bytes = match ? o_iw + IsectWork::bytes(nr, out.isect.pos != nullptr) : search ? o_nc + 4 * nr : o_tb + 4 * nb;
     if ((rc = ensure(c, c->rng_dev, bytes))) return rc;
     u8* w = (u8*)c->rng_dev.p;
+    if (match) out.iw = IsectWork(w + o_iw, nr, out.isect.pos != nullptr);
     if (search) {
         u64* nf = (u64*)(w + o_nf);
         u32* nc = (u32*)(w + o_nc);
@@ -2127,7 +2174,7 @@ int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in
     if (total_ints) *total_ints = total;
     if (total > cap) return ANSX_ERR_CAPACITY;
     if (total == 0) {
-        if (search) {  // (no target found and no tail: the outputs are filled here; the call returns with them written, as ever)
+        if (search && !match) {  // (no target found and no tail: the outputs are filled here; the call returns with them written, as ever)
             LAUNCH(c, "k_ng_none", k_ng_none, (u32)((nr + ANSX_NG_NT - 1) / ANSX_NG_NT), ANSX_NG_NT, 0, s, n, (u32)nr, out.d_pos,
                 out.d_ids);
             HIPCHK(c, hipStreamSynchronize(s));
@@ -2141,6 +2188,15 @@ int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in
     t.T = T, t.last_b = hs[ANSX_DR_LASTB1] - 1, t.dtb = tb, t.R = R, t.pstart = pstart, t.nr = (u32)nne, t.npieces = npieces;
     t.dflags = (u32*)&sc[ANSX_DR_FLAGS];
     return range_tail(c, kind, f, t, out, s);
+}
+
+int decode_device_ranges(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, const u64* d_first,
+    const u32* d_count, size_t nranges, size_t cap, u64* d_offsets, u64* total_ints, const RangeOut& out, hipStream_t s)
+{
+    int rc;
+    RangeTail t = { d_in };
+    if ((rc = range_source(c, kind, f, d_in, in_bytes, s, &t.H, &t.P))) return rc;
+    return device_ranges_from(c, kind, f, t, d_first, d_count, nranges, cap, d_offsets, total_ints, out, s);
 }
 
 // --------------------------------------------------------------------------------- batches of containers
@@ -2739,12 +2795,9 @@ int sums_finish(ansx_ctx* c, const SumsPlan& S, size_t* bad_index, hipStream_t s
     return ANSX_ERR_DOMAIN;
 }
 
-// d[offs[i] - offs[0] .. offs[i + 1] - offs[0]) -> its inclusive running sums, for every list, in place
-int sums_run(ansx_ctx* c, u32* d, u64 n, const u64* offs, size_t count, size_t* bad_index, hipStream_t s)
+// the scan's kernels behind sums_prepare, enqueued
+int sums_launch(ansx_ctx* c, u32* d, u64 n, size_t count, SumsPlan& S, hipStream_t s)
 {
-    int rc;
-    SumsPlan S;
-    if ((rc = sums_prepare(c, (uintptr_t)d, n, offs, count, s, &S))) return rc;
     u32* base = (u32*)((uintptr_t)d & ~(uintptr_t)15);
     if (S.ntiles > 1) {
         LAUNCH(c, "k_sums_reduce", k_sums_reduce, S.ntiles, ANSX_SS_NT, 0, s, (const u32*)base, S.head, n, S.offs, (u32)count, S.agg);
@@ -2756,6 +2809,16 @@ int sums_run(ansx_ctx* c, u32* d, u64 n, const u64* offs, size_t count, size_t* 
     }
     LAUNCH(c, "k_sums_apply", k_sums_apply, S.ntiles, ANSX_SS_NT, 0, s, base, S.head, n, S.offs, (u32)count, (const u64*)S.agg,
         (const u64*)S.carry, S.flag);
+    return ANSX_OK;
+}
+
+// d[offs[i] - offs[0] .. offs[i + 1] - offs[0]) -> its inclusive running sums, for every list, in place
+int sums_run(ansx_ctx* c, u32* d, u64 n, const u64* offs, size_t count, size_t* bad_index, hipStream_t s)
+{
+    int rc;
+    SumsPlan S;
+    if ((rc = sums_prepare(c, (uintptr_t)d, n, offs, count, s, &S))) return rc;
+    if ((rc = sums_launch(c, d, n, count, S, s))) return rc;
     return sums_finish(c, S, bad_index, s);
 }
 
@@ -2822,6 +2885,159 @@ int block_bases(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, u
     DecodeOpts O;
     O.speculate = O.remember = false, O.epilogue = &epilogue;
     return decode_dev(c, P, d_in, in_bytes, list, s, O);
+}
+
+// --------------------------------------------------------------------------------- intersection
+// ansx_intersect_ids_dev / ansx_intersect_dev (ansx_intersect.h).  A step asks which of nc
+// candidates in device memory are ids of one list and writes the members back to back, in one of two forms:
+//   selective  ansx_next_geq_dev's path (device_ranges_from) with OUT_SUMS_MATCH as the way out: k_ng_locate, the
+//              planner, the decode of the touched blocks, range_sums_scan, k_isect_match.  Workspace: next_geq's plus
+//              IsectWork.  Host waits: the planner's read-back and the decode's final one, which brings the total too
+//              -- none over ansx_next_geq_dev.
+//   full       the whole list decoded into rng_list with no trace in the context (decode_ids), the whole-list scan
+//              and k_isect_match_full in the decode's epilogue.  Workspace: 4 bytes per int of the list, the scan's
+//              16 bytes per tile of 4096 ints, IsectWork.  Host waits: decode_dev's two (header, final read-back).
+// Both end in isect_compact.  The caller has read the header (one more wait per call of ansx_intersect_ids_dev, none per
+// step of ansx_intersect_dev, whose headers come in one round trip).  Full when nc >= ANSX_ISECT_FULL_PER_BLOCK * nblocks:
+// the measured crossing of the two forms on 4096 blocks of 16384 ints, at 1.2 candidates per block (DESIGN.md section 3i,
+// profiles/intersect_bench.json).
+#define ANSX_ISECT_FULL_PER_BLOCK 1u
+
+int isect_compact(ansx_ctx* c, const IsectWork& W, const u32* d_cand, u32 nc, const IsectOut& o, const u32* gflags,
+    const u32* dflags, hipStream_t s)
+{
+    LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
+    LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, d_cand, nc, (const u64*)W.ballots,
+        (const u64*)W.counts, (const u64*)W.total, o.cap, (const u64*)W.wpos, o.ids, o.idx, o.pos, gflags, dflags);
+    HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
+    return ANSX_OK;
+}
+
+// The container of plan P decoded whole into dst (16-byte aligned, room for 4 n + 64 bytes) as ids -- no remembered
+// header in or out -- with the whole-list scan of section 3e and then `extra` (given the decode's flags and the scan's
+// flag word, which has a zero word behind it) as the decode's epilogue.  ANSX_ERR_DOMAIN: the sum left 32 bits.
+template <class Extra> int decode_ids(ansx_ctx* c, const Plan& P, const u8* d_in, size_t in_bytes, u32* dst, u64 n,
+    const Extra& extra, hipStream_t s)
+{
+    int rc;
+    SumsPlan S;
+    const u64 offs[2] = { 0, n };
+    if ((rc = sums_prepare(c, (uintptr_t)dst, n, offs, 1, s, &S))) return rc;
+    u32* hflag = &c->pin->isect_sflag;
+    *hflag = ANSX_SS_NONE;
+    const std::function<int(const u32*)> epilogue = [&](const u32* gflags) -> int {
+        if ((rc = sums_launch(c, dst, n, 1, S, s))) return rc;
+        if ((rc = extra((u32*)gflags, (const u32*)S.flag))) return rc;
+        HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
+        return ANSX_OK;
+    };
+    DecodeOpts O;
+    O.speculate = O.remember = false, O.epilogue = &epilogue;
+    if ((rc = decode_dev(c, P, d_in, in_bytes, dst, s, O))) return rc;
+    return *hflag == ANSX_SS_NONE ? ANSX_OK : ANSX_ERR_DOMAIN;
+}
+
+// One step.  src: the list's container, header and plan (range_source, or batch_headers and container_plan).
+// *total: the members, on ANSX_OK and on ANSX_ERR_CAPACITY (more than o.cap: nothing is written).
+int isect_step(ansx_ctx* c, int kind, int f, const RangeTail& src, size_t in_bytes, const u32* d_bases, size_t nbases,
+    const u32* d_cand, u32 nc, const IsectOut& o, u64* total, hipStream_t s)
+{
+    int rc;
+    const u64 n = src.H.n, bi = src.P.g.block_ints;
+    const u32 nb = src.P.g.nblocks;
+    *total = 0;
+    if (nbases != (size_t)nb + 1) return ANSX_ERR_ARG;
+    if (n == 0) return ANSX_OK;  // (an empty list has no member)
+    c->pin->isect_total = 0;
+    const bool full = c->dbg.intersect_form ? c->dbg.intersect_form == 2 : nc >= (u64)ANSX_ISECT_FULL_PER_BLOCK * nb;
+    if (!full) {
+        RangeOut out = { OUT_SUMS_MATCH, nullptr, d_bases, nbases, d_cand, nc };
+        out.isect = o;
+        u64 found = 0;  // (the candidates at or below the last id; none: no tail has run)
+        if ((rc = device_ranges_from(c, kind, f, src, nullptr, nullptr, nc, nc, nullptr, &found, out, s))) return rc;
+        if (found == 0) return ANSX_OK;
+    } else {
+        if ((rc = ensure(c, c->rng_list, 4 * (size_t)n + 64))) return rc;
+        if ((rc = ensure(c, c->rng_dev, IsectWork::bytes(nc, o.pos != nullptr)))) return rc;
+        const IsectWork W((u8*)c->rng_dev.p, nc, o.pos != nullptr);
+        u32* list = (u32*)c->rng_list.p;
+        rc = decode_ids(c, src.P, src.d_in, in_bytes, list, n, [&](u32* gflags, const u32* sflag) -> int {
+            LAUNCH(c, "k_isect_match_full", k_isect_match_full, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)list, n, bi, d_bases,
+                nb, d_cand, nc, W.ballots, W.counts, W.wpos, gflags, sflag);
+            return isect_compact(c, W, d_cand, nc, o, gflags, sflag + 1, s);
+        }, s);
+        if (rc) return rc;
+    }
+    *total = c->pin->isect_total;
+    return *total > o.cap ? ANSX_ERR_CAPACITY : ANSX_OK;
+}
+
+// ansx_intersect_dev: every header in one round trip (batch_headers) -> the driver, the list of fewest ints, decoded
+// as ids into isect_ids (decode_ids) -> the other lists by ascending n, a step each, the survivors going back and
+// forth between the two halves of isect_ids, until a step leaves nothing -> one copy to the caller.  Workspace: the
+// step's own and 8 bytes per int of the driver.  Host waits: one for the headers, decode_dev's two for the driver,
+// two per step (selective: planner, final; full: header, final), one behind the copy.
+int intersect_lists(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u32* const* d_bases,
+    const size_t* nbases, size_t count, u32* d_out, size_t cap, u64* nfound, size_t* bad, hipStream_t s)
+{
+    int rc;
+    std::vector<BatchSrc> src;
+    size_t b = count;
+    if ((rc = batch_headers(c, kind, f, d_ins, in_bytes, nullptr, count, &src, &b, s))) {
+        if (rc == ANSX_ERR_FORMAT && bad) *bad = b;
+        return rc;
+    }
+    std::vector<u32> ord(count);  // ascending n; ties: the smaller batch index first
+    for (size_t i = 0; i < count; i++) ord[i] = (u32)i;
+    std::stable_sort(ord.begin(), ord.end(), [&](u32 x, u32 y) { return src[x].H.n < src[y].H.n; });
+    const u32 drv = ord[0];
+    for (size_t i = 0; i < count; i++)  // (the driver's bases are not read)
+        if (i != drv && (!d_bases[i] || nbases[i] != (size_t)src[i].nblocks + 1)) {
+            if (bad) *bad = i;
+            return ANSX_ERR_ARG;
+        }
+    auto source = [&](u32 i, RangeTail* t) -> int {
+        t->d_in = d_ins[i], t->H = src[i].H;
+        if (container_plan(t->H, (u32)kind, (u32)f, in_bytes[i], &t->P)) return ANSX_ERR_FORMAT;  // (cannot happen: batch_headers did)
+        t->P.g.payload_bytes = t->H.payload_bytes;
+        return ANSX_OK;
+    };
+    const u64 n0 = src[drv].H.n;
+    if (n0 > 0xFFFFFFFFull) return ANSX_ERR_ARG;  // (a step takes at most 2^32 - 1 candidates)
+    u64 m = n0;
+    u32* buf[2] = { nullptr, nullptr };
+    u32 cur = 0;
+    if (n0 > 0) {
+        const size_t half = rup((size_t)n0, 4) + 16;  // (ints: 16-byte aligned halves with the decoders' slack behind)
+        if ((rc = ensure(c, c->isect_ids, 8 * half))) return rc;
+        buf[0] = (u32*)c->isect_ids.p, buf[1] = buf[0] + half;
+        RangeTail t = {};
+        if ((rc = source(drv, &t))) return rc;
+        rc = decode_ids(c, t.P, t.d_in, in_bytes[drv], buf[0], n0, [](u32*, const u32*) -> int { return ANSX_OK; }, s);
+        if (rc) {
+            if ((rc == ANSX_ERR_DOMAIN || rc == ANSX_ERR_FORMAT) && bad) *bad = drv;
+            return rc;
+        }
+    }
+    for (size_t k = 1; k < count && m > 0; k++) {
+        const u32 i = ord[k];
+        RangeTail t = {};
+        if ((rc = source(i, &t))) return rc;
+        const IsectOut o = { buf[1 - cur], nullptr, nullptr, n0 };
+        u64 tot = 0;
+        if ((rc = isect_step(c, kind, f, t, in_bytes[i], d_bases[i], nbases[i], buf[cur], (u32)m, o, &tot, s))) {
+            if (rc == ANSX_ERR_FORMAT && bad) *bad = count;  // (found on the device)
+            if (rc == ANSX_ERR_DOMAIN && bad) *bad = i;
+            return rc;
+        }
+        m = tot, cur = 1 - cur;
+    }
+    if (nfound) *nfound = m;
+    if (m > cap) return ANSX_ERR_CAPACITY;
+    if (m == 0) return ANSX_OK;
+    HIPCHK(c, hipMemcpyAsync(d_out, buf[cur], 4 * (size_t)m, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ANSX_OK;
 }
 
 // The argument checks of the random-access entry points, one per argument shape: everything a call decides before the
@@ -2994,7 +3210,7 @@ int ansx_init(int device, ansx_ctx** out)
     }
     static const char* const names[] = { "ANSX_TEST_TABLE16_FIXUP", "ANSX_ENCODE_GTAB16", "ANSX_PARSE_GENERIC", "ANSX_PARSE_WIN", "ANSX_PARSE_FAST",
         "ANSX_DECODE_TABLE", "ANSX_NO_STREAM_LDS", "ANSX_DECODE_MODE", "ANSX_PARSE_STAGE_WORDS", "ANSX_MODEL_FUSED", "ANSX_MODEL_SYNC", "ANSX_NS_HINT", "ANSX_T_HINT", "ANSX_NO_FAST_MODEL", "ANSX_FAST_GUARD", "ANSX_CAND_CHAINS", "ANSX_NEAR_BAND", "ANSX_TEST_NEAR_FLIP", "ANSX_WIDE_RESTART", "ANSX_TEST_WIDE_AT",
-        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP", "ANSX_MODEL_CHAIN" };
+        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP", "ANSX_MODEL_CHAIN", "ANSX_INTERSECT_FORM" };
     for (const char* nm : names)
         if (const char* v = getenv(nm))
             if (ansx_debug_set(c, nm, v) != ANSX_OK)  // (a value the key does not take selects nothing: said, not passed over)
@@ -3116,6 +3332,11 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         else if (!strcmp(value, "old")) c->dbg.chain_old = true;
         else return ANSX_ERR_ARG;
     }
+    else if (!strcmp(name, "ANSX_INTERSECT_FORM")) {
+        const int w = debug_word(value, "selective", "full");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.intersect_form = w;
+    }
     else if (!strcmp(name, "ANSX_DECODE_PAIR_LDS")) c->dbg.pair_lds_limit = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_FORGET_HINTS")) {  // the next call of every geometry is a first call again (bench.py: first_call_ms)
         c->ns_hint.clear();
@@ -3167,7 +3388,7 @@ void ansx_destroy(ansx_ctx* c)
     DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->log2lut, &c->pa_alpha, &c->pa_info, &c->pairs, &c->lg2i, &c->sizes, &c->nearlist, &c->force, &c->geo_big,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints, &c->isect_ids };
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& kv : c->geo)
@@ -3310,6 +3531,49 @@ int ansx_next_geq_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t 
     });
     if (rc == ANSX_OK && found) *found = total;
     return rc;
+}
+
+int ansx_intersect_ids_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, const uint32_t* d_bases,
+    size_t nbases, const uint32_t* d_cand, size_t ncand, uint32_t* d_out_ids, uint32_t* d_out_idx, uint64_t* d_out_pos,
+    size_t out_capacity, uint64_t* nfound, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || !d_in) return ANSX_ERR_ARG;
+    if (ncand > 0 && (!d_bases || !d_cand || (!d_out_ids && !d_out_idx && !d_out_pos))) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_bases & 3u) || ((uintptr_t)d_cand & 3u) || ((uintptr_t)d_out_ids & 3u)
+        || ((uintptr_t)d_out_idx & 3u) || ((uintptr_t)d_out_pos & 7u))
+        return ANSX_ERR_ARG;
+    if (ncand > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (ncand == 0) return empty_batch(nullptr, nfound);
+    const IsectOut o = { d_out_ids, d_out_idx, (u64*)d_out_pos, (u64)out_capacity };
+    u64 total = 0;
+    const int rc = run_call(c, stream, [&](hipStream_t s) -> int {
+        int r;
+        RangeTail t = { d_in };
+        if ((r = range_source(c, kind, f, d_in, in_bytes, s, &t.H, &t.P))) return r;
+        return isect_step(c, kind, f, t, in_bytes, d_bases, nbases, d_cand, (u32)ncand, o, &total, s);
+    });
+    if ((rc == ANSX_OK || rc == ANSX_ERR_CAPACITY) && nfound) *nfound = total;
+    return rc;
+}
+
+int ansx_intersect_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint32_t* const* d_bases, const size_t* nbases, size_t count, uint32_t* d_out_ids, size_t out_capacity,
+    uint64_t* nfound, size_t* bad_container, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c || count == 0 || count > 0xFFFFFFFFull || !d_ins || !in_bytes) return ANSX_ERR_ARG;
+    if (count > 1 && (!d_bases || !nbases)) return ANSX_ERR_ARG;
+    if ((!d_out_ids && out_capacity > 0) || ((uintptr_t)d_out_ids & 3u)) return ANSX_ERR_ARG;
+    for (size_t i = 0; i < count; i++)
+        if (!d_ins[i] || ((uintptr_t)d_ins[i] & 15u) || (d_bases && ((uintptr_t)d_bases[i] & 3u))) {
+            if (bad_container) *bad_container = i;
+            return ANSX_ERR_ARG;
+        }
+    return run_call(c, stream, [&](hipStream_t s) {
+        return intersect_lists(c, kind, f, d_ins, in_bytes, d_bases, nbases, count, d_out_ids, out_capacity, (u64*)nfound,
+            bad_container, s);
+    });
 }
 
 int ansx_block_bases_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, uint32_t* d_bases,
@@ -3815,7 +4079,7 @@ size_t ansx_workspace_bytes(const ansx_ctx* c)
     const DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->pa_alpha, &c->pa_info, &c->pairs, &c->sizes,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints, &c->isect_ids };
     size_t t = 0;
     for (const DevBuf* b : bufs) t += b->cap;
     return t;

@@ -34,21 +34,50 @@
 // are staged whole; 16384 blocks are sampled at every 4th entry and leave two levels to global memory.
 #define ANSX_NG_LDS 4096u
 
-// Per target the block that holds its answer, as a range for the device planner.  The entries e[b] = bases[b + 1],
-// b in [0, nb), are searched in two levels: smp[k] = the last entry of group k of `stride` consecutive ones (stride 1:
-// every entry) in LDS, staged once per workgroup with independent loads; then the group itself in global memory,
-// ceil(log2 stride) dependent loads.  first[i] / count[i]: the workspace the planner reads.
+// The entries e[b] = bases[b + 1], b in [0, nb), are searched in two levels: smp[k] = the last entry of group k of
+// `stride` consecutive ones (stride 1: every entry) in LDS, staged once per workgroup with independent loads; then the
+// group itself in global memory, ceil(log2 stride) dependent loads.  ng_stage and ng_find_block are the two levels,
+// shared with k_isect_match_full (ansx_intersect.h), so that the argument at the head of the file is made once.
+// smp[ANSX_NG_LDS] <- the samples; *stride, *m: the group length and count (nb >= 1; m <= ANSX_NG_LDS).  Ends in a barrier.
+__device__ __forceinline__ void ng_stage(const u32* __restrict__ bases, u32 nb, u32* smp, u32 tid, u32* stride, u32* m)
+{
+    const u32 st = (nb + ANSX_NG_LDS - 1) / ANSX_NG_LDS, mm = (nb + st - 1) / st;
+    for (u32 k = tid; k < mm; k += ANSX_NG_NT) {
+        const u64 e = ((u64)k + 1) * st;
+        smp[k] = bases[e < nb ? e : nb];  // (the last group may be short: it ends on bases[nb])
+    }
+    __syncthreads();
+    *stride = st, *m = mm;
+}
+
+// The smallest block b with bases[b + 1] >= t, for t <= smp[m - 1] = bases[nb]
+__device__ __forceinline__ u32 ng_find_block(const u32* smp, u32 m, u32 stride, const u32* __restrict__ bases, u32 nb, u32 t)
+{
+    u32 lo = 0, hi = m - 1;  // smp[hi] >= t, here and after every step
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (smp[mid] >= t) hi = mid;
+        else lo = mid + 1;
+    }
+    const u64 gend = ((u64)hi + 1) * stride;
+    u32 glo = hi * stride, ghi = (u32)(gend < nb ? gend : nb) - 1u;  // bases[ghi + 1] is smp[hi]: read as >= t
+    while (glo < ghi) {
+        const u32 mid = (glo + ghi) >> 1;
+        if (bases[mid + 1] >= t) ghi = mid;
+        else glo = mid + 1;
+    }
+    return ghi;
+}
+
+// Per target the block that holds its answer, as a range for the device planner.  first[i] / count[i]: the workspace
+// the planner reads.
 __global__ __launch_bounds__(ANSX_NG_NT) void k_ng_locate(const u32* __restrict__ bases, u32 nb, u64 bi,
     const u32* __restrict__ targets, u32 nt, u64* __restrict__ first, u32* __restrict__ count)
 {
     __shared__ u32 smp[ANSX_NG_LDS];
     const u32 tid = threadIdx.x;
-    const u32 stride = (nb + ANSX_NG_LDS - 1) / ANSX_NG_LDS, m = (nb + stride - 1) / stride;  // (nb >= 1; m <= ANSX_NG_LDS)
-    for (u32 k = tid; k < m; k += ANSX_NG_NT) {
-        const u64 e = ((u64)k + 1) * stride;
-        smp[k] = bases[e < nb ? e : nb];  // (the last group may be short: it ends on bases[nb])
-    }
-    __syncthreads();
+    u32 stride, m;
+    ng_stage(bases, nb, smp, tid, &stride, &m);
     const u32 last = smp[m - 1];  // bases[nb], the last id of the list
 #pragma unroll
     for (u32 q = 0; q < ANSX_NG_TPT; q++) {  // (coalesced: target q * 256 + tid of the tile)
@@ -59,20 +88,7 @@ __global__ __launch_bounds__(ANSX_NG_NT) void k_ng_locate(const u32* __restrict_
             first[i] = 0, count[i] = 0;
             continue;
         }
-        u32 lo = 0, hi = m - 1;  // smp[hi] >= t, here and after every step
-        while (lo < hi) {
-            const u32 mid = (lo + hi) >> 1;
-            if (smp[mid] >= t) hi = mid;
-            else lo = mid + 1;
-        }
-        const u64 gend = ((u64)hi + 1) * stride;
-        u32 glo = hi * stride, ghi = (u32)(gend < nb ? gend : nb) - 1u;  // bases[ghi + 1] is smp[hi]: read as >= t
-        while (glo < ghi) {
-            const u32 mid = (glo + ghi) >> 1;
-            if (bases[mid + 1] >= t) ghi = mid;
-            else glo = mid + 1;
-        }
-        first[i] = (u64)ghi * bi, count[i] = 1;
+        first[i] = (u64)ng_find_block(smp, m, stride, bases, nb, t) * bi, count[i] = 1;
     }
 }
 

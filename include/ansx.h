@@ -543,6 +543,67 @@ int ansx_next_geq_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t
     size_t ntargets, uint64_t* d_pos, uint32_t* d_ids, uint64_t* found, size_t* bad_container, size_t* bad_target,
     void* stream);
 
+/* Intersection of gap-coded lists.
+ *
+ * ansx_intersect_ids_dev: the members of a candidate array in one list.  Let s be what ansx_decode_sums_dev returns for
+ * the container, n ids.  Candidate i is a member when some s[j] == d_cand[i].  The members are written in candidate
+ * order, back to back -- a stable filter: a candidate that repeats is kept every time it is a member; candidates may be
+ * unsorted.  For the k-th member, i_k its index in d_cand: d_out_ids[k] its value, d_out_idx[k] = i_k, d_out_pos[k] =
+ * min{ j : s[j] == value }, the lower bound as in ansx_next_geq_dev.  Membership is decided from "found and equal", never
+ * from a comparison with ANSX_NO_ID: a candidate 2^32 - 1 is a member exactly when the list's last id is 2^32 - 1.
+ * d_cand: ncand uint32_t in 4-byte aligned DEVICE memory, read on `stream`.  d_out_ids, d_out_idx (4-byte aligned),
+ * d_out_pos (8-byte aligned): DEVICE arrays of out_capacity entries; any may be NULL, not all three; none may overlap
+ * d_cand.  *nfound (optional, host): the number of members, set on ANSX_OK and on ANSX_ERR_CAPACITY.
+ * Accepted forms, header checks, what the bases promise, no trace in the context and "returns after the status has been
+ * read back" are ansx_next_geq_dev's (a single-stream stream is ANSX_ERR_FORMAT).
+ * Errors, in this order:
+ *   before the context is touched, ANSX_ERR_ARG for a null ctx or d_in; a null d_bases or d_cand, or all three outputs
+ *   null, with ncand > 0; a misaligned pointer (d_in 16 bytes, d_bases 4, d_cand 4, d_out_ids 4, d_out_idx 4,
+ *   d_out_pos 8); ncand > UINT32_MAX.  ncand == 0: ANSX_OK, *nfound = 0, nothing launched, the context untouched;
+ *   on the host once the header is known, before any launch: ANSX_ERR_FORMAT as in the range calls, then ANSX_ERR_ARG
+ *   if nbases != nblocks + 1;
+ *   on the device: ANSX_ERR_FORMAT for an invalid index entry or stream, and for bases that are not the list's at a
+ *   touched block -- a block some candidate was sent to; ANSX_ERR_DOMAIN or ANSX_ERR_FORMAT for a list whose sum leaves
+ *   32 bits (it has no valid bases).  NO output array is written then;
+ *   ANSX_ERR_CAPACITY when there are more members than out_capacity: *nfound is the size of a retry and no output
+ *   entry is written.
+ * A wrong entry of d_bases at an untouched block can misdirect a candidate undetected, which here means that a member
+ * may be missed.  Memory safety and termination hold for any content of d_bases and d_cand.
+ * Two forms of one step, with identical outputs for valid inputs.  Selective (ncand < nblocks): ansx_next_geq_dev's
+ * path -- of a block no candidate lands in nothing is read, no grid grows with the block count -- with the match and
+ * the compaction in the search's place.  Workspace: ansx_next_geq_dev's plus 8 bytes per 64 candidates and, with
+ * d_out_pos, 8 per candidate.  Host waits: ansx_next_geq_dev's three and none more (the total rides on the last).
+ * Full (ncand >= nblocks, where the candidates reach most blocks anyway): the whole list decoded to ids in workspace,
+ * 4 bytes per int, the bases checked against it at touched blocks.  Host waits: three (the header twice, the status). */
+int ansx_intersect_ids_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* d_in, size_t in_bytes,
+    const uint32_t* d_bases, size_t nbases, const uint32_t* d_cand, size_t ncand, uint32_t* d_out_ids, uint32_t* d_out_idx,
+    uint64_t* d_out_pos, size_t out_capacity, uint64_t* nfound, void* stream);
+
+/* ansx_intersect_dev: the ids common to `count` lists.  The batch arrays are ansx_next_geq_batch_dev's: HOST arrays of
+ * DEVICE pointers, mixed geometries allowed, the same pointer at several positions allowed.  The result: the ids of
+ * the DRIVER -- the list of fewest ints, of equal ones the smallest batch index -- that occur in every other list,
+ * ascending, with the driver's own multiplicities; count == 1 gives that list's ids.  d_out_ids: DEVICE, 4-byte aligned,
+ * out_capacity entries.  *nfound (optional, host): the size of the result, set on ANSX_OK and ANSX_ERR_CAPACITY, where
+ * nothing is written: d_out_ids = NULL, out_capacity = 0 is a size query.
+ * How it runs: every header in one round trip; the driver decoded as ids into workspace; the other lists in ascending
+ * order of n, each one step of ansx_intersect_ids_dev (ids only, the form chosen per step) over the survivors so far;
+ * the loop stops as soon as a step leaves nothing, and the lists behind are not read beyond their headers; one copy.
+ * Errors, in this order: before the context is touched, ANSX_ERR_ARG for a null ctx, count == 0, null arrays (d_bases
+ * and nbases may be NULL for count == 1), a null d_out_ids with out_capacity > 0 or a misaligned one, and with
+ * *bad_container = i for a null or misaligned d_ins[i] (16 bytes) or a misaligned d_bases[i] (4);
+ *   ANSX_ERR_FORMAT with *bad_container = i for the first header that fails decode_dev's checks;
+ *   ANSX_ERR_ARG with *bad_container = i for the first list but the driver, whose bases are not read, with a null
+ *   d_bases[i] or nbases[i] != nblocks_i + 1;
+ *   ANSX_ERR_DOMAIN with *bad_container = the driver if its sum leaves 32 bits;
+ *   from a step: ANSX_ERR_FORMAT found on the device with *bad_container = count, as in the batch calls;
+ *   ANSX_ERR_CAPACITY.
+ * No trace is left in the context, which stays usable after any error.  Workspace: the step's own, 8 bytes per int of
+ * the driver, and the whole list (4 bytes per int) of a full-form step.  Host waits: one for the headers, two for the
+ * driver, two per step (selective: the planner's scalars, the status; full: the header, the status), one for the copy. */
+int ansx_intersect_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint32_t* const* d_bases, const size_t* nbases, size_t count, uint32_t* d_out_ids, size_t out_capacity,
+    uint64_t* nfound, size_t* bad_container, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
@@ -700,7 +761,9 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
  * cross-check test and the paired timing of tests/tools/bench_decode_setup.py), ANSX_MODEL_CHAIN ("old"; ""/"0"/NULL:
  * the default; anything else: ANSX_ERR_ARG -- the fast model path as it was before k_model_maxima: every block of
  * k_model_finish reads and raises the call's running maxima itself; for the cross-check test and the paired timing of
- * tests/tools/bench_model_chain.py);
+ * tests/tools/bench_model_chain.py), ANSX_INTERSECT_FORM ("selective" | "full"; ""/"0"/NULL: by the candidates per block;
+ * anything else: ANSX_ERR_ARG -- the form of every step of ansx_intersect_ids_dev and ansx_intersect_dev; for the tests,
+ * which compare the two, and the timing of tests/tools/bench_intersect.py);
  * through this call only (round 4): ANSX_NO_PC / ANSX_FORCE_PC / ANSX_NO_PC_AUTO / ANSX_PC_B_PAIRS (the producer /
  * consumer encoder never / whatever the list length / only on request; pairs per workgroup of its two-round shape),
  * ANSX_ENCODE_MODE2, ANSX_DECODE_PAIR, ANSX_DECODE_SMALL_RING ("never" | "always"; ""/"0"/NULL: the default; anything
