@@ -603,6 +603,56 @@ class _Codec:
             raise err
         return int(found.value)
 
+    def intersect_batch_dev(self, in_ptrs, in_bytes, queries, out_ids_ptr, out_capacity, stream=None):
+        """intersect_dev for many queries over the batch in_ptrs / in_bytes in one call (no bases
+        are needed).  queries: a sequence of non-empty sequences of batch indices.  The result of query q, exactly what
+        intersect_dev gives for its lists in that order, goes to uint32 entries [offsets[q], offsets[q + 1]) of
+        out_ids_ptr (device, out_capacity entries); returns offsets, np.uint64 of len(queries) + 1.  A total above
+        out_capacity raises AnsxError(ERR_CAPACITY) with .needed = the total and .offsets, except that out_ids_ptr=None,
+        out_capacity=0 is a size query and returns the offsets.  A container no query names is not looked at and may be
+        0.  An AnsxError carries .bad_container / .bad_query where the call set them (None otherwise)."""
+        ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
+        if ptrs.size != sizes.size:
+            raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
+        if isinstance(out_capacity, bool) or not isinstance(out_capacity, (int, np.integer)) or out_capacity < 0:
+            raise ValueError("out_capacity must be a non-negative integer, got %r" % (out_capacity,))
+        if isinstance(queries, (str, bytes)) or not hasattr(queries, "__len__"):
+            raise ValueError("queries must be a sequence of sequences of batch indices")
+        qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
+        flat = []
+        for q, terms in enumerate(queries):
+            if isinstance(terms, (str, bytes)) or not hasattr(terms, "__len__"):
+                raise ValueError("query %d is not a sequence of batch indices" % q)
+            t = np.asarray(terms)
+            if t.ndim != 1 or (t.size and t.dtype.kind not in "ui"):
+                raise ValueError("query %d must be a flat sequence of integers" % q)
+            if t.size and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+                raise ValueError("query %d names a list outside [0, 2^32)" % q)
+            flat.append(t.astype(np.uint32))
+            qoff[q + 1] = qoff[q] + np.uint64(t.size)
+        # (never empty, so that the library and not a null array answers queries that are all empty)
+        terms = np.ascontiguousarray(np.concatenate(flat + [np.zeros(1, dtype=np.uint32)]), dtype=np.uint32)
+        nc, nq = ptrs.size, len(queries)
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c, bad_q = C.c_size_t(unset), C.c_size_t(unset)
+        st = L.lib().ansx_intersect_batch_dev(
+            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None, nc,
+            terms.ctypes.data, qoff.ctypes.data, nq, out_ids_ptr, int(out_capacity),
+            offsets.ctypes.data, C.byref(bad_c), C.byref(bad_q), stream)
+        if st == L.ERR_CAPACITY and out_ids_ptr is None and int(out_capacity) == 0:
+            return offsets
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".intersect_batch_dev")
+            err.bad_container = int(bad_c.value) if bad_c.value != unset else None
+            err.bad_query = int(bad_q.value) if bad_q.value != unset else None
+            if st == L.ERR_CAPACITY:
+                err.needed = int(offsets[nq])
+                err.offsets = offsets
+            raise err
+        return offsets
+
 
 class ANSfold(_Codec):
     """methods.hpp:529-547"""

@@ -35,6 +35,7 @@
 #include "ansx_rangesums.h"
 #include "ansx_nextgeq.h"
 #include "ansx_intersect.h"
+#include "ansx_intersect_batch.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
@@ -125,6 +126,9 @@ struct ansx_ctx {
     DevBuf bat_hdr;                       // ansx_decode_batch_dev: input addresses and headers of the batch
     DevBuf enb_plan, enb_wc;              // ansx_encode_batch_dev: a pass's plan and results; its restart points and hints (work area)
     DevBuf isect_ids;                     // ansx_intersect_dev: the driver's ids and the survivors of a step, two arrays of n_driver ints
+    DevBuf isectb_ids, isectb_work;       // ansx_intersect_batch_dev: a group's ids and two candidate buffers; its tables, segments and IsectWork
+    u8* isectb_pin = nullptr;             // ... and the pinned host image of its tables (rng_pin belongs to the decode's
+    size_t isectb_pin_cap = 0;            //     passes and the scan, whose uploads are under way when the tables go up)
     DevBuf sums_plan, sums_ints;          // running sums and gaps: flag word + list starts + tile aggregates and carries; the gaps of a call (4 bytes per int)
     u8* rng_pin = nullptr;                // ... and the pinned host image of rng_plan (an asynchronous upload from
     size_t rng_pin_cap = 0;               //     pageable memory is staged by the runtime: 0.666 -> 0.618 ms at 4096 ranges)
@@ -196,6 +200,7 @@ struct ansx_ctx {
         int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
         u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev, ansx_decode_batch_ranges_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
         int intersect_form = 0;       // ANSX_INTERSECT_FORM: 0 by ANSX_ISECT_FULL_PER_BLOCK, 1 "selective", 2 "full" (tests and the bench tool force one)
+        u64 isect_batch_ints = 0;     // ANSX_ISECT_BATCH_INTS: the ints a group of ansx_intersect_batch_dev may take (0 = ANSX_ISECT_BATCH_INTS_DEFAULT; tests force small groups)
         u32 range_sums_wg_max = 0;    // ANSX_RANGE_SUMS_WG_MAX: the largest block the one-kernel scan of the range sums takes (0 = ANSX_RS_WG_MAX; the bench tool measures both sides of the switch)
     } dbg;
 };
@@ -1802,18 +1807,21 @@ int decode_dev(ansx_ctx* c, const Plan& Pin, const u8* d_in, size_t in_bytes, u3
 // scan in front of it, the scan and k_ng_search, or the scan, k_isect_match and the compaction of an intersect step
 // (RangeOut).
 
-// rng_pin holds at least `bytes` (its content is not kept)
-int ensure_pin(ansx_ctx* c, size_t bytes)
+// the pinned buffer p of cap bytes holds at least `bytes` (its content is not kept)
+int ensure_pinned(ansx_ctx* c, u8*& p, size_t& cap, size_t bytes)
 {
-    if (bytes <= c->rng_pin_cap) return ANSX_OK;
-    if (c->rng_pin) HIPCHK(c, hipHostFree(c->rng_pin));
-    c->rng_pin = nullptr;
-    c->rng_pin_cap = 0;
+    if (bytes <= cap) return ANSX_OK;
+    if (p) HIPCHK(c, hipHostFree(p));
+    p = nullptr;
+    cap = 0;
     const size_t want = bytes + (bytes >> 3) + 4096;
-    HIPCHK(c, hipHostMalloc((void**)&c->rng_pin, want, hipHostMallocDefault));
-    c->rng_pin_cap = want;
+    HIPCHK(c, hipHostMalloc((void**)&p, want, hipHostMallocDefault));
+    cap = want;
     return ANSX_OK;
 }
+
+// ... rng_pin
+int ensure_pin(ansx_ctx* c, size_t bytes) { return ensure_pinned(c, c->rng_pin, c->rng_pin_cap, bytes); }
 
 // The source container's header, checked as decode_dev checks it, and its plan
 int range_source(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, hipStream_t s, ansx_container_header* H,
@@ -2320,6 +2328,22 @@ int batch_pass(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& src, c
     }, s);
 }
 
+// The containers of `groups` (members of src, by geometry) whole, src[i] to off[i] of d_out, in passes of at most
+// ANSX_BATCH_PASS_BLOCKS blocks.  A format error found on the device: *bad_index = count.
+int batch_decode_groups(ansx_ctx* c, int kind, int f, const std::vector<BatchSrc>& src, const std::vector<u64>& off,
+    const GeometryGroups& groups, size_t count, u32* d_out, size_t* bad_index, hipStream_t s)
+{
+    const u32 PB = batch_pass_blocks(c);
+    return for_each_group(groups, count, bad_index, [&](const std::vector<u32>& ids) -> int {
+        int rc;
+        size_t ci = 0;
+        u32 b0 = 0;
+        while (ci < ids.size())
+            if ((rc = batch_pass(c, kind, f, src, off, ids, &ci, &b0, PB, d_out, s))) return rc;
+        return ANSX_OK;
+    });
+}
+
 int decode_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
     u32* d_out, size_t cap, u64* offsets, u64* total_ints, size_t* bad_index, hipStream_t s)
 {
@@ -2345,14 +2369,7 @@ int decode_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const siz
     // groups of one geometry, batch order inside each
     GeometryGroups groups;
     for (size_t i = 0; i < count; i++) groups[br_geometry(src[i].H)].push_back((u32)i);
-    const u32 PB = batch_pass_blocks(c);
-    return for_each_group(groups, count, bad_index, [&](const std::vector<u32>& ids) -> int {
-        size_t ci = 0;
-        u32 b0 = 0;
-        while (ci < ids.size())
-            if ((rc = batch_pass(c, kind, f, src, off, ids, &ci, &b0, PB, d_out, s))) return rc;
-        return ANSX_OK;
-    });
+    return batch_decode_groups(c, kind, f, src, off, groups, count, d_out, bad_index, s);
 }
 
 // --------------------------------------------------------------------------------- ranges of a batch
@@ -3040,6 +3057,111 @@ int intersect_lists(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
     return ANSX_OK;
 }
 
+// ansx_intersect_batch_dev (ansx_intersect_batch.h; the plan: ansx_plan.h, isb_plan): the headers
+// of the referenced containers in one round trip (batch_ranges_front) -> the groups -> per group (isb_group): its lists
+// decoded back to back into isectb_ids by the passes of ansx_decode_batch_dev, one segmented scan over all of them,
+// k_isectb_gather, then a round per non-driver list of its longest query -- k_isectb_match, k_dr_scan, k_isect_compact,
+// k_isectb_bounds, between the two candidate buffers behind the lists -- and one copy of the survivors to the caller.
+// Workspace: 4 bytes per int of the group's lists and 8 per int of its drivers (the budget bounds their sum unless one
+// query exceeds it alone), a pass's, the scan's 16 bytes per 4096 ints, IsectWork over the candidates, and per query 16
+// bytes of tables, 12 of segments and 16 per non-driver term.
+// Host waits: one for the headers; per group those of its decode passes (decode_dev's on a sub-container: header and
+// final read-back, one more where the form validates the index first), ONE for the scan's flag word and ONE per round,
+// which brings the members' count (and, with the last round, the segments); one behind the copies, per call.  None
+// grows with the number of queries.
+int isb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& g, std::vector<u64>& off, size_t count,
+    u32* d_out, size_t cap, u64* run, u64* out_offsets, size_t* bad_container, hipStream_t s)
+{
+    int rc;
+    const size_t Q = g.q1 - g.q0, q1 = rup(Q + 1, 4);
+    const u64 L = g.at.back(), nc0 = g.G[Q].dst;
+    if (nc0 == 0) {  // (every driver is empty: nothing to look up, nothing is decoded)
+        for (size_t j = 0; j <= Q; j++) out_offsets[g.q0 + j] = *run;
+        return ANSX_OK;
+    }
+    // the lists | two candidate buffers, each with the decoders' slack behind
+    const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)nc0, 4) + 16;
+    if ((rc = ensure(c, c->isectb_ids, 4 * (o_c + 2 * half)))) return rc;
+    u32* ids = (u32*)c->isectb_ids.p;
+    u32* buf[2] = { ids + o_c, ids + o_c + half };
+    GeometryGroups geo;
+    for (size_t k = 0; k < g.lists.size(); k++) off[g.lists[k]] = g.at[k], geo[br_geometry(F.rs[g.lists[k]].H)].push_back(g.lists[k]);
+    if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, ids, bad_container, s))) return rc;
+
+    // one upload: zero flag words | queries | round table; behind it on the device: two arrays of segments | IsectWork
+    Upload U;
+    const auto s_fl = U.add<u32>(4);
+    const auto s_g = U.add<ansx_isb_query>(Q + 1);
+    const auto s_ro = U.add<u32>(Q + 1);
+    const auto s_rt = U.add<ansx_isb_list>(g.rt.size());
+    const size_t up = U.end;
+    const auto s_seg = U.add<u32>(2 * q1);  // (the host's copy: the last round's, read back)
+    const size_t o_w = rup(U.end, 16);
+    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, U.end))) return rc;
+    if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(nc0, false)))) return rc;
+    U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
+    memset(U.pin(s_fl), 0, s_fl.bytes);
+    U.put(s_g, g.G.data()), U.put(s_ro, g.rt_off.data());
+    if (!g.rt.empty()) U.put(s_rt, g.rt.data());
+    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
+    u32* seg[2] = { U.dev(s_seg), U.dev(s_seg) + q1 };
+    const u32* zero = U.dev(s_fl);
+
+    SumsPlan S;
+    if ((rc = sums_prepare(c, (uintptr_t)ids, L, g.at.data(), g.lists.size(), s, &S))) return rc;
+    if ((rc = sums_launch(c, ids, L, g.lists.size(), S, s))) return rc;
+    LAUNCH(c, "k_isectb_gather", k_isectb_gather, (u32)((std::max<u64>(nc0, Q + 1) + ANSX_ISECT_TILE - 1) / ANSX_ISECT_TILE),
+        ANSX_ISECT_NT, 0, s, (const u32*)ids, (const ansx_isb_query*)U.dev(s_g), (u32)Q, buf[0], (u32)nc0, seg[0], (const u32*)S.flag);
+    u32* hflag = &c->pin->isect_sflag;
+    HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (*hflag != ANSX_SS_NONE) {  // the first list of the buffer whose sum left 32 bits
+        if (bad_container && *hflag < g.lists.size()) *bad_container = F.ref[g.lists[*hflag]];
+        return ANSX_ERR_DOMAIN;
+    }
+
+    u32 nc = (u32)nc0, cur = 0, r = 0;
+    for (; r < g.rounds && nc > 0; r++) {
+        const IsectWork W(U.devp + o_w, nc, false);
+        LAUNCH(c, "k_isectb_match", k_isectb_match, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)buf[cur], nc,
+            (const u32*)seg[cur], (u32)Q, (const u32*)U.dev(s_ro), (const ansx_isb_list*)U.dev(s_rt), r, W.ballots, W.counts);
+        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
+        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)buf[cur], nc, (const u64*)W.ballots,
+            (const u64*)W.counts, (const u64*)W.total, (u64)nc, (const u64*)nullptr, buf[1 - cur], (u32*)nullptr, (u64*)nullptr, zero, zero);
+        LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, (const u32*)seg[cur], (u32)Q, nc,
+            (const u64*)W.ballots, (const u64*)W.counts, (const u64*)W.total, seg[1 - cur]);
+        HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
+        if (r + 1 == g.rounds) HIPCHK(c, hipMemcpyAsync(U.pin(s_seg), seg[1 - cur], 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        nc = (u32)c->pin->isect_total, cur = 1 - cur;
+    }
+    // the segments behind the last round: the drivers' (no round), what came back, or nothing left
+    const u32* hseg = U.pin(s_seg);
+    for (size_t j = 0; j <= Q; j++) out_offsets[g.q0 + j] = *run + (g.rounds == 0 ? g.G[j].dst : r == g.rounds ? hseg[j] : 0);
+    if (nc > 0 && *run + nc <= cap) HIPCHK(c, hipMemcpyAsync(d_out + *run, buf[cur], 4 * (size_t)nc, hipMemcpyDeviceToDevice, s));
+    *run += nc;
+    return ANSX_OK;
+}
+
+int intersect_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count, const u32* terms,
+    const u64* qoff, size_t nq, u32* d_out, size_t cap, u64* out_offsets, size_t* bad_container, size_t* bad_query, hipStream_t s)
+{
+    int rc;
+    BrFront F;
+    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, terms, (size_t)qoff[nq], nullptr, &F, bad_container, s))) return rc;
+    std::vector<u64> n(F.ref.size());
+    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
+    std::vector<IsbGroup> groups;
+    const u64 budget = c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT;
+    if ((rc = isb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, &groups, bad_query))) return rc;
+    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
+    u64 run = 0;
+    for (const IsbGroup& g : groups)
+        if ((rc = isb_group(c, kind, f, F, g, off, count, d_out, cap, &run, out_offsets, bad_container, s))) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));  // (the copies)
+    return run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
+}
+
 // The argument checks of the random-access entry points, one per argument shape: everything a call decides before the
 // context is touched.  The plain and the sums entry of a shape share them; what a sums or search entry adds (bases,
 // targets, outputs) it checks itself.
@@ -3210,7 +3332,7 @@ int ansx_init(int device, ansx_ctx** out)
     }
     static const char* const names[] = { "ANSX_TEST_TABLE16_FIXUP", "ANSX_ENCODE_GTAB16", "ANSX_PARSE_GENERIC", "ANSX_PARSE_WIN", "ANSX_PARSE_FAST",
         "ANSX_DECODE_TABLE", "ANSX_NO_STREAM_LDS", "ANSX_DECODE_MODE", "ANSX_PARSE_STAGE_WORDS", "ANSX_MODEL_FUSED", "ANSX_MODEL_SYNC", "ANSX_NS_HINT", "ANSX_T_HINT", "ANSX_NO_FAST_MODEL", "ANSX_FAST_GUARD", "ANSX_CAND_CHAINS", "ANSX_NEAR_BAND", "ANSX_TEST_NEAR_FLIP", "ANSX_WIDE_RESTART", "ANSX_TEST_WIDE_AT",
-        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP", "ANSX_MODEL_CHAIN", "ANSX_INTERSECT_FORM" };
+        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP", "ANSX_MODEL_CHAIN", "ANSX_INTERSECT_FORM", "ANSX_ISECT_BATCH_INTS" };
     for (const char* nm : names)
         if (const char* v = getenv(nm))
             if (ansx_debug_set(c, nm, v) != ANSX_OK)  // (a value the key does not take selects nothing: said, not passed over)
@@ -3354,6 +3476,7 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
     else if (!strcmp(name, "ANSX_NEAR_BAND")) c->dbg.near_band = (value && value[0]) ? strtod(value, nullptr) : ANSX_NEAR_BAND;
     else if (!strcmp(name, "ANSX_TEST_NEAR_FLIP")) c->dbg.near_flip = on;
     else if (!strcmp(name, "ANSX_BATCH_PASS_BLOCKS")) c->dbg.batch_pass_blocks = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
+    else if (!strcmp(name, "ANSX_ISECT_BATCH_INTS")) c->dbg.isect_batch_ints = (value && value[0]) ? (u64)strtoull(value, nullptr, 10) : 0ull;
     else if (!strcmp(name, "ANSX_RANGE_SUMS_WG_MAX")) c->dbg.range_sums_wg_max = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_MODEL_PIPELINE")) {
         if (!value || !value[0] || !strcmp(value, "0")) c->dbg.model_pipeline = 0;
@@ -3388,7 +3511,7 @@ void ansx_destroy(ansx_ctx* c)
     DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->log2lut, &c->pa_alpha, &c->pa_info, &c->pairs, &c->lg2i, &c->sizes, &c->nearlist, &c->force, &c->geo_big,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints, &c->isect_ids };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints, &c->isect_ids, &c->isectb_ids, &c->isectb_work };
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& kv : c->geo)
@@ -3399,6 +3522,7 @@ void ansx_destroy(ansx_ctx* c)
     }
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->rng_pin) (void)hipHostFree(c->rng_pin);
+    if (c->isectb_pin) (void)hipHostFree(c->isectb_pin);
     (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -3573,6 +3697,40 @@ int ansx_intersect_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins
     return run_call(c, stream, [&](hipStream_t s) {
         return intersect_lists(c, kind, f, d_ins, in_bytes, d_bases, nbases, count, d_out_ids, out_capacity, (u64*)nfound,
             bad_container, s);
+    });
+}
+
+int ansx_intersect_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count,
+    const uint32_t* terms, const uint64_t* qoff, size_t nqueries, uint32_t* d_out_ids, size_t out_capacity,
+    uint64_t* out_offsets, size_t* bad_container, size_t* bad_query, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (!c) return ANSX_ERR_ARG;
+    if (nqueries > 0 && (!d_ins || !in_bytes || !terms || !qoff || !out_offsets)) return ANSX_ERR_ARG;
+    if ((!d_out_ids && out_capacity > 0) || ((uintptr_t)d_out_ids & 3u)) return ANSX_ERR_ARG;
+    if (count > 0xFFFFFFFFull || nqueries > 0xFFFFFFFFull || (nqueries > 0 && qoff[nqueries] > 0xFFFFFFFFull)) return ANSX_ERR_ARG;
+    for (size_t q = 0; q < nqueries; q++)
+        if ((q == 0 && qoff[0] != 0) || qoff[q + 1] <= qoff[q]) {  // (an empty query has no driver)
+            if (bad_query) *bad_query = q;
+            return ANSX_ERR_ARG;
+        }
+    for (size_t q = 0; q < nqueries; q++)
+        for (u64 j = qoff[q]; j < qoff[q + 1]; j++)
+            if (terms[j] >= count) {
+                if (bad_query) *bad_query = q;
+                return ANSX_ERR_ARG;
+            }
+    for (size_t q = 0; q < nqueries; q++)  // (only the containers some query names are looked at)
+        for (u64 j = qoff[q]; j < qoff[q + 1]; j++)
+            if (!d_ins[terms[j]] || ((uintptr_t)d_ins[terms[j]] & 15u)) {
+                if (bad_query) *bad_query = q;
+                if (bad_container) *bad_container = terms[j];
+                return ANSX_ERR_ARG;
+            }
+    if (nqueries == 0) return empty_batch(out_offsets, (u64*)nullptr);
+    return run_call(c, stream, [&](hipStream_t s) {
+        return intersect_batch(c, kind, f, d_ins, in_bytes, count, terms, (const u64*)qoff, nqueries, d_out_ids, out_capacity,
+            (u64*)out_offsets, bad_container, bad_query, s);
     });
 }
 
@@ -4079,7 +4237,7 @@ size_t ansx_workspace_bytes(const ansx_ctx* c)
     const DevBuf* bufs[] = { &c->pre_work, &c->hist, &c->hterm, &c->sortF, &c->sortSym, &c->attS, &c->prevS, &c->attMeta, &c->blk,
         &c->table, &c->tab32, &c->scratch, &c->misc, &c->mapped, &c->mostfreq, &c->stage_in, &c->stage_out,
         &c->dec_s2s, &c->dec_cum, &c->dec_info, &c->plain, &c->rf_tmp, &c->pa_alpha, &c->pa_info, &c->pairs, &c->sizes,
-        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints, &c->isect_ids };
+        &c->rng_plan, &c->rng_cont, &c->rng_list, &c->rng_dev, &c->bat_hdr, &c->enb_plan, &c->enb_wc, &c->sums_plan, &c->sums_ints, &c->isect_ids, &c->isectb_ids, &c->isectb_work };
     size_t t = 0;
     for (const DevBuf* b : bufs) t += b->cap;
     return t;

@@ -1,9 +1,10 @@
 // ansx -- the host's plans of the random-access calls ("Host side of the random-access calls"):
 // which blocks a set of ranges touches, where every range's ints lie in the work list those blocks decode to, and the
 // tables a pass over blocks of many containers takes; and the steps and pass tables of a batch of lists to encode
-// (ansx_encode_batch_dev).  Pure host arithmetic: no context, no stream, no device pointer
+// (ansx_encode_batch_dev); and the groups, drivers and round tables of a batch of conjunctive queries
+// (ansx_intersect_batch_dev).  Pure host arithmetic: no context, no stream, no device pointer
 // (addresses travel as integers), so it builds with a plain host compiler and is tested on the CPU
-// (tests/tools/plan_check.cpp).  The plain structs the kernels read these plans through are in ansx_plan_types.h,
+// (tests/tools/plan_check.cpp, tests/tools/isect_batch_plan_check.cpp).  The plain structs the kernels read these plans through are in ansx_plan_types.h,
 // which the kernel headers include.
 #pragma once
 #include "../../include/ansx.h"
@@ -428,6 +429,96 @@ static inline bool encb_pass_tables(const u64* offsets, size_t l0, size_t l1, u6
         for (u32 b = 0; b < NB; b++) hid[at[encb_class(remap, T, hblk[b].n)]++] = b;
     }
     return true;
+}
+
+// ------------------------------------------------------------------------------- batches of conjunctive queries
+// ansx_intersect_batch_dev cuts its queries, in order, into groups that are decoded and
+// intersected together.  Query q names the referenced lists rid[qoff[q] .. qoff[q + 1]) (br_refs' places), list r has
+// n[r] ints.  Its driver is the list of fewest ints, of equal ones the earliest position in the query; the others
+// follow by ascending n (ties: the earlier position) as its rounds 0, 1, ...
+
+// The ints a group may take -- its referenced lists once and its drivers' twice (two candidate buffers) -- unless
+// ANSX_ISECT_BATCH_INTS says otherwise: 2^28 ints, 1 GiB of workspace, the size of section 3h's batch of 4096 lists of
+// 64 Ki ids.  A bound on the workspace, not a tuned value: no other budget has been measured.
+#define ANSX_ISECT_BATCH_INTS_DEFAULT ((u64)1 << 28)
+
+struct IsbGroup {
+    size_t q0, q1;                   // its queries
+    std::vector<u32> lists;          // the non-empty referenced lists it decodes, ascending: its buffer, back to back
+    std::vector<u64> at;             // lists.size() + 1: where each one's ids start in the buffer; the last: its ints
+    std::vector<ansx_isb_query> G;   // q1 - q0 + 1: every query's driver and segment; the last closes them
+    std::vector<u32> rt_off;         // q1 - q0 + 1: query j's rounds are rt[rt_off[j] .. rt_off[j + 1])
+    std::vector<ansx_isb_list> rt;   // the round table
+    std::vector<u32> rt_list, drv;   // the referenced list behind every entry of rt, and every query's driver (what the CPU check holds the tables against)
+    u64 ints;                        // buffer + twice the candidates: what the budget bounds
+    u32 rounds;                      // most rounds of a query
+};
+
+// -> ANSX_OK, or ANSX_ERR_ARG with *bad_query the first query whose driver has 2^32 ints or more (a step takes at most
+// 2^32 - 1 candidates).  A group ends in front of the query that would take it over `budget` ints or its candidates to
+// 2^32; a query over the budget alone is a group of its own.  A list two groups name is decoded in both.
+static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64* qoff, size_t nq, u64 budget,
+    std::vector<IsbGroup>* groups, size_t* bad_query)
+{
+    groups->clear();
+    std::vector<u32> stamp(nref, 0xFFFFFFFFu), slot(nref, 0), fresh, ord;
+    for (size_t q = 0; q < nq;) {
+        groups->emplace_back();
+        IsbGroup& g = groups->back();
+        const u32 gid = (u32)(groups->size() - 1);
+        g.q0 = q, g.ints = 0, g.rounds = 0;
+        u64 cand = 0;
+        for (; q < nq; q++) {  // the queries it takes
+            const u32* t = rid + qoff[q];
+            const size_t m = (size_t)(qoff[q + 1] - qoff[q]);
+            u64 nd = n[t[0]], add = 0;
+            for (size_t j = 1; j < m; j++) nd = std::min(nd, n[t[j]]);
+            if (nd > 0xFFFFFFFFull) {
+                if (bad_query) *bad_query = q;
+                return ANSX_ERR_ARG;
+            }
+            fresh.clear();
+            for (size_t j = 0; j < m; j++)
+                if (stamp[t[j]] != gid) stamp[t[j]] = gid, fresh.push_back(t[j]), add += n[t[j]];
+            add += 2 * nd;
+            // (the stamps of a query that does not fit stay behind: the next group has another number)
+            if (q > g.q0 && (add > budget || g.ints > budget - add || cand + nd > 0xFFFFFFFFull)) break;
+            for (const u32 r : fresh)
+                if (n[r]) g.lists.push_back(r);
+            g.ints += add, cand += nd;
+        }
+        g.q1 = q;
+        std::sort(g.lists.begin(), g.lists.end());
+        g.at.resize(g.lists.size() + 1);
+        u64 at = 0;
+        for (size_t k = 0; k < g.lists.size(); k++) g.at[k] = at, slot[g.lists[k]] = (u32)k, at += n[g.lists[k]];
+        g.at.back() = at;
+        const size_t Q = g.q1 - g.q0;
+        g.G.resize(Q + 1), g.rt_off.resize(Q + 1), g.drv.resize(Q);
+        g.rt.reserve((size_t)(qoff[g.q1] - qoff[g.q0]) - Q), g.rt_list.reserve(g.rt.capacity());
+        u64 dst = 0;
+        for (size_t j = 0; j < Q; j++) {
+            const u32* t = rid + qoff[g.q0 + j];
+            const size_t m = (size_t)(qoff[g.q0 + j + 1] - qoff[g.q0 + j]);
+            ord.resize(m);
+            for (size_t k = 0; k < m; k++) ord[k] = (u32)k;
+            std::stable_sort(ord.begin(), ord.end(), [&](u32 x, u32 y) { return n[t[x]] < n[t[y]]; });
+            const u32 d = t[ord[0]];
+            g.drv[j] = d;
+            g.G[j] = { n[d] ? g.at[slot[d]] : 0, dst };
+            dst += n[d];
+            g.rt_off[j] = (u32)g.rt.size();
+            for (size_t k = 1; k < m; k++) {
+                const u32 r = t[ord[k]];
+                g.rt.push_back({ n[r] ? g.at[slot[r]] : 0, n[r] });
+                g.rt_list.push_back(r);
+            }
+            g.rounds = std::max(g.rounds, (u32)(m - 1));
+        }
+        g.G[Q] = { 0, dst };
+        g.rt_off[Q] = (u32)g.rt.size();
+    }
+    return ANSX_OK;
 }
 
 }  // namespace ansx_plan

@@ -119,3 +119,12 @@ struct ansx_brs_src {  // a source of a pass, beside its ansx_batch_src: the cal
     u32 nblocks;
     u32 pad_;
 };
+
+// A group of conjunctive queries (ansx_intersect_batch_dev, ansx_intersect_batch.h).  Both count in ints of the group's
+// buffer of ids, the lists the group decodes back to back.
+struct ansx_isb_query {  // query j of the group: its driver's ids lie from src on and become candidates [dst, next dst);
+    u64 src, dst;        // the entry behind the last query closes it: dst = the group's candidates
+};
+struct ansx_isb_list {  // a round of a query: the list's ids [at, at + n) of the buffer; an empty list has n = 0
+    u64 at, n;
+};

@@ -604,6 +604,45 @@ int ansx_intersect_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* con
     const uint32_t* const* d_bases, const size_t* nbases, size_t count, uint32_t* d_out_ids, size_t out_capacity,
     uint64_t* nfound, size_t* bad_container, void* stream);
 
+/* ansx_intersect_batch_dev: many conjunctive queries over one batch of gap-coded lists in one call (DESIGN.md section
+ * 3j).  The batch is d_ins / in_bytes / count as above (HOST arrays of DEVICE pointers, 16-byte aligned; mixed
+ * geometries allowed).  Query q names the lists terms[qoff[q] .. qoff[q + 1]) (HOST arrays; qoff has nqueries + 1
+ * entries from 0, ascending, no query empty).  d_out_ids[out_offsets[q] .. out_offsets[q + 1]) is exactly what
+ * ansx_intersect_dev returns for those lists in that order: the ids of the query's driver -- its list of fewest ints, of
+ * equal ones the earliest position in the query -- that occur in every other list, ascending, with the driver's
+ * multiplicities; a one-term query gives that list's ids.  A list may appear in many queries and more than once in
+ * one.  d_out_ids: DEVICE, 4-byte aligned, out_capacity entries; out_offsets: HOST, nqueries + 1 entries,
+ * out_offsets[0] = 0 and out_offsets[nqueries] the total.  No block bases are needed.
+ * How it runs: the headers of the referenced containers in one round trip; the queries are cut, in order, into groups
+ * whose referenced lists plus twice their drivers' ints stay within 2^28 ints (ANSX_ISECT_BATCH_INTS; a query above it
+ * is a group of its own; a list two groups name is decoded in both) and whose drivers' ints stay below 2^32.  Per
+ * group: its lists are decoded whole, back to back, by the passes of ansx_decode_batch_dev; one segmented scan makes
+ * them ids; every query's driver ids become the candidates; then one round per non-driver list of the group's longest
+ * query, lists in ascending n, over the survivors of ALL queries at once (a query with no list left passes its
+ * candidates through), until nothing is left; one copy of the survivors to d_out_ids.
+ * Errors, in this order: before the context is touched, ANSX_ERR_ARG for a null ctx; a null d_ins, in_bytes, terms, qoff
+ * or out_offsets with nqueries > 0; a null d_out_ids with out_capacity > 0 or a misaligned one; count, nqueries or
+ * qoff[nqueries] above UINT32_MAX; with *bad_query = q for qoff[0] != 0, a decrease or an empty query; with *bad_query
+ * for a terms[j] >= count; with *bad_query the first query that names it and *bad_container = its batch index for a
+ * null or misaligned d_ins[t] of a REFERENCED list.  nqueries == 0: ANSX_OK, nothing is launched, the context is
+ * untouched.  Then ANSX_ERR_FORMAT with *bad_container = the smallest batch index of a referenced container whose
+ * header fails decode_dev's checks (a single-stream stream is one such);
+ *   ANSX_ERR_ARG with *bad_query for a driver of 2^32 ints or more;
+ *   found on the device: ANSX_ERR_FORMAT with *bad_container = count for a bad stream or index entry; ANSX_ERR_DOMAIN
+ *   with *bad_container = a referenced list whose sum leaves 32 bits -- of the first group at fault, the first in the
+ *   order of its buffer (ascending batch index);
+ *   ANSX_ERR_CAPACITY when the total exceeds out_capacity: out_offsets is complete, so d_out_ids = NULL, out_capacity = 0
+ *   is a size query; nothing is written at or beyond d_out_ids + out_capacity, what lies below is unspecified.
+ * Containers no query names are not examined and may be NULL.  No trace is left in the context, which stays usable
+ * after any error.  Workspace: per group 4 bytes per int of its lists and 8 per int of its drivers (1 GiB at the
+ * default budget unless one query needs more), a decode pass's, 16 bytes per 4096 ints for the scan, and per query 28
+ * bytes plus 16 per non-driver term.  Host waits: one for the headers; per group those of its decode passes (header
+ * and status of every pass, one more where a pass validates its index first), one for the scan's flag word and one
+ * per round; one per call behind the copies, after which the call returns.  None grows with the number of queries. */
+int ansx_intersect_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    size_t count, const uint32_t* terms, const uint64_t* qoff, size_t nqueries, uint32_t* d_out_ids, size_t out_capacity,
+    uint64_t* out_offsets, size_t* bad_container, size_t* bad_query, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
@@ -763,7 +802,9 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
  * k_model_finish reads and raises the call's running maxima itself; for the cross-check test and the paired timing of
  * tests/tools/bench_model_chain.py), ANSX_INTERSECT_FORM ("selective" | "full"; ""/"0"/NULL: by the candidates per block;
  * anything else: ANSX_ERR_ARG -- the form of every step of ansx_intersect_ids_dev and ansx_intersect_dev; for the tests,
- * which compare the two, and the timing of tests/tools/bench_intersect.py);
+ * which compare the two, and the timing of tests/tools/bench_intersect.py), ANSX_ISECT_BATCH_INTS (number: the ints a
+ * group of ansx_intersect_batch_dev may take, its lists once and its drivers' twice; ""/"0"/NULL: 2^28 -- the results
+ * do not depend on it; the tests force several groups and a group per query);
  * through this call only (round 4): ANSX_NO_PC / ANSX_FORCE_PC / ANSX_NO_PC_AUTO / ANSX_PC_B_PAIRS (the producer /
  * consumer encoder never / whatever the list length / only on request; pairs per workgroup of its two-round shape),
  * ANSX_ENCODE_MODE2, ANSX_DECODE_PAIR, ANSX_DECODE_SMALL_RING ("never" | "always"; ""/"0"/NULL: the default; anything
