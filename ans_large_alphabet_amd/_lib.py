@@ -33,7 +33,7 @@ EXPORTS = [
     "ansx_encode_batch_gaps_dev", "ansx_block_bases_dev", "ansx_encode_gaps_bases_dev", "ansx_decode_ranges_sums_dev",
     "ansx_decode_device_ranges_sums_dev", "ansx_next_geq_dev", "ansx_encode_batch_gaps_bases_dev",
     "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
-    "ansx_intersect_ids_dev", "ansx_intersect_dev", "ansx_intersect_batch_dev",
+    "ansx_intersect_ids_dev", "ansx_intersect_dev", "ansx_intersect_batch_dev", "ansx_union_batch_dev", "ansx_union_dev",
 ]
 
 
@@ -183,6 +183,10 @@ def lib():
     # ... of many queries over one batch in one call
     L.ansx_intersect_batch_dev.restype = C.c_int
     L.ansx_intersect_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, vp, sz, vp, C.POINTER(sz), C.POINTER(sz), vp]
+    L.ansx_union_batch_dev.restype = C.c_int
+    L.ansx_union_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, C.POINTER(sz), C.POINTER(sz), vp]
+    L.ansx_union_dev.restype = C.c_int
+    L.ansx_union_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(sz), vp]
     L.ansx_container_info.restype = C.c_int
     L.ansx_container_info.argtypes = [vp, sz, C.POINTER(ContainerHeader)]
     L.ansx_profile_enable.restype = C.c_int

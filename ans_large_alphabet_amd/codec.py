@@ -603,14 +603,9 @@ class _Codec:
             raise err
         return int(found.value)
 
-    def intersect_batch_dev(self, in_ptrs, in_bytes, queries, out_ids_ptr, out_capacity, stream=None):
-        """intersect_dev for many queries over the batch in_ptrs / in_bytes in one call (DESIGN.md section 3j; no bases
-        are needed).  queries: a sequence of non-empty sequences of batch indices.  The result of query q, exactly what
-        intersect_dev gives for its lists in that order, goes to uint32 entries [offsets[q], offsets[q + 1]) of
-        out_ids_ptr (device, out_capacity entries); returns offsets, np.uint64 of len(queries) + 1.  A total above
-        out_capacity raises AnsxError(ERR_CAPACITY) with .needed = the total and .offsets, except that out_ids_ptr=None,
-        out_capacity=0 is a size query and returns the offsets.  A container no query names is not looked at and may be
-        0.  An AnsxError carries .bad_container / .bad_query where the call set them (None otherwise)."""
+    @staticmethod
+    def _batch_queries(in_ptrs, in_bytes, queries, out_capacity):
+        """The checked host arrays of a call over queries of a batch -> (ptrs, sizes, terms, qoff)"""
         ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
         sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
         if ptrs.size != sizes.size:
@@ -633,6 +628,17 @@ class _Codec:
             qoff[q + 1] = qoff[q] + np.uint64(t.size)
         # (never empty, so that the library and not a null array answers queries that are all empty)
         terms = np.ascontiguousarray(np.concatenate(flat + [np.zeros(1, dtype=np.uint32)]), dtype=np.uint32)
+        return ptrs, sizes, terms, qoff
+
+    def intersect_batch_dev(self, in_ptrs, in_bytes, queries, out_ids_ptr, out_capacity, stream=None):
+        """intersect_dev for many queries over the batch in_ptrs / in_bytes in one call (DESIGN.md section 3j; no bases
+        are needed).  queries: a sequence of non-empty sequences of batch indices.  The result of query q, exactly what
+        intersect_dev gives for its lists in that order, goes to uint32 entries [offsets[q], offsets[q + 1]) of
+        out_ids_ptr (device, out_capacity entries); returns offsets, np.uint64 of len(queries) + 1.  A total above
+        out_capacity raises AnsxError(ERR_CAPACITY) with .needed = the total and .offsets, except that out_ids_ptr=None,
+        out_capacity=0 is a size query and returns the offsets.  A container no query names is not looked at and may be
+        0.  An AnsxError carries .bad_container / .bad_query where the call set them (None otherwise)."""
+        ptrs, sizes, terms, qoff = self._batch_queries(in_ptrs, in_bytes, queries, out_capacity)
         nc, nq = ptrs.size, len(queries)
         offsets = np.zeros(nq + 1, dtype=np.uint64)
         unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
@@ -652,6 +658,65 @@ class _Codec:
                 err.offsets = offsets
             raise err
         return offsets
+
+    # ---- union (include/ansx.h)
+    def union_batch_dev(self, in_ptrs, in_bytes, queries, out_ids_ptr, out_capacity, out_cnt_ptr=None, stream=None):
+        """Many disjunctive queries over the batch in_ptrs / in_bytes in one call (no bases are needed).  queries: a
+        sequence of non-empty sequences of batch indices.  The distinct docids that occur in any list of query q,
+        ascending, go to uint32 entries [offsets[q], offsets[q + 1]) of out_ids_ptr (device, out_capacity entries) and,
+        when out_cnt_ptr is given (device, uint32, the same capacity and offsets), how often each occurs in the query's
+        lists as named; returns offsets, np.uint64 of len(queries) + 1.  A total above out_capacity raises
+        AnsxError(ERR_CAPACITY) with .needed = the total and .offsets, except that out_ids_ptr=None, out_capacity=0 is a
+        size query and returns the offsets.  A container no query names is not looked at and may be 0.  An AnsxError
+        carries .bad_container / .bad_query where the call set them (None otherwise)."""
+        ptrs, sizes, terms, qoff = self._batch_queries(in_ptrs, in_bytes, queries, out_capacity)
+        nc, nq = ptrs.size, len(queries)
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c, bad_q = C.c_size_t(unset), C.c_size_t(unset)
+        st = L.lib().ansx_union_batch_dev(
+            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None, nc,
+            terms.ctypes.data, qoff.ctypes.data, nq, out_ids_ptr, out_cnt_ptr, int(out_capacity),
+            offsets.ctypes.data, C.byref(bad_c), C.byref(bad_q), stream)
+        if st == L.ERR_CAPACITY and out_ids_ptr is None and int(out_capacity) == 0:
+            return offsets
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".union_batch_dev")
+            err.bad_container = int(bad_c.value) if bad_c.value != unset else None
+            err.bad_query = int(bad_q.value) if bad_q.value != unset else None
+            if st == L.ERR_CAPACITY:
+                err.needed = int(offsets[nq])
+                err.offsets = offsets
+            raise err
+        return offsets
+
+    def union_dev(self, in_ptrs, in_bytes, out_ids_ptr, out_capacity, out_cnt_ptr=None, stream=None):
+        """union_batch_dev's single query over all the lists of the batch in_ptrs / in_bytes, in batch order.  Returns the
+        number of distinct docids; more than out_capacity raises AnsxError(ERR_CAPACITY) with .needed = that number,
+        except that out_ids_ptr=None, out_capacity=0 is a size query and returns the number.  An AnsxError carries
+        .bad_container where the call set it (None otherwise)."""
+        ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
+        if ptrs.size != sizes.size:
+            raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
+        if isinstance(out_capacity, bool) or not isinstance(out_capacity, (int, np.integer)) or out_capacity < 0:
+            raise ValueError("out_capacity must be a non-negative integer, got %r" % (out_capacity,))
+        nc = ptrs.size
+        found = C.c_uint64(0)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c = C.c_size_t(unset)
+        st = L.lib().ansx_union_dev(
+            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None, nc,
+            out_ids_ptr, out_cnt_ptr, int(out_capacity), C.byref(found), C.byref(bad_c), stream)
+        if st == L.ERR_CAPACITY and out_ids_ptr is None and int(out_capacity) == 0:
+            return int(found.value)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".union_dev")
+            err.bad_container = err.container = int(bad_c.value) if bad_c.value != unset else None
+            if st == L.ERR_CAPACITY:
+                err.needed = int(found.value)
+            raise err
+        return int(found.value)
 
 
 class ANSfold(_Codec):

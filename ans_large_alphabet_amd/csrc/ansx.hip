@@ -36,6 +36,7 @@
 #include "ansx_nextgeq.h"
 #include "ansx_intersect.h"
 #include "ansx_intersect_batch.h"
+#include "ansx_union.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
@@ -126,7 +127,7 @@ struct ansx_ctx {
     DevBuf bat_hdr;                       // ansx_decode_batch_dev: input addresses and headers of the batch
     DevBuf enb_plan, enb_wc;              // ansx_encode_batch_dev: a pass's plan and results; its restart points and hints (work area)
     DevBuf isect_ids;                     // ansx_intersect_dev: the driver's ids and the survivors of a step, two arrays of n_driver ints
-    DevBuf isectb_ids, isectb_work;       // ansx_intersect_batch_dev: a group's ids and two candidate buffers; its tables, segments and IsectWork
+    DevBuf isectb_ids, isectb_work;       // ansx_intersect_batch_dev, ansx_union_batch_dev: a group's ids and two candidate buffers; its tables, segments and IsectWork
     u8* isectb_pin = nullptr;             // ... and the pinned host image of its tables (rng_pin belongs to the decode's
     size_t isectb_pin_cap = 0;            //     passes and the scan, whose uploads are under way when the tables go up)
     DevBuf sums_plan, sums_ints;          // running sums and gaps: flag word + list starts + tile aggregates and carries; the gaps of a call (4 bytes per int)
@@ -200,7 +201,7 @@ struct ansx_ctx {
         int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
         u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev, ansx_decode_batch_ranges_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
         int intersect_form = 0;       // ANSX_INTERSECT_FORM: 0 by ANSX_ISECT_FULL_PER_BLOCK, 1 "selective", 2 "full" (tests and the bench tool force one)
-        u64 isect_batch_ints = 0;     // ANSX_ISECT_BATCH_INTS: the ints a group of ansx_intersect_batch_dev may take (0 = ANSX_ISECT_BATCH_INTS_DEFAULT; tests force small groups)
+        u64 isect_batch_ints = 0;     // ANSX_ISECT_BATCH_INTS: the ints a group of ansx_intersect_batch_dev or ansx_union_batch_dev may take (0 = ANSX_ISECT_BATCH_INTS_DEFAULT; tests force small groups)
         u32 range_sums_wg_max = 0;    // ANSX_RANGE_SUMS_WG_MAX: the largest block the one-kernel scan of the range sums takes (0 = ANSX_RS_WG_MAX; the bench tool measures both sides of the switch)
     } dbg;
 };
@@ -3162,6 +3163,126 @@ int intersect_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
     return run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
 }
 
+// ansx_union_batch_dev (ansx_union.h; the plan: ansx_plan.h, unb_plan): the front end of
+// ansx_intersect_batch_dev -- the headers of the referenced containers in one round trip, the groups -> per group
+// (unb_group): its lists decoded back to back into isectb_ids and scanned into ids, one upload of every round's pair
+// table, a launch of k_union_merge per round between the two merge buffers behind the lists, then the unique step over
+// the last round's buffer -- k_union_heads, k_dr_scan, k_isect_compact into the other buffer, k_isectb_bounds and, with
+// counts, k_union_counts -- and one copy per output to the caller.  The context's buffers are those of
+// ansx_intersect_batch_dev (a context runs one call at a time).
+// Workspace: 4 bytes per int of the group's lists and 8 per int of its queries' lists as named (16 with counts: the
+// heads' positions and the counts), a pass's, the scan's, IsectWork over the merge buffer, and 8 bytes per query and 40
+// per pair of tables -- fewer than two pairs per term.
+// Host waits: one for the headers; per group those of its decode passes and ONE more, behind the unique step, which
+// brings the scan's flag word, the total and the queries' bounds: every size between the scan and the unique step is
+// the plan's.  One behind the copies, per call.  None grows with the queries or the rounds.
+int unb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g, std::vector<u64>& off, size_t count,
+    u32* d_out, u32* d_cnt, size_t cap, u64* run, u64* out_offsets, size_t* bad_container, size_t* bad_query, hipStream_t s)
+{
+    int rc;
+    const size_t Q = g.q1 - g.q0, q1 = rup(Q + 1, 4);
+    const u64 L = g.at.back(), M = g.seg[Q];
+    if (M == 0) {  // (every list is empty: nothing is decoded)
+        for (size_t j = 0; j <= Q; j++) out_offsets[g.q0 + j] = *run;
+        return ANSX_OK;
+    }
+    for (const u64 t : g.tiles)
+        if (t > 0x7FFFFFFFull) {  // (a grid; 2^31 non-empty pairs in a round)
+            if (bad_query) *bad_query = g.q0;
+            return ANSX_ERR_ARG;
+        }
+    // the lists | two merge buffers | with counts: the heads' positions | the counts; each with the decoders' slack behind
+    const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)M, 4) + 16;
+    if ((rc = ensure(c, c->isectb_ids, 4 * (o_c + (d_cnt ? 4 : 2) * half)))) return rc;
+    u32* ids = (u32*)c->isectb_ids.p;
+    u32* buf[2] = { ids + o_c, ids + o_c + half };
+    u32* idx = d_cnt ? ids + o_c + 2 * half : nullptr;
+    u32* cnt = d_cnt ? ids + o_c + 3 * half : nullptr;
+    GeometryGroups geo;
+    for (size_t k = 0; k < g.lists.size(); k++) off[g.lists[k]] = g.at[k], geo[br_geometry(F.rs[g.lists[k]].H)].push_back(g.lists[k]);
+    if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, ids, bad_container, s))) return rc;
+
+    // one upload: zero flag words (k_isect_compact's four, k_union_heads' one) | the queries' spans | every round's pairs;
+    // behind it on the device: the bounds among the heads | IsectWork
+    Upload U;
+    const auto s_fl = U.add<u32>(8);
+    const auto s_seg = U.add<u32>(Q + 1);
+    const auto s_p = U.add<ansx_unb_pair>(g.pairs.size());
+    const size_t up = U.end;
+    const auto s_hs = U.add<u32>(q1);  // (the host's copy: read back)
+    const size_t o_w = rup(U.end, 16);
+    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, U.end))) return rc;
+    if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(M, false)))) return rc;
+    U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
+    memset(U.pin(s_fl), 0, s_fl.bytes);
+    U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
+    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
+    const u32* zero = U.dev(s_fl);
+    u32* uflag = U.dev(s_fl) + 4;
+    const u32* seg = U.dev(s_seg);
+    u32* hseg = U.dev(s_hs);
+
+    SumsPlan S;
+    if ((rc = sums_prepare(c, (uintptr_t)ids, L, g.at.data(), g.lists.size(), s, &S))) return rc;
+    if ((rc = sums_launch(c, ids, L, g.lists.size(), S, s))) return rc;
+    for (u32 r = 0; r < g.rounds; r++) {
+        const u32 np = g.roff[r + 1] - g.roff[r];
+        if (np == 0) continue;  // (the queries that have this round are empty)
+        LAUNCH(c, "k_union_merge", k_union_merge, (u32)g.tiles[r], ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)buf[1 - (r & 1u)],
+            buf[r & 1u], (const ansx_unb_pair*)U.dev(s_p) + g.roff[r], np, (const u32*)S.flag);
+    }
+    const u32 fin = (g.rounds - 1u) & 1u;
+    const IsectWork W(U.devp + o_w, M, false);
+    LAUNCH(c, "k_union_heads", k_union_heads, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)buf[fin], (u32)M, seg, (u32)Q, W.ballots,
+        W.counts, (const u32*)S.flag, uflag);
+    LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
+    LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)buf[fin], (u32)M, (const u64*)W.ballots,
+        (const u64*)W.counts, (const u64*)W.total, M, (const u64*)nullptr, buf[1 - fin], idx, (u64*)nullptr, zero, (const u32*)uflag);
+    LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, seg, (u32)Q, (u32)M, (const u64*)W.ballots,
+        (const u64*)W.counts, (const u64*)W.total, hseg);
+    if (d_cnt)
+        LAUNCH(c, "k_union_counts", k_union_counts, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)idx, (const u32*)hseg, seg, (u32)Q,
+            (const u64*)W.total, (u32)M, cnt, (const u32*)S.flag);
+    u32* hflag = &c->pin->isect_sflag;
+    HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(U.pin(s_hs), hseg, 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (*hflag != ANSX_SS_NONE) {  // the first list of the buffer whose sum left 32 bits
+        if (bad_container && *hflag < g.lists.size()) *bad_container = F.ref[g.lists[*hflag]];
+        return ANSX_ERR_DOMAIN;
+    }
+    const u64 nu = c->pin->isect_total;
+    const u32* hs = U.pin(s_hs);
+    for (size_t j = 0; j <= Q; j++) out_offsets[g.q0 + j] = *run + hs[j];
+    if (nu > 0 && *run + nu <= cap) {
+        HIPCHK(c, hipMemcpyAsync(d_out + *run, buf[1 - fin], 4 * (size_t)nu, hipMemcpyDeviceToDevice, s));
+        if (d_cnt) HIPCHK(c, hipMemcpyAsync(d_cnt + *run, cnt, 4 * (size_t)nu, hipMemcpyDeviceToDevice, s));
+    }
+    *run += nu;
+    return ANSX_OK;
+}
+
+int union_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count, const u32* terms,
+    const u64* qoff, size_t nq, u32* d_out, u32* d_cnt, size_t cap, u64* out_offsets, size_t* bad_container, size_t* bad_query,
+    hipStream_t s)
+{
+    int rc;
+    BrFront F;
+    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, terms, (size_t)qoff[nq], nullptr, &F, bad_container, s))) return rc;
+    std::vector<u64> n(F.ref.size());
+    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
+    std::vector<UnbGroup> groups;
+    const u64 budget = c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT;
+    if ((rc = unb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query))) return rc;
+    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
+    u64 run = 0;
+    for (const UnbGroup& g : groups)
+        if ((rc = unb_group(c, kind, f, F, g, off, count, d_out, d_cnt, cap, &run, out_offsets, bad_container, bad_query, s))) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));  // (the copies)
+    return run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
+}
+
 // The argument checks of the random-access entry points, one per argument shape: everything a call decides before the
 // context is touched.  The plain and the sums entry of a shape share them; what a sums or search entry adds (bases,
 // targets, outputs) it checks itself.
@@ -3172,6 +3293,37 @@ int ranges_args(const ansx_ctx* c, const uint8_t* d_in, const uint32_t* d_out, c
     if (!c || !d_in || !d_out) return ANSX_ERR_ARG;
     if (nranges > 0 && (!first || !count)) return ANSX_ERR_ARG;
     if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 3u)) return ANSX_ERR_ARG;
+    return ANSX_OK;
+}
+
+// ... a batch and queries over it (ansx_intersect_batch_dev; ansx_union_batch_dev, which has the optional d_out_cnt)
+int queries_args(const ansx_ctx* c, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count, const uint32_t* terms,
+    const uint64_t* qoff, size_t nqueries, const uint32_t* d_out_ids, const uint32_t* d_out_cnt, size_t out_capacity,
+    const uint64_t* out_offsets, size_t* bad_container, size_t* bad_query)
+{
+    if (!c) return ANSX_ERR_ARG;
+    if (nqueries > 0 && (!d_ins || !in_bytes || !terms || !qoff || !out_offsets)) return ANSX_ERR_ARG;
+    if ((!d_out_ids && out_capacity > 0) || ((uintptr_t)d_out_ids & 3u)) return ANSX_ERR_ARG;
+    if ((d_out_cnt && !d_out_ids) || ((uintptr_t)d_out_cnt & 3u)) return ANSX_ERR_ARG;
+    if (count > 0xFFFFFFFFull || nqueries > 0xFFFFFFFFull || (nqueries > 0 && qoff[nqueries] > 0xFFFFFFFFull)) return ANSX_ERR_ARG;
+    for (size_t q = 0; q < nqueries; q++)
+        if ((q == 0 && qoff[0] != 0) || qoff[q + 1] <= qoff[q]) {  // (an empty query has no list)
+            if (bad_query) *bad_query = q;
+            return ANSX_ERR_ARG;
+        }
+    for (size_t q = 0; q < nqueries; q++)
+        for (u64 j = qoff[q]; j < qoff[q + 1]; j++)
+            if (terms[j] >= count) {
+                if (bad_query) *bad_query = q;
+                return ANSX_ERR_ARG;
+            }
+    for (size_t q = 0; q < nqueries; q++)  // (only the containers some query names are looked at)
+        for (u64 j = qoff[q]; j < qoff[q + 1]; j++)
+            if (!d_ins[terms[j]] || ((uintptr_t)d_ins[terms[j]] & 15u)) {
+                if (bad_query) *bad_query = q;
+                if (bad_container) *bad_container = terms[j];
+                return ANSX_ERR_ARG;
+            }
     return ANSX_OK;
 }
 
@@ -3705,33 +3857,51 @@ int ansx_intersect_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const*
     uint64_t* out_offsets, size_t* bad_container, size_t* bad_query, void* stream)
 {
     // (every argument check comes before the context is touched)
-    if (!c) return ANSX_ERR_ARG;
-    if (nqueries > 0 && (!d_ins || !in_bytes || !terms || !qoff || !out_offsets)) return ANSX_ERR_ARG;
-    if ((!d_out_ids && out_capacity > 0) || ((uintptr_t)d_out_ids & 3u)) return ANSX_ERR_ARG;
-    if (count > 0xFFFFFFFFull || nqueries > 0xFFFFFFFFull || (nqueries > 0 && qoff[nqueries] > 0xFFFFFFFFull)) return ANSX_ERR_ARG;
-    for (size_t q = 0; q < nqueries; q++)
-        if ((q == 0 && qoff[0] != 0) || qoff[q + 1] <= qoff[q]) {  // (an empty query has no driver)
-            if (bad_query) *bad_query = q;
-            return ANSX_ERR_ARG;
-        }
-    for (size_t q = 0; q < nqueries; q++)
-        for (u64 j = qoff[q]; j < qoff[q + 1]; j++)
-            if (terms[j] >= count) {
-                if (bad_query) *bad_query = q;
-                return ANSX_ERR_ARG;
-            }
-    for (size_t q = 0; q < nqueries; q++)  // (only the containers some query names are looked at)
-        for (u64 j = qoff[q]; j < qoff[q + 1]; j++)
-            if (!d_ins[terms[j]] || ((uintptr_t)d_ins[terms[j]] & 15u)) {
-                if (bad_query) *bad_query = q;
-                if (bad_container) *bad_container = terms[j];
-                return ANSX_ERR_ARG;
-            }
+    if (queries_args(c, d_ins, in_bytes, count, terms, qoff, nqueries, d_out_ids, nullptr, out_capacity, out_offsets, bad_container,
+            bad_query))
+        return ANSX_ERR_ARG;
     if (nqueries == 0) return empty_batch(out_offsets, (u64*)nullptr);
     return run_call(c, stream, [&](hipStream_t s) {
         return intersect_batch(c, kind, f, d_ins, in_bytes, count, terms, (const u64*)qoff, nqueries, d_out_ids, out_capacity,
             (u64*)out_offsets, bad_container, bad_query, s);
     });
+}
+
+int ansx_union_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count,
+    const uint32_t* terms, const uint64_t* qoff, size_t nqueries, uint32_t* d_out_ids, uint32_t* d_out_cnt, size_t out_capacity,
+    uint64_t* out_offsets, size_t* bad_container, size_t* bad_query, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (queries_args(c, d_ins, in_bytes, count, terms, qoff, nqueries, d_out_ids, d_out_cnt, out_capacity, out_offsets, bad_container,
+            bad_query))
+        return ANSX_ERR_ARG;
+    if (nqueries == 0) return empty_batch(out_offsets, (u64*)nullptr);
+    return run_call(c, stream, [&](hipStream_t s) {
+        return union_batch(c, kind, f, d_ins, in_bytes, count, terms, (const u64*)qoff, nqueries, d_out_ids, d_out_cnt, out_capacity,
+            (u64*)out_offsets, bad_container, bad_query, s);
+    });
+}
+
+int ansx_union_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count,
+    uint32_t* d_out_ids, uint32_t* d_out_cnt, size_t out_capacity, uint64_t* nfound, size_t* bad_container, void* stream)
+{
+    // the batch call with the one query 0, 1, ..., count - 1
+    if (!c || count == 0 || count > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    std::vector<u32> terms;
+    try {
+        terms.resize(count);
+    } catch (const std::bad_alloc&) {
+        c->last_hip = (int)hipErrorOutOfMemory;
+        return ANSX_ERR_HIP;
+    }
+    for (size_t i = 0; i < count; i++) terms[i] = (u32)i;
+    const uint64_t qoff[2] = { 0, (uint64_t)count };
+    uint64_t offs[2] = { 0, 0 };
+    size_t bad_query = 0;
+    const int rc = ansx_union_batch_dev(c, kind, f, d_ins, in_bytes, count, terms.data(), qoff, 1, d_out_ids, d_out_cnt, out_capacity,
+        offs, bad_container, &bad_query, stream);
+    if ((rc == ANSX_OK || rc == ANSX_ERR_CAPACITY) && nfound) *nfound = offs[1];
+    return rc;
 }
 
 int ansx_block_bases_dev(ansx_ctx* c, int kind, int f, const uint8_t* d_in, size_t in_bytes, uint32_t* d_bases,

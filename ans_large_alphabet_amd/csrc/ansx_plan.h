@@ -2,9 +2,10 @@
 // which blocks a set of ranges touches, where every range's ints lie in the work list those blocks decode to, and the
 // tables a pass over blocks of many containers takes; and the steps and pass tables of a batch of lists to encode
 // (ansx_encode_batch_dev); and the groups, drivers and round tables of a batch of conjunctive queries
-// (ansx_intersect_batch_dev).  Pure host arithmetic: no context, no stream, no device pointer
+// (ansx_intersect_batch_dev); and the groups, rounds and pair tables of a batch of disjunctive queries
+// (ansx_union_batch_dev).  Pure host arithmetic: no context, no stream, no device pointer
 // (addresses travel as integers), so it builds with a plain host compiler and is tested on the CPU
-// (tests/tools/plan_check.cpp, tests/tools/isect_batch_plan_check.cpp).  The plain structs the kernels read these plans through are in ansx_plan_types.h,
+// (tests/tools/plan_check.cpp, tests/tools/isect_batch_plan_check.cpp, tests/tools/union_plan_check.cpp).  The plain structs the kernels read these plans through are in ansx_plan_types.h,
 // which the kernel headers include.
 #pragma once
 #include "../../include/ansx.h"
@@ -440,6 +441,8 @@ static inline bool encb_pass_tables(const u64* offsets, size_t l0, size_t l1, u6
 // The ints a group may take -- its referenced lists once and its drivers' twice (two candidate buffers) -- unless
 // ANSX_ISECT_BATCH_INTS says otherwise: 2^28 ints, 1 GiB of workspace, the size of section 3h's batch of 4096 lists of
 // 64 Ki ids.  A bound on the workspace, not a tuned value: no other budget has been measured.
+// ansx_union_batch_dev's groups take the same budget: their lists once and their queries' lists as named twice (two
+// merge buffers).
 #define ANSX_ISECT_BATCH_INTS_DEFAULT ((u64)1 << 28)
 
 struct IsbGroup {
@@ -517,6 +520,128 @@ static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64*
         }
         g.G[Q] = { 0, dst };
         g.rt_off[Q] = (u32)g.rt.size();
+    }
+    return ANSX_OK;
+}
+
+// ------------------------------------------------------------------------------- batches of disjunctive queries
+// ansx_union_batch_dev cuts its queries, in order, into groups as isb_plan does, under the same
+// budget (ANSX_ISECT_BATCH_INTS): the group's referenced lists once and, twice, the ints of every query's lists as
+// named -- the two merge buffers, in which query j's runs stand back to back in query order from seg[j] on.
+//
+// A query of m terms takes rq = max(1, ceil(log2 m)) rounds of pairwise merges; the group takes R, the most of its
+// queries, and query j runs in the LAST rq of them, so that all queries end in the same buffer and none is copied
+// through a round it has no merge in.  Its first round reads the runs where the decode left them, in the buffer of
+// lists; round r writes merge buffer r & 1 and, from a query's second round on, reads the other.  In its local round
+// k, runs 2i and 2i + 1 of 2^k terms each become one at the place of the first; a run without a partner is a pair
+// with nb = 0.  A pair of no ints is left out.  A pair's span is the same before and after, so every offset of every
+// round is known here.
+
+struct UnbGroup {
+    size_t q0, q1;                     // its queries
+    std::vector<u32> lists;            // the non-empty referenced lists it decodes, ascending: its buffer, back to back
+    std::vector<u64> at;               // lists.size() + 1: where each one's ids start in the buffer; the last: its ints
+    std::vector<u32> seg;              // q1 - q0 + 1: query j's span of the merge buffers; the last: their ints
+    std::vector<ansx_unb_pair> pairs;  // every round's pairs, round after round, queries in order inside a round
+    std::vector<u32> roff;             // rounds + 1: round r's pairs are pairs[roff[r] .. roff[r + 1])
+    std::vector<u64> tiles;            // rounds: the tiles of round r
+    u64 ints;                          // buffer + twice the merge buffer: what the budget bounds
+    u32 rounds;                        // R
+};
+
+static inline u32 unb_rounds(u64 m)
+{
+    u32 r = 0;
+    while (((u64)1 << r) < m) r++;
+    return r ? r : 1u;
+}
+
+// -> ANSX_OK, or ANSX_ERR_ARG with *bad_query the first query whose lists together have 2^32 ints or more (a run offset
+// is a u32).  A group ends in front of the query that would take it over `budget` ints or its merge buffer to 2^32; a
+// query over the budget alone is a group of its own.  A list two groups name is decoded in both.  tile: the outputs
+// of a workgroup of the merge.
+static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64* qoff, size_t nq, u64 budget, u32 tile,
+    std::vector<UnbGroup>* groups, size_t* bad_query)
+{
+    groups->clear();
+    std::vector<u64> tot(nq);
+    for (size_t q = 0; q < nq; q++) {
+        u64 a = 0;
+        for (u64 j = qoff[q]; j < qoff[q + 1] && a <= 0xFFFFFFFFull; j++) a = n[rid[j]] > 0xFFFFFFFFull ? ~0ull : a + n[rid[j]];
+        if (a > 0xFFFFFFFFull) {
+            if (bad_query) *bad_query = q;
+            return ANSX_ERR_ARG;
+        }
+        tot[q] = a;
+    }
+    std::vector<u32> stamp(nref, 0xFFFFFFFFu), slot(nref, 0), fresh;
+    std::vector<std::vector<ansx_unb_pair>> byround;
+    std::vector<std::pair<u32, u32>> runs;  // (where in the merge buffers, ints)
+    for (size_t q = 0; q < nq;) {
+        groups->emplace_back();
+        UnbGroup& g = groups->back();
+        const u32 gid = (u32)(groups->size() - 1);
+        g.q0 = q, g.ints = 0, g.rounds = 1;
+        u64 merge = 0;
+        for (; q < nq; q++) {  // the queries it takes
+            const u32* t = rid + qoff[q];
+            const size_t m = (size_t)(qoff[q + 1] - qoff[q]);
+            u64 add = 0;
+            fresh.clear();
+            for (size_t j = 0; j < m; j++)
+                if (stamp[t[j]] != gid) stamp[t[j]] = gid, fresh.push_back(t[j]), add += n[t[j]];
+            add += 2 * tot[q];
+            // (the stamps of a query that does not fit stay behind: the next group has another number)
+            if (q > g.q0 && (add > budget || g.ints > budget - add || merge + tot[q] > 0xFFFFFFFFull)) break;
+            for (const u32 r : fresh)
+                if (n[r]) g.lists.push_back(r);
+            g.ints += add, merge += tot[q];
+            g.rounds = std::max(g.rounds, unb_rounds(m));
+        }
+        g.q1 = q;
+        std::sort(g.lists.begin(), g.lists.end());
+        g.at.resize(g.lists.size() + 1);
+        u64 at = 0;
+        for (size_t k = 0; k < g.lists.size(); k++) g.at[k] = at, slot[g.lists[k]] = (u32)k, at += n[g.lists[k]];
+        g.at.back() = at;
+        const size_t Q = g.q1 - g.q0;
+        const u32 R = g.rounds;
+        g.seg.resize(Q + 1);
+        byround.assign(R, {});
+        u32 dst = 0;
+        for (size_t j = 0; j < Q; j++) {
+            const u32* t = rid + qoff[g.q0 + j];
+            const size_t m = (size_t)(qoff[g.q0 + j + 1] - qoff[g.q0 + j]);
+            g.seg[j] = dst;
+            runs.resize(m);
+            for (size_t k = 0; k < m; k++) runs[k] = { dst, (u32)n[t[k]] }, dst += (u32)n[t[k]];
+            const u32 rq = unb_rounds(m);
+            size_t have = m;
+            for (u32 k = 0; k < rq; k++, have = (have + 1) / 2)
+                for (size_t i = 0; 2 * i < have; i++) {
+                    const std::pair<u32, u32> A = runs[2 * i], B = 2 * i + 1 < have ? runs[2 * i + 1] : std::pair<u32, u32>(0, 0);
+                    runs[i] = { A.first, A.second + B.second };
+                    if (A.second + B.second == 0) continue;
+                    ansx_unb_pair p = { A.first, B.first, A.second, B.second, A.first, 0, 0, 0 };
+                    if (k == 0) {  // where the decode left them
+                        const u32 ra = t[2 * i], rb = 2 * i + 1 < m ? t[2 * i + 1] : ra;
+                        p.a = A.second ? g.at[slot[ra]] : 0, p.b = B.second ? g.at[slot[rb]] : 0, p.from_lists = 1;
+                    }
+                    byround[R - rq + k].push_back(p);
+                }
+        }
+        g.seg[Q] = dst;
+        g.roff.assign(1, 0), g.tiles.clear();
+        for (u32 r = 0; r < R; r++) {
+            u64 first = 0;
+            for (ansx_unb_pair& p : byround[r]) {
+                p.tile = (u32)first;  // (the caller refuses a round of 2^31 tiles or more)
+                first += ((u64)p.na + p.nb + tile - 1) / tile;
+            }
+            g.pairs.insert(g.pairs.end(), byround[r].begin(), byround[r].end());
+            g.roff.push_back((u32)g.pairs.size());
+            g.tiles.push_back(first);
+        }
     }
     return ANSX_OK;
 }

@@ -128,3 +128,14 @@ struct ansx_isb_query {  // query j of the group: its driver's ids lie from src 
 struct ansx_isb_list {  // a round of a query: the list's ids [at, at + n) of the buffer; an empty list has n = 0
     u64 at, n;
 };
+
+// A group of disjunctive queries (ansx_union_batch_dev, ansx_union.h).  A pair of a round: the sorted runs A and B
+// become one sorted run of na + nb ints at dst of the round's merge buffer.  from_lists: a and b count in ints of the
+// group's buffer of ids (the pair is the first of its query); otherwise in ints of the other merge buffer, where
+// a == dst and b == a + na.  nb == 0: a copy.  tile: the round's tiles of ANSX_UNION_TILE outputs in front of this pair.
+struct ansx_unb_pair {
+    u64 a, b;
+    u32 na, nb;
+    u32 dst, tile;
+    u32 from_lists, pad_;
+};

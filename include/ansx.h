@@ -643,6 +643,54 @@ int ansx_intersect_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_
     size_t count, const uint32_t* terms, const uint64_t* qoff, size_t nqueries, uint32_t* d_out_ids, size_t out_capacity,
     uint64_t* out_offsets, size_t* bad_container, size_t* bad_query, void* stream);
 
+/* ansx_union_batch_dev: many disjunctive queries over one batch of gap-coded lists in one call.
+ * The batch, terms, qoff, out_offsets, bad_container and bad_query are ansx_intersect_batch_dev's: HOST arrays of
+ * 16-byte aligned DEVICE pointers, mixed geometries allowed; a list may appear in many queries and more than once in
+ * one; containers no query names are not examined and may be NULL.  No block bases are needed.
+ * d_out_ids[out_offsets[q] .. out_offsets[q + 1]) are the distinct ids that occur in at least one of the lists of
+ * query q, ascending, each once: with s_t what ansx_decode_sums_dev returns for list t, the sorted distinct values of
+ * the concatenation of s_t over the query's terms.  d_out_cnt (optional; DEVICE, 4-byte aligned, shares out_capacity and
+ * out_offsets) holds for every id written the number of entries equal to it in that concatenation: for lists without
+ * repeated ids the number of matching terms; a list named twice counts twice, a list's own repeats count.  A one-term
+ * query gives that list's distinct ids.  0xFFFFFFFF is an id like any other; nothing compares with ANSX_NO_ID.
+ * d_out_ids: DEVICE, 4-byte aligned, out_capacity entries; NULL only with out_capacity == 0.
+ * How it runs: the headers of the referenced containers in one round trip; the queries are cut, in order, into groups
+ * whose referenced lists plus twice the ints of their queries' lists as named stay within 2^28 ints
+ * (ANSX_ISECT_BATCH_INTS; a query above it is a group of its own; a list two groups name is decoded in both) and whose
+ * queries' lists stay below 2^32 ints together.  Per group: its lists are decoded whole, back to back, by the passes of
+ * ansx_decode_batch_dev; one segmented scan makes them ids, so every list is a sorted run; ceil(log2(most terms of a
+ * query)) rounds, at least one, of pairwise merges over ALL queries at once, one launch each, from host-made tables (a
+ * query of fewer terms joins in the last rounds, its first round reading the decoded lists where they lie); the first
+ * of every run of equal ids inside a query is kept and compacted, its count the distance to the next; one copy per
+ * output to the caller.
+ * Errors, in this order: before the context is touched, ansx_intersect_batch_dev's argument checks with the same
+ * *bad_query / *bad_container, and ANSX_ERR_ARG for a misaligned d_out_cnt or one given with a NULL d_out_ids.
+ * nqueries == 0: ANSX_OK, nothing is launched, the context is untouched.  Then ANSX_ERR_FORMAT with *bad_container = the
+ * smallest batch index of a referenced container whose header fails decode_dev's checks;
+ *   ANSX_ERR_ARG with *bad_query = the first query whose lists together have 2^32 ints or more (a run offset has 32
+ *   bits), or the first query of a group one of whose rounds would take 2^31 workgroups or more;
+ *   found on the device: ANSX_ERR_FORMAT with *bad_container = count for a bad stream or index entry; ANSX_ERR_DOMAIN
+ *   with *bad_container = a referenced list whose sum leaves 32 bits -- of the first group at fault, the first in the
+ *   order of its buffer (ascending batch index);
+ *   ANSX_ERR_CAPACITY when the total exceeds out_capacity: out_offsets is complete, so d_out_ids = NULL, out_capacity = 0
+ *   is a size query; nothing is written at or beyond out_capacity in either output, what lies below is unspecified.
+ * No trace is left in the context, which stays usable after any error.  Workspace: per group 4 bytes per int of its
+ * lists and 8 per int of its queries' lists as named (16 with d_out_cnt), a decode pass's, 16 bytes per 4096 ints for
+ * the scan, 8 bytes per 64 merged ints, 8 bytes per query and 40 per pair, fewer than two pairs per term.  Host waits:
+ * one for the headers; per group those of its decode passes and one behind the unique step (the scan's flag word, the
+ * total and the queries' bounds; no size in between depends on the data); one per call behind the copies.  None grows
+ * with the number of queries or of rounds. */
+int ansx_union_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    size_t count, const uint32_t* terms, const uint64_t* qoff, size_t nqueries, uint32_t* d_out_ids, uint32_t* d_out_cnt,
+    size_t out_capacity, uint64_t* out_offsets, size_t* bad_container, size_t* bad_query, void* stream);
+
+/* ansx_union_dev: the batch call above with the single query 0, 1, ..., count - 1 -- a thin wrapper, not a second
+ * path.  *nfound (optional, host): the number of distinct ids, set on ANSX_OK and ANSX_ERR_CAPACITY, so d_out_ids = NULL,
+ * out_capacity = 0 is a size query.  count == 0: ANSX_ERR_ARG, as in ansx_intersect_dev.  Every other error as above. */
+int ansx_union_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    size_t count, uint32_t* d_out_ids, uint32_t* d_out_cnt, size_t out_capacity, uint64_t* nfound,
+    size_t* bad_container, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
@@ -803,8 +851,9 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
  * tests/tools/bench_model_chain.py), ANSX_INTERSECT_FORM ("selective" | "full"; ""/"0"/NULL: by the candidates per block;
  * anything else: ANSX_ERR_ARG -- the form of every step of ansx_intersect_ids_dev and ansx_intersect_dev; for the tests,
  * which compare the two, and the timing of tests/tools/bench_intersect.py), ANSX_ISECT_BATCH_INTS (number: the ints a
- * group of ansx_intersect_batch_dev may take, its lists once and its drivers' twice; ""/"0"/NULL: 2^28 -- the results
- * do not depend on it; the tests force several groups and a group per query);
+ * group of ansx_intersect_batch_dev may take, its lists once and its drivers' twice, and a group of ansx_union_batch_dev,
+ * its lists once and its queries' lists as named twice; ""/"0"/NULL: 2^28 -- the results do not depend on it; the tests
+ * force several groups and a group per query);
  * through this call only (round 4): ANSX_NO_PC / ANSX_FORCE_PC / ANSX_NO_PC_AUTO / ANSX_PC_B_PAIRS (the producer /
  * consumer encoder never / whatever the list length / only on request; pairs per workgroup of its two-round shape),
  * ANSX_ENCODE_MODE2, ANSX_DECODE_PAIR, ANSX_DECODE_SMALL_RING ("never" | "always"; ""/"0"/NULL: the default; anything
