@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libansx.so")
 FOLD, RFOLD, MSB, INT = 0, 1, 2, 3
 FLAG_COMPACT_ALPHABET = 1
 OK, ERR_ARG, ERR_CAPACITY, ERR_FORMAT, ERR_HIP, ERR_NO_DEVICE, ERR_DOMAIN, ERR_MODEL = range(8)
+BOOL_ALL, BOOL_ANY = 0, 1  # the op of ansx_bool_batch_dev
 SINGLE_STREAM = 0xFFFFFFFF
 NO_CHECKPOINTS = 0xFFFFFFFF
 DEFAULT_BLOCK_INTS = 16384
@@ -34,6 +35,7 @@ EXPORTS = [
     "ansx_decode_device_ranges_sums_dev", "ansx_next_geq_dev", "ansx_encode_batch_gaps_bases_dev",
     "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
     "ansx_intersect_ids_dev", "ansx_intersect_dev", "ansx_intersect_batch_dev", "ansx_union_batch_dev", "ansx_union_dev",
+    "ansx_bool_batch_dev",
 ]
 
 
@@ -185,6 +187,8 @@ def lib():
     L.ansx_intersect_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, vp, sz, vp, C.POINTER(sz), C.POINTER(sz), vp]
     L.ansx_union_batch_dev.restype = C.c_int
     L.ansx_union_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, C.POINTER(sz), C.POINTER(sz), vp]
+    L.ansx_bool_batch_dev.restype = C.c_int
+    L.ansx_bool_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, C.c_int, vp, vp, vp, vp, sz, vp, sz, vp, C.POINTER(sz), C.POINTER(sz), vp]
     L.ansx_union_dev.restype = C.c_int
     L.ansx_union_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(sz), vp]
     L.ansx_container_info.restype = C.c_int

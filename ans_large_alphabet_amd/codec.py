@@ -612,23 +612,29 @@ class _Codec:
             raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
         if isinstance(out_capacity, bool) or not isinstance(out_capacity, (int, np.integer)) or out_capacity < 0:
             raise ValueError("out_capacity must be a non-negative integer, got %r" % (out_capacity,))
+        terms, qoff = _Codec._flatten_queries(queries, "queries", "query")
+        return ptrs, sizes, terms, qoff
+
+    @staticmethod
+    def _flatten_queries(queries, what, one):
+        """A sequence of sequences of batch indices -> (terms, qoff), the flat uint32 and uint64 host arrays of a call"""
         if isinstance(queries, (str, bytes)) or not hasattr(queries, "__len__"):
-            raise ValueError("queries must be a sequence of sequences of batch indices")
+            raise ValueError("%s must be a sequence of sequences of batch indices" % what)
         qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
         flat = []
         for q, terms in enumerate(queries):
             if isinstance(terms, (str, bytes)) or not hasattr(terms, "__len__"):
-                raise ValueError("query %d is not a sequence of batch indices" % q)
+                raise ValueError("%s %d is not a sequence of batch indices" % (one, q))
             t = np.asarray(terms)
             if t.ndim != 1 or (t.size and t.dtype.kind not in "ui"):
-                raise ValueError("query %d must be a flat sequence of integers" % q)
+                raise ValueError("%s %d must be a flat sequence of integers" % (one, q))
             if t.size and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
-                raise ValueError("query %d names a list outside [0, 2^32)" % q)
+                raise ValueError("%s %d names a list outside [0, 2^32)" % (one, q))
             flat.append(t.astype(np.uint32))
             qoff[q + 1] = qoff[q] + np.uint64(t.size)
         # (never empty, so that the library and not a null array answers queries that are all empty)
         terms = np.ascontiguousarray(np.concatenate(flat + [np.zeros(1, dtype=np.uint32)]), dtype=np.uint32)
-        return ptrs, sizes, terms, qoff
+        return terms, qoff
 
     def intersect_batch_dev(self, in_ptrs, in_bytes, queries, out_ids_ptr, out_capacity, stream=None):
         """intersect_dev for many queries over the batch in_ptrs / in_bytes in one call (no bases
@@ -682,6 +688,44 @@ class _Codec:
             return offsets
         if st != L.OK:
             err = L.AnsxError(st, self.name() + ".union_batch_dev")
+            err.bad_container = int(bad_c.value) if bad_c.value != unset else None
+            err.bad_query = int(bad_q.value) if bad_q.value != unset else None
+            if st == L.ERR_CAPACITY:
+                err.needed = int(offsets[nq])
+                err.offsets = offsets
+            raise err
+        return offsets
+
+    # ---- Boolean queries with exclusion (include/ansx.h)
+    def bool_batch_dev(self, in_ptrs, in_bytes, queries, excludes, out_ids_ptr, out_capacity, op="all", stream=None):
+        """Many Boolean queries over the batch in_ptrs / in_bytes in one call.  queries: as for intersect_batch_dev;
+        op "all" intersects a query's lists (intersect_batch_dev's result), "any" unites them (union_batch_dev's ids).
+        excludes: None, or a sequence as long as queries of (possibly empty) sequences of batch indices: every docid
+        that occurs in one of query q's excluded lists is removed from its result.  Outputs, offsets (np.uint64 of
+        len(queries) + 1), the size query and the errors are intersect_batch_dev's; an AnsxError carries .bad_container
+        / .bad_query where the call set them (None otherwise)."""
+        ops = {"all": L.BOOL_ALL, "any": L.BOOL_ANY}
+        if op not in ops:
+            raise ValueError("op must be 'all' or 'any', got %r" % (op,))
+        ptrs, sizes, terms, qoff = self._batch_queries(in_ptrs, in_bytes, queries, out_capacity)
+        nc, nq = ptrs.size, len(queries)
+        xterms = xqoff = None
+        if excludes is not None:
+            xterms, xqoff = self._flatten_queries(excludes, "excludes", "excludes of query")
+            if xqoff.size != nq + 1:
+                raise ValueError("excludes and queries differ in length (%d, %d)" % (xqoff.size - 1, nq))
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c, bad_q = C.c_size_t(unset), C.c_size_t(unset)
+        st = L.lib().ansx_bool_batch_dev(
+            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None, nc,
+            ops[op], terms.ctypes.data, qoff.ctypes.data, None if xterms is None else xterms.ctypes.data,
+            None if xqoff is None else xqoff.ctypes.data, nq, out_ids_ptr, int(out_capacity),
+            offsets.ctypes.data, C.byref(bad_c), C.byref(bad_q), stream)
+        if st == L.ERR_CAPACITY and out_ids_ptr is None and int(out_capacity) == 0:
+            return offsets
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".bool_batch_dev")
             err.bad_container = int(bad_c.value) if bad_c.value != unset else None
             err.bad_query = int(bad_q.value) if bad_q.value != unset else None
             if st == L.ERR_CAPACITY:

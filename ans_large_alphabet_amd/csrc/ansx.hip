@@ -37,6 +37,7 @@
 #include "ansx_intersect.h"
 #include "ansx_intersect_batch.h"
 #include "ansx_union.h"
+#include "ansx_bool.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
@@ -200,6 +201,7 @@ struct ansx_ctx {
         double fast_guard = ANSX_FAST_GUARD;  // ANSX_FAST_GUARD: relative guard band of the fast model path's stop rule (tests widen it)
         int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
         u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev, ansx_decode_batch_ranges_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
+        int bool_form = 0;            // ANSX_BOOL_FORM: 0 k_bool_exclude's own rule, 1 "search", 2 "staged" (ANSX_BOOL_FORM_*; tests and the bench tool force one)
         int intersect_form = 0;       // ANSX_INTERSECT_FORM: 0 by ANSX_ISECT_FULL_PER_BLOCK, 1 "selective", 2 "full" (tests and the bench tool force one)
         u64 isect_batch_ints = 0;     // ANSX_ISECT_BATCH_INTS: the ints a group of ansx_intersect_batch_dev or ansx_union_batch_dev may take (0 = ANSX_ISECT_BATCH_INTS_DEFAULT; tests force small groups)
         u32 range_sums_wg_max = 0;    // ANSX_RANGE_SUMS_WG_MAX: the largest block the one-kernel scan of the range sums takes (0 = ANSX_RS_WG_MAX; the bench tool measures both sides of the switch)
@@ -3058,6 +3060,24 @@ int intersect_lists(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
     return ANSX_OK;
 }
 
+// The exclusion step of ansx_bool_batch_dev (ansx_bool.h) behind either positive phase: the n candidates of `cand`
+// (d_total: null, or where the device holds how many of them there are), query j's in [seg[j], seg[j + 1]), that are in
+// none of their query's lists xt[xo[j] .. xo[j + 1]) -> out, their bounds -> nseg, their count -> W.total.  gf / df:
+// k_isect_compact's two flag words.  Enqueues only.
+int bool_exclude_step(ansx_ctx* c, const IsectWork& W, const u32* ids, const u32* cand, u32 n, const u64* d_total, const u32* seg,
+    size_t Q, const u32* xo, const ansx_isb_list* xt, const u32* sflag, u32* out, u32* nseg, const u32* gf, const u32* df,
+    hipStream_t s)
+{
+    LAUNCH(c, "k_bool_exclude", k_bool_exclude, W.ntiles, ANSX_ISECT_NT, 0, s, ids, cand, n, d_total, seg, (u32)Q, xo, xt,
+        (u32)c->dbg.bool_form, W.ballots, W.counts, sflag);
+    LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
+    LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, cand, n, (const u64*)W.ballots, (const u64*)W.counts,
+        (const u64*)W.total, (u64)n, (const u64*)nullptr, out, (u32*)nullptr, (u64*)nullptr, gf, df);
+    LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, seg, (u32)Q, n, (const u64*)W.ballots,
+        (const u64*)W.counts, (const u64*)W.total, nseg);
+    return ANSX_OK;
+}
+
 // ansx_intersect_batch_dev (ansx_intersect_batch.h; the plan: ansx_plan.h, isb_plan): the headers
 // of the referenced containers in one round trip (batch_ranges_front) -> the groups -> per group (isb_group): its lists
 // decoded back to back into isectb_ids by the passes of ansx_decode_batch_dev, one segmented scan over all of them,
@@ -3070,6 +3090,8 @@ int intersect_lists(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
 // final read-back, one more where the form validates the index first), ONE for the scan's flag word and ONE per round,
 // which brings the members' count (and, with the last round, the segments); one behind the copies, per call.  None
 // grows with the number of queries.
+// A group of ansx_bool_batch_dev that excludes something (g.xt) adds its second table to the upload and, where the
+// rounds leave candidates, bool_exclude_step and ONE wait behind it; without g.xt nothing here differs.
 int isb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& g, std::vector<u64>& off, size_t count,
     u32* d_out, size_t cap, u64* run, u64* out_offsets, size_t* bad_container, hipStream_t s)
 {
@@ -3095,6 +3117,9 @@ int isb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& g,
     const auto s_g = U.add<ansx_isb_query>(Q + 1);
     const auto s_ro = U.add<u32>(Q + 1);
     const auto s_rt = U.add<ansx_isb_list>(g.rt.size());
+    const bool excl = !g.xt.empty();  // (ansx_bool_batch_dev only: the group excludes something)
+    const auto s_xo = U.add<u32>(excl ? Q + 1 : 0);
+    const auto s_xt = U.add<ansx_isb_list>(g.xt.size());
     const size_t up = U.end;
     const auto s_seg = U.add<u32>(2 * q1);  // (the host's copy: the last round's, read back)
     const size_t o_w = rup(U.end, 16);
@@ -3104,6 +3129,7 @@ int isb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& g,
     memset(U.pin(s_fl), 0, s_fl.bytes);
     U.put(s_g, g.G.data()), U.put(s_ro, g.rt_off.data());
     if (!g.rt.empty()) U.put(s_rt, g.rt.data());
+    if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
     HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
     u32* seg[2] = { U.dev(s_seg), U.dev(s_seg) + q1 };
     const u32* zero = U.dev(s_fl);
@@ -3136,9 +3162,21 @@ int isb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& g,
         HIPCHK(c, hipStreamSynchronize(s));
         nc = (u32)c->pin->isect_total, cur = 1 - cur;
     }
-    // the segments behind the last round: the drivers' (no round), what came back, or nothing left
+    const bool xran = excl && nc > 0;
+    if (xran) {  // ONE exclusion step over what the rounds left (ansx_bool.h), and one more wait
+        const IsectWork W(U.devp + o_w, nc, false);
+        if ((rc = bool_exclude_step(c, W, ids, buf[cur], nc, nullptr, seg[cur], Q, U.dev(s_xo), U.dev(s_xt), (const u32*)S.flag,
+                 buf[1 - cur], seg[1 - cur], zero, zero, s)))
+            return rc;
+        HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(U.pin(s_seg), seg[1 - cur], 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        nc = (u32)c->pin->isect_total, cur = 1 - cur;
+    }
+    // the segments behind the last step: the drivers' (none), what came back, or nothing left
     const u32* hseg = U.pin(s_seg);
-    for (size_t j = 0; j <= Q; j++) out_offsets[g.q0 + j] = *run + (g.rounds == 0 ? g.G[j].dst : r == g.rounds ? hseg[j] : 0);
+    for (size_t j = 0; j <= Q; j++)
+        out_offsets[g.q0 + j] = *run + (xran ? hseg[j] : g.rounds == 0 ? g.G[j].dst : r == g.rounds ? hseg[j] : 0);
     if (nc > 0 && *run + nc <= cap) HIPCHK(c, hipMemcpyAsync(d_out + *run, buf[cur], 4 * (size_t)nc, hipMemcpyDeviceToDevice, s));
     *run += nc;
     return ANSX_OK;
@@ -3176,6 +3214,8 @@ int intersect_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
 // Host waits: one for the headers; per group those of its decode passes and ONE more, behind the unique step, which
 // brings the scan's flag word, the total and the queries' bounds: every size between the scan and the unique step is
 // the plan's.  One behind the copies, per call.  None grows with the queries or the rounds.
+// A group of ansx_bool_batch_dev that excludes something (g.xt) adds its second table to the upload and
+// bool_exclude_step in front of that one wait (the heads' count stays on the device); without g.xt nothing here differs.
 int unb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g, std::vector<u64>& off, size_t count,
     u32* d_out, u32* d_cnt, size_t cap, u64* run, u64* out_offsets, size_t* bad_container, size_t* bad_query, hipStream_t s)
 {
@@ -3208,14 +3248,19 @@ int unb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g,
     const auto s_fl = U.add<u32>(8);
     const auto s_seg = U.add<u32>(Q + 1);
     const auto s_p = U.add<ansx_unb_pair>(g.pairs.size());
+    const bool excl = !g.xt.empty();  // (ansx_bool_batch_dev only: the group excludes something)
+    const auto s_xo = U.add<u32>(excl ? Q + 1 : 0);
+    const auto s_xt = U.add<ansx_isb_list>(g.xt.size());
     const size_t up = U.end;
     const auto s_hs = U.add<u32>(q1);  // (the host's copy: read back)
+    const auto s_xs = U.add<u32>(excl ? q1 : 0);  // (the bounds behind the exclusion step)
     const size_t o_w = rup(U.end, 16);
     if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, U.end))) return rc;
     if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(M, false)))) return rc;
     U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
     memset(U.pin(s_fl), 0, s_fl.bytes);
     U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
+    if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
     HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
     const u32* zero = U.dev(s_fl);
     u32* uflag = U.dev(s_fl) + 4;
@@ -3243,6 +3288,13 @@ int unb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g,
     if (d_cnt)
         LAUNCH(c, "k_union_counts", k_union_counts, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)idx, (const u32*)hseg, seg, (u32)Q,
             (const u64*)W.total, (u32)M, cnt, (const u32*)S.flag);
+    u32* res = buf[1 - fin];
+    if (excl) {  // ONE exclusion step over the heads (ansx_bool.h): their count stays on the device, no wait is added
+        if ((rc = bool_exclude_step(c, W, ids, buf[1 - fin], (u32)M, W.total, hseg, Q, U.dev(s_xo), U.dev(s_xt), (const u32*)S.flag,
+                 buf[fin], U.dev(s_xs), zero, uflag, s)))
+            return rc;
+        hseg = U.dev(s_xs), res = buf[fin];
+    }
     u32* hflag = &c->pin->isect_sflag;
     HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
@@ -3256,7 +3308,7 @@ int unb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g,
     const u32* hs = U.pin(s_hs);
     for (size_t j = 0; j <= Q; j++) out_offsets[g.q0 + j] = *run + hs[j];
     if (nu > 0 && *run + nu <= cap) {
-        HIPCHK(c, hipMemcpyAsync(d_out + *run, buf[1 - fin], 4 * (size_t)nu, hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(d_out + *run, res, 4 * (size_t)nu, hipMemcpyDeviceToDevice, s));
         if (d_cnt) HIPCHK(c, hipMemcpyAsync(d_cnt + *run, cnt, 4 * (size_t)nu, hipMemcpyDeviceToDevice, s));
     }
     *run += nu;
@@ -3279,6 +3331,44 @@ int union_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size
     u64 run = 0;
     for (const UnbGroup& g : groups)
         if ((rc = unb_group(c, kind, f, F, g, off, count, d_out, d_cnt, cap, &run, out_offsets, bad_container, bad_query, s))) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));  // (the copies)
+    return run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
+}
+
+// ansx_bool_batch_dev (ansx_bool.h): the front end of the two calls above over the terms followed
+// by the excluded terms -- still one round trip for the headers -- then the plan of the chosen op with the excluded
+// lists (plan_excl_tables) and the op's own groups, which run the exclusion step where a group excludes something.
+// Workspace: the parent's, the excluded lists among the group's lists, and 4 bytes per query and 16 per excluded term
+// of tables (ANY: 4 more per query of bounds).  Host waits: ALL one more per group that excludes something and has
+// candidates left behind its rounds; ANY none more -- the heads' count stays on the device.
+int bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count, int op, const u32* terms,
+    const u64* qoff, const u32* xterms, const u64* xqoff, size_t nq, u32* d_out, size_t cap, u64* out_offsets, size_t* bad_container,
+    size_t* bad_query, hipStream_t s)
+{
+    int rc;
+    const size_t nt = (size_t)qoff[nq], nx = xqoff ? (size_t)xqoff[nq] : 0;
+    std::vector<u32> all(terms, terms + nt);
+    if (nx) all.insert(all.end(), xterms, xterms + nx);
+    BrFront F;
+    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, all.data(), all.size(), nullptr, &F, bad_container, s))) return rc;
+    std::vector<u64> n(F.ref.size());
+    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
+    const u32* xrid = F.rid.data() + nt;
+    const u64 budget = c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT;
+    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
+    u64 run = 0;
+    if (op == ANSX_BOOL_ALL) {
+        std::vector<IsbGroup> groups;
+        if ((rc = isb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, &groups, bad_query, xrid, xqoff))) return rc;
+        for (const IsbGroup& g : groups)
+            if ((rc = isb_group(c, kind, f, F, g, off, count, d_out, cap, &run, out_offsets, bad_container, s))) return rc;
+    } else {
+        std::vector<UnbGroup> groups;
+        if ((rc = unb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query, xrid, xqoff))) return rc;
+        for (const UnbGroup& g : groups)
+            if ((rc = unb_group(c, kind, f, F, g, off, count, d_out, nullptr, cap, &run, out_offsets, bad_container, bad_query, s)))
+                return rc;
+    }
     HIPCHK(c, hipStreamSynchronize(s));  // (the copies)
     return run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
 }
@@ -3484,7 +3574,7 @@ int ansx_init(int device, ansx_ctx** out)
     }
     static const char* const names[] = { "ANSX_TEST_TABLE16_FIXUP", "ANSX_ENCODE_GTAB16", "ANSX_PARSE_GENERIC", "ANSX_PARSE_WIN", "ANSX_PARSE_FAST",
         "ANSX_DECODE_TABLE", "ANSX_NO_STREAM_LDS", "ANSX_DECODE_MODE", "ANSX_PARSE_STAGE_WORDS", "ANSX_MODEL_FUSED", "ANSX_MODEL_SYNC", "ANSX_NS_HINT", "ANSX_T_HINT", "ANSX_NO_FAST_MODEL", "ANSX_FAST_GUARD", "ANSX_CAND_CHAINS", "ANSX_NEAR_BAND", "ANSX_TEST_NEAR_FLIP", "ANSX_WIDE_RESTART", "ANSX_TEST_WIDE_AT",
-        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP", "ANSX_MODEL_CHAIN", "ANSX_INTERSECT_FORM", "ANSX_ISECT_BATCH_INTS" };
+        "ANSX_BATCH_PASS_BLOCKS", "ANSX_MODEL_PIPELINE", "ANSX_DECODE_SETUP", "ANSX_MODEL_CHAIN", "ANSX_INTERSECT_FORM", "ANSX_ISECT_BATCH_INTS", "ANSX_BOOL_FORM" };
     for (const char* nm : names)
         if (const char* v = getenv(nm))
             if (ansx_debug_set(c, nm, v) != ANSX_OK)  // (a value the key does not take selects nothing: said, not passed over)
@@ -3610,6 +3700,11 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         const int w = debug_word(value, "selective", "full");
         if (w < 0) return ANSX_ERR_ARG;
         c->dbg.intersect_form = w;
+    }
+    else if (!strcmp(name, "ANSX_BOOL_FORM")) {
+        const int w = debug_word(value, "search", "staged");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.bool_form = w;
     }
     else if (!strcmp(name, "ANSX_DECODE_PAIR_LDS")) c->dbg.pair_lds_limit = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_FORGET_HINTS")) {  // the next call of every geometry is a first call again (bench.py: first_call_ms)
@@ -3879,6 +3974,51 @@ int ansx_union_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_i
     return run_call(c, stream, [&](hipStream_t s) {
         return union_batch(c, kind, f, d_ins, in_bytes, count, terms, (const u64*)qoff, nqueries, d_out_ids, d_out_cnt, out_capacity,
             (u64*)out_offsets, bad_container, bad_query, s);
+    });
+}
+
+// ... what ansx_bool_batch_dev adds to queries_args: op and the excluded terms
+static int bool_args(const uint8_t* const* d_ins, size_t count, int op, const uint32_t* xterms, const uint64_t* xqoff, size_t nqueries,
+    size_t* bad_container, size_t* bad_query)
+{
+    if (op != ANSX_BOOL_ALL && op != ANSX_BOOL_ANY) return ANSX_ERR_ARG;
+    if (!xqoff || nqueries == 0) return ANSX_OK;
+    for (size_t q = 0; q < nqueries; q++)
+        if ((q == 0 && xqoff[0] != 0) || xqoff[q + 1] < xqoff[q]) {
+            if (bad_query) *bad_query = q;
+            return ANSX_ERR_ARG;
+        }
+    if (xqoff[nqueries] > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (!xterms && xqoff[nqueries] > 0) return ANSX_ERR_ARG;
+    for (size_t q = 0; q < nqueries; q++)
+        for (u64 j = xqoff[q]; j < xqoff[q + 1]; j++)
+            if (xterms[j] >= count) {
+                if (bad_query) *bad_query = q;
+                return ANSX_ERR_ARG;
+            }
+    for (size_t q = 0; q < nqueries; q++)
+        for (u64 j = xqoff[q]; j < xqoff[q + 1]; j++)
+            if (!d_ins[xterms[j]] || ((uintptr_t)d_ins[xterms[j]] & 15u)) {
+                if (bad_query) *bad_query = q;
+                if (bad_container) *bad_container = xterms[j];
+                return ANSX_ERR_ARG;
+            }
+    return ANSX_OK;
+}
+
+int ansx_bool_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes, size_t count, int op,
+    const uint32_t* terms, const uint64_t* qoff, const uint32_t* xterms, const uint64_t* xqoff, size_t nqueries, uint32_t* d_out_ids,
+    size_t out_capacity, uint64_t* out_offsets, size_t* bad_container, size_t* bad_query, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (queries_args(c, d_ins, in_bytes, count, terms, qoff, nqueries, d_out_ids, nullptr, out_capacity, out_offsets, bad_container,
+            bad_query))
+        return ANSX_ERR_ARG;
+    if (bool_args(d_ins, count, op, xterms, xqoff, nqueries, bad_container, bad_query)) return ANSX_ERR_ARG;
+    if (nqueries == 0) return empty_batch(out_offsets, (u64*)nullptr);
+    return run_call(c, stream, [&](hipStream_t s) {
+        return bool_batch(c, kind, f, d_ins, in_bytes, count, op, terms, (const u64*)qoff, xterms, (const u64*)xqoff, nqueries, d_out_ids,
+            out_capacity, (u64*)out_offsets, bad_container, bad_query, s);
     });
 }
 

@@ -445,6 +445,34 @@ static inline bool encb_pass_tables(const u64* offsets, size_t l0, size_t l1, u6
 // merge buffers).
 #define ANSX_ISECT_BATCH_INTS_DEFAULT ((u64)1 << 28)
 
+// What isb_plan and unb_plan share.  The lists t[0 .. m) that group gid has not stamped yet -> fresh, their ints -> add.
+static inline void plan_fresh(const u32* t, size_t m, const u64* n, u32 gid, std::vector<u32>& stamp, std::vector<u32>& fresh, u64& add)
+{
+    for (size_t j = 0; j < m; j++)
+        if (stamp[t[j]] != gid) stamp[t[j]] = gid, fresh.push_back(t[j]), add += n[t[j]];
+}
+
+// ansx_bool_batch_dev: query q also EXCLUDES the referenced lists xrid[xqoff[q] .. xqoff[q + 1]).
+// They are decoded with the group's other lists -- a list counts once in the budget, however it is named -- and the
+// group gets a second table: query j's excluded lists are xt[xt_off[j] .. xt_off[j + 1]), {at, n} into the buffer of
+// ids, an empty list kept as n = 0.  Without xqoff the tables stay empty; a group excludes something when xt is not.
+static inline void plan_excl_tables(const u64* n, const u32* xrid, const u64* xqoff, size_t q0, size_t q1,
+    const std::vector<u64>& at, const std::vector<u32>& slot, std::vector<u32>* xt_off, std::vector<ansx_isb_list>* xt,
+    std::vector<u32>* xt_list)
+{
+    if (!xqoff) return;
+    xt_off->resize(q1 - q0 + 1);
+    for (size_t q = q0; q < q1; q++) {
+        (*xt_off)[q - q0] = (u32)xt->size();
+        for (u64 j = xqoff[q]; j < xqoff[q + 1]; j++) {
+            const u32 r = xrid[j];
+            xt->push_back({ n[r] ? at[slot[r]] : 0, n[r] });
+            xt_list->push_back(r);
+        }
+    }
+    (*xt_off)[q1 - q0] = (u32)xt->size();
+}
+
 struct IsbGroup {
     size_t q0, q1;                   // its queries
     std::vector<u32> lists;          // the non-empty referenced lists it decodes, ascending: its buffer, back to back
@@ -453,6 +481,9 @@ struct IsbGroup {
     std::vector<u32> rt_off;         // q1 - q0 + 1: query j's rounds are rt[rt_off[j] .. rt_off[j + 1])
     std::vector<ansx_isb_list> rt;   // the round table
     std::vector<u32> rt_list, drv;   // the referenced list behind every entry of rt, and every query's driver (what the CPU check holds the tables against)
+    std::vector<u32> xt_off;         // with exclusions (plan_excl_tables): q1 - q0 + 1
+    std::vector<ansx_isb_list> xt;   // ... every query's excluded lists
+    std::vector<u32> xt_list;        // ... the referenced list behind every entry of xt
     u64 ints;                        // buffer + twice the candidates: what the budget bounds
     u32 rounds;                      // most rounds of a query
 };
@@ -460,8 +491,9 @@ struct IsbGroup {
 // -> ANSX_OK, or ANSX_ERR_ARG with *bad_query the first query whose driver has 2^32 ints or more (a step takes at most
 // 2^32 - 1 candidates).  A group ends in front of the query that would take it over `budget` ints or its candidates to
 // 2^32; a query over the budget alone is a group of its own.  A list two groups name is decoded in both.
+// xrid / xqoff: null, or the lists every query excludes (plan_excl_tables).
 static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64* qoff, size_t nq, u64 budget,
-    std::vector<IsbGroup>* groups, size_t* bad_query)
+    std::vector<IsbGroup>* groups, size_t* bad_query, const u32* xrid = nullptr, const u64* xqoff = nullptr)
 {
     groups->clear();
     std::vector<u32> stamp(nref, 0xFFFFFFFFu), slot(nref, 0), fresh, ord;
@@ -481,8 +513,8 @@ static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64*
                 return ANSX_ERR_ARG;
             }
             fresh.clear();
-            for (size_t j = 0; j < m; j++)
-                if (stamp[t[j]] != gid) stamp[t[j]] = gid, fresh.push_back(t[j]), add += n[t[j]];
+            plan_fresh(t, m, n, gid, stamp, fresh, add);
+            if (xqoff) plan_fresh(xrid + xqoff[q], (size_t)(xqoff[q + 1] - xqoff[q]), n, gid, stamp, fresh, add);
             add += 2 * nd;
             // (the stamps of a query that does not fit stay behind: the next group has another number)
             if (q > g.q0 && (add > budget || g.ints > budget - add || cand + nd > 0xFFFFFFFFull)) break;
@@ -520,6 +552,7 @@ static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64*
         }
         g.G[Q] = { 0, dst };
         g.rt_off[Q] = (u32)g.rt.size();
+        plan_excl_tables(n, xrid, xqoff, g.q0, g.q1, g.at, slot, &g.xt_off, &g.xt, &g.xt_list);
     }
     return ANSX_OK;
 }
@@ -545,6 +578,9 @@ struct UnbGroup {
     std::vector<ansx_unb_pair> pairs;  // every round's pairs, round after round, queries in order inside a round
     std::vector<u32> roff;             // rounds + 1: round r's pairs are pairs[roff[r] .. roff[r + 1])
     std::vector<u64> tiles;            // rounds: the tiles of round r
+    std::vector<u32> xt_off;           // with exclusions (plan_excl_tables): q1 - q0 + 1
+    std::vector<ansx_isb_list> xt;     // ... every query's excluded lists
+    std::vector<u32> xt_list;          // ... the referenced list behind every entry of xt
     u64 ints;                          // buffer + twice the merge buffer: what the budget bounds
     u32 rounds;                        // R
 };
@@ -559,9 +595,9 @@ static inline u32 unb_rounds(u64 m)
 // -> ANSX_OK, or ANSX_ERR_ARG with *bad_query the first query whose lists together have 2^32 ints or more (a run offset
 // is a u32).  A group ends in front of the query that would take it over `budget` ints or its merge buffer to 2^32; a
 // query over the budget alone is a group of its own.  A list two groups name is decoded in both.  tile: the outputs
-// of a workgroup of the merge.
+// of a workgroup of the merge.  xrid / xqoff: null, or the lists every query excludes (plan_excl_tables).
 static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64* qoff, size_t nq, u64 budget, u32 tile,
-    std::vector<UnbGroup>* groups, size_t* bad_query)
+    std::vector<UnbGroup>* groups, size_t* bad_query, const u32* xrid = nullptr, const u64* xqoff = nullptr)
 {
     groups->clear();
     std::vector<u64> tot(nq);
@@ -588,8 +624,8 @@ static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64*
             const size_t m = (size_t)(qoff[q + 1] - qoff[q]);
             u64 add = 0;
             fresh.clear();
-            for (size_t j = 0; j < m; j++)
-                if (stamp[t[j]] != gid) stamp[t[j]] = gid, fresh.push_back(t[j]), add += n[t[j]];
+            plan_fresh(t, m, n, gid, stamp, fresh, add);
+            if (xqoff) plan_fresh(xrid + xqoff[q], (size_t)(xqoff[q + 1] - xqoff[q]), n, gid, stamp, fresh, add);
             add += 2 * tot[q];
             // (the stamps of a query that does not fit stay behind: the next group has another number)
             if (q > g.q0 && (add > budget || g.ints > budget - add || merge + tot[q] > 0xFFFFFFFFull)) break;
@@ -642,6 +678,7 @@ static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64*
             g.roff.push_back((u32)g.pairs.size());
             g.tiles.push_back(first);
         }
+        plan_excl_tables(n, xrid, xqoff, g.q0, g.q1, g.at, slot, &g.xt_off, &g.xt, &g.xt_list);
     }
     return ANSX_OK;
 }

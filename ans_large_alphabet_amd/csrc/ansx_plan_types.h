@@ -126,7 +126,7 @@ struct ansx_isb_query {  // query j of the group: its driver's ids lie from src 
     u64 src, dst;        // the entry behind the last query closes it: dst = the group's candidates
 };
 struct ansx_isb_list {  // a round of a query: the list's ids [at, at + n) of the buffer; an empty list has n = 0
-    u64 at, n;
+    u64 at, n;          // (also an entry of xt, the lists a query of ansx_bool_batch_dev excludes: ansx_bool.h)
 };
 
 // A group of disjunctive queries (ansx_union_batch_dev, ansx_union.h).  A pair of a round: the sorted runs A and B

@@ -691,6 +691,49 @@ int ansx_union_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* 
     size_t count, uint32_t* d_out_ids, uint32_t* d_out_cnt, size_t out_capacity, uint64_t* nfound,
     size_t* bad_container, void* stream);
 
+/* ansx_bool_batch_dev: Boolean queries with exclusion over one batch of gap-coded lists in one call (DESIGN.md section
+ * 3l).  The batch, terms, qoff, d_out_ids, out_capacity, out_offsets, bad_container, bad_query and stream are exactly
+ * ansx_intersect_batch_dev's.  op says how a query's terms combine: */
+#define ANSX_BOOL_ALL 0 /* a query's terms are intersected (ansx_intersect_batch_dev's result) */
+#define ANSX_BOOL_ANY 1 /* a query's terms are united      (ansx_union_batch_dev's ids)        */
+/* Query q EXCLUDES the lists xterms[xqoff[q] .. xqoff[q + 1]) -- HOST arrays; xqoff has nqueries + 1 entries, starts at
+ * 0 and is non-decreasing: a query may exclude nothing.  xqoff == NULL: no query excludes anything, and xterms may be
+ * NULL as well.  A list may be excluded by many queries and named more than once.
+ * Result of query q: with P what ansx_intersect_batch_dev (ANSX_BOOL_ALL) or ansx_union_batch_dev without counts
+ * (ANSX_BOOL_ANY) returns for its terms, and X the set of ids that occur in at least one of its excluded lists, P with
+ * every entry whose id is in X removed; the order and, under ALL, the driver's multiplicities are kept.  0xFFFFFFFF is
+ * an id like any other: membership is "found and equal", nothing compares with ANSX_NO_ID.  With no excluded list
+ * anywhere the output and out_offsets are the parent call's exactly.  A list may be both a term and excluded: under ANY
+ * its ids vanish, under ALL the result is empty.
+ * How it runs: the headers of all REFERENCED containers -- those a term or an excluded term names; the others are not
+ * examined and may be NULL -- in one round trip; the parent's groups under the same budget (ANSX_ISECT_BATCH_INTS), an
+ * excluded list counting once among the group's lists; per group the parent's positive phase unchanged, then, when the
+ * group excludes something and candidates are left, ONE exclusion step over the candidates of all its queries however
+ * many lists they exclude (k_bool_exclude, csrc/ansx_bool.h), then the copy to the caller.  A group that excludes nothing runs
+ * exactly the parent's sequence.
+ * Errors, in this order: before the context is touched, the parents' argument checks on terms / qoff and the outputs with
+ * the same *bad_query / *bad_container; ANSX_ERR_ARG for an op other than the two values; for a non-NULL xqoff with
+ * xqoff[0] != 0 or a decrease (*bad_query = the query); for xqoff[nqueries] > UINT32_MAX; for a NULL xterms with
+ * xqoff[nqueries] > 0; for an xterms[j] >= count (*bad_query); for a null or misaligned d_ins[t] of an excluded list
+ * (*bad_query, *bad_container).  nqueries == 0: ANSX_OK, nothing is launched, the context is untouched.  Then
+ * ANSX_ERR_FORMAT with *bad_container = the smallest referenced batch index whose header fails decode_dev's checks;
+ *   ANSX_ERR_ARG with *bad_query for the parent plan's limits: ALL, the first query whose driver has 2^32 ints or more;
+ *   ANY, the first query whose terms together have 2^32 ints or more, or the first query of a group one of whose rounds
+ *   would take 2^31 workgroups or more.  An excluded list may have any length;
+ *   found on the device: ANSX_ERR_FORMAT with *bad_container = count; ANSX_ERR_DOMAIN with *bad_container = a referenced
+ *   list, an excluded one included, whose sum leaves 32 bits, as in the parents;
+ *   ANSX_ERR_CAPACITY when the total exceeds out_capacity: out_offsets is complete, so d_out_ids = NULL, out_capacity = 0
+ *   is a size query; nothing is written at or beyond out_capacity.
+ * No trace is left in the context, which stays usable after any error.  Workspace: the parent's, with the excluded lists
+ * among the group's, and 4 bytes per query and 16 per excluded term of tables.  Host waits: ALL, one more than the
+ * parent per group in which the step runs; ANY, the parent's -- the number of heads stays on the device.
+ * Out of scope: union counts behind an exclusion (there is no d_out_cnt), a minimum-should-match threshold, nested
+ * expressions, and fusing the unique step into the last merge round. */
+int ansx_bool_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    size_t count, int op, const uint32_t* terms, const uint64_t* qoff, const uint32_t* xterms, const uint64_t* xqoff,
+    size_t nqueries, uint32_t* d_out_ids, size_t out_capacity, uint64_t* out_offsets, size_t* bad_container,
+    size_t* bad_query, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
@@ -853,7 +896,10 @@ int ansx_generate_host(int dist, double a, double b, uint64_t seed, uint64_t fir
  * which compare the two, and the timing of tests/tools/bench_intersect.py), ANSX_ISECT_BATCH_INTS (number: the ints a
  * group of ansx_intersect_batch_dev may take, its lists once and its drivers' twice, and a group of ansx_union_batch_dev,
  * its lists once and its queries' lists as named twice; ""/"0"/NULL: 2^28 -- the results do not depend on it; the tests
- * force several groups and a group per query);
+ * force several groups and a group per query), ANSX_BOOL_FORM ("search" | "staged"; ""/"0"/NULL: the default rule;
+ * anything else: ANSX_ERR_ARG -- how a tile of k_bool_exclude that lies inside one query meets an excluded list: "search"
+ * never stages the list's range in LDS, "staged" stages it whenever it fits ANSX_BOOL_STAGE ints; the outputs are the
+ * same; for the tests, which compare them, and the timing of tests/tools/bench_bool_batch.py);
  * through this call only (round 4): ANSX_NO_PC / ANSX_FORCE_PC / ANSX_NO_PC_AUTO / ANSX_PC_B_PAIRS (the producer /
  * consumer encoder never / whatever the list length / only on request; pairs per workgroup of its two-round shape),
  * ANSX_ENCODE_MODE2, ANSX_DECODE_PAIR, ANSX_DECODE_SMALL_RING ("never" | "always"; ""/"0"/NULL: the default; anything
