@@ -35,7 +35,7 @@ EXPORTS = [
     "ansx_decode_device_ranges_sums_dev", "ansx_next_geq_dev", "ansx_encode_batch_gaps_bases_dev",
     "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
     "ansx_intersect_ids_dev", "ansx_intersect_dev", "ansx_intersect_batch_dev", "ansx_union_batch_dev", "ansx_union_dev",
-    "ansx_bool_batch_dev",
+    "ansx_bool_batch_dev", "ansx_last_encode_form",
 ]
 
 
@@ -67,6 +67,24 @@ class DecodeStats(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in (
         "parser", "p_variant", "decoder", "p_grid", "p_threads", "p_lds", "d_grid", "d_threads", "d_lds", "stream_cap",
         "maxM", "max_ns", "max_ep", "max_block_bytes", "nblocks", "flags")]
+
+
+# ansx_encode_form_report: the forms of the most recent encode (include/ansx.h); the enumerations' names by value
+FORM_HIST = ("WORDS", "PACKED", "NONE")
+FORM_SORT = ("U16", "U32", "U32_UNSTAGED", "NONE")
+FORM_FIN = ("WAVES", "16_5", "16_8", "ONE_WAVE_5", "ONE_WAVE_8", "GENERIC_5", "GENERIC_8", "NONE")
+FORM_RF = ("NONE", "HBM_HASH", "LDS_OPT", "LDS_FULL", "SORT")
+FORM_PRELUDE = ("W4", "W16", "RANK_SPACE", "GENERIC", "GENERIC_HBM", "NONE")
+FORM_ENC = ("INT_STATE", "MODE1", "MODE2", "NONE")
+FORM_PC = ("NONE", "A", "B", "C")
+FORM_ATTEMPT_BITS = (("optimistic", 1), ("fast_model", 2), ("fused", 4), ("rank_space", 8), ("sp_full_lds", 16), ("batch_pass", 32))
+
+
+class EncodeFormReport(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in (
+        "attempt", "ns_cap", "nt", "hist", "cpb", "h_deferred", "h_in_hist", "sort", "fin", "fcap", "cand_chains", "nranges",
+        "range_blocks", "big_geo", "rf", "rf_slots", "pa_small", "pa_slots", "pa_uqcap", "prelude", "table16_first", "pre_cap",
+        "enc", "enc_grid", "enc_threads", "enc_lds", "criterion", "pairs", "S", "pc_grid", "first", "nblocks")]
 
 
 class KernelTime(C.Structure):
@@ -209,6 +227,8 @@ def lib():
     L.ansx_merge_containers_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.c_int, vp, sz, C.POINTER(sz), vp]
     L.ansx_last_encode_stats.restype = C.c_int
     L.ansx_last_encode_stats.argtypes = [vp, C.POINTER(EncodeStats)]
+    L.ansx_last_encode_form.restype = C.c_int
+    L.ansx_last_encode_form.argtypes = [vp, C.POINTER(EncodeFormReport)]
     L.ansx_last_decode_stats.restype = C.c_int
     L.ansx_last_decode_stats.argtypes = [vp, C.POINTER(DecodeStats)]
     L.ansx_last_gather_ranks.restype = C.c_int

@@ -61,6 +61,23 @@ class Context:
         L.lib().ansx_last_encode_stats(self._h, C.byref(st))
         return {k: int(getattr(st, k)) for k, _ in L.EncodeStats._fields_}
 
+    def last_encode_form(self):
+        """The forms of the most recent encode as they were launched (ansx_encode_form_report in include/ansx.h): a dict
+        of the struct's fields as ints, the enumerations as names ("hist", "sort", "fin", "rf", "prelude", "enc",
+        "criterion": _lib.FORM_*) and the bits of "attempt" as bools "optimistic", "fast_model", "fused", "rank_space",
+        "sp_full_lds", "batch_pass"."""
+        st = L.EncodeFormReport()
+        rc = L.lib().ansx_last_encode_form(self._h, C.byref(st))
+        if rc != L.OK:
+            raise L.AnsxError(rc, "ansx_last_encode_form")
+        d = {k: int(getattr(st, k)) for k, _ in L.EncodeFormReport._fields_}
+        for k, names in (("hist", L.FORM_HIST), ("sort", L.FORM_SORT), ("fin", L.FORM_FIN), ("rf", L.FORM_RF),
+                         ("prelude", L.FORM_PRELUDE), ("enc", L.FORM_ENC), ("criterion", L.FORM_PC)):
+            d[k] = names[d[k]]
+        for k, bit in L.FORM_ATTEMPT_BITS:
+            d[k] = bool(d["attempt"] & bit)
+        return d
+
     def last_decode_stats(self):
         """The form of the most recent decode as it ran (ansx_decode_stats in include/ansx.h): a dict of the struct's
         fields as ints, "parser" and "decoder" as names ("PAR", "SMALL_RING", ...; _lib.PARSERS / _lib.DECODERS) and the

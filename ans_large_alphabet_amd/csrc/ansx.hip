@@ -154,6 +154,7 @@ struct ansx_ctx {
         std::set<u64> wide_hint, int_sparse_hint;
     } bat;
     ansx_encode_stats last = {};
+    ansx_encode_form_report last_form = {};  // the forms of the most recent encode attempt whose container was returned (ansx_last_encode_form)
     ansx_decode_stats last_dec = {};  // the form of the most recent decode attempt that ran to its end (ansx_last_decode_stats)
     // Block-range pipeline of the fast model path (model_fast): two side streams and the events of its fork and join,
     // created by the first call that needs them (pipeline_prepare) and destroyed with the context, never per call.
@@ -523,6 +524,7 @@ struct EncodeOutcome {
     bool used_fast = false;    // the model came from k_candidates / k_model_finish
     bool used_pc = false;      // the producer / consumer encoder kernel ran
     bool sp_repeated = false;  // a rank-space attempt was repeated with the full-size prelude writer
+    ansx_encode_form_report form = {};  // the forms the attempt's phases launched with (ansx_last_encode_form): written, never read
 };
 
 // What the phases of one attempt share: the call's arguments and the workspace pointers encode_begin carves.
@@ -670,6 +672,7 @@ int encode_remap(ansx_ctx* c, EncodeWs& W)
     const u32 NB = g.nblocks;
     hipStream_t s = W.s;
     const RemapForm R = ansx_enc::choose_remap_form(W.G, a);
+    ansx_enc::report_remap(W.out->form, R, g.pa || a.int_sparse);
     int rc;
     if (g.kind == ANSX_RFOLD && W.P->bat) {
         // a batch pass (g.n is not its ints): `mapped` holds the pass's own stretch of the input's index space, and the
@@ -914,6 +917,7 @@ int model_fast(ansx_ctx* c, EncodeWs& W, ModelForm M)
     const u32 range_blocks = M.range_blocks, nranges = M.nranges;
     // k_candidates: the chain counts its launches will use (a full range and the last, shorter one)
     const ansx_enc::Launch cand[2] = { ansx_enc::cand_launch(M, range_blocks), ansx_enc::cand_launch(M, nranges ? NB - (nranges - 1) * range_blocks : NB) };
+    ansx_enc::report_model(W.out->form, M, (u32)cand[1].variant, NSP > 4096 && !c->dbg.no_big_geo);
     for (int nch = 1; nch <= 2; nch++) {
         const ansx_enc::Launch& L = cand[0].variant == nch ? cand[0] : cand[1];
         if (L.variant == nch && L.raise && (rc = raise_lds(c, cand_kernel(W.a->nt, nch), L.lds))) return rc;
@@ -972,6 +976,7 @@ int write_preludes(ansx_ctx* c, EncodeWs& W, const PreludeForm& F)
     u8* scratch = (u8*)c->scratch.p;
     const Launch& L = F.w;
     int rc;
+    report_prelude(W.out->form, F);
     if (F.table16_first)
         LAUNCH(c, "k_table16_from32", k_table16_from32, g.nblocks, 256, 0, s, g, NSP, (const ansx_blk*)W.blk, tab32, (ansx_enc_entry*)c->table.p);
     if (L.variant == PRE_RANK_SPACE) {
@@ -1009,6 +1014,7 @@ int launch_encoder(ansx_ctx* c, EncodeWs& W, const EncoderForm& E)
     const bool pow2 = W.G.map_pow2;
     int rc;
     W.out->used_pc = false;  // (true below, once the pair kernel has taken blocks of this call)
+    report_encoder(W.out->form, E);
     if (E.pc.grid) {  // producer / consumer pairs
         const auto kern = pow2 ? (E.S == 8 ? k_encode_pc<true, 8> : k_encode_pc<true, 4>) : (E.S == 8 ? k_encode_pc<false, 8> : k_encode_pc<false, 4>);
         if ((rc = raise_lds(c, kern, E.pc.lds))) return rc;
@@ -1088,6 +1094,8 @@ int encode_general(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_
     // (profile mode: the event pairs of LAUNCH would time overlapped kernels -- serial there)
     const ModelForm M = ansx_enc::choose_model_form(W.G, a, W.K, c->num_cus, c->profile);
     out->used_fast = M.fast;
+    ansx_enc::report_attempt(out->form, W.G, a, false);  // (behind encode_remap, which has noted its own form: neither touches the other's fields)
+    ansx_enc::report_model(out->form, M, 0, false);      // (model_fast notes the form it ends up launching)
     if ((rc = model_prepare(c, W, M))) return rc;
     if ((rc = M.fast ? model_fast(c, W, M) : model_exact(c, W, M))) return rc;  // K1 .. K4
     if (!P.plain && !g.ckw && g.nckf != 0 && W.max_logM > c->dbg.wide_at) return ANSX_RETRY_WIDE;  // (discovery path: known before anything is encoded)
@@ -1157,6 +1165,7 @@ int encode_fast(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size_t c
     int rc;
     if ((rc = encode_begin(c, W))) return rc;
     if ((rc = encode_remap(c, W))) return rc;
+    ansx_enc::report_attempt(out->form, W.G, a, true);
     const auto kern = a.ns_cap <= 1024 ? k_model_fused<4> : k_model_fused<16>;
     if (ML.total > ansx_enc::LDS_NO_ATTRIBUTE && (rc = raise_lds(c, kern, ML.total))) return rc;
     LAUNCH(c, "k_model_fused", kern, P.g.nblocks, 256, ML.total, s, W.src, P.g, P.NSP, ML, (const ansx_log2_ent*)c->log2lut.p, W.blk,
@@ -1371,6 +1380,7 @@ int encode_dev_once(ansx_ctx* c, const Plan& P, const u32* d_in, u8* d_out, size
     c->last.max_nsyms = o.flags[ANSX_G_MAXNSYMS];
     c->last.max_log2_frame = o.flags[ANSX_G_MAXLOGM];
     c->last.near_threshold_decisions = near_blocks;
+    if (rc == ANSX_OK) c->last_form = o.form;
     if (rc == ANSX_OK && !P.plain) {
         // a miss raises the hint past what was seen, so inputs whose alphabets creep upwards do not
         // miss on every call
@@ -3627,6 +3637,13 @@ int ansx_last_encode_stats(const ansx_ctx* c, ansx_encode_stats* out)
         }
     }
 #endif
+    return ANSX_OK;
+}
+
+int ansx_last_encode_form(const ansx_ctx* c, ansx_encode_form_report* out)
+{
+    if (!c || !out) return ANSX_ERR_ARG;
+    *out = c->last_form;
     return ANSX_OK;
 }
 

@@ -85,10 +85,12 @@ struct Launch {
 };
 
 // ------------------------------------------------------------------------------------------ the model phase
-enum { HIST_WORDS, HIST_PACKED };                 // k_fold_hist<false / true>
-enum { SORT_U16, SORT_U32, SORT_U32_UNSTAGED };   // k_sort_entropy<u16>, <u32>, <u32, false>
+// (the variants have the values of the public enumerations, which ansx_last_encode_form reports)
+enum { HIST_WORDS = ANSX_HIST_WORDS, HIST_PACKED = ANSX_HIST_PACKED };  // k_fold_hist<false / true>
+enum { SORT_U16 = ANSX_SORT_U16, SORT_U32 = ANSX_SORT_U32, SORT_U32_UNSTAGED = ANSX_SORT_U32_UNSTAGED };  // k_sort_entropy<u16>, <u32>, <u32, false>
 // k_model_finish<4, 8, 256> (wave per candidate), <16, NTC, 256>, <16, NTC, 64> (one wave per block), <0, NTC, 256> (generic)
-enum { FIN_WAVES, FIN_16_5, FIN_16_8, FIN_ONE_WAVE_5, FIN_ONE_WAVE_8, FIN_GENERIC_5, FIN_GENERIC_8 };
+enum { FIN_WAVES = ANSX_FIN_WAVES, FIN_16_5 = ANSX_FIN_16_5, FIN_16_8 = ANSX_FIN_16_8, FIN_ONE_WAVE_5 = ANSX_FIN_ONE_WAVE_5,
+    FIN_ONE_WAVE_8 = ANSX_FIN_ONE_WAVE_8, FIN_GENERIC_5 = ANSX_FIN_GENERIC_5, FIN_GENERIC_8 = ANSX_FIN_GENERIC_8 };
 
 // Launch shapes of the model kernels.  hist, sort and fin are launched per block range: their grid is workgroups PER BLOCK.
 struct ModelForm {
@@ -193,7 +195,7 @@ static inline u32 rf_opt_slots(u32 distinct, u32 T)
 // attempts), HBM hash table for longer blocks (incl. whole-list single-stream mode) and T > 4096 (f = 6, 7 -- the
 // selection buffer alone is 64 / 128 KB); RF_SORT is what is left of the older sort form (T > 4096 in short blocks: no
 // geometry reaches it while RF_HBM_HASH takes every T > 4096)
-enum { RF_NONE, RF_HBM_HASH, RF_LDS_OPT, RF_LDS_FULL, RF_SORT };
+enum { RF_NONE = ANSX_RF_NONE, RF_HBM_HASH = ANSX_RF_HBM_HASH, RF_LDS_OPT = ANSX_RF_LDS_OPT, RF_LDS_FULL = ANSX_RF_LDS_FULL, RF_SORT = ANSX_RF_SORT };
 struct RemapForm {
     int rf;
     u32 rf_slots;      // RF_HBM_HASH: slots per block in HBM; the LDS forms: table slots; RF_SORT: the sort's length
@@ -246,7 +248,8 @@ static inline RemapForm choose_remap_form(const EncGeo& g, const EncAttempt& a)
 
 // ------------------------------------------------------------------------------------------ the exact form's prelude writers
 // k_write_prelude<4>, <16>, k_int_sparse_prelude, k_write_prelude<0> with its two arrays in LDS / in HBM (f = 6, 7)
-enum { PRE_W4, PRE_W16, PRE_RANK_SPACE, PRE_GENERIC, PRE_GENERIC_HBM };
+enum { PRE_W4 = ANSX_PRE_W4, PRE_W16 = ANSX_PRE_W16, PRE_RANK_SPACE = ANSX_PRE_RANK_SPACE, PRE_GENERIC = ANSX_PRE_GENERIC,
+    PRE_GENERIC_HBM = ANSX_PRE_GENERIC_HBM };
 struct PreludeForm {
     bool table16_first;  // mixed call: a frame above 2^16 sends every block to the integer-state encoder (k_table16_from32)
     Launch w;            // variant: PRE_*
@@ -291,8 +294,8 @@ static inline PreludeForm choose_prelude_form(const EncGeo& g, const EncAttempt&
 //                 last workgroup pads itself with neutral steps (blocks that do not exist, the partial last block)
 //   k_encode<1>   one wave per 16 blocks, 4-byte LDS entries: geometries the pair kernel does not take
 //   k_encode<2>   compact tables in HBM with the hottest 1151 symbols per block in LDS: alphabets that fit neither
-enum { ENC_INT_STATE, ENC_MODE1, ENC_MODE2 };
-enum { PC_NONE, PC_A, PC_B, PC_C };
+enum { ENC_INT_STATE = ANSX_ENC_INT_STATE, ENC_MODE1 = ANSX_ENC_MODE1, ENC_MODE2 = ANSX_ENC_MODE2 };
+enum { PC_NONE = ANSX_PC_NONE, PC_A = ANSX_PC_A, PC_B = ANSX_PC_B, PC_C = ANSX_PC_C };
 struct EncoderForm {
     bool f64;
     int criterion;      // PC_*: the criterion that chose the pair kernel; pc.grid == 0 where its restart rule then refused it
@@ -355,6 +358,43 @@ static inline EncoderForm choose_encoder_form(const EncGeo& g, const EncKeys& db
         E.lds_stride = ANSX_ENC_HOT;
     }
     return E;
+}
+
+// ------------------------------------------------------------------------------------------ what the call reports
+// ansx_last_encode_form: each phase copies the form it launched with into the attempt's report (ansx.hip: EncodeOutcome).
+// Assignments only -- no chooser is asked here.
+static inline void report_attempt(ansx_encode_form_report& r, const EncGeo& g, const EncAttempt& a, bool fused)
+{
+    r.attempt = (a.ns_cap ? ANSX_FORM_OPTIMISTIC : 0u) | (fused ? ANSX_FORM_FUSED : 0u) | (a.int_sparse ? ANSX_FORM_RANK_SPACE : 0u)
+        | (a.int_sparse && a.sp_full_lds ? ANSX_FORM_SP_FULL_LDS : 0u) | (g.batch_pass ? ANSX_FORM_BATCH_PASS : 0u);
+    r.ns_cap = a.ns_cap, r.nt = a.nt, r.nblocks = g.nblocks;
+    // (until a phase says otherwise: the kernels of these stages did not run)
+    r.hist = ANSX_HIST_NONE, r.sort = ANSX_SORT_NONE, r.fin = ANSX_FIN_NONE, r.prelude = ANSX_PRE_NONE, r.enc = ANSX_ENC_NONE;
+}
+// last_cand: the chain count of the last k_candidates launch (fast only); big_geo: the table for alphabets above 4096 slots
+static inline void report_model(ansx_encode_form_report& r, const ModelForm& M, u32 last_cand, bool big_geo)
+{
+    if (M.fast) r.attempt |= ANSX_FORM_FAST_MODEL;
+    r.hist = (u32)M.hist.variant, r.cpb = M.cpb, r.h_deferred = M.h_deferred, r.h_in_hist = M.h_in_hist;
+    r.sort = (u32)M.sort.variant;
+    r.fin = M.fast ? (u32)M.fin.variant : (u32)ANSX_FIN_NONE, r.fcap = M.fast ? M.fcap : 0u;
+    r.cand_chains = M.fast ? last_cand : 0u;
+    r.nranges = M.nranges, r.range_blocks = M.range_blocks, r.big_geo = big_geo;
+}
+static inline void report_remap(ansx_encode_form_report& r, const RemapForm& R, bool pa_ran)
+{
+    r.rf = (u32)R.rf, r.rf_slots = R.rf_slots;
+    r.pa_small = pa_ran && R.pa_small, r.pa_slots = pa_ran ? R.pa_slots : 0u, r.pa_uqcap = pa_ran ? R.pa_uqcap : 0u;
+}
+static inline void report_prelude(ansx_encode_form_report& r, const PreludeForm& F)
+{
+    r.prelude = (u32)F.w.variant, r.table16_first = F.table16_first, r.pre_cap = F.pre_cap;
+}
+static inline void report_encoder(ansx_encode_form_report& r, const EncoderForm& E)
+{
+    r.enc = E.rest.grid ? (u32)E.rest.variant : (u32)ANSX_ENC_NONE;
+    r.enc_grid = E.rest.grid, r.enc_threads = E.rest.threads, r.enc_lds = (u32)E.rest.lds;
+    r.criterion = (u32)E.criterion, r.pairs = E.pairs, r.S = E.S, r.pc_grid = E.pc.grid, r.first = E.first;
 }
 
 }  // namespace ansx_enc

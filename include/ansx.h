@@ -805,6 +805,62 @@ typedef struct {
 } ansx_encode_stats;
 int ansx_last_encode_stats(const ansx_ctx* ctx, ansx_encode_stats* out);
 
+/* The forms of the context's most recent encode, as they were launched: which instantiation of every templated kernel
+ * of the model phase, the remap front, the prelude writers and the encoder ran, and in what shape (DESIGN.md section 5,
+ * "Host side of an encode call").  The fields are copies of the values the launches were made with, for the attempt
+ * whose container was returned (a repeated call reports its last attempt).  ansx_encode_batch_dev reports its last
+ * pass -- or the last list that went alone -- and, unlike ansx_last_encode_stats, does not put the earlier report
+ * back.  A call that fails leaves the previous values.  For tests and logs: no encode path looks at it.
+ *   attempt           ANSX_FORM_OPTIMISTIC   launched back to back on the geometry's hints (ns_cap != 0), else discovery
+ *                     ANSX_FORM_FAST_MODEL   k_candidates / k_model_finish instead of the exact model kernels
+ *                     ANSX_FORM_FUSED        k_model_fused (hist, sort, fin and prelude are then "NONE")
+ *                     ANSX_FORM_RANK_SPACE   plain ANSint modelled in rank space
+ *                     ANSX_FORM_SP_FULL_LDS  ... and its prelude writer repeated with the full-size LDS arrays
+ *                     ANSX_FORM_BATCH_PASS   a pass of ansx_encode_batch_dev (blocks through the per-block table)
+ *   ns_cap, nt        the alphabet hint of the attempt (0: discovery) and the candidates per block of the fast model
+ *                     path (0: the exact model kernels)
+ *   hist .. big_geo   the model phase: k_fold_hist's variant, its workgroups per block (cpb), whether the entropy sum is
+ *                     deferred to k_sort_entropy / taken in k_fold_hist itself; k_sort_entropy's variant;
+ *                     k_model_finish's variant (ANSX_FIN_NONE where it did not run) and alphabet capacity (fcap, 0
+ *                     likewise); chains per lane of the last k_candidates launch (0: none); the block-range pipeline's
+ *                     range count (0: one launch of each kernel over all blocks) and blocks per range; whether
+ *                     k_model_finish<0> took its tree nodes from the table built for alphabets above 4096 slots
+ *   rf .. pa_uqcap    the remap front: ANSrfold's form (ANSX_RF_NONE: no ANSrfold) and its table slots; the compaction
+ *                     layer's (and rank-space ANSint's) hash-set and value-list sizes, pa_small: the hint-sized kernel
+ *                     (all three 0 where neither ran; a batch pass: of its large class)
+ *   prelude ..        the exact form's prelude writer (ANSX_PRE_NONE: k_model_finish or k_model_fused wrote the
+ *   pre_cap           preludes), whether k_table16_from32 ran first, and the writer's array length (0 under NONE)
+ *   enc .. first      the encoder: the kernel that took the blocks the pair kernel left (ANSX_ENC_NONE: it left none)
+ *                     with its grid, threads and bytes of dynamic LDS; the criterion that chose the pair kernel
+ *                     (ANSX_PC_NONE: none) with its pairs per workgroup and S -- pc_grid == 0 with a criterion: the
+ *                     restart rule then refused it --, the pair launch's workgroups and the blocks it took (first)
+ *   nblocks           blocks of the call (a batch pass: of the pass) */
+typedef enum { ANSX_HIST_WORDS = 0, ANSX_HIST_PACKED = 1, ANSX_HIST_NONE = 2 } ansx_form_hist;
+typedef enum { ANSX_SORT_U16 = 0, ANSX_SORT_U32 = 1, ANSX_SORT_U32_UNSTAGED = 2, ANSX_SORT_NONE = 3 } ansx_form_sort;
+typedef enum { ANSX_FIN_WAVES = 0, ANSX_FIN_16_5 = 1, ANSX_FIN_16_8 = 2, ANSX_FIN_ONE_WAVE_5 = 3, ANSX_FIN_ONE_WAVE_8 = 4,
+    ANSX_FIN_GENERIC_5 = 5, ANSX_FIN_GENERIC_8 = 6, ANSX_FIN_NONE = 7 } ansx_form_fin;
+/* (ANSX_RF_SORT: no geometry reaches it while ANSX_RF_HBM_HASH takes every ANSrfold-6 and -7 list) */
+typedef enum { ANSX_RF_NONE = 0, ANSX_RF_HBM_HASH = 1, ANSX_RF_LDS_OPT = 2, ANSX_RF_LDS_FULL = 3, ANSX_RF_SORT = 4 } ansx_form_rf;
+typedef enum { ANSX_PRE_W4 = 0, ANSX_PRE_W16 = 1, ANSX_PRE_RANK_SPACE = 2, ANSX_PRE_GENERIC = 3, ANSX_PRE_GENERIC_HBM = 4,
+    ANSX_PRE_NONE = 5 } ansx_form_prelude;
+typedef enum { ANSX_ENC_INT_STATE = 0, ANSX_ENC_MODE1 = 1, ANSX_ENC_MODE2 = 2, ANSX_ENC_NONE = 3 } ansx_form_enc;
+typedef enum { ANSX_PC_NONE = 0, ANSX_PC_A = 1, ANSX_PC_B = 2, ANSX_PC_C = 3 } ansx_form_pc;
+#define ANSX_FORM_OPTIMISTIC 1u
+#define ANSX_FORM_FAST_MODEL 2u
+#define ANSX_FORM_FUSED 4u
+#define ANSX_FORM_RANK_SPACE 8u
+#define ANSX_FORM_SP_FULL_LDS 16u
+#define ANSX_FORM_BATCH_PASS 32u
+typedef struct {
+    uint32_t attempt, ns_cap, nt;
+    uint32_t hist, cpb, h_deferred, h_in_hist, sort, fin, fcap, cand_chains, nranges, range_blocks, big_geo;
+    uint32_t rf, rf_slots, pa_small, pa_slots, pa_uqcap;
+    uint32_t prelude, table16_first, pre_cap;
+    uint32_t enc, enc_grid, enc_threads, enc_lds, criterion, pairs, S, pc_grid, first;
+    uint32_t nblocks;
+} ansx_encode_form_report;
+int ansx_last_encode_form(const ansx_ctx* ctx, ansx_encode_form_report* out);
+
 /* The form of the context's most recent decode, as it ran: which prelude parser and which block decoder, in what
  * launch shape.  Every read call ends in one decode of a container or of a sub-container built for the call (the range
  * calls, the batch calls pass by pass, the sums / ids variants, next_geq); the fields describe that decode, for the

@@ -22,13 +22,18 @@ REFUSED_ROWS = 18
 
 
 @pytest.fixture(scope="module")
-def form_check(tmp_path_factory):
+def form_exe(tmp_path_factory):
     cxx = shutil.which(os.environ.get("CXX", "g++")) or shutil.which("c++")
     assert cxx, "no host C++ compiler"
     exe = str(tmp_path_factory.mktemp("encode_form_check") / "encode_form_check.x")
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-Wall", "-Werror", "-o", exe, SRC])
-    return subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    return exe
+
+
+@pytest.fixture(scope="module")
+def form_check(form_exe):
+    return subprocess.run([form_exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
 
 
 def test_the_form_header_is_host_only():
@@ -68,3 +73,31 @@ def test_the_library_takes_the_forms_from_the_header():
     for bare in ("150 * 1024", "160 * 1024", "78 * 1024", "48 * 1024", "40 * 1024", "32 * 1024"):
         assert bare not in body, bare
     assert body.count("num_cus") == body.count("c->num_cus, ") == 4  # the model form (twice: serial again), the encoder form (twice: both drivers)
+
+
+def test_the_gpu_case_table_matches_the_choosers_at_256_cus(form_exe):
+    """Every case of tests/test_gpu_encode_forms.py as one line of encode_form_check --form: each literal the GPU test
+    expects of ansx_last_encode_form is what the choosers give for the case's geometry, attempt, keys and the frame /
+    alphabet its list has, at 256 CUs.  (That the list has them, and that the library launches what it reports, is the GPU
+    test's business.)  The table's own coverage test runs here too."""
+    import test_gpu_encode_forms as T
+    from ans_large_alphabet_amd import _lib as L
+
+    assert T.CUS == 256
+    out = subprocess.run([form_exe, "--form"], input="".join(T.form_line(c) + "\n" for c in T.CASES), stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True, timeout=60)
+    assert out.returncode == 0 and out.stderr == "", out.stderr[-2000:]
+    lines = out.stdout.splitlines()
+    assert len(lines) == len(T.CASES)
+    names = dict(hist=L.FORM_HIST, sort=L.FORM_SORT, fin=L.FORM_FIN, rf=L.FORM_RF, prelude=L.FORM_PRELUDE, enc=L.FORM_ENC, criterion=L.FORM_PC)
+    for c, line in zip(T.CASES, lines):
+        rep = {k: int(v) for k, v in (kv.split("=") for kv in line.split())}
+        assert sorted(rep) == sorted(k for k, _ in L.EncodeFormReport._fields_)  # (the program prints every field of the struct)
+        for k, bit in L.FORM_ATTEMPT_BITS:
+            rep[k] = bool(rep["attempt"] & bit)
+        for k, table in names.items():
+            rep[k] = table[rep[k]]
+        for k, v in c["want"].items():
+            assert rep[k] == v, (c["name"], k, v, rep)
+        assert rep["nblocks"] == (c["n"] + c["block"] - 1) // c["block"], c["name"]
+    T.test_the_case_table_names_every_form()

@@ -10,10 +10,17 @@
 // every threshold a form reads, whole lists and lists with a partial last block, batch passes, discovery and hinted
 // attempts with alphabets from a short list up to the row stride, nt in {0, 4..8}, frames 2^12, 2^16, 2^17 under the
 // default keys; each key on its own over the same geometries with a thinner list of attempts.
+// `encode_form_check --form` runs no sweep: it reads lines of name=value words from standard input -- one encode attempt
+// each: geometry, attempt, keys, the two values the model phase finds, CU count -- and prints for each the report
+// ansx_last_encode_form would give (the same report_* assignments the library makes), one line of name=value words.
+// tests/test_encode_form_cpu.py holds the case table of tests/test_gpu_encode_forms.py against it.
 #include "../../ans_large_alphabet_amd/csrc/ansx_encode_form.h"
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <sstream>
 #include <map>
 #include <string>
 #include <vector>
@@ -346,8 +353,68 @@ struct KeySet {
     EncKeys K;
 };
 
-int main()
+// ---------------------------------------------------------------------------------- --form: one attempt per line
+// words: kind f pa bi ck n (the geometry; nsp: a compacted pass's shorter row stride) batch longest | ns_cap nt rf_slots
+// pa_distinct sparse full fused | the keys by their EncKeys names, no_big_geo | logM max_ns cus serial.  Unnamed words are 0
+// (pc_b_pairs: 2; cus: 256).  An optimistic attempt (ns_cap != 0) is sized for frames of 2^16 and alphabets of ns_cap.
+static int print_forms()
 {
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        if (line.empty() || line[0] == '#') continue;
+        std::map<std::string, unsigned long long> w;
+        std::istringstream in(line);
+        std::string tok;
+        while (in >> tok) {
+            const size_t eq = tok.find('=');
+            if (eq == std::string::npos) { fprintf(stderr, "not name=value: %s\n", tok.c_str()); return 2; }
+            w[tok.substr(0, eq)] = strtoull(tok.c_str() + eq + 1, nullptr, 0);
+        }
+        auto get = [&](const char* k, unsigned long long d = 0) { auto it = w.find(k); if (it == w.end()) return d; const unsigned long long v = it->second; w.erase(it); return v; };
+        EncGeo g = {};
+        g.kind = (u32)get("kind"), g.f = (u32)get("f"), g.pa = (u32)get("pa"), g.block_ints = (u32)get("bi"), g.ckpt = (u32)get("ck"), g.n = get("n");
+        if (!g.block_ints || !g.n) { fprintf(stderr, "bi and n are needed: %s\n", line.c_str()); return 2; }
+        g.nblocks = (u32)((g.n + g.block_ints - 1) / g.block_ints);
+        g.NSP = (u32)get("nsp", slots_of(g.kind, g.f));
+        g.batch_pass = get("batch") != 0, g.longest = (u32)get("longest"), g.map_pow2 = g.kind != ANSX_INT;
+        EncAttempt a;
+        a.ns_cap = (u32)get("ns_cap"), a.nt = (u32)get("nt"), a.rf_slots = (u32)get("rf_slots"), a.pa_distinct = (u32)get("pa_distinct");
+        a.int_sparse = get("sparse") != 0, a.sp_full_lds = get("full") != 0;
+        const bool fused = get("fused") != 0;
+        EncKeys K;
+        K.table16_fixup = get("table16_fixup"), K.encode_gtab16 = get("encode_gtab16"), K.fin_one_wave = get("fin_one_wave");
+        K.use_pc = get("use_pc"), K.no_pc_auto = get("no_pc_auto"), K.force_pc = get("force_pc"), K.no_pc = get("no_pc"), K.encode_mode2 = get("encode_mode2");
+        K.pc_b_pairs = (u32)get("pc_b_pairs", 2), K.test_sp_bits = (u32)get("test_sp_bits"), K.cand_chains = (u32)get("cand_chains");
+        K.model_pipeline = (int)get("model_pipeline");
+        const bool no_big_geo = get("no_big_geo") != 0;
+        u32 logM = (u32)get("logM"), max_ns = (u32)get("max_ns");
+        const u32 cus = (u32)get("cus", CUS);
+        const bool serial = get("serial") != 0;
+        if (!w.empty()) { fprintf(stderr, "unknown word %s\n", w.begin()->first.c_str()); return 2; }
+        if (a.ns_cap) logM = 16, max_ns = a.ns_cap;
+        ansx_encode_form_report r = {};
+        report_remap(r, choose_remap_form(g, a), g.pa || a.int_sparse);
+        report_attempt(r, g, a, fused);
+        if (!fused) {
+            const ModelForm M = choose_model_form(g, a, K, cus, serial);
+            const u32 last = M.nranges ? g.nblocks - (M.nranges - 1) * M.range_blocks : g.nblocks;
+            report_model(r, M, M.fast ? (u32)cand_launch(M, last).variant : 0u, M.fast && g.NSP > 4096 && !no_big_geo);
+            if (!M.fast) report_prelude(r, choose_prelude_form(g, a, K, M.always16, logM, max_ns));
+        }
+        report_encoder(r, choose_encoder_form(g, K, cus, logM, max_ns));
+        printf("attempt=%u ns_cap=%u nt=%u hist=%u cpb=%u h_deferred=%u h_in_hist=%u sort=%u fin=%u fcap=%u cand_chains=%u nranges=%u range_blocks=%u big_geo=%u "
+               "rf=%u rf_slots=%u pa_small=%u pa_slots=%u pa_uqcap=%u prelude=%u table16_first=%u pre_cap=%u enc=%u enc_grid=%u enc_threads=%u enc_lds=%u "
+               "criterion=%u pairs=%u S=%u pc_grid=%u first=%u nblocks=%u\n",
+            r.attempt, r.ns_cap, r.nt, r.hist, r.cpb, r.h_deferred, r.h_in_hist, r.sort, r.fin, r.fcap, r.cand_chains, r.nranges, r.range_blocks, r.big_geo, r.rf,
+            r.rf_slots, r.pa_small, r.pa_slots, r.pa_uqcap, r.prelude, r.table16_first, r.pre_cap, r.enc, r.enc_grid, r.enc_threads, r.enc_lds, r.criterion, r.pairs,
+            r.S, r.pc_grid, r.first, r.nblocks);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 1 && !strcmp(argv[1], "--form")) return print_forms();
     std::vector<Codec> codecs;
     for (u32 f = 1; f <= 7; f++) codecs.push_back({ ANSX_FOLD, f, 0 }), codecs.push_back({ ANSX_RFOLD, f, 0 }), codecs.push_back({ ANSX_FOLD, f, 1 });
     codecs.push_back({ ANSX_MSB, 0, 0 }), codecs.push_back({ ANSX_MSB, 0, 1 }), codecs.push_back({ ANSX_INT, 0, 0 }), codecs.push_back({ ANSX_INT, 0, 1 });
