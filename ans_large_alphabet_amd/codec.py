@@ -751,6 +751,60 @@ class _Codec:
             raise err
         return offsets
 
+    # ---- ranked disjunctive queries (include/ansx.h)
+    def topk_batch_dev(self, in_ptrs, in_bytes, queries, weights, k, out_ids_ptr, out_scores_ptr=None, pay_ptrs=None,
+                       pay_sizes=None, stream=None):
+        """Many ranked disjunctive queries over the batch in_ptrs / in_bytes in one call.  queries: as for
+        union_batch_dev; weights: a sequence as long as queries of sequences of integers in [0, 2^32), weights[q][i] the
+        weight of queries[q][i].  pay_ptrs / pay_sizes: None (every payload is 1), or per list of the batch a container
+        of this codec with a value per posting.  The k ids of query q's union with the largest scores -- the sum over
+        its postings of weight * payload -- ordered by (score descending, id ascending) go to uint32 entries
+        [q * k, q * k + counts[q]) of out_ids_ptr (device, len(queries) * k entries) and their scores to out_scores_ptr
+        when given; the entries behind are ANSX_NO_ID / 0.  Returns counts, np.uint32 of len(queries): min(k, distinct
+        ids).  A score of 2^32 - 1 or more raises AnsxError(ERR_DOMAIN) with .bad_query.  An AnsxError carries
+        .bad_container / .bad_query where the call set them (None otherwise)."""
+        ptrs, sizes, terms, qoff = self._batch_queries(in_ptrs, in_bytes, queries, 0)
+        nc, nq = ptrs.size, len(queries)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k <= 0xFFFFFFFF:
+            raise ValueError("k must be an integer in [0, 2^32), got %r" % (k,))
+        if isinstance(weights, (str, bytes)) or not hasattr(weights, "__len__") or len(weights) != nq:
+            raise ValueError("weights must be a sequence as long as queries")
+        flat = []
+        for q, w in enumerate(weights):
+            if isinstance(w, (str, bytes)) or not hasattr(w, "__len__"):
+                raise ValueError("weights of query %d are not a sequence of integers" % q)
+            w = np.asarray(w)
+            if w.ndim != 1 or w.size != int(qoff[q + 1] - qoff[q]) or (w.size and w.dtype.kind not in "ui"):
+                raise ValueError("weights of query %d must be a flat sequence of integers, one per term" % q)
+            if w.size and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF):
+                raise ValueError("weights of query %d lie outside [0, 2^32)" % q)
+            flat.append(w.astype(np.uint32))
+        wts = np.ascontiguousarray(np.concatenate(flat + [np.zeros(1, dtype=np.uint32)]), dtype=np.uint32)  # (never empty)
+        pays = psizes = None
+        if (pay_ptrs is None) != (pay_sizes is None):
+            raise ValueError("pay_ptrs and pay_sizes go together")
+        if pay_ptrs is not None:
+            pays = np.ascontiguousarray(pay_ptrs, dtype=np.uint64).reshape(-1)
+            psizes = np.ascontiguousarray(pay_sizes, dtype=np.uint64).reshape(-1)
+            if pays.size != nc or psizes.size != nc:
+                raise ValueError("pay_ptrs / pay_sizes and in_ptrs differ in length (%d, %d, %d)" % (pays.size, psizes.size, nc))
+            if nc == 0:  # (never a null array: the library answers)
+                pays, psizes = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+        counts = np.zeros(nq, dtype=np.uint32)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c, bad_q = C.c_size_t(unset), C.c_size_t(unset)
+        st = L.lib().ansx_topk_batch_dev(
+            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None,
+            None if pays is None else pays.ctypes.data, None if psizes is None else psizes.ctypes.data, nc,
+            terms.ctypes.data, wts.ctypes.data, qoff.ctypes.data, nq, int(k), out_ids_ptr, out_scores_ptr,
+            counts.ctypes.data if nq else None, C.byref(bad_c), C.byref(bad_q), stream)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + ".topk_batch_dev")
+            err.bad_container = int(bad_c.value) if bad_c.value != unset else None
+            err.bad_query = int(bad_q.value) if bad_q.value != unset else None
+            raise err
+        return counts
+
     def union_dev(self, in_ptrs, in_bytes, out_ids_ptr, out_capacity, out_cnt_ptr=None, stream=None):
         """union_batch_dev's single query over all the lists of the batch in_ptrs / in_bytes, in batch order.  Returns the
         number of distinct docids; more than out_capacity raises AnsxError(ERR_CAPACITY) with .needed = that number,

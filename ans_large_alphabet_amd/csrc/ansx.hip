@@ -38,6 +38,7 @@
 #include "ansx_intersect_batch.h"
 #include "ansx_union.h"
 #include "ansx_bool.h"
+#include "ansx_topk.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
@@ -3383,6 +3384,197 @@ int bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_
     return run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
 }
 
+// ansx_topk_batch_dev (ansx_topk.h; the plan: unb_plan with the terms behind its pairs).  The front
+// end of the calls above over the id containers AND the payloads of the referenced lists, interleaved (list u of the
+// referenced ones at 2u, its payload at 2u + 1), still one round trip for the headers; the groups of unb_plan under HALF
+// the budget -- a group holds twice what a union's does; per group (topk_group): ids and payloads decoded with the same
+// offsets into two buffers of one layout, the scan over the ids, one upload of the pair and weight tables, a launch of
+// k_topk_merge per round, the unique step as in unb_group (with positions), k_topk_scores, the eight rounds of
+// k_topk_hist / k_topk_pick, k_topk_gather and k_topk_sort, which writes the caller's arrays.
+// Workspace: 4 (8 with payloads) bytes per int of the group's lists, 20 per int of its queries' lists as named (two key and
+// two value merge buffers, the scores), a pass's, the scan's, IsectWork over the merge buffer, and per query 8 k bytes of
+// slots, 1 KiB of histogram, 24 bytes of state and bounds and 48 per pair of tables.
+// Host waits: one for the headers; per group those of its decode passes (ids, then payloads) and ONE behind the sort,
+// which brings the scan's flag word, the overflow word and the bounds among the heads; one per call at the end.  None
+// between merge rounds or select rounds; no grid depends on data the host has not seen.
+struct TopkOut {
+    const u32* weights;
+    u32 k, pow2;
+    u32 *ids, *scores, *counts;
+    bool pays;
+};
+int topk_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g, std::vector<u64>& off, size_t count,
+    const TopkOut& o, const std::function<size_t(u32)>& batch_index, size_t* bad_container, size_t* bad_query, hipStream_t s)
+{
+    int rc;
+    const size_t Q = g.q1 - g.q0, q1 = rup(Q + 1, 4);
+    const u64 L = g.at.back(), M = g.seg[Q];
+    const u32 k = o.k;
+    if (M == 0) {  // (every list is empty: nothing is decoded, every slot is ANSX_NO_ID / 0)
+        LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)nullptr, (const u32*)nullptr, (u64)g.q0, k, o.pow2,
+            o.ids, o.scores, (const u32*)nullptr);
+        if (o.counts) memset(o.counts + g.q0, 0, 4 * Q);
+        return ANSX_OK;
+    }
+    for (const u64 t : g.tiles)
+        if (t > 0x7FFFFFFFull) {  // (a grid; 2^31 non-empty pairs in a round)
+            if (bad_query) *bad_query = g.q0;
+            return ANSX_ERR_ARG;
+        }
+    // the lists | their payloads | two key and two value merge buffers | the scores | the slots (u64: at an even int); each
+    // with the decoders' slack behind
+    const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)M, 4) + 16;
+    const size_t o_m = (o.pays ? 2 : 1) * o_c, o_s = o_m + 5 * half;
+    if ((rc = ensure(c, c->isectb_ids, 4 * o_s + 8 * Q * (size_t)k))) return rc;
+    u32* ids = (u32*)c->isectb_ids.p;
+    u32* pay = o.pays ? ids + o_c : nullptr;
+    u32* kb[2] = { ids + o_m, ids + o_m + half };
+    u32* vb[2] = { ids + o_m + 2 * half, ids + o_m + 3 * half };
+    u32* score = ids + o_m + 4 * half;
+    u64* slots = (u64*)(ids + o_s);
+    GeometryGroups geo;
+    for (size_t i = 0; i < g.lists.size(); i++) off[g.lists[i]] = g.at[i], geo[br_geometry(F.rs[g.lists[i]].H)].push_back(g.lists[i]);
+    if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, ids, bad_container, s))) return rc;
+    if (o.pays) {  // (the payload of referenced list r stands at r + 1: the same n, any geometry)
+        geo.clear();
+        for (size_t i = 0; i < g.lists.size(); i++) {
+            const u32 r = g.lists[i] + 1u;
+            off[r] = g.at[i], geo[br_geometry(F.rs[r].H)].push_back(r);
+        }
+        if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, pay, bad_container, s))) return rc;
+    }
+
+    // one upload: zero flag words (k_isect_compact's four, k_union_heads' one) | the overflow word | the queries' spans |
+    // every round's pairs | their weights; behind it on the device: the bounds among the heads | prefixes | what is left
+    // to find | cursors | histograms | IsectWork
+    Upload U;
+    const auto s_fl = U.add<u32>(8);
+    const auto s_of = U.add<u32>(4);
+    const auto s_seg = U.add<u32>(Q + 1);
+    const auto s_p = U.add<ansx_unb_pair>(g.pairs.size());
+    const auto s_w = U.add<u32>(2 * g.pairs.size());
+    const size_t up = U.end;
+    const auto s_hs = U.add<u32>(q1);  // (the host's copy: read back)
+    const auto s_pre = U.add<u64>(Q);
+    const auto s_want = U.add<u32>(Q);
+    const auto s_cur = U.add<u32>(rup(Q, 4));  // (cleared with the histograms behind it)
+    const auto s_hist = U.add<u32>(Q * (size_t)ANSX_TOPK_BINS);
+    const size_t o_w = rup(U.end, 16);
+    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, s_hs.off + s_hs.bytes))) return rc;
+    if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(M, false)))) return rc;
+    U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
+    memset(U.pin(s_fl), 0, s_fl.bytes);
+    u32* hof = U.pin(s_of);
+    hof[0] = ANSX_TOPK_NONE, hof[1] = hof[2] = hof[3] = 0;
+    U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
+    u32* hw = U.pin(s_w);
+    for (size_t i = 0; i < g.pterm.size(); i++) hw[i] = g.pterm[i] == ANSX_TOPK_NONE ? 0u : o.weights[g.pterm[i]];
+    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(U.dev(s_cur), 0, s_hist.off + s_hist.bytes - s_cur.off, s));
+    const u32* zero = U.dev(s_fl);
+    u32* uflag = U.dev(s_fl) + 4;
+    const u32* seg = U.dev(s_seg);
+    u32* hseg = U.dev(s_hs);
+
+    SumsPlan S;
+    if ((rc = sums_prepare(c, (uintptr_t)ids, L, g.at.data(), g.lists.size(), s, &S))) return rc;
+    if ((rc = sums_launch(c, ids, L, g.lists.size(), S, s))) return rc;
+    for (u32 r = 0; r < g.rounds; r++) {
+        const u32 np = g.roff[r + 1] - g.roff[r];
+        if (np == 0) continue;  // (the queries that have this round are empty)
+        LAUNCH(c, "k_topk_merge", k_topk_merge, (u32)g.tiles[r], ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)pay,
+            (const u32*)kb[1 - (r & 1u)], (const u32*)vb[1 - (r & 1u)], kb[r & 1u], vb[r & 1u],
+            (const ansx_unb_pair*)U.dev(s_p) + g.roff[r], (const u32*)U.dev(s_w) + 2 * (size_t)g.roff[r], np, (const u32*)S.flag);
+    }
+    const u32 fin = (g.rounds - 1u) & 1u;
+    u32 *hid = kb[1 - fin], *idx = vb[1 - fin];  // the heads' ids and positions: where the last round read
+    const IsectWork W(U.devp + o_w, M, false);
+    LAUNCH(c, "k_union_heads", k_union_heads, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)kb[fin], (u32)M, seg, (u32)Q, W.ballots,
+        W.counts, (const u32*)S.flag, uflag);
+    LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
+    LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)kb[fin], (u32)M, (const u64*)W.ballots,
+        (const u64*)W.counts, (const u64*)W.total, M, (const u64*)nullptr, hid, idx, (u64*)nullptr, zero, (const u32*)uflag);
+    LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, seg, (u32)Q, (u32)M, (const u64*)W.ballots,
+        (const u64*)W.counts, (const u64*)W.total, hseg);
+    LAUNCH(c, "k_topk_scores", k_topk_scores, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)idx, (const u32*)vb[fin], (const u32*)hseg, seg,
+        (u32)Q, (const u64*)W.total, (u32)M, score, U.dev(s_of), (const u32*)S.flag);
+    for (u32 r = 0; r < ANSX_TOPK_ROUNDS; r++) {
+        LAUNCH(c, "k_topk_hist", k_topk_hist, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)hid, (const u32*)score, (const u32*)hseg, (u32)Q,
+            (const u64*)W.total, (u32)M, r, (const u64*)U.dev(s_pre), U.dev(s_hist), (const u32*)S.flag);
+        LAUNCH(c, "k_topk_pick", k_topk_pick, (u32)((Q + 3) / 4), 256, 0, s, (const u32*)hseg, (u32)Q, k, r, U.dev(s_pre), U.dev(s_want),
+            U.dev(s_hist), (const u32*)S.flag);
+    }
+    LAUNCH(c, "k_topk_gather", k_topk_gather, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)hid, (const u32*)score, (const u32*)hseg, (u32)Q,
+        (const u64*)W.total, (u32)M, k, (const u64*)U.dev(s_pre), U.dev(s_cur), slots, (const u32*)S.flag);
+    LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)slots, (const u32*)hseg, (u64)g.q0, k, o.pow2, o.ids,
+        o.scores, (const u32*)S.flag);
+    u32* hflag = &c->pin->isect_sflag;
+    HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(hof, U.dev(s_of), 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(U.pin(s_hs), hseg, 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (*hflag != ANSX_SS_NONE) {  // the first list of the buffer whose sum left 32 bits
+        if (bad_container && *hflag < g.lists.size()) *bad_container = batch_index(g.lists[*hflag]);
+        return ANSX_ERR_DOMAIN;
+    }
+    if (hof[0] != ANSX_TOPK_NONE) {  // the first query of the group with a score of 2^32 - 1 or more
+        if (bad_query) *bad_query = g.q0 + hof[0];
+        return ANSX_ERR_DOMAIN;
+    }
+    const u32* hs = U.pin(s_hs);
+    if (o.counts)
+        for (size_t j = 0; j < Q; j++) o.counts[g.q0 + j] = std::min<u32>(k, hs[j + 1] - hs[j]);
+    return ANSX_OK;
+}
+
+int topk_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
+    const size_t* pay_bytes, size_t count, const u32* terms, const u32* weights, const u64* qoff, size_t nq, u32 k, u32* d_out_ids,
+    u32* d_out_scores, u32* out_counts, size_t* bad_container, size_t* bad_query, hipStream_t s)
+{
+    int rc;
+    const size_t nt = (size_t)qoff[nq];
+    BrFront F;
+    std::vector<u32> uniq;  // (with payloads: the referenced lists, ascending)
+    if (d_pays) {
+        std::vector<u32> urid, all(2 * nt);
+        br_refs(terms, nt, count, &uniq, &urid);
+        std::vector<const u8*> ptr(2 * uniq.size());
+        std::vector<size_t> len(2 * uniq.size());
+        for (size_t u = 0; u < uniq.size(); u++)
+            ptr[2 * u] = d_ins[uniq[u]], len[2 * u] = in_bytes[uniq[u]], ptr[2 * u + 1] = d_pays[uniq[u]], len[2 * u + 1] = pay_bytes[uniq[u]];
+        for (size_t j = 0; j < nt; j++) all[j] = 2 * urid[j], all[nt + j] = 2 * urid[j] + 1;
+        size_t bad = ptr.size();
+        rc = batch_ranges_front(c, kind, f, ptr.data(), len.data(), ptr.size(), all.data(), all.size(), nullptr, &F, &bad, s);
+        if (rc && rc != ANSX_ERR_FORMAT) return rc;
+        // the smallest referenced list whose headers fail the checks (bad: every entry in front of it passed) or differ in n
+        for (size_t u = 0; 2 * u + 1 < bad; u++)
+            if (F.rs[2 * u].H.n != F.rs[2 * u + 1].H.n) {
+                bad = 2 * u, rc = ANSX_ERR_FORMAT;
+                break;
+            }
+        if (rc) {
+            if (bad_container) *bad_container = uniq[bad / 2];
+            return rc;
+        }
+    } else if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, terms, nt, nullptr, &F, bad_container, s)))
+        return rc;
+    const std::function<size_t(u32)> batch_index = [&](u32 r) -> size_t { return d_pays ? uniq[r / 2] : F.ref[r]; };
+    std::vector<u64> n(F.ref.size());
+    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
+    std::vector<UnbGroup> groups;
+    const u64 budget = (c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT) / 2;
+    if ((rc = unb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query, nullptr, nullptr, true)))
+        return rc;
+    u32 pow2 = 1;
+    while (pow2 < k) pow2 <<= 1;
+    const TopkOut o = { weights, k, pow2, d_out_ids, d_out_scores, out_counts, d_pays != nullptr };
+    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
+    for (const UnbGroup& g : groups)
+        if ((rc = topk_group(c, kind, f, F, g, off, count, o, batch_index, bad_container, bad_query, s))) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ANSX_OK;
+}
+
 // The argument checks of the random-access entry points, one per argument shape: everything a call decides before the
 // context is touched.  The plain and the sums entry of a shape share them; what a sums or search entry adds (bases,
 // targets, outputs) it checks itself.
@@ -4036,6 +4228,35 @@ int ansx_bool_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_in
     return run_call(c, stream, [&](hipStream_t s) {
         return bool_batch(c, kind, f, d_ins, in_bytes, count, op, terms, (const u64*)qoff, xterms, (const u64*)xqoff, nqueries, d_out_ids,
             out_capacity, (u64*)out_offsets, bad_container, bad_query, s);
+    });
+}
+
+int ansx_topk_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint64_t* qoff, size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts,
+    size_t* bad_container, size_t* bad_query, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    uint64_t offs_stand_in = 0;  // (the parents' out_offsets: this call has none)
+    if (queries_args(c, d_ins, in_bytes, count, terms, qoff, nqueries, d_out_ids, nullptr, 0, &offs_stand_in, bad_container, bad_query))
+        return ANSX_ERR_ARG;
+    if (nqueries > 0 && !weights) return ANSX_ERR_ARG;
+    if (k == 0 || k > ANSX_TOPK_MAX_K || (u64)nqueries * k > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (!d_out_ids || ((uintptr_t)d_out_scores & 3u)) return ANSX_ERR_ARG;
+    if (d_pays && nqueries > 0) {
+        if (!pay_bytes) return ANSX_ERR_ARG;
+        for (size_t q = 0; q < nqueries; q++)  // (only the payloads of the lists some query names are looked at)
+            for (u64 j = qoff[q]; j < qoff[q + 1]; j++)
+                if (!d_pays[terms[j]] || ((uintptr_t)d_pays[terms[j]] & 15u)) {
+                    if (bad_query) *bad_query = q;
+                    if (bad_container) *bad_container = terms[j];
+                    return ANSX_ERR_ARG;
+                }
+    }
+    if (nqueries == 0) return ANSX_OK;
+    return run_call(c, stream, [&](hipStream_t s) {
+        return topk_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, (const u64*)qoff, nqueries, k, d_out_ids,
+            d_out_scores, out_counts, bad_container, bad_query, s);
     });
 }
 

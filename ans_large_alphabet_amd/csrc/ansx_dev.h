@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#define ANSX_PLAN_FN __host__ __device__ __forceinline__  // the functions ansx_plan_types.h shares with the host's checks
 #include "ansx_plan_types.h"  // u8 .. i64, and the plain structs the host's plans fill (ansx_blk_out, ...)
 
 #define ANSX_HD __host__ __device__ __forceinline__

@@ -3,9 +3,9 @@
 // tables a pass over blocks of many containers takes; and the steps and pass tables of a batch of lists to encode
 // (ansx_encode_batch_dev); and the groups, drivers and round tables of a batch of conjunctive queries
 // (ansx_intersect_batch_dev); and the groups, rounds and pair tables of a batch of disjunctive queries
-// (ansx_union_batch_dev).  Pure host arithmetic: no context, no stream, no device pointer
+// (ansx_union_batch_dev, and with the terms behind the pairs of ansx_topk_batch_dev).  Pure host arithmetic: no context, no stream, no device pointer
 // (addresses travel as integers), so it builds with a plain host compiler and is tested on the CPU
-// (tests/tools/plan_check.cpp, tests/tools/isect_batch_plan_check.cpp, tests/tools/union_plan_check.cpp).  The plain structs the kernels read these plans through are in ansx_plan_types.h,
+// (tests/tools/plan_check.cpp, tests/tools/isect_batch_plan_check.cpp, tests/tools/union_plan_check.cpp, tests/tools/topk_plan_check.cpp).  The plain structs the kernels read these plans through are in ansx_plan_types.h,
 // which the kernel headers include.
 #pragma once
 #include "../../include/ansx.h"
@@ -581,6 +581,9 @@ struct UnbGroup {
     std::vector<u32> xt_off;           // with exclusions (plan_excl_tables): q1 - q0 + 1
     std::vector<ansx_isb_list> xt;     // ... every query's excluded lists
     std::vector<u32> xt_list;          // ... the referenced list behind every entry of xt
+    std::vector<u32> pterm;            // with want_terms (ansx_topk_batch_dev): two per pair -- the named term (its place in
+                                       // rid) sides a and b of a first-round pair came from, ANSX_TOPK_NONE for a side of no
+                                       // ints and for every side of a later round
     u64 ints;                          // buffer + twice the merge buffer: what the budget bounds
     u32 rounds;                        // R
 };
@@ -596,8 +599,10 @@ static inline u32 unb_rounds(u64 m)
 // is a u32).  A group ends in front of the query that would take it over `budget` ints or its merge buffer to 2^32; a
 // query over the budget alone is a group of its own.  A list two groups name is decoded in both.  tile: the outputs
 // of a workgroup of the merge.  xrid / xqoff: null, or the lists every query excludes (plan_excl_tables).
+// want_terms: pterm is filled beside pairs (a ranked query lays its weights there); nothing else differs.
 static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64* qoff, size_t nq, u64 budget, u32 tile,
-    std::vector<UnbGroup>* groups, size_t* bad_query, const u32* xrid = nullptr, const u64* xqoff = nullptr)
+    std::vector<UnbGroup>* groups, size_t* bad_query, const u32* xrid = nullptr, const u64* xqoff = nullptr,
+    bool want_terms = false)
 {
     groups->clear();
     std::vector<u64> tot(nq);
@@ -612,6 +617,7 @@ static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64*
     }
     std::vector<u32> stamp(nref, 0xFFFFFFFFu), slot(nref, 0), fresh;
     std::vector<std::vector<ansx_unb_pair>> byround;
+    std::vector<std::vector<u32>> byterm;   // (want_terms: two per pair of byround)
     std::vector<std::pair<u32, u32>> runs;  // (where in the merge buffers, ints)
     for (size_t q = 0; q < nq;) {
         groups->emplace_back();
@@ -644,6 +650,7 @@ static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64*
         const u32 R = g.rounds;
         g.seg.resize(Q + 1);
         byround.assign(R, {});
+        byterm.assign(want_terms ? R : 0, {});
         u32 dst = 0;
         for (size_t j = 0; j < Q; j++) {
             const u32* t = rid + qoff[g.q0 + j];
@@ -664,6 +671,11 @@ static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64*
                         p.a = A.second ? g.at[slot[ra]] : 0, p.b = B.second ? g.at[slot[rb]] : 0, p.from_lists = 1;
                     }
                     byround[R - rq + k].push_back(p);
+                    if (want_terms) {
+                        const u64 ta = qoff[g.q0 + j] + 2 * i;
+                        byterm[R - rq + k].push_back(k == 0 && A.second ? (u32)ta : ANSX_TOPK_NONE);
+                        byterm[R - rq + k].push_back(k == 0 && B.second ? (u32)(ta + 1) : ANSX_TOPK_NONE);
+                    }
                 }
         }
         g.seg[Q] = dst;
@@ -675,6 +687,7 @@ static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64*
                 first += ((u64)p.na + p.nb + tile - 1) / tile;
             }
             g.pairs.insert(g.pairs.end(), byround[r].begin(), byround[r].end());
+            if (want_terms) g.pterm.insert(g.pterm.end(), byterm[r].begin(), byterm[r].end());
             g.roff.push_back((u32)g.pairs.size());
             g.tiles.push_back(first);
         }

@@ -1,5 +1,6 @@
 // ansx -- the integer names and the plain structs and constants the host's plans (ansx_plan.h) fill and the kernels read
-// them through.  No code: it builds with a plain host compiler, and the kernel headers take it through ansx_dev.h.
+// them through.  No code but the arithmetic of ansx_topk_batch_dev's selection at its end: it builds with a plain host
+// compiler, and the kernel headers take it through ansx_dev.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -139,3 +140,53 @@ struct ansx_unb_pair {
     u32 dst, tile;
     u32 from_lists, pad_;
 };
+
+// Ranked disjunctive queries (ansx_topk_batch_dev, ansx_topk.h).  The only code of this header: the arithmetic of the
+// selection, which the kernels and the CPU check (tests/tools/topk_plan_check.cpp) both run, so it is written once and
+// builds for either side.
+#ifndef ANSX_PLAN_FN  // (ansx_dev.h names the kernels' side before it includes this header)
+#define ANSX_PLAN_FN static inline
+#endif
+
+#define ANSX_TOPK_NONE 0xFFFFFFFFu  // the overflow word while no query's score has left 32 bits; no term behind a side of a pair
+#define ANSX_TOPK_DIGIT_BITS 8u     // the radix select's digit ...
+#define ANSX_TOPK_BINS (1u << ANSX_TOPK_DIGIT_BITS)
+#define ANSX_TOPK_ROUNDS (64u / ANSX_TOPK_DIGIT_BITS)  // ... and its rounds over a 64-bit key, from the top digit down
+
+// weight * payload in 64 bits, saturated
+ANSX_PLAN_FN u32 topk_sat32(u32 w, u32 p)
+{
+    const u64 v = (u64)w * p;
+    return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)v;
+}
+
+// The key of an id inside its query: larger = ranked earlier (score descending, id ascending); distinct ids, distinct keys.
+ANSX_PLAN_FN u64 topk_key(u32 score, u32 id) { return ((u64)score << 32) | (u32)~id; }
+ANSX_PLAN_FN u32 topk_key_id(u64 key) { return ~(u32)key; }
+ANSX_PLAN_FN u32 topk_key_score(u64 key) { return (u32)(key >> 32); }
+
+// round r = 0 .. ANSX_TOPK_ROUNDS - 1 looks at this digit of a key ...
+ANSX_PLAN_FN u32 topk_digit(u64 key, u32 r) { return (u32)(key >> (64u - ANSX_TOPK_DIGIT_BITS * (r + 1u))) & (ANSX_TOPK_BINS - 1u); }
+
+// ... of the keys that agree with the prefix found so far in the digits of the rounds before
+ANSX_PLAN_FN bool topk_candidate(u64 key, u64 prefix, u32 r)
+{
+    const u32 sh = 64u - ANSX_TOPK_DIGIT_BITS * r;
+    return r == 0 || (key >> sh) == (prefix >> sh);
+}
+ANSX_PLAN_FN u64 topk_with_digit(u64 prefix, u32 r, u32 d) { return prefix | ((u64)d << (64u - ANSX_TOPK_DIGIT_BITS * (r + 1u))); }
+
+// The digit that holds the want-th largest (want >= 1) of the keys counted in h[0 .. n): the largest d with
+// h[d] + ... + h[n - 1] >= want; *above: the keys in the digits above it (< want).  Fewer than `want` keys in all -- not
+// with a histogram of at least `want` keys -- gives digit 0.
+ANSX_PLAN_FN u32 topk_pick(const u32* h, u32 n, u32 want, u32* above)
+{
+    u32 a = 0, d = n;
+    while (d > 0) {
+        d--;
+        if (h[d] >= want - a) break;  // (a < want: no wrap)
+        a += h[d];  // (still below want)
+    }
+    *above = a;
+    return d;
+}

@@ -734,6 +734,42 @@ int ansx_bool_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* co
     size_t nqueries, uint32_t* d_out_ids, size_t out_capacity, uint64_t* out_offsets, size_t* bad_container,
     size_t* bad_query, void* stream);
 
+/* ansx_topk_batch_dev: ranked disjunctive queries over one batch of gap-coded lists in one call (DESIGN.md section 3m,
+ * csrc/ansx_topk.h).  The batch, terms, qoff, bad_container, bad_query and stream are ansx_union_batch_dev's.  weights is
+ * a HOST array beside terms: weights[j] belongs to the term named at terms[j].  d_pays[t] (HOST array of 16-byte aligned
+ * DEVICE pointers, pay_bytes[t] its size) is a container of the same codec holding a value per posting of list t (a term
+ * frequency); its header's n must equal the list's, its geometry may differ.  d_pays == NULL: every payload is 1 and
+ * pay_bytes is ignored.
+ * With s_t the ids ansx_decode_sums_dev gives for list t and p_t what ansx_decode_dev gives for its payload, query q scores
+ *   score(d) = sum over j in [qoff[q], qoff[q + 1]), t = terms[j], of the sum over i with s_t[i] == d of weights[j] * p_t[i]
+ * for every id d of its union: a list named twice contributes twice, a list's own repeated ids each contribute, a score
+ * of 0 is still a result.  Its result is the union's ids ordered by (score descending, id ascending) and cut to the first
+ * k, at a fixed stride: d_out_ids[q * k + r] and d_out_scores[q * k + r] (optional) for r < out_counts[q] =
+ * min(k, distinct ids) -- out_counts an optional HOST array of nqueries -- and ANSX_NO_ID / 0 in the entries behind, so
+ * the whole image of nqueries * k entries is defined; there is no size query.  0xFFFFFFFF is an id like any other.
+ * A product weight * payload is taken in 64 bits and saturates at 2^32 - 1; the sum per id is taken in 64 bits and a sum
+ * of 2^32 - 1 or more is ANSX_ERR_DOMAIN with *bad_query = the first such query in batch order (an atomic minimum on the
+ * device, read back with the group's one wait); the outputs are unspecified then.
+ * Errors, in this order: before the context is touched, ANSX_ERR_ARG for the parents' checks on ctx / batch / terms /
+ * qoff with the same *bad_query / *bad_container; a null weights with nqueries > 0; k == 0 or k > ANSX_TOPK_MAX_K;
+ * nqueries * k > UINT32_MAX; a null or misaligned d_out_ids or a misaligned d_out_scores; with d_pays, a null pay_bytes or
+ * a null or misaligned d_pays[t] of a referenced list (*bad_query, *bad_container).  nqueries == 0: ANSX_OK, nothing is
+ * launched, the context is untouched.  Then ANSX_ERR_FORMAT with *bad_container = the smallest referenced batch index
+ * whose id header or payload header fails decode_dev's checks or whose payload's n differs from the list's;
+ *   ANSX_ERR_ARG with *bad_query for the union plan's limits;
+ *   found on the device: ANSX_ERR_FORMAT with *bad_container = count; ANSX_ERR_DOMAIN with *bad_container = a list whose
+ *   id sum leaves 32 bits, or with *bad_query for a score (above).
+ * Unreferenced containers and payloads are not examined and may be NULL.  No trace is left in the context, which stays
+ * usable after any error.  Groups, workspace and host waits: DESIGN.md section 3m -- the union's groups under half of
+ * ANSX_ISECT_BATCH_INTS; one wait for the headers, per group its decode passes' and ONE behind the sort, one per call.
+ * Out of scope: exclusion behind a ranked query, floating-point scores, k above 1024, dynamic pruning (WAND / MaxScore),
+ * a ranked AND. */
+#define ANSX_TOPK_MAX_K 1024u
+int ansx_topk_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint64_t* qoff, size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts,
+    size_t* bad_container, size_t* bad_query, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
