@@ -35,7 +35,7 @@ EXPORTS = [
     "ansx_decode_device_ranges_sums_dev", "ansx_next_geq_dev", "ansx_encode_batch_gaps_bases_dev",
     "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
     "ansx_intersect_ids_dev", "ansx_intersect_dev", "ansx_intersect_batch_dev", "ansx_union_batch_dev", "ansx_union_dev",
-    "ansx_bool_batch_dev", "ansx_last_encode_form", "ansx_topk_batch_dev",
+    "ansx_bool_batch_dev", "ansx_last_encode_form", "ansx_topk_batch_dev", "ansx_topk_bool_batch_dev",
 ]
 
 
@@ -210,6 +210,9 @@ def lib():
     L.ansx_topk_batch_dev.restype = C.c_int
     L.ansx_topk_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, sz, C.c_uint32, vp, vp, vp,
                                       C.POINTER(sz), C.POINTER(sz), vp]
+    L.ansx_topk_bool_batch_dev.restype = C.c_int
+    L.ansx_topk_bool_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, C.c_int, vp, vp, vp, vp, vp, sz, C.c_uint32,
+                                           vp, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]
     L.ansx_union_dev.restype = C.c_int
     L.ansx_union_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(sz), vp]
     L.ansx_container_info.restype = C.c_int

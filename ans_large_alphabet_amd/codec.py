@@ -763,8 +763,35 @@ class _Codec:
         when given; the entries behind are ANSX_NO_ID / 0.  Returns counts, np.uint32 of len(queries): min(k, distinct
         ids).  A score of 2^32 - 1 or more raises AnsxError(ERR_DOMAIN) with .bad_query.  An AnsxError carries
         .bad_container / .bad_query where the call set them (None otherwise)."""
+        return self._topk_call("topk_batch_dev", in_ptrs, in_bytes, queries, weights, None, k, out_ids_ptr, None, out_scores_ptr,
+                               pay_ptrs, pay_sizes, stream)
+
+    # ---- ranked Boolean queries (include/ansx.h, DESIGN.md section 3n)
+    def topk_bool_batch_dev(self, in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, op="all", out_scores_ptr=None,
+                            pay_ptrs=None, pay_sizes=None, stream=None):
+        """topk_batch_dev over the ids of ALL of a query's lists (op "all") or of ANY of them (op "any"), less every id that
+        occurs in one of the query's excluded lists.  excludes: None, or a sequence as long as queries of (possibly empty)
+        sequences of batch indices, as for bool_batch_dev.  Scores, the order, the outputs and counts (np.uint32 of
+        len(queries): min(k, ids in the result)) are topk_batch_dev's; every posting of a result's id is scored, and the
+        id appears once.  A list that is only excluded needs no payload (its pay_ptrs entry may be 0).  A score of
+        2^32 - 1 or more of an id of the result raises AnsxError(ERR_DOMAIN) with .bad_query.  An AnsxError carries
+        .bad_container / .bad_query where the call set them (None otherwise)."""
+        ops = {"all": L.BOOL_ALL, "any": L.BOOL_ANY}
+        if op not in ops:
+            raise ValueError("op must be 'all' or 'any', got %r" % (op,))
+        return self._topk_call("topk_bool_batch_dev", in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, ops[op],
+                               out_scores_ptr, pay_ptrs, pay_sizes, stream)
+
+    def _topk_call(self, what, in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, op, out_scores_ptr, pay_ptrs,
+                   pay_sizes, stream):
+        """What the two ranked calls share: the checks of their arguments and the call; op None: ansx_topk_batch_dev"""
         ptrs, sizes, terms, qoff = self._batch_queries(in_ptrs, in_bytes, queries, 0)
         nc, nq = ptrs.size, len(queries)
+        xterms = xqoff = None
+        if excludes is not None:
+            xterms, xqoff = self._flatten_queries(excludes, "excludes", "excludes of query")
+            if xqoff.size != nq + 1:
+                raise ValueError("excludes and queries differ in length (%d, %d)" % (xqoff.size - 1, nq))
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k <= 0xFFFFFFFF:
             raise ValueError("k must be an integer in [0, 2^32), got %r" % (k,))
         if isinstance(weights, (str, bytes)) or not hasattr(weights, "__len__") or len(weights) != nq:
@@ -793,13 +820,17 @@ class _Codec:
         counts = np.zeros(nq, dtype=np.uint32)
         unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
         bad_c, bad_q = C.c_size_t(unset), C.c_size_t(unset)
-        st = L.lib().ansx_topk_batch_dev(
-            self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None,
-            None if pays is None else pays.ctypes.data, None if psizes is None else psizes.ctypes.data, nc,
-            terms.ctypes.data, wts.ctypes.data, qoff.ctypes.data, nq, int(k), out_ids_ptr, out_scores_ptr,
-            counts.ctypes.data if nq else None, C.byref(bad_c), C.byref(bad_q), stream)
+        head = (self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None,
+                None if pays is None else pays.ctypes.data, None if psizes is None else psizes.ctypes.data, nc)
+        tail = (nq, int(k), out_ids_ptr, out_scores_ptr, counts.ctypes.data if nq else None, C.byref(bad_c), C.byref(bad_q), stream)
+        if op is None:
+            st = L.lib().ansx_topk_batch_dev(*head, terms.ctypes.data, wts.ctypes.data, qoff.ctypes.data, *tail)
+        else:
+            st = L.lib().ansx_topk_bool_batch_dev(
+                *head, op, terms.ctypes.data, wts.ctypes.data, qoff.ctypes.data, None if xterms is None else xterms.ctypes.data,
+                None if xqoff is None else xqoff.ctypes.data, *tail)
         if st != L.OK:
-            err = L.AnsxError(st, self.name() + ".topk_batch_dev")
+            err = L.AnsxError(st, self.name() + "." + what)
             err.bad_container = int(bad_c.value) if bad_c.value != unset else None
             err.bad_query = int(bad_q.value) if bad_q.value != unset else None
             raise err

@@ -39,6 +39,7 @@
 #include "ansx_union.h"
 #include "ansx_bool.h"
 #include "ansx_topk.h"
+#include "ansx_topk_bool.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
@@ -204,6 +205,7 @@ struct ansx_ctx {
         int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
         u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev, ansx_decode_batch_ranges_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
         int bool_form = 0;            // ANSX_BOOL_FORM: 0 k_bool_exclude's own rule, 1 "search", 2 "staged" (ANSX_BOOL_FORM_*; tests and the bench tool force one)
+        int topk_bool_form = 0;       // ANSX_TOPK_BOOL_FORM: 0 the default of k_topkb_match, 1 "search", 2 "bounded" (tests and the bench tool force one)
         int intersect_form = 0;       // ANSX_INTERSECT_FORM: 0 by ANSX_ISECT_FULL_PER_BLOCK, 1 "selective", 2 "full" (tests and the bench tool force one)
         u64 isect_batch_ints = 0;     // ANSX_ISECT_BATCH_INTS: the ints a group of ansx_intersect_batch_dev or ansx_union_batch_dev may take (0 = ANSX_ISECT_BATCH_INTS_DEFAULT; tests force small groups)
         u32 range_sums_wg_max = 0;    // ANSX_RANGE_SUMS_WG_MAX: the largest block the one-kernel scan of the range sums takes (0 = ANSX_RS_WG_MAX; the bench tool measures both sides of the switch)
@@ -3402,7 +3404,48 @@ struct TopkOut {
     u32 k, pow2;
     u32 *ids, *scores, *counts;
     bool pays;
+    // ansx_topk_bool_batch_dev: the overflow word is lowered by k_topkb_check, behind the exclusion
+    // step; payof: where the payload of referenced list r stands (ANSX_TOPK_NONE: a list that is only excluded has none;
+    // null: at r + 1); form: ANSX_TOPKB_FORM_*
+    bool check = false;
+    const std::vector<u32>* payof = nullptr;
+    u32 form = 0;
 };
+
+// The payloads of a group's lists into `pay`, laid out as its ids are
+template <class Group> int topk_decode_payloads(ansx_ctx* c, int kind, int f, const BrFront& F, const Group& g, std::vector<u64>& off,
+    size_t count, const TopkOut& o, u32* pay, size_t* bad_container, hipStream_t s)
+{
+    GeometryGroups geo;
+    for (size_t i = 0; i < g.lists.size(); i++) {
+        const u32 r = o.payof ? (*o.payof)[g.lists[i]] : g.lists[i] + 1u;
+        if (r == ANSX_TOPK_NONE) continue;  // (only excluded: no payload is read)
+        off[r] = g.at[i], geo[br_geometry(F.rs[r].H)].push_back(r);
+    }
+    return batch_decode_groups(c, kind, f, F.rs, off, geo, count, pay, bad_container, s);
+}
+
+// The select of a ranked call over the candidates (ids[h], score[h]), h < min(*total, n), query j's in [hseg[j], hseg[j + 1]),
+// all on the device: the eight rounds of k_topk_hist / k_topk_pick, k_topk_gather and k_topk_sort, which writes the
+// caller's arrays.  ntiles: the tiles of n.  cur and hist are zero.  Enqueues only.
+struct TopkSelect {
+    u64* pre;
+    u32 *want, *cur, *hist;
+    u64* slots;
+};
+int topk_select(ansx_ctx* c, const u32* ids, const u32* score, const u32* hseg, size_t Q, const u64* total, u32 n, u32 ntiles,
+    const TopkSelect& T, size_t q0, const TopkOut& o, const u32* sflag, hipStream_t s)
+{
+    for (u32 r = 0; r < ANSX_TOPK_ROUNDS; r++) {
+        LAUNCH(c, "k_topk_hist", k_topk_hist, ntiles, ANSX_ISECT_NT, 0, s, ids, score, hseg, (u32)Q, total, n, r, (const u64*)T.pre, T.hist,
+            sflag);
+        LAUNCH(c, "k_topk_pick", k_topk_pick, (u32)((Q + 3) / 4), 256, 0, s, hseg, (u32)Q, o.k, r, T.pre, T.want, T.hist, sflag);
+    }
+    LAUNCH(c, "k_topk_gather", k_topk_gather, ntiles, ANSX_ISECT_NT, 0, s, ids, score, hseg, (u32)Q, total, n, o.k, (const u64*)T.pre, T.cur,
+        T.slots, sflag);
+    LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)T.slots, hseg, (u64)q0, o.k, o.pow2, o.ids, o.scores, sflag);
+    return ANSX_OK;
+}
 int topk_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g, std::vector<u64>& off, size_t count,
     const TopkOut& o, const std::function<size_t(u32)>& batch_index, size_t* bad_container, size_t* bad_query, hipStream_t s)
 {
@@ -3435,38 +3478,38 @@ int topk_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g
     GeometryGroups geo;
     for (size_t i = 0; i < g.lists.size(); i++) off[g.lists[i]] = g.at[i], geo[br_geometry(F.rs[g.lists[i]].H)].push_back(g.lists[i]);
     if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, ids, bad_container, s))) return rc;
-    if (o.pays) {  // (the payload of referenced list r stands at r + 1: the same n, any geometry)
-        geo.clear();
-        for (size_t i = 0; i < g.lists.size(); i++) {
-            const u32 r = g.lists[i] + 1u;
-            off[r] = g.at[i], geo[br_geometry(F.rs[r].H)].push_back(r);
-        }
-        if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, pay, bad_container, s))) return rc;
-    }
+    // (the payload of referenced list r stands at r + 1: the same n, any geometry)
+    if (o.pays && (rc = topk_decode_payloads(c, kind, f, F, g, off, count, o, pay, bad_container, s))) return rc;
 
     // one upload: zero flag words (k_isect_compact's four, k_union_heads' one) | the overflow word | the queries' spans |
-    // every round's pairs | their weights; behind it on the device: the bounds among the heads | prefixes | what is left
-    // to find | cursors | histograms | IsectWork
+    // every round's pairs | their weights | with exclusions (ansx_topk_bool_batch_dev) the second table; behind it on the
+    // device: the bounds among the heads | those behind the exclusion step | prefixes | what is left to find | cursors |
+    // histograms | IsectWork
     Upload U;
     const auto s_fl = U.add<u32>(8);
     const auto s_of = U.add<u32>(4);
     const auto s_seg = U.add<u32>(Q + 1);
     const auto s_p = U.add<ansx_unb_pair>(g.pairs.size());
     const auto s_w = U.add<u32>(2 * g.pairs.size());
+    const bool excl = !g.xt.empty();  // (ansx_topk_bool_batch_dev only: the group excludes something)
+    const auto s_xo = U.add<u32>(excl ? Q + 1 : 0);
+    const auto s_xt = U.add<ansx_isb_list>(g.xt.size());
     const size_t up = U.end;
     const auto s_hs = U.add<u32>(q1);  // (the host's copy: read back)
+    const auto s_xs = U.add<u32>(excl ? q1 : 0);
     const auto s_pre = U.add<u64>(Q);
     const auto s_want = U.add<u32>(Q);
     const auto s_cur = U.add<u32>(rup(Q, 4));  // (cleared with the histograms behind it)
     const auto s_hist = U.add<u32>(Q * (size_t)ANSX_TOPK_BINS);
     const size_t o_w = rup(U.end, 16);
-    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, s_hs.off + s_hs.bytes))) return rc;
+    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, s_hs.off + s_hs.bytes))) return rc;  // (what the host reads or writes)
     if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(M, false)))) return rc;
     U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
     memset(U.pin(s_fl), 0, s_fl.bytes);
     u32* hof = U.pin(s_of);
     hof[0] = ANSX_TOPK_NONE, hof[1] = hof[2] = hof[3] = 0;
     U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
+    if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
     u32* hw = U.pin(s_w);
     for (size_t i = 0; i < g.pterm.size(); i++) hw[i] = g.pterm[i] == ANSX_TOPK_NONE ? 0u : o.weights[g.pterm[i]];
     HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
@@ -3496,18 +3539,23 @@ int topk_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g
         (const u64*)W.counts, (const u64*)W.total, M, (const u64*)nullptr, hid, idx, (u64*)nullptr, zero, (const u32*)uflag);
     LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, seg, (u32)Q, (u32)M, (const u64*)W.ballots,
         (const u64*)W.counts, (const u64*)W.total, hseg);
+    // (ansx_topk_bool_batch_dev: a score that leaves 32 bits may belong to an excluded id -- the scores' word is one that
+    // nobody reads, and k_topkb_check lowers the real one over what the exclusion step leaves)
     LAUNCH(c, "k_topk_scores", k_topk_scores, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)idx, (const u32*)vb[fin], (const u32*)hseg, seg,
-        (u32)Q, (const u64*)W.total, (u32)M, score, U.dev(s_of), (const u32*)S.flag);
-    for (u32 r = 0; r < ANSX_TOPK_ROUNDS; r++) {
-        LAUNCH(c, "k_topk_hist", k_topk_hist, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)hid, (const u32*)score, (const u32*)hseg, (u32)Q,
-            (const u64*)W.total, (u32)M, r, (const u64*)U.dev(s_pre), U.dev(s_hist), (const u32*)S.flag);
-        LAUNCH(c, "k_topk_pick", k_topk_pick, (u32)((Q + 3) / 4), 256, 0, s, (const u32*)hseg, (u32)Q, k, r, U.dev(s_pre), U.dev(s_want),
-            U.dev(s_hist), (const u32*)S.flag);
+        (u32)Q, (const u64*)W.total, (u32)M, score, U.dev(s_of) + (o.check ? 1 : 0), (const u32*)S.flag);
+    if (excl) {  // ONE exclusion step over the heads, as in unb_group, and the scores moved by the same ballots: no wait
+        if ((rc = bool_exclude_step(c, W, ids, hid, (u32)M, W.total, hseg, Q, U.dev(s_xo), U.dev(s_xt), (const u32*)S.flag, kb[fin],
+                 U.dev(s_xs), zero, uflag, s)))
+            return rc;
+        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)score, (u32)M, (const u64*)W.ballots,
+            (const u64*)W.counts, (const u64*)W.total, M, (const u64*)nullptr, vb[fin], (u32*)nullptr, (u64*)nullptr, zero, (const u32*)uflag);
+        hid = kb[fin], score = vb[fin], hseg = U.dev(s_xs);
     }
-    LAUNCH(c, "k_topk_gather", k_topk_gather, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)hid, (const u32*)score, (const u32*)hseg, (u32)Q,
-        (const u64*)W.total, (u32)M, k, (const u64*)U.dev(s_pre), U.dev(s_cur), slots, (const u32*)S.flag);
-    LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)slots, (const u32*)hseg, (u64)g.q0, k, o.pow2, o.ids,
-        o.scores, (const u32*)S.flag);
+    if (o.check)
+        LAUNCH(c, "k_topkb_check", k_topkb_check, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)score, (const u32*)hseg, (u32)Q,
+            (const u64*)W.total, (u32)M, U.dev(s_of), (const u32*)S.flag);
+    const TopkSelect sel = { U.dev(s_pre), U.dev(s_want), U.dev(s_cur), U.dev(s_hist), slots };
+    if ((rc = topk_select(c, hid, score, hseg, Q, W.total, (u32)M, W.ntiles, sel, g.q0, o, (const u32*)S.flag, s))) return rc;
     u32* hflag = &c->pin->isect_sflag;
     HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(hof, U.dev(s_of), 4, hipMemcpyDeviceToHost, s));
@@ -3571,6 +3619,221 @@ int topk_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_
     std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
     for (const UnbGroup& g : groups)
         if ((rc = topk_group(c, kind, f, F, g, off, count, o, batch_index, bad_container, bad_query, s))) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ANSX_OK;
+}
+
+// ansx_topk_bool_batch_dev (ansx_topk_bool.h).  The front end of ansx_topk_batch_dev over the terms
+// followed by the excluded terms: the id containers of every referenced list and, behind each list some query names as
+// a term, its payload -- a list that is only excluded has none -- still one round trip for the headers.  Then the plan
+// of the chosen op with the excluded lists under HALF the budget: ANY runs topk_group, which adds the exclusion step and
+// k_topkb_check between k_topk_scores and the select; ALL runs topkb_group: ids and payloads decoded with the same
+// offsets, the scan, one upload of the tables with the weights beside them, k_isectb_gather, then per round
+// k_topkb_match, k_dr_scan, k_isect_compact for the ids and again for the scores, k_isectb_bounds -- at least one round,
+// which seeds the scores and drops a driver's repeats -- the exclusion step where the group excludes something,
+// k_topkb_check and the select.
+// Workspace (ALL): 4 (8 with payloads) bytes per int of the group's lists, 16 per int of its drivers (two candidate and
+// two score buffers), a pass's, the scan's, IsectWork over the candidates, and per query 8 k bytes of slots, 1 KiB of
+// histogram, 60 bytes of tables, state and bounds, 20 per non-driver term and 16 per excluded term.
+// Host waits (ALL): one for the headers; per group those of its decode passes (ids, then payloads), ONE for the scan's
+// flag word, ONE per round, which brings the members' count, and ONE behind the sort, which brings the overflow word and
+// the bounds; one per call at the end.  The exclusion step adds none: its count stays on the device, and the select's
+// grids cover the last count the host has seen.
+int topkb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& g, std::vector<u64>& off, size_t count,
+    const TopkOut& o, const std::function<size_t(u32)>& batch_index, size_t* bad_container, size_t* bad_query, hipStream_t s)
+{
+    int rc;
+    const size_t Q = g.q1 - g.q0, q1 = rup(Q + 1, 4);
+    const u64 L = g.at.back(), nc0 = g.G[Q].dst;
+    const u32 k = o.k;
+    const auto nothing = [&]() -> int {  // no query has a result: every slot is ANSX_NO_ID / 0
+        LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)nullptr, (const u32*)nullptr, (u64)g.q0, k, o.pow2,
+            o.ids, o.scores, (const u32*)nullptr);
+        if (o.counts) memset(o.counts + g.q0, 0, 4 * Q);
+        return ANSX_OK;
+    };
+    if (nc0 == 0) return nothing();  // (every driver is empty: nothing is decoded)
+    // the lists | their payloads | two candidate and two score buffers | the slots (u64: at an even int); each with the
+    // decoders' slack behind
+    const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)nc0, 4) + 16;
+    const size_t o_m = (o.pays ? 2 : 1) * o_c, o_s = o_m + 4 * half;
+    if ((rc = ensure(c, c->isectb_ids, 4 * o_s + 8 * Q * (size_t)k))) return rc;
+    u32* ids = (u32*)c->isectb_ids.p;
+    u32* pay = o.pays ? ids + o_c : nullptr;
+    u32* buf[2] = { ids + o_m, ids + o_m + half };
+    u32* sb[2] = { ids + o_m + 2 * half, ids + o_m + 3 * half };
+    u64* slots = (u64*)(ids + o_s);
+    GeometryGroups geo;
+    for (size_t i = 0; i < g.lists.size(); i++) off[g.lists[i]] = g.at[i], geo[br_geometry(F.rs[g.lists[i]].H)].push_back(g.lists[i]);
+    if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, ids, bad_container, s))) return rc;
+    if (o.pays && (rc = topk_decode_payloads(c, kind, f, F, g, off, count, o, pay, bad_container, s))) return rc;
+
+    // one upload: zero flag words | the overflow word | queries | their drivers' weights | round table | its weights | with
+    // exclusions the second table; behind it on the device: two arrays of segments | prefixes | what is left to find |
+    // cursors | histograms | IsectWork
+    Upload U;
+    const auto s_fl = U.add<u32>(4);
+    const auto s_of = U.add<u32>(4);
+    const auto s_g = U.add<ansx_isb_query>(Q + 1);
+    const auto s_wd = U.add<u32>(Q);
+    const auto s_ro = U.add<u32>(Q + 1);
+    const auto s_rt = U.add<ansx_isb_list>(g.rt.size());
+    const auto s_rw = U.add<u32>(g.rt.size());
+    const bool excl = !g.xt.empty();
+    const auto s_xo = U.add<u32>(excl ? Q + 1 : 0);
+    const auto s_xt = U.add<ansx_isb_list>(g.xt.size());
+    const size_t up = U.end;
+    const auto s_seg = U.add<u32>(2 * q1);  // (the host's copy: the last step's, read back)
+    const auto s_pre = U.add<u64>(Q);
+    const auto s_want = U.add<u32>(Q);
+    const auto s_cur = U.add<u32>(rup(Q, 4));  // (cleared with the histograms behind it)
+    const auto s_hist = U.add<u32>(Q * (size_t)ANSX_TOPK_BINS);
+    const size_t o_w = rup(U.end, 16);
+    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, s_seg.off + s_seg.bytes))) return rc;  // (what the host reads or writes)
+    if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(nc0, false)))) return rc;
+    U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
+    memset(U.pin(s_fl), 0, s_fl.bytes);
+    u32* hof = U.pin(s_of);
+    hof[0] = ANSX_TOPK_NONE, hof[1] = hof[2] = hof[3] = 0;
+    U.put(s_g, g.G.data()), U.put(s_ro, g.rt_off.data());
+    if (!g.rt.empty()) U.put(s_rt, g.rt.data());
+    for (size_t j = 0; j < Q; j++) U.pin(s_wd)[j] = o.weights[g.dterm[j]];
+    for (size_t e = 0; e < g.rterm.size(); e++) U.pin(s_rw)[e] = o.weights[g.rterm[e]];
+    if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
+    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(U.dev(s_cur), 0, s_hist.off + s_hist.bytes - s_cur.off, s));
+    u32* seg[2] = { U.dev(s_seg), U.dev(s_seg) + q1 };
+    const u32* zero = U.dev(s_fl);
+
+    SumsPlan S;
+    if ((rc = sums_prepare(c, (uintptr_t)ids, L, g.at.data(), g.lists.size(), s, &S))) return rc;
+    if ((rc = sums_launch(c, ids, L, g.lists.size(), S, s))) return rc;
+    LAUNCH(c, "k_isectb_gather", k_isectb_gather, (u32)((std::max<u64>(nc0, Q + 1) + ANSX_ISECT_TILE - 1) / ANSX_ISECT_TILE),
+        ANSX_ISECT_NT, 0, s, (const u32*)ids, (const ansx_isb_query*)U.dev(s_g), (u32)Q, buf[0], (u32)nc0, seg[0], (const u32*)S.flag);
+    u32* hflag = &c->pin->isect_sflag;
+    HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (*hflag != ANSX_SS_NONE) {  // the first list of the buffer whose sum left 32 bits
+        if (bad_container && *hflag < g.lists.size()) *bad_container = batch_index(g.lists[*hflag]);
+        return ANSX_ERR_DOMAIN;
+    }
+
+    // (at least one round: the first seeds the scores and drops the repeats of a driver, whatever the queries' terms)
+    const u32 rounds = std::max<u32>(g.rounds, 1u);
+    u32 nc = (u32)nc0, cur = 0;
+    for (u32 r = 0; r < rounds && nc > 0; r++) {
+        const IsectWork W(U.devp + o_w, nc, false);
+        LAUNCH(c, "k_topkb_match", k_topkb_match, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)pay, (const u32*)buf[cur],
+            sb[cur], nc, (const u32*)seg[cur], (u32)Q, (const ansx_isb_query*)U.dev(s_g), (const u32*)U.dev(s_wd),
+            (const u32*)U.dev(s_ro), (const ansx_isb_list*)U.dev(s_rt), (const u32*)U.dev(s_rw), r, o.form, W.ballots, W.counts);
+        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
+        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)buf[cur], nc, (const u64*)W.ballots,
+            (const u64*)W.counts, (const u64*)W.total, (u64)nc, (const u64*)nullptr, buf[1 - cur], (u32*)nullptr, (u64*)nullptr, zero, zero);
+        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)sb[cur], nc, (const u64*)W.ballots,
+            (const u64*)W.counts, (const u64*)W.total, (u64)nc, (const u64*)nullptr, sb[1 - cur], (u32*)nullptr, (u64*)nullptr, zero, zero);
+        LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, (const u32*)seg[cur], (u32)Q, nc,
+            (const u64*)W.ballots, (const u64*)W.counts, (const u64*)W.total, seg[1 - cur]);
+        HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        nc = (u32)c->pin->isect_total, cur = 1 - cur;
+    }
+    if (nc == 0) return nothing();  // (a round left nothing: no id is in all lists of any query)
+    const IsectWork W(U.devp + o_w, nc, false);  // (total: the last round's, nc, at the same place)
+    if (excl) {  // ONE exclusion step over what the rounds left, the scores moved by the same ballots: no wait
+        if ((rc = bool_exclude_step(c, W, ids, buf[cur], nc, nullptr, seg[cur], Q, U.dev(s_xo), U.dev(s_xt), (const u32*)S.flag,
+                 buf[1 - cur], seg[1 - cur], zero, zero, s)))
+            return rc;
+        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)sb[cur], nc, (const u64*)W.ballots,
+            (const u64*)W.counts, (const u64*)W.total, (u64)nc, (const u64*)nullptr, sb[1 - cur], (u32*)nullptr, (u64*)nullptr, zero, zero);
+        cur = 1 - cur;
+    }
+    LAUNCH(c, "k_topkb_check", k_topkb_check, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)sb[cur], (const u32*)seg[cur], (u32)Q,
+        (const u64*)W.total, nc, U.dev(s_of), (const u32*)S.flag);
+    const TopkSelect sel = { U.dev(s_pre), U.dev(s_want), U.dev(s_cur), U.dev(s_hist), slots };
+    if ((rc = topk_select(c, buf[cur], sb[cur], seg[cur], Q, W.total, nc, W.ntiles, sel, g.q0, o, (const u32*)S.flag, s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(hof, U.dev(s_of), 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(U.pin(s_seg), seg[cur], 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (hof[0] != ANSX_TOPK_NONE) {  // the first query of the group with a score of 2^32 - 1 or more among its results
+        if (bad_query) *bad_query = g.q0 + hof[0];
+        return ANSX_ERR_DOMAIN;
+    }
+    const u32* hs = U.pin(s_seg);
+    if (o.counts)
+        for (size_t j = 0; j < Q; j++) o.counts[g.q0 + j] = std::min<u32>(k, hs[j + 1] - hs[j]);
+    return ANSX_OK;
+}
+
+int topk_bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
+    const size_t* pay_bytes, size_t count, int op, const u32* terms, const u32* weights, const u64* qoff, const u32* xterms,
+    const u64* xqoff, size_t nq, u32 k, u32* d_out_ids, u32* d_out_scores, u32* out_counts, size_t* bad_container, size_t* bad_query,
+    hipStream_t s)
+{
+    int rc;
+    const size_t nt = (size_t)qoff[nq], nx = xqoff ? (size_t)xqoff[nq] : 0;
+    std::vector<u32> named(terms, terms + nt);
+    if (nx) named.insert(named.end(), xterms, xterms + nx);
+    BrFront F;
+    std::vector<u32> uniq, owner, payof, rid;  // (with payloads: the referenced lists, ascending; the list behind every entry)
+    if (d_pays) {
+        std::vector<u32> urid, all;
+        br_refs(named.data(), named.size(), count, &uniq, &urid);
+        std::vector<char> term(uniq.size(), 0);
+        for (size_t j = 0; j < nt; j++) term[urid[j]] = 1;
+        std::vector<u32> idpos(uniq.size());
+        std::vector<const u8*> ptr;
+        std::vector<size_t> len;
+        for (size_t u = 0; u < uniq.size(); u++) {  // list u's id container, then its payload where it is a term
+            idpos[u] = (u32)ptr.size();
+            ptr.push_back(d_ins[uniq[u]]), len.push_back(in_bytes[uniq[u]]), owner.push_back((u32)u), all.push_back(idpos[u]);
+            payof.push_back(term[u] ? idpos[u] + 1u : ANSX_TOPK_NONE);
+            if (!term[u]) continue;
+            ptr.push_back(d_pays[uniq[u]]), len.push_back(pay_bytes[uniq[u]]), owner.push_back((u32)u), all.push_back(idpos[u] + 1u);
+            payof.push_back(ANSX_TOPK_NONE);
+        }
+        size_t bad = ptr.size();
+        rc = batch_ranges_front(c, kind, f, ptr.data(), len.data(), ptr.size(), all.data(), all.size(), nullptr, &F, &bad, s);
+        if (rc && rc != ANSX_ERR_FORMAT) return rc;
+        // the smallest referenced list whose headers fail the checks (bad: every entry in front of it passed) or differ in n
+        for (size_t e = 0; e + 1 < bad; e++)
+            if (payof[e] != ANSX_TOPK_NONE && F.rs[e].H.n != F.rs[e + 1].H.n) {
+                bad = e, rc = ANSX_ERR_FORMAT;
+                break;
+            }
+        if (rc) {
+            if (bad_container) *bad_container = uniq[owner[bad]];
+            return rc;
+        }
+        rid.resize(named.size());
+        for (size_t j = 0; j < named.size(); j++) rid[j] = idpos[urid[j]];
+    } else {
+        if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, named.data(), named.size(), nullptr, &F, bad_container, s)))
+            return rc;
+        rid = F.rid;
+    }
+    const std::function<size_t(u32)> batch_index = [&](u32 r) -> size_t { return d_pays ? uniq[owner[r]] : F.ref[r]; };
+    std::vector<u64> n(F.ref.size());
+    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
+    const u32* xrid = rid.data() + nt;
+    const u64 budget = (c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT) / 2;
+    u32 pow2 = 1;
+    while (pow2 < k) pow2 <<= 1;
+    TopkOut o = { weights, k, pow2, d_out_ids, d_out_scores, out_counts, d_pays != nullptr };
+    o.check = true, o.payof = d_pays ? &payof : nullptr;
+    o.form = c->dbg.topk_bool_form == 1 ? ANSX_TOPKB_FORM_SEARCH : ANSX_TOPKB_FORM_DEFAULT;
+    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
+    if (op == ANSX_BOOL_ALL) {
+        std::vector<IsbGroup> groups;
+        if ((rc = isb_plan(n.data(), n.size(), rid.data(), qoff, nq, budget, &groups, bad_query, xrid, xqoff, true))) return rc;
+        for (const IsbGroup& g : groups)
+            if ((rc = topkb_group(c, kind, f, F, g, off, count, o, batch_index, bad_container, bad_query, s))) return rc;
+    } else {
+        std::vector<UnbGroup> groups;
+        if ((rc = unb_plan(n.data(), n.size(), rid.data(), qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query, xrid, xqoff, true)))
+            return rc;
+        for (const UnbGroup& g : groups)
+            if ((rc = topk_group(c, kind, f, F, g, off, count, o, batch_index, bad_container, bad_query, s))) return rc;
+    }
     HIPCHK(c, hipStreamSynchronize(s));
     return ANSX_OK;
 }
@@ -3915,6 +4178,11 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         if (w < 0) return ANSX_ERR_ARG;
         c->dbg.bool_form = w;
     }
+    else if (!strcmp(name, "ANSX_TOPK_BOOL_FORM")) {
+        const int w = debug_word(value, "search", "bounded");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.topk_bool_form = w;
+    }
     else if (!strcmp(name, "ANSX_DECODE_PAIR_LDS")) c->dbg.pair_lds_limit = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_FORGET_HINTS")) {  // the next call of every geometry is a first call again (bench.py: first_call_ms)
         c->ns_hint.clear();
@@ -4231,13 +4499,12 @@ int ansx_bool_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_in
     });
 }
 
-int ansx_topk_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
-    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
-    const uint64_t* qoff, size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts,
-    size_t* bad_container, size_t* bad_query, void* stream)
+// ... what the ranked calls check: queries_args and the weights, k, the outputs and the payloads of the named lists
+static int topk_args(const ansx_ctx* c, const uint8_t* const* d_ins, const size_t* in_bytes, const uint8_t* const* d_pays,
+    const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights, const uint64_t* qoff, size_t nqueries,
+    uint32_t k, const uint32_t* d_out_ids, const uint32_t* d_out_scores, size_t* bad_container, size_t* bad_query)
 {
-    // (every argument check comes before the context is touched)
-    uint64_t offs_stand_in = 0;  // (the parents' out_offsets: this call has none)
+    uint64_t offs_stand_in = 0;  // (the parents' out_offsets: these calls have none)
     if (queries_args(c, d_ins, in_bytes, count, terms, qoff, nqueries, d_out_ids, nullptr, 0, &offs_stand_in, bad_container, bad_query))
         return ANSX_ERR_ARG;
     if (nqueries > 0 && !weights) return ANSX_ERR_ARG;
@@ -4253,10 +4520,39 @@ int ansx_topk_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_in
                     return ANSX_ERR_ARG;
                 }
     }
+    return ANSX_OK;
+}
+
+int ansx_topk_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint64_t* qoff, size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts,
+    size_t* bad_container, size_t* bad_query, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (topk_args(c, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, qoff, nqueries, k, d_out_ids, d_out_scores, bad_container,
+            bad_query))
+        return ANSX_ERR_ARG;
     if (nqueries == 0) return ANSX_OK;
     return run_call(c, stream, [&](hipStream_t s) {
         return topk_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, (const u64*)qoff, nqueries, k, d_out_ids,
             d_out_scores, out_counts, bad_container, bad_query, s);
+    });
+}
+
+int ansx_topk_bool_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, int op, const uint32_t* terms, const uint32_t* weights,
+    const uint64_t* qoff, const uint32_t* xterms, const uint64_t* xqoff, size_t nqueries, uint32_t k, uint32_t* d_out_ids,
+    uint32_t* d_out_scores, uint32_t* out_counts, size_t* bad_container, size_t* bad_query, void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (topk_args(c, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, qoff, nqueries, k, d_out_ids, d_out_scores, bad_container,
+            bad_query))
+        return ANSX_ERR_ARG;
+    if (bool_args(d_ins, count, op, xterms, xqoff, nqueries, bad_container, bad_query)) return ANSX_ERR_ARG;
+    if (nqueries == 0) return ANSX_OK;
+    return run_call(c, stream, [&](hipStream_t s) {
+        return topk_bool_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, op, terms, weights, (const u64*)qoff, xterms,
+            (const u64*)xqoff, nqueries, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
     });
 }
 

@@ -484,6 +484,8 @@ struct IsbGroup {
     std::vector<u32> xt_off;         // with exclusions (plan_excl_tables): q1 - q0 + 1
     std::vector<ansx_isb_list> xt;   // ... every query's excluded lists
     std::vector<u32> xt_list;        // ... the referenced list behind every entry of xt
+    std::vector<u32> dterm, rterm;   // with want_terms (ansx_topk_bool_batch_dev): the named term (its place in rid) behind
+                                     // every query's driver and behind every entry of rt -- a ranked query lays its weights there
     u64 ints;                        // buffer + twice the candidates: what the budget bounds
     u32 rounds;                      // most rounds of a query
 };
@@ -492,8 +494,10 @@ struct IsbGroup {
 // 2^32 - 1 candidates).  A group ends in front of the query that would take it over `budget` ints or its candidates to
 // 2^32; a query over the budget alone is a group of its own.  A list two groups name is decoded in both.
 // xrid / xqoff: null, or the lists every query excludes (plan_excl_tables).
+// want_terms: dterm and rterm are filled beside drv and rt; nothing else differs.
 static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64* qoff, size_t nq, u64 budget,
-    std::vector<IsbGroup>* groups, size_t* bad_query, const u32* xrid = nullptr, const u64* xqoff = nullptr)
+    std::vector<IsbGroup>* groups, size_t* bad_query, const u32* xrid = nullptr, const u64* xqoff = nullptr,
+    bool want_terms = false)
 {
     groups->clear();
     std::vector<u32> stamp(nref, 0xFFFFFFFFu), slot(nref, 0), fresh, ord;
@@ -540,6 +544,7 @@ static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64*
             std::stable_sort(ord.begin(), ord.end(), [&](u32 x, u32 y) { return n[t[x]] < n[t[y]]; });
             const u32 d = t[ord[0]];
             g.drv[j] = d;
+            if (want_terms) g.dterm.push_back((u32)(qoff[g.q0 + j] + ord[0]));
             g.G[j] = { n[d] ? g.at[slot[d]] : 0, dst };
             dst += n[d];
             g.rt_off[j] = (u32)g.rt.size();
@@ -547,6 +552,7 @@ static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64*
                 const u32 r = t[ord[k]];
                 g.rt.push_back({ n[r] ? g.at[slot[r]] : 0, n[r] });
                 g.rt_list.push_back(r);
+                if (want_terms) g.rterm.push_back((u32)(qoff[g.q0 + j] + ord[k]));
             }
             g.rounds = std::max(g.rounds, (u32)(m - 1));
         }

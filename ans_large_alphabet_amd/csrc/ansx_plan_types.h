@@ -160,6 +160,14 @@ ANSX_PLAN_FN u32 topk_sat32(u32 w, u32 p)
     return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)v;
 }
 
+// a + b, saturated: with u32 terms the result is 0xFFFFFFFF exactly when the 64-bit sum of all of them reaches 2^32 - 1
+// (ansx_topk_bool_batch_dev, ansx_topk_bool.h, and tests/tools/topk_bool_plan_check.cpp)
+ANSX_PLAN_FN u32 topk_sat_add(u32 a, u32 b)
+{
+    const u64 v = (u64)a + b;
+    return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)v;
+}
+
 // The key of an id inside its query: larger = ranked earlier (score descending, id ascending); distinct ids, distinct keys.
 ANSX_PLAN_FN u64 topk_key(u32 score, u32 id) { return ((u64)score << 32) | (u32)~id; }
 ANSX_PLAN_FN u32 topk_key_id(u64 key) { return ~(u32)key; }

@@ -762,13 +762,51 @@ int ansx_bool_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* co
  * Unreferenced containers and payloads are not examined and may be NULL.  No trace is left in the context, which stays
  * usable after any error.  Groups, workspace and host waits: DESIGN.md section 3m -- the union's groups under half of
  * ANSX_ISECT_BATCH_INTS; one wait for the headers, per group its decode passes' and ONE behind the sort, one per call.
- * Out of scope: exclusion behind a ranked query, floating-point scores, k above 1024, dynamic pruning (WAND / MaxScore),
- * a ranked AND. */
+ * Out of scope: floating-point scores, k above 1024, dynamic pruning (WAND / MaxScore).  Exclusion behind a ranked query
+ * and a ranked AND: ansx_topk_bool_batch_dev, below. */
 #define ANSX_TOPK_MAX_K 1024u
 int ansx_topk_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
     const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
     const uint64_t* qoff, size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts,
     size_t* bad_container, size_t* bad_query, void* stream);
+
+/* ansx_topk_bool_batch_dev: ranked Boolean queries -- `+a +b` by score, anything ranked with NOT deleted behind it -- in
+ * one call (csrc/ansx_topk_bool.h).  op is ANSX_BOOL_ALL or ANSX_BOOL_ANY; xterms / xqoff are
+ * ansx_bool_batch_dev's (xqoff == NULL: nothing is excluded; non-decreasing; a query may exclude nothing); every other
+ * argument is ansx_topk_batch_dev's.
+ * The result set R(q) of query q is a set of DISTINCT ids: under ANY the ids that occur in at least one list named in its
+ * terms, under ALL the ids that occur in every one of them; in both cases less every id that occurs in at least one of
+ * its excluded lists.  score(d) is ansx_topk_batch_dev's formula unchanged -- the sum over the query's terms j, t =
+ * terms[j], and over all i with s_t[i] == d of sat32(weights[j] * p_t[i]): a list named twice contributes twice, and a
+ * list's own repeated ids each contribute, under ALL the driver's too, while the id appears once.  The output is
+ * ansx_topk_batch_dev's image: R(q) ordered by (score descending, id ascending), cut to k, at stride k, ANSX_NO_ID / 0
+ * behind the results, out_counts[q] = min(k, |R(q)|); 0xFFFFFFFF is an id like any other.  With op == ANSX_BOOL_ANY and
+ * no exclusions every output equals ansx_topk_batch_dev's.
+ * A score of 2^32 - 1 or more OF AN ID OF R(q) is ANSX_ERR_DOMAIN with *bad_query = the first such query in batch order.
+ * An excluded id, and under ALL an id that a later list lacks, is no error whatever its partial sum.
+ * A list that is only excluded needs no payload: its d_pays[t] is not examined and may be NULL.  Unreferenced containers
+ * and payloads are not examined either.  A list may be both a term and excluded (ALL: an empty result; ANY: its ids
+ * vanish).
+ * Errors, in this order: before the context is touched, ANSX_ERR_ARG for ansx_topk_batch_dev's checks, for an op outside
+ * the two values, and for ansx_bool_batch_dev's checks on xterms / xqoff with the same *bad_query / *bad_container.
+ * nqueries == 0: ANSX_OK, nothing is launched.  Then ANSX_ERR_FORMAT with *bad_container = the smallest referenced batch
+ * index whose id header fails decode_dev's checks or -- for a term's list -- whose payload header fails them or whose
+ * payload's n differs, the id header before the payload;
+ *   ANSX_ERR_ARG with *bad_query for the chosen plan's limits (ALL: ansx_intersect_batch_dev's; ANY: the union's);
+ *   found on the device, as in the parents: ANSX_ERR_FORMAT with *bad_container = count; ANSX_ERR_DOMAIN with
+ *   *bad_container = a referenced list, an excluded one included, whose id sum leaves 32 bits, or with *bad_query for a
+ *   score (above).
+ * No trace is left in the context, which stays usable after any error.  Groups: the chosen parent's, with the excluded
+ * lists, under half of ANSX_ISECT_BATCH_INTS.  Host waits: one for the headers; per group its decode passes'; ALL: one
+ * for the scan's flag word, one per round of its longest query (at least one round) and ONE behind the sort; ANY: ONE
+ * behind the sort; one per call.  The exclusion step adds none.
+ * Out of scope: floating-point or BM25 scores, k above 1024, dynamic pruning (WAND / MaxScore), a minimum-should-match
+ * threshold, nested expressions. */
+int ansx_topk_bool_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, int op, const uint32_t* terms,
+    const uint32_t* weights, const uint64_t* qoff, const uint32_t* xterms, const uint64_t* xqoff, size_t nqueries,
+    uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts, size_t* bad_container,
+    size_t* bad_query, void* stream);
 
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
