@@ -36,6 +36,7 @@ EXPORTS = [
     "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
     "ansx_intersect_ids_dev", "ansx_intersect_dev", "ansx_intersect_batch_dev", "ansx_union_batch_dev", "ansx_union_dev",
     "ansx_bool_batch_dev", "ansx_last_encode_form", "ansx_topk_batch_dev", "ansx_topk_bool_batch_dev",
+    "ansx_decode_batch_device_ranges_dev", "ansx_decode_batch_device_ranges_sums_dev",
 ]
 
 
@@ -192,6 +193,13 @@ def lib():
     L.ansx_decode_batch_ranges_sums_dev.restype = C.c_int
     L.ansx_decode_batch_ranges_sums_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp,
                                                     C.POINTER(C.c_uint64), C.POINTER(sz), C.POINTER(sz), vp]
+    # ... with src / first / cnt in device memory: d_offsets is a device pointer too
+    L.ansx_decode_batch_device_ranges_dev.restype = C.c_int
+    L.ansx_decode_batch_device_ranges_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp,
+                                                      C.POINTER(C.c_uint64), C.POINTER(sz), C.POINTER(sz), vp]
+    L.ansx_decode_batch_device_ranges_sums_dev.restype = C.c_int
+    L.ansx_decode_batch_device_ranges_sums_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, sz,
+                                                           vp, C.POINTER(C.c_uint64), C.POINTER(sz), C.POINTER(sz), vp]
     L.ansx_next_geq_batch_dev.restype = C.c_int
     L.ansx_next_geq_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, sz, vp, vp,
                                           C.POINTER(C.c_uint64), C.POINTER(sz), C.POINTER(sz), vp]

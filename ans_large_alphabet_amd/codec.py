@@ -538,6 +538,57 @@ class _Codec:
             raise err
         return offsets
 
+    def decode_batch_device_ranges_dev(self, in_ptrs, in_bytes, src_ptr, first_ptr, count_ptr, nranges, out_ptr, out_capacity,
+                                       offsets_ptr=None, stream=None):
+        """decode_batch_ranges_dev with the ranges in device memory and the plan built on the device: src_ptr ->
+        nranges uint32 container numbers, first_ptr -> nranges uint64 firsts, count_ptr -> nranges uint32 counts, all
+        device pointers read on `stream`.  in_ptrs / in_bytes are host sequences as in decode_batch_dev (a container no
+        range names may be 0).  Writes the ranges back to back to out_ptr (out_capacity ints) and, if offsets_ptr (a
+        device pointer) is given, the nranges + 1 exclusive prefix sums of count there.  Returns sum(count);
+        out_ptr=None with out_capacity=0 is a size query.  An AnsxError carries .bad_container / .bad_range where the
+        call set them (None otherwise); ERR_CAPACITY also .needed = sum(count)."""
+        return self._batch_device_ranges("decode_batch_device_ranges_dev", in_ptrs, in_bytes, None, None, src_ptr, first_ptr,
+                                         count_ptr, nranges, out_ptr, out_capacity, offsets_ptr, stream)
+
+    def decode_batch_device_ranges_sums_dev(self, in_ptrs, in_bytes, bases_ptrs, nbases, src_ptr, first_ptr, count_ptr, nranges,
+                                            out_ptr, out_capacity, offsets_ptr=None, stream=None):
+        """decode_batch_device_ranges_dev returning docids, as decode_batch_ranges_sums_dev does: bases_ptrs / nbases
+        are host sequences as long as in_ptrs (those of a container no range names are not looked at)."""
+        return self._batch_device_ranges("decode_batch_device_ranges_sums_dev", in_ptrs, in_bytes, bases_ptrs, nbases, src_ptr,
+                                         first_ptr, count_ptr, nranges, out_ptr, out_capacity, offsets_ptr, stream)
+
+    def _batch_device_ranges(self, what, in_ptrs, in_bytes, bases_ptrs, nbases, src_ptr, first_ptr, count_ptr, nranges, out_ptr,
+                             out_capacity, offsets_ptr, stream):
+        for name, v in (("nranges", nranges), ("out_capacity", out_capacity)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(in_bytes, dtype=np.uint64).reshape(-1)
+        if ptrs.size != sizes.size:
+            raise ValueError("in_ptrs and in_bytes differ in length (%d, %d)" % (ptrs.size, sizes.size))
+        nc = ptrs.size
+        head = [self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None]
+        if bases_ptrs is not None:
+            bptrs, nb = self._batch_bases(ptrs, bases_ptrs, nbases)
+            # (the arrays themselves must not be null, even for an empty batch)
+            head += [bptrs.ctypes.data if nc else np.zeros(1, np.uint64).ctypes.data,
+                     nb.ctypes.data if nc else np.zeros(1, np.uint64).ctypes.data]
+        total = C.c_uint64(0)
+        unset = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+        bad_c, bad_r = C.c_size_t(unset), C.c_size_t(unset)
+        st = getattr(L.lib(), "ansx_" + what)(*head, nc, src_ptr, first_ptr, count_ptr, int(nranges), out_ptr, int(out_capacity),
+                                              offsets_ptr, C.byref(total), C.byref(bad_c), C.byref(bad_r), stream)
+        if st == L.ERR_CAPACITY and out_ptr is None and int(out_capacity) == 0:
+            return int(total.value)
+        if st != L.OK:
+            err = L.AnsxError(st, self.name() + "." + what)
+            err.bad_container = err.container = int(bad_c.value) if bad_c.value != unset else None
+            err.bad_range = err.range = int(bad_r.value) if bad_r.value != unset else None
+            if st == L.ERR_CAPACITY:
+                err.needed = int(total.value)
+            raise err
+        return int(total.value)
+
     def next_geq_batch_dev(self, in_ptrs, in_bytes, bases_ptrs, nbases, src, targets_ptr, pos_ptr, ids_ptr, stream=None):
         """next_geq_dev over a batch: target i, the uint32 at targets_ptr + 4 i (device), is looked up in the list of
         container src[i] (host array; its length is the number of targets) of the batch in_ptrs / in_bytes /

@@ -42,6 +42,7 @@
 #include "ansx_topk_bool.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
+#include "ansx_batchdevranges.h"
 #include "ansx_plan.h"  // the host's plans of the random-access calls, Layout, BatchSrc, rup
 #include "ansx_decode_form.h"  // the form of a decode call: parser, decoder, launch shapes
 #include "ansx_encode_form.h"  // the forms of an encode attempt: model, remap, prelude writer, encoder
@@ -2563,6 +2564,256 @@ int decode_batch_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, co
     });
 }
 
+// ansx_decode_batch_device_ranges_dev ("device plan"; ansx_batchdevranges.h): src / first / cnt
+// are device arrays, and nothing here is O(nranges).  Three waits before the passes: the front's scalars (how many
+// containers are referenced), their headers, and the planner's scalars with every pass's.
+//   front  the addresses and sizes of all `count` containers go up unjudged; k_bdr_mark, k_bdr_slots
+//   host   batch_headers' checks on the referenced containers; the geometry groups; per referenced container its
+//          ansx_bdr_ref, ansx_batch_src and (the sums) ansx_brs_src, in the order of the global blocks: one upload
+//   plan   section 3a's planner over the global blocks, then the pass scalars
+//   pass   k_bdr_pass_table and the pieces on the device in pass_build's place, then the pass of the host-array call
+int decode_batch_device_ranges(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count,
+    const u32* d_src, const u64* d_first, const u32* d_cnt, size_t nranges, u32* d_out, size_t cap, u64* d_offsets,
+    u64* total_ints, size_t* bad_container, size_t* bad_range, const u32* const* d_bases, const size_t* nbases, hipStream_t s)
+{
+    int rc;
+    const bool sums = d_bases != nullptr;
+    const u64 nr = nranges, nt = (nr + ANSX_DR_TILE - 1) / ANSX_DR_TILE;
+    const u32 g_nr = (u32)((nr + ANSX_DR_NT - 1) / ANSX_DR_NT);
+
+    // ---- front: scalars | addresses | sizes | bases | marks go up; slots, the referenced list and its addresses stay
+    const size_t mref = (size_t)std::min<u64>(count, nr);
+    Upload F;
+    const auto f_sc = F.add<u64>(ANSX_BDR_F_SCALARS);
+    const auto f_addr = F.add<u64>(count);
+    const auto f_inb = F.add<u64>(count);
+    const auto f_bas = F.add<u64>(sums ? count : 0);
+    const auto f_mark = F.add<u32>(count);
+    const size_t f_up = F.end;
+    const auto f_slot = F.add<u32>(count);
+    const auto f_ref = F.add<u32>(mref);
+    const auto f_ra = F.add<u64>(mref);
+    if ((rc = ensure_pin(c, f_up)) || (rc = ensure(c, c->bat_hdr, F.end))) return rc;
+    F.host = c->rng_pin, F.devp = (u8*)c->bat_hdr.p;
+    memset(F.pin(f_sc), 0, f_sc.bytes);
+    F.pin(f_sc)[ANSX_BDR_F_BADSRC] = F.pin(f_sc)[ANSX_BDR_F_BADPTR] = ~0ull;
+    memcpy(F.pin(f_addr), d_ins, 8 * count);  // (unjudged: a container no range names may be null)
+    memcpy(F.pin(f_inb), in_bytes, 8 * count);
+    if (sums) memcpy(F.pin(f_bas), d_bases, 8 * count);
+    memset(F.pin(f_mark), 0, f_mark.bytes);
+    HIPCHK(c, hipMemcpyAsync(F.devp, F.host, f_up, hipMemcpyHostToDevice, s));
+    LAUNCH(c, "k_bdr_mark", k_bdr_mark, g_nr, ANSX_DR_NT, 0, s, d_src, nr, (u32)count, (const u64*)F.dev(f_addr),
+        (const u64*)(sums ? F.dev(f_bas) : nullptr), F.dev(f_mark), F.dev(f_sc));
+    LAUNCH(c, "k_bdr_slots", k_bdr_slots, 1, ANSX_DR_NT, 0, s, (const u32*)F.dev(f_mark), (u32)count, (const u64*)F.dev(f_addr),
+        (const u64*)F.dev(f_inb), F.dev(f_slot), F.dev(f_ref), F.dev(f_ra), F.dev(f_sc));
+    u64* hs = c->pin->planner;
+    HIPCHK(c, hipMemcpyAsync(hs, F.dev(f_sc), 64, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (hs[ANSX_BDR_F_BADSRC] != ~0ull || hs[ANSX_BDR_F_BADPTR] != ~0ull) {
+        if (bad_range) *bad_range = (size_t)(hs[ANSX_BDR_F_BADSRC] != ~0ull ? hs[ANSX_BDR_F_BADSRC] : hs[ANSX_BDR_F_BADPTR]);
+        return ANSX_ERR_ARG;
+    }
+    const size_t nref = (size_t)hs[ANSX_BDR_F_NREF];
+    if (nref == 0 || nref > mref) return ANSX_ERR_HIP;  // (cannot happen: a front fault)
+
+    // ---- the referenced containers' headers, and which they are
+    std::vector<u32> ref(nref);
+    std::vector<BatchSrc> rs(nref);
+    {
+        Upload U;
+        const auto s_ref = U.add<u32>(nref);
+        const auto s_hdr = U.add<uint4>(4 * nref);
+        if ((rc = upload_room(c, U, c->rng_plan))) return rc;
+        LAUNCH(c, "k_batch_headers", k_batch_headers, (u32)((4 * (u64)nref + 255) / 256), 256, 0, s, (const u64*)F.dev(f_ra), (u64)nref,
+            U.dev(s_hdr));
+        HIPCHK(c, hipMemcpyAsync(U.pin(s_hdr), U.dev(s_hdr), s_hdr.bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(U.pin(s_ref), F.dev(f_ref), s_ref.bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        memcpy(ref.data(), U.pin(s_ref), s_ref.bytes);
+        for (size_t j = 0; j < nref; j++) {  // batch_headers' checks, in batch order
+            const size_t i = ref[j];
+            BatchSrc& b = rs[j];
+            Plan P;
+            if (i >= count) return ANSX_ERR_HIP;
+            if (in_bytes[i] < sizeof(ansx_container_header) || parse_header((const u8*)U.pin(s_hdr) + 64 * j, in_bytes[i], &b.H)
+                || container_plan(b.H, (u32)kind, (u32)f, in_bytes[i], &P) || P.g.nblocks == 0) {
+                if (bad_container) *bad_container = i;
+                return ANSX_ERR_FORMAT;
+            }
+            b.lay = P.lay, b.base = (u64)(uintptr_t)d_ins[i], b.nblocks = P.g.nblocks;
+        }
+    }
+    for (size_t j = 0; sums && j < nref; j++)
+        if (nbases[ref[j]] != (size_t)rs[j].nblocks + 1) {
+            if (bad_container) *bad_container = ref[j];
+            return ANSX_ERR_ARG;
+        }
+
+    // ---- the groups and the global blocks: group after group, batch order inside (ansx_plan.h, bdr_tables)
+    const u32 PB = batch_pass_blocks(c);
+    BdrTables Tb;
+    if (!bdr_tables(rs, PB, [&](const ansx_container_header& H0) {
+            return block_bound(kind, (u32)f, (size_t)H0.block_ints, (H0.kind & 0x100u) != 0);
+        }, &Tb))
+        return ANSX_ERR_ARG;
+    const std::vector<u32>& rmap = Tb.rmap;
+    const std::vector<ansx_bdr_ref>& recs = Tb.R;
+    const std::vector<ansx_bdr_group>& grp = Tb.G;
+    const std::vector<ansx_batch_src>& S = Tb.S;
+    const std::vector<ansx_container_header>& Hs = Tb.Hs;
+    const u32 ng = (u32)grp.size();
+    const u64 nbtot = Tb.nbtot, nslots = Tb.nslots;
+    std::vector<ansx_brs_src> SB;  // (the sums: every referenced container's bases, in the order of R)
+    if (sums) {
+        SB.resize(nref);
+        for (size_t j = 0; j < nref; j++) SB[rmap[j]] = { (u64)(uintptr_t)d_bases[ref[j]], rs[j].nblocks, 0 };
+    }
+    u32 kb = 0;  // key bits of a global block
+    while ((1ull << kb) < nbtot) kb++;
+
+    // ---- the planner's workspace: what comes back | what goes up | what stays
+    Upload W;
+    const auto w_sc = W.add<u64>(ANSX_BDR_SCALARS);
+    const auto w_tg = W.add<u64>((size_t)ng + 1);
+    const auto w_ps = W.add<ansx_bdr_pass>(nslots);
+    const size_t w_back = W.end;
+    const auto w_rmap = W.add<u32>(nref);
+    const auto w_rec = W.add<ansx_bdr_ref>(nref);
+    const auto w_grp = W.add<ansx_bdr_group>(ng);
+    const auto w_S = W.add<ansx_batch_src>(nref);
+    const auto w_SB = W.add<ansx_brs_src>(SB.size());
+    const size_t w_up = W.end;
+    const auto w_part = W.add<u64>(4 * nt);
+    const auto w_hist = W.add<u32>(16 * nt);
+    const auto w_rng = W.add<ansx_bdr_range>(nr);
+    const auto w_kv = W.add<u32>(4 * nr);
+    const auto w_tb = W.add<u32>(nbtot);
+    if ((rc = ensure_pin(c, w_up)) || (rc = ensure(c, c->rng_dev, W.end))) return rc;
+    W.host = c->rng_pin, W.devp = (u8*)c->rng_dev.p;
+    memset(W.host, 0, w_back);
+    W.pin(w_sc)[ANSX_BDR_BADRANGE] = ~0ull;
+    W.put(w_rmap, rmap.data()), W.put(w_rec, recs.data()), W.put(w_grp, grp.data()), W.put(w_S, S.data());
+    if (sums) W.put(w_SB, SB.data());
+    HIPCHK(c, hipMemcpyAsync(W.devp, W.host, w_up, hipMemcpyHostToDevice, s));
+    u64* sc = W.dev(w_sc);
+    u64* part = W.dev(w_part);
+    u64* partm = part + 2 * nt;
+    u64* parta = part + 3 * nt;
+    u32* hist = W.dev(w_hist);
+    u32* kv[4] = { W.dev(w_kv), W.dev(w_kv) + nr, W.dev(w_kv) + 2 * nr, W.dev(w_kv) + 3 * nr };
+    const ansx_bdr_ref* dR = W.dev(w_rec);
+    const ansx_bdr_group* dG = W.dev(w_grp);
+    ansx_bdr_range* rng = W.dev(w_rng);
+    u32* tb = W.dev(w_tb);
+    u32 cur = 0;  // the sorted spans are kv[cur], kv[cur + 1]; the union goes to the other pair
+    {
+        const u32 g = (u32)nt;
+        const u32* slot = F.dev(f_slot);
+        LAUNCH(c, "k_bdr_spans", k_bdr_spans, g, ANSX_DR_NT, 0, s, d_src, d_first, d_cnt, nr, slot, (const u32*)W.dev(w_rmap), dR,
+            part, sc);
+        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, part, nt, 2u, nt, sc, (u32*)nullptr);
+        LAUNCH(c, "k_bdr_compact", k_bdr_compact, g, ANSX_DR_NT, 0, s, d_src, d_first, d_cnt, nr, slot, (const u32*)W.dev(w_rmap),
+            dR, dG, (const u64*)part, (const u64*)sc, d_offsets, kv[0], kv[1], rng);
+        for (u32 sh = 0; sh < kb; sh += 4) {
+            LAUNCH(c, "k_dr_digit_count", k_dr_digit_count, g, ANSX_DR_NT, 0, s, kv[cur], (const u64*)sc, sh, hist);
+            LAUNCH(c, "k_dr_scan", (k_dr_scan<u32, false>), 1, ANSX_DR_NT, 0, s, hist, 16 * nt, 1u, 0ull, (u64*)nullptr,
+                (u32*)nullptr);
+            LAUNCH(c, "k_dr_digit_scatter", k_dr_digit_scatter, g, ANSX_DR_NT, 0, s, kv[cur], kv[cur + 1], kv[2 - cur],
+                kv[3 - cur], (const u64*)sc, sh, (const u32*)hist);
+            cur = 2 - cur;
+        }
+        LAUNCH(c, "k_dr_tile_max", k_dr_tile_max, g, ANSX_DR_NT, 0, s, kv[cur + 1], (const u64*)sc, partm);
+        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, true>), 1, ANSX_DR_NT, 0, s, partm, nt, 1u, 0ull, sc + ANSX_DR_LASTB1,
+            (u32*)nullptr);
+        LAUNCH(c, "k_dr_adds", k_dr_adds, g, ANSX_DR_NT, 0, s, kv[cur], kv[cur + 1], (const u64*)sc, (const u64*)partm,
+            kv[2 - cur], kv[3 - cur], parta);
+        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, parta, nt, 1u, 0ull, sc + ANSX_DR_T, (u32*)nullptr);
+        const u32* dS = kv[2 - cur];
+        const u32* offl = kv[3 - cur];
+        LAUNCH(c, "k_bdr_k0", k_bdr_k0, g_nr, ANSX_DR_NT, 0, s, rng, (const u64*)sc, dR, dG, dS, offl, (const u64*)parta);
+        LAUNCH(c, "k_bdr_groups", k_bdr_groups, (ng + ANSX_DR_NT) / ANSX_DR_NT, ANSX_DR_NT, 0, s, dG, ng, (const u32*)kv[cur], offl,
+            (const u64*)parta, (const u64*)sc, W.dev(w_tg));
+        // (the grids over tb follow the ranges or the referenced blocks, whichever is less, in strides: T is not known here)
+        const u32 g_tb = (u32)std::min<u64>((std::min<u64>(nbtot, 1 + nr * 16) + ANSX_DR_NT - 1) / ANSX_DR_NT, 4096);
+        LAUNCH(c, "k_bdr_blocks", k_bdr_blocks, g_tb, ANSX_DR_NT, 0, s, tb, (const u64*)sc, dS, offl, (const u64*)parta);
+        LAUNCH(c, "k_bdr_pass_blocks", k_bdr_pass_blocks, g_tb, ANSX_DR_NT, 0, s, (const u32*)tb, (const u64*)sc, dR, (u32)nref, dG,
+            (const u64*)W.dev(w_tg), PB, W.dev(w_ps));
+        LAUNCH(c, "k_bdr_pass_pieces", k_bdr_pass_pieces, g, ANSX_DR_NT, 0, s, (const ansx_bdr_range*)rng, (const u64*)sc, dR, dG,
+            (const u64*)W.dev(w_tg), PB, W.dev(w_ps));
+    }
+    HIPCHK(c, hipMemcpyAsync(W.host, W.devp, w_back, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const u64* hsc = W.pin(w_sc);
+    if (hsc[ANSX_BDR_BADRANGE] != ~0ull) {
+        if (bad_range) *bad_range = (size_t)hsc[ANSX_BDR_BADRANGE];
+        return ANSX_ERR_ARG;
+    }
+    const u64 total = hsc[ANSX_DR_TOTAL], T = hsc[ANSX_DR_T];
+    if (total_ints) *total_ints = total;
+    if (total > cap) return ANSX_ERR_CAPACITY;
+    if (total == 0) return ANSX_OK;
+    if (T == 0 || T > nbtot || hsc[ANSX_DR_NNE] == 0) return ANSX_ERR_HIP;  // (cannot happen: a planner fault)
+    // (the pinned page is written again by the first pass: what the passes need of it is taken out here, O(passes))
+    const std::vector<u64> tg(W.pin(w_tg), W.pin(w_tg) + ng + 1);
+    const std::vector<ansx_bdr_pass> ps(W.pin(w_ps), W.pin(w_ps) + nslots);
+
+    // ---- the passes
+    const u64 ntn = (hsc[ANSX_DR_NNE] + ANSX_DR_TILE - 1) / ANSX_DR_TILE;  // tiles of non-empty ranges
+    for (u32 g = 0; g < ng; g++) {
+        const u64 bi = grp[g].bi;
+        if (tg[g] > tg[g + 1] || tg[g + 1] > T) return ANSX_ERR_HIP;
+        for (u64 ka = tg[g], p = 0; ka < tg[g + 1]; ka += PB, p++) {
+            const u64 kb_ = std::min<u64>(ka + PB, tg[g + 1]);
+            const u32 Tp = (u32)(kb_ - ka);
+            const ansx_bdr_pass& q = ps[grp[g].pslot + p];
+            if (q.np > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+            if (q.last_n == 0 || q.last_n > bi || q.wl < q.last_n) return ANSX_ERR_HIP;  // (a planner fault)
+            Upload D;  // (nothing of it goes up: the pass's plan is built where it is read)
+            const auto s_fl = D.add<u32>(4);
+            const auto s_B = D.add<ansx_batch_blk>(Tp);
+            const auto s_O = D.add<ansx_blk_out>(Tp);
+            const auto s_pp = D.add<ansx_piece>(q.np);
+            const auto s_wp = D.add<u64>(q.np + 1);
+            const auto s_pt = D.add<u64>(2 * ntn);
+            u64* agg = nullptr;
+            if (sums && (rc = range_sums_workspace(c, bi, Tp, &agg))) return rc;
+            if ((rc = ensure(c, c->rng_plan, D.end))) return rc;
+            D.devp = (u8*)c->rng_plan.p;
+            u32* dflags = D.dev(s_fl);
+            LAUNCH(c, "k_bdr_pass_table", k_bdr_pass_table, 1, ANSX_DR_NT, 0, s, (const u32*)(tb + ka), Tp, dR, (u32)nref, (u32)bi,
+                dflags, D.dev(s_B), D.dev(s_O));
+            if (q.np) {
+                LAUNCH(c, "k_bdr_piece_part", k_bdr_piece_part, (u32)ntn, ANSX_DR_NT, 0, s, (const ansx_bdr_range*)rng, (const u64*)sc,
+                    dR, dG, (u32)ka, (u32)kb_, D.dev(s_pt));
+                LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, D.dev(s_pt), ntn, 2u, ntn, (u64*)nullptr,
+                    (u32*)nullptr);
+                LAUNCH(c, "k_bdr_piece_put", k_bdr_piece_put, (u32)ntn, ANSX_DR_NT, 0, s, (const ansx_bdr_range*)rng, (const u64*)sc,
+                    dR, dG, (u32)ka, (u32)kb_, (const u64*)D.dev(s_pt), (const ansx_blk_out*)D.dev(s_O), D.dev(s_pp), D.dev(s_wp),
+                    q.np, q.ints);
+            }
+            Sub sub;
+            // (the sub-header's maxima are the group's, not the pass's: another decode form at most, the same ints)
+            if ((rc = sub_prepare(c, kind, f, Hs[g], (u64)(Tp - 1) * bi + q.last_n, Tp, q.cap_pay, q.wl, D.dev(s_O), &sub))) return rc;
+            LAUNCH(c, "k_batch_index", k_batch_index, 1, 1024, 0, s, (const ansx_batch_src*)W.dev(w_S), (const ansx_batch_blk*)D.dev(s_B),
+                sub.P.g, Tp, sub.H, sub.cont, q.cap_pay, dflags);
+            LAUNCH(c, "k_batch_copy", k_batch_copy, Tp, 256, 0, s, (const ansx_batch_src*)W.dev(w_S), (const ansx_batch_blk*)D.dev(s_B),
+                sub.P.g, sub.lay(), sub.cont, q.cap_pay, dflags);
+            rc = sub_decode(c, sub, dflags, [&](u32* gflags) -> int {
+                int st;
+                if (sums && (st = batch_sums_scan(c, sub.list, bi, Tp, D.dev(s_O), D.dev(s_B), W.dev(w_SB), agg, gflags, s))) return st;
+                if (!q.np) return ANSX_OK;
+                const u32 grid = (u32)std::min<u64>((q.ints + ANSX_PIECE_CHUNK - 1) / ANSX_PIECE_CHUNK, 1u << 20);
+                LAUNCH(c, "k_piece_gather", k_piece_gather, grid, 256, 0, s, (const u32*)sub.list, (const ansx_piece*)D.dev(s_pp),
+                    (const u64*)D.dev(s_wp), (u32)q.np, q.ints, d_out, (const u32*)gflags);
+                return ANSX_OK;
+            }, s);
+            if (rc == ANSX_ERR_FORMAT && bad_container) *bad_container = count;
+            if (rc) return rc;
+        }
+    }
+    return ANSX_OK;
+}
+
 // ansx_next_geq_batch_dev (ansx_batchnextgeq.h): the front half above over the lists the targets
 // name -> k_ngb_locate, a lane per target -> ONE read-back of the located blocks, checked -> the found targets as ranges
 // of one int at the start of their blocks, destination the target's own index -> the passes of the sums call with
@@ -4630,6 +4881,62 @@ int ansx_decode_batch_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_
     return run_call(c, stream, [&](hipStream_t s) {
         return decode_batch_ranges(c, kind, f, d_ins, in_bytes, count, src, (const u64*)first, cnt, nranges, d_out,
             out_capacity_ints, (u64*)offsets, (u64*)total_ints, bad_container, bad_range, d_bases, nbases, s);
+    });
+}
+
+// (every argument check of the two entries below: before the context is touched)
+static int batch_device_ranges_args(const ansx_ctx* c, const uint8_t* const* d_ins, const size_t* in_bytes, bool with_bases,
+    const uint32_t* const* d_bases, const size_t* nbases, size_t count, const uint32_t* d_src, const uint64_t* d_first,
+    const uint32_t* d_cnt, size_t nranges, const uint32_t* d_out, size_t out_capacity_ints, const uint64_t* d_offsets)
+{
+    if (!c || count > 0xFFFFFFFFull || nranges > 0xFFFFFFFFull) return ANSX_ERR_ARG;
+    if (nranges > 0 && (!d_src || !d_first || !d_cnt || !d_ins || !in_bytes)) return ANSX_ERR_ARG;
+    if (with_bases && (!d_bases || !nbases)) return ANSX_ERR_ARG;
+    if (((uintptr_t)d_src & 3u) || ((uintptr_t)d_first & 7u) || ((uintptr_t)d_cnt & 3u) || ((uintptr_t)d_out & 3u)
+        || ((uintptr_t)d_offsets & 7u))
+        return ANSX_ERR_ARG;
+    if (!d_out && out_capacity_ints > 0) return ANSX_ERR_ARG;
+    return ANSX_OK;
+}
+
+// no ranges: total 0 and, the one thing such a call enqueues, d_offsets[0] = 0
+static int batch_device_ranges_none(ansx_ctx* c, uint64_t* d_offsets, uint64_t* total_ints, void* stream)
+{
+    if (total_ints) *total_ints = 0;
+    if (!d_offsets) return ANSX_OK;
+    return run_call(c, stream, [&](hipStream_t s) -> int {
+        HIPCHK(c, hipMemsetAsync(d_offsets, 0, 8, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        return ANSX_OK;
+    });
+}
+
+int ansx_decode_batch_device_ranges_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    size_t count, const uint32_t* d_src, const uint64_t* d_first, const uint32_t* d_cnt, size_t nranges, uint32_t* d_out,
+    size_t out_capacity_ints, uint64_t* d_offsets, uint64_t* total_ints, size_t* bad_container, size_t* bad_range, void* stream)
+{
+    if (batch_device_ranges_args(c, d_ins, in_bytes, false, nullptr, nullptr, count, d_src, d_first, d_cnt, nranges, d_out,
+            out_capacity_ints, d_offsets))
+        return ANSX_ERR_ARG;
+    if (nranges == 0) return batch_device_ranges_none(c, d_offsets, total_ints, stream);
+    return run_call(c, stream, [&](hipStream_t s) {
+        return decode_batch_device_ranges(c, kind, f, d_ins, in_bytes, count, d_src, (const u64*)d_first, d_cnt, nranges, d_out,
+            out_capacity_ints, (u64*)d_offsets, (u64*)total_ints, bad_container, bad_range, nullptr, nullptr, s);
+    });
+}
+
+int ansx_decode_batch_device_ranges_sums_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint32_t* const* d_bases, const size_t* nbases, size_t count, const uint32_t* d_src, const uint64_t* d_first,
+    const uint32_t* d_cnt, size_t nranges, uint32_t* d_out, size_t out_capacity_ints, uint64_t* d_offsets, uint64_t* total_ints,
+    size_t* bad_container, size_t* bad_range, void* stream)
+{
+    if (batch_device_ranges_args(c, d_ins, in_bytes, true, d_bases, nbases, count, d_src, d_first, d_cnt, nranges, d_out,
+            out_capacity_ints, d_offsets))
+        return ANSX_ERR_ARG;
+    if (nranges == 0) return batch_device_ranges_none(c, d_offsets, total_ints, stream);
+    return run_call(c, stream, [&](hipStream_t s) {
+        return decode_batch_device_ranges(c, kind, f, d_ins, in_bytes, count, d_src, (const u64*)d_first, d_cnt, nranges, d_out,
+            out_capacity_ints, (u64*)d_offsets, (u64*)total_ints, bad_container, bad_range, d_bases, nbases, s);
     });
 }
 

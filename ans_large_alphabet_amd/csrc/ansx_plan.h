@@ -3,7 +3,8 @@
 // tables a pass over blocks of many containers takes; and the steps and pass tables of a batch of lists to encode
 // (ansx_encode_batch_dev); and the groups, drivers and round tables of a batch of conjunctive queries
 // (ansx_intersect_batch_dev); and the groups, rounds and pair tables of a batch of disjunctive queries
-// (ansx_union_batch_dev, and with the terms behind the pairs of ansx_topk_batch_dev).  Pure host arithmetic: no context, no stream, no device pointer
+// (ansx_union_batch_dev, and with the terms behind the pairs of ansx_topk_batch_dev); and the host's tables of the device
+// plan of ansx_decode_batch_device_ranges_dev (tests/tools/batch_dev_plan_check.cpp).  Pure host arithmetic: no context, no stream, no device pointer
 // (addresses travel as integers), so it builds with a plain host compiler and is tested on the CPU
 // (tests/tools/plan_check.cpp, tests/tools/isect_batch_plan_check.cpp, tests/tools/union_plan_check.cpp, tests/tools/topk_plan_check.cpp).  The plain structs the kernels read these plans through are in ansx_plan_types.h,
 // which the kernel headers include.
@@ -13,6 +14,7 @@
 
 #include <algorithm>
 #include <array>
+#include <map>
 #include <utility>
 #include <vector>
 
@@ -334,6 +336,51 @@ __attribute__((noinline)) static u64 batch_pass_plan(const std::vector<BatchSrc>
     P->close(bbound);
     pstart->push_back((u32)npieces);
     return npieces;
+}
+
+// ------------------------------------------------------------------------------- ranges of a batch, planned on the device
+// The host's part of ansx_decode_batch_device_ranges_dev ("device plan"), O(referenced
+// containers): rs, the referenced containers in batch order, laid end to end as global blocks -- geometry group after
+// group, batch order inside a group.  R / S (and rmap, a container's place among them) are in that order; G: the groups,
+// each with its first global block, its first pass slot (a group of NB blocks makes at most ceil(NB / PB) passes) and
+// bbound(H) of its geometry; Hs: a group's sub-header, its geometry with the maxima over its referenced containers.
+struct BdrTables {
+    std::vector<u32> rmap;
+    std::vector<ansx_bdr_ref> R;
+    std::vector<ansx_bdr_group> G;
+    std::vector<ansx_batch_src> S;
+    std::vector<ansx_container_header> Hs;
+    u64 nbtot = 0, nslots = 0;  // global blocks, pass slots
+};
+// -> false if the containers have 2^32 - 1 blocks or more together (a global block, and one behind the last, is a u32)
+template <class Bound> static inline bool bdr_tables(const std::vector<BatchSrc>& rs, u32 PB, const Bound& bbound, BdrTables* T)
+{
+    std::map<Geometry, std::vector<u32>> groups;
+    for (size_t j = 0; j < rs.size(); j++) groups[br_geometry(rs[j].H)].push_back((u32)j);
+    T->rmap.resize(rs.size());
+    T->R.reserve(rs.size()), T->S.reserve(rs.size());
+    for (const auto& gr : groups) {
+        const ansx_container_header& H0 = rs[gr.second[0]].H;
+        ansx_container_header H = H0;
+        H.max_nsyms = 0, H.max_log2_frame = 0, H.max_present_m1 = 0;
+        const u64 gb0 = T->nbtot;
+        for (const u32 j : gr.second) {
+            const BatchSrc& cs = rs[j];
+            T->rmap[j] = (u32)T->R.size();
+            T->R.push_back({ cs.H.n, cs.H.payload_bytes, (u32)T->nbtot, cs.nblocks, (u32)T->G.size(), 0 });
+            T->S.push_back({ cs.base, cs.lay.ckoff_off, cs.lay.ckstate_off, cs.lay.hint_off, cs.lay.payload_off, cs.H.payload_bytes,
+                cs.nblocks, 0 });
+            H.max_nsyms = std::max(H.max_nsyms, cs.H.max_nsyms);
+            H.max_log2_frame = std::max(H.max_log2_frame, cs.H.max_log2_frame);
+            H.max_present_m1 = std::max(H.max_present_m1, cs.H.max_present_m1);
+            T->nbtot += cs.nblocks;
+            if (T->nbtot >= 0xFFFFFFFFull) return false;
+        }
+        T->G.push_back({ (u64)bbound(H0), (u32)gb0, (u32)T->nslots, H0.block_ints, 0 });
+        T->Hs.push_back(H);
+        T->nslots += (T->nbtot - gb0 + PB - 1) / PB;
+    }
+    return true;
 }
 
 // ------------------------------------------------------------------------------- batches of lists to encode

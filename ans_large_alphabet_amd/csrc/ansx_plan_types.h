@@ -1,6 +1,7 @@
 // ansx -- the integer names and the plain structs and constants the host's plans (ansx_plan.h) fill and the kernels read
-// them through.  No code but the arithmetic of ansx_topk_batch_dev's selection at its end: it builds with a plain host
-// compiler, and the kernel headers take it through ansx_dev.h.
+// them through.  No code but the arithmetic of ansx_topk_batch_dev's selection and of the device plan of
+// ansx_decode_batch_device_ranges_dev at its end: it builds with a plain host compiler, and the kernel headers take it
+// through ansx_dev.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -197,4 +198,105 @@ ANSX_PLAN_FN u32 topk_pick(const u32* h, u32 n, u32 want, u32* above)
     }
     *above = a;
     return d;
+}
+
+// Ranges of a batch planned on the device (ansx_decode_batch_device_ranges_dev, ansx_batchdevranges.h; DESIGN.md
+// section 3d, "device plan").  The referenced containers, ordered by geometry group and by batch position inside a
+// group, are laid end to end as one virtual container: block b of referenced container r is GLOBAL block
+// R[r].gbase + b.  The touched global blocks, sorted and unique, are tb[0 .. T); a group's stretch of tb starts at
+// tg[group] and is cut into passes every PB entries.  The arithmetic of one item -- a range, an entry of tb, a piece --
+// is written here once: the kernels and the CPU check (tests/tools/batch_dev_plan_check.cpp) both run it.
+struct ansx_bdr_ref {    // a referenced container, in the order of the global blocks
+    u64 n;               // its ints
+    u64 payload_bytes;   // its header's
+    u32 gbase;           // its first global block (strictly ascending: no container is empty)
+    u32 nblocks;
+    u32 group;
+    u32 pad_;
+};
+struct ansx_bdr_group {  // a geometry group: containers of one block size, decoded together
+    u64 bbound;          // the most bytes a block's stream takes in this geometry
+    u32 gbase;           // its first global block
+    u32 pslot;           // the slot of its first pass among the call's pass scalars
+    u32 bi;              // ints per block
+    u32 pad_;
+};
+struct ansx_bdr_pass {   // the scalars of a pass, summed on the device and read back once with the planner's own
+    u64 wl;              // ints of its work list: every block's rounded up to 4
+    u64 cap_pay;         // the bound of its payload: over its sources, min(payload_bytes, blocks in the pass x bbound)
+    u64 np, ints;        // its pieces and their ints
+    u32 last_n, pad_;    // ints of its last block
+    u64 pad2_;
+};
+struct ansx_bdr_range {  // a non-empty range, in range order
+    u64 first, dst;      // its first int in its container, and in the caller's buffer
+    u32 count, r;        // r: its referenced container
+    u32 k0, pad_;        // the entry of tb its first block is; its blocks are consecutive entries from there
+};
+
+ANSX_PLAN_FN u32 bdr_rup4(u32 n) { return (n + 3u) & ~3u; }
+
+// range -> its span of global blocks [*gb0, *gb1p) (count > 0)
+ANSX_PLAN_FN void bdr_span(u64 first, u32 count, u32 bi, u32 gbase, u32* gb0, u32* gb1p)
+{
+    *gb0 = gbase + (u32)(first / bi);
+    *gb1p = gbase + (u32)((first + count - 1) / bi) + 1u;
+}
+
+// the referenced container a global block lies in: the last r with R[r].gbase <= gb
+ANSX_PLAN_FN u32 bdr_ref_of(const ansx_bdr_ref* R, u32 nref, u32 gb)
+{
+    u32 lo = 0, hi = nref;
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (R[mid].gbase <= gb) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// ints of block b of a container of n ints in blocks of bi: only its last block is short
+ANSX_PLAN_FN u32 bdr_block_ints(u64 n, u32 bi, u32 b)
+{
+    const u64 left = n - (u64)b * bi;
+    return left < bi ? (u32)left : bi;
+}
+
+// entry k of tb, in a group whose stretch starts at tg: its pass among the group's, and that pass's first entry
+ANSX_PLAN_FN u32 bdr_pass_of(u32 k, u32 tg, u32 PB) { return (k - tg) / PB; }
+ANSX_PLAN_FN u32 bdr_pass_first(u32 p, u32 tg, u32 PB) { return tg + p * PB; }  // (below T: no wrap)
+
+// the first entry of tb[0 .. T) that is not below gb
+ANSX_PLAN_FN u32 bdr_lower_bound(const u32* tb, u32 T, u32 gb)
+{
+    u32 lo = 0, hi = T;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (tb[mid] < gb) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// what a source adds to the payload bound of a pass that holds nblk of its blocks
+ANSX_PLAN_FN u64 bdr_src_bound(u64 payload_bytes, u32 nblk, u64 bbound)
+{
+    const u64 v = (u64)nblk * bbound;
+    return payload_bytes < v ? payload_bytes : v;
+}
+
+// The part of a range that lies in the pass of tb entries [ka, kb): ints [*start, *start + count) of its container,
+// the first of them in entry *k of tb, which is block *b.  -> count, 0 if the range has no block in the pass.  A range
+// that crosses passes gives one piece in each.
+ANSX_PLAN_FN u32 bdr_piece(const ansx_bdr_range& g, u32 bi, u32 ka, u32 kb, u64* start, u32* k, u32* b)
+{
+    const u32 b0 = (u32)(g.first / bi), b1 = (u32)((g.first + g.count - 1) / bi);
+    const u32 k1 = g.k0 + (b1 - b0);
+    if (g.k0 >= kb || k1 < ka) return 0;
+    const u32 kA = g.k0 > ka ? g.k0 : ka, kB = k1 < kb - 1 ? k1 : kb - 1;
+    const u32 bA = b0 + (kA - g.k0), bB = b0 + (kB - g.k0);
+    const u64 lo = (u64)bA * bi, hi = ((u64)bB + 1) * bi, end = g.first + g.count;
+    const u64 s = g.first > lo ? g.first : lo, e = end < hi ? end : hi;
+    *start = s, *k = kA, *b = bA;
+    return (u32)(e - s);
 }

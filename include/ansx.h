@@ -509,6 +509,54 @@ int ansx_decode_batch_ranges_sums_dev(ansx_ctx* ctx, int kind, int fidelity, con
     const uint64_t* first, const uint32_t* cnt, size_t nranges, uint32_t* d_out, size_t out_capacity_ints, uint64_t* offsets,
     uint64_t* total_ints, size_t* bad_container, size_t* bad_range, void* stream);
 
+/* ansx_decode_batch_device_ranges_dev / ansx_decode_batch_device_ranges_sums_dev: ansx_decode_batch_ranges_dev /
+ * ansx_decode_batch_ranges_sums_dev with (src, first, cnt) in DEVICE memory and the plan built on the device
+ * ("device plan").  d_ins / in_bytes (and d_bases / nbases) are HOST arrays of `count` entries as
+ * there.  d_src (4-byte aligned), d_first (8) and d_cnt (4) are DEVICE arrays of nranges entries, read on `stream`: a
+ * kernel that wrote them earlier on that stream is ordered before the read.  d_out receives, byte for byte, what the
+ * host-array call writes for the same ranges: range i at d_out[offsets[i] ..), in range order, back to back; ranges
+ * may overlap, repeat, be unsorted, have count 0 and name the containers in any order; one pointer may stand at
+ * several batch positions; geometries may be mixed.  d_offsets (optional, DEVICE, 8-byte aligned, nranges + 1 entries)
+ * receives the exclusive prefix sum of cnt and the total; *total_ints (optional, HOST) the total.  Both are written on
+ * ANSX_OK and ANSX_ERR_CAPACITY.
+ * Nothing on the host grows with nranges: host work and copies are O(count) + O(referenced containers) + O(passes), and
+ * the call waits for the device three times before the passes -- the number of referenced containers, their headers,
+ * the plan's scalars -- and then as the host-array call does for every pass's decode.
+ * Errors, in this order; nothing of d_out is written before the last of them is decided:
+ *   before the context is touched, ANSX_ERR_ARG for a null ctx; a null d_src / d_first / d_cnt / d_ins / in_bytes with
+ *   nranges > 0; a misaligned d_src, d_first, d_cnt, d_out or d_offsets; d_out == NULL with out_capacity_ints > 0; count
+ *   or nranges > UINT32_MAX; for the sums a null d_bases or nbases array.  nranges == 0: ANSX_OK, *total_ints = 0 and,
+ *   the one thing such a call enqueues, d_offsets[0] = 0 if d_offsets is given; the context is otherwise untouched;
+ *   found on the device, before any header is judged: ANSX_ERR_ARG with *bad_range = the smallest i with
+ *   d_src[i] >= count; then ANSX_ERR_ARG with *bad_range = the first range that names a container whose d_ins entry (for
+ *   the sums: or d_bases entry) is null or not 16-byte (4-byte) aligned;
+ *   on the host, once the referenced headers are back: ANSX_ERR_FORMAT with *bad_container = the first referenced
+ *   container in batch order that fails the checks of ansx_decode_batch_ranges_dev; for the sums then ANSX_ERR_ARG with
+ *   *bad_container where nbases[i] != nblocks_i + 1; ANSX_ERR_ARG if the referenced containers have 2^32 - 1 blocks or
+ *   more together;
+ *   on the device, read back with the plan's scalars: ANSX_ERR_ARG with *bad_range = the smallest i with first[i] > n or
+ *   cnt[i] > n - first[i], n that of container src[i]; then ANSX_ERR_CAPACITY if sum(cnt) > out_capacity_ints
+ *   (d_out = NULL with capacity 0 is the size query);
+ *   from a pass: ANSX_ERR_FORMAT with *bad_container = count (a bad stream or index entry; for the sums also foreign
+ *   bases at a touched block).  d_out is then unspecified; nothing is written at or beyond d_out + out_capacity_ints.
+ * The context stays usable after any error and keeps no trace of the call.
+ * Selectivity is that of the host-array call with two differences: d_ins[i] / in_bytes[i] / d_bases[i] of ALL count
+ * containers are copied to the device unjudged (null is allowed for an unreferenced one), and one workgroup scans 4
+ * bytes of marks per container of the batch.  No container but a referenced one is read, and of those the header, the
+ * index entries and bytes of touched blocks and, for the sums, bases b and b + 1 of touched blocks b.
+ * Workspace beyond the host-array call's: 24 bytes per container of the batch (32 for the sums) and 12 per
+ * min(count, nranges); 160 per referenced container (176); 48 per range and 112 per 4096 ranges; 4 per block of a
+ * referenced container; 48 per pass the referenced blocks could make.  A pass's 24 bytes per block and 24 per piece
+ * are those of the host-array call, built on the device where that call uploads them. */
+int ansx_decode_batch_device_ranges_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins,
+    const size_t* in_bytes, size_t count, const uint32_t* d_src, const uint64_t* d_first, const uint32_t* d_cnt,
+    size_t nranges, uint32_t* d_out, size_t out_capacity_ints, uint64_t* d_offsets, uint64_t* total_ints,
+    size_t* bad_container, size_t* bad_range, void* stream);
+int ansx_decode_batch_device_ranges_sums_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins,
+    const size_t* in_bytes, const uint32_t* const* d_bases, const size_t* nbases, size_t count, const uint32_t* d_src,
+    const uint64_t* d_first, const uint32_t* d_cnt, size_t nranges, uint32_t* d_out, size_t out_capacity_ints,
+    uint64_t* d_offsets, uint64_t* total_ints, size_t* bad_container, size_t* bad_range, void* stream);
+
 /* ansx_next_geq_batch_dev: ansx_next_geq_dev over a batch.  With s the ids of container src[i], n of them:
  * d_pos[i] = min{ j : s[j] >= d_targets[i] } (the lower bound: of equal ids the first), d_ids[i] = s[d_pos[i]]; beyond
  * the last id d_pos[i] = n of that container and d_ids[i] = ANSX_NO_ID.  src is a HOST array of ntargets entries,
