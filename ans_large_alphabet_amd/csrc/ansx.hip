@@ -3187,12 +3187,28 @@ int block_bases(ansx_ctx* c, int kind, int f, const u8* d_in, size_t in_bytes, u
 // profiles/intersect_bench.json).
 #define ANSX_ISECT_FULL_PER_BLOCK 1u
 
+// The two launches every compaction is made of, behind a kernel that has written W's ballots and tile counts over nc
+// candidates: the scan of the tile counts -> W.total ...
+int isect_tile_scan(ansx_ctx* c, const IsectWork& W, hipStream_t s)
+{
+    LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
+    return ANSX_OK;
+}
+// ... and the values d_cand[i] whose ballot bit is set moved to the front of o (gflags / dflags: the two flag words
+// k_isect_compact looks at before it writes).  Any array of nc values may be moved by the same ballots.
+int isect_move(ansx_ctx* c, const IsectWork& W, const u32* d_cand, u32 nc, const IsectOut& o, const u32* gflags, const u32* dflags,
+    hipStream_t s)
+{
+    LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, d_cand, nc, (const u64*)W.ballots,
+        (const u64*)W.counts, (const u64*)W.total, o.cap, (const u64*)W.wpos, o.ids, o.idx, o.pos, gflags, dflags);
+    return ANSX_OK;
+}
+
 int isect_compact(ansx_ctx* c, const IsectWork& W, const u32* d_cand, u32 nc, const IsectOut& o, const u32* gflags,
     const u32* dflags, hipStream_t s)
 {
-    LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
-    LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, d_cand, nc, (const u64*)W.ballots,
-        (const u64*)W.counts, (const u64*)W.total, o.cap, (const u64*)W.wpos, o.ids, o.idx, o.pos, gflags, dflags);
+    int rc;
+    if ((rc = isect_tile_scan(c, W, s)) || (rc = isect_move(c, W, d_cand, nc, o, gflags, dflags, s))) return rc;
     HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
     return ANSX_OK;
 }
@@ -3324,29 +3340,263 @@ int intersect_lists(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
     return ANSX_OK;
 }
 
-// The exclusion step of ansx_bool_batch_dev (ansx_bool.h) behind either positive phase: the n candidates of `cand`
-// (d_total: null, or where the device holds how many of them there are), query j's in [seg[j], seg[j + 1]), that are in
-// none of their query's lists xt[xo[j] .. xo[j + 1]) -> out, their bounds -> nseg, their count -> W.total.  gf / df:
-// k_isect_compact's two flag words.  Enqueues only.
-int bool_exclude_step(ansx_ctx* c, const IsectWork& W, const u32* ids, const u32* cand, u32 n, const u64* d_total, const u32* seg,
-    size_t Q, const u32* xo, const ansx_isb_list* xt, const u32* sflag, u32* out, u32* nseg, const u32* gf, const u32* df,
-    hipStream_t s)
+// --------------------------------------------------------------------------------- queries over a batch of lists
+// The host path of ansx_intersect_batch_dev, ansx_union_batch_dev, ansx_bool_batch_dev, ansx_topk_batch_dev and
+// ansx_topk_bool_batch_dev: ONE front end (query_front), one budget (query_budget), one loop
+// over the groups (run_groups), and the phases below, which the four group functions string together.  A phase enqueues
+// only; every host wait stands in a group function.
+
+struct Moved {  // an array the ballots of a step compact: from -> to and, when asked for, every kept value's position -> idx
+    const u32* from;
+    u32 *to, *idx;
+};
+
+// The compact step behind a kernel that has written W's ballots and tile counts over the n candidates of queries
+// [seg[j], seg[j + 1]), j < Q: the scan of the tile counts -> W.total, `a` compacted (and `b`, moved by the same ballots,
+// when given), and the queries' bounds among what is kept -> nseg.  gf / df: k_isect_compact's two flag words.
+int compact_step(ansx_ctx* c, const IsectWork& W, u32 n, const Moved& a, const Moved* b, const u32* seg, size_t Q, u32* nseg,
+    const u32* gf, const u32* df, hipStream_t s)
 {
-    LAUNCH(c, "k_bool_exclude", k_bool_exclude, W.ntiles, ANSX_ISECT_NT, 0, s, ids, cand, n, d_total, seg, (u32)Q, xo, xt,
-        (u32)c->dbg.bool_form, W.ballots, W.counts, sflag);
-    LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
-    LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, cand, n, (const u64*)W.ballots, (const u64*)W.counts,
-        (const u64*)W.total, (u64)n, (const u64*)nullptr, out, (u32*)nullptr, (u64*)nullptr, gf, df);
+    int rc;
+    if ((rc = isect_tile_scan(c, W, s))) return rc;
+    if ((rc = isect_move(c, W, a.from, n, { a.to, a.idx, nullptr, n }, gf, df, s))) return rc;
+    if (b && (rc = isect_move(c, W, b->from, n, { b->to, b->idx, nullptr, n }, gf, df, s))) return rc;
     LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, seg, (u32)Q, n, (const u64*)W.ballots,
         (const u64*)W.counts, (const u64*)W.total, nseg);
     return ANSX_OK;
 }
 
+// The exclusion step of ansx_bool_batch_dev (ansx_bool.h) behind either positive phase: the n candidates of `cand`
+// (d_total: null, or where the device holds how many of them there are), query j's in [seg[j], seg[j + 1]), that are in
+// none of their query's lists xt[xo[j] .. xo[j + 1]) -> cand.to, their bounds -> nseg, their count -> W.total.  gf / df:
+// k_isect_compact's two flag words.
+int bool_exclude_step(ansx_ctx* c, const IsectWork& W, const u32* ids, const Moved& cand, u32 n, const u64* d_total, const u32* seg,
+    size_t Q, const u32* xo, const ansx_isb_list* xt, const u32* sflag, u32* nseg, const u32* gf, const u32* df, hipStream_t s)
+{
+    LAUNCH(c, "k_bool_exclude", k_bool_exclude, W.ntiles, ANSX_ISECT_NT, 0, s, ids, cand.from, n, d_total, seg, (u32)Q, xo, xt,
+        (u32)c->dbg.bool_form, W.ballots, W.counts, sflag);
+    return compact_step(c, W, n, cand, nullptr, seg, Q, nseg, gf, df, s);
+}
+
+// The unique step of ansx_union_batch_dev (ansx_union.h) over a group's last merge buffer: of the n merged ids of
+// `heads.from`, query j's in [seg[j], seg[j + 1]), the first of every run of equal ones -> heads.to, its position ->
+// heads.idx (when asked for), the queries' bounds among the heads -> hseg, their count -> W.total.  uflag: k_union_heads'
+// own flag word, which the compaction looks at as well.
+int unique_step(ansx_ctx* c, const IsectWork& W, const Moved& heads, u32 n, const u32* seg, size_t Q, const u32* sflag, u32* uflag,
+    u32* hseg, const u32* gf, hipStream_t s)
+{
+    LAUNCH(c, "k_union_heads", k_union_heads, W.ntiles, ANSX_ISECT_NT, 0, s, heads.from, n, seg, (u32)Q, W.ballots, W.counts, sflag,
+        uflag);
+    return compact_step(c, W, n, heads, nullptr, seg, Q, hseg, gf, (const u32*)uflag, s);
+}
+
+// What the front end leaves for the planners and the groups.  Without payloads the entries of br are the referenced
+// lists; with payloads they are the entries of the source list (ansx_plan.h, query_sources): every referenced list's id
+// container and, behind each term's, its payload.
+struct QueryFront {
+    int kind, f;
+    size_t count;                   // the containers of the batch
+    BrFront br;                     // the entries, their checked headers
+    QuerySources src;               // with payloads: the source list
+    const u32 *rid, *xrid;          // per term / per excluded term: its list's entry (what the planners read)
+    const std::vector<u32>* index;  // per entry: the batch index an error names
+    const std::vector<u32>* payof;  // with payloads: per entry, the entry of its payload or ANSX_TOPK_NONE
+    std::vector<u32> entry_index;   // (with payloads: what index points to)
+    std::vector<u64> n, off;        // per entry: its ints, and where the group at hand decodes it to (every group sets its own lists')
+};
+
+// The front end of the five calls: the headers of the containers the terms and the excluded terms name -- with d_pays,
+// also of the payloads of the lists that are terms -- in ONE round trip, checked.  ANSX_ERR_FORMAT names in
+// *bad_container the smallest batch index whose header fails the checks or whose payload differs from it in n.
+// Without excluded terms the caller's array of terms is read where it is.
+int query_front(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
+    const size_t* pay_bytes, size_t count, const u32* terms, size_t nt, const u32* xterms, size_t nx, QueryFront* Q,
+    size_t* bad_container, hipStream_t s)
+{
+    int rc;
+    Q->kind = kind, Q->f = f, Q->count = count;
+    std::vector<u32> both;
+    const u32* named = terms;
+    if (nx) both.assign(terms, terms + nt), both.insert(both.end(), xterms, xterms + nx), named = both.data();
+    if (!d_pays) {
+        if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, named, nt + nx, nullptr, &Q->br, bad_container, s))) return rc;
+        Q->rid = Q->br.rid.data(), Q->index = &Q->br.ref, Q->payof = nullptr;
+    } else {
+        const QuerySources& S = Q->src;
+        query_sources(named, nt, nt + nx, count, &Q->src);
+        const size_t ne = S.owner.size();
+        std::vector<const u8*> ptr(ne);
+        std::vector<size_t> len(ne);
+        std::vector<u32> all(ne);
+        Q->entry_index.resize(ne);
+        for (size_t e = 0; e < ne; e++) {
+            const size_t i = S.batch_index(e);
+            ptr[e] = S.pay[e] ? d_pays[i] : d_ins[i], len[e] = S.pay[e] ? pay_bytes[i] : in_bytes[i];
+            all[e] = (u32)e, Q->entry_index[e] = (u32)i;
+        }
+        size_t failed = ne;
+        rc = batch_ranges_front(c, kind, f, ptr.data(), len.data(), ne, all.data(), ne, nullptr, &Q->br, &failed, s);
+        if (rc && rc != ANSX_ERR_FORMAT) return rc;
+        const size_t bad = query_sources_first_bad(S, Q->br.rs, failed);
+        if (bad < ne) {
+            if (bad_container) *bad_container = S.batch_index(bad);
+            return ANSX_ERR_FORMAT;
+        }
+        Q->rid = S.rid.data(), Q->index = &Q->entry_index, Q->payof = &S.payof;
+    }
+    Q->xrid = Q->rid + nt;
+    Q->n.resize(Q->br.rs.size());
+    for (size_t j = 0; j < Q->n.size(); j++) Q->n[j] = Q->br.rs[j].H.n;
+    Q->off.assign(Q->n.size(), 0);
+    return ANSX_OK;
+}
+
+// The ints a group may take: ANSX_ISECT_BATCH_INTS or the default -- HALF of it for a ranked call, whose groups hold
+// twice what an unranked one's do
+u64 query_budget(const ansx_ctx* c, bool ranked)
+{
+    const u64 ints = c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT;
+    return ranked ? ints / 2 : ints;
+}
+
+// The groups of a call, one after the other, and the call's last wait: behind the copies to the caller's arrays
+template <class Group, class One> int run_groups(ansx_ctx* c, const std::vector<Group>& groups, const One& one, hipStream_t s)
+{
+    int rc;
+    for (const Group& g : groups)
+        if ((rc = one(g))) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ANSX_OK;
+}
+
+// Where an unranked call's results go: the caller's arrays of cap entries (cnt: ansx_union_batch_dev's counts, or null),
+// how many of them the groups so far have taken, and every query's offset
+struct IdsOut {
+    u32 *ids, *cnt;
+    size_t cap;
+    u64 run;
+    u64* offsets;
+};
+
+// Two buffers a step reads one of and writes the other
+struct Flip {
+    u32* b[2];
+    u32 cur = 0;
+    u32* from() const { return b[cur]; }
+    u32* to() const { return b[1 - cur]; }
+    void flip() { cur = 1 - cur; }
+};
+
+// ... decode: the group's lists whole, list lists[k] to ids + at[k], back to back, by the passes of ansx_decode_batch_dev;
+// with `pay`, the payloads of those that have one to pay + at[k] -- the same layout, any geometry (a list that is only
+// excluded has none: its part of pay is never read).  Host waits: those of the passes.
+int group_decode(ansx_ctx* c, QueryFront& F, const std::vector<u32>& lists, const std::vector<u64>& at, u32* ids, u32* pay,
+    size_t* bad_container, hipStream_t s)
+{
+    int rc;
+    GeometryGroups geo;
+    for (size_t k = 0; k < lists.size(); k++) F.off[lists[k]] = at[k], geo[br_geometry(F.br.rs[lists[k]].H)].push_back(lists[k]);
+    if ((rc = batch_decode_groups(c, F.kind, F.f, F.br.rs, F.off, geo, F.count, ids, bad_container, s)) || !pay) return rc;
+    geo.clear();
+    for (size_t k = 0; k < lists.size(); k++) {
+        const u32 r = (*F.payof)[lists[k]];
+        if (r == ANSX_TOPK_NONE) continue;
+        F.off[r] = at[k], geo[br_geometry(F.br.rs[r].H)].push_back(r);
+    }
+    return batch_decode_groups(c, F.kind, F.f, F.br.rs, F.off, geo, F.count, pay, bad_container, s);
+}
+
+// ... group workspace set-up.  The caller has laid out U: what goes up first, then what stays on the device.  Room for
+// the first host_bytes of it in the upload page (what the host reads or writes) and for all of it with IsectWork over
+// ncand candidates behind it in the device work area; the flag words s_fl zeroed and, when given, the overflow word of
+// the ranked calls set (ANSX_TOPK_NONE, three zero words behind it).  No copy out of the page is pending: a group ends
+// in a synchronisation.
+struct GroupWs {
+    u8* work;    // IsectWork's place
+    u32* sflag;  // pinned: the scan's flag word, read back
+    u64* total;  // pinned: a step's count, read back
+};
+int group_room(ansx_ctx* c, Upload& U, size_t host_bytes, u64 ncand, Upload::Sec<u32> s_fl, const Upload::Sec<u32>* s_of, GroupWs* ws)
+{
+    int rc;
+    const size_t o_w = rup(U.end, 16);
+    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, host_bytes))) return rc;
+    if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(ncand, false)))) return rc;
+    U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;
+    memset(U.pin(s_fl), 0, s_fl.bytes);
+    if (s_of) {
+        u32* hof = U.pin(*s_of);
+        hof[0] = ANSX_TOPK_NONE, hof[1] = hof[2] = hof[3] = 0;
+    }
+    ws->work = U.devp + o_w, ws->sflag = &c->pin->isect_sflag, ws->total = &c->pin->isect_total;
+    return ANSX_OK;
+}
+
+// The select state of a ranked group, sections on the device behind what goes up: prefixes | what is left to find |
+// cursors | histograms (the cursors are cleared with the histograms behind them)
+struct SelectSecs {
+    Upload::Sec<u64> pre;
+    Upload::Sec<u32> want, cur, hist;
+};
+SelectSecs select_sections(Upload& U, size_t Q)
+{
+    SelectSecs t;
+    t.pre = U.add<u64>(Q), t.want = U.add<u32>(Q), t.cur = U.add<u32>(rup(Q, 4)), t.hist = U.add<u32>(Q * (size_t)ANSX_TOPK_BINS);
+    return t;
+}
+
+// ... and, the caller's tables put: the first `up` bytes of U in one copy and, for a ranked group, its select state cleared
+int group_upload(ansx_ctx* c, const Upload& U, size_t up, const SelectSecs* sel, hipStream_t s)
+{
+    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
+    if (sel) HIPCHK(c, hipMemsetAsync(U.dev(sel->cur), 0, sel->hist.off + sel->hist.bytes - sel->cur.off, s));
+    return ANSX_OK;
+}
+
+// ... scan: the decoded gaps of the group's lists become ids, in place (section 3e's three kernels over all of them)
+int group_scan(ansx_ctx* c, u32* ids, const std::vector<u64>& at, hipStream_t s, SumsPlan* S)
+{
+    int rc;
+    const size_t nlists = at.size() - 1;
+    if ((rc = sums_prepare(c, (uintptr_t)ids, at.back(), at.data(), nlists, s, S))) return rc;
+    return sums_launch(c, ids, at.back(), nlists, *S, s);
+}
+
+// ... what its flag word says once it has come home (to ws.sflag) and the host has waited: the first list of the buffer
+// whose sum left 32 bits -> ANSX_ERR_DOMAIN and its batch index
+int scan_flag_status(const GroupWs& ws, const std::vector<u32>& lists, const std::vector<u32>& index, size_t* bad_container)
+{
+    const u32 flag = *ws.sflag;
+    if (flag == ANSX_SS_NONE) return ANSX_OK;
+    if (bad_container && flag < lists.size()) *bad_container = index[lists[flag]];
+    return ANSX_ERR_DOMAIN;
+}
+
+// ... the drivers' ids gathered into the first candidate buffer, with the queries' first bounds (ansx_intersect_batch.h)
+int gather_drivers(ansx_ctx* c, const u32* ids, const ansx_isb_query* G, size_t Q, u64 nc0, u32* cand, u32* seg, const u32* sflag,
+    hipStream_t s)
+{
+    LAUNCH(c, "k_isectb_gather", k_isectb_gather, (u32)((std::max<u64>(nc0, Q + 1) + ANSX_ISECT_TILE - 1) / ANSX_ISECT_TILE),
+        ANSX_ISECT_NT, 0, s, ids, G, (u32)Q, cand, (u32)nc0, seg, sflag);
+    return ANSX_OK;
+}
+
+// a grid; 2^31 non-empty pairs in a round of merges
+int merge_tiles_check(const UnbGroup& g, size_t* bad_query)
+{
+    for (const u64 t : g.tiles)
+        if (t > 0x7FFFFFFFull) {
+            if (bad_query) *bad_query = g.q0;
+            return ANSX_ERR_ARG;
+        }
+    return ANSX_OK;
+}
+
 // ansx_intersect_batch_dev (ansx_intersect_batch.h; the plan: ansx_plan.h, isb_plan): the headers
-// of the referenced containers in one round trip (batch_ranges_front) -> the groups -> per group (isb_group): its lists
+// of the referenced containers in one round trip (query_front) -> the groups -> per group (isb_group): its lists
 // decoded back to back into isectb_ids by the passes of ansx_decode_batch_dev, one segmented scan over all of them,
-// k_isectb_gather, then a round per non-driver list of its longest query -- k_isectb_match, k_dr_scan, k_isect_compact,
-// k_isectb_bounds, between the two candidate buffers behind the lists -- and one copy of the survivors to the caller.
+// k_isectb_gather, then a round per non-driver list of its longest query -- k_isectb_match and the compact step,
+// between the two candidate buffers behind the lists -- and one copy of the survivors to the caller.
 // Workspace: 4 bytes per int of the group's lists and 8 per int of its drivers (the budget bounds their sum unless one
 // query exceeds it alone), a pass's, the scan's 16 bytes per 4096 ints, IsectWork over the candidates, and per query 16
 // bytes of tables, 12 of segments and 16 per non-driver term.
@@ -3356,24 +3606,21 @@ int bool_exclude_step(ansx_ctx* c, const IsectWork& W, const u32* ids, const u32
 // grows with the number of queries.
 // A group of ansx_bool_batch_dev that excludes something (g.xt) adds its second table to the upload and, where the
 // rounds leave candidates, bool_exclude_step and ONE wait behind it; without g.xt nothing here differs.
-int isb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& g, std::vector<u64>& off, size_t count,
-    u32* d_out, size_t cap, u64* run, u64* out_offsets, size_t* bad_container, hipStream_t s)
+int isb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, IdsOut& out, size_t* bad_container, hipStream_t s)
 {
     int rc;
     const size_t Q = g.q1 - g.q0, q1 = rup(Q + 1, 4);
     const u64 L = g.at.back(), nc0 = g.G[Q].dst;
     if (nc0 == 0) {  // (every driver is empty: nothing to look up, nothing is decoded)
-        for (size_t j = 0; j <= Q; j++) out_offsets[g.q0 + j] = *run;
+        for (size_t j = 0; j <= Q; j++) out.offsets[g.q0 + j] = out.run;
         return ANSX_OK;
     }
     // the lists | two candidate buffers, each with the decoders' slack behind
     const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)nc0, 4) + 16;
     if ((rc = ensure(c, c->isectb_ids, 4 * (o_c + 2 * half)))) return rc;
     u32* ids = (u32*)c->isectb_ids.p;
-    u32* buf[2] = { ids + o_c, ids + o_c + half };
-    GeometryGroups geo;
-    for (size_t k = 0; k < g.lists.size(); k++) off[g.lists[k]] = g.at[k], geo[br_geometry(F.rs[g.lists[k]].H)].push_back(g.lists[k]);
-    if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, ids, bad_container, s))) return rc;
+    Flip buf = { { ids + o_c, ids + o_c + half } };
+    if ((rc = group_decode(c, F, g.lists, g.at, ids, nullptr, bad_container, s))) return rc;
 
     // one upload: zero flag words | queries | round table; behind it on the device: two arrays of segments | IsectWork
     Upload U;
@@ -3386,92 +3633,60 @@ int isb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& g,
     const auto s_xt = U.add<ansx_isb_list>(g.xt.size());
     const size_t up = U.end;
     const auto s_seg = U.add<u32>(2 * q1);  // (the host's copy: the last round's, read back)
-    const size_t o_w = rup(U.end, 16);
-    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, U.end))) return rc;
-    if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(nc0, false)))) return rc;
-    U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
-    memset(U.pin(s_fl), 0, s_fl.bytes);
+    GroupWs ws;
+    if ((rc = group_room(c, U, U.end, nc0, s_fl, nullptr, &ws))) return rc;
     U.put(s_g, g.G.data()), U.put(s_ro, g.rt_off.data());
     if (!g.rt.empty()) U.put(s_rt, g.rt.data());
     if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
-    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
-    u32* seg[2] = { U.dev(s_seg), U.dev(s_seg) + q1 };
+    if ((rc = group_upload(c, U, up, nullptr, s))) return rc;
+    Flip seg = { { U.dev(s_seg), U.dev(s_seg) + q1 } };
     const u32* zero = U.dev(s_fl);
 
     SumsPlan S;
-    if ((rc = sums_prepare(c, (uintptr_t)ids, L, g.at.data(), g.lists.size(), s, &S))) return rc;
-    if ((rc = sums_launch(c, ids, L, g.lists.size(), S, s))) return rc;
-    LAUNCH(c, "k_isectb_gather", k_isectb_gather, (u32)((std::max<u64>(nc0, Q + 1) + ANSX_ISECT_TILE - 1) / ANSX_ISECT_TILE),
-        ANSX_ISECT_NT, 0, s, (const u32*)ids, (const ansx_isb_query*)U.dev(s_g), (u32)Q, buf[0], (u32)nc0, seg[0], (const u32*)S.flag);
-    u32* hflag = &c->pin->isect_sflag;
-    HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
+    if ((rc = group_scan(c, ids, g.at, s, &S))) return rc;
+    if ((rc = gather_drivers(c, ids, U.dev(s_g), Q, nc0, buf.from(), seg.from(), S.flag, s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(ws.sflag, S.flag, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (*hflag != ANSX_SS_NONE) {  // the first list of the buffer whose sum left 32 bits
-        if (bad_container && *hflag < g.lists.size()) *bad_container = F.ref[g.lists[*hflag]];
-        return ANSX_ERR_DOMAIN;
-    }
+    if ((rc = scan_flag_status(ws, g.lists, *F.index, bad_container))) return rc;
 
-    u32 nc = (u32)nc0, cur = 0, r = 0;
+    u32 nc = (u32)nc0, r = 0;
     for (; r < g.rounds && nc > 0; r++) {
-        const IsectWork W(U.devp + o_w, nc, false);
-        LAUNCH(c, "k_isectb_match", k_isectb_match, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)buf[cur], nc,
-            (const u32*)seg[cur], (u32)Q, (const u32*)U.dev(s_ro), (const ansx_isb_list*)U.dev(s_rt), r, W.ballots, W.counts);
-        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
-        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)buf[cur], nc, (const u64*)W.ballots,
-            (const u64*)W.counts, (const u64*)W.total, (u64)nc, (const u64*)nullptr, buf[1 - cur], (u32*)nullptr, (u64*)nullptr, zero, zero);
-        LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, (const u32*)seg[cur], (u32)Q, nc,
-            (const u64*)W.ballots, (const u64*)W.counts, (const u64*)W.total, seg[1 - cur]);
-        HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
-        if (r + 1 == g.rounds) HIPCHK(c, hipMemcpyAsync(U.pin(s_seg), seg[1 - cur], 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+        const IsectWork W(ws.work, nc, false);
+        LAUNCH(c, "k_isectb_match", k_isectb_match, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)buf.from(), nc,
+            (const u32*)seg.from(), (u32)Q, (const u32*)U.dev(s_ro), (const ansx_isb_list*)U.dev(s_rt), r, W.ballots, W.counts);
+        if ((rc = compact_step(c, W, nc, { buf.from(), buf.to(), nullptr }, nullptr, seg.from(), Q, seg.to(), zero, zero, s))) return rc;
+        HIPCHK(c, hipMemcpyAsync(ws.total, W.total, 8, hipMemcpyDeviceToHost, s));
+        if (r + 1 == g.rounds) HIPCHK(c, hipMemcpyAsync(U.pin(s_seg), seg.to(), 4 * (Q + 1), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        nc = (u32)c->pin->isect_total, cur = 1 - cur;
+        nc = (u32)*ws.total, buf.flip(), seg.flip();
     }
     const bool xran = excl && nc > 0;
     if (xran) {  // ONE exclusion step over what the rounds left (ansx_bool.h), and one more wait
-        const IsectWork W(U.devp + o_w, nc, false);
-        if ((rc = bool_exclude_step(c, W, ids, buf[cur], nc, nullptr, seg[cur], Q, U.dev(s_xo), U.dev(s_xt), (const u32*)S.flag,
-                 buf[1 - cur], seg[1 - cur], zero, zero, s)))
+        const IsectWork W(ws.work, nc, false);
+        if ((rc = bool_exclude_step(c, W, ids, { buf.from(), buf.to(), nullptr }, nc, nullptr, seg.from(), Q, U.dev(s_xo), U.dev(s_xt),
+                 S.flag, seg.to(), zero, zero, s)))
             return rc;
-        HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(U.pin(s_seg), seg[1 - cur], 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(ws.total, W.total, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(U.pin(s_seg), seg.to(), 4 * (Q + 1), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        nc = (u32)c->pin->isect_total, cur = 1 - cur;
+        nc = (u32)*ws.total, buf.flip(), seg.flip();
     }
     // the segments behind the last step: the drivers' (none), what came back, or nothing left
     const u32* hseg = U.pin(s_seg);
     for (size_t j = 0; j <= Q; j++)
-        out_offsets[g.q0 + j] = *run + (xran ? hseg[j] : g.rounds == 0 ? g.G[j].dst : r == g.rounds ? hseg[j] : 0);
-    if (nc > 0 && *run + nc <= cap) HIPCHK(c, hipMemcpyAsync(d_out + *run, buf[cur], 4 * (size_t)nc, hipMemcpyDeviceToDevice, s));
-    *run += nc;
+        out.offsets[g.q0 + j] = out.run + (xran ? hseg[j] : g.rounds == 0 ? g.G[j].dst : r == g.rounds ? hseg[j] : 0);
+    if (nc > 0 && out.run + nc <= out.cap)
+        HIPCHK(c, hipMemcpyAsync(out.ids + out.run, buf.from(), 4 * (size_t)nc, hipMemcpyDeviceToDevice, s));
+    out.run += nc;
     return ANSX_OK;
-}
-
-int intersect_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count, const u32* terms,
-    const u64* qoff, size_t nq, u32* d_out, size_t cap, u64* out_offsets, size_t* bad_container, size_t* bad_query, hipStream_t s)
-{
-    int rc;
-    BrFront F;
-    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, terms, (size_t)qoff[nq], nullptr, &F, bad_container, s))) return rc;
-    std::vector<u64> n(F.ref.size());
-    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
-    std::vector<IsbGroup> groups;
-    const u64 budget = c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT;
-    if ((rc = isb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, &groups, bad_query))) return rc;
-    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
-    u64 run = 0;
-    for (const IsbGroup& g : groups)
-        if ((rc = isb_group(c, kind, f, F, g, off, count, d_out, cap, &run, out_offsets, bad_container, s))) return rc;
-    HIPCHK(c, hipStreamSynchronize(s));  // (the copies)
-    return run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
 }
 
 // ansx_union_batch_dev (ansx_union.h; the plan: ansx_plan.h, unb_plan): the front end of
 // ansx_intersect_batch_dev -- the headers of the referenced containers in one round trip, the groups -> per group
 // (unb_group): its lists decoded back to back into isectb_ids and scanned into ids, one upload of every round's pair
 // table, a launch of k_union_merge per round between the two merge buffers behind the lists, then the unique step over
-// the last round's buffer -- k_union_heads, k_dr_scan, k_isect_compact into the other buffer, k_isectb_bounds and, with
-// counts, k_union_counts -- and one copy per output to the caller.  The context's buffers are those of
-// ansx_intersect_batch_dev (a context runs one call at a time).
+// the last round's buffer into the other and, with counts, k_union_counts -- and one copy per output to the caller.  The
+// context's buffers are those of ansx_intersect_batch_dev (a context runs one call at a time).
 // Workspace: 4 bytes per int of the group's lists and 8 per int of its queries' lists as named (16 with counts: the
 // heads' positions and the counts), a pass's, the scan's, IsectWork over the merge buffer, and 8 bytes per query and 40
 // per pair of tables -- fewer than two pairs per term.
@@ -3480,31 +3695,24 @@ int intersect_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
 // the plan's.  One behind the copies, per call.  None grows with the queries or the rounds.
 // A group of ansx_bool_batch_dev that excludes something (g.xt) adds its second table to the upload and
 // bool_exclude_step in front of that one wait (the heads' count stays on the device); without g.xt nothing here differs.
-int unb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g, std::vector<u64>& off, size_t count,
-    u32* d_out, u32* d_cnt, size_t cap, u64* run, u64* out_offsets, size_t* bad_container, size_t* bad_query, hipStream_t s)
+int unb_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, IdsOut& out, size_t* bad_container, size_t* bad_query, hipStream_t s)
 {
     int rc;
     const size_t Q = g.q1 - g.q0, q1 = rup(Q + 1, 4);
     const u64 L = g.at.back(), M = g.seg[Q];
     if (M == 0) {  // (every list is empty: nothing is decoded)
-        for (size_t j = 0; j <= Q; j++) out_offsets[g.q0 + j] = *run;
+        for (size_t j = 0; j <= Q; j++) out.offsets[g.q0 + j] = out.run;
         return ANSX_OK;
     }
-    for (const u64 t : g.tiles)
-        if (t > 0x7FFFFFFFull) {  // (a grid; 2^31 non-empty pairs in a round)
-            if (bad_query) *bad_query = g.q0;
-            return ANSX_ERR_ARG;
-        }
+    if ((rc = merge_tiles_check(g, bad_query))) return rc;
     // the lists | two merge buffers | with counts: the heads' positions | the counts; each with the decoders' slack behind
     const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)M, 4) + 16;
-    if ((rc = ensure(c, c->isectb_ids, 4 * (o_c + (d_cnt ? 4 : 2) * half)))) return rc;
+    if ((rc = ensure(c, c->isectb_ids, 4 * (o_c + (out.cnt ? 4 : 2) * half)))) return rc;
     u32* ids = (u32*)c->isectb_ids.p;
-    u32* buf[2] = { ids + o_c, ids + o_c + half };
-    u32* idx = d_cnt ? ids + o_c + 2 * half : nullptr;
-    u32* cnt = d_cnt ? ids + o_c + 3 * half : nullptr;
-    GeometryGroups geo;
-    for (size_t k = 0; k < g.lists.size(); k++) off[g.lists[k]] = g.at[k], geo[br_geometry(F.rs[g.lists[k]].H)].push_back(g.lists[k]);
-    if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, ids, bad_container, s))) return rc;
+    u32* const mb[2] = { ids + o_c, ids + o_c + half };
+    u32* idx = out.cnt ? ids + o_c + 2 * half : nullptr;
+    u32* cnt = out.cnt ? ids + o_c + 3 * half : nullptr;
+    if ((rc = group_decode(c, F, g.lists, g.at, ids, nullptr, bad_container, s))) return rc;
 
     // one upload: zero flag words (k_isect_compact's four, k_union_heads' one) | the queries' spans | every round's pairs;
     // behind it on the device: the bounds among the heads | IsectWork
@@ -3518,123 +3726,83 @@ int unb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g,
     const size_t up = U.end;
     const auto s_hs = U.add<u32>(q1);  // (the host's copy: read back)
     const auto s_xs = U.add<u32>(excl ? q1 : 0);  // (the bounds behind the exclusion step)
-    const size_t o_w = rup(U.end, 16);
-    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, U.end))) return rc;
-    if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(M, false)))) return rc;
-    U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
-    memset(U.pin(s_fl), 0, s_fl.bytes);
+    GroupWs ws;
+    if ((rc = group_room(c, U, U.end, M, s_fl, nullptr, &ws))) return rc;
     U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
     if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
-    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
+    if ((rc = group_upload(c, U, up, nullptr, s))) return rc;
     const u32* zero = U.dev(s_fl);
     u32* uflag = U.dev(s_fl) + 4;
     const u32* seg = U.dev(s_seg);
-    u32* hseg = U.dev(s_hs);
 
     SumsPlan S;
-    if ((rc = sums_prepare(c, (uintptr_t)ids, L, g.at.data(), g.lists.size(), s, &S))) return rc;
-    if ((rc = sums_launch(c, ids, L, g.lists.size(), S, s))) return rc;
+    if ((rc = group_scan(c, ids, g.at, s, &S))) return rc;
     for (u32 r = 0; r < g.rounds; r++) {
         const u32 np = g.roff[r + 1] - g.roff[r];
         if (np == 0) continue;  // (the queries that have this round are empty)
-        LAUNCH(c, "k_union_merge", k_union_merge, (u32)g.tiles[r], ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)buf[1 - (r & 1u)],
-            buf[r & 1u], (const ansx_unb_pair*)U.dev(s_p) + g.roff[r], np, (const u32*)S.flag);
+        const u32* from = mb[1 - (r & 1u)];
+        LAUNCH(c, "k_union_merge", k_union_merge, (u32)g.tiles[r], ANSX_ISECT_NT, 0, s, (const u32*)ids, from, mb[r & 1u],
+            (const ansx_unb_pair*)U.dev(s_p) + g.roff[r], np, (const u32*)S.flag);
     }
-    const u32 fin = (g.rounds - 1u) & 1u;
-    const IsectWork W(U.devp + o_w, M, false);
-    LAUNCH(c, "k_union_heads", k_union_heads, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)buf[fin], (u32)M, seg, (u32)Q, W.ballots,
-        W.counts, (const u32*)S.flag, uflag);
-    LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
-    LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)buf[fin], (u32)M, (const u64*)W.ballots,
-        (const u64*)W.counts, (const u64*)W.total, M, (const u64*)nullptr, buf[1 - fin], idx, (u64*)nullptr, zero, (const u32*)uflag);
-    LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, seg, (u32)Q, (u32)M, (const u64*)W.ballots,
-        (const u64*)W.counts, (const u64*)W.total, hseg);
-    if (d_cnt)
-        LAUNCH(c, "k_union_counts", k_union_counts, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)idx, (const u32*)hseg, seg, (u32)Q,
+    u32 *merged = mb[(g.rounds - 1u) & 1u], *heads = mb[g.rounds & 1u];  // (what the last round wrote, and the other buffer)
+    const IsectWork W(ws.work, M, false);
+    const u32* hseg = U.dev(s_hs);
+    if ((rc = unique_step(c, W, { merged, heads, idx }, (u32)M, seg, Q, S.flag, uflag, U.dev(s_hs), zero, s))) return rc;
+    if (out.cnt)
+        LAUNCH(c, "k_union_counts", k_union_counts, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)idx, hseg, seg, (u32)Q,
             (const u64*)W.total, (u32)M, cnt, (const u32*)S.flag);
-    u32* res = buf[1 - fin];
+    const u32* res = heads;
     if (excl) {  // ONE exclusion step over the heads (ansx_bool.h): their count stays on the device, no wait is added
-        if ((rc = bool_exclude_step(c, W, ids, buf[1 - fin], (u32)M, W.total, hseg, Q, U.dev(s_xo), U.dev(s_xt), (const u32*)S.flag,
-                 buf[fin], U.dev(s_xs), zero, uflag, s)))
+        if ((rc = bool_exclude_step(c, W, ids, { heads, merged, nullptr }, (u32)M, W.total, hseg, Q, U.dev(s_xo), U.dev(s_xt), S.flag,
+                 U.dev(s_xs), zero, uflag, s)))
             return rc;
-        hseg = U.dev(s_xs), res = buf[fin];
+        hseg = U.dev(s_xs), res = merged;
     }
-    u32* hflag = &c->pin->isect_sflag;
-    HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(ws.sflag, S.flag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(ws.total, W.total, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(U.pin(s_hs), hseg, 4 * (Q + 1), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (*hflag != ANSX_SS_NONE) {  // the first list of the buffer whose sum left 32 bits
-        if (bad_container && *hflag < g.lists.size()) *bad_container = F.ref[g.lists[*hflag]];
-        return ANSX_ERR_DOMAIN;
-    }
-    const u64 nu = c->pin->isect_total;
+    if ((rc = scan_flag_status(ws, g.lists, *F.index, bad_container))) return rc;
+    const u64 nu = *ws.total;
     const u32* hs = U.pin(s_hs);
-    for (size_t j = 0; j <= Q; j++) out_offsets[g.q0 + j] = *run + hs[j];
-    if (nu > 0 && *run + nu <= cap) {
-        HIPCHK(c, hipMemcpyAsync(d_out + *run, res, 4 * (size_t)nu, hipMemcpyDeviceToDevice, s));
-        if (d_cnt) HIPCHK(c, hipMemcpyAsync(d_cnt + *run, cnt, 4 * (size_t)nu, hipMemcpyDeviceToDevice, s));
+    for (size_t j = 0; j <= Q; j++) out.offsets[g.q0 + j] = out.run + hs[j];
+    if (nu > 0 && out.run + nu <= out.cap) {
+        HIPCHK(c, hipMemcpyAsync(out.ids + out.run, res, 4 * (size_t)nu, hipMemcpyDeviceToDevice, s));
+        if (out.cnt) HIPCHK(c, hipMemcpyAsync(out.cnt + out.run, cnt, 4 * (size_t)nu, hipMemcpyDeviceToDevice, s));
     }
-    *run += nu;
+    out.run += nu;
     return ANSX_OK;
 }
 
-int union_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count, const u32* terms,
-    const u64* qoff, size_t nq, u32* d_out, u32* d_cnt, size_t cap, u64* out_offsets, size_t* bad_container, size_t* bad_query,
-    hipStream_t s)
-{
-    int rc;
-    BrFront F;
-    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, terms, (size_t)qoff[nq], nullptr, &F, bad_container, s))) return rc;
-    std::vector<u64> n(F.ref.size());
-    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
-    std::vector<UnbGroup> groups;
-    const u64 budget = c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT;
-    if ((rc = unb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query))) return rc;
-    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
-    u64 run = 0;
-    for (const UnbGroup& g : groups)
-        if ((rc = unb_group(c, kind, f, F, g, off, count, d_out, d_cnt, cap, &run, out_offsets, bad_container, bad_query, s))) return rc;
-    HIPCHK(c, hipStreamSynchronize(s));  // (the copies)
-    return run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
-}
-
-// ansx_bool_batch_dev (ansx_bool.h): the front end of the two calls above over the terms followed
-// by the excluded terms -- still one round trip for the headers -- then the plan of the chosen op with the excluded
-// lists (plan_excl_tables) and the op's own groups, which run the exclusion step where a group excludes something.
-// Workspace: the parent's, the excluded lists among the group's lists, and 4 bytes per query and 16 per excluded term
+// ansx_bool_batch_dev (ansx_bool.h) and, as its cases without excluded terms,
+// ansx_intersect_batch_dev (op ALL) and ansx_union_batch_dev (op ANY; d_cnt: its counts, null for the other two).  The
+// front end over the terms followed by the excluded terms -- still one round trip for the headers -- then the plan of
+// the chosen op with the excluded lists (plan_excl_tables) and the op's own groups, which run the exclusion step where
+// a group excludes something.
+// Workspace: the op's, the excluded lists among the group's lists, and 4 bytes per query and 16 per excluded term
 // of tables (ANY: 4 more per query of bounds).  Host waits: ALL one more per group that excludes something and has
 // candidates left behind its rounds; ANY none more -- the heads' count stays on the device.
 int bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, size_t count, int op, const u32* terms,
-    const u64* qoff, const u32* xterms, const u64* xqoff, size_t nq, u32* d_out, size_t cap, u64* out_offsets, size_t* bad_container,
-    size_t* bad_query, hipStream_t s)
+    const u64* qoff, const u32* xterms, const u64* xqoff, size_t nq, u32* d_out, u32* d_cnt, size_t cap, u64* out_offsets,
+    size_t* bad_container, size_t* bad_query, hipStream_t s)
 {
     int rc;
-    const size_t nt = (size_t)qoff[nq], nx = xqoff ? (size_t)xqoff[nq] : 0;
-    std::vector<u32> all(terms, terms + nt);
-    if (nx) all.insert(all.end(), xterms, xterms + nx);
-    BrFront F;
-    if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, all.data(), all.size(), nullptr, &F, bad_container, s))) return rc;
-    std::vector<u64> n(F.ref.size());
-    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
-    const u32* xrid = F.rid.data() + nt;
-    const u64 budget = c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT;
-    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
-    u64 run = 0;
+    QueryFront F;
+    if ((rc = query_front(c, kind, f, d_ins, in_bytes, nullptr, nullptr, count, terms, (size_t)qoff[nq], xterms,
+             xqoff ? (size_t)xqoff[nq] : 0, &F, bad_container, s)))
+        return rc;
+    const u64 budget = query_budget(c, false);
+    IdsOut out = { d_out, d_cnt, cap, 0, out_offsets };
     if (op == ANSX_BOOL_ALL) {
         std::vector<IsbGroup> groups;
-        if ((rc = isb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, &groups, bad_query, xrid, xqoff))) return rc;
-        for (const IsbGroup& g : groups)
-            if ((rc = isb_group(c, kind, f, F, g, off, count, d_out, cap, &run, out_offsets, bad_container, s))) return rc;
+        if ((rc = isb_plan(F.n.data(), F.n.size(), F.rid, qoff, nq, budget, &groups, bad_query, F.xrid, xqoff))) return rc;
+        rc = run_groups(c, groups, [&](const IsbGroup& g) { return isb_group(c, F, g, out, bad_container, s); }, s);
     } else {
         std::vector<UnbGroup> groups;
-        if ((rc = unb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query, xrid, xqoff))) return rc;
-        for (const UnbGroup& g : groups)
-            if ((rc = unb_group(c, kind, f, F, g, off, count, d_out, nullptr, cap, &run, out_offsets, bad_container, bad_query, s)))
-                return rc;
+        if ((rc = unb_plan(F.n.data(), F.n.size(), F.rid, qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query, F.xrid, xqoff))) return rc;
+        rc = run_groups(c, groups, [&](const UnbGroup& g) { return unb_group(c, F, g, out, bad_container, bad_query, s); }, s);
     }
-    HIPCHK(c, hipStreamSynchronize(s));  // (the copies)
-    return run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
+    return rc ? rc : out.run > cap ? ANSX_ERR_CAPACITY : ANSX_OK;
 }
 
 // ansx_topk_batch_dev (ansx_topk.h; the plan: unb_plan with the terms behind its pairs).  The front
@@ -3642,8 +3810,8 @@ int bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_
 // referenced ones at 2u, its payload at 2u + 1), still one round trip for the headers; the groups of unb_plan under HALF
 // the budget -- a group holds twice what a union's does; per group (topk_group): ids and payloads decoded with the same
 // offsets into two buffers of one layout, the scan over the ids, one upload of the pair and weight tables, a launch of
-// k_topk_merge per round, the unique step as in unb_group (with positions), k_topk_scores, the eight rounds of
-// k_topk_hist / k_topk_pick, k_topk_gather and k_topk_sort, which writes the caller's arrays.
+// k_topk_merge per round, the unique step as in unb_group (with positions), k_topk_scores and the ranked tail: the eight
+// rounds of k_topk_hist / k_topk_pick, k_topk_gather and k_topk_sort, which writes the caller's arrays.
 // Workspace: 4 (8 with payloads) bytes per int of the group's lists, 20 per int of its queries' lists as named (two key and
 // two value merge buffers, the scores), a pass's, the scan's, IsectWork over the merge buffer, and per query 8 k bytes of
 // slots, 1 KiB of histogram, 24 bytes of state and bounds and 48 per pair of tables.
@@ -3656,86 +3824,93 @@ struct TopkOut {
     u32 *ids, *scores, *counts;
     bool pays;
     // ansx_topk_bool_batch_dev: the overflow word is lowered by k_topkb_check, behind the exclusion
-    // step; payof: where the payload of referenced list r stands (ANSX_TOPK_NONE: a list that is only excluded has none;
-    // null: at r + 1); form: ANSX_TOPKB_FORM_*
-    bool check = false;
-    const std::vector<u32>* payof = nullptr;
-    u32 form = 0;
+    // step; form: ANSX_TOPKB_FORM_*
+    bool check;
+    u32 form;
 };
-
-// The payloads of a group's lists into `pay`, laid out as its ids are
-template <class Group> int topk_decode_payloads(ansx_ctx* c, int kind, int f, const BrFront& F, const Group& g, std::vector<u64>& off,
-    size_t count, const TopkOut& o, u32* pay, size_t* bad_container, hipStream_t s)
-{
-    GeometryGroups geo;
-    for (size_t i = 0; i < g.lists.size(); i++) {
-        const u32 r = o.payof ? (*o.payof)[g.lists[i]] : g.lists[i] + 1u;
-        if (r == ANSX_TOPK_NONE) continue;  // (only excluded: no payload is read)
-        off[r] = g.at[i], geo[br_geometry(F.rs[r].H)].push_back(r);
-    }
-    return batch_decode_groups(c, kind, f, F.rs, off, geo, count, pay, bad_container, s);
-}
 
 // The select of a ranked call over the candidates (ids[h], score[h]), h < min(*total, n), query j's in [hseg[j], hseg[j + 1]),
 // all on the device: the eight rounds of k_topk_hist / k_topk_pick, k_topk_gather and k_topk_sort, which writes the
-// caller's arrays.  ntiles: the tiles of n.  cur and hist are zero.  Enqueues only.
-struct TopkSelect {
-    u64* pre;
-    u32 *want, *cur, *hist;
-    u64* slots;
+// caller's arrays.  ntiles: the tiles of n.  T: the select state in U (select_sections), cleared; slots: 8 k bytes per query.
+struct Ranked {
+    const u32 *ids, *score, *hseg;
+    const u64* total;
+    u32 n, ntiles;
 };
-int topk_select(ansx_ctx* c, const u32* ids, const u32* score, const u32* hseg, size_t Q, const u64* total, u32 n, u32 ntiles,
-    const TopkSelect& T, size_t q0, const TopkOut& o, const u32* sflag, hipStream_t s)
+int topk_select(ansx_ctx* c, const Ranked& R, size_t Q, const Upload& U, const SelectSecs& T, u64* slots, size_t q0, const TopkOut& o,
+    const u32* sflag, hipStream_t s)
 {
     for (u32 r = 0; r < ANSX_TOPK_ROUNDS; r++) {
-        LAUNCH(c, "k_topk_hist", k_topk_hist, ntiles, ANSX_ISECT_NT, 0, s, ids, score, hseg, (u32)Q, total, n, r, (const u64*)T.pre, T.hist,
-            sflag);
-        LAUNCH(c, "k_topk_pick", k_topk_pick, (u32)((Q + 3) / 4), 256, 0, s, hseg, (u32)Q, o.k, r, T.pre, T.want, T.hist, sflag);
+        LAUNCH(c, "k_topk_hist", k_topk_hist, R.ntiles, ANSX_ISECT_NT, 0, s, R.ids, R.score, R.hseg, (u32)Q, R.total, R.n, r,
+            (const u64*)U.dev(T.pre), U.dev(T.hist), sflag);
+        LAUNCH(c, "k_topk_pick", k_topk_pick, (u32)((Q + 3) / 4), 256, 0, s, R.hseg, (u32)Q, o.k, r, U.dev(T.pre), U.dev(T.want),
+            U.dev(T.hist), sflag);
     }
-    LAUNCH(c, "k_topk_gather", k_topk_gather, ntiles, ANSX_ISECT_NT, 0, s, ids, score, hseg, (u32)Q, total, n, o.k, (const u64*)T.pre, T.cur,
-        T.slots, sflag);
-    LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)T.slots, hseg, (u64)q0, o.k, o.pow2, o.ids, o.scores, sflag);
+    LAUNCH(c, "k_topk_gather", k_topk_gather, R.ntiles, ANSX_ISECT_NT, 0, s, R.ids, R.score, R.hseg, (u32)Q, R.total, R.n, o.k,
+        (const u64*)U.dev(T.pre), U.dev(T.cur), slots, sflag);
+    LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)slots, R.hseg, (u64)q0, o.k, o.pow2, o.ids, o.scores, sflag);
     return ANSX_OK;
 }
-int topk_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g, std::vector<u64>& off, size_t count,
-    const TopkOut& o, const std::function<size_t(u32)>& batch_index, size_t* bad_container, size_t* bad_query, hipStream_t s)
+
+// ... the ranked tail over the candidates R of queries q0 .. q0 + Q: k_topkb_check when the call asks for it (it lowers
+// the overflow word s_of over the scores that are left), the select, and the overflow word and the bounds on their way
+// home to the upload page (the bounds to s_back) -- in front of them the scan's flag word, to h_sflag, where the host
+// has not seen it yet (null: it has).  The caller waits; ranked_counts reads what came.
+int ranked_tail(ansx_ctx* c, const Ranked& R, size_t Q, size_t q0, const TopkOut& o, const Upload& U, const SelectSecs& T, u64* slots,
+    Upload::Sec<u32> s_of, Upload::Sec<u32> s_back, const u32* sflag, u32* h_sflag, hipStream_t s)
+{
+    int rc;
+    if (o.check)
+        LAUNCH(c, "k_topkb_check", k_topkb_check, R.ntiles, ANSX_ISECT_NT, 0, s, R.score, R.hseg, (u32)Q, R.total, R.n, U.dev(s_of), sflag);
+    if ((rc = topk_select(c, R, Q, U, T, slots, q0, o, sflag, s))) return rc;
+    if (h_sflag) HIPCHK(c, hipMemcpyAsync(h_sflag, sflag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(U.pin(s_of), U.dev(s_of), 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(U.pin(s_back), R.hseg, 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+    return ANSX_OK;
+}
+// the first query of the group with a score of 2^32 - 1 or more among its results -> ANSX_ERR_DOMAIN; else the counts
+int ranked_counts(const u32* h_of, const u32* h_seg, size_t Q, size_t q0, const TopkOut& o, size_t* bad_query)
+{
+    if (h_of[0] != ANSX_TOPK_NONE) {
+        if (bad_query) *bad_query = q0 + h_of[0];
+        return ANSX_ERR_DOMAIN;
+    }
+    if (o.counts)
+        for (size_t j = 0; j < Q; j++) o.counts[q0 + j] = std::min<u32>(o.k, h_seg[j + 1] - h_seg[j]);
+    return ANSX_OK;
+}
+// no query of the group has a result: every slot is ANSX_NO_ID / 0
+int ranked_nothing(ansx_ctx* c, size_t Q, size_t q0, const TopkOut& o, hipStream_t s)
+{
+    LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)nullptr, (const u32*)nullptr, (u64)q0, o.k, o.pow2,
+        o.ids, o.scores, (const u32*)nullptr);
+    if (o.counts) memset(o.counts + q0, 0, 4 * Q);
+    return ANSX_OK;
+}
+
+int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, size_t* bad_container, size_t* bad_query, hipStream_t s)
 {
     int rc;
     const size_t Q = g.q1 - g.q0, q1 = rup(Q + 1, 4);
     const u64 L = g.at.back(), M = g.seg[Q];
-    const u32 k = o.k;
-    if (M == 0) {  // (every list is empty: nothing is decoded, every slot is ANSX_NO_ID / 0)
-        LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)nullptr, (const u32*)nullptr, (u64)g.q0, k, o.pow2,
-            o.ids, o.scores, (const u32*)nullptr);
-        if (o.counts) memset(o.counts + g.q0, 0, 4 * Q);
-        return ANSX_OK;
-    }
-    for (const u64 t : g.tiles)
-        if (t > 0x7FFFFFFFull) {  // (a grid; 2^31 non-empty pairs in a round)
-            if (bad_query) *bad_query = g.q0;
-            return ANSX_ERR_ARG;
-        }
+    if (M == 0) return ranked_nothing(c, Q, g.q0, o, s);  // (every list is empty: nothing is decoded)
+    if ((rc = merge_tiles_check(g, bad_query))) return rc;
     // the lists | their payloads | two key and two value merge buffers | the scores | the slots (u64: at an even int); each
     // with the decoders' slack behind
     const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)M, 4) + 16;
     const size_t o_m = (o.pays ? 2 : 1) * o_c, o_s = o_m + 5 * half;
-    if ((rc = ensure(c, c->isectb_ids, 4 * o_s + 8 * Q * (size_t)k))) return rc;
+    if ((rc = ensure(c, c->isectb_ids, 4 * o_s + 8 * Q * (size_t)o.k))) return rc;
     u32* ids = (u32*)c->isectb_ids.p;
     u32* pay = o.pays ? ids + o_c : nullptr;
-    u32* kb[2] = { ids + o_m, ids + o_m + half };
-    u32* vb[2] = { ids + o_m + 2 * half, ids + o_m + 3 * half };
+    u32* const kb[2] = { ids + o_m, ids + o_m + half };
+    u32* const vb[2] = { ids + o_m + 2 * half, ids + o_m + 3 * half };
     u32* score = ids + o_m + 4 * half;
     u64* slots = (u64*)(ids + o_s);
-    GeometryGroups geo;
-    for (size_t i = 0; i < g.lists.size(); i++) off[g.lists[i]] = g.at[i], geo[br_geometry(F.rs[g.lists[i]].H)].push_back(g.lists[i]);
-    if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, ids, bad_container, s))) return rc;
-    // (the payload of referenced list r stands at r + 1: the same n, any geometry)
-    if (o.pays && (rc = topk_decode_payloads(c, kind, f, F, g, off, count, o, pay, bad_container, s))) return rc;
+    if ((rc = group_decode(c, F, g.lists, g.at, ids, pay, bad_container, s))) return rc;
 
     // one upload: zero flag words (k_isect_compact's four, k_union_heads' one) | the overflow word | the queries' spans |
     // every round's pairs | their weights | with exclusions (ansx_topk_bool_batch_dev) the second table; behind it on the
-    // device: the bounds among the heads | those behind the exclusion step | prefixes | what is left to find | cursors |
-    // histograms | IsectWork
+    // device: the bounds among the heads | those behind the exclusion step | the select state | IsectWork
     Upload U;
     const auto s_fl = U.add<u32>(8);
     const auto s_of = U.add<u32>(4);
@@ -3748,130 +3923,49 @@ int topk_group(ansx_ctx* c, int kind, int f, const BrFront& F, const UnbGroup& g
     const size_t up = U.end;
     const auto s_hs = U.add<u32>(q1);  // (the host's copy: read back)
     const auto s_xs = U.add<u32>(excl ? q1 : 0);
-    const auto s_pre = U.add<u64>(Q);
-    const auto s_want = U.add<u32>(Q);
-    const auto s_cur = U.add<u32>(rup(Q, 4));  // (cleared with the histograms behind it)
-    const auto s_hist = U.add<u32>(Q * (size_t)ANSX_TOPK_BINS);
-    const size_t o_w = rup(U.end, 16);
-    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, s_hs.off + s_hs.bytes))) return rc;  // (what the host reads or writes)
-    if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(M, false)))) return rc;
-    U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
-    memset(U.pin(s_fl), 0, s_fl.bytes);
-    u32* hof = U.pin(s_of);
-    hof[0] = ANSX_TOPK_NONE, hof[1] = hof[2] = hof[3] = 0;
+    const SelectSecs s_sel = select_sections(U, Q);
+    GroupWs ws;
+    if ((rc = group_room(c, U, s_hs.off + s_hs.bytes, M, s_fl, &s_of, &ws))) return rc;
     U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
     if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
     u32* hw = U.pin(s_w);
     for (size_t i = 0; i < g.pterm.size(); i++) hw[i] = g.pterm[i] == ANSX_TOPK_NONE ? 0u : o.weights[g.pterm[i]];
-    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(U.dev(s_cur), 0, s_hist.off + s_hist.bytes - s_cur.off, s));
+    if ((rc = group_upload(c, U, up, &s_sel, s))) return rc;
     const u32* zero = U.dev(s_fl);
     u32* uflag = U.dev(s_fl) + 4;
     const u32* seg = U.dev(s_seg);
-    u32* hseg = U.dev(s_hs);
 
     SumsPlan S;
-    if ((rc = sums_prepare(c, (uintptr_t)ids, L, g.at.data(), g.lists.size(), s, &S))) return rc;
-    if ((rc = sums_launch(c, ids, L, g.lists.size(), S, s))) return rc;
+    if ((rc = group_scan(c, ids, g.at, s, &S))) return rc;
     for (u32 r = 0; r < g.rounds; r++) {
         const u32 np = g.roff[r + 1] - g.roff[r];
         if (np == 0) continue;  // (the queries that have this round are empty)
-        LAUNCH(c, "k_topk_merge", k_topk_merge, (u32)g.tiles[r], ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)pay,
-            (const u32*)kb[1 - (r & 1u)], (const u32*)vb[1 - (r & 1u)], kb[r & 1u], vb[r & 1u],
-            (const ansx_unb_pair*)U.dev(s_p) + g.roff[r], (const u32*)U.dev(s_w) + 2 * (size_t)g.roff[r], np, (const u32*)S.flag);
+        const u32 to = r & 1u, from = 1 - to;
+        LAUNCH(c, "k_topk_merge", k_topk_merge, (u32)g.tiles[r], ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)pay, (const u32*)kb[from],
+            (const u32*)vb[from], kb[to], vb[to], (const ansx_unb_pair*)U.dev(s_p) + g.roff[r],
+            (const u32*)U.dev(s_w) + 2 * (size_t)g.roff[r], np, (const u32*)S.flag);
     }
+    // what the last round wrote, and the other pair of buffers: the heads' ids and positions go where it read
     const u32 fin = (g.rounds - 1u) & 1u;
-    u32 *hid = kb[1 - fin], *idx = vb[1 - fin];  // the heads' ids and positions: where the last round read
-    const IsectWork W(U.devp + o_w, M, false);
-    LAUNCH(c, "k_union_heads", k_union_heads, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)kb[fin], (u32)M, seg, (u32)Q, W.ballots,
-        W.counts, (const u32*)S.flag, uflag);
-    LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
-    LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)kb[fin], (u32)M, (const u64*)W.ballots,
-        (const u64*)W.counts, (const u64*)W.total, M, (const u64*)nullptr, hid, idx, (u64*)nullptr, zero, (const u32*)uflag);
-    LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, seg, (u32)Q, (u32)M, (const u64*)W.ballots,
-        (const u64*)W.counts, (const u64*)W.total, hseg);
+    u32 *merged = kb[fin], *values = vb[fin], *heads = kb[1 - fin], *idx = vb[1 - fin];
+    const IsectWork W(ws.work, M, false);
+    if ((rc = unique_step(c, W, { merged, heads, idx }, (u32)M, seg, Q, S.flag, uflag, U.dev(s_hs), zero, s))) return rc;
     // (ansx_topk_bool_batch_dev: a score that leaves 32 bits may belong to an excluded id -- the scores' word is one that
     // nobody reads, and k_topkb_check lowers the real one over what the exclusion step leaves)
-    LAUNCH(c, "k_topk_scores", k_topk_scores, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)idx, (const u32*)vb[fin], (const u32*)hseg, seg,
-        (u32)Q, (const u64*)W.total, (u32)M, score, U.dev(s_of) + (o.check ? 1 : 0), (const u32*)S.flag);
+    LAUNCH(c, "k_topk_scores", k_topk_scores, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)idx, (const u32*)values, (const u32*)U.dev(s_hs),
+        seg, (u32)Q, (const u64*)W.total, (u32)M, score, U.dev(s_of) + (o.check ? 1 : 0), (const u32*)S.flag);
+    Ranked R = { heads, score, U.dev(s_hs), W.total, (u32)M, W.ntiles };
     if (excl) {  // ONE exclusion step over the heads, as in unb_group, and the scores moved by the same ballots: no wait
-        if ((rc = bool_exclude_step(c, W, ids, hid, (u32)M, W.total, hseg, Q, U.dev(s_xo), U.dev(s_xt), (const u32*)S.flag, kb[fin],
+        if ((rc = bool_exclude_step(c, W, ids, { heads, merged, nullptr }, (u32)M, W.total, R.hseg, Q, U.dev(s_xo), U.dev(s_xt), S.flag,
                  U.dev(s_xs), zero, uflag, s)))
             return rc;
-        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)score, (u32)M, (const u64*)W.ballots,
-            (const u64*)W.counts, (const u64*)W.total, M, (const u64*)nullptr, vb[fin], (u32*)nullptr, (u64*)nullptr, zero, (const u32*)uflag);
-        hid = kb[fin], score = vb[fin], hseg = U.dev(s_xs);
+        if ((rc = isect_move(c, W, score, (u32)M, { values, nullptr, nullptr, M }, zero, uflag, s))) return rc;
+        R.ids = merged, R.score = values, R.hseg = U.dev(s_xs);
     }
-    if (o.check)
-        LAUNCH(c, "k_topkb_check", k_topkb_check, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)score, (const u32*)hseg, (u32)Q,
-            (const u64*)W.total, (u32)M, U.dev(s_of), (const u32*)S.flag);
-    const TopkSelect sel = { U.dev(s_pre), U.dev(s_want), U.dev(s_cur), U.dev(s_hist), slots };
-    if ((rc = topk_select(c, hid, score, hseg, Q, W.total, (u32)M, W.ntiles, sel, g.q0, o, (const u32*)S.flag, s))) return rc;
-    u32* hflag = &c->pin->isect_sflag;
-    HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(hof, U.dev(s_of), 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(U.pin(s_hs), hseg, 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+    if ((rc = ranked_tail(c, R, Q, g.q0, o, U, s_sel, slots, s_of, s_hs, S.flag, ws.sflag, s))) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
-    if (*hflag != ANSX_SS_NONE) {  // the first list of the buffer whose sum left 32 bits
-        if (bad_container && *hflag < g.lists.size()) *bad_container = batch_index(g.lists[*hflag]);
-        return ANSX_ERR_DOMAIN;
-    }
-    if (hof[0] != ANSX_TOPK_NONE) {  // the first query of the group with a score of 2^32 - 1 or more
-        if (bad_query) *bad_query = g.q0 + hof[0];
-        return ANSX_ERR_DOMAIN;
-    }
-    const u32* hs = U.pin(s_hs);
-    if (o.counts)
-        for (size_t j = 0; j < Q; j++) o.counts[g.q0 + j] = std::min<u32>(k, hs[j + 1] - hs[j]);
-    return ANSX_OK;
-}
-
-int topk_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
-    const size_t* pay_bytes, size_t count, const u32* terms, const u32* weights, const u64* qoff, size_t nq, u32 k, u32* d_out_ids,
-    u32* d_out_scores, u32* out_counts, size_t* bad_container, size_t* bad_query, hipStream_t s)
-{
-    int rc;
-    const size_t nt = (size_t)qoff[nq];
-    BrFront F;
-    std::vector<u32> uniq;  // (with payloads: the referenced lists, ascending)
-    if (d_pays) {
-        std::vector<u32> urid, all(2 * nt);
-        br_refs(terms, nt, count, &uniq, &urid);
-        std::vector<const u8*> ptr(2 * uniq.size());
-        std::vector<size_t> len(2 * uniq.size());
-        for (size_t u = 0; u < uniq.size(); u++)
-            ptr[2 * u] = d_ins[uniq[u]], len[2 * u] = in_bytes[uniq[u]], ptr[2 * u + 1] = d_pays[uniq[u]], len[2 * u + 1] = pay_bytes[uniq[u]];
-        for (size_t j = 0; j < nt; j++) all[j] = 2 * urid[j], all[nt + j] = 2 * urid[j] + 1;
-        size_t bad = ptr.size();
-        rc = batch_ranges_front(c, kind, f, ptr.data(), len.data(), ptr.size(), all.data(), all.size(), nullptr, &F, &bad, s);
-        if (rc && rc != ANSX_ERR_FORMAT) return rc;
-        // the smallest referenced list whose headers fail the checks (bad: every entry in front of it passed) or differ in n
-        for (size_t u = 0; 2 * u + 1 < bad; u++)
-            if (F.rs[2 * u].H.n != F.rs[2 * u + 1].H.n) {
-                bad = 2 * u, rc = ANSX_ERR_FORMAT;
-                break;
-            }
-        if (rc) {
-            if (bad_container) *bad_container = uniq[bad / 2];
-            return rc;
-        }
-    } else if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, terms, nt, nullptr, &F, bad_container, s)))
-        return rc;
-    const std::function<size_t(u32)> batch_index = [&](u32 r) -> size_t { return d_pays ? uniq[r / 2] : F.ref[r]; };
-    std::vector<u64> n(F.ref.size());
-    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
-    std::vector<UnbGroup> groups;
-    const u64 budget = (c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT) / 2;
-    if ((rc = unb_plan(n.data(), n.size(), F.rid.data(), qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query, nullptr, nullptr, true)))
-        return rc;
-    u32 pow2 = 1;
-    while (pow2 < k) pow2 <<= 1;
-    const TopkOut o = { weights, k, pow2, d_out_ids, d_out_scores, out_counts, d_pays != nullptr };
-    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
-    for (const UnbGroup& g : groups)
-        if ((rc = topk_group(c, kind, f, F, g, off, count, o, batch_index, bad_container, bad_query, s))) return rc;
-    HIPCHK(c, hipStreamSynchronize(s));
-    return ANSX_OK;
+    if ((rc = scan_flag_status(ws, g.lists, *F.index, bad_container))) return rc;
+    return ranked_counts(U.pin(s_of), U.pin(s_hs), Q, g.q0, o, bad_query);
 }
 
 // ansx_topk_bool_batch_dev (ansx_topk_bool.h).  The front end of ansx_topk_batch_dev over the terms
@@ -3880,9 +3974,8 @@ int topk_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_
 // of the chosen op with the excluded lists under HALF the budget: ANY runs topk_group, which adds the exclusion step and
 // k_topkb_check between k_topk_scores and the select; ALL runs topkb_group: ids and payloads decoded with the same
 // offsets, the scan, one upload of the tables with the weights beside them, k_isectb_gather, then per round
-// k_topkb_match, k_dr_scan, k_isect_compact for the ids and again for the scores, k_isectb_bounds -- at least one round,
-// which seeds the scores and drops a driver's repeats -- the exclusion step where the group excludes something,
-// k_topkb_check and the select.
+// k_topkb_match and the compact step over the ids and the scores -- at least one round, which seeds the scores and drops
+// a driver's repeats -- the exclusion step where the group excludes something, and the ranked tail.
 // Workspace (ALL): 4 (8 with payloads) bytes per int of the group's lists, 16 per int of its drivers (two candidate and
 // two score buffers), a pass's, the scan's, IsectWork over the candidates, and per query 8 k bytes of slots, 1 KiB of
 // histogram, 60 bytes of tables, state and bounds, 20 per non-driver term and 16 per excluded term.
@@ -3890,38 +3983,26 @@ int topk_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_
 // flag word, ONE per round, which brings the members' count, and ONE behind the sort, which brings the overflow word and
 // the bounds; one per call at the end.  The exclusion step adds none: its count stays on the device, and the select's
 // grids cover the last count the host has seen.
-int topkb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& g, std::vector<u64>& off, size_t count,
-    const TopkOut& o, const std::function<size_t(u32)>& batch_index, size_t* bad_container, size_t* bad_query, hipStream_t s)
+int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o, size_t* bad_container, size_t* bad_query, hipStream_t s)
 {
     int rc;
     const size_t Q = g.q1 - g.q0, q1 = rup(Q + 1, 4);
     const u64 L = g.at.back(), nc0 = g.G[Q].dst;
-    const u32 k = o.k;
-    const auto nothing = [&]() -> int {  // no query has a result: every slot is ANSX_NO_ID / 0
-        LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)nullptr, (const u32*)nullptr, (u64)g.q0, k, o.pow2,
-            o.ids, o.scores, (const u32*)nullptr);
-        if (o.counts) memset(o.counts + g.q0, 0, 4 * Q);
-        return ANSX_OK;
-    };
-    if (nc0 == 0) return nothing();  // (every driver is empty: nothing is decoded)
+    if (nc0 == 0) return ranked_nothing(c, Q, g.q0, o, s);  // (every driver is empty: nothing is decoded)
     // the lists | their payloads | two candidate and two score buffers | the slots (u64: at an even int); each with the
     // decoders' slack behind
     const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)nc0, 4) + 16;
     const size_t o_m = (o.pays ? 2 : 1) * o_c, o_s = o_m + 4 * half;
-    if ((rc = ensure(c, c->isectb_ids, 4 * o_s + 8 * Q * (size_t)k))) return rc;
+    if ((rc = ensure(c, c->isectb_ids, 4 * o_s + 8 * Q * (size_t)o.k))) return rc;
     u32* ids = (u32*)c->isectb_ids.p;
     u32* pay = o.pays ? ids + o_c : nullptr;
-    u32* buf[2] = { ids + o_m, ids + o_m + half };
-    u32* sb[2] = { ids + o_m + 2 * half, ids + o_m + 3 * half };
+    Flip buf = { { ids + o_m, ids + o_m + half } };
+    Flip sb = { { ids + o_m + 2 * half, ids + o_m + 3 * half } };
     u64* slots = (u64*)(ids + o_s);
-    GeometryGroups geo;
-    for (size_t i = 0; i < g.lists.size(); i++) off[g.lists[i]] = g.at[i], geo[br_geometry(F.rs[g.lists[i]].H)].push_back(g.lists[i]);
-    if ((rc = batch_decode_groups(c, kind, f, F.rs, off, geo, count, ids, bad_container, s))) return rc;
-    if (o.pays && (rc = topk_decode_payloads(c, kind, f, F, g, off, count, o, pay, bad_container, s))) return rc;
+    if ((rc = group_decode(c, F, g.lists, g.at, ids, pay, bad_container, s))) return rc;
 
     // one upload: zero flag words | the overflow word | queries | their drivers' weights | round table | its weights | with
-    // exclusions the second table; behind it on the device: two arrays of segments | prefixes | what is left to find |
-    // cursors | histograms | IsectWork
+    // exclusions the second table; behind it on the device: two arrays of segments | the select state | IsectWork
     Upload U;
     const auto s_fl = U.add<u32>(4);
     const auto s_of = U.add<u32>(4);
@@ -3935,158 +4016,80 @@ int topkb_group(ansx_ctx* c, int kind, int f, const BrFront& F, const IsbGroup& 
     const auto s_xt = U.add<ansx_isb_list>(g.xt.size());
     const size_t up = U.end;
     const auto s_seg = U.add<u32>(2 * q1);  // (the host's copy: the last step's, read back)
-    const auto s_pre = U.add<u64>(Q);
-    const auto s_want = U.add<u32>(Q);
-    const auto s_cur = U.add<u32>(rup(Q, 4));  // (cleared with the histograms behind it)
-    const auto s_hist = U.add<u32>(Q * (size_t)ANSX_TOPK_BINS);
-    const size_t o_w = rup(U.end, 16);
-    if ((rc = ensure_pinned(c, c->isectb_pin, c->isectb_pin_cap, s_seg.off + s_seg.bytes))) return rc;  // (what the host reads or writes)
-    if ((rc = ensure(c, c->isectb_work, o_w + IsectWork::bytes(nc0, false)))) return rc;
-    U.host = c->isectb_pin, U.devp = (u8*)c->isectb_work.p;  // (no copy out of the page is pending: a group ends in a synchronisation)
-    memset(U.pin(s_fl), 0, s_fl.bytes);
-    u32* hof = U.pin(s_of);
-    hof[0] = ANSX_TOPK_NONE, hof[1] = hof[2] = hof[3] = 0;
+    const SelectSecs s_sel = select_sections(U, Q);
+    GroupWs ws;
+    if ((rc = group_room(c, U, s_seg.off + s_seg.bytes, nc0, s_fl, &s_of, &ws))) return rc;
     U.put(s_g, g.G.data()), U.put(s_ro, g.rt_off.data());
     if (!g.rt.empty()) U.put(s_rt, g.rt.data());
     for (size_t j = 0; j < Q; j++) U.pin(s_wd)[j] = o.weights[g.dterm[j]];
     for (size_t e = 0; e < g.rterm.size(); e++) U.pin(s_rw)[e] = o.weights[g.rterm[e]];
     if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
-    HIPCHK(c, hipMemcpyAsync(U.devp, U.host, up, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(U.dev(s_cur), 0, s_hist.off + s_hist.bytes - s_cur.off, s));
-    u32* seg[2] = { U.dev(s_seg), U.dev(s_seg) + q1 };
+    if ((rc = group_upload(c, U, up, &s_sel, s))) return rc;
+    Flip seg = { { U.dev(s_seg), U.dev(s_seg) + q1 } };
     const u32* zero = U.dev(s_fl);
 
     SumsPlan S;
-    if ((rc = sums_prepare(c, (uintptr_t)ids, L, g.at.data(), g.lists.size(), s, &S))) return rc;
-    if ((rc = sums_launch(c, ids, L, g.lists.size(), S, s))) return rc;
-    LAUNCH(c, "k_isectb_gather", k_isectb_gather, (u32)((std::max<u64>(nc0, Q + 1) + ANSX_ISECT_TILE - 1) / ANSX_ISECT_TILE),
-        ANSX_ISECT_NT, 0, s, (const u32*)ids, (const ansx_isb_query*)U.dev(s_g), (u32)Q, buf[0], (u32)nc0, seg[0], (const u32*)S.flag);
-    u32* hflag = &c->pin->isect_sflag;
-    HIPCHK(c, hipMemcpyAsync(hflag, S.flag, 4, hipMemcpyDeviceToHost, s));
+    if ((rc = group_scan(c, ids, g.at, s, &S))) return rc;
+    if ((rc = gather_drivers(c, ids, U.dev(s_g), Q, nc0, buf.from(), seg.from(), S.flag, s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(ws.sflag, S.flag, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (*hflag != ANSX_SS_NONE) {  // the first list of the buffer whose sum left 32 bits
-        if (bad_container && *hflag < g.lists.size()) *bad_container = batch_index(g.lists[*hflag]);
-        return ANSX_ERR_DOMAIN;
-    }
+    if ((rc = scan_flag_status(ws, g.lists, *F.index, bad_container))) return rc;
 
     // (at least one round: the first seeds the scores and drops the repeats of a driver, whatever the queries' terms)
     const u32 rounds = std::max<u32>(g.rounds, 1u);
-    u32 nc = (u32)nc0, cur = 0;
+    u32 nc = (u32)nc0;
     for (u32 r = 0; r < rounds && nc > 0; r++) {
-        const IsectWork W(U.devp + o_w, nc, false);
-        LAUNCH(c, "k_topkb_match", k_topkb_match, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)pay, (const u32*)buf[cur],
-            sb[cur], nc, (const u32*)seg[cur], (u32)Q, (const ansx_isb_query*)U.dev(s_g), (const u32*)U.dev(s_wd),
+        const IsectWork W(ws.work, nc, false);
+        const Moved scores = { sb.from(), sb.to(), nullptr };
+        LAUNCH(c, "k_topkb_match", k_topkb_match, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)ids, (const u32*)pay, (const u32*)buf.from(),
+            sb.from(), nc, (const u32*)seg.from(), (u32)Q, (const ansx_isb_query*)U.dev(s_g), (const u32*)U.dev(s_wd),
             (const u32*)U.dev(s_ro), (const ansx_isb_list*)U.dev(s_rt), (const u32*)U.dev(s_rw), r, o.form, W.ballots, W.counts);
-        LAUNCH(c, "k_dr_scan", (k_dr_scan<u64, false>), 1, ANSX_DR_NT, 0, s, W.counts, (u64)W.ntiles, 1u, 0ull, W.total, (u32*)nullptr);
-        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)buf[cur], nc, (const u64*)W.ballots,
-            (const u64*)W.counts, (const u64*)W.total, (u64)nc, (const u64*)nullptr, buf[1 - cur], (u32*)nullptr, (u64*)nullptr, zero, zero);
-        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)sb[cur], nc, (const u64*)W.ballots,
-            (const u64*)W.counts, (const u64*)W.total, (u64)nc, (const u64*)nullptr, sb[1 - cur], (u32*)nullptr, (u64*)nullptr, zero, zero);
-        LAUNCH(c, "k_isectb_bounds", k_isectb_bounds, (u32)((Q + 256) / 256), 256, 0, s, (const u32*)seg[cur], (u32)Q, nc,
-            (const u64*)W.ballots, (const u64*)W.counts, (const u64*)W.total, seg[1 - cur]);
-        HIPCHK(c, hipMemcpyAsync(&c->pin->isect_total, W.total, 8, hipMemcpyDeviceToHost, s));
+        if ((rc = compact_step(c, W, nc, { buf.from(), buf.to(), nullptr }, &scores, seg.from(), Q, seg.to(), zero, zero, s))) return rc;
+        HIPCHK(c, hipMemcpyAsync(ws.total, W.total, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        nc = (u32)c->pin->isect_total, cur = 1 - cur;
+        nc = (u32)*ws.total, buf.flip(), sb.flip(), seg.flip();
     }
-    if (nc == 0) return nothing();  // (a round left nothing: no id is in all lists of any query)
-    const IsectWork W(U.devp + o_w, nc, false);  // (total: the last round's, nc, at the same place)
+    if (nc == 0) return ranked_nothing(c, Q, g.q0, o, s);  // (a round left nothing: no id is in all lists of any query)
+    const IsectWork W(ws.work, nc, false);  // (total: the last round's, nc, at the same place)
     if (excl) {  // ONE exclusion step over what the rounds left, the scores moved by the same ballots: no wait
-        if ((rc = bool_exclude_step(c, W, ids, buf[cur], nc, nullptr, seg[cur], Q, U.dev(s_xo), U.dev(s_xt), (const u32*)S.flag,
-                 buf[1 - cur], seg[1 - cur], zero, zero, s)))
+        if ((rc = bool_exclude_step(c, W, ids, { buf.from(), buf.to(), nullptr }, nc, nullptr, seg.from(), Q, U.dev(s_xo), U.dev(s_xt),
+                 S.flag, seg.to(), zero, zero, s)))
             return rc;
-        LAUNCH(c, "k_isect_compact", k_isect_compact, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)sb[cur], nc, (const u64*)W.ballots,
-            (const u64*)W.counts, (const u64*)W.total, (u64)nc, (const u64*)nullptr, sb[1 - cur], (u32*)nullptr, (u64*)nullptr, zero, zero);
-        cur = 1 - cur;
+        if ((rc = isect_move(c, W, sb.from(), nc, { sb.to(), nullptr, nullptr, nc }, zero, zero, s))) return rc;
+        buf.flip(), sb.flip(), seg.flip();
     }
-    LAUNCH(c, "k_topkb_check", k_topkb_check, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)sb[cur], (const u32*)seg[cur], (u32)Q,
-        (const u64*)W.total, nc, U.dev(s_of), (const u32*)S.flag);
-    const TopkSelect sel = { U.dev(s_pre), U.dev(s_want), U.dev(s_cur), U.dev(s_hist), slots };
-    if ((rc = topk_select(c, buf[cur], sb[cur], seg[cur], Q, W.total, nc, W.ntiles, sel, g.q0, o, (const u32*)S.flag, s))) return rc;
-    HIPCHK(c, hipMemcpyAsync(hof, U.dev(s_of), 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(U.pin(s_seg), seg[cur], 4 * (Q + 1), hipMemcpyDeviceToHost, s));
+    const Ranked R = { buf.from(), sb.from(), seg.from(), W.total, nc, W.ntiles };
+    if ((rc = ranked_tail(c, R, Q, g.q0, o, U, s_sel, slots, s_of, s_seg, S.flag, nullptr, s))) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
-    if (hof[0] != ANSX_TOPK_NONE) {  // the first query of the group with a score of 2^32 - 1 or more among its results
-        if (bad_query) *bad_query = g.q0 + hof[0];
-        return ANSX_ERR_DOMAIN;
-    }
-    const u32* hs = U.pin(s_seg);
-    if (o.counts)
-        for (size_t j = 0; j < Q; j++) o.counts[g.q0 + j] = std::min<u32>(k, hs[j + 1] - hs[j]);
-    return ANSX_OK;
+    return ranked_counts(U.pin(s_of), U.pin(s_seg), Q, g.q0, o, bad_query);
 }
 
+// The two ranked calls: ansx_topk_bool_batch_dev and, as its case ANY with nothing excluded and no check,
+// ansx_topk_batch_dev (`check`: the overflow word is k_topkb_check's, not k_topk_scores').
 int topk_bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
-    const size_t* pay_bytes, size_t count, int op, const u32* terms, const u32* weights, const u64* qoff, const u32* xterms,
+    const size_t* pay_bytes, size_t count, int op, bool check, const u32* terms, const u32* weights, const u64* qoff, const u32* xterms,
     const u64* xqoff, size_t nq, u32 k, u32* d_out_ids, u32* d_out_scores, u32* out_counts, size_t* bad_container, size_t* bad_query,
     hipStream_t s)
 {
     int rc;
-    const size_t nt = (size_t)qoff[nq], nx = xqoff ? (size_t)xqoff[nq] : 0;
-    std::vector<u32> named(terms, terms + nt);
-    if (nx) named.insert(named.end(), xterms, xterms + nx);
-    BrFront F;
-    std::vector<u32> uniq, owner, payof, rid;  // (with payloads: the referenced lists, ascending; the list behind every entry)
-    if (d_pays) {
-        std::vector<u32> urid, all;
-        br_refs(named.data(), named.size(), count, &uniq, &urid);
-        std::vector<char> term(uniq.size(), 0);
-        for (size_t j = 0; j < nt; j++) term[urid[j]] = 1;
-        std::vector<u32> idpos(uniq.size());
-        std::vector<const u8*> ptr;
-        std::vector<size_t> len;
-        for (size_t u = 0; u < uniq.size(); u++) {  // list u's id container, then its payload where it is a term
-            idpos[u] = (u32)ptr.size();
-            ptr.push_back(d_ins[uniq[u]]), len.push_back(in_bytes[uniq[u]]), owner.push_back((u32)u), all.push_back(idpos[u]);
-            payof.push_back(term[u] ? idpos[u] + 1u : ANSX_TOPK_NONE);
-            if (!term[u]) continue;
-            ptr.push_back(d_pays[uniq[u]]), len.push_back(pay_bytes[uniq[u]]), owner.push_back((u32)u), all.push_back(idpos[u] + 1u);
-            payof.push_back(ANSX_TOPK_NONE);
-        }
-        size_t bad = ptr.size();
-        rc = batch_ranges_front(c, kind, f, ptr.data(), len.data(), ptr.size(), all.data(), all.size(), nullptr, &F, &bad, s);
-        if (rc && rc != ANSX_ERR_FORMAT) return rc;
-        // the smallest referenced list whose headers fail the checks (bad: every entry in front of it passed) or differ in n
-        for (size_t e = 0; e + 1 < bad; e++)
-            if (payof[e] != ANSX_TOPK_NONE && F.rs[e].H.n != F.rs[e + 1].H.n) {
-                bad = e, rc = ANSX_ERR_FORMAT;
-                break;
-            }
-        if (rc) {
-            if (bad_container) *bad_container = uniq[owner[bad]];
-            return rc;
-        }
-        rid.resize(named.size());
-        for (size_t j = 0; j < named.size(); j++) rid[j] = idpos[urid[j]];
-    } else {
-        if ((rc = batch_ranges_front(c, kind, f, d_ins, in_bytes, count, named.data(), named.size(), nullptr, &F, bad_container, s)))
-            return rc;
-        rid = F.rid;
-    }
-    const std::function<size_t(u32)> batch_index = [&](u32 r) -> size_t { return d_pays ? uniq[owner[r]] : F.ref[r]; };
-    std::vector<u64> n(F.ref.size());
-    for (size_t j = 0; j < n.size(); j++) n[j] = F.rs[j].H.n;
-    const u32* xrid = rid.data() + nt;
-    const u64 budget = (c->dbg.isect_batch_ints ? c->dbg.isect_batch_ints : ANSX_ISECT_BATCH_INTS_DEFAULT) / 2;
+    QueryFront F;
+    if ((rc = query_front(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, (size_t)qoff[nq], xterms,
+             xqoff ? (size_t)xqoff[nq] : 0, &F, bad_container, s)))
+        return rc;
+    const u64 budget = query_budget(c, true);
     u32 pow2 = 1;
     while (pow2 < k) pow2 <<= 1;
-    TopkOut o = { weights, k, pow2, d_out_ids, d_out_scores, out_counts, d_pays != nullptr };
-    o.check = true, o.payof = d_pays ? &payof : nullptr;
-    o.form = c->dbg.topk_bool_form == 1 ? ANSX_TOPKB_FORM_SEARCH : ANSX_TOPKB_FORM_DEFAULT;
-    std::vector<u64> off(n.size(), 0);  // (every group sets its own lists')
+    const TopkOut o = { weights, k, pow2, d_out_ids, d_out_scores, out_counts, d_pays != nullptr, check,
+        c->dbg.topk_bool_form == 1 ? ANSX_TOPKB_FORM_SEARCH : ANSX_TOPKB_FORM_DEFAULT };
     if (op == ANSX_BOOL_ALL) {
         std::vector<IsbGroup> groups;
-        if ((rc = isb_plan(n.data(), n.size(), rid.data(), qoff, nq, budget, &groups, bad_query, xrid, xqoff, true))) return rc;
-        for (const IsbGroup& g : groups)
-            if ((rc = topkb_group(c, kind, f, F, g, off, count, o, batch_index, bad_container, bad_query, s))) return rc;
-    } else {
-        std::vector<UnbGroup> groups;
-        if ((rc = unb_plan(n.data(), n.size(), rid.data(), qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query, xrid, xqoff, true)))
-            return rc;
-        for (const UnbGroup& g : groups)
-            if ((rc = topk_group(c, kind, f, F, g, off, count, o, batch_index, bad_container, bad_query, s))) return rc;
+        if ((rc = isb_plan(F.n.data(), F.n.size(), F.rid, qoff, nq, budget, &groups, bad_query, F.xrid, xqoff, true))) return rc;
+        return run_groups(c, groups, [&](const IsbGroup& g) { return topkb_group(c, F, g, o, bad_container, bad_query, s); }, s);
     }
-    HIPCHK(c, hipStreamSynchronize(s));
-    return ANSX_OK;
+    std::vector<UnbGroup> groups;
+    if ((rc = unb_plan(F.n.data(), F.n.size(), F.rid, qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query, F.xrid, xqoff, true)))
+        return rc;
+    return run_groups(c, groups, [&](const UnbGroup& g) { return topk_group(c, F, g, o, bad_container, bad_query, s); }, s);
 }
 
 // The argument checks of the random-access entry points, one per argument shape: everything a call decides before the
@@ -4685,8 +4688,8 @@ int ansx_intersect_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const*
         return ANSX_ERR_ARG;
     if (nqueries == 0) return empty_batch(out_offsets, (u64*)nullptr);
     return run_call(c, stream, [&](hipStream_t s) {
-        return intersect_batch(c, kind, f, d_ins, in_bytes, count, terms, (const u64*)qoff, nqueries, d_out_ids, out_capacity,
-            (u64*)out_offsets, bad_container, bad_query, s);
+        return bool_batch(c, kind, f, d_ins, in_bytes, count, ANSX_BOOL_ALL, terms, (const u64*)qoff, nullptr, nullptr, nqueries, d_out_ids,
+            nullptr, out_capacity, (u64*)out_offsets, bad_container, bad_query, s);
     });
 }
 
@@ -4700,8 +4703,8 @@ int ansx_union_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_i
         return ANSX_ERR_ARG;
     if (nqueries == 0) return empty_batch(out_offsets, (u64*)nullptr);
     return run_call(c, stream, [&](hipStream_t s) {
-        return union_batch(c, kind, f, d_ins, in_bytes, count, terms, (const u64*)qoff, nqueries, d_out_ids, d_out_cnt, out_capacity,
-            (u64*)out_offsets, bad_container, bad_query, s);
+        return bool_batch(c, kind, f, d_ins, in_bytes, count, ANSX_BOOL_ANY, terms, (const u64*)qoff, nullptr, nullptr, nqueries, d_out_ids,
+            d_out_cnt, out_capacity, (u64*)out_offsets, bad_container, bad_query, s);
     });
 }
 
@@ -4746,7 +4749,7 @@ int ansx_bool_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_in
     if (nqueries == 0) return empty_batch(out_offsets, (u64*)nullptr);
     return run_call(c, stream, [&](hipStream_t s) {
         return bool_batch(c, kind, f, d_ins, in_bytes, count, op, terms, (const u64*)qoff, xterms, (const u64*)xqoff, nqueries, d_out_ids,
-            out_capacity, (u64*)out_offsets, bad_container, bad_query, s);
+            nullptr, out_capacity, (u64*)out_offsets, bad_container, bad_query, s);
     });
 }
 
@@ -4785,8 +4788,8 @@ int ansx_topk_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_in
         return ANSX_ERR_ARG;
     if (nqueries == 0) return ANSX_OK;
     return run_call(c, stream, [&](hipStream_t s) {
-        return topk_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, (const u64*)qoff, nqueries, k, d_out_ids,
-            d_out_scores, out_counts, bad_container, bad_query, s);
+        return topk_bool_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, ANSX_BOOL_ANY, false, terms, weights, (const u64*)qoff,
+            nullptr, nullptr, nqueries, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
     });
 }
 
@@ -4802,7 +4805,7 @@ int ansx_topk_bool_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const*
     if (bool_args(d_ins, count, op, xterms, xqoff, nqueries, bad_container, bad_query)) return ANSX_ERR_ARG;
     if (nqueries == 0) return ANSX_OK;
     return run_call(c, stream, [&](hipStream_t s) {
-        return topk_bool_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, op, terms, weights, (const u64*)qoff, xterms,
+        return topk_bool_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, op, true, terms, weights, (const u64*)qoff, xterms,
             (const u64*)xqoff, nqueries, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
     });
 }

@@ -131,6 +131,49 @@ static inline void br_refs(const u32* src, size_t nranges, size_t count, std::ve
     for (size_t i = 0; i < nranges; i++) (*rid)[i] = (u32)(std::lower_bound(ref->begin(), ref->end(), src[i]) - ref->begin());
 }
 
+// The source list of a ranked call with payloads (ansx_topk_batch_dev, ansx_topk_bool_batch_dev):
+// the id container of every list `named` refers to, ascending by batch index, and behind each list that is a TERM --
+// one of named[0 .. nt), the rest are excluded lists -- the container of its payload.  A list that is only excluded
+// has no payload entry.  With nothing excluded, list u of the referenced ones stands at entry 2u and its payload at
+// 2u + 1.  The front end reads the headers of the entries in this order; the planners read rid.
+struct QuerySources {
+    std::vector<u32> uniq;   // the referenced lists, ascending (batch indices)
+    std::vector<u32> idpos;  // per referenced list: the entry of its id container
+    std::vector<u32> owner;  // per entry: the referenced list (its place in uniq) the container belongs to
+    std::vector<u8> pay;     // per entry: 1 its owner's payload container, 0 its id container
+    std::vector<u32> payof;  // per entry: the entry of its payload (an id container of a term), else ANSX_TOPK_NONE
+    std::vector<u32> rid;    // per name: the entry of its id container
+    size_t batch_index(size_t e) const { return uniq[owner[e]]; }
+};
+static inline void query_sources(const u32* named, size_t nt, size_t nnamed, size_t count, QuerySources* S)
+{
+    std::vector<u32> urid;
+    br_refs(named, nnamed, count, &S->uniq, &urid);
+    const size_t nu = S->uniq.size();
+    std::vector<u8> term(nu, 0);
+    for (size_t j = 0; j < nt; j++) term[urid[j]] = 1;
+    S->idpos.resize(nu), S->owner.clear(), S->pay.clear(), S->payof.clear();
+    for (size_t u = 0; u < nu; u++) {
+        const u32 e = (u32)S->owner.size();
+        S->idpos[u] = e;
+        S->owner.push_back((u32)u), S->pay.push_back(0), S->payof.push_back(term[u] ? e + 1u : ANSX_TOPK_NONE);
+        if (term[u]) S->owner.push_back((u32)u), S->pay.push_back(1), S->payof.push_back(ANSX_TOPK_NONE);
+    }
+    S->rid.resize(nnamed);
+    for (size_t j = 0; j < nnamed; j++) S->rid[j] = S->idpos[urid[j]];
+}
+
+// The first entry of the source list that is at fault, given the headers rs of the entries and `failed`, the first
+// entry whose header fails the checks (every entry in front of it passed; the number of entries: none fails): the first
+// id container in front of `failed` whose payload differs from it in n, else `failed`.  Entries ascend by batch index,
+// so batch_index() of the result is the smallest batch index at fault.
+static inline size_t query_sources_first_bad(const QuerySources& S, const std::vector<BatchSrc>& rs, size_t failed)
+{
+    for (size_t e = 0; e + 1 < failed; e++)
+        if (S.payof[e] != ANSX_TOPK_NONE && rs[e].H.n != rs[e + 1].H.n) return e;
+    return failed;
+}
+
 struct BrRun {     // consecutive touched blocks b0..b1 of referenced container r, inside one pass
     u32 r, b0, b1, pass;
     u64 wl;        // its first int in the pass's work list (a multiple of 4)

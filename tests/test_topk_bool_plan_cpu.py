@@ -2,8 +2,9 @@
 with the terms behind its drivers and rounds; ansx_plan_types.h, the saturating arithmetic of the scores) on the CPU:
 tests/tools/topk_bool_plan_check.cpp checks the terms against the terms as named over synthetic headers, holds the
 plan's other outputs equal with and without them, and runs every group the way the kernels do -- the seed round, the
-saturating adds, repeats, compaction, exclusion, the overflow rule -- against a brute-force scorer (see the program's
-head).  Built here with the host compiler alone under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone
+saturating adds, repeats, compaction, exclusion, the overflow rule -- against a brute-force scorer, and checks the source
+list of the ranked calls with payloads (query_sources and its "first bad list" rule) over synthetic term and exclusion
+sets (see the program's head).  Built here with the host compiler alone under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone
 program."""
 import os
 import shutil

@@ -13,6 +13,12 @@
 //      exclusion step drops what an excluded list holds; then the overflow rule: a SURVIVOR with score 0xFFFFFFFF names
 //      its query, the smallest such.  Against a brute-force scorer: per query the set logic with std::set, 64-bit sums
 //      of saturated products over all postings of the terms as named, the overflow rule on the ids of the result only.
+//   3. The source list of the ranked calls with payloads (query_sources, query_sources_first_bad) over synthetic term and
+//      exclusion sets, small and large batches (both ways of br_refs): with nothing excluded it is the layout written
+//      out here on its own -- the referenced lists ascending, list u at entry 2u and its payload at 2u + 1, a term at
+//      2 * (its list's rank); a list that is only excluded gets no payload entry; rid maps every name to the id entry
+//      of its list; and the first bad entry names the smallest batch index, for a failing header and for a payload
+//      whose n differs alike.
 // Built with -fsanitize=address,undefined and run by tests/test_topk_bool_plan_cpu.py; exit status 0 and "ok".
 #include "../../ans_large_alphabet_amd/csrc/ansx_plan.h"
 
@@ -309,10 +315,81 @@ static void plan_cases()
     }
 }
 
+// the smallest batch index at fault, found the slow way: a list whose id or payload header fails, or whose two differ in n
+static size_t slow_first_bad(const std::vector<u32>& named, size_t nt, const std::set<u32>& fails_id, const std::set<u32>& fails_pay,
+    const std::set<u32>& differs)
+{
+    std::set<u32> terms(named.begin(), named.begin() + nt), all(named.begin(), named.end());
+    for (const u32 i : all) {  // (ascending)
+        if (fails_id.count(i)) return i;
+        if (terms.count(i) && (fails_pay.count(i) || differs.count(i))) return i;
+    }
+    return ~(size_t)0;
+}
+
+static void source_cases()
+{
+    std::mt19937_64 rng(21);
+    const char* what = "source list";
+    for (int round = 0; round < 300; round++) {
+        const size_t count = round % 3 == 0 ? 40 : round % 3 == 1 ? 5000 : 1 + rng() % 9;  // (5000 > 4 * names + 1024: br_refs sorts)
+        const size_t nt = 1 + rng() % 30, nx = round % 4 == 0 ? 0 : rng() % 12;
+        std::vector<u32> named(nt + nx);
+        for (u32& t : named) t = (u32)(rng() % count);
+        QuerySources S;
+        query_sources(named.data(), nt, named.size(), count, &S);
+        const std::set<u32> terms(named.begin(), named.begin() + nt), all(named.begin(), named.end());
+        // every referenced list once, ascending; its id entry, then its payload's where it is a term and only there
+        CHECK(S.uniq == std::vector<u32>(all.begin(), all.end()) && S.idpos.size() == S.uniq.size());
+        CHECK(S.owner.size() == all.size() + terms.size() && S.pay.size() == S.owner.size() && S.payof.size() == S.owner.size());
+        size_t e = 0;
+        for (size_t u = 0; u < S.uniq.size(); u++) {
+            const bool term = terms.count(S.uniq[u]) != 0;
+            CHECK(S.idpos[u] == e && S.owner[e] == u && !S.pay[e] && S.batch_index(e) == S.uniq[u]);
+            CHECK(S.payof[e] == (term ? (u32)e + 1 : ANSX_TOPK_NONE));
+            e++;
+            if (!term) continue;  // (only excluded: no payload entry)
+            CHECK(S.owner[e] == u && S.pay[e] == 1 && S.payof[e] == ANSX_TOPK_NONE && S.batch_index(e) == S.uniq[u]);
+            e++;
+        }
+        CHECK(e == S.owner.size() && S.rid.size() == named.size());
+        for (size_t j = 0; j < named.size(); j++) CHECK(!S.pay[S.rid[j]] && S.batch_index(S.rid[j]) == named[j]);
+        if (nx == 0) {  // the layout of ansx_topk_batch_dev, written out on its own
+            std::vector<u32> sorted(named.begin(), named.end());
+            std::sort(sorted.begin(), sorted.end());
+            sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+            CHECK(S.owner.size() == 2 * sorted.size());
+            for (size_t u = 0; u < sorted.size(); u++) {
+                CHECK(S.batch_index(2 * u) == sorted[u] && S.batch_index(2 * u + 1) == sorted[u] && !S.pay[2 * u] && S.pay[2 * u + 1]);
+                CHECK(S.payof[2 * u] == 2 * u + 1);
+            }
+            for (size_t j = 0; j < nt; j++)
+                CHECK(S.rid[j] == 2 * (u32)(std::lower_bound(sorted.begin(), sorted.end(), named[j]) - sorted.begin()));
+        }
+        // the first bad list: headers with n = 100 + the batch index; some fail, some payloads differ in n
+        std::set<u32> fails_id, fails_pay, differs;
+        for (int k = (int)(rng() % 3); k > 0; k--) ((rng() & 1) ? fails_id : fails_pay).insert(named[rng() % named.size()]);
+        for (int k = (int)(rng() % 3); k > 0; k--) differs.insert(named[rng() % named.size()]);
+        std::vector<BatchSrc> rs(S.owner.size());
+        size_t failed = rs.size();
+        for (size_t i = 0; i < rs.size(); i++) {
+            const u32 b = (u32)S.batch_index(i);
+            memset(&rs[i], 0, sizeof rs[i]);
+            rs[i].H.n = 100 + b + (S.pay[i] && differs.count(b) ? 1 : 0);
+            if (failed == rs.size() && (S.pay[i] ? fails_pay : fails_id).count(b)) failed = i;
+        }
+        for (size_t i = failed; i < rs.size(); i++) rs[i].H.n = 0xDEAD;  // (behind the first failure nothing is looked at)
+        const size_t bad = query_sources_first_bad(S, rs, failed), want = slow_first_bad(named, nt, fails_id, fails_pay, differs);
+        CHECK(bad <= failed && (bad == rs.size()) == (want == ~(size_t)0));
+        if (bad < rs.size()) CHECK(S.batch_index(bad) == want);
+    }
+}
+
 int main()
 {
     sat_cases();
     plan_cases();
+    source_cases();
     printf("ok: %ld checks\n", checks);
     return 0;
 }
