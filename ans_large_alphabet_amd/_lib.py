@@ -14,6 +14,7 @@ FOLD, RFOLD, MSB, INT = 0, 1, 2, 3
 FLAG_COMPACT_ALPHABET = 1
 OK, ERR_ARG, ERR_CAPACITY, ERR_FORMAT, ERR_HIP, ERR_NO_DEVICE, ERR_DOMAIN, ERR_MODEL = range(8)
 BOOL_ALL, BOOL_ANY = 0, 1  # the op of ansx_bool_batch_dev
+OCCUR_SHOULD, OCCUR_MUST = 0, 1  # the occur values of ansx_topk_query_batch_dev
 SINGLE_STREAM = 0xFFFFFFFF
 NO_CHECKPOINTS = 0xFFFFFFFF
 DEFAULT_BLOCK_INTS = 16384
@@ -36,6 +37,7 @@ EXPORTS = [
     "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
     "ansx_intersect_ids_dev", "ansx_intersect_dev", "ansx_intersect_batch_dev", "ansx_union_batch_dev", "ansx_union_dev",
     "ansx_bool_batch_dev", "ansx_last_encode_form", "ansx_topk_batch_dev", "ansx_topk_bool_batch_dev",
+    "ansx_topk_query_batch_dev",
     "ansx_decode_batch_device_ranges_dev", "ansx_decode_batch_device_ranges_sums_dev",
 ]
 
@@ -221,6 +223,9 @@ def lib():
     L.ansx_topk_bool_batch_dev.restype = C.c_int
     L.ansx_topk_bool_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, C.c_int, vp, vp, vp, vp, vp, sz, C.c_uint32,
                                            vp, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]
+    L.ansx_topk_query_batch_dev.restype = C.c_int
+    L.ansx_topk_query_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint32,
+                                            vp, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]
     L.ansx_union_dev.restype = C.c_int
     L.ansx_union_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(sz), vp]
     L.ansx_container_info.restype = C.c_int

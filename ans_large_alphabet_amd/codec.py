@@ -833,11 +833,52 @@ class _Codec:
         return self._topk_call("topk_bool_batch_dev", in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, ops[op],
                                out_scores_ptr, pay_ptrs, pay_sizes, stream)
 
+    # ---- ranked queries with required, optional and excluded terms (include/ansx.h)
+    def topk_query_batch_dev(self, in_ptrs, in_bytes, queries, weights, occurs, min_should, excludes, k, out_ids_ptr,
+                             out_scores_ptr=None, pay_ptrs=None, pay_sizes=None, stream=None):
+        """topk_bool_batch_dev with a role per term and a threshold per query instead of one op.  occurs: None (every term
+        is optional), or a sequence as long as queries of sequences of OCCUR_MUST (1, required) / OCCUR_SHOULD (0, optional),
+        occurs[q][i] the role of queries[q][i].  min_should: None (all zero), or a sequence of len(queries) integers in
+        [0, 2^32).  The result of query q: the ids that occur in every required list, have at least min_should[q] entries
+        in its optional lists as named (at least one where it has no required term) and occur in none of its excluded
+        lists; every posting of a result's id, in required and optional lists, is scored.  Outputs, counts and errors are
+        topk_bool_batch_dev's."""
+        return self._topk_call("topk_query_batch_dev", in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, None,
+                               out_scores_ptr, pay_ptrs, pay_sizes, stream, query=(occurs, min_should))
+
     def _topk_call(self, what, in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, op, out_scores_ptr, pay_ptrs,
-                   pay_sizes, stream):
-        """What the two ranked calls share: the checks of their arguments and the call; op None: ansx_topk_batch_dev"""
+                   pay_sizes, stream, query=None):
+        """What the ranked calls share: the checks of their arguments and the call; op None: ansx_topk_batch_dev or, with
+        query = (occurs, min_should), ansx_topk_query_batch_dev"""
         ptrs, sizes, terms, qoff = self._batch_queries(in_ptrs, in_bytes, queries, 0)
         nc, nq = ptrs.size, len(queries)
+        occ = msm = None
+        if query is not None and query[0] is not None:
+            occurs = query[0]
+            if isinstance(occurs, (str, bytes)) or not hasattr(occurs, "__len__") or len(occurs) != nq:
+                raise ValueError("occurs must be a sequence as long as queries")
+            # (one conversion for all queries: a conversion per query costs microseconds each, which a batch of
+            # thousands of short queries would see)
+            lens = qoff[1:] - qoff[:-1]
+            for q, oc in enumerate(occurs):
+                if isinstance(oc, (str, bytes)) or not hasattr(oc, "__len__"):
+                    raise ValueError("occurs of query %d are not a sequence of integers" % q)
+                if len(oc) != lens[q]:
+                    raise ValueError("occurs of query %d must be a flat sequence of integers, one per term" % q)
+            flat = np.array([o for oc in occurs for o in oc] + [0])  # (never empty)
+            if flat.ndim != 1 or flat.dtype.kind not in "uib":
+                raise ValueError("occurs must be flat sequences of integers, one per term")
+            if int(flat.min()) < 0 or int(flat.max()) > 0xFF:
+                raise ValueError("occurs lie outside [0, 256)")
+            occ = np.ascontiguousarray(flat, dtype=np.uint8)
+        if query is not None and query[1] is not None:
+            ms = query[1]
+            if isinstance(ms, (str, bytes)) or not hasattr(ms, "__len__") or len(ms) != nq:
+                raise ValueError("min_should must be a sequence as long as queries")
+            ms = np.asarray(ms).reshape(-1)
+            if ms.size and (ms.dtype.kind not in "ui" or int(ms.min()) < 0 or int(ms.max()) > 0xFFFFFFFF):
+                raise ValueError("min_should must hold integers in [0, 2^32)")
+            msm = np.ascontiguousarray(np.concatenate([ms.astype(np.uint32), np.zeros(1, dtype=np.uint32)]), dtype=np.uint32)
         xterms = xqoff = None
         if excludes is not None:
             xterms, xqoff = self._flatten_queries(excludes, "excludes", "excludes of query")
@@ -874,7 +915,12 @@ class _Codec:
         head = (self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None,
                 None if pays is None else pays.ctypes.data, None if psizes is None else psizes.ctypes.data, nc)
         tail = (nq, int(k), out_ids_ptr, out_scores_ptr, counts.ctypes.data if nq else None, C.byref(bad_c), C.byref(bad_q), stream)
-        if op is None:
+        if query is not None:
+            st = L.lib().ansx_topk_query_batch_dev(
+                *head, terms.ctypes.data, wts.ctypes.data, None if occ is None else occ.ctypes.data, qoff.ctypes.data,
+                None if msm is None else msm.ctypes.data, None if xterms is None else xterms.ctypes.data,
+                None if xqoff is None else xqoff.ctypes.data, *tail)
+        elif op is None:
             st = L.lib().ansx_topk_batch_dev(*head, terms.ctypes.data, wts.ctypes.data, qoff.ctypes.data, *tail)
         else:
             st = L.lib().ansx_topk_bool_batch_dev(

@@ -40,6 +40,7 @@
 #include "ansx_bool.h"
 #include "ansx_topk.h"
 #include "ansx_topk_bool.h"
+#include "ansx_topk_query.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_batchdevranges.h"
@@ -206,6 +207,7 @@ struct ansx_ctx {
         int model_pipeline = 0;       // ANSX_MODEL_PIPELINE: 0 by the call's size, ANSX_PIPE_NEVER, ANSX_PIPE_ALWAYS, or a range count (1 .. ANSX_PIPE_MAX_RANGES)
         u32 batch_pass_blocks = 0;    // ANSX_BATCH_PASS_BLOCKS: blocks per pass of ansx_decode_batch_dev, ansx_decode_batch_ranges_dev and ansx_encode_batch_dev (0 = ANSX_BATCH_PASS_DEFAULT; tests force tiny passes)
         int bool_form = 0;            // ANSX_BOOL_FORM: 0 k_bool_exclude's own rule, 1 "search", 2 "staged" (ANSX_BOOL_FORM_*; tests and the bench tool force one)
+        int topk_query_form = 0;      // ANSX_TOPK_QUERY_FORM: 0 k_topkq_should's own rule, 1 "search", 2 "staged" (ANSX_TOPKQ_FORM_*; tests and the bench tool force one)
         int topk_bool_form = 0;       // ANSX_TOPK_BOOL_FORM: 0 the default of k_topkb_match, 1 "search", 2 "bounded" (tests and the bench tool force one)
         int intersect_form = 0;       // ANSX_INTERSECT_FORM: 0 by ANSX_ISECT_FULL_PER_BLOCK, 1 "selective", 2 "full" (tests and the bench tool force one)
         u64 isect_batch_ints = 0;     // ANSX_ISECT_BATCH_INTS: the ints a group of ansx_intersect_batch_dev or ansx_union_batch_dev may take (0 = ANSX_ISECT_BATCH_INTS_DEFAULT; tests force small groups)
@@ -3827,7 +3829,42 @@ struct TopkOut {
     // step; form: ANSX_TOPKB_FORM_*
     bool check;
     u32 form;
+    // ansx_topk_query_batch_dev: null, or every query's threshold as it applies (query_split's m,
+    // by the call's query number) and, for a group with required terms, the weight of every optional term as named in
+    // isb_plan's orid; qform: ANSX_TOPKQ_FORM_*
+    const u32 *msm = nullptr, *oweights = nullptr;
+    u32 qform = 0;
 };
+
+// ... the optional step of ansx_topk_query_batch_dev (ansx_topk_query.h) behind the required rounds: the n candidates of
+// `cand` with `score` beside them (d_total: null, or where the device holds their count), query j's in [seg[j], seg[j + 1]),
+// take the postings of their query's optional lists ot[oo[j] .. oo[j + 1]) -- the scores in place -- and those with at
+// least msm[j] of them -> cand.to, their scores -> score.to, their bounds -> nseg, their count -> W.total.
+struct ShouldTables {
+    const u32* oo;
+    const ansx_isb_list* ot;
+    const u32 *ow, *msm;
+    u32 form;
+};
+int should_step(ansx_ctx* c, const IsectWork& W, const u32* ids, const u32* pay, const Moved& cand, const Moved& score, u32 n,
+    const u64* d_total, const u32* seg, size_t Q, const ShouldTables& T, const u32* sflag, u32* nseg, const u32* gf, const u32* df,
+    hipStream_t s)
+{
+    LAUNCH(c, "k_topkq_should", k_topkq_should, W.ntiles, ANSX_ISECT_NT, 0, s, ids, pay, cand.from, (u32*)score.from, n, d_total, seg, (u32)Q,
+        T.oo, T.ot, T.ow, T.msm, T.form, W.ballots, W.counts, sflag);
+    return compact_step(c, W, n, cand, &score, seg, Q, nseg, gf, df, s);
+}
+
+// ... its threshold step behind k_topk_scores, for a group without required terms in which some query asks for two
+// entries or more (k_topkq_atleast): the heads with at least msm[j] entries -> heads.to, their scores -> score.to, their
+// bounds -> nseg, their count -> W.total, which held the heads'
+int atleast_step(ansx_ctx* c, const IsectWork& W, const u32* idx, const Moved& heads, const Moved& score, u32 n, const u32* hseg,
+    const u32* seg, size_t Q, const u32* msm, const u32* sflag, u32* nseg, const u32* gf, const u32* df, hipStream_t s)
+{
+    LAUNCH(c, "k_topkq_atleast", k_topkq_atleast, W.ntiles, ANSX_ISECT_NT, 0, s, idx, hseg, seg, (u32)Q, (const u64*)W.total, n, msm,
+        W.ballots, W.counts, sflag);
+    return compact_step(c, W, n, heads, &score, hseg, Q, nseg, gf, df, s);
+}
 
 // The select of a ranked call over the candidates (ids[h], score[h]), h < min(*total, n), query j's in [hseg[j], hseg[j + 1]),
 // all on the device: the eight rounds of k_topk_hist / k_topk_pick, k_topk_gather and k_topk_sort, which writes the
@@ -3920,14 +3957,19 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
     const bool excl = !g.xt.empty();  // (ansx_topk_bool_batch_dev only: the group excludes something)
     const auto s_xo = U.add<u32>(excl ? Q + 1 : 0);
     const auto s_xt = U.add<ansx_isb_list>(g.xt.size());
+    // (ansx_topk_query_batch_dev only: some query of the group asks for two entries or more -- the thresholds go up too)
+    const bool least = o.msm && std::any_of(o.msm + g.q0, o.msm + g.q1, [](u32 m) { return m >= 2; });
+    const auto s_m = U.add<u32>(least ? Q : 0);
     const size_t up = U.end;
     const auto s_hs = U.add<u32>(q1);  // (the host's copy: read back)
     const auto s_xs = U.add<u32>(excl ? q1 : 0);
+    const auto s_as = U.add<u32>(least ? q1 : 0);
     const SelectSecs s_sel = select_sections(U, Q);
     GroupWs ws;
     if ((rc = group_room(c, U, s_hs.off + s_hs.bytes, M, s_fl, &s_of, &ws))) return rc;
     U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
     if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
+    if (least) U.put(s_m, o.msm + g.q0);
     u32* hw = U.pin(s_w);
     for (size_t i = 0; i < g.pterm.size(); i++) hw[i] = g.pterm[i] == ANSX_TOPK_NONE ? 0u : o.weights[g.pterm[i]];
     if ((rc = group_upload(c, U, up, &s_sel, s))) return rc;
@@ -3955,12 +3997,22 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
     LAUNCH(c, "k_topk_scores", k_topk_scores, W.ntiles, ANSX_ISECT_NT, 0, s, (const u32*)idx, (const u32*)values, (const u32*)U.dev(s_hs),
         seg, (u32)Q, (const u64*)W.total, (u32)M, score, U.dev(s_of) + (o.check ? 1 : 0), (const u32*)S.flag);
     Ranked R = { heads, score, U.dev(s_hs), W.total, (u32)M, W.ntiles };
+    // (what a step compacts into: the merged ids and their values are through, and a second step writes where the first read)
+    Flip hb = { { heads, merged } }, vs = { { score, values } };
+    if (least) {  // ansx_topk_query_batch_dev: the threshold over the heads, the scores moved by the same ballots: no wait
+        if ((rc = atleast_step(c, W, idx, { hb.from(), hb.to(), nullptr }, { vs.from(), vs.to(), nullptr }, (u32)M, R.hseg, seg, Q,
+                 U.dev(s_m), S.flag, U.dev(s_as), zero, uflag, s)))
+            return rc;
+        hb.flip(), vs.flip();
+        R.ids = hb.from(), R.score = vs.from(), R.hseg = U.dev(s_as);
+    }
     if (excl) {  // ONE exclusion step over the heads, as in unb_group, and the scores moved by the same ballots: no wait
-        if ((rc = bool_exclude_step(c, W, ids, { heads, merged, nullptr }, (u32)M, W.total, R.hseg, Q, U.dev(s_xo), U.dev(s_xt), S.flag,
+        if ((rc = bool_exclude_step(c, W, ids, { hb.from(), hb.to(), nullptr }, (u32)M, W.total, R.hseg, Q, U.dev(s_xo), U.dev(s_xt), S.flag,
                  U.dev(s_xs), zero, uflag, s)))
             return rc;
-        if ((rc = isect_move(c, W, score, (u32)M, { values, nullptr, nullptr, M }, zero, uflag, s))) return rc;
-        R.ids = merged, R.score = values, R.hseg = U.dev(s_xs);
+        if ((rc = isect_move(c, W, vs.from(), (u32)M, { vs.to(), nullptr, nullptr, M }, zero, uflag, s))) return rc;
+        hb.flip(), vs.flip();
+        R.ids = hb.from(), R.score = vs.from(), R.hseg = U.dev(s_xs);
     }
     if ((rc = ranked_tail(c, R, Q, g.q0, o, U, s_sel, slots, s_of, s_hs, S.flag, ws.sflag, s))) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
@@ -4014,6 +4066,13 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
     const bool excl = !g.xt.empty();
     const auto s_xo = U.add<u32>(excl ? Q + 1 : 0);
     const auto s_xt = U.add<ansx_isb_list>(g.xt.size());
+    // (ansx_topk_query_batch_dev only: the group has an optional term or a threshold -- a third table, its weights and the
+    // thresholds go up too)
+    const bool should = o.msm && (!g.ot.empty() || std::any_of(o.msm + g.q0, o.msm + g.q1, [](u32 m) { return m != 0; }));
+    const auto s_oo = U.add<u32>(should ? Q + 1 : 0);
+    const auto s_ot = U.add<ansx_isb_list>(should ? g.ot.size() : 0);
+    const auto s_ow = U.add<u32>(should ? g.ot.size() : 0);
+    const auto s_m = U.add<u32>(should ? Q : 0);
     const size_t up = U.end;
     const auto s_seg = U.add<u32>(2 * q1);  // (the host's copy: the last step's, read back)
     const SelectSecs s_sel = select_sections(U, Q);
@@ -4024,6 +4083,11 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
     for (size_t j = 0; j < Q; j++) U.pin(s_wd)[j] = o.weights[g.dterm[j]];
     for (size_t e = 0; e < g.rterm.size(); e++) U.pin(s_rw)[e] = o.weights[g.rterm[e]];
     if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
+    if (should) {
+        U.put(s_oo, g.ot_off.data()), U.put(s_m, o.msm + g.q0);
+        if (!g.ot.empty()) U.put(s_ot, g.ot.data());
+        for (size_t e = 0; e < g.oterm.size(); e++) U.pin(s_ow)[e] = o.oweights[g.oterm[e]];
+    }
     if ((rc = group_upload(c, U, up, &s_sel, s))) return rc;
     Flip seg = { { U.dev(s_seg), U.dev(s_seg) + q1 } };
     const u32* zero = U.dev(s_fl);
@@ -4051,8 +4115,16 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
     }
     if (nc == 0) return ranked_nothing(c, Q, g.q0, o, s);  // (a round left nothing: no id is in all lists of any query)
     const IsectWork W(ws.work, nc, false);  // (total: the last round's, nc, at the same place)
-    if (excl) {  // ONE exclusion step over what the rounds left, the scores moved by the same ballots: no wait
-        if ((rc = bool_exclude_step(c, W, ids, { buf.from(), buf.to(), nullptr }, nc, nullptr, seg.from(), Q, U.dev(s_xo), U.dev(s_xt),
+    if (should) {  // ansx_topk_query_batch_dev: ONE optional step over what the rounds left, whatever the optional lists: no wait
+        const ShouldTables T = { U.dev(s_oo), U.dev(s_ot), U.dev(s_ow), U.dev(s_m), o.qform };
+        if ((rc = should_step(c, W, ids, pay, { buf.from(), buf.to(), nullptr }, { sb.from(), sb.to(), nullptr }, nc, nullptr, seg.from(), Q,
+                 T, S.flag, seg.to(), zero, zero, s)))
+            return rc;
+        buf.flip(), sb.flip(), seg.flip();
+    }
+    if (excl) {  // ONE exclusion step over what the rounds left (behind an optional step, their count is the device's), the
+                 // scores moved by the same ballots: no wait
+        if ((rc = bool_exclude_step(c, W, ids, { buf.from(), buf.to(), nullptr }, nc, should ? W.total : nullptr, seg.from(), Q, U.dev(s_xo), U.dev(s_xt),
                  S.flag, seg.to(), zero, zero, s)))
             return rc;
         if ((rc = isect_move(c, W, sb.from(), nc, { sb.to(), nullptr, nullptr, nc }, zero, zero, s))) return rc;
@@ -4090,6 +4162,54 @@ int topk_bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
     if ((rc = unb_plan(F.n.data(), F.n.size(), F.rid, qoff, nq, budget, ANSX_UNION_TILE, &groups, bad_query, F.xrid, xqoff, true)))
         return rc;
     return run_groups(c, groups, [&](const UnbGroup& g) { return topk_group(c, F, g, o, bad_container, bad_query, s); }, s);
+}
+
+// ansx_topk_query_batch_dev (ansx_topk_query.h).  The front end of ansx_topk_bool_batch_dev over
+// ALL terms, required and optional, followed by the excluded terms; query_plan (ansx_plan.h, host-only): the terms split
+// by occur, the batch cut into runs of one kind, every run planned by its kind's planner under HALF the budget with its
+// query numbers offset -- ALL runs are planned before anything is launched -- and the runs' groups in batch order:
+//   kind R  topkb_group over the REQUIRED terms (isb_plan with the optional terms as orid / oqoff: their lists are
+//           decoded with the group's): the rounds as they are, then should_step where the group has an optional term or
+//           a threshold, then the exclusion step, which takes the device's count behind it, and the ranked tail;
+//   kind O  topk_group over the terms: up to k_topk_scores as it is, then atleast_step where some query asks for two
+//           entries or more, the exclusion step and the ranked tail.
+// Neither step adds a host wait: the waits per group are topkb_group's and topk_group's.  Workspace: topkb_group's with
+// the optional lists among the group's, plus per query 4 bytes of threshold and 4 of table offset and per optional term
+// 16 of table and 4 of weight; topk_group's, plus 8 bytes per query (threshold and bounds) where the threshold step runs.
+int topk_query_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
+    const size_t* pay_bytes, size_t count, const u32* terms, const u32* weights, const u8* occur, const u64* qoff, const u32* msm,
+    const u32* xterms, const u64* xqoff, size_t nq, u32 k, u32* d_out_ids, u32* d_out_scores, u32* out_counts, size_t* bad_container,
+    size_t* bad_query, hipStream_t s)
+{
+    int rc;
+    QueryFront F;
+    if ((rc = query_front(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, (size_t)qoff[nq], xterms,
+             xqoff ? (size_t)xqoff[nq] : 0, &F, bad_container, s)))
+        return rc;
+    const u64 budget = query_budget(c, true);
+    u32 pow2 = 1;
+    while (pow2 < k) pow2 <<= 1;
+    // the whole plan before anything is launched: a limit names the first query in batch order, whatever its kind
+    QueryPlan Q;
+    if ((rc = query_plan(F.n.data(), F.n.size(), F.rid, occur, qoff, msm, F.xrid, xqoff, nq, budget, ANSX_UNION_TILE, &Q, bad_query)))
+        return rc;
+    const QuerySplit& P = Q.split;
+    std::vector<u32> rw(P.rpos.size()), ow(P.opos.size());  // the weights beside the split terms
+    for (size_t i = 0; i < rw.size(); i++) rw[i] = weights[P.rpos[i]];
+    for (size_t i = 0; i < ow.size(); i++) ow[i] = weights[P.opos[i]];
+    TopkOut o = { weights, k, pow2, d_out_ids, d_out_scores, out_counts, d_pays != nullptr, true,
+        c->dbg.topk_bool_form == 1 ? ANSX_TOPKB_FORM_SEARCH : ANSX_TOPKB_FORM_DEFAULT };
+    o.msm = P.m.data(), o.oweights = ow.data(), o.qform = (u32)c->dbg.topk_query_form;
+    TopkOut oreq = o;  // (a group of kind R reads its drivers' and rounds' weights at the required terms' places)
+    oreq.weights = rw.data();
+    for (const QueryPlan::Run& run : Q.plans) {
+        for (const IsbGroup& g : run.req)
+            if ((rc = topkb_group(c, F, g, oreq, bad_container, bad_query, s))) return rc;
+        for (const UnbGroup& g : run.opt)
+            if ((rc = topk_group(c, F, g, o, bad_container, bad_query, s))) return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ANSX_OK;
 }
 
 // The argument checks of the random-access entry points, one per argument shape: everything a call decides before the
@@ -4431,6 +4551,11 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         const int w = debug_word(value, "search", "staged");
         if (w < 0) return ANSX_ERR_ARG;
         c->dbg.bool_form = w;
+    }
+    else if (!strcmp(name, "ANSX_TOPK_QUERY_FORM")) {
+        const int w = debug_word(value, "search", "staged");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.topk_query_form = w;
     }
     else if (!strcmp(name, "ANSX_TOPK_BOOL_FORM")) {
         const int w = debug_word(value, "search", "bounded");
@@ -4806,6 +4931,31 @@ int ansx_topk_bool_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const*
     if (nqueries == 0) return ANSX_OK;
     return run_call(c, stream, [&](hipStream_t s) {
         return topk_bool_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, op, true, terms, weights, (const u64*)qoff, xterms,
+            (const u64*)xqoff, nqueries, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
+    });
+}
+
+int ansx_topk_query_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff, size_t nqueries,
+    uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts, size_t* bad_container, size_t* bad_query,
+    void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (topk_args(c, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, qoff, nqueries, k, d_out_ids, d_out_scores, bad_container,
+            bad_query))
+        return ANSX_ERR_ARG;
+    if (bool_args(d_ins, count, ANSX_BOOL_ALL, xterms, xqoff, nqueries, bad_container, bad_query)) return ANSX_ERR_ARG;
+    if (occur)
+        for (size_t q = 0; q < nqueries; q++)
+            for (u64 j = qoff[q]; j < qoff[q + 1]; j++)
+                if (occur[j] != ANSX_OCCUR_SHOULD && occur[j] != ANSX_OCCUR_MUST) {
+                    if (bad_query) *bad_query = q;
+                    return ANSX_ERR_ARG;
+                }
+    if (nqueries == 0) return ANSX_OK;
+    return run_call(c, stream, [&](hipStream_t s) {
+        return topk_query_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, (const u64*)qoff, msm, xterms,
             (const u64*)xqoff, nqueries, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
     });
 }

@@ -576,6 +576,10 @@ struct IsbGroup {
     std::vector<u32> xt_list;        // ... the referenced list behind every entry of xt
     std::vector<u32> dterm, rterm;   // with want_terms (ansx_topk_bool_batch_dev): the named term (its place in rid) behind
                                      // every query's driver and behind every entry of rt -- a ranked query lays its weights there
+    std::vector<u32> ot_off;         // with optional terms (ansx_topk_query_batch_dev; plan_excl_tables over them): q1 - q0 + 1
+    std::vector<ansx_isb_list> ot;   // ... every query's optional lists
+    std::vector<u32> ot_list, oterm; // ... the referenced list behind every entry of ot, and the named term (its place in
+                                     // orid) -- the optional step lays its weights there
     u64 ints;                        // buffer + twice the candidates: what the budget bounds
     u32 rounds;                      // most rounds of a query
 };
@@ -585,9 +589,12 @@ struct IsbGroup {
 // 2^32; a query over the budget alone is a group of its own.  A list two groups name is decoded in both.
 // xrid / xqoff: null, or the lists every query excludes (plan_excl_tables).
 // want_terms: dterm and rterm are filled beside drv and rt; nothing else differs.
+// orid / oqoff: null, or the OPTIONAL terms of every query (ansx_topk_query_batch_dev; rid / qoff are then its required
+// terms): their lists are decoded with the group's and count once in the budget as the excluded ones do, and the group
+// gets the tables ot_off / ot / ot_list / oterm.  They choose no driver and take no round.
 static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64* qoff, size_t nq, u64 budget,
     std::vector<IsbGroup>* groups, size_t* bad_query, const u32* xrid = nullptr, const u64* xqoff = nullptr,
-    bool want_terms = false)
+    bool want_terms = false, const u32* orid = nullptr, const u64* oqoff = nullptr)
 {
     groups->clear();
     std::vector<u32> stamp(nref, 0xFFFFFFFFu), slot(nref, 0), fresh, ord;
@@ -609,6 +616,7 @@ static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64*
             fresh.clear();
             plan_fresh(t, m, n, gid, stamp, fresh, add);
             if (xqoff) plan_fresh(xrid + xqoff[q], (size_t)(xqoff[q + 1] - xqoff[q]), n, gid, stamp, fresh, add);
+            if (oqoff) plan_fresh(orid + oqoff[q], (size_t)(oqoff[q + 1] - oqoff[q]), n, gid, stamp, fresh, add);
             add += 2 * nd;
             // (the stamps of a query that does not fit stay behind: the next group has another number)
             if (q > g.q0 && (add > budget || g.ints > budget - add || cand + nd > 0xFFFFFFFFull)) break;
@@ -649,6 +657,9 @@ static inline int isb_plan(const u64* n, size_t nref, const u32* rid, const u64*
         g.G[Q] = { 0, dst };
         g.rt_off[Q] = (u32)g.rt.size();
         plan_excl_tables(n, xrid, xqoff, g.q0, g.q1, g.at, slot, &g.xt_off, &g.xt, &g.xt_list);
+        plan_excl_tables(n, orid, oqoff, g.q0, g.q1, g.at, slot, &g.ot_off, &g.ot, &g.ot_list);
+        if (oqoff)
+            for (u64 j = oqoff[g.q0]; j < oqoff[g.q1]; j++) g.oterm.push_back((u32)j);
     }
     return ANSX_OK;
 }
@@ -788,6 +799,96 @@ static inline int unb_plan(const u64* n, size_t nref, const u32* rid, const u64*
             g.tiles.push_back(first);
         }
         plan_excl_tables(n, xrid, xqoff, g.q0, g.q1, g.at, slot, &g.xt_off, &g.xt, &g.xt_list);
+    }
+    return ANSX_OK;
+}
+
+// ------------------------------------------------------------------------------- required, optional, excluded terms
+// ansx_topk_query_batch_dev.  The terms of every query, split by occur (null: all optional): the
+// required ones for isb_plan's rid / qoff, the optional ones for its orid / oqoff, each with its list (rid[j], the
+// front end's entry of term j) and its place j in the caller's arrays, which is where its weight stands.  msm (null: all
+// zero) -> m: the threshold as it applies, msm[q] with a required term and max(msm[q], 1) without one.
+struct QuerySplit {
+    std::vector<u32> rrid, rpos, orid, opos;  // per required / per optional term: its list and its place in `terms`
+    std::vector<u64> rqoff, oqoff;            // nq + 1 each
+    std::vector<u32> m;                       // nq
+};
+static inline void query_split(const u32* rid, const u8* occur, const u64* qoff, const u32* msm, size_t nq, QuerySplit* S)
+{
+    S->rqoff.assign(nq + 1, 0), S->oqoff.assign(nq + 1, 0), S->m.resize(nq);
+    for (size_t q = 0; q < nq; q++) {
+        for (u64 j = qoff[q]; j < qoff[q + 1]; j++)
+            if (occur && occur[j]) S->rrid.push_back(rid[j]), S->rpos.push_back((u32)j);
+            else S->orid.push_back(rid[j]), S->opos.push_back((u32)j);
+        S->rqoff[q + 1] = S->rrid.size(), S->oqoff[q + 1] = S->orid.size();
+        const u32 t = msm ? msm[q] : 0u;
+        S->m[q] = S->rqoff[q + 1] > S->rqoff[q] ? t : std::max(t, 1u);
+    }
+}
+
+// The batch cut into maximal runs [a, b) of consecutive queries of one kind: req, "has a required term", or not.  Every
+// run is planned by its kind's planner and its groups run in batch order.
+struct QueryRun {
+    size_t a, b;
+    bool req;
+};
+static inline void query_runs(const u64* rqoff, size_t nq, std::vector<QueryRun>* runs)
+{
+    runs->clear();
+    for (size_t q = 0; q < nq; q++) {
+        const bool req = rqoff[q + 1] > rqoff[q];
+        if (runs->empty() || runs->back().req != req) runs->push_back({ q, q + 1, req });
+        else runs->back().b = q + 1;
+    }
+}
+
+// The whole plan of a call: the split, the runs and every run's groups -- req for a run with required terms (isb_plan
+// over them, the optional terms as orid / oqoff), opt for one without (unb_plan over the terms) -- with the groups' q0 / q1
+// as the CALL's query numbers.
+struct QueryPlan {
+    struct Run {
+        std::vector<IsbGroup> req;
+        std::vector<UnbGroup> opt;
+    };
+    QuerySplit split;
+    std::vector<QueryRun> runs;
+    std::vector<Run> plans;  // one per run
+};
+
+// rid: the front end's entry of every term, xrid / xqoff (null: nothing is excluded) of every excluded term; tile: the
+// outputs of a workgroup of the merge.  Every run is planned by its kind's planner over its own queries -- the offset
+// arrays advanced to the run's first query, the term arrays whole -- under `budget`, and ALL runs are planned before the
+// caller launches anything.  -> ANSX_OK, or ANSX_ERR_ARG with *bad_query the first query in BATCH order that exceeds
+// its plan's limits: with a required term its shortest required list has 2^32 ints or more (isb_plan); without one its
+// lists together have (unb_plan), or its group's round of merges has 2^31 tiles or more (then the group's first query).
+static inline int query_plan(const u64* n, size_t nref, const u32* rid, const u8* occur, const u64* qoff, const u32* msm,
+    const u32* xrid, const u64* xqoff, size_t nq, u64 budget, u32 tile, QueryPlan* P, size_t* bad_query)
+{
+    query_split(rid, occur, qoff, msm, nq, &P->split);
+    const QuerySplit& S = P->split;
+    query_runs(S.rqoff.data(), nq, &P->runs);
+    P->plans.assign(P->runs.size(), {});
+    for (size_t r = 0; r < P->runs.size(); r++) {
+        const size_t a = P->runs[r].a, cnt = P->runs[r].b - a;
+        const u64* xq = xqoff ? xqoff + a : nullptr;
+        size_t bad = 0;  // (the planners count from the run's first query)
+        int rc;
+        if (P->runs[r].req) {
+            rc = isb_plan(n, nref, S.rrid.data(), S.rqoff.data() + a, cnt, budget, &P->plans[r].req, &bad, xrid, xq, true, S.orid.data(),
+                S.oqoff.data() + a);
+            for (IsbGroup& g : P->plans[r].req) g.q0 += a, g.q1 += a;
+        } else {
+            rc = unb_plan(n, nref, rid, qoff + a, cnt, budget, tile, &P->plans[r].opt, &bad, xrid, xq, true);
+            for (UnbGroup& g : P->plans[r].opt) {
+                for (size_t k = 0; !rc && k < g.tiles.size(); k++)
+                    if (g.tiles[k] > 0x7FFFFFFFull) rc = ANSX_ERR_ARG, bad = g.q0;  // (a grid; g.q0: still the run's own number)
+                g.q0 += a, g.q1 += a;
+            }
+        }
+        if (rc) {
+            if (bad_query) *bad_query = a + bad;
+            return rc;
+        }
     }
     return ANSX_OK;
 }

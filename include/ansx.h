@@ -849,11 +849,63 @@ int ansx_topk_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* co
  * for the scan's flag word, one per round of its longest query (at least one round) and ONE behind the sort; ANY: ONE
  * behind the sort; one per call.  The exclusion step adds none.
  * Out of scope: floating-point or BM25 scores, k above 1024, dynamic pruning (WAND / MaxScore), a minimum-should-match
- * threshold, nested expressions. */
+ * threshold, nested expressions.  (Required, optional and excluded terms with a threshold in one query:
+ * ansx_topk_query_batch_dev, below.) */
 int ansx_topk_bool_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
     const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, int op, const uint32_t* terms,
     const uint32_t* weights, const uint64_t* qoff, const uint32_t* xterms, const uint64_t* xqoff, size_t nqueries,
     uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts, size_t* bad_container,
+    size_t* bad_query, void* stream);
+
+/* ansx_topk_query_batch_dev: ranked flat Boolean queries -- `+a b c -d`, or `a b c d` with "at least two must match" -- in
+ * one call (csrc/ansx_topk_query.h).  There is no op.  occur is a HOST array beside terms: occur[j]
+ * says whether the term named at terms[j] is required (ANSX_OCCUR_MUST) or optional (ANSX_OCCUR_SHOULD); NULL: every term
+ * is optional.  msm is a HOST array of nqueries thresholds; NULL: all zero.  Every other argument is
+ * ansx_topk_bool_batch_dev's.
+ * With s_t the ids of list t, M(q) the required and S(q) the optional terms of query q, matches(d) is the number of
+ * ENTRIES equal to d in the concatenation of s_t over S(q) as named -- the count ansx_union_batch_dev writes to d_out_cnt:
+ * a list named twice counts twice, and a list's own repeats count; for lists without repeats it is the number of
+ * matching optional terms.  The threshold is m = msm[q] where M(q) is not empty and max(msm[q], 1) where it is: a query
+ * of optional terms only must match one of them.  The result set R(q) is the set of DISTINCT ids d that occur in every
+ * list of M(q), have matches(d) >= m and occur in no excluded list of q.  The host takes no shortcut from m and the
+ * number of terms: the counts decide (a threshold no id reaches is an empty result).
+ * score(d) is ansx_topk_batch_dev's formula unchanged over ALL of the query's terms, required and optional: the sum over
+ * the postings of d of sat32(weights[j] * payload).  A list may be required and optional in one query: it scores twice
+ * and counts once in matches.  A list may be both a term and excluded.  The output image, out_counts, the order (score
+ * descending, id ascending) and ANSX_NO_ID / 0 behind the results are ansx_topk_bool_batch_dev's; 0xFFFFFFFF is an id
+ * like any other.
+ * Two identities, every output array equal byte for byte: every term MUST with msm NULL or all 0 is
+ * ansx_topk_bool_batch_dev under ANSX_BOOL_ALL; every term SHOULD (or occur NULL) with every msm[q] <= 1 (or NULL) is
+ * ansx_topk_bool_batch_dev under ANSX_BOOL_ANY -- and the same kernels are launched.
+ * A score of 2^32 - 1 or more OF AN ID OF R(q) is ANSX_ERR_DOMAIN with *bad_query = the first such query in batch order.
+ * An id that misses a required list, fails the threshold or is excluded is no error, whatever its partial sum.
+ * Errors, in this order: before the context is touched, ANSX_ERR_ARG for ansx_topk_bool_batch_dev's checks less the op,
+ * then for an occur[j] outside the two values (*bad_query).  nqueries == 0: ANSX_OK, nothing is launched.  Then
+ * ANSX_ERR_FORMAT with *bad_container = the smallest referenced batch index, the id header before the payload; a list
+ * that is only excluded needs no payload.  Then ANSX_ERR_ARG with *bad_query = the first query in batch order that
+ * exceeds its plan's limits -- with a required term: its shortest REQUIRED list has 2^32 ints or more; without one: the
+ * union plan's limits -- every query is planned before anything is launched.  Then the parents' device errors.
+ * No trace is left in the context, which stays usable after any error.
+ * Groups: the batch is cut into maximal runs of consecutive queries of one kind -- "has a required term" or "has none" --
+ * and every run is planned as the parent of its kind plans it, under half of ANSX_ISECT_BATCH_INTS; the runs' groups
+ * execute in batch order and every result lands at q * k.  A batch that alternates kinds gets a group per run: a caller
+ * with many queries sorts them by kind.  With a required term the driver is the shortest REQUIRED list and the rounds
+ * are the other required lists; ONE further launch (k_topkq_should) serves all optional lists of all queries of the
+ * group, where it has an optional term or a threshold.  Without one the ANY path runs, with one filter
+ * (k_topkq_atleast) where some threshold is 2 or more.
+ * Host waits: exactly ansx_topk_bool_batch_dev's per group (ALL's with a required term, ANY's without); neither new step
+ * adds one.  Workspace: the parent's, the optional lists among the group's decoded lists, plus per query 4 bytes of
+ * threshold and 4 of table offset and per optional term 16 of table and 4 of weight (the match count lives in
+ * registers); without a required term the parent's, plus 8 bytes per query (threshold and bounds) where the filter runs.
+ * Out of scope: floating-point or BM25 scores, k above 1024, dynamic pruning, nested expressions beyond the flat form, a
+ * threshold counted in distinct terms instead of postings, one group across query kinds, an unranked variant
+ * (ansx_union_batch_dev's counts serve it). */
+#define ANSX_OCCUR_SHOULD 0
+#define ANSX_OCCUR_MUST 1
+int ansx_topk_query_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
+    size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts, size_t* bad_container,
     size_t* bad_query, void* stream);
 
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
