@@ -846,10 +846,31 @@ class _Codec:
         return self._topk_call("topk_query_batch_dev", in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, None,
                                out_scores_ptr, pay_ptrs, pay_sizes, stream, query=(occurs, min_should))
 
+    # ---- ranked queries with length-normalised scores (include/ansx.h)
+    def topk_scored_batch_dev(self, in_ptrs, in_bytes, queries, weights, occurs, min_should, excludes, k, out_ids_ptr,
+                              out_scores_ptr=None, pay_ptrs=None, pay_sizes=None, stream=None, scorer=None):
+        """topk_query_batch_dev in which a posting contributes weight * table[min(payload, tf_rows - 1)][norms[id]] -- a
+        quantised impact, BM25 among them -- and not weight * payload.  scorer: None (topk_query_batch_dev itself, the same
+        bytes and launches), or (norms_ptr, ndocs, table_ptr, tf_rows): the device address of ndocs uint8 norms, one per
+        document id, and of tf_rows * 256 uint32 impacts, row-major; bm25_norms and bm25_table make both for BM25, the IDF
+        being the weights.  A scorer needs pay_ptrs (the term frequencies).  An id of ndocs or more in a list that is a term
+        raises AnsxError(ERR_DOMAIN) with .bad_container; everything else is topk_query_batch_dev's."""
+        return self._topk_call("topk_scored_batch_dev", in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, None,
+                               out_scores_ptr, pay_ptrs, pay_sizes, stream, query=(occurs, min_should), scorer=scorer, scored=True)
+
     def _topk_call(self, what, in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, op, out_scores_ptr, pay_ptrs,
-                   pay_sizes, stream, query=None):
+                   pay_sizes, stream, query=None, scorer=None, scored=False):
         """What the ranked calls share: the checks of their arguments and the call; op None: ansx_topk_batch_dev or, with
-        query = (occurs, min_should), ansx_topk_query_batch_dev"""
+        query = (occurs, min_should), ansx_topk_query_batch_dev -- with scored, ansx_topk_scored_batch_dev, scorer its
+        (norms_ptr, ndocs, table_ptr, tf_rows) or None"""
+        sc = None
+        if scorer is not None:
+            if isinstance(scorer, (str, bytes)) or not hasattr(scorer, "__len__") or len(scorer) != 4:
+                raise ValueError("scorer must be (norms_ptr, ndocs, table_ptr, tf_rows)")
+            for name, v, top in zip(("norms_ptr", "ndocs", "table_ptr", "tf_rows"), scorer, (1 << 64, 1 << 64, 1 << 64, 1 << 32)):
+                if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < top):
+                    raise ValueError("scorer: %s must be a non-negative integer, got %r" % (name, v))
+            sc = L.Scorer(scorer[0], int(scorer[1] or 0), scorer[2], int(scorer[3] or 0))
         ptrs, sizes, terms, qoff = self._batch_queries(in_ptrs, in_bytes, queries, 0)
         nc, nq = ptrs.size, len(queries)
         occ = msm = None
@@ -915,7 +936,12 @@ class _Codec:
         head = (self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None,
                 None if pays is None else pays.ctypes.data, None if psizes is None else psizes.ctypes.data, nc)
         tail = (nq, int(k), out_ids_ptr, out_scores_ptr, counts.ctypes.data if nq else None, C.byref(bad_c), C.byref(bad_q), stream)
-        if query is not None:
+        if scored:
+            st = L.lib().ansx_topk_scored_batch_dev(
+                *head, terms.ctypes.data, wts.ctypes.data, None if occ is None else occ.ctypes.data, qoff.ctypes.data,
+                None if msm is None else msm.ctypes.data, None if xterms is None else xterms.ctypes.data,
+                None if xqoff is None else xqoff.ctypes.data, None if sc is None else C.byref(sc), *tail)
+        elif query is not None:
             st = L.lib().ansx_topk_query_batch_dev(
                 *head, terms.ctypes.data, wts.ctypes.data, None if occ is None else occ.ctypes.data, qoff.ctypes.data,
                 None if msm is None else msm.ctypes.data, None if xterms is None else xterms.ctypes.data,
@@ -995,6 +1021,67 @@ class ANSint(_Codec):
 
 
 # ---------------------------------------------------------------- container parsing (host)
+
+# ---- BM25 as quantised integer impacts for topk_scored_batch_dev; pure numpy, no device
+# The lower edge of every length class: lengths 0 .. 31 have a class each, and from 32 on every octave [2^e, 2^(e + 1))
+# is cut into 16 classes of equal width (sixteenth-octaves), up to 2^19; class 255 holds every length from 507904 on.
+# Written out as literals, so that no floating-point rounding ever decides a class.
+BM25_LENGTH_EDGES = (
+    0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15,
+    16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31,
+    32, 34, 36, 38, 40, 42, 44, 46, 48, 50, 52, 54, 56, 58, 60, 62,
+    64, 68, 72, 76, 80, 84, 88, 92, 96, 100, 104, 108, 112, 116, 120, 124,
+    128, 136, 144, 152, 160, 168, 176, 184, 192, 200, 208, 216, 224, 232, 240, 248,
+    256, 272, 288, 304, 320, 336, 352, 368, 384, 400, 416, 432, 448, 464, 480, 496,
+    512, 544, 576, 608, 640, 672, 704, 736, 768, 800, 832, 864, 896, 928, 960, 992,
+    1024, 1088, 1152, 1216, 1280, 1344, 1408, 1472, 1536, 1600, 1664, 1728, 1792, 1856, 1920, 1984,
+    2048, 2176, 2304, 2432, 2560, 2688, 2816, 2944, 3072, 3200, 3328, 3456, 3584, 3712, 3840, 3968,
+    4096, 4352, 4608, 4864, 5120, 5376, 5632, 5888, 6144, 6400, 6656, 6912, 7168, 7424, 7680, 7936,
+    8192, 8704, 9216, 9728, 10240, 10752, 11264, 11776, 12288, 12800, 13312, 13824, 14336, 14848, 15360, 15872,
+    16384, 17408, 18432, 19456, 20480, 21504, 22528, 23552, 24576, 25600, 26624, 27648, 28672, 29696, 30720, 31744,
+    32768, 34816, 36864, 38912, 40960, 43008, 45056, 47104, 49152, 51200, 53248, 55296, 57344, 59392, 61440, 63488,
+    65536, 69632, 73728, 77824, 81920, 86016, 90112, 94208, 98304, 102400, 106496, 110592, 114688, 118784, 122880, 126976,
+    131072, 139264, 147456, 155648, 163840, 172032, 180224, 188416, 196608, 204800, 212992, 221184, 229376, 237568, 245760,
+    253952, 262144, 278528, 294912, 311296, 327680, 344064, 360448, 376832, 393216, 409600, 425984, 442368, 458752, 475136,
+    491520, 507904,
+)
+
+
+def bm25_norms(doc_lens):
+    """The norm byte of every document for topk_scored_batch_dev: doc_lens (non-negative integers, one per document id)
+    -> np.uint8, the class c of a length l being the last one with BM25_LENGTH_EDGES[c] <= l (np.searchsorted over the
+    edges, integers throughout).  Longer documents never get a smaller class; bm25_table takes the class's lower edge as
+    the length of all of its documents."""
+    lens = np.asarray(doc_lens)
+    if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "ui"):
+        raise ValueError("doc_lens must be a flat sequence of integers")
+    if lens.size and int(lens.min()) < 0:
+        raise ValueError("doc_lens must not be negative")
+    edges = np.array(BM25_LENGTH_EDGES, dtype=np.uint64)
+    return (np.searchsorted(edges, lens.astype(np.uint64), side="right") - 1).astype(np.uint8)
+
+
+def bm25_table(avgdl, k1=1.2, b=0.75, tf_rows=64, bits=16):
+    """The impact table of BM25 for topk_scored_batch_dev: np.uint32 of shape (tf_rows, 256), table[t][c] the quantised
+    term-frequency part of a posting with payload t in a document of class c (bm25_norms).  Row 0 is zero, and for t >= 1
+      table[t][c] = round((2^bits - 1) / (k1 + 1) * t * (k1 + 1) / (t + k1 * (1 - b + b * rep(c) / avgdl)))
+    in float64, rep(c) = BM25_LENGTH_EDGES[c], the class's lower edge.  The BM25 factor t (k1 + 1) / (t + ...) lies below
+    k1 + 1, so every entry lies below 2^bits; bits <= 24, so that an IDF weight of up to 8 bits cannot saturate one
+    posting.  The IDF is not in the table: it is the caller's weight of the term.  A payload of tf_rows or more scores as
+    tf_rows - 1 (the factor is within k1 / (tf_rows + k1) of its limit there)."""
+    for name, v, lo, hi in (("tf_rows", tf_rows, 1, 256), ("bits", bits, 1, 24)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    avgdl, k1, b = float(avgdl), float(k1), float(b)
+    if not (avgdl > 0 and np.isfinite(avgdl)) or not (k1 >= 0 and np.isfinite(k1)) or not 0 <= b <= 1:
+        raise ValueError("bm25_table needs avgdl > 0, k1 >= 0 and b in [0, 1]")
+    t = np.arange(tf_rows, dtype=np.float64)[:, None]
+    rep = np.array(BM25_LENGTH_EDGES, dtype=np.float64)[None, :]
+    scale = (2.0 ** bits - 1.0) / (k1 + 1.0)
+    table = np.zeros((tf_rows, 256), dtype=np.float64)
+    table[1:] = np.floor(scale * t[1:] * (k1 + 1.0) / (t[1:] + k1 * (1.0 - b + b * rep / avgdl)) + 0.5)
+    return table.astype(np.uint32)
+
 
 def unpack_restart_points(raw):
     """29-byte restart points -> (cursors u32[n], states u64[n * 4]): states 0, 1 as one 104-bit little-endian

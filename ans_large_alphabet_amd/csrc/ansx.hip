@@ -41,6 +41,7 @@
 #include "ansx_topk.h"
 #include "ansx_topk_bool.h"
 #include "ansx_topk_query.h"
+#include "ansx_topk_scored.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_batchdevranges.h"
@@ -147,6 +148,7 @@ struct ansx_ctx {
     std::map<u32, DevBuf> geo;   // tree nodes of the interpolative code per alphabet size, tabulated per symbol-array size (<= 4096)
     DevBuf geo_big;              // the same for alphabets up to geo_big_cap symbols (symbol arrays above 4096 slots, fast model path:
     u32 geo_big_cap = 0;         //   sized from the geometry's alphabet hint, cap^2 * 4 bytes -- 284 MB for fidelity 5 on 2^20-valued lists)
+    std::map<u32, u32> impact_wgs;  // k_topk_impacts, staged: the workgroups the chip holds, per (uint4 per lane, rows in LDS)
     int last_gather_ranks = 0;   // ranks of the communicator the last ansx_gather_containers call ran on (ncclCommCount)
     std::set<u64> wide_hint;     // geometries that met a frame above 2^16: wide restart points from the start
     std::map<u64, u32> t_hint;   // largest chosen candidate index t (frame M0 * 2^t) + 1 seen per geometry: lanes per block of k_candidates
@@ -210,6 +212,10 @@ struct ansx_ctx {
         int topk_query_form = 0;      // ANSX_TOPK_QUERY_FORM: 0 k_topkq_should's own rule, 1 "search", 2 "staged" (ANSX_TOPKQ_FORM_*; tests and the bench tool force one)
         int topk_bool_form = 0;       // ANSX_TOPK_BOOL_FORM: 0 the default of k_topkb_match, 1 "search", 2 "bounded" (tests and the bench tool force one)
         int intersect_form = 0;       // ANSX_INTERSECT_FORM: 0 by ANSX_ISECT_FULL_PER_BLOCK, 1 "selective", 2 "full" (tests and the bench tool force one)
+        int topk_impact_form = 0;     // ANSX_TOPK_IMPACT_FORM: 0 the default of k_topk_impacts (staged), 1 "global", 2 "staged" (ANSX_IMPACT_FORM_*; tests and the bench tool force one)
+        u32 topk_impact_rounds = 0;   // ANSX_TOPK_IMPACT_TILE: 1024 | 2048 | 4096 postings per tile of k_topk_impacts, kept as uint4 per lane (0 = ANSX_IMPACT_ROUNDS_DEFAULT; the bench tool measures all three)
+        u32 topk_impact_stage = 0;    // ANSX_TOPK_IMPACT_STAGE: the rows of the table its staged form keeps in LDS, 1 .. ANSX_IMPACT_STAGE_MAX (0 = ANSX_IMPACT_STAGE_ROWS)
+        u32 topk_impact_grid = 0;     // ANSX_TOPK_IMPACT_GRID: the most workgroups of its staged form (0 = what the chip holds; tests force a few, so that one walks several tiles)
         u64 isect_batch_ints = 0;     // ANSX_ISECT_BATCH_INTS: the ints a group of ansx_intersect_batch_dev or ansx_union_batch_dev may take (0 = ANSX_ISECT_BATCH_INTS_DEFAULT; tests force small groups)
         u32 range_sums_wg_max = 0;    // ANSX_RANGE_SUMS_WG_MAX: the largest block the one-kernel scan of the range sums takes (0 = ANSX_RS_WG_MAX; the bench tool measures both sides of the switch)
     } dbg;
@@ -3834,7 +3840,70 @@ struct TopkOut {
     // isb_plan's orid; qform: ANSX_TOPKQ_FORM_*
     const u32 *msm = nullptr, *oweights = nullptr;
     u32 qform = 0;
+    // ansx_topk_scored_batch_dev: null, or the scorer that turns the payloads into impacts
+    const ansx_scorer* scorer = nullptr;
 };
+
+// ... the impact step of ansx_topk_scored_batch_dev (ansx_topk_scored.h) behind the scan: the payload of every posting of
+// every list of the group that has one -> its impact, in place (k_topk_impacts: ONE launch).  impact_tables, before
+// anything of the group is launched: the host's table over the group's lists (impact_plan), which goes up with the
+// group's other tables; more than 2^31 - 1 tiles: ANSX_ERR_ARG with the group's first query.  An id the norms have no
+// entry for lowers the scan's flag word: the wait that brings it home is the group's own.
+struct ImpactTables {
+    std::vector<ansx_impact_list> P;
+    u64 tiles = 0;
+    u32 rounds = ANSX_IMPACT_ROUNDS_DEFAULT;
+};
+int impact_tables(const ansx_ctx* c, const std::vector<u32>& lists, const std::vector<u64>& at, const std::vector<u32>* payof, size_t q0,
+    ImpactTables* T, size_t* bad_query)
+{
+    T->rounds = c->dbg.topk_impact_rounds ? c->dbg.topk_impact_rounds : ANSX_IMPACT_ROUNDS_DEFAULT;
+    const int rc = impact_plan(lists, at, payof, T->rounds * ANSX_IMPACT_NT * 4u, &T->P, &T->tiles);
+    if (rc && bad_query) *bad_query = q0;
+    return rc;
+}
+// the workgroups of the staged form that the chip holds at the kernel's occupancy with srows rows of stage
+template <u32 ROUNDS> int impact_staged_wgs(ansx_ctx* c, u32 srows, u32* wgs)
+{
+    const u32 key = ROUNDS << 16 | srows;
+    const auto it = c->impact_wgs.find(key);
+    if (it != c->impact_wgs.end()) {
+        *wgs = it->second;
+        return ANSX_OK;
+    }
+    int per_cu = 0;
+    HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_topk_impacts<ROUNDS, true>, (int)ANSX_IMPACT_NT,
+                  (size_t)srows * ANSX_IMPACT_COLS * 4u));
+    *wgs = c->impact_wgs[key] = (u32)std::max(per_cu, 1) * c->num_cus;
+    return ANSX_OK;
+}
+template <u32 ROUNDS> int impact_launch(ansx_ctx* c, const ansx_scorer& sc, const ImpactTables& T, const ansx_impact_list* d_P,
+    const u32* ids, u32* pay, u32* sflag, hipStream_t s)
+{
+    const u32 np = (u32)T.P.size(), ntiles = (u32)T.tiles, rows = sc.tf_rows;
+    // (the default is the staged form: DESIGN.md section 3q, "the form")
+    if (c->dbg.topk_impact_form == (int)ANSX_IMPACT_FORM_GLOBAL) {
+        LAUNCH(c, "k_topk_impacts", (k_topk_impacts<ROUNDS, false>), ntiles, ANSX_IMPACT_NT, 0, s, ids, pay, d_P, np, ntiles, sc.d_norms,
+            (u64)sc.ndocs, sc.d_table, rows, 0u, sflag);
+        return ANSX_OK;
+    }
+    const u32 srows = std::min(rows, c->dbg.topk_impact_stage ? c->dbg.topk_impact_stage : ANSX_IMPACT_STAGE_ROWS);
+    u32 wgs = 0;
+    int rc;
+    if ((rc = impact_staged_wgs<ROUNDS>(c, srows, &wgs))) return rc;
+    if (c->dbg.topk_impact_grid) wgs = c->dbg.topk_impact_grid;
+    LAUNCH(c, "k_topk_impacts", (k_topk_impacts<ROUNDS, true>), std::min(wgs, ntiles), ANSX_IMPACT_NT, (size_t)srows * ANSX_IMPACT_COLS * 4u,
+        s, ids, pay, d_P, np, ntiles, sc.d_norms, (u64)sc.ndocs, sc.d_table, rows, srows, sflag);
+    return ANSX_OK;
+}
+int impact_step(ansx_ctx* c, const ansx_scorer& sc, const ImpactTables& T, const ansx_impact_list* d_P, const u32* ids, u32* pay,
+    u32* sflag, hipStream_t s)
+{
+    if (T.P.empty()) return ANSX_OK;  // (no list of the group has a payload: nothing is scored)
+    return T.rounds == 1 ? impact_launch<1>(c, sc, T, d_P, ids, pay, sflag, s)
+        : T.rounds == 2  ? impact_launch<2>(c, sc, T, d_P, ids, pay, sflag, s)
+                         : impact_launch<4>(c, sc, T, d_P, ids, pay, sflag, s);
+}
 
 // ... the optional step of ansx_topk_query_batch_dev (ansx_topk_query.h) behind the required rounds: the n candidates of
 // `cand` with `score` beside them (d_total: null, or where the device holds their count), query j's in [seg[j], seg[j + 1]),
@@ -3932,6 +4001,8 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
     const u64 L = g.at.back(), M = g.seg[Q];
     if (M == 0) return ranked_nothing(c, Q, g.q0, o, s);  // (every list is empty: nothing is decoded)
     if ((rc = merge_tiles_check(g, bad_query))) return rc;
+    ImpactTables IT;  // (ansx_topk_scored_batch_dev only: the lists whose payloads become impacts)
+    if (o.scorer && (rc = impact_tables(c, g.lists, g.at, F.payof, g.q0, &IT, bad_query))) return rc;
     // the lists | their payloads | two key and two value merge buffers | the scores | the slots (u64: at an even int); each
     // with the decoders' slack behind
     const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)M, 4) + 16;
@@ -3960,6 +4031,7 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
     // (ansx_topk_query_batch_dev only: some query of the group asks for two entries or more -- the thresholds go up too)
     const bool least = o.msm && std::any_of(o.msm + g.q0, o.msm + g.q1, [](u32 m) { return m >= 2; });
     const auto s_m = U.add<u32>(least ? Q : 0);
+    const auto s_ip = U.add<ansx_impact_list>(IT.P.size());
     const size_t up = U.end;
     const auto s_hs = U.add<u32>(q1);  // (the host's copy: read back)
     const auto s_xs = U.add<u32>(excl ? q1 : 0);
@@ -3970,6 +4042,7 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
     U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
     if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
     if (least) U.put(s_m, o.msm + g.q0);
+    if (!IT.P.empty()) U.put(s_ip, IT.P.data());
     u32* hw = U.pin(s_w);
     for (size_t i = 0; i < g.pterm.size(); i++) hw[i] = g.pterm[i] == ANSX_TOPK_NONE ? 0u : o.weights[g.pterm[i]];
     if ((rc = group_upload(c, U, up, &s_sel, s))) return rc;
@@ -3979,6 +4052,7 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
 
     SumsPlan S;
     if ((rc = group_scan(c, ids, g.at, s, &S))) return rc;
+    if (o.scorer && (rc = impact_step(c, *o.scorer, IT, U.dev(s_ip), ids, pay, S.flag, s))) return rc;
     for (u32 r = 0; r < g.rounds; r++) {
         const u32 np = g.roff[r + 1] - g.roff[r];
         if (np == 0) continue;  // (the queries that have this round are empty)
@@ -4041,6 +4115,8 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
     const size_t Q = g.q1 - g.q0, q1 = rup(Q + 1, 4);
     const u64 L = g.at.back(), nc0 = g.G[Q].dst;
     if (nc0 == 0) return ranked_nothing(c, Q, g.q0, o, s);  // (every driver is empty: nothing is decoded)
+    ImpactTables IT;  // (ansx_topk_scored_batch_dev only: the lists whose payloads become impacts)
+    if (o.scorer && (rc = impact_tables(c, g.lists, g.at, F.payof, g.q0, &IT, bad_query))) return rc;
     // the lists | their payloads | two candidate and two score buffers | the slots (u64: at an even int); each with the
     // decoders' slack behind
     const size_t o_c = rup((size_t)L, 4) + 16, half = rup((size_t)nc0, 4) + 16;
@@ -4073,6 +4149,7 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
     const auto s_ot = U.add<ansx_isb_list>(should ? g.ot.size() : 0);
     const auto s_ow = U.add<u32>(should ? g.ot.size() : 0);
     const auto s_m = U.add<u32>(should ? Q : 0);
+    const auto s_ip = U.add<ansx_impact_list>(IT.P.size());
     const size_t up = U.end;
     const auto s_seg = U.add<u32>(2 * q1);  // (the host's copy: the last step's, read back)
     const SelectSecs s_sel = select_sections(U, Q);
@@ -4088,12 +4165,14 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
         if (!g.ot.empty()) U.put(s_ot, g.ot.data());
         for (size_t e = 0; e < g.oterm.size(); e++) U.pin(s_ow)[e] = o.oweights[g.oterm[e]];
     }
+    if (!IT.P.empty()) U.put(s_ip, IT.P.data());
     if ((rc = group_upload(c, U, up, &s_sel, s))) return rc;
     Flip seg = { { U.dev(s_seg), U.dev(s_seg) + q1 } };
     const u32* zero = U.dev(s_fl);
 
     SumsPlan S;
     if ((rc = group_scan(c, ids, g.at, s, &S))) return rc;
+    if (o.scorer && (rc = impact_step(c, *o.scorer, IT, U.dev(s_ip), ids, pay, S.flag, s))) return rc;
     if ((rc = gather_drivers(c, ids, U.dev(s_g), Q, nc0, buf.from(), seg.from(), S.flag, s))) return rc;
     HIPCHK(c, hipMemcpyAsync(ws.sflag, S.flag, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
@@ -4176,10 +4255,13 @@ int topk_bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
 // Neither step adds a host wait: the waits per group are topkb_group's and topk_group's.  Workspace: topkb_group's with
 // the optional lists among the group's, plus per query 4 bytes of threshold and 4 of table offset and per optional term
 // 16 of table and 4 of weight; topk_group's, plus 8 bytes per query (threshold and bounds) where the threshold step runs.
-int topk_query_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
+// ansx_topk_scored_batch_dev (ansx_topk_scored.h) is the same call with a scorer: the same front,
+// plan, runs and groups, and in every group that decodes something impact_step behind the scan -- one launch, no wait, 24
+// bytes of table per list with a payload.  scorer null: ansx_topk_query_batch_dev, launch for launch.
+int topk_scored_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
     const size_t* pay_bytes, size_t count, const u32* terms, const u32* weights, const u8* occur, const u64* qoff, const u32* msm,
-    const u32* xterms, const u64* xqoff, size_t nq, u32 k, u32* d_out_ids, u32* d_out_scores, u32* out_counts, size_t* bad_container,
-    size_t* bad_query, hipStream_t s)
+    const u32* xterms, const u64* xqoff, const ansx_scorer* scorer, size_t nq, u32 k, u32* d_out_ids, u32* d_out_scores, u32* out_counts,
+    size_t* bad_container, size_t* bad_query, hipStream_t s)
 {
     int rc;
     QueryFront F;
@@ -4200,6 +4282,7 @@ int topk_query_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const
     TopkOut o = { weights, k, pow2, d_out_ids, d_out_scores, out_counts, d_pays != nullptr, true,
         c->dbg.topk_bool_form == 1 ? ANSX_TOPKB_FORM_SEARCH : ANSX_TOPKB_FORM_DEFAULT };
     o.msm = P.m.data(), o.oweights = ow.data(), o.qform = (u32)c->dbg.topk_query_form;
+    o.scorer = scorer;
     TopkOut oreq = o;  // (a group of kind R reads its drivers' and rounds' weights at the required terms' places)
     oreq.weights = rw.data();
     for (const QueryPlan::Run& run : Q.plans) {
@@ -4210,6 +4293,14 @@ int topk_query_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const
     }
     HIPCHK(c, hipStreamSynchronize(s));
     return ANSX_OK;
+}
+int topk_query_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
+    const size_t* pay_bytes, size_t count, const u32* terms, const u32* weights, const u8* occur, const u64* qoff, const u32* msm,
+    const u32* xterms, const u64* xqoff, size_t nq, u32 k, u32* d_out_ids, u32* d_out_scores, u32* out_counts, size_t* bad_container,
+    size_t* bad_query, hipStream_t s)
+{
+    return topk_scored_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, qoff, msm, xterms, xqoff, nullptr,
+        nq, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
 }
 
 // The argument checks of the random-access entry points, one per argument shape: everything a call decides before the
@@ -4557,6 +4648,22 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         if (w < 0) return ANSX_ERR_ARG;
         c->dbg.topk_query_form = w;
     }
+    else if (!strcmp(name, "ANSX_TOPK_IMPACT_FORM")) {
+        const int w = debug_word(value, "global", "staged");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.topk_impact_form = w;
+    }
+    else if (!strcmp(name, "ANSX_TOPK_IMPACT_TILE")) {
+        const u32 v = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
+        if (v != 0 && v != 1024 && v != 2048 && v != 4096) return ANSX_ERR_ARG;
+        c->dbg.topk_impact_rounds = v / 1024u;
+    }
+    else if (!strcmp(name, "ANSX_TOPK_IMPACT_STAGE")) {
+        const u32 v = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
+        if (v > ANSX_IMPACT_STAGE_MAX) return ANSX_ERR_ARG;
+        c->dbg.topk_impact_stage = v;
+    }
+    else if (!strcmp(name, "ANSX_TOPK_IMPACT_GRID")) c->dbg.topk_impact_grid = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_TOPK_BOOL_FORM")) {
         const int w = debug_word(value, "search", "bounded");
         if (w < 0) return ANSX_ERR_ARG;
@@ -4935,13 +5042,12 @@ int ansx_topk_bool_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const*
     });
 }
 
-int ansx_topk_query_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
-    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
-    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff, size_t nqueries,
-    uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts, size_t* bad_container, size_t* bad_query,
-    void* stream)
+// ... what ansx_topk_query_batch_dev and ansx_topk_scored_batch_dev check: topk_args, the excluded terms, the occur values
+static int topk_query_args(const ansx_ctx* c, const uint8_t* const* d_ins, const size_t* in_bytes, const uint8_t* const* d_pays,
+    const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights, const uint8_t* occur, const uint64_t* qoff,
+    const uint32_t* xterms, const uint64_t* xqoff, size_t nqueries, uint32_t k, const uint32_t* d_out_ids, const uint32_t* d_out_scores,
+    size_t* bad_container, size_t* bad_query)
 {
-    // (every argument check comes before the context is touched)
     if (topk_args(c, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, qoff, nqueries, k, d_out_ids, d_out_scores, bad_container,
             bad_query))
         return ANSX_ERR_ARG;
@@ -4953,10 +5059,46 @@ int ansx_topk_query_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const
                     if (bad_query) *bad_query = q;
                     return ANSX_ERR_ARG;
                 }
+    return ANSX_OK;
+}
+
+int ansx_topk_query_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff, size_t nqueries,
+    uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts, size_t* bad_container, size_t* bad_query,
+    void* stream)
+{
+    // (every argument check comes before the context is touched)
+    if (topk_query_args(c, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, qoff, xterms, xqoff, nqueries, k, d_out_ids,
+            d_out_scores, bad_container, bad_query))
+        return ANSX_ERR_ARG;
     if (nqueries == 0) return ANSX_OK;
     return run_call(c, stream, [&](hipStream_t s) {
         return topk_query_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, (const u64*)qoff, msm, xterms,
             (const u64*)xqoff, nqueries, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
+    });
+}
+
+int ansx_topk_scored_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
+    const ansx_scorer* scorer, size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts,
+    size_t* bad_container, size_t* bad_query, void* stream)
+{
+    // (every argument check comes before the context is touched: the parent's, then the scorer's)
+    if (topk_query_args(c, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, qoff, xterms, xqoff, nqueries, k, d_out_ids,
+            d_out_scores, bad_container, bad_query))
+        return ANSX_ERR_ARG;
+    if (scorer) {
+        if (!d_pays) return ANSX_ERR_ARG;  // (a term frequency is needed)
+        if (!scorer->d_norms || !scorer->d_table || ((uintptr_t)scorer->d_table & 3u)) return ANSX_ERR_ARG;
+        if (scorer->ndocs == 0 || (u64)scorer->ndocs > ((u64)1 << 32)) return ANSX_ERR_ARG;
+        if (scorer->tf_rows == 0 || scorer->tf_rows > ANSX_IMPACT_MAX_ROWS) return ANSX_ERR_ARG;
+    }
+    if (nqueries == 0) return ANSX_OK;
+    return run_call(c, stream, [&](hipStream_t s) {
+        return topk_scored_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, (const u64*)qoff, msm, xterms,
+            (const u64*)xqoff, scorer, nqueries, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
     });
 }
 

@@ -893,4 +893,28 @@ static inline int query_plan(const u64* n, size_t nref, const u32* rid, const u8
     return ANSX_OK;
 }
 
+// ------------------------------------------------------------------------------- length-normalised scores
+// ansx_topk_scored_batch_dev (ansx_topk_scored.h).  The lists of a group that k_topk_impacts
+// rewrites: list lists[k] of the group, ints [at[k], at[k + 1]) of its buffers, gets an entry when it has ints and a
+// payload (payof: per referenced list the entry of its payload or ANSX_TOPK_NONE -- a list that is only excluded has
+// none; null: no list has one), in the order of the buffer, with the tiles of `tile` ints in front of it and its place
+// k, which is what the scan's flag word names.  *tiles: the launch's tiles.  A group's lists are distinct, so a list
+// several queries name is rewritten once.  -> ANSX_OK, or ANSX_ERR_ARG where the tiles exceed 2^31 - 1 (a grid, as
+// merge_tiles_check has it for a round of merges).
+static inline int impact_plan(const std::vector<u32>& lists, const std::vector<u64>& at, const std::vector<u32>* payof, u32 tile,
+    std::vector<ansx_impact_list>* P, u64* tiles)
+{
+    P->clear();
+    u64 t = 0;
+    for (size_t k = 0; k < lists.size(); k++) {
+        const u64 n = at[k + 1] - at[k];
+        if (n == 0 || !payof || (*payof)[lists[k]] == ANSX_TOPK_NONE) continue;
+        if (t > 0x7FFFFFFFull) return ANSX_ERR_ARG;  // (and no entry's `tile` wraps)
+        P->push_back({ at[k], n, (u32)t, (u32)k });
+        t += impact_tiles(at[k], n, tile);
+    }
+    *tiles = t;
+    return t > 0x7FFFFFFFull ? ANSX_ERR_ARG : ANSX_OK;
+}
+
 }  // namespace ansx_plan

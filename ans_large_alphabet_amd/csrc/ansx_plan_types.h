@@ -1,7 +1,7 @@
 // ansx -- the integer names and the plain structs and constants the host's plans (ansx_plan.h) fill and the kernels read
-// them through.  No code but the arithmetic of ansx_topk_batch_dev's selection and of the device plan of
-// ansx_decode_batch_device_ranges_dev at its end: it builds with a plain host compiler, and the kernel headers take it
-// through ansx_dev.h.
+// them through.  No code but the arithmetic of ansx_topk_batch_dev's selection, of a tile of k_topk_impacts and of the
+// device plan of ansx_decode_batch_device_ranges_dev at its end: it builds with a plain host compiler, and the kernel
+// headers take it through ansx_dev.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -199,6 +199,53 @@ ANSX_PLAN_FN u32 topk_pick(const u32* h, u32 n, u32 want, u32* above)
     *above = a;
     return d;
 }
+
+// Length-normalised scores (ansx_topk_scored_batch_dev, ansx_topk_scored.h).  k_topk_impacts
+// rewrites the payloads of a group's lists in place; the host's table (ansx_plan.h, impact_plan) has an entry per list
+// that has a payload.  A tile is `tile` ints (a multiple of 4) of the group's buffers, counted from the list's start
+// rounded DOWN to four ints, so that every uint4 of a tile is aligned: tile t of a list covers the buffer's ints
+// [at - (at & 3) + t * tile, ... + tile), cut to the list's own [at, at + n).  The arithmetic of one tile and one
+// posting is written here once: the kernel and the CPU check (tests/tools/topk_scored_plan_check.cpp) both run it.
+struct ansx_impact_list {
+    u64 at, n;  // the list's ids and payloads: ints [at, at + n) of the group's two buffers (n > 0)
+    u32 tile;   // the launch's tiles in front of this list (strictly ascending; the first is 0)
+    u32 pos;    // its place in the group's lists: what the scan's flag word names
+};
+
+#define ANSX_IMPACT_COLS 256u  // the columns of a scorer's table: a norm is a byte
+#define ANSX_IMPACT_MAX_ROWS 256u  // ... and the most rows it may have (ansx_scorer.tf_rows)
+
+// the tiles of a list
+ANSX_PLAN_FN u64 impact_tiles(u64 at, u64 n, u32 tile) { return ((at & 3u) + n + tile - 1u) / tile; }
+
+// the list of tile t: the last entry of P[0 .. np) with tile <= t (P[0].tile == 0)
+ANSX_PLAN_FN u32 impact_list_of(const ansx_impact_list* P, u32 np, u32 t)
+{
+    u32 lo = 0, hi = np - 1u;
+    while (lo < hi) {
+        const u32 mid = lo + (hi - lo + 1u) / 2u;
+        if (P[mid].tile <= t) lo = mid;
+        else hi = mid - 1u;
+    }
+    return lo;
+}
+
+// the buffer's int where tile t of the list starts (a multiple of 4)
+ANSX_PLAN_FN u64 impact_tile_start(const ansx_impact_list& L, u32 t, u32 tile) { return (L.at & ~(u64)3u) + (u64)(t - L.tile) * tile; }
+
+// bit j: int i + j of the buffer (i a multiple of 4) belongs to the list; 15: the uint4 at i is the list's own
+ANSX_PLAN_FN u32 impact_mask(const ansx_impact_list& L, u64 i)
+{
+    u32 m = 0;
+    for (u32 j = 0; j < 4u; j++) m |= (i + j >= L.at && i + j < L.at + L.n) ? 1u << j : 0u;
+    return m;
+}
+
+// an id the norms have no entry for (64 bits: ndocs == 2^32 admits every id)
+ANSX_PLAN_FN bool impact_bad_id(u32 id, u64 ndocs) { return (u64)id >= ndocs; }
+
+// the table's word of (payload, norm): below rows * ANSX_IMPACT_COLS whatever the payload, for a norm below 256
+ANSX_PLAN_FN u32 impact_word(u32 tf, u32 norm, u32 rows) { return (tf < rows - 1u ? tf : rows - 1u) * ANSX_IMPACT_COLS + norm; }
 
 // Ranges of a batch planned on the device (ansx_decode_batch_device_ranges_dev, ansx_batchdevranges.h; DESIGN.md
 // section 3d, "device plan").  The referenced containers, ordered by geometry group and by batch position inside a

@@ -810,8 +810,9 @@ int ansx_bool_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* co
  * Unreferenced containers and payloads are not examined and may be NULL.  No trace is left in the context, which stays
  * usable after any error.  Groups, workspace and host waits: DESIGN.md section 3m -- the union's groups under half of
  * ANSX_ISECT_BATCH_INTS; one wait for the headers, per group its decode passes' and ONE behind the sort, one per call.
- * Out of scope: floating-point scores, k above 1024, dynamic pruning (WAND / MaxScore).  Exclusion behind a ranked query
- * and a ranked AND: ansx_topk_bool_batch_dev, below. */
+ * Out of scope: floating-point scores (length-normalised integer impacts, BM25 among them: ansx_topk_scored_batch_dev,
+ * below), k above 1024, dynamic pruning (WAND / MaxScore).  Exclusion behind a ranked query and a ranked AND:
+ * ansx_topk_bool_batch_dev, below. */
 #define ANSX_TOPK_MAX_K 1024u
 int ansx_topk_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
     const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
@@ -848,8 +849,8 @@ int ansx_topk_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* co
  * lists, under half of ANSX_ISECT_BATCH_INTS.  Host waits: one for the headers; per group its decode passes'; ALL: one
  * for the scan's flag word, one per round of its longest query (at least one round) and ONE behind the sort; ANY: ONE
  * behind the sort; one per call.  The exclusion step adds none.
- * Out of scope: floating-point or BM25 scores, k above 1024, dynamic pruning (WAND / MaxScore), a minimum-should-match
- * threshold, nested expressions.  (Required, optional and excluded terms with a threshold in one query:
+ * Out of scope: floating-point scores (BM25-style integer impacts: ansx_topk_scored_batch_dev, below), k above 1024,
+ * dynamic pruning (WAND / MaxScore), a minimum-should-match threshold, nested expressions.  (Required, optional and excluded terms with a threshold in one query:
  * ansx_topk_query_batch_dev, below.) */
 int ansx_topk_bool_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
     const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, int op, const uint32_t* terms,
@@ -897,8 +898,8 @@ int ansx_topk_bool_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_
  * adds one.  Workspace: the parent's, the optional lists among the group's decoded lists, plus per query 4 bytes of
  * threshold and 4 of table offset and per optional term 16 of table and 4 of weight (the match count lives in
  * registers); without a required term the parent's, plus 8 bytes per query (threshold and bounds) where the filter runs.
- * Out of scope: floating-point or BM25 scores, k above 1024, dynamic pruning, nested expressions beyond the flat form, a
- * threshold counted in distinct terms instead of postings, one group across query kinds, an unranked variant
+ * Out of scope: floating-point scores (BM25-style integer impacts: ansx_topk_scored_batch_dev, below), k above 1024,
+ * dynamic pruning, nested expressions beyond the flat form, a threshold counted in distinct terms instead of postings, one group across query kinds, an unranked variant
  * (ansx_union_batch_dev's counts serve it). */
 #define ANSX_OCCUR_SHOULD 0
 #define ANSX_OCCUR_MUST 1
@@ -907,6 +908,46 @@ int ansx_topk_query_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8
     const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
     size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts, size_t* bad_container,
     size_t* bad_query, void* stream);
+
+/* ansx_topk_scored_batch_dev: ansx_topk_query_batch_dev with length-normalised scores -- BM25 and its kin as quantised
+ * integer impacts -- in one call (csrc/ansx_topk_scored.h).  scorer stands in front of nqueries;
+ * every other argument is ansx_topk_query_batch_dev's, in its order.
+ * A scorer names two DEVICE arrays: d_norms, a byte per document id d < ndocs (its length class), and d_table, tf_rows
+ * rows of 256 uint32_t, row-major (4-byte aligned): the impact of a payload (a term frequency) at a norm.  A payload of
+ * tf_rows or more reads row tf_rows - 1; a payload of 0 reads row 0.  With a scorer the contribution of posting i of list
+ * t, named at terms[j], is
+ *   sat32(weights[j] * d_table[min(p_t[i], tf_rows - 1) * 256 + d_norms[s_t[i]]])
+ * where the parent has sat32(weights[j] * p_t[i]).  Everything else is ansx_topk_query_batch_dev's contract word for
+ * word: the result sets and matches, the thresholds, exclusion and order, the output image and out_counts, the overflow
+ * rule (a score of 2^32 - 1 or more of an id of R(q)), the groups, the budget and the host waits.  The IDF is the
+ * caller's weights; bm25_norms / bm25_table of the Python package make the two arrays for BM25.
+ * scorer == NULL is ansx_topk_query_batch_dev: the same bytes come out and the same kernels are launched.
+ * Errors, in this order: before the context is touched, ANSX_ERR_ARG for every check of ansx_topk_query_batch_dev with
+ * the same *bad_query / *bad_container; then, with neither touched, for a scorer with d_pays == NULL (a term frequency is
+ * needed); a null d_norms or d_table, or a d_table that is not 4-byte aligned; ndocs == 0 or ndocs > 2^32; tf_rows == 0
+ * or tf_rows > 256.  nqueries == 0: ANSX_OK, nothing is launched.  Then the parent's errors, and one more found on the
+ * device: an id of ndocs or more in a list that has a payload in the group -- a list some query names as a required or
+ * optional term -- is ANSX_ERR_DOMAIN with *bad_container = that list's batch index; nothing is read at that id.  Where
+ * several lists of a group offend, or one of them and a list whose id sum leaves 32 bits, the one first in the group's
+ * buffer is named.  A list that is only excluded is never looked up: its ids may be anything.  The comparison is made in
+ * 64 bits: ndocs == 2^32 admits the id 0xFFFFFFFF.  A plan's limit more: the tiles of the rewriting kernel over a
+ * group, 2^31 - 1 at most (ANSX_ERR_ARG with *bad_query = the group's first query).
+ * No trace is left in the context, which stays usable after any error.
+ * Per group that decodes something ONE launch is added (k_topk_impacts, behind the scan, in front of the first kernel
+ * that reads a payload), no host wait, no upload of its own, and 24 bytes of table per list with a payload.
+ * Out of scope: floating-point scores, per-field norms or several scorers in one call, norms wider than a byte, k above
+ * 1024, dynamic pruning, a scorer for the unranked calls. */
+typedef struct ansx_scorer {
+    const uint8_t* d_norms;  /* DEVICE, ndocs bytes: the length class of document id d */
+    size_t ndocs;            /* 1 .. 2^32 */
+    const uint32_t* d_table; /* DEVICE, tf_rows * 256 uint32_t, row-major: the impact of (tf, norm) */
+    uint32_t tf_rows;        /* 1 .. 256; a payload of tf_rows or more reads row tf_rows - 1 */
+} ansx_scorer;
+int ansx_topk_scored_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
+    const ansx_scorer* scorer, size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts,
+    size_t* bad_container, size_t* bad_query, void* stream);
 
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
