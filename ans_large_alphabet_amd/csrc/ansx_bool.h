@@ -46,27 +46,7 @@
 #define ANSX_BOOL_FORM_SEARCH 1u  // never stages
 #define ANSX_BOOL_FORM_STAGED 2u  // stages whenever the range fits
 
-// the first j in [lo, hi) with list[j] >= t, hi where there is none
-template <class P> ANSX_D u64 bx_lower(P list, u64 lo, u64 hi, u32 t)
-{
-    while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        if (list[mid] >= t) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// the first j in [lo, hi) with list[j] > t, hi where there is none
-ANSX_D u64 bx_upper(const u32* __restrict__ list, u64 lo, u64 hi, u32 t)
-{
-    while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        if (list[mid] > t) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
+// (bx_lower, bx_upper: ansx_query_tile.h)
 
 // cand[0, n): the candidates, those of query j in [seg[j], seg[j + 1]); total: null, or the device's count of them
 // (clamped to n).  The grid covers n > 0.  form: ANSX_BOOL_FORM_*.

@@ -27,11 +27,7 @@
 #pragma once
 
 #include "ansx_nextgeq.h"
-
-#define ANSX_ISECT_NT 256u
-#define ANSX_ISECT_CPT 4u                                   // candidates per thread
-#define ANSX_ISECT_TILE (ANSX_ISECT_NT * ANSX_ISECT_CPT)    // ... per workgroup: 16 ballot words
-#define ANSX_ISECT_WORDS (ANSX_ISECT_TILE / 64u)
+#include "ansx_query_tile.h"  // the tile's size (ANSX_ISECT_NT, _CPT, _TILE, _WORDS) and the frame of the batch kernels
 
 // The ballot of `member` over the wave -> word (i0 / 64) of ballots, i0 the wave's first candidate, when that is one;
 // its popcount to wcnt[k], k the word's index in the tile.  Every lane of the wave calls it.

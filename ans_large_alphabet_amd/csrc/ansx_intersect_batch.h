@@ -19,28 +19,19 @@
 // Memory safety for ANY content of the containers.  Every index comes from the host: the tables (ansx_plan.h,
 // isb_plan: src + count and at + n lie inside the buffer it laid out from the checked headers; rt_off ascends to the
 // entries of rt) and seg, whose first form is the table's dst and whose later forms k_isectb_bounds derives from
-// counts of ballot bits, so 0 <= seg[j] <= seg[j + 1] <= nc always.  k_isectb_gather writes candidate i < nc and entry
-// i <= Q of seg, and nothing when the scan's flag word names a list.  k_isectb_match reads candidate i < nc, ids
-// [at, at + n) only, and writes word i / 64 of the ballots and its own tile's count (isect_ballot, isect_tile_count).
+// counts of ballot bits, so 0 <= seg[j] <= seg[j + 1] <= nc always: what the frame's pieces (ansx_query_tile.h) assume,
+// and their contracts are not repeated here.  k_isectb_gather writes candidate i < nc and entry i <= Q of seg, and
+// nothing when the scan's flag word names a list.  k_isectb_match reads candidate i < nc and ids [at, at + n) only
+// (bx_lower), and writes through isect_ballot and isect_tile_count.
 // k_isectb_bounds reads ballot words of tiles that hold a candidate below nc and writes entry j <= Q.  The host
 // enqueues no round before the decode's and the scan's flag words have come back clean.
 #pragma once
 
 #include "ansx_intersect.h"
 
-// last j in [lo, hi] with seg[j] <= i (seg[lo] <= i)
-ANSX_D u32 isb_query_of(const u32* __restrict__ seg, u32 lo, u32 hi, u32 i)
-{
-    while (lo < hi) {
-        const u32 mid = lo + (hi - lo + 1) / 2;
-        if (seg[mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // A workgroup per ANSX_ISECT_TILE indices i: candidate i < nc is id (i - dst) of its query's driver, the query the last
-// j with G[j].dst <= i (G[Q].dst == nc); entry i <= Q of seg is G[i].dst.  The grid covers max(nc, Q + 1).
+// j with G[j].dst <= i (G[Q].dst == nc): the frame's search with G[].dst as its key, seg being this kernel's output;
+// entry i <= Q of seg is G[i].dst.  The grid covers max(nc, Q + 1): a tile at or beyond nc writes entries of seg only.
 __global__ __launch_bounds__(ANSX_ISECT_NT) void k_isectb_gather(const u32* __restrict__ ids,
     const ansx_isb_query* __restrict__ G, u32 Q, u32* __restrict__ cand, u32 nc, u32* __restrict__ seg,
     const u32* __restrict__ sflag)
@@ -49,35 +40,15 @@ __global__ __launch_bounds__(ANSX_ISECT_NT) void k_isectb_gather(const u32* __re
     __shared__ u32 qb[2];
     const u32 tid = threadIdx.x;
     const u64 i0 = (u64)blockIdx.x * ANSX_ISECT_TILE;
-    if (tid == 0 && i0 < nc) {  // the queries of the tile's first and last candidate
-        const u64 last = (i0 + ANSX_ISECT_TILE < nc ? i0 + ANSX_ISECT_TILE : nc) - 1;
-        u32 lo = 0, hi = Q - 1;
-        while (lo < hi) {
-            const u32 mid = lo + (hi - lo + 1) / 2;
-            if (G[mid].dst <= i0) lo = mid;
-            else hi = mid - 1;
-        }
-        qb[0] = lo, hi = Q - 1;
-        while (lo < hi) {
-            const u32 mid = lo + (hi - lo + 1) / 2;
-            if (G[mid].dst <= last) lo = mid;
-            else hi = mid - 1;
-        }
-        qb[1] = lo;
-    }
-    __syncthreads();
+    const auto dst = [G](u32 j) { return G[j].dst; };
+    qt_prologue_by(dst, Q, i0, nc, qb);
 #pragma unroll
     for (u32 k = 0; k < ANSX_ISECT_CPT; k++) {
-        const u64 i = i0 + k * ANSX_ISECT_NT + tid;
+        const u64 i = qt_elem(i0, k, tid);
         if (i <= Q) seg[i] = (u32)G[i].dst;
         if (i >= nc) continue;
-        u32 lo = qb[0], hi = qb[1];
-        while (lo < hi) {
-            const u32 mid = lo + (hi - lo + 1) / 2;
-            if (G[mid].dst <= i) lo = mid;
-            else hi = mid - 1;
-        }
-        cand[i] = ids[G[lo].src + (i - G[lo].dst)];
+        const u32 q = qt_last_le(dst, qb[0], qb[1], i);
+        cand[i] = ids[G[q].src + (i - G[q].dst)];
     }
 }
 
@@ -90,31 +61,21 @@ __global__ __launch_bounds__(ANSX_ISECT_NT) void k_isectb_match(const u32* __res
     __shared__ u32 qb[2];
     const u32 tid = threadIdx.x;
     const u64 i0 = (u64)blockIdx.x * ANSX_ISECT_TILE;
-    if (tid == 0) {  // the queries of the tile's first and last candidate (the grid: i0 < nc)
-        const u64 last = (i0 + ANSX_ISECT_TILE < nc ? i0 + ANSX_ISECT_TILE : nc) - 1;
-        qb[0] = isb_query_of(seg, 0, Q - 1, (u32)i0);
-        qb[1] = isb_query_of(seg, qb[0], Q - 1, (u32)last);
-    }
-    __syncthreads();
+    qt_prologue(seg, Q, i0, nc, qb);  // (the grid: i0 < nc)
 #pragma unroll
     for (u32 k = 0; k < ANSX_ISECT_CPT; k++) {
-        const u64 i = i0 + k * ANSX_ISECT_NT + tid;
+        const u64 i = qt_elem(i0, k, tid);
         bool member = false;
         if (i < nc) {
-            const u32 q = isb_query_of(seg, qb[0], qb[1], (u32)i);  // (no step while the tile lies inside one query)
+            const u32 q = isb_query_of(seg, qb[0], qb[1], (u32)i);
             const u32 e = rt_off[q] + round;
             member = true;  // no list in this round: passed through
             if (e >= rt_off[q] && e < rt_off[q + 1]) {
                 const u32 t = cand[i];
                 const ansx_isb_list L = rt[e];
                 const u32* list = ids + L.at;
-                u64 lo = 0, hi = L.n;  // the first j with list[j] >= t, L.n where there is none
-                while (lo < hi) {
-                    const u64 mid = (lo + hi) >> 1;
-                    if (list[mid] >= t) hi = mid;
-                    else lo = mid + 1;
-                }
-                member = lo < L.n && list[lo] == t;
+                const u64 p = bx_lower(list, 0, L.n, t);
+                member = p < L.n && list[p] == t;
             }
         }
         isect_ballot(member, i - (tid & 63u), nc, k * (ANSX_ISECT_NT / 64u) + (tid >> 6), ballots, wcnt);

@@ -160,22 +160,17 @@ __global__ __launch_bounds__(ANSX_ISECT_NT) void k_topk_hist(const u32* __restri
     __shared__ u32 qb[2];
     __shared__ u32 lh[ANSX_TOPK_BINS];
     const u32 tid = threadIdx.x;
-    const u64 tot = total[0] < n ? total[0] : n;
+    const u64 tot = qt_clamp(total[0], n);
     const u64 i0 = (u64)blockIdx.x * ANSX_ISECT_TILE;
     if (i0 >= tot) return;  // (the whole workgroup)
-    if (tid == 0) {
-        const u64 last = (i0 + ANSX_ISECT_TILE < tot ? i0 + ANSX_ISECT_TILE : tot) - 1;
-        qb[0] = isb_query_of(hseg, 0, Q - 1, (u32)i0);
-        qb[1] = isb_query_of(hseg, qb[0], Q - 1, (u32)last);
-    }
-    if (tid < ANSX_TOPK_BINS) lh[tid] = 0;
-    __syncthreads();
+    if (tid < ANSX_TOPK_BINS) lh[tid] = 0;  // (in front of the prologue's barrier)
+    qt_prologue(hseg, Q, i0, (u32)tot, qb);
     const u32 q0 = qb[0], q1 = qb[1];
     const bool one = q0 == q1;  // (the workgroup's)
     const u64 pre1 = r ? prefix[q0] : 0ull;
 #pragma unroll
     for (u32 q = 0; q < ANSX_ISECT_CPT; q++) {
-        const u64 h = i0 + q * ANSX_ISECT_NT + tid;
+        const u64 h = qt_elem(i0, q, tid);
         const u64 key = h < tot ? topk_key(score[h], ids[h]) : 0ull;
         const u32 dg = topk_digit(key, r);
         if (one) {
@@ -251,21 +246,16 @@ __global__ __launch_bounds__(ANSX_ISECT_NT) void k_topk_gather(const u32* __rest
     if (sflag[0] != ANSX_SS_NONE) return;
     __shared__ u32 qb[2];
     const u32 tid = threadIdx.x;
-    const u64 tot = total[0] < n ? total[0] : n;
+    const u64 tot = qt_clamp(total[0], n);
     const u64 i0 = (u64)blockIdx.x * ANSX_ISECT_TILE;
     if (i0 >= tot) return;  // (the whole workgroup)
-    if (tid == 0) {
-        const u64 last = (i0 + ANSX_ISECT_TILE < tot ? i0 + ANSX_ISECT_TILE : tot) - 1;
-        qb[0] = isb_query_of(hseg, 0, Q - 1, (u32)i0);
-        qb[1] = isb_query_of(hseg, qb[0], Q - 1, (u32)last);
-    }
-    __syncthreads();
+    qt_prologue(hseg, Q, i0, (u32)tot, qb);
     const u32 q0 = qb[0], q1 = qb[1];
     const bool one = q0 == q1;  // (the workgroup's)
     const u64 pre1 = prefix[q0];
 #pragma unroll
     for (u32 q = 0; q < ANSX_ISECT_CPT; q++) {
-        const u64 h = i0 + q * ANSX_ISECT_NT + tid;
+        const u64 h = qt_elem(i0, q, tid);
         const u64 key = h < tot ? topk_key(score[h], ids[h]) : 0ull;
         if (one) {  // (every lane gets here): one atomic per wave, the lanes take consecutive places behind it
             const bool take = h < tot && key >= pre1;

@@ -11,7 +11,7 @@
 //                     which its query has a list it takes the lower bound t's position p in the list, member = found
 //                     and equal, and adds sat32(weight * payload[p']) for every p' >= p with list[p'] == t.
 //                     Two forms (ANSX_TOPK_BOOL_FORM): "search", the parent's whole-list lower bound; the default,
-//                     where a tile inside one query first bounds -- two threads, bx_lower / bx_upper of ansx_bool.h --
+//                     where a tile inside one query first bounds -- two threads, bx_lower / bx_upper --
 //                     the part [lo, hi) of the round's list its first and last candidate can meet, and every thread
 //                     searches only there.  A tile that spans queries searches whole lists.
 //   k_dr_scan<u64, false>, k_isect_compact (once for the ids, once more with the scores as its `cand`: the same
@@ -127,11 +127,11 @@ __global__ __launch_bounds__(ANSX_ISECT_NT) void k_topkb_check(const u32* __rest
     const u64* __restrict__ total, u32 n, u32* __restrict__ oflow, const u32* __restrict__ sflag)
 {
     if (sflag[0] != ANSX_SS_NONE) return;
-    const u64 tot = total ? (total[0] < n ? total[0] : n) : n;
+    const u64 tot = qt_limit(total, n);
     const u64 i0 = (u64)blockIdx.x * ANSX_ISECT_TILE;
 #pragma unroll
     for (u32 q = 0; q < ANSX_ISECT_CPT; q++) {
-        const u64 h = i0 + q * ANSX_ISECT_NT + threadIdx.x;
+        const u64 h = qt_elem(i0, q, threadIdx.x);
         if (h < tot && score[h] == 0xFFFFFFFFu) atomicMin(oflow, isb_query_of(hseg, 0, Q - 1, (u32)h));
     }
 }

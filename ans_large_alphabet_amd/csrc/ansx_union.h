@@ -119,15 +119,10 @@ __global__ __launch_bounds__(ANSX_ISECT_NT) void k_union_heads(const u32* __rest
     __shared__ u32 qb[2];
     const u32 tid = threadIdx.x;
     const u64 i0 = (u64)blockIdx.x * ANSX_ISECT_TILE;
-    if (tid == 0) {  // the queries of the tile's first and last element (the grid: i0 < n)
-        const u64 last = (i0 + ANSX_ISECT_TILE < n ? i0 + ANSX_ISECT_TILE : n) - 1;
-        qb[0] = isb_query_of(seg, 0, Q - 1, (u32)i0);
-        qb[1] = isb_query_of(seg, qb[0], Q - 1, (u32)last);
-    }
-    __syncthreads();
+    qt_prologue(seg, Q, i0, n, qb);  // (the grid: i0 < n)
 #pragma unroll
     for (u32 k = 0; k < ANSX_ISECT_CPT; k++) {
-        const u64 i = i0 + k * ANSX_ISECT_NT + tid;
+        const u64 i = qt_elem(i0, k, tid);
         bool head = false;
         if (i < n) {
             const u32 q = isb_query_of(seg, qb[0], qb[1], (u32)i);
