@@ -37,7 +37,7 @@ EXPORTS = [
     "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
     "ansx_intersect_ids_dev", "ansx_intersect_dev", "ansx_intersect_batch_dev", "ansx_union_batch_dev", "ansx_union_dev",
     "ansx_bool_batch_dev", "ansx_last_encode_form", "ansx_topk_batch_dev", "ansx_topk_bool_batch_dev",
-    "ansx_topk_query_batch_dev", "ansx_topk_scored_batch_dev",
+    "ansx_topk_query_batch_dev", "ansx_topk_scored_batch_dev", "ansx_topk_facets_batch_dev",
     "ansx_decode_batch_device_ranges_dev", "ansx_decode_batch_device_ranges_sums_dev",
 ]
 
@@ -51,6 +51,12 @@ class Scorer(C.Structure):
     """ansx_scorer: the norms (a byte per document id) and the impact table (tf_rows rows of 256 uint32) of
     ansx_topk_scored_batch_dev, both on the device"""
     _fields_ = [("d_norms", C.c_void_p), ("ndocs", C.c_size_t), ("d_table", C.c_void_p), ("tf_rows", C.c_uint32)]
+
+
+class Facets(C.Structure):
+    """ansx_facets: the column (a uint32 per document id) and the room for nqueries * nvalues counts of
+    ansx_topk_facets_batch_dev, both on the device"""
+    _fields_ = [("d_values", C.c_void_p), ("ndocs", C.c_size_t), ("nvalues", C.c_uint32), ("d_counts", C.c_void_p)]
 
 
 class ContainerHeader(C.Structure):
@@ -235,6 +241,9 @@ def lib():
     L.ansx_topk_scored_batch_dev.restype = C.c_int
     L.ansx_topk_scored_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Scorer), sz,
                                              C.c_uint32, vp, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]
+    L.ansx_topk_facets_batch_dev.restype = C.c_int
+    L.ansx_topk_facets_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Scorer),
+                                             C.POINTER(Facets), sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]
     L.ansx_union_dev.restype = C.c_int
     L.ansx_union_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(sz), vp]
     L.ansx_container_info.restype = C.c_int

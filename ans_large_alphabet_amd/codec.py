@@ -858,11 +858,36 @@ class _Codec:
         return self._topk_call("topk_scored_batch_dev", in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, None,
                                out_scores_ptr, pay_ptrs, pay_sizes, stream, query=(occurs, min_should), scorer=scorer, scored=True)
 
+    # ---- ranked queries with total hits and facet counts (include/ansx.h)
+    def topk_facets_batch_dev(self, in_ptrs, in_bytes, queries, weights, occurs, min_should, excludes, k, out_ids_ptr,
+                              out_scores_ptr=None, pay_ptrs=None, pay_sizes=None, stream=None, scorer=None, facets=None, totals=True):
+        """topk_scored_batch_dev that also says how many documents matched and how they fall over one column.  facets: None,
+        or (values_ptr, ndocs, nvalues, counts_ptr): the device address of ndocs uint32 values, one per document id, and of
+        len(queries) * nvalues uint32 counts, which the call zeroes and fills: counts[q * nvalues + v] = the ids of query
+        q's whole result with value v; a value of nvalues or more is counted nowhere.  Returns (counts, totals): what
+        topk_scored_batch_dev returns, and np.uint32 of len(queries), the size of every query's result, not cut to k
+        (totals=False: None, and the library is handed no array).  An id of ndocs or more in a result raises
+        AnsxError(ERR_DOMAIN) with .bad_query; everything else is topk_scored_batch_dev's.  With facets=None and
+        totals=False it is that call: the same bytes and launches."""
+        return self._topk_call("topk_facets_batch_dev", in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, None,
+                               out_scores_ptr, pay_ptrs, pay_sizes, stream, query=(occurs, min_should), scorer=scorer, scored=True,
+                               facets=(facets, bool(totals)))
+
     def _topk_call(self, what, in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, op, out_scores_ptr, pay_ptrs,
-                   pay_sizes, stream, query=None, scorer=None, scored=False):
+                   pay_sizes, stream, query=None, scorer=None, scored=False, facets=None):
         """What the ranked calls share: the checks of their arguments and the call; op None: ansx_topk_batch_dev or, with
         query = (occurs, min_should), ansx_topk_query_batch_dev -- with scored, ansx_topk_scored_batch_dev, scorer its
-        (norms_ptr, ndocs, table_ptr, tf_rows) or None"""
+        (norms_ptr, ndocs, table_ptr, tf_rows) or None -- with facets = ((values_ptr, ndocs, nvalues, counts_ptr) or None,
+        whether the totals are wanted), ansx_topk_facets_batch_dev, which returns (counts, totals or None)"""
+        fc = None
+        if facets is not None and facets[0] is not None:
+            fa = facets[0]
+            if isinstance(fa, (str, bytes)) or not hasattr(fa, "__len__") or len(fa) != 4:
+                raise ValueError("facets must be (values_ptr, ndocs, nvalues, counts_ptr)")
+            for name, v, top in zip(("values_ptr", "ndocs", "nvalues", "counts_ptr"), fa, (1 << 64, 1 << 64, 1 << 32, 1 << 64)):
+                if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < top):
+                    raise ValueError("facets: %s must be a non-negative integer, got %r" % (name, v))
+            fc = L.Facets(fa[0], int(fa[1] or 0), int(fa[2] or 0), fa[3])
         sc = None
         if scorer is not None:
             if isinstance(scorer, (str, bytes)) or not hasattr(scorer, "__len__") or len(scorer) != 4:
@@ -936,7 +961,14 @@ class _Codec:
         head = (self._ctx().handle, self.KIND, self.f, ptrs.ctypes.data if nc else None, sizes.ctypes.data if nc else None,
                 None if pays is None else pays.ctypes.data, None if psizes is None else psizes.ctypes.data, nc)
         tail = (nq, int(k), out_ids_ptr, out_scores_ptr, counts.ctypes.data if nq else None, C.byref(bad_c), C.byref(bad_q), stream)
-        if scored:
+        totals = np.zeros(nq, dtype=np.uint32) if facets is not None and facets[1] else None
+        if facets is not None:
+            st = L.lib().ansx_topk_facets_batch_dev(
+                *head, terms.ctypes.data, wts.ctypes.data, None if occ is None else occ.ctypes.data, qoff.ctypes.data,
+                None if msm is None else msm.ctypes.data, None if xterms is None else xterms.ctypes.data,
+                None if xqoff is None else xqoff.ctypes.data, None if sc is None else C.byref(sc), None if fc is None else C.byref(fc),
+                *tail[:5], totals.ctypes.data if totals is not None and nq else None, *tail[5:])
+        elif scored:
             st = L.lib().ansx_topk_scored_batch_dev(
                 *head, terms.ctypes.data, wts.ctypes.data, None if occ is None else occ.ctypes.data, qoff.ctypes.data,
                 None if msm is None else msm.ctypes.data, None if xterms is None else xterms.ctypes.data,
@@ -957,7 +989,7 @@ class _Codec:
             err.bad_container = int(bad_c.value) if bad_c.value != unset else None
             err.bad_query = int(bad_q.value) if bad_q.value != unset else None
             raise err
-        return counts
+        return counts if facets is None else (counts, totals)
 
     def union_dev(self, in_ptrs, in_bytes, out_ids_ptr, out_capacity, out_cnt_ptr=None, stream=None):
         """union_batch_dev's single query over all the lists of the batch in_ptrs / in_bytes, in batch order.  Returns the

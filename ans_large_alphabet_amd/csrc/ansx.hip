@@ -42,6 +42,7 @@
 #include "ansx_topk_bool.h"
 #include "ansx_topk_query.h"
 #include "ansx_topk_scored.h"
+#include "ansx_facet.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_batchdevranges.h"
@@ -149,6 +150,7 @@ struct ansx_ctx {
     DevBuf geo_big;              // the same for alphabets up to geo_big_cap symbols (symbol arrays above 4096 slots, fast model path:
     u32 geo_big_cap = 0;         //   sized from the geometry's alphabet hint, cap^2 * 4 bytes -- 284 MB for fidelity 5 on 2^20-valued lists)
     std::map<u32, u32> impact_wgs;  // k_topk_impacts, staged: the workgroups the chip holds, per (uint4 per lane, rows in LDS)
+    std::map<u32, u32> facet_wgs;   // k_facet_count, lds: the workgroups the chip holds, per (values in LDS, combining or not)
     int last_gather_ranks = 0;   // ranks of the communicator the last ansx_gather_containers call ran on (ncclCommCount)
     std::set<u64> wide_hint;     // geometries that met a frame above 2^16: wide restart points from the start
     std::map<u64, u32> t_hint;   // largest chosen candidate index t (frame M0 * 2^t) + 1 seen per geometry: lanes per block of k_candidates
@@ -216,6 +218,9 @@ struct ansx_ctx {
         u32 topk_impact_rounds = 0;   // ANSX_TOPK_IMPACT_TILE: 1024 | 2048 | 4096 postings per tile of k_topk_impacts, kept as uint4 per lane (0 = ANSX_IMPACT_ROUNDS_DEFAULT; the bench tool measures all three)
         u32 topk_impact_stage = 0;    // ANSX_TOPK_IMPACT_STAGE: the rows of the table its staged form keeps in LDS, 1 .. ANSX_IMPACT_STAGE_MAX (0 = ANSX_IMPACT_STAGE_ROWS)
         u32 topk_impact_grid = 0;     // ANSX_TOPK_IMPACT_GRID: the most workgroups of its staged form (0 = what the chip holds; tests force a few, so that one walks several tiles)
+        int facet_form = 0;           // ANSX_FACET_FORM: 0 the default of k_facet_count (lds where nvalues allows), 1 "atomic", 2 "lds" (ANSX_FACET_FORM_*; tests and the bench tool force one)
+        u32 facet_grid = 0;           // ANSX_FACET_GRID: the most workgroups of its lds form (0 = what the chip holds; tests force a few, so that one walks several tiles)
+        bool facet_no_combine = false;  // ANSX_FACET_NO_COMBINE: its lds form without the wave's combined add (the bench tool measures both)
         u64 isect_batch_ints = 0;     // ANSX_ISECT_BATCH_INTS: the ints a group of ansx_intersect_batch_dev or ansx_union_batch_dev may take (0 = ANSX_ISECT_BATCH_INTS_DEFAULT; tests force small groups)
         u32 range_sums_wg_max = 0;    // ANSX_RANGE_SUMS_WG_MAX: the largest block the one-kernel scan of the range sums takes (0 = ANSX_RS_WG_MAX; the bench tool measures both sides of the switch)
     } dbg;
@@ -3842,6 +3847,10 @@ struct TopkOut {
     u32 qform = 0;
     // ansx_topk_scored_batch_dev: null, or the scorer that turns the payloads into impacts
     const ansx_scorer* scorer = nullptr;
+    // ansx_topk_facets_batch_dev: null, or the column the results are counted over; null, or where
+    // every query's |R(q)| goes (host)
+    const ansx_facets* facets = nullptr;
+    u32* totals = nullptr;
 };
 
 // ... the impact step of ansx_topk_scored_batch_dev (ansx_topk_scored.h) behind the scan: the payload of every posting of
@@ -3958,10 +3967,58 @@ int topk_select(ansx_ctx* c, const Ranked& R, size_t Q, const Upload& U, const S
     return ANSX_OK;
 }
 
+// ... the facet step of ansx_topk_facets_batch_dev (ansx_facet.h) in front of the ranked tail, behind every step that
+// filters: the ids of R fall into the rows of counts of queries q0 .. q0 + Q (k_facet_count: ONE launch, no wait, no
+// upload).  An id the column has no entry for lowers the bad-id word, the third of s_of, which facet_word raises before
+// the group's upload and ranked_tail sends home with the overflow word.
+void facet_word(const TopkOut& o, const Upload& U, Upload::Sec<u32> s_of)
+{
+    if (o.facets) U.pin(s_of)[2] = ANSX_TOPK_NONE;
+}
+// the workgroups of the lds form that the chip holds at the kernel's occupancy with nvalues words of LDS
+template <bool COMBINE> int facet_lds_wgs(ansx_ctx* c, u32 nvalues, u32* wgs)
+{
+    const u32 key = nvalues << 1 | (COMBINE ? 1u : 0u);  // (nvalues <= ANSX_FACET_LDS_VALUES)
+    const auto it = c->facet_wgs.find(key);
+    if (it != c->facet_wgs.end()) {
+        *wgs = it->second;
+        return ANSX_OK;
+    }
+    int per_cu = 0;
+    HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_facet_count<true, COMBINE>, (int)ANSX_ISECT_NT, (size_t)nvalues * 4u));
+    *wgs = c->facet_wgs[key] = (u32)std::max(per_cu, 1) * c->num_cus;
+    return ANSX_OK;
+}
+template <bool COMBINE> int facet_launch_lds(ansx_ctx* c, const Ranked& R, size_t Q, const ansx_facets& f, u32* rows, u32* d_bad,
+    const u32* sflag, hipStream_t s)
+{
+    u32 wgs = 0;
+    int rc;
+    if ((rc = facet_lds_wgs<COMBINE>(c, f.nvalues, &wgs))) return rc;
+    if (c->dbg.facet_grid) wgs = c->dbg.facet_grid;
+    LAUNCH(c, "k_facet_count", (k_facet_count<true, COMBINE>), std::min(wgs, R.ntiles), ANSX_ISECT_NT, (size_t)f.nvalues * 4u, s, R.ids, R.hseg,
+        (u32)Q, R.total, R.n, f.d_values, (u64)f.ndocs, f.nvalues, rows, d_bad, sflag);
+    return ANSX_OK;
+}
+int facet_step(ansx_ctx* c, const Ranked& R, size_t Q, size_t q0, const TopkOut& o, u32* d_bad, const u32* sflag, hipStream_t s)
+{
+    const ansx_facets& f = *o.facets;
+    u32* rows = f.d_counts + q0 * (size_t)f.nvalues;
+    // (the default is the lds form where the values fit: DESIGN.md section 3r, "the form")
+    if (f.nvalues > ANSX_FACET_LDS_VALUES || c->dbg.facet_form == (int)ANSX_FACET_FORM_ATOMIC) {
+        LAUNCH(c, "k_facet_count", (k_facet_count<false, false>), R.ntiles, ANSX_ISECT_NT, 0, s, R.ids, R.hseg, (u32)Q, R.total, R.n, f.d_values,
+            (u64)f.ndocs, f.nvalues, rows, d_bad, sflag);
+        return ANSX_OK;
+    }
+    return c->dbg.facet_no_combine ? facet_launch_lds<false>(c, R, Q, f, rows, d_bad, sflag, s)
+                                   : facet_launch_lds<true>(c, R, Q, f, rows, d_bad, sflag, s);
+}
+
 // ... the ranked tail over the candidates R of queries q0 .. q0 + Q: k_topkb_check when the call asks for it (it lowers
 // the overflow word s_of over the scores that are left), the select, and the overflow word and the bounds on their way
 // home to the upload page (the bounds to s_back) -- in front of them the scan's flag word, to h_sflag, where the host
-// has not seen it yet (null: it has).  The caller waits; ranked_counts reads what came.
+// has not seen it yet (null: it has); with facets the bad-id word rides in the overflow word's copy.  The caller waits;
+// ranked_counts reads what came.
 int ranked_tail(ansx_ctx* c, const Ranked& R, size_t Q, size_t q0, const TopkOut& o, const Upload& U, const SelectSecs& T, u64* slots,
     Upload::Sec<u32> s_of, Upload::Sec<u32> s_back, const u32* sflag, u32* h_sflag, hipStream_t s)
 {
@@ -3970,19 +4027,23 @@ int ranked_tail(ansx_ctx* c, const Ranked& R, size_t Q, size_t q0, const TopkOut
         LAUNCH(c, "k_topkb_check", k_topkb_check, R.ntiles, ANSX_ISECT_NT, 0, s, R.score, R.hseg, (u32)Q, R.total, R.n, U.dev(s_of), sflag);
     if ((rc = topk_select(c, R, Q, U, T, slots, q0, o, sflag, s))) return rc;
     if (h_sflag) HIPCHK(c, hipMemcpyAsync(h_sflag, sflag, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(U.pin(s_of), U.dev(s_of), 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(U.pin(s_of), U.dev(s_of), o.facets ? 12 : 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(U.pin(s_back), R.hseg, 4 * (Q + 1), hipMemcpyDeviceToHost, s));
     return ANSX_OK;
 }
-// the first query of the group with a score of 2^32 - 1 or more among its results -> ANSX_ERR_DOMAIN; else the counts
+// the first query of the group with a score of 2^32 - 1 or more among its results -> ANSX_ERR_DOMAIN; then, with facets,
+// the first with an id the column has no entry for -> ANSX_ERR_DOMAIN; else the counts and the totals, from the same bounds
 int ranked_counts(const u32* h_of, const u32* h_seg, size_t Q, size_t q0, const TopkOut& o, size_t* bad_query)
 {
-    if (h_of[0] != ANSX_TOPK_NONE) {
-        if (bad_query) *bad_query = q0 + h_of[0];
+    const u32 bad = h_of[0] != ANSX_TOPK_NONE ? h_of[0] : o.facets ? h_of[2] : ANSX_TOPK_NONE;
+    if (bad != ANSX_TOPK_NONE) {
+        if (bad_query) *bad_query = q0 + bad;
         return ANSX_ERR_DOMAIN;
     }
     if (o.counts)
         for (size_t j = 0; j < Q; j++) o.counts[q0 + j] = std::min<u32>(o.k, h_seg[j + 1] - h_seg[j]);
+    if (o.totals)
+        for (size_t j = 0; j < Q; j++) o.totals[q0 + j] = h_seg[j + 1] - h_seg[j];
     return ANSX_OK;
 }
 // no query of the group has a result: every slot is ANSX_NO_ID / 0
@@ -3991,6 +4052,7 @@ int ranked_nothing(ansx_ctx* c, size_t Q, size_t q0, const TopkOut& o, hipStream
     LAUNCH(c, "k_topk_sort", k_topk_sort, (u32)Q, ANSX_ISECT_NT, 0, s, (const u64*)nullptr, (const u32*)nullptr, (u64)q0, o.k, o.pow2,
         o.ids, o.scores, (const u32*)nullptr);
     if (o.counts) memset(o.counts + q0, 0, 4 * Q);
+    if (o.totals) memset(o.totals + q0, 0, 4 * Q);
     return ANSX_OK;
 }
 
@@ -4039,6 +4101,7 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
     const SelectSecs s_sel = select_sections(U, Q);
     GroupWs ws;
     if ((rc = group_room(c, U, s_hs.off + s_hs.bytes, M, s_fl, &s_of, &ws))) return rc;
+    facet_word(o, U, s_of);
     U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
     if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
     if (least) U.put(s_m, o.msm + g.q0);
@@ -4088,6 +4151,7 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
         hb.flip(), vs.flip();
         R.ids = hb.from(), R.score = vs.from(), R.hseg = U.dev(s_xs);
     }
+    if (o.facets && (rc = facet_step(c, R, Q, g.q0, o, U.dev(s_of) + 2, S.flag, s))) return rc;
     if ((rc = ranked_tail(c, R, Q, g.q0, o, U, s_sel, slots, s_of, s_hs, S.flag, ws.sflag, s))) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
     if ((rc = scan_flag_status(ws, g.lists, *F.index, bad_container))) return rc;
@@ -4155,6 +4219,7 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
     const SelectSecs s_sel = select_sections(U, Q);
     GroupWs ws;
     if ((rc = group_room(c, U, s_seg.off + s_seg.bytes, nc0, s_fl, &s_of, &ws))) return rc;
+    facet_word(o, U, s_of);
     U.put(s_g, g.G.data()), U.put(s_ro, g.rt_off.data());
     if (!g.rt.empty()) U.put(s_rt, g.rt.data());
     for (size_t j = 0; j < Q; j++) U.pin(s_wd)[j] = o.weights[g.dterm[j]];
@@ -4210,6 +4275,7 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
         buf.flip(), sb.flip(), seg.flip();
     }
     const Ranked R = { buf.from(), sb.from(), seg.from(), W.total, nc, W.ntiles };
+    if (o.facets && (rc = facet_step(c, R, Q, g.q0, o, U.dev(s_of) + 2, S.flag, s))) return rc;
     if ((rc = ranked_tail(c, R, Q, g.q0, o, U, s_sel, slots, s_of, s_seg, S.flag, nullptr, s))) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
     return ranked_counts(U.pin(s_of), U.pin(s_seg), Q, g.q0, o, bad_query);
@@ -4258,10 +4324,13 @@ int topk_bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
 // ansx_topk_scored_batch_dev (ansx_topk_scored.h) is the same call with a scorer: the same front,
 // plan, runs and groups, and in every group that decodes something impact_step behind the scan -- one launch, no wait, 24
 // bytes of table per list with a payload.  scorer null: ansx_topk_query_batch_dev, launch for launch.
+// ansx_topk_facets_batch_dev (ansx_facet.h) is that call with facets and / or totals: the counts
+// zeroed once behind the plan, and in every group that reaches its ranked tail facet_step in front of it -- one launch, no
+// wait, no upload; the totals come from the bounds the tail's wait brings home.  Both null: the scored call, launch for launch.
 int topk_scored_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
     const size_t* pay_bytes, size_t count, const u32* terms, const u32* weights, const u8* occur, const u64* qoff, const u32* msm,
-    const u32* xterms, const u64* xqoff, const ansx_scorer* scorer, size_t nq, u32 k, u32* d_out_ids, u32* d_out_scores, u32* out_counts,
-    size_t* bad_container, size_t* bad_query, hipStream_t s)
+    const u32* xterms, const u64* xqoff, const ansx_scorer* scorer, const ansx_facets* facets, size_t nq, u32 k, u32* d_out_ids,
+    u32* d_out_scores, u32* out_counts, u32* out_totals, size_t* bad_container, size_t* bad_query, hipStream_t s)
 {
     int rc;
     QueryFront F;
@@ -4282,7 +4351,8 @@ int topk_scored_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, cons
     TopkOut o = { weights, k, pow2, d_out_ids, d_out_scores, out_counts, d_pays != nullptr, true,
         c->dbg.topk_bool_form == 1 ? ANSX_TOPKB_FORM_SEARCH : ANSX_TOPKB_FORM_DEFAULT };
     o.msm = P.m.data(), o.oweights = ow.data(), o.qform = (u32)c->dbg.topk_query_form;
-    o.scorer = scorer;
+    o.scorer = scorer, o.facets = facets, o.totals = out_totals;
+    if (facets) HIPCHK(c, hipMemsetAsync(facets->d_counts, 0, 4 * nq * (size_t)facets->nvalues, s));
     TopkOut oreq = o;  // (a group of kind R reads its drivers' and rounds' weights at the required terms' places)
     oreq.weights = rw.data();
     for (const QueryPlan::Run& run : Q.plans) {
@@ -4300,7 +4370,7 @@ int topk_query_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const
     size_t* bad_query, hipStream_t s)
 {
     return topk_scored_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, qoff, msm, xterms, xqoff, nullptr,
-        nq, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
+        nullptr, nq, k, d_out_ids, d_out_scores, out_counts, nullptr, bad_container, bad_query, s);
 }
 
 // The argument checks of the random-access entry points, one per argument shape: everything a call decides before the
@@ -4664,6 +4734,13 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         c->dbg.topk_impact_stage = v;
     }
     else if (!strcmp(name, "ANSX_TOPK_IMPACT_GRID")) c->dbg.topk_impact_grid = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
+    else if (!strcmp(name, "ANSX_FACET_FORM")) {
+        const int w = debug_word(value, "atomic", "lds");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.facet_form = w;
+    }
+    else if (!strcmp(name, "ANSX_FACET_GRID")) c->dbg.facet_grid = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
+    else if (!strcmp(name, "ANSX_FACET_NO_COMBINE")) c->dbg.facet_no_combine = on;
     else if (!strcmp(name, "ANSX_TOPK_BOOL_FORM")) {
         const int w = debug_word(value, "search", "bounded");
         if (w < 0) return ANSX_ERR_ARG;
@@ -5079,6 +5156,17 @@ int ansx_topk_query_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const
     });
 }
 
+// ... what a scorer adds, behind them
+static int scorer_args(const ansx_scorer* scorer, const uint8_t* const* d_pays)
+{
+    if (!scorer) return ANSX_OK;
+    if (!d_pays) return ANSX_ERR_ARG;  // (a term frequency is needed)
+    if (!scorer->d_norms || !scorer->d_table || ((uintptr_t)scorer->d_table & 3u)) return ANSX_ERR_ARG;
+    if (scorer->ndocs == 0 || (u64)scorer->ndocs > ((u64)1 << 32)) return ANSX_ERR_ARG;
+    if (scorer->tf_rows == 0 || scorer->tf_rows > ANSX_IMPACT_MAX_ROWS) return ANSX_ERR_ARG;
+    return ANSX_OK;
+}
+
 int ansx_topk_scored_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
     const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
     const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
@@ -5089,16 +5177,34 @@ int ansx_topk_scored_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* cons
     if (topk_query_args(c, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, qoff, xterms, xqoff, nqueries, k, d_out_ids,
             d_out_scores, bad_container, bad_query))
         return ANSX_ERR_ARG;
-    if (scorer) {
-        if (!d_pays) return ANSX_ERR_ARG;  // (a term frequency is needed)
-        if (!scorer->d_norms || !scorer->d_table || ((uintptr_t)scorer->d_table & 3u)) return ANSX_ERR_ARG;
-        if (scorer->ndocs == 0 || (u64)scorer->ndocs > ((u64)1 << 32)) return ANSX_ERR_ARG;
-        if (scorer->tf_rows == 0 || scorer->tf_rows > ANSX_IMPACT_MAX_ROWS) return ANSX_ERR_ARG;
+    if (scorer_args(scorer, d_pays)) return ANSX_ERR_ARG;
+    if (nqueries == 0) return ANSX_OK;
+    return run_call(c, stream, [&](hipStream_t s) {
+        return topk_scored_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, (const u64*)qoff, msm, xterms,
+            (const u64*)xqoff, scorer, nullptr, nqueries, k, d_out_ids, d_out_scores, out_counts, nullptr, bad_container, bad_query, s);
+    });
+}
+
+int ansx_topk_facets_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
+    const ansx_scorer* scorer, const ansx_facets* facets, size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores,
+    uint32_t* out_counts, uint32_t* out_totals, size_t* bad_container, size_t* bad_query, void* stream)
+{
+    // (every argument check comes before the context is touched: the parent's, the scorer's, then the facets')
+    if (topk_query_args(c, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, qoff, xterms, xqoff, nqueries, k, d_out_ids,
+            d_out_scores, bad_container, bad_query))
+        return ANSX_ERR_ARG;
+    if (scorer_args(scorer, d_pays)) return ANSX_ERR_ARG;
+    if (facets) {
+        if (!facets->d_values || !facets->d_counts || ((uintptr_t)facets->d_values & 3u) || ((uintptr_t)facets->d_counts & 3u)) return ANSX_ERR_ARG;
+        if (facets->ndocs == 0 || (u64)facets->ndocs > ((u64)1 << 32)) return ANSX_ERR_ARG;
+        if (facets->nvalues == 0 || facets->nvalues > ANSX_FACET_MAX_VALUES) return ANSX_ERR_ARG;
     }
     if (nqueries == 0) return ANSX_OK;
     return run_call(c, stream, [&](hipStream_t s) {
         return topk_scored_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, (const u64*)qoff, msm, xterms,
-            (const u64*)xqoff, scorer, nqueries, k, d_out_ids, d_out_scores, out_counts, bad_container, bad_query, s);
+            (const u64*)xqoff, scorer, facets, nqueries, k, d_out_ids, d_out_scores, out_counts, out_totals, bad_container, bad_query, s);
     });
 }
 

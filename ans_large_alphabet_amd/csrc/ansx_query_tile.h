@@ -3,7 +3,8 @@
 // Two parts.  The arithmetic is ANSX_PLAN_FN, as in ansx_plan_types.h: the kernels inline it and the host compiler
 // alone builds it, so tests/tools/query_tile_check.cpp runs, under the sanitizers, the code the kernels run.  The
 // device pieces (ANSX_D) add the thread that does it and the barrier, and are there for the kernels only.
-// On it today: k_isectb_gather, k_isectb_match, k_union_heads, k_topk_hist, k_topk_gather (and k_topkb_check's limit).
+// On it today: k_isectb_gather, k_isectb_match, k_union_heads, k_topk_hist, k_topk_gather, k_facet_count (and
+// k_topkb_check's limit).
 // The other kernels of the same shape still write their frame out, and every kernel its ballot (isect_ballot): DESIGN.md
 // section 3o-2 says which pieces changed their code generation and are therefore not here.
 //
@@ -89,6 +90,20 @@ template <class K> ANSX_PLAN_FN void qt_tile_queries_by(K key, u32 Q, u64 i0, u3
     qb[0] = qt_last_le(key, 0, Q - 1, i0);
     qb[1] = qt_last_le(key, qb[0], Q - 1, qt_tile_last(i0, n));
 }
+
+// ---- the facet step (ansx_facet.h, k_facet_count) ----------------------------------------
+// The tiles of `tot` elements, and the chunk of them that workgroup wg of `grid` walks in the persistent form: tiles
+// [t[0], t[1]), contiguous, the chunks of wg = 0 .. grid - 1 back to back from 0 to ntiles, their lengths at most one
+// apart; grid > ntiles leaves some of them empty.  (ntiles * grid stays far below 2^64: ntiles <= 2^22, grid a u32.)
+ANSX_PLAN_FN u64 facet_tiles(u64 tot) { return (tot + ANSX_ISECT_TILE - 1u) / ANSX_ISECT_TILE; }
+ANSX_PLAN_FN void facet_chunk(u64 ntiles, u32 grid, u32 wg, u64* t)
+{
+    t[0] = ntiles * wg / grid, t[1] = ntiles * ((u64)wg + 1u) / grid;
+}
+// Is this id looked up (in 64 bits: ndocs == 2^32 admits 0xFFFFFFFF); is this value counted; query j's row of counts
+ANSX_PLAN_FN bool facet_lookup(u32 id, u64 ndocs) { return (u64)id < ndocs; }
+ANSX_PLAN_FN bool facet_counted(u32 v, u32 nvalues) { return v < nvalues; }
+ANSX_PLAN_FN u64 facet_row(u32 j, u32 nvalues) { return (u64)j * nvalues; }
 
 // ---- the device pieces -------------------------------------------------------------------------------------------
 #ifdef ANSX_D

@@ -949,6 +949,48 @@ int ansx_topk_scored_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint
     const ansx_scorer* scorer, size_t nqueries, uint32_t k, uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts,
     size_t* bad_container, size_t* bad_query, void* stream);
 
+/* ansx_topk_facets_batch_dev: ansx_topk_scored_batch_dev that also says how many documents matched and how they fall
+ * over one category column -- the rest of a results page -- in one call (csrc/ansx_facet.h).
+ * facets stands behind scorer and out_totals behind out_counts; every other argument is ansx_topk_scored_batch_dev's, in
+ * its order.  The result set R(q), the scores, the order, the output image and out_counts are that call's, word for
+ * word, with and without a scorer.  facets == NULL && out_totals == NULL is that call: the same bytes come out and the
+ * same kernels are launched.
+ * out_totals (optional, HOST, nqueries entries): out_totals[q] = |R(q)|, not cut to k.  It comes from the bounds the
+ * group's last wait already brings home: no launch, no copy and no wait is added.  A group that ends early -- every list
+ * or every driver empty, or a round that leaves nothing -- writes zeros.
+ * facets (optional): d_values is a DEVICE column, the value of document id d < ndocs (4-byte aligned), and d_counts
+ * DEVICE room for nqueries * nvalues counts (4-byte aligned), row q at q * nvalues:
+ *   d_counts[q * nvalues + v] = the number of ids d of R(q) with d_values[d] == v, for v < nvalues.
+ * A value of nvalues or more is "no value" and is counted nowhere (a caller marks documents without the field so,
+ * 0xFFFFFFFF for instance); hence the sum of row q is at most out_totals[q].  An id counts once, however many postings
+ * it has, and the counts run over all of R(q), not only over the k results.  The call zeroes all nqueries * nvalues
+ * counts itself, on `stream`, before the first group.  After any error d_counts is unspecified.
+ * A bad id: an id of ndocs or more that is an id of R(q) is ANSX_ERR_DOMAIN with *bad_query = the first such query of its
+ * group; nothing is read at that id.  The comparison is made in 64 bits: ndocs == 2^32 admits the id 0xFFFFFFFF.  An id
+ * that misses a required list, fails the threshold or is excluded is never looked up, whatever its value -- the rule of
+ * an overflowing score.  Where a group has both a score overflow and a bad id, the overflow is reported.
+ * Errors, in this order: before the context is touched, every ANSX_ERR_ARG of ansx_topk_scored_batch_dev, the scorer's
+ * included, with the same *bad_query / *bad_container; then, with neither touched, ANSX_ERR_ARG for a null or misaligned
+ * d_values or d_counts; ndocs == 0 or ndocs > 2^32; nvalues == 0 or nvalues > ANSX_FACET_MAX_VALUES.  nqueries == 0:
+ * ANSX_OK, nothing is launched and nothing is zeroed.  Then the parent's errors and the bad id above.
+ * Per group that reaches its ranked tail ONE launch is added (k_facet_count, between the last step that filters and the
+ * select), no host wait and no upload of its own; the bad-id word rides home with the overflow word.  No trace is left in
+ * the context, which stays usable after any error.
+ * Out of scope: multi-valued fields, numeric ranges / buckets, the top values of a facet, several facet columns in one
+ * call, columns narrower than 32 bits, facets for the unranked calls, a call without a ranking (k == 0). */
+#define ANSX_FACET_MAX_VALUES (1u << 24)
+typedef struct ansx_facets {
+    const uint32_t* d_values; /* DEVICE, ndocs uint32_t, 4-byte aligned: the facet value of document id d */
+    size_t ndocs;             /* 1 .. 2^32 */
+    uint32_t nvalues;         /* 1 .. ANSX_FACET_MAX_VALUES: values 0 .. nvalues - 1 are counted */
+    uint32_t* d_counts;       /* DEVICE, nqueries * nvalues uint32_t, 4-byte aligned, row q at q * nvalues */
+} ansx_facets;
+int ansx_topk_facets_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
+    const ansx_scorer* scorer, const ansx_facets* facets, size_t nqueries, uint32_t k, uint32_t* d_out_ids,
+    uint32_t* d_out_scores, uint32_t* out_counts, uint32_t* out_totals, size_t* bad_container, size_t* bad_query, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
