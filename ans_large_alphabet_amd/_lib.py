@@ -15,6 +15,8 @@ FLAG_COMPACT_ALPHABET = 1
 OK, ERR_ARG, ERR_CAPACITY, ERR_FORMAT, ERR_HIP, ERR_NO_DEVICE, ERR_DOMAIN, ERR_MODEL = range(8)
 BOOL_ALL, BOOL_ANY = 0, 1  # the op of ansx_bool_batch_dev
 OCCUR_SHOULD, OCCUR_MUST = 0, 1  # the occur values of ansx_topk_query_batch_dev
+FILTER_NOT = 1  # the flag of an ansx_filter_clause (ansx_topk_filter_batch_dev)
+FILTER_MAX_COLUMNS, FILTER_MAX_CLAUSES = 64, 16
 SINGLE_STREAM = 0xFFFFFFFF
 NO_CHECKPOINTS = 0xFFFFFFFF
 DEFAULT_BLOCK_INTS = 16384
@@ -37,7 +39,7 @@ EXPORTS = [
     "ansx_decode_batch_ranges_sums_dev", "ansx_next_geq_batch_dev", "ansx_last_decode_stats",
     "ansx_intersect_ids_dev", "ansx_intersect_dev", "ansx_intersect_batch_dev", "ansx_union_batch_dev", "ansx_union_dev",
     "ansx_bool_batch_dev", "ansx_last_encode_form", "ansx_topk_batch_dev", "ansx_topk_bool_batch_dev",
-    "ansx_topk_query_batch_dev", "ansx_topk_scored_batch_dev", "ansx_topk_facets_batch_dev",
+    "ansx_topk_query_batch_dev", "ansx_topk_scored_batch_dev", "ansx_topk_facets_batch_dev", "ansx_topk_filter_batch_dev",
     "ansx_decode_batch_device_ranges_dev", "ansx_decode_batch_device_ranges_sums_dev",
 ]
 
@@ -57,6 +59,18 @@ class Facets(C.Structure):
     """ansx_facets: the column (a uint32 per document id) and the room for nqueries * nvalues counts of
     ansx_topk_facets_batch_dev, both on the device"""
     _fields_ = [("d_values", C.c_void_p), ("ndocs", C.c_size_t), ("nvalues", C.c_uint32), ("d_counts", C.c_void_p)]
+
+
+class FilterClause(C.Structure):
+    """ansx_filter_clause: lo <= column[d] <= hi, or with FILTER_NOT in flags its negation"""
+    _fields_ = [("column", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class Filters(C.Structure):
+    """ansx_filters: the columns (a host array of device addresses, each ndocs uint32) and every query's clauses (host) of
+    ansx_topk_filter_batch_dev"""
+    _fields_ = [("d_columns", C.c_void_p), ("ncolumns", C.c_uint32), ("ndocs", C.c_size_t), ("clauses", C.c_void_p),
+                ("fqoff", C.c_void_p)]
 
 
 class ContainerHeader(C.Structure):
@@ -244,6 +258,10 @@ def lib():
     L.ansx_topk_facets_batch_dev.restype = C.c_int
     L.ansx_topk_facets_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Scorer),
                                              C.POINTER(Facets), sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]
+    L.ansx_topk_filter_batch_dev.restype = C.c_int
+    L.ansx_topk_filter_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Scorer),
+                                             C.POINTER(Facets), C.POINTER(Filters), sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(sz),
+                                             C.POINTER(sz), vp]
     L.ansx_union_dev.restype = C.c_int
     L.ansx_union_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(sz), vp]
     L.ansx_container_info.restype = C.c_int

@@ -873,12 +873,64 @@ class _Codec:
                                out_scores_ptr, pay_ptrs, pay_sizes, stream, query=(occurs, min_should), scorer=scorer, scored=True,
                                facets=(facets, bool(totals)))
 
+    # ---- ranked queries with range filters over document columns (include/ansx.h)
+    def topk_filter_batch_dev(self, in_ptrs, in_bytes, queries, weights, occurs, min_should, excludes, k, out_ids_ptr,
+                              out_scores_ptr=None, pay_ptrs=None, pay_sizes=None, stream=None, scorer=None, facets=None, totals=True,
+                              filters=None):
+        """topk_facets_batch_dev over the ids of every query's result that pass the query's clauses, applied before the
+        ranking, the totals and the facet counts.  filters: None (that call itself, the same bytes and launches), or
+        (column_ptrs, ndocs, clauses_per_query): the device addresses of the columns, each ndocs uint32 values, one per
+        document id (None / 0 for a column no clause names), and a sequence as long as queries of (possibly empty) sequences
+        of clauses (column, lo, hi) or (column, lo, hi, negate): the clause passes for document d iff
+        (lo <= column[d] <= hi) != negate; lo > hi is the empty range.  A query's clauses are conjunctive; a query without
+        clauses is not filtered.  sortable_u32 maps int32 and float32 columns and bounds to uint32, order-preserving.
+        Returns what topk_facets_batch_dev returns, over the filtered results.  An id of ndocs or more in the result of a
+        query with a clause raises AnsxError(ERR_DOMAIN) with .bad_query."""
+        return self._topk_call("topk_filter_batch_dev", in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, None,
+                               out_scores_ptr, pay_ptrs, pay_sizes, stream, query=(occurs, min_should), scorer=scorer, scored=True,
+                               facets=(facets, bool(totals)), filters=(filters,))
+
+    @staticmethod
+    def _filters_struct(fl, nq):
+        """filters = (column_ptrs, ndocs, clauses_per_query) -> (L.Filters, the arrays it points into); what can be
+        checked before the library is checked here"""
+        if isinstance(fl, (str, bytes)) or not hasattr(fl, "__len__") or len(fl) != 3:
+            raise ValueError("filters must be (column_ptrs, ndocs, clauses_per_query)")
+        cols, ndocs, per = fl
+        if isinstance(cols, (str, bytes)) or not hasattr(cols, "__len__"):
+            raise ValueError("filters: column_ptrs must be a sequence of device addresses")
+        for v in cols:
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 1 << 64):
+                raise ValueError("filters: a column pointer must be a non-negative integer or None, got %r" % (v,))
+        if isinstance(ndocs, bool) or not isinstance(ndocs, (int, np.integer)) or not 0 <= ndocs < 1 << 64:
+            raise ValueError("filters: ndocs must be a non-negative integer, got %r" % (ndocs,))
+        if isinstance(per, (str, bytes)) or not hasattr(per, "__len__") or len(per) != nq:
+            raise ValueError("filters: clauses_per_query must be a sequence as long as queries")
+        colarr = np.array([int(v or 0) for v in cols] + [0], dtype=np.uint64)  # (never empty)
+        fqoff = np.zeros(nq + 1, dtype=np.uint64)
+        rows = []
+        for q, cl in enumerate(per):
+            if isinstance(cl, (str, bytes)) or not hasattr(cl, "__len__"):
+                raise ValueError("filters: the clauses of query %d are not a sequence" % q)
+            for c in cl:
+                if isinstance(c, (str, bytes)) or not hasattr(c, "__len__") or len(c) not in (3, 4):
+                    raise ValueError("filters: a clause of query %d is not (column, lo, hi[, negate])" % q)
+                for v in c[:3]:
+                    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 0xFFFFFFFF:
+                        raise ValueError("filters: a clause of query %d holds %r, not an integer in [0, 2^32)" % (q, v))
+                rows.append((int(c[0]), int(c[1]), int(c[2]), L.FILTER_NOT if len(c) == 4 and c[3] else 0))
+            fqoff[q + 1] = len(rows)
+        clauses = np.array(rows + [(0, 0, 0, 0)], dtype=np.uint32).reshape(-1, 4)  # (never empty)
+        st = L.Filters(colarr.ctypes.data, len(cols), int(ndocs), clauses.ctypes.data, fqoff.ctypes.data)
+        return st, (colarr, fqoff, clauses)
+
     def _topk_call(self, what, in_ptrs, in_bytes, queries, weights, excludes, k, out_ids_ptr, op, out_scores_ptr, pay_ptrs,
-                   pay_sizes, stream, query=None, scorer=None, scored=False, facets=None):
+                   pay_sizes, stream, query=None, scorer=None, scored=False, facets=None, filters=None):
         """What the ranked calls share: the checks of their arguments and the call; op None: ansx_topk_batch_dev or, with
         query = (occurs, min_should), ansx_topk_query_batch_dev -- with scored, ansx_topk_scored_batch_dev, scorer its
         (norms_ptr, ndocs, table_ptr, tf_rows) or None -- with facets = ((values_ptr, ndocs, nvalues, counts_ptr) or None,
-        whether the totals are wanted), ansx_topk_facets_batch_dev, which returns (counts, totals or None)"""
+        whether the totals are wanted), ansx_topk_facets_batch_dev, which returns (counts, totals or None) -- with filters =
+        ((column_ptrs, ndocs, clauses_per_query) or None,) as well, ansx_topk_filter_batch_dev"""
         fc = None
         if facets is not None and facets[0] is not None:
             fa = facets[0]
@@ -962,7 +1014,15 @@ class _Codec:
                 None if pays is None else pays.ctypes.data, None if psizes is None else psizes.ctypes.data, nc)
         tail = (nq, int(k), out_ids_ptr, out_scores_ptr, counts.ctypes.data if nq else None, C.byref(bad_c), C.byref(bad_q), stream)
         totals = np.zeros(nq, dtype=np.uint32) if facets is not None and facets[1] else None
-        if facets is not None:
+        if filters is not None:
+            fl, keep = (None, None) if filters[0] is None else self._filters_struct(filters[0], nq)
+            st = L.lib().ansx_topk_filter_batch_dev(
+                *head, terms.ctypes.data, wts.ctypes.data, None if occ is None else occ.ctypes.data, qoff.ctypes.data,
+                None if msm is None else msm.ctypes.data, None if xterms is None else xterms.ctypes.data,
+                None if xqoff is None else xqoff.ctypes.data, None if sc is None else C.byref(sc), None if fc is None else C.byref(fc),
+                None if fl is None else C.byref(fl), *tail[:5], totals.ctypes.data if totals is not None and nq else None, *tail[5:])
+            del keep
+        elif facets is not None:
             st = L.lib().ansx_topk_facets_batch_dev(
                 *head, terms.ctypes.data, wts.ctypes.data, None if occ is None else occ.ctypes.data, qoff.ctypes.data,
                 None if msm is None else msm.ctypes.data, None if xterms is None else xterms.ctypes.data,
@@ -1091,6 +1151,22 @@ def bm25_norms(doc_lens):
         raise ValueError("doc_lens must not be negative")
     edges = np.array(BM25_LENGTH_EDGES, dtype=np.uint64)
     return (np.searchsorted(edges, lens.astype(np.uint64), side="right") - 1).astype(np.uint8)
+
+
+def sortable_u32(array):
+    """An int32 or float32 array -> np.uint32 of the same shape whose unsigned order is the order of the values, so that
+    the one uint32 comparison of topk_filter_batch_dev serves dates, prices and floats; bounds go through the same map.
+    int32: the sign bit flipped.  float32: a set sign bit flips every bit, a clear one only the sign bit -- so
+    -inf < ... < -0.0 < +0.0 < ... < +inf -- and every NaN, whatever its sign and payload, goes to 0xFFFFFFFF, above
+    +inf (where np.sort puts it)."""
+    a = np.asarray(array)
+    if a.dtype == np.int32:
+        return a.view(np.uint32) ^ np.uint32(0x80000000)
+    if a.dtype == np.float32:
+        b = np.ascontiguousarray(a).view(np.uint32)
+        out = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+        return np.where(np.isnan(a), np.uint32(0xFFFFFFFF), out).astype(np.uint32)
+    raise ValueError("sortable_u32 takes an int32 or float32 array, got %s" % (a.dtype,))
 
 
 def bm25_table(avgdl, k1=1.2, b=0.75, tf_rows=64, bits=16):

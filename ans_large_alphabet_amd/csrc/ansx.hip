@@ -43,6 +43,7 @@
 #include "ansx_topk_query.h"
 #include "ansx_topk_scored.h"
 #include "ansx_facet.h"
+#include "ansx_filter.h"
 #include "ansx_batchrangesums.h"
 #include "ansx_batchnextgeq.h"
 #include "ansx_batchdevranges.h"
@@ -220,6 +221,7 @@ struct ansx_ctx {
         u32 topk_impact_grid = 0;     // ANSX_TOPK_IMPACT_GRID: the most workgroups of its staged form (0 = what the chip holds; tests force a few, so that one walks several tiles)
         int facet_form = 0;           // ANSX_FACET_FORM: 0 the default of k_facet_count (lds where nvalues allows), 1 "atomic", 2 "lds" (ANSX_FACET_FORM_*; tests and the bench tool force one)
         u32 facet_grid = 0;           // ANSX_FACET_GRID: the most workgroups of its lds form (0 = what the chip holds; tests force a few, so that one walks several tiles)
+        int filter_form = 0;          // ANSX_FILTER_FORM: 0 the default of the filter step (fused where the group excludes something), 1 "own", 2 "fused" (ANSX_FILTER_FORM_*; tests and the bench tool force one)
         bool facet_no_combine = false;  // ANSX_FACET_NO_COMBINE: its lds form without the wave's combined add (the bench tool measures both)
         u64 isect_batch_ints = 0;     // ANSX_ISECT_BATCH_INTS: the ints a group of ansx_intersect_batch_dev or ansx_union_batch_dev may take (0 = ANSX_ISECT_BATCH_INTS_DEFAULT; tests force small groups)
         u32 range_sums_wg_max = 0;    // ANSX_RANGE_SUMS_WG_MAX: the largest block the one-kernel scan of the range sums takes (0 = ANSX_RS_WG_MAX; the bench tool measures both sides of the switch)
@@ -3383,11 +3385,19 @@ int compact_step(ansx_ctx* c, const IsectWork& W, u32 n, const Moved& a, const M
 // (d_total: null, or where the device holds how many of them there are), query j's in [seg[j], seg[j + 1]), that are in
 // none of their query's lists xt[xo[j] .. xo[j + 1]) -> cand.to, their bounds -> nseg, their count -> W.total.  gf / df:
 // k_isect_compact's two flag words.
+// (its launch alone: the fused form of the filter step, DESIGN.md section 3s, marks between it and the compact step)
+int bool_exclude_launch(ansx_ctx* c, const IsectWork& W, const u32* ids, const u32* cand, u32 n, const u64* d_total, const u32* seg,
+    size_t Q, const u32* xo, const ansx_isb_list* xt, const u32* sflag, hipStream_t s)
+{
+    LAUNCH(c, "k_bool_exclude", k_bool_exclude, W.ntiles, ANSX_ISECT_NT, 0, s, ids, cand, n, d_total, seg, (u32)Q, xo, xt,
+        (u32)c->dbg.bool_form, W.ballots, W.counts, sflag);
+    return ANSX_OK;
+}
 int bool_exclude_step(ansx_ctx* c, const IsectWork& W, const u32* ids, const Moved& cand, u32 n, const u64* d_total, const u32* seg,
     size_t Q, const u32* xo, const ansx_isb_list* xt, const u32* sflag, u32* nseg, const u32* gf, const u32* df, hipStream_t s)
 {
-    LAUNCH(c, "k_bool_exclude", k_bool_exclude, W.ntiles, ANSX_ISECT_NT, 0, s, ids, cand.from, n, d_total, seg, (u32)Q, xo, xt,
-        (u32)c->dbg.bool_form, W.ballots, W.counts, sflag);
+    int rc;
+    if ((rc = bool_exclude_launch(c, W, ids, cand.from, n, d_total, seg, Q, xo, xt, sflag, s))) return rc;
     return compact_step(c, W, n, cand, nullptr, seg, Q, nseg, gf, df, s);
 }
 
@@ -3851,6 +3861,8 @@ struct TopkOut {
     // every query's |R(q)| goes (host)
     const ansx_facets* facets = nullptr;
     u32* totals = nullptr;
+    // ansx_topk_filter_batch_dev: null, or the columns and the clauses that cut R(q) down to R'(q)
+    const ansx_filters* filters = nullptr;
 };
 
 // ... the impact step of ansx_topk_scored_batch_dev (ansx_topk_scored.h) behind the scan: the payload of every posting of
@@ -4014,28 +4026,78 @@ int facet_step(ansx_ctx* c, const Ranked& R, size_t Q, size_t q0, const TopkOut&
                                    : facet_launch_lds<true>(c, R, Q, f, rows, d_bad, sflag, s);
 }
 
+// ... the filter step of ansx_topk_filter_batch_dev (ansx_filter.h) behind every other step that filters and in front of
+// facet_step: the ids of R that pass their query's clauses.  A group's clause table (filter_tables): Q + 1 offsets and its
+// queries' clauses with the column's address in them; both ride in the group's one upload.  Empty where no query of the
+// group has a clause: such a group launches and uploads nothing more.  An id the columns have no entry for lowers the
+// bad-id word, the fourth of s_of, which filter_word raises (in the page: a group without clauses never copies it back).
+struct FilterTables {
+    std::vector<u32> off;
+    std::vector<ansx_filter_dev> cl;
+    bool active() const { return !cl.empty(); }
+};
+void filter_tables(const TopkOut& o, size_t q0, size_t Q, FilterTables* T)
+{
+    if (!o.filters) return;
+    const ansx_filters& f = *o.filters;
+    const u64 a = f.fqoff[q0], b = f.fqoff[q0 + Q];
+    if (a == b) return;
+    T->off.resize(Q + 1);
+    for (size_t j = 0; j <= Q; j++) T->off[j] = (u32)(f.fqoff[q0 + j] - a);  // (at most ANSX_FILTER_MAX_CLAUSES per query)
+    T->cl.resize((size_t)(b - a));
+    for (u64 e = a; e < b; e++) {
+        const ansx_filter_clause& k = f.clauses[e];
+        T->cl[(size_t)(e - a)] = { f.d_columns[k.column], k.lo, k.hi, k.flags, 0u };
+    }
+}
+void filter_word(const TopkOut& o, const Upload& U, Upload::Sec<u32> s_of)
+{
+    if (o.filters) U.pin(s_of)[3] = ANSX_TOPK_NONE;
+}
+// does the step ride on the exclusion step of a group that has one (the fused form), or run on its own
+bool filter_fused(const ansx_ctx* c, bool excl) { return excl && c->dbg.filter_form != (int)ANSX_FILTER_FORM_OWN; }
+template <bool PRIOR> int filter_mark(ansx_ctx* c, const IsectWork& W, const u32* cand, u32 n, const u64* d_total, const u32* seg, size_t Q,
+    const u32* foff, const ansx_filter_dev* fc, const TopkOut& o, u32* d_bad, const u32* sflag, hipStream_t s)
+{
+    LAUNCH(c, "k_filter_mark", k_filter_mark<PRIOR>, W.ntiles, ANSX_ISECT_NT, 0, s, cand, seg, (u32)Q, d_total, n, foff, fc,
+        (u64)o.filters->ndocs, W.ballots, W.counts, d_bad, sflag);
+    return ANSX_OK;
+}
+// the own form, atleast_step's shape: the mark, then ids and scores moved by its ballots, the new bounds -> nseg, the
+// count -> W.total
+int filter_step(ansx_ctx* c, const IsectWork& W, const Moved& cand, const Moved& score, u32 n, const u64* d_total, const u32* seg, size_t Q,
+    const u32* foff, const ansx_filter_dev* fc, const TopkOut& o, u32* d_bad, const u32* sflag, u32* nseg, const u32* gf, const u32* df,
+    hipStream_t s)
+{
+    int rc;
+    if ((rc = filter_mark<false>(c, W, cand.from, n, d_total, seg, Q, foff, fc, o, d_bad, sflag, s))) return rc;
+    return compact_step(c, W, n, cand, &score, seg, Q, nseg, gf, df, s);
+}
+
 // ... the ranked tail over the candidates R of queries q0 .. q0 + Q: k_topkb_check when the call asks for it (it lowers
 // the overflow word s_of over the scores that are left), the select, and the overflow word and the bounds on their way
 // home to the upload page (the bounds to s_back) -- in front of them the scan's flag word, to h_sflag, where the host
-// has not seen it yet (null: it has); with facets the bad-id word rides in the overflow word's copy.  The caller waits;
-// ranked_counts reads what came.
+// has not seen it yet (null: it has); with facets the bad-id word rides in the overflow word's copy, and so does the
+// filter's where the group has a clause (`filtered`).  The caller waits; ranked_counts reads what came.
 int ranked_tail(ansx_ctx* c, const Ranked& R, size_t Q, size_t q0, const TopkOut& o, const Upload& U, const SelectSecs& T, u64* slots,
-    Upload::Sec<u32> s_of, Upload::Sec<u32> s_back, const u32* sflag, u32* h_sflag, hipStream_t s)
+    Upload::Sec<u32> s_of, Upload::Sec<u32> s_back, const u32* sflag, u32* h_sflag, hipStream_t s, bool filtered = false)
 {
     int rc;
     if (o.check)
         LAUNCH(c, "k_topkb_check", k_topkb_check, R.ntiles, ANSX_ISECT_NT, 0, s, R.score, R.hseg, (u32)Q, R.total, R.n, U.dev(s_of), sflag);
     if ((rc = topk_select(c, R, Q, U, T, slots, q0, o, sflag, s))) return rc;
     if (h_sflag) HIPCHK(c, hipMemcpyAsync(h_sflag, sflag, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(U.pin(s_of), U.dev(s_of), o.facets ? 12 : 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(U.pin(s_of), U.dev(s_of), filtered ? 16 : o.facets ? 12 : 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(U.pin(s_back), R.hseg, 4 * (Q + 1), hipMemcpyDeviceToHost, s));
     return ANSX_OK;
 }
-// the first query of the group with a score of 2^32 - 1 or more among its results -> ANSX_ERR_DOMAIN; then, with facets,
-// the first with an id the column has no entry for -> ANSX_ERR_DOMAIN; else the counts and the totals, from the same bounds
+// the first query of the group with a score of 2^32 - 1 or more among its results -> ANSX_ERR_DOMAIN; then, with filters,
+// the first with an id the columns have no entry for; then, with facets, the first with an id the column has no entry
+// for -> ANSX_ERR_DOMAIN; else the counts and the totals, from the same bounds
 int ranked_counts(const u32* h_of, const u32* h_seg, size_t Q, size_t q0, const TopkOut& o, size_t* bad_query)
 {
-    const u32 bad = h_of[0] != ANSX_TOPK_NONE ? h_of[0] : o.facets ? h_of[2] : ANSX_TOPK_NONE;
+    const u32 fbad = o.filters ? h_of[3] : ANSX_TOPK_NONE;  // (a group without clauses: filter_word's, never copied over)
+    const u32 bad = h_of[0] != ANSX_TOPK_NONE ? h_of[0] : fbad != ANSX_TOPK_NONE ? fbad : o.facets ? h_of[2] : ANSX_TOPK_NONE;
     if (bad != ANSX_TOPK_NONE) {
         if (bad_query) *bad_query = q0 + bad;
         return ANSX_ERR_DOMAIN;
@@ -4094,14 +4156,22 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
     const bool least = o.msm && std::any_of(o.msm + g.q0, o.msm + g.q1, [](u32 m) { return m >= 2; });
     const auto s_m = U.add<u32>(least ? Q : 0);
     const auto s_ip = U.add<ansx_impact_list>(IT.P.size());
+    // (ansx_topk_filter_batch_dev only: some query of the group has a clause -- the clause table goes up too)
+    FilterTables FT;
+    filter_tables(o, g.q0, Q, &FT);
+    const bool filt = FT.active(), fused = filt && filter_fused(c, excl);
+    const auto s_fo = U.add<u32>(FT.off.size());
+    const auto s_fc = U.add<ansx_filter_dev>(FT.cl.size());
     const size_t up = U.end;
     const auto s_hs = U.add<u32>(q1);  // (the host's copy: read back)
     const auto s_xs = U.add<u32>(excl ? q1 : 0);
     const auto s_as = U.add<u32>(least ? q1 : 0);
+    const auto s_fs = U.add<u32>(filt && !fused ? q1 : 0);
     const SelectSecs s_sel = select_sections(U, Q);
     GroupWs ws;
     if ((rc = group_room(c, U, s_hs.off + s_hs.bytes, M, s_fl, &s_of, &ws))) return rc;
-    facet_word(o, U, s_of);
+    facet_word(o, U, s_of), filter_word(o, U, s_of);
+    if (filt) U.put(s_fo, FT.off.data()), U.put(s_fc, FT.cl.data());
     U.put(s_seg, g.seg.data()), U.put(s_p, g.pairs.data());
     if (excl) U.put(s_xo, g.xt_off.data()), U.put(s_xt, g.xt.data());
     if (least) U.put(s_m, o.msm + g.q0);
@@ -4143,16 +4213,30 @@ int topk_group(ansx_ctx* c, QueryFront& F, const UnbGroup& g, const TopkOut& o, 
         hb.flip(), vs.flip();
         R.ids = hb.from(), R.score = vs.from(), R.hseg = U.dev(s_as);
     }
-    if (excl) {  // ONE exclusion step over the heads, as in unb_group, and the scores moved by the same ballots: no wait
+    if (fused) {  // ansx_topk_filter_batch_dev: the exclusion's launch, the filter's mark over its ballots, ONE compact step
+        if ((rc = bool_exclude_launch(c, W, ids, hb.from(), (u32)M, W.total, R.hseg, Q, U.dev(s_xo), U.dev(s_xt), S.flag, s))) return rc;
+        if ((rc = filter_mark<true>(c, W, hb.from(), (u32)M, W.total, R.hseg, Q, U.dev(s_fo), U.dev(s_fc), o, U.dev(s_of) + 3, S.flag, s)))
+            return rc;
+        if ((rc = compact_step(c, W, (u32)M, { hb.from(), hb.to(), nullptr }, nullptr, R.hseg, Q, U.dev(s_xs), zero, uflag, s))) return rc;
+    } else if (excl) {  // ONE exclusion step over the heads, as in unb_group, and the scores moved by the same ballots: no wait
         if ((rc = bool_exclude_step(c, W, ids, { hb.from(), hb.to(), nullptr }, (u32)M, W.total, R.hseg, Q, U.dev(s_xo), U.dev(s_xt), S.flag,
                  U.dev(s_xs), zero, uflag, s)))
             return rc;
+    }
+    if (excl) {
         if ((rc = isect_move(c, W, vs.from(), (u32)M, { vs.to(), nullptr, nullptr, M }, zero, uflag, s))) return rc;
         hb.flip(), vs.flip();
         R.ids = hb.from(), R.score = vs.from(), R.hseg = U.dev(s_xs);
     }
+    if (filt && !fused) {  // ansx_topk_filter_batch_dev, the own form: the mark and a compact step of its own: no wait
+        if ((rc = filter_step(c, W, { hb.from(), hb.to(), nullptr }, { vs.from(), vs.to(), nullptr }, (u32)M, W.total, R.hseg, Q, U.dev(s_fo),
+                 U.dev(s_fc), o, U.dev(s_of) + 3, S.flag, U.dev(s_fs), zero, uflag, s)))
+            return rc;
+        hb.flip(), vs.flip();
+        R.ids = hb.from(), R.score = vs.from(), R.hseg = U.dev(s_fs);
+    }
     if (o.facets && (rc = facet_step(c, R, Q, g.q0, o, U.dev(s_of) + 2, S.flag, s))) return rc;
-    if ((rc = ranked_tail(c, R, Q, g.q0, o, U, s_sel, slots, s_of, s_hs, S.flag, ws.sflag, s))) return rc;
+    if ((rc = ranked_tail(c, R, Q, g.q0, o, U, s_sel, slots, s_of, s_hs, S.flag, ws.sflag, s, filt))) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
     if ((rc = scan_flag_status(ws, g.lists, *F.index, bad_container))) return rc;
     return ranked_counts(U.pin(s_of), U.pin(s_hs), Q, g.q0, o, bad_query);
@@ -4214,12 +4298,19 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
     const auto s_ow = U.add<u32>(should ? g.ot.size() : 0);
     const auto s_m = U.add<u32>(should ? Q : 0);
     const auto s_ip = U.add<ansx_impact_list>(IT.P.size());
+    // (ansx_topk_filter_batch_dev only: some query of the group has a clause -- the clause table goes up too)
+    FilterTables FT;
+    filter_tables(o, g.q0, Q, &FT);
+    const bool filt = FT.active(), fused = filt && filter_fused(c, excl);
+    const auto s_fo = U.add<u32>(FT.off.size());
+    const auto s_fc = U.add<ansx_filter_dev>(FT.cl.size());
     const size_t up = U.end;
     const auto s_seg = U.add<u32>(2 * q1);  // (the host's copy: the last step's, read back)
     const SelectSecs s_sel = select_sections(U, Q);
     GroupWs ws;
     if ((rc = group_room(c, U, s_seg.off + s_seg.bytes, nc0, s_fl, &s_of, &ws))) return rc;
-    facet_word(o, U, s_of);
+    facet_word(o, U, s_of), filter_word(o, U, s_of);
+    if (filt) U.put(s_fo, FT.off.data()), U.put(s_fc, FT.cl.data());
     U.put(s_g, g.G.data()), U.put(s_ro, g.rt_off.data());
     if (!g.rt.empty()) U.put(s_rt, g.rt.data());
     for (size_t j = 0; j < Q; j++) U.pin(s_wd)[j] = o.weights[g.dterm[j]];
@@ -4266,17 +4357,31 @@ int topkb_group(ansx_ctx* c, QueryFront& F, const IsbGroup& g, const TopkOut& o,
             return rc;
         buf.flip(), sb.flip(), seg.flip();
     }
-    if (excl) {  // ONE exclusion step over what the rounds left (behind an optional step, their count is the device's), the
-                 // scores moved by the same ballots: no wait
+    if (fused) {  // ansx_topk_filter_batch_dev: the exclusion's launch, the filter's mark over its ballots, ONE compact step
+        const u64* tot = should ? W.total : nullptr;
+        if ((rc = bool_exclude_launch(c, W, ids, buf.from(), nc, tot, seg.from(), Q, U.dev(s_xo), U.dev(s_xt), S.flag, s))) return rc;
+        if ((rc = filter_mark<true>(c, W, buf.from(), nc, tot, seg.from(), Q, U.dev(s_fo), U.dev(s_fc), o, U.dev(s_of) + 3, S.flag, s)))
+            return rc;
+        if ((rc = compact_step(c, W, nc, { buf.from(), buf.to(), nullptr }, nullptr, seg.from(), Q, seg.to(), zero, zero, s))) return rc;
+    } else if (excl) {  // ONE exclusion step over what the rounds left (behind an optional step, their count is the device's), the
+                        // scores moved by the same ballots: no wait
         if ((rc = bool_exclude_step(c, W, ids, { buf.from(), buf.to(), nullptr }, nc, should ? W.total : nullptr, seg.from(), Q, U.dev(s_xo), U.dev(s_xt),
                  S.flag, seg.to(), zero, zero, s)))
             return rc;
+    }
+    if (excl) {
         if ((rc = isect_move(c, W, sb.from(), nc, { sb.to(), nullptr, nullptr, nc }, zero, zero, s))) return rc;
+        buf.flip(), sb.flip(), seg.flip();
+    }
+    if (filt && !fused) {  // ansx_topk_filter_batch_dev, the own form: the mark and a compact step of its own: no wait
+        if ((rc = filter_step(c, W, { buf.from(), buf.to(), nullptr }, { sb.from(), sb.to(), nullptr }, nc, W.total, seg.from(), Q,
+                 U.dev(s_fo), U.dev(s_fc), o, U.dev(s_of) + 3, S.flag, seg.to(), zero, zero, s)))
+            return rc;
         buf.flip(), sb.flip(), seg.flip();
     }
     const Ranked R = { buf.from(), sb.from(), seg.from(), W.total, nc, W.ntiles };
     if (o.facets && (rc = facet_step(c, R, Q, g.q0, o, U.dev(s_of) + 2, S.flag, s))) return rc;
-    if ((rc = ranked_tail(c, R, Q, g.q0, o, U, s_sel, slots, s_of, s_seg, S.flag, nullptr, s))) return rc;
+    if ((rc = ranked_tail(c, R, Q, g.q0, o, U, s_sel, slots, s_of, s_seg, S.flag, nullptr, s, filt))) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
     return ranked_counts(U.pin(s_of), U.pin(s_seg), Q, g.q0, o, bad_query);
 }
@@ -4327,10 +4432,14 @@ int topk_bool_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const 
 // ansx_topk_facets_batch_dev (ansx_facet.h) is that call with facets and / or totals: the counts
 // zeroed once behind the plan, and in every group that reaches its ranked tail facet_step in front of it -- one launch, no
 // wait, no upload; the totals come from the bounds the tail's wait brings home.  Both null: the scored call, launch for launch.
+// ansx_topk_filter_batch_dev (ansx_filter.h) is that call with filters: in every group in which some
+// query has a clause the filter step in front of facet_step -- fused into the exclusion step (one launch) or on its own
+// (five), no wait, the clause table in the group's upload.  filters null: the facets call, launch for launch.
 int topk_scored_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, const size_t* in_bytes, const u8* const* d_pays,
     const size_t* pay_bytes, size_t count, const u32* terms, const u32* weights, const u8* occur, const u64* qoff, const u32* msm,
     const u32* xterms, const u64* xqoff, const ansx_scorer* scorer, const ansx_facets* facets, size_t nq, u32 k, u32* d_out_ids,
-    u32* d_out_scores, u32* out_counts, u32* out_totals, size_t* bad_container, size_t* bad_query, hipStream_t s)
+    u32* d_out_scores, u32* out_counts, u32* out_totals, size_t* bad_container, size_t* bad_query, hipStream_t s,
+    const ansx_filters* filters = nullptr)
 {
     int rc;
     QueryFront F;
@@ -4351,7 +4460,7 @@ int topk_scored_batch(ansx_ctx* c, int kind, int f, const u8* const* d_ins, cons
     TopkOut o = { weights, k, pow2, d_out_ids, d_out_scores, out_counts, d_pays != nullptr, true,
         c->dbg.topk_bool_form == 1 ? ANSX_TOPKB_FORM_SEARCH : ANSX_TOPKB_FORM_DEFAULT };
     o.msm = P.m.data(), o.oweights = ow.data(), o.qform = (u32)c->dbg.topk_query_form;
-    o.scorer = scorer, o.facets = facets, o.totals = out_totals;
+    o.scorer = scorer, o.facets = facets, o.totals = out_totals, o.filters = filters;
     if (facets) HIPCHK(c, hipMemsetAsync(facets->d_counts, 0, 4 * nq * (size_t)facets->nvalues, s));
     TopkOut oreq = o;  // (a group of kind R reads its drivers' and rounds' weights at the required terms' places)
     oreq.weights = rw.data();
@@ -4738,6 +4847,11 @@ int ansx_debug_set(ansx_ctx* c, const char* name, const char* value)
         const int w = debug_word(value, "atomic", "lds");
         if (w < 0) return ANSX_ERR_ARG;
         c->dbg.facet_form = w;
+    }
+    else if (!strcmp(name, "ANSX_FILTER_FORM")) {
+        const int w = debug_word(value, "own", "fused");
+        if (w < 0) return ANSX_ERR_ARG;
+        c->dbg.filter_form = w;
     }
     else if (!strcmp(name, "ANSX_FACET_GRID")) c->dbg.facet_grid = (value && value[0]) ? (u32)strtoul(value, nullptr, 10) : 0u;
     else if (!strcmp(name, "ANSX_FACET_NO_COMBINE")) c->dbg.facet_no_combine = on;
@@ -5167,6 +5281,16 @@ static int scorer_args(const ansx_scorer* scorer, const uint8_t* const* d_pays)
     return ANSX_OK;
 }
 
+// ... what facets add, behind them
+static int facets_args(const ansx_facets* facets)
+{
+    if (!facets) return ANSX_OK;
+    if (!facets->d_values || !facets->d_counts || ((uintptr_t)facets->d_values & 3u) || ((uintptr_t)facets->d_counts & 3u)) return ANSX_ERR_ARG;
+    if (facets->ndocs == 0 || (u64)facets->ndocs > ((u64)1 << 32)) return ANSX_ERR_ARG;
+    if (facets->nvalues == 0 || facets->nvalues > ANSX_FACET_MAX_VALUES) return ANSX_ERR_ARG;
+    return ANSX_OK;
+}
+
 int ansx_topk_scored_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
     const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
     const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
@@ -5196,15 +5320,62 @@ int ansx_topk_facets_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* cons
             d_out_scores, bad_container, bad_query))
         return ANSX_ERR_ARG;
     if (scorer_args(scorer, d_pays)) return ANSX_ERR_ARG;
-    if (facets) {
-        if (!facets->d_values || !facets->d_counts || ((uintptr_t)facets->d_values & 3u) || ((uintptr_t)facets->d_counts & 3u)) return ANSX_ERR_ARG;
-        if (facets->ndocs == 0 || (u64)facets->ndocs > ((u64)1 << 32)) return ANSX_ERR_ARG;
-        if (facets->nvalues == 0 || facets->nvalues > ANSX_FACET_MAX_VALUES) return ANSX_ERR_ARG;
-    }
+    if (facets_args(facets)) return ANSX_ERR_ARG;
     if (nqueries == 0) return ANSX_OK;
     return run_call(c, stream, [&](hipStream_t s) {
         return topk_scored_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, (const u64*)qoff, msm, xterms,
             (const u64*)xqoff, scorer, facets, nqueries, k, d_out_ids, d_out_scores, out_counts, out_totals, bad_container, bad_query, s);
+    });
+}
+
+// ... what filters add, behind them: the pointers, the columns' number, the columns the clauses name, ndocs, the offsets,
+// then per query -- *bad_query the first that offends -- the number of its clauses, their columns and flags
+static int filters_args(const ansx_filters* fl, size_t nqueries, size_t* bad_query)
+{
+    if (!fl) return ANSX_OK;
+    if (!fl->d_columns || !fl->fqoff) return ANSX_ERR_ARG;
+    const u64 ncl = fl->fqoff[nqueries];
+    if (!fl->clauses && ncl > 0) return ANSX_ERR_ARG;
+    if (fl->ncolumns == 0 || fl->ncolumns > ANSX_FILTER_MAX_COLUMNS) return ANSX_ERR_ARG;
+    for (u64 e = 0; e < ncl; e++) {
+        const u32 col = fl->clauses[e].column;
+        if (col < fl->ncolumns && (!fl->d_columns[col] || ((uintptr_t)fl->d_columns[col] & 3u))) return ANSX_ERR_ARG;
+    }
+    if (fl->ndocs == 0 || (u64)fl->ndocs > ((u64)1 << 32)) return ANSX_ERR_ARG;
+    if (fl->fqoff[0] != 0) return ANSX_ERR_ARG;
+    for (size_t q = 0; q < nqueries; q++)
+        if (fl->fqoff[q] > fl->fqoff[q + 1]) return ANSX_ERR_ARG;
+    for (size_t q = 0; q < nqueries; q++) {
+        bool bad = fl->fqoff[q + 1] - fl->fqoff[q] > ANSX_FILTER_MAX_CLAUSES;
+        for (u64 e = fl->fqoff[q]; !bad && e < fl->fqoff[q + 1]; e++)
+            bad = fl->clauses[e].column >= fl->ncolumns || (fl->clauses[e].flags & ~ANSX_FILTER_NOT) != 0;
+        if (bad) {
+            if (bad_query) *bad_query = q;
+            return ANSX_ERR_ARG;
+        }
+    }
+    return ANSX_OK;
+}
+
+int ansx_topk_filter_batch_dev(ansx_ctx* c, int kind, int f, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
+    const ansx_scorer* scorer, const ansx_facets* facets, const ansx_filters* filters, size_t nqueries, uint32_t k,
+    uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts, uint32_t* out_totals, size_t* bad_container,
+    size_t* bad_query, void* stream)
+{
+    // (every argument check comes before the context is touched: the parent's, the scorer's, the facets', then the filters')
+    if (topk_query_args(c, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, qoff, xterms, xqoff, nqueries, k, d_out_ids,
+            d_out_scores, bad_container, bad_query))
+        return ANSX_ERR_ARG;
+    if (scorer_args(scorer, d_pays)) return ANSX_ERR_ARG;
+    if (facets_args(facets)) return ANSX_ERR_ARG;
+    if (filters_args(filters, nqueries, bad_query)) return ANSX_ERR_ARG;
+    if (nqueries == 0) return ANSX_OK;
+    return run_call(c, stream, [&](hipStream_t s) {
+        return topk_scored_batch(c, kind, f, d_ins, in_bytes, d_pays, pay_bytes, count, terms, weights, occur, (const u64*)qoff, msm, xterms,
+            (const u64*)xqoff, scorer, facets, nqueries, k, d_out_ids, d_out_scores, out_counts, out_totals, bad_container, bad_query, s,
+            filters);
     });
 }
 

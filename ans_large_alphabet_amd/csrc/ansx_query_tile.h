@@ -3,8 +3,8 @@
 // Two parts.  The arithmetic is ANSX_PLAN_FN, as in ansx_plan_types.h: the kernels inline it and the host compiler
 // alone builds it, so tests/tools/query_tile_check.cpp runs, under the sanitizers, the code the kernels run.  The
 // device pieces (ANSX_D) add the thread that does it and the barrier, and are there for the kernels only.
-// On it today: k_isectb_gather, k_isectb_match, k_union_heads, k_topk_hist, k_topk_gather, k_facet_count (and
-// k_topkb_check's limit).
+// On it today: k_isectb_gather, k_isectb_match, k_union_heads, k_topk_hist, k_topk_gather, k_facet_count, k_filter_mark
+// (and k_topkb_check's limit).
 // The other kernels of the same shape still write their frame out, and every kernel its ballot (isect_ballot): DESIGN.md
 // section 3o-2 says which pieces changed their code generation and are therefore not here.
 //
@@ -104,6 +104,23 @@ ANSX_PLAN_FN void facet_chunk(u64 ntiles, u32 grid, u32 wg, u64* t)
 ANSX_PLAN_FN bool facet_lookup(u32 id, u64 ndocs) { return (u64)id < ndocs; }
 ANSX_PLAN_FN bool facet_counted(u32 v, u32 nvalues) { return v < nvalues; }
 ANSX_PLAN_FN u64 facet_row(u32 j, u32 nvalues) { return (u64)j * nvalues; }
+
+// ---- the filter step (ansx_filter.h, k_filter_mark) --------------------------------------
+// Is this id looked up (in 64 bits, as facet_lookup); does value v pass the clause [lo, hi] with `flags` -- lo > hi is the
+// empty range, which with ANSX_FILTER_NOT (bit 0) admits everything; no value is special
+ANSX_PLAN_FN bool filter_lookup(u32 id, u64 ndocs) { return (u64)id < ndocs; }
+ANSX_PLAN_FN bool filter_pass(u32 v, u32 lo, u32 hi, u32 flags) { return (lo <= v && v <= hi) != ((flags & 1u) != 0); }
+// The fused form: is lane's candidate alive in the ballot word the step in front wrote; the word that goes back -- the
+// AND of that word and the filter's verdicts, which is what the ballot of "alive and passes" gives
+ANSX_PLAN_FN bool filter_prior_bit(u64 word, u32 lane) { return ((word >> lane) & 1u) != 0; }
+ANSX_PLAN_FN u64 filter_and(u64 prior, u64 verdict) { return prior & verdict; }
+// the tile's count: the popcounts of its ANSX_ISECT_WORDS ballot words, one per word in wcnt
+ANSX_PLAN_FN u32 filter_tile_count(const u32* wcnt)
+{
+    u32 a = 0;
+    for (u32 k = 0; k < ANSX_ISECT_WORDS; k++) a += wcnt[k];
+    return a;
+}
 
 // ---- the device pieces -------------------------------------------------------------------------------------------
 #ifdef ANSX_D

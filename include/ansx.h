@@ -991,6 +991,60 @@ int ansx_topk_facets_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint
     const ansx_scorer* scorer, const ansx_facets* facets, size_t nqueries, uint32_t k, uint32_t* d_out_ids,
     uint32_t* d_out_scores, uint32_t* out_counts, uint32_t* out_totals, size_t* bad_container, size_t* bad_query, void* stream);
 
+/* ansx_topk_filter_batch_dev: ansx_topk_facets_batch_dev with range filters over document columns -- `year in [2019,
+ * 2024]`, `price <= 5000`, `language != 7`, the click on a facet value (`brand == 17`) -- applied BEFORE the ranking, the
+ * totals and the facet counts (csrc/ansx_filter.h).  filters stands behind facets; every other
+ * argument is ansx_topk_facets_batch_dev's, in its order.  filters == NULL is that call: the same bytes come out and the
+ * same kernels are launched.
+ * A column is a DEVICE array of ndocs uint32_t, the value of document id d < ndocs (4-byte aligned); d_columns is a HOST
+ * array of their ncolumns addresses.  Query q's clauses are clauses[fqoff[q] .. fqoff[q + 1]) (HOST).
+ * A clause passes for document d iff (lo <= v && v <= hi) != ((flags & ANSX_FILTER_NOT) != 0), v = d_columns[column][d].
+ * lo > hi is legal: the empty range, which with ANSX_FILTER_NOT admits every document.  No value has a special meaning: a
+ * caller's "no field" marker such as 0xFFFFFFFF passes or fails like any value.  (Signed integers and floats compare as
+ * uint32 after an order-preserving map: the sign bit flipped, and for floats the usual sign-dependent flip.)
+ * A query's clauses are conjunctive.  A query with no clauses is not filtered and looks nothing up.
+ * The result set: with R(q) the scored call's, R'(q) = { d in R(q) : every clause of q passes }.  Everything
+ * ansx_topk_facets_batch_dev defines over R(q) is defined over R'(q), word for word: the scores and the order (score
+ * descending, id ascending), the output image with ANSX_NO_ID / 0 behind it, out_counts[q] = min(k, |R'(q)|),
+ * out_totals[q] = |R'(q)|, the facet counts, and the overflow rule: a score of 2^32 - 1 or more is an error only for an
+ * id of R'(q).
+ * A bad id: an id of ndocs or more that is in R(q) of a query with at least one clause is ANSX_ERR_DOMAIN with
+ * *bad_query = the first such query of its group; nothing is read at that id.  The comparison is made in 64 bits:
+ * ndocs == 2^32 admits the id 0xFFFFFFFF.  An id that misses a required list, fails the threshold or is excluded is never
+ * looked up, whatever its value.  Where one group has several errors the order is: the score overflow, then the filter's
+ * bad id, then the facets' bad id.
+ * Errors, in this order: before the context is touched, every ANSX_ERR_ARG of ansx_topk_facets_batch_dev (the scorer's
+ * and the facets' included), with the same *bad_query / *bad_container; then, with neither touched, ANSX_ERR_ARG for a
+ * null d_columns or fqoff, or null clauses with fqoff[nqueries] > 0; ncolumns == 0 or above ANSX_FILTER_MAX_COLUMNS;
+ * a null or misaligned column that some clause of clauses[0 .. fqoff[nqueries]) names (a column no clause names is never
+ * touched and may be null); ndocs == 0 or ndocs > 2^32; fqoff[0] != 0 or a descending fqoff; then, with *bad_query = the first offending query, more than
+ * ANSX_FILTER_MAX_CLAUSES clauses, a column >= ncolumns, a flags with a bit other than ANSX_FILTER_NOT.  nqueries == 0:
+ * ANSX_OK, nothing is launched.  Then the parent's errors and the bad id above.
+ * Per group in which some query has a clause: where the group excludes something ONE launch is added (k_filter_mark
+ * between k_bool_exclude and its compaction), else five (k_filter_mark and a compact step); Q + 1 offsets and 24 bytes
+ * per clause ride in the group's one upload, the bad-id word rides home with the overflow word, and no host wait is
+ * added.  A group none of whose queries has a clause launches and uploads nothing more.  No trace is left in the
+ * context, which stays usable after any error.
+ * Out of scope: OR between clauses, multi-valued fields, columns narrower or wider than 32 bits, drill-sideways facet
+ * counts (a facet's counts without its own filter), filters for the unranked calls, a bitmap of live documents. */
+#define ANSX_FILTER_MAX_COLUMNS 64u
+#define ANSX_FILTER_MAX_CLAUSES 16u /* per query */
+#define ANSX_FILTER_NOT 1u
+typedef struct ansx_filter_clause { uint32_t column, lo, hi, flags; } ansx_filter_clause; /* HOST */
+typedef struct ansx_filters {
+    const uint32_t* const* d_columns;  /* HOST array of ncolumns DEVICE pointers, each ndocs uint32_t, 4-byte aligned */
+    uint32_t ncolumns;                 /* 1 .. ANSX_FILTER_MAX_COLUMNS */
+    size_t ndocs;                      /* 1 .. 2^32, one for all columns */
+    const ansx_filter_clause* clauses; /* HOST, fqoff[nqueries] entries */
+    const uint64_t* fqoff;             /* HOST, nqueries + 1: query q's clauses are [fqoff[q], fqoff[q + 1]) */
+} ansx_filters;
+int ansx_topk_filter_batch_dev(ansx_ctx* ctx, int kind, int fidelity, const uint8_t* const* d_ins, const size_t* in_bytes,
+    const uint8_t* const* d_pays, const size_t* pay_bytes, size_t count, const uint32_t* terms, const uint32_t* weights,
+    const uint8_t* occur, const uint64_t* qoff, const uint32_t* msm, const uint32_t* xterms, const uint64_t* xqoff,
+    const ansx_scorer* scorer, const ansx_facets* facets, const ansx_filters* filters, size_t nqueries, uint32_t k,
+    uint32_t* d_out_ids, uint32_t* d_out_scores, uint32_t* out_counts, uint32_t* out_totals, size_t* bad_container,
+    size_t* bad_query, void* stream);
+
 /* Multi-GPU concatenation (the path shards by contiguous ranges of whole blocks, one container per
  * GPU; the reference is single-threaded and has no counterpart -- its per-block calls in
  * src/pseudo_adaptive.cpp:77-130 are the unit that is sharded).  d_parts[i] (8-byte aligned DEVICE
