@@ -1,11 +1,13 @@
-"""One evaluator and one set of generators for the seven query calls on gap-coded lists (no GPU, no torch).
+"""One evaluator and one set of generators for the nine query calls on gap-coded lists (no GPU, no torch).
 
 The evaluator (Model) is written from the contracts in include/ansx.h -- the comments above ansx_intersect_batch_dev,
-ansx_union_batch_dev, ansx_bool_batch_dev, ansx_topk_batch_dev, ansx_topk_bool_batch_dev, ansx_topk_query_batch_dev and
-ansx_topk_scored_batch_dev -- and from nothing else: not from the kernels, not from the numpy judges of the GPU test files.
+ansx_union_batch_dev, ansx_bool_batch_dev, ansx_topk_batch_dev, ansx_topk_bool_batch_dev, ansx_topk_query_batch_dev,
+ansx_topk_scored_batch_dev, ansx_topk_facets_batch_dev and ansx_topk_filter_batch_dev -- and from nothing else: not from
+the kernels, not from the numpy judges of the GPU test files.
 It works in plain Python over dict / collections.Counter / sorted(), ints of unbounded size, and uses numpy only to hold
-the arrays it is handed.  tests/test_query_model_cpu.py holds it against the seven numpy judges and against mutants of
-itself; tests/test_gpu_query_fuzz.py and tests/tools/soak_queries.py hold the library against it.
+the arrays it is handed.  tests/test_query_model_cpu.py and tests/test_query_model_page_cpu.py hold it against the nine
+numpy judges and against mutants of itself; tests/test_gpu_query_fuzz.py, tests/test_gpu_query_fuzz_page.py and
+tests/tools/soak_queries.py hold the library against it.
 
 The generators draw, from a seed, a pool of at most 48 lists (draw_pool) and batches of queries over it (draw_batch).
 POOL_SHAPES names what every pool holds; pool_shapes(pool) recomputes it from the ids alone.
@@ -13,6 +15,13 @@ POOL_SHAPES names what every pool holds; pool_shapes(pool) recomputes it from th
 A query record is a dict: terms, weights, occur (1 required, 0 optional), msm, excl.  A batch is a dict: call, codec, k,
 op ("all" / "any" / None), pays (False: every payload is 1), rows (the scorer's tf_rows, or None), queries, plant.
 Calls that lack an argument ignore the field (CALLS says what each call reads).
+
+The two page calls (PAGE_CALLS: totals, facet counts, range filters) have a numbering of their own, page_case(pool, n),
+whose generator streams are disjoint from those of case(pool, n): every case of the other seven calls and every pool is
+what it was before the page calls were added (tests/golden/query_corpus_digest.json).  A page batch is a batch of the
+scored call with, in addition: totals (whether out_totals is asked for), nvalues (None: no facets), fndocs (the facet
+column's ndocs), clauses (per query a list of (column, lo, hi, negate); the facets call has none) and ndocs (the filter
+columns').  The columns are drawn per seed (columns_of) and are not part of draw_pool's result.
 """
 from collections import Counter
 
@@ -31,8 +40,16 @@ TF_ROWS = (1, 15, 16, 17, 64, 256)
 NDOCS = 1 << 21  # the scorer's norms: lists tagged "low" stay below it
 MAX_WEIGHT, MAX_PAY, MAX_TF, MAX_RUN, MAX_TERMS, MAX_IMPACT = 1 << 10, 1 << 12, 300, 70, 9, 1 << 12
 EDGE_SIZES = (1, 2, 63, 64, 65, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097)
-MUTANTS = ("tie_desc", "matches_terms", "msm_no_floor", "driver_once", "repeats_once", "product_wraps", "row_clamp",
-           "skip_pay0", "drop_noid", "cut_before_tiebreak")
+PAGE_CALLS = ("topk_facets", "topk_filter")
+QUERY_CALLS = ("topk_query", "topk_scored") + PAGE_CALLS  # the calls that plan every run of one kind of query by itself
+NVALUES = (1, 2, 7, 64, 300, 4096, 4097)  # 4096: the most the facet kernel's lds form takes
+FILTER_MAX_CLAUSES = 16  # ANSX_FILTER_MAX_CLAUSES
+CALL_MUTANTS = ("tie_desc", "matches_terms", "msm_no_floor", "driver_once", "repeats_once", "product_wraps", "row_clamp",
+                "skip_pay0", "drop_noid", "cut_before_tiebreak")  # faults of the seven calls: told apart by corpus()
+PAGE_MUTANTS = ("clause_or", "not_ignored", "hi_exclusive", "swapped_range", "total_cut", "facet_k_only", "facet_per_posting",
+                "nvalues_last_bin", "over_unfiltered", "bad_rejected", "bad_clauseless", "facet_bad_unfiltered", "bad_order_swapped",
+                "bad_query_whole_batch")  # faults of the two page calls: told apart by page_corpus()
+MUTANTS = CALL_MUTANTS + PAGE_MUTANTS
 # Two faults of the list the contract makes equivalent to the true evaluator, so that no corpus can tell them apart:
 EQUIVALENT = {
     # matches(d) counts the entries of the optional lists as named, whatever the excluded lists hold, so R(q) = required
@@ -170,13 +187,107 @@ class Model:
         top = scored[:k]
         return dict(ids=[d for d, _ in top], scores=[sat32(s) for _, s in top], count=len(top), size=len(scored), over=over)
 
+    # ---------------------------------------------------------------------------------------------- the page calls
+    def passes(self, clauses, columns, d):
+        """Whether document d passes every clause (column, lo, hi[, negate]) of a query: (lo <= v <= hi) != negate with
+        v = columns[column][d]; lo > hi is the empty range; a query without clauses passes and looks nothing up"""
+        verdicts = []
+        for c in clauses:
+            col, lo, hi = int(c[0]), int(c[1]), int(c[2])
+            negate = len(c) == 4 and bool(c[3])
+            if self.mutant == "not_ignored":
+                negate = False
+            if self.mutant == "swapped_range" and lo > hi:
+                lo, hi = hi, lo
+            v = int(columns[col][d])
+            inside = lo <= v < hi if self.mutant == "hi_exclusive" else lo <= v <= hi
+            verdicts.append(inside != negate)
+        if self.mutant == "clause_or" and verdicts:
+            return any(verdicts)
+        return all(verdicts)
+
+    def page(self, q, k, pays=True, scorer=None, clauses=(), filters=None, facets=None):
+        """One query of ansx_topk_filter_batch_dev (clauses == (): of ansx_topk_facets_batch_dev).  filters: (columns,
+        ndocs), the host images of the columns; facets: (values, ndocs, nvalues) or None.
+        -> dict(ids, scores: the first k of R'(q); count = min(k, |R'|); total = |R'|; row: the facet counts over all of
+        R'(q), None without facets; over: a score of R'(q) reaches 2^32 - 1; filter_bad: the query has a clause and an id
+        of R(q) is ndocs of the filters or more; facet_bad: an id of R'(q) is ndocs of the facets or more).  Behind
+        filter_bad R'(q) is not defined and everything else is None; behind facet_bad the row is None."""
+        r = self.ranked(q, 1 << 32, pays=pays, scorer=scorer)  # all of R(q), in order
+        R = list(zip(r["ids"], r["scores"]))
+        out = dict(ids=None, scores=None, count=None, total=None, row=None, over=False, filter_bad=False, facet_bad=False)
+        looked_up = bool(clauses)
+        if self.mutant == "bad_clauseless":
+            looked_up = filters is not None
+        if looked_up:
+            seen = [d for d, _ in R]
+            if self.mutant == "bad_rejected":
+                seen = [d for t in q["terms"] for d in self.ids[t]]  # every candidate, whatever became of it
+            if any(d >= filters[1] for d in seen):
+                # (R'(q) is not defined here, so neither is "a kept score overflows": over stays False.  A query that has
+                # both a bad id and a score of 2^32 - 1 is therefore not the evaluator's to judge; draw_page_batch asserts
+                # that it draws none -- the queries over the top of the id space carry ordinary weights)
+                return dict(out, filter_bad=True)
+        kept = [(d, s) for d, s in R if self.passes(clauses, filters[0], d)] if clauses else R  # R'(q); no clause: nothing is read
+        judged = R if self.mutant == "over_unfiltered" else kept
+        out["over"] = any(s >= TOP for _, s in judged)  # (ranked() saturates: a score of 2^32 - 1 is one that reached it)
+        top = kept[:k]
+        out.update(ids=[d for d, _ in top], scores=[s for _, s in top], count=len(top), total=len(kept))
+        if self.mutant == "total_cut":
+            out["total"] = len(top)
+        if facets is not None:
+            values, fndocs, nvalues = facets
+            if any(d >= fndocs for d, _ in (R if self.mutant == "facet_bad_unfiltered" else kept)):
+                return dict(out, facet_bad=True)
+            row = [0] * nvalues
+            for d, _ in (top if self.mutant == "facet_k_only" else kept):
+                once = 1  # an id counts once, however many postings it has
+                if self.mutant == "facet_per_posting":
+                    once = sum(self.view(t, pays)[1].get(d, 0) for t in q["terms"])
+                v = int(values[d])
+                if v < nvalues:
+                    row[v] += once
+                elif self.mutant == "nvalues_last_bin" and v == nvalues:
+                    row[nvalues - 1] += once
+            out["row"] = row
+        return out
+
+    def page_results(self, B, scorer, columns):
+        """page() of every query of a page batch; columns: what columns_of(pool) gives"""
+        facets = None if B["nvalues"] is None else (facet_column(columns, B["nvalues"]), B["fndocs"], B["nvalues"])
+        filters = (columns["cols"], B["ndocs"]) if B["call"] == "topk_filter" else None
+        return [self.page(q, B["k"], pays=B["pays"], scorer=scorer, clauses=B["clauses"][i] if filters else (), filters=filters, facets=facets)
+                for i, q in enumerate(B["queries"])]
+
+    def page_errors(self, results, groups):
+        """-> the query the call names, or None.  The call executes its groups in batch order and stops at the first
+        that has an error; inside a group the order is the score overflow, then the filter's bad id, then the facets',
+        and of one kind the first query of the group."""
+        order = ("over", "filter_bad", "facet_bad")
+        if self.mutant == "bad_order_swapped":
+            order = ("over", "facet_bad", "filter_bad")
+        if self.mutant == "bad_query_whole_batch":
+            groups = [(0, len(results))]
+        for q0, q1 in groups:
+            for kind in order:
+                hit = [i for i in range(q0, q1) if results[i][kind]]
+                if hit:
+                    return hit[0]
+        return None
+
     # ---------------------------------------------------------------------------------------------- a whole batch
-    def batch(self, B, scorer=None):
+    def batch(self, B, scorer=None, groups=None, columns=None, results=None):
         """What the call must write for batch B -> dict(status: "ok" or "domain", bad_query, bad_containers, results).
-        results, per query: intersect / bool: the ids; union: (ids, counts); ranked: the dict of ranked()."""
+        results, per query: intersect / bool: the ids; union: (ids, counts); ranked: the dict of ranked(); the page calls:
+        the dict of page().
+        The page calls need `groups`, [(q0, q1)] in batch order, and `columns` (columns_of): which query an error names
+        depends on how the call cut its batch.  ansx_topk_facets_batch_dev and ansx_topk_filter_batch_dev run through
+        the scored call's front, query_plan (csrc/ansx_plan.h) and group loop with two arguments more, so they plan
+        exactly as the scored call does and plan_groups gives their groups by the scored call's rule.  results: the
+        page_results of the batch where the caller has them already (they do not depend on the groups)."""
         call, op = B["call"], B.get("op")
         out = dict(status="ok", bad_query=None, bad_containers=[], results=[])
-        if call == "topk_scored" and B.get("rows") is not None:
+        if call in ("topk_scored",) + PAGE_CALLS and B.get("rows") is not None:
             assert scorer is not None
             ndocs = scorer[2]
             named = sorted({t for q in B["queries"] for t in q["terms"]})
@@ -186,6 +297,14 @@ class Model:
                 return out
         else:
             scorer = None
+        if call in PAGE_CALLS:
+            assert groups is not None and columns is not None, "a page call's error depends on its groups"
+            assert groups[0][0] == 0 and groups[-1][1] == len(B["queries"]) and all(a[1] == b[0] for a, b in zip(groups, groups[1:]))
+            out["results"] = self.page_results(B, scorer, columns) if results is None else results
+            bad = self.page_errors(out["results"], groups)
+            if bad is not None:
+                out["status"], out["bad_query"] = "domain", bad
+            return out
         for i, q in enumerate(B["queries"]):
             if call == "intersect":
                 r = self.intersect(q["terms"])
@@ -662,6 +781,328 @@ def corpus(pool, call):
     return [case(pool, CALLS.index(call) + len(CALLS) * j) for j in range(BATCHES_PER_CALL)]
 
 
+# ====================================================================================================== the page calls' generators
+HASH, MOD7, IDENT, CONST, EXTREME = range(5)  # the filter columns of a seed
+EXTREMES = (0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFE, 0xFFFFFFFF)
+EVERY = (HASH, 0, 0xFFFFFFFF, False)  # a clause every document passes
+FACET_PLANTS = ("overflow", "rejected", "domain", "facet_id")
+FILTER_PLANTS = ("filter_id", "kept_overflow_only", "order")  # ... and one of FACET_PLANTS, another in every seed (page_plants)
+
+
+def draw_columns(seed):
+    """The seed's filter columns over NDOCS documents -- a 16-value hash, id mod 7, the id itself, a constant, extreme
+    values -- and room for its facet columns (facet_column).  A generator of its own: draw_pool is not touched."""
+    rng = np.random.default_rng([seed, 0, 2])
+    ids = np.arange(NDOCS, dtype=np.uint64)
+    mult = int(rng.integers(1 << 20, 1 << 31)) | 1
+    const = int(rng.integers(1, TOP))
+    cols = [((ids * mult % (1 << 32)) >> 28).astype(np.uint32), (ids % 7).astype(np.uint32), ids.astype(np.uint32),
+            np.full(NDOCS, const, dtype=np.uint32), np.array(EXTREMES, dtype=np.uint32)[rng.integers(0, len(EXTREMES), NDOCS)]]
+    return dict(seed=seed, ndocs=NDOCS, cols=cols, const=const, facet={})
+
+
+def facet_column(C, nv):
+    """The seed's facet column for nvalues = nv (made once): values below nv, and nv - 1, nv, nv + 1 and 0xFFFFFFFF"""
+    if nv not in C["facet"]:
+        rng = np.random.default_rng([C["seed"], nv, 3])
+        v = rng.integers(0, nv, NDOCS).astype(np.uint32)
+        edge = rng.random(NDOCS)
+        v[edge < 0.05] = nv - 1
+        v[(edge >= 0.05) & (edge < 0.10)] = nv
+        v[(edge >= 0.10) & (edge < 0.13)] = nv + 1
+        v[(edge >= 0.13) & (edge < 0.16)] = 0xFFFFFFFF
+        C["facet"][nv] = v
+    return C["facet"][nv]
+
+
+def columns_of(pool):
+    if "columns" not in pool:
+        pool["columns"] = draw_columns(pool["seed"])
+    return pool["columns"]
+
+
+def _clause(rng, C):
+    """One clause: any column, a fifth negated; lo == hi, lo > hi, and bounds at 0 and 0xFFFFFFFF among them"""
+    col = int(rng.integers(0, 5))
+    neg = bool(rng.random() < 0.2)
+    if col in (HASH, MOD7):
+        top = 15 if col == HASH else 6
+        lo = int(rng.integers(0, top + 1))
+        hi = int(rng.integers(lo, top + 1)) if rng.random() < 0.85 else int(rng.integers(0, top + 1))
+        r = rng.random()
+        if r < 0.15:
+            hi = lo
+        elif r < 0.25:
+            lo = 0
+        elif r < 0.35:
+            hi = TOP
+    elif col == IDENT:
+        cut, r = int(rng.integers(1, 60000)), rng.random()
+        lo, hi = (0, cut) if r < 0.4 else (cut, TOP) if r < 0.8 else (cut, cut + int(rng.integers(0, 20000)))
+    elif col == CONST:
+        c, r = C["const"], rng.random()
+        lo, hi = (c, c) if r < 0.5 else (0, TOP) if r < 0.7 else (c + 1, TOP) if r < 0.85 else (c, c - 1)
+    else:
+        a, b = (EXTREMES[int(i)] for i in rng.integers(0, len(EXTREMES), 2))
+        lo, hi = (min(a, b), max(a, b)) if rng.random() < 0.8 else (a, b)
+    return (col, lo, hi, neg)
+
+
+def _lenient(rng, C, earlier):
+    """A clause every document passes -- or one the query has already: the same column twice"""
+    r = rng.random()
+    if r < 0.3 and earlier:
+        return earlier[int(rng.integers(0, len(earlier)))]
+    return ((CONST, C["const"], C["const"], False), (HASH, 0, TOP, False), (MOD7, 5, 3, True), (EXTREME, 0, TOP, False),
+            (CONST, C["const"], C["const"] - 1, True), (IDENT, 0, NDOCS - 1, False))[int(rng.integers(0, 6))]
+
+
+def _moderate(rng):
+    """A clause that about half of the documents pass"""
+    col = (HASH, MOD7, IDENT, EXTREME)[int(rng.integers(0, 4))]
+    if col == HASH:
+        lo = int(rng.integers(0, 7))
+        hi = lo + int(rng.integers(6, 10))
+    elif col == MOD7:
+        lo = int(rng.integers(0, 3))
+        hi = lo + int(rng.integers(2, 5))
+    elif col == IDENT:
+        cut = int(rng.integers(10000, 40000))
+        lo, hi = ((0, cut), (cut, TOP), (cut // 2, cut // 2 + 20000))[int(rng.integers(0, 3))]
+    else:
+        a = int(rng.integers(1, len(EXTREMES) - 1))
+        lo, hi = ((0, EXTREMES[a]), (EXTREMES[a], TOP), (EXTREMES[a - 1], EXTREMES[a + 1]))[int(rng.integers(0, 3))]
+    return (col, lo, hi, bool(rng.random() < 0.2))
+
+
+def _clauses(rng, C, n):
+    """n clauses of one query, in a drawn order: one that about half of the documents pass, up to two of any kind, and
+    beyond that lenient ones, so that a query of 16 clauses still has results"""
+    out = []
+    for j in range(n):
+        out.append(_moderate(rng) if j == 0 else _clause(rng, C) if j < 3 and rng.random() < 0.5 else _lenient(rng, C, out))
+    return [out[int(j)] for j in rng.permutation(n)]
+
+
+def draw_page_batch(rng, pool, call, plant="draw", sixteen=False, reach_top=False):
+    """A batch of draw_batch(..., "topk_scored") with or without its scorer, and on top of it: whether totals are asked
+    for, nvalues or no facets, 0 .. 16 clauses per query (the filter call) -- none anywhere in an eighth of the batches, on
+    a single query in another eighth -- and, without a scorer, queries over the pool's lists that reach the top of the id
+    space: excluded, below the threshold, beside a required list, in a query without a clause, and (plant "draw" only)
+    where the id is looked up.  plant: None, "draw", one of FACET_PLANTS, or for the filter call of FILTER_PLANTS.
+    sixteen: some query has exactly FILTER_MAX_CLAUSES clauses.  reach_top: no scorer, facets, the queries over the lists
+    that reach the top of the id space are there, and (the filter call) the facet column is shorter than the filter's."""
+    assert call in PAGE_CALLS and (plant in (None, "draw") + FACET_PLANTS or (call == "topk_filter" and plant in FILTER_PLANTS))
+    L, C = pool["lists"], columns_of(pool)
+    filt = call == "topk_filter"
+    own = plant in ("facet_id", "filter_id", "kept_overflow_only", "order")
+    B = draw_batch(rng, pool, "topk_scored", plant="overflow" if plant == "kept_overflow_only" else None if own else plant)
+    B["call"] = call
+    if plant == "order":
+        B["queries"] = B["queries"][:70]
+    qs = B["queries"]
+    if own or (reach_top and B["plant"] is None) or (not (B["plant"] and B["plant"][0] == "domain") and rng.random() < 0.5):
+        B["rows"] = None  # no scorer: a payload is its own impact (MAX_PAY is within the same bound as MAX_IMPACT)
+    B["totals"] = bool(rng.random() < 0.8) or plant in ("facet_id", "order")
+    B["nvalues"] = NVALUES[int(rng.integers(0, len(NVALUES)))] if rng.random() < 0.8 or plant in ("facet_id", "order") or reach_top else None
+    B["ndocs"] = B["fndocs"] = NDOCS
+    tiny = [L[q["terms"][0]]["ids"].size == 1 for q in qs]
+    part = pool["parts"][B["codec"]]
+    tops = [t for t in part if "top" in L[t]["tags"] and L[t]["pay"] is not None]
+
+    # ---- the clauses
+    clauses = [[] for _ in qs]
+    if filt:
+        def count(i):
+            r = rng.random()
+            # (a result of one id is kept or dropped whole; a high threshold or two required lists mostly leave nothing)
+            barren = qs[i]["msm"] >= 2 or len({t for t, o in zip(qs[i]["terms"], qs[i]["occur"]) if o == MUST}) >= 2
+            barren = barren or bool(set(qs[i]["excl"]) & set(qs[i]["terms"]))
+            if r < (0.95 if tiny[i] else 0.85 if barren else 0.1):
+                return 0
+            return 1 if r < 0.75 else 2 if r < 0.88 else 3 if r < 0.94 else int(rng.integers(4, FILTER_MAX_CLAUSES + 1))
+        shape = rng.random()
+        wide = [i for i in range(len(qs)) if not tiny[i]] or list(range(len(qs)))
+        if shape < 0.125:
+            pass
+        elif shape < 0.25:
+            clauses[wide[int(rng.integers(0, len(wide)))]] = _clauses(rng, C, int(rng.integers(1, 4)))
+        else:
+            clauses = [_clauses(rng, C, count(i)) for i in range(len(qs))]
+        if shape >= 0.25:  # the click on a facet value: a few queries of one mid-sized list under one or two clauses
+            mids = [t for t in part if "low" in L[t]["tags"] and L[t]["pay"] is not None and 50 <= L[t]["ids"].size <= 5000]
+            for _ in range(int(rng.integers(2, 5)) if mids and len(qs) <= 70 else 0):
+                t = int(mids[int(rng.integers(0, len(mids)))])
+                qs.append(dict(terms=[t], weights=[_weight(rng)], occur=[int(rng.integers(0, 2))], msm=0, excl=[]))
+                clauses.append(_clauses(rng, C, int(rng.integers(1, 3))))
+                tiny.append(False)
+        if sixteen:  # ... and beside it a query under the empty range, which nothing passes
+            clauses[max(wide, key=lambda i: L[qs[i]["terms"][0]]["ids"].size)] = _clauses(rng, C, FILTER_MAX_CLAUSES)
+            at = wide[int(rng.integers(0, len(wide)))]
+            qs.append(dict(qs[at], terms=list(qs[at]["terms"]), weights=list(qs[at]["weights"]), occur=list(qs[at]["occur"]), excl=list(qs[at]["excl"])))
+            clauses.append([(EXTREME, 1, 0, False)])
+            tiny.append(False)
+
+    # ---- ids beyond the columns, where nothing looks them up -- and, drawn only, where something does
+    if B["rows"] is None and B["plant"] is None and plant in (None, "draw") and tops and (reach_top or rng.random() < 0.5):
+        kinds = ["excluded", "threshold", "required"] + (["clauseless"] if B["nvalues"] is None or plant == "draw" else [])
+        kinds += ["clause"] if filt and plant == "draw" else []
+        for _ in range(int(rng.integers(1, 4))):
+            at, T = int(rng.integers(0, len(qs))), int(tops[int(rng.integers(0, len(tops)))])
+            low, w = int(qs[at]["terms"][0]), [_weight(rng), _weight(rng)]
+            kind = kinds[int(rng.integers(0, len(kinds)))]
+            if "low" not in L[low]["tags"]:
+                continue  # (the query is one of these already)
+            if filt and kind in ("excluded", "threshold", "required") and not clauses[at] and rng.random() < 0.8:
+                clauses[at] = _clauses(rng, C, int(rng.integers(1, 3)))  # a clause: the ids that stay are looked up, the others never
+            if kind == "excluded":
+                qs[at] = dict(terms=[T, low], weights=w, occur=[SHOULD, SHOULD], msm=0, excl=[T])
+            elif kind == "threshold":  # (the ids beyond the columns are T's alone: they match once, 2^32 - 1 twice)
+                qs[at] = dict(terms=[low, low, T], weights=w + [_weight(rng)], occur=[SHOULD] * 3, msm=3, excl=[])
+            elif kind == "required":
+                qs[at] = dict(terms=[low, T], weights=w, occur=[MUST, SHOULD], msm=0, excl=[])
+            else:
+                qs[at] = dict(terms=[T], weights=w[:1], occur=[SHOULD], msm=0, excl=[])
+                clauses[at] = [EVERY] if kind == "clause" else []
+                B["plant"] = ("mixed", at) if kind == "clause" or B["nvalues"] is not None else B["plant"]
+    # ---- a facet column shorter than the filter's: the clause `id < fndocs` removes in front of the facets what they cannot look up
+    if filt and B["nvalues"] is not None and B["plant"] is None and plant in (None, "draw") and (reach_top or rng.random() < 0.25):
+        ones = [int(L[q["terms"][0]]["ids"][0]) for q, one in zip(qs, tiny) if one and q["occur"][0] == MUST]
+        B["fndocs"] = max([int(rng.integers(20000, 60000))] + [d + 1 for d in ones])  # (a query of that one id needs no clause)
+        spare = int(rng.integers(0, len(qs))) if plant == "draw" and rng.random() < 0.3 else None
+        for i in range(len(qs)):
+            need = max(int(L[t]["ids"][-1]) for t in qs[i]["terms"]) >= B["fndocs"] and not (tiny[i] and qs[i]["occur"][0] == MUST)
+            if i != spare and need:  # (else no id of its result can reach fndocs)
+                clauses[i] = clauses[i][:FILTER_MAX_CLAUSES - 1] + [(IDENT, 0, B["fndocs"] - 1, False)]
+        B["plant"] = ("mixed", spare) if spare is not None else B["plant"]
+
+    # ---- the planted errors of the page calls
+    def lone(t, w=None):
+        return dict(terms=[int(t)], weights=[_weight(rng) if w is None else w], occur=[SHOULD], msm=0, excl=[])
+    if plant in ("facet_id", "filter_id"):
+        at = int(rng.integers(0, len(qs)))
+        qs[at] = lone(tops[int(rng.integers(0, len(tops)))])
+        clauses[at] = [EVERY] if plant == "filter_id" else []
+        B["plant"] = (plant, at)
+    elif plant == "rejected" and filt:
+        clauses = [[] for _ in qs]  # (the committed filter batch without a clause anywhere)
+    elif plant == "overflow" and filt:
+        clauses[B["plant"][1]] = [(IDENT, 0, TOP, False)]  # the clauses keep the overflowing id: the error stands
+    elif plant == "kept_overflow_only":
+        at = B["plant"][1]
+        e, w = L[qs[at]["terms"][0]], qs[at]["weights"][0]
+        calm = [int(d) for d in np.unique(e["ids"]) if w * int(e["pay"][e["ids"] == d].sum()) < TOP]
+        clauses = [[] for _ in qs]  # (clauses on this single query)
+        clauses[at] = [(IDENT, calm[0], calm[0], False)] if calm else [(MOD7, 5, 3, False)]  # only an id that does not overflow, or none
+        B["plant"] = (plant, at)
+    elif plant == "order":
+        # one group (every query optional: one run under the default budget) with the facets' bad id in front of the
+        # filter's, and behind it a group of the other kind with an overflow, which is never reached
+        T = tops[int(rng.integers(0, len(tops)))]
+        low = [t for t in part if "low" in L[t]["tags"] and L[t]["pay"] is not None and L[t]["ids"].size >= 3]
+        a, b = (int(low[int(i)]) for i in rng.integers(0, len(low), 2))
+        at = len(qs)
+        qs += [lone(T), lone(a), lone(T), dict(lone(b, (1 << 31) + int(rng.integers(0, 1 << 20))), occur=[MUST])]
+        clauses += [[], [_moderate(rng)], [_moderate(rng)], [EVERY]]
+        B["plant"] = (plant, at + 2 if filt else at, at)  # (under the default budget, with one group per query)
+    B["clauses"] = clauses if filt else [[] for _ in qs]
+    for q in qs:  # (what Model.page counts on: no query can have a bad id and an overflowing score at once)
+        assert max(q["weights"]) <= MAX_WEIGHT or all("low" in L[t]["tags"] for t in q["terms"]), q
+    assert len(qs) <= 80 and all(len(cl) <= FILTER_MAX_CLAUSES for cl in B["clauses"])
+    return B
+
+
+def page_plants(seed, call):
+    """The plants of the committed cases: the facets call's four; the filter call's own three and ONE of the facets'
+    call's, a different one in each of four consecutive seeds -- seven would leave no committed batch without a plant.
+    (kept_overflow_only is the removed half; a filter batch under "overflow" is the half whose clauses keep the id.)"""
+    return FACET_PLANTS if call == "topk_facets" else FILTER_PLANTS + (FACET_PLANTS[seed % len(FACET_PLANTS)],)
+
+
+def page_case(pool, n):
+    """Page case n of the pool's seed: the call is PAGE_CALLS[n % 2]; as with case(), a call's first cases carry its
+    plants, the others below BATCHES_PER_CALL none, and beyond that they are drawn.  The generator is [seed, n, 1]: no
+    stream of case(), whose generators are [seed, n] (tests/tools/soak_queries.py --seed S --page-case N replays one)"""
+    call = PAGE_CALLS[n % len(PAGE_CALLS)]
+    j = n // len(PAGE_CALLS)
+    plants = page_plants(pool["seed"], call)
+    plant = plants[j] if j < len(plants) else None if j < BATCHES_PER_CALL else "draw"
+    B = draw_page_batch(np.random.default_rng([pool["seed"], n, 1]), pool, call, plant=plant, sixteen=call == "topk_filter" and j == len(plants),
+                        reach_top=j == len(plants) + 1)
+    B["case"], B["page"] = n, True
+    return B
+
+
+def page_corpus(pool, call):
+    """The committed page batches of (the pool's seed, call)"""
+    return [page_case(pool, PAGE_CALLS.index(call) + len(PAGE_CALLS) * j) for j in range(BATCHES_PER_CALL)]
+
+
+def page_expected(pool, B, value=1 << 28, mutant=None):
+    """The evaluator's word on page batch B under ANSX_ISECT_BATCH_INTS = value (the default: 2^28).  The per-query
+    results of the true evaluator are computed once per numbered case; the error is worked out per value."""
+    n = [e["ids"].size for e in pool["lists"]]
+    scorer = scorer_of(pool, B["rows"]) if B["rows"] is not None else None
+    M, C = model_of(pool, mutant), columns_of(pool)
+    key = ("page results", B.get("case"))
+    memo = mutant is None and B.get("case") is not None
+    E = M.batch(B, scorer, groups=plan_groups(n, B, value), columns=C, results=pool.get(key) if memo else None)
+    if memo and E["results"]:
+        pool[key] = E["results"]
+    return E
+
+
+# ====================================================================================================== the digest of what must not change
+def _canonical(x):
+    """x as JSON can write it, the same on every machine: dicts by sorted key, sets sorted, arrays as (dtype, shape, sha256)"""
+    import hashlib
+
+    if isinstance(x, dict):
+        return {str(key): _canonical(v) for key, v in sorted(x.items(), key=lambda e: str(e[0]))}
+    if isinstance(x, (list, tuple)):
+        return [_canonical(v) for v in x]
+    if isinstance(x, (set, frozenset)):
+        return sorted(_canonical(v) for v in x)
+    if isinstance(x, np.ndarray):
+        return [str(x.dtype), list(x.shape), hashlib.sha256(np.ascontiguousarray(x).tobytes()).hexdigest()]
+    if isinstance(x, np.integer):
+        return int(x)
+    if isinstance(x, np.bool_):
+        return bool(x)
+    assert x is None or isinstance(x, (int, str, bool)), type(x)
+    return x
+
+
+def digest(x):
+    import hashlib
+    import json
+
+    return hashlib.sha256(json.dumps(_canonical(x), sort_keys=True, separators=(",", ":")).encode()).hexdigest()
+
+
+def corpus_digest(seed, cases=len(CALLS) * 12):
+    """-> dict(pool, cases): the digests of draw_pool(seed) and of case(pool, n) for n < cases (a fresh pool: nothing the
+    helpers keep in it is hashed)"""
+    P = draw_pool(seed)
+    pool = digest({key: P[key] for key in ("seed", "lists", "parts", "ndocs", "norms", "tables")})
+    return dict(pool=pool, cases=digest([case(P, n) for n in range(cases)]))
+
+
+def expected_page_plant(pool, B, E):
+    """Whether E, the evaluator's outcome under the default budget, is what the page batch's plant set out to cause"""
+    p = B["plant"]
+    if p is None or p[0] in ("rejected", "kept_overflow_only"):
+        return E["status"] == "ok"
+    if p[0] in ("overflow", "facet_id", "filter_id", "order"):
+        ok = E["status"] == "domain" and E["bad_query"] == p[1] and not E["bad_containers"]
+        if p[0] == "order":  # one group per query: the query in front, whatever its kind of error
+            ok = ok and page_expected(pool, B, 1)["bad_query"] == p[2]
+        return ok
+    if p[0] == "domain":
+        return E["status"] == "domain" and E["bad_containers"] == [p[1]] and E["bad_query"] is None
+    return True  # ("mixed": drawn, nothing is promised)
+
+
 # ====================================================================================================== the groups of a call
 # How a call cuts its batch into groups under ANSX_ISECT_BATCH_INTS, restated from the rules above isb_plan, unb_plan and
 # query_plan (csrc/ansx_plan.h) and query_budget (csrc/ansx.hip): not part of the evaluator -- the results do not depend
@@ -669,20 +1110,21 @@ def corpus(pool, call):
 def plan_groups(n, B, value):
     """n: the ints of every list; value: ANSX_ISECT_BATCH_INTS -> [(q0, q1)], the groups of batch B in order.
     A ranked call plans under half the value.  A query's kind is "isb" (its driver set: intersect, op all, a required
-    term) or "unb"; ansx_topk_query_batch_dev and the scored call plan every maximal run of one kind by itself.  A group
+    term) or "unb"; ansx_topk_query_batch_dev, the scored call and the two page calls, which are the scored call with
+    arguments more, plan every maximal run of one kind by itself.  A group
     takes every list it references once (terms, excluded and optional ones alike) and twice the driver's ints (isb: the
     shortest list of the driver set) or twice the ints of the terms as named (unb); it ends in front of the query that
     would take it over the budget, and a query over the budget alone is a group of its own."""
     call, op = B["call"], B.get("op")
-    budget = value // 2 if call in RANKED else value
+    budget = value // 2 if call in RANKED + PAGE_CALLS else value
     kinds, drivers = [], []
     for q in B["queries"]:
-        if call in ("topk_query", "topk_scored"):
+        if call in QUERY_CALLS:
             d = [t for t, o in zip(q["terms"], q["occur"]) if o == MUST]
         else:
             d = list(q["terms"]) if call == "intersect" or op == "all" else []
         kinds.append("isb" if d else "unb"), drivers.append(d)
-    with_excl = call in ("bool", "topk_bool", "topk_query", "topk_scored")
+    with_excl = call in ("bool", "topk_bool") + QUERY_CALLS
     groups, q, nq = [], 0, len(kinds)
     while q < nq:
         q0, ints, seen = q, 0, set()

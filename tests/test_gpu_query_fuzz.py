@@ -1,4 +1,6 @@
-"""Seeded differential tests of the seven query calls on the GPU (-m gpu) against ONE evaluator, tests/query_model.py.
+"""Seeded differential tests of seven of the nine query calls on the GPU (-m gpu) against ONE evaluator,
+tests/query_model.py (the two page calls, ansx_topk_facets_batch_dev and ansx_topk_filter_batch_dev, and all nine on one
+context: tests/test_gpu_query_fuzz_page.py, which imports this file's pool and helpers).
 
 Expected values never come from the code under test and, unlike in the sibling files, not from a judge written beside a
 kernel either: query_model.Model is plain Python over the contracts of include/ansx.h, held against the seven numpy judges

@@ -11,6 +11,7 @@ filled with a sentinel -- the counts with garbage, which the call must zero -- a
 checked intact.  Every case runs under both values of ANSX_FACET_FORM and the default, with ANSX_FACET_GRID of 1, 2 and 3,
 without the wave's combined add, and once with ANSX_ISECT_BATCH_INTS=1, which gives one group per query.
 
+Batches drawn from a seed, with their plants, forms and agreements: tests/test_gpu_query_fuzz_page.py (the two of section 5 stay).
 Not covered here: ndocs = 2^32, a device total that differs from the host's bound, and grids beyond the tiles -- they live
 in tests/tools/facet_check.cpp, which runs the kernel's arithmetic (ansx_query_tile.h) over made-up candidates.
 """

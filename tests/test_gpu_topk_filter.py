@@ -11,6 +11,7 @@ id itself, which lets a clause keep exactly one id or only the ids of a query's 
 a sentinel and has SPARE entries behind, which are checked intact.  Every case runs under both values of
 ANSX_FILTER_FORM and the default, and with ANSX_ISECT_BATCH_INTS=1, which gives one group per query.
 
+Batches drawn from a seed, with their plants, forms and agreements: tests/test_gpu_query_fuzz_page.py (the two of section 5 stay).
 Not covered here: ndocs = 2^32, a device total that differs from the host's bound, 16 clauses in the workgroup's path with
 every kind of bound -- they live in tests/tools/filter_check.cpp, which runs the kernel's arithmetic (ansx_query_tile.h)
 over made-up candidates.

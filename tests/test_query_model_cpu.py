@@ -1,4 +1,5 @@
-"""The evaluator and the generators of tests/query_model.py, checked without a GPU.
+"""The evaluator and the generators of tests/query_model.py, checked without a GPU: the seven calls that page_case() does
+not number (the two page calls, their generators and their mutants: tests/test_query_model_page_cpu.py).
 
 1. The evaluator against worked examples of the tree, copied as literal numbers.
 2. The evaluator against the seven numpy judges of the GPU test files (expected_lists / expect of test_gpu_intersect.py,
@@ -180,7 +181,7 @@ def differs(P, B, mutant):
     return [strip(r) for r in a["results"]] != [strip(r) for r in b["results"]]
 
 
-@pytest.mark.parametrize("mutant", Q.MUTANTS)
+@pytest.mark.parametrize("mutant", Q.CALL_MUTANTS)  # (the page calls' mutants: tests/test_query_model_page_cpu.py)
 def test_the_committed_corpus_tells_every_mutant_from_the_evaluator(mutant):
     found = None
     for seed in Q.SEEDS:
@@ -268,7 +269,7 @@ def as_written(F, B, E):
     return got
 
 
-@pytest.mark.parametrize("mutant", [m for m in Q.MUTANTS if m not in Q.EQUIVALENT])
+@pytest.mark.parametrize("mutant", [m for m in Q.CALL_MUTANTS if m not in Q.EQUIVALENT])
 def test_the_gpu_files_comparator_rejects_what_a_mutant_would_have_written(mutant):
     """judge of tests/test_gpu_query_fuzz.py, which needs no GPU: it accepts the evaluator's own image of a case and rejects
     the image a mutant's result makes, so a kernel with that fault could not pass the GPU file"""

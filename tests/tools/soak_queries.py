@@ -1,12 +1,16 @@
-"""Randomised soak of the seven query calls against the evaluator of tests/query_model.py (manual tool, not collected by pytest):
+"""Randomised soak of the nine query calls against the evaluator of tests/query_model.py (manual tool, not collected by pytest):
 
     SOAK_SECONDS=240 SOAK_SEED=101 python tests/tools/soak_queries.py     # on an MI355X box: seeds 101 and 102, half the time each
     python tests/tools/soak_queries.py --seed 11 --case 37                 # replays one case, under every form of its call
+    python tests/tools/soak_queries.py --seed 11 --page-case 5             # replays one case of the two page calls, likewise
+    SOAK_PAGE=1 SOAK_SECONDS=240 python tests/tools/soak_queries.py        # the soak over the page cases 0, 1, 2, ...
 
 The generators and the evaluator are those of tests/test_gpu_query_fuzz.py: per seed one pool of 48 lists (query_model.draw_pool)
 and the cases 0, 1, 2, ... of that seed (query_model.case: the call is CALLS[n % 7], the first cases of a call carry its planted
 errors, later ones draw them).  Case n runs under the default form and under form n // 7 of its call's cycle (FORMS of the test
-file); every output array, count, offset and error field is compared with the evaluator and the two runs byte for byte.  One
+file); every output array, count, offset and error field is compared with the evaluator and the two runs byte for byte.  The
+page cases (query_model.page_case: ansx_topk_facets_batch_dev, ansx_topk_filter_batch_dev) have a numbering of their own and run
+through run / judge / PAGE_FORMS of tests/test_gpu_query_fuzz_page.py, totals and facet rows included.  One
 process, one time limit, no retry: it stops at the first mismatch, and at the first HIP error, abort or fault, and prints the case.
 
 Run on one MI355X (the calls as of ansx_topk_scored_batch_dev): SOAK_SECONDS=240 SOAK_SEED=101, seeds 101 and 102, 120 s each:
@@ -29,6 +33,7 @@ torch.zeros(1).cuda()
 import ans_large_alphabet_amd as A  # noqa: E402
 import query_model as Q  # noqa: E402
 import test_gpu_query_fuzz as F  # noqa: E402
+import test_gpu_query_fuzz_page as FP  # noqa: E402
 
 
 def one_case(ctx, G, n, forms):
@@ -45,12 +50,34 @@ def one_case(ctx, G, n, forms):
     return B
 
 
+def one_page_case(ctx, G, n, forms):
+    """-> the page case; raises on the first difference"""
+    B = Q.page_case(G["pool"], n)
+    ref = FP.run(torch, ctx, G, B)
+    FP.judge(G, B, FP.expected(G, B), ref)
+    for keys in forms(B):
+        E = FP.expected(G, B, keys)  # (which query an error names depends on the keys' budget)
+        got = FP.run(torch, ctx, G, B, keys=keys)
+        FP.judge(G, B, E, got, keys)
+        assert E["status"] != "ok" or FP.image(got) == FP.image(ref), FP.describe(G, B, keys) + ": not the bytes of the default form"
+    return B
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--case", type=int, default=None)
+    ap.add_argument("--page-case", type=int, default=None)
     args = ap.parse_args()
     ctx = A.Context(0)
+    if args.page_case is not None:
+        seed = args.seed if args.seed is not None else int(os.environ.get("SOAK_SEED", "1"))
+        G = FP.page_pool(A, torch, ctx, seed)
+        B = one_page_case(ctx, G, args.page_case, lambda B: FP.PAGE_FORMS[B["call"]])
+        print("page case", args.page_case, "of seed", seed, "passes:", FP.describe(G, B))
+        for i, q in enumerate(B["queries"]):
+            print("  query", i, q, "clauses", B["clauses"][i])
+        return 0
     if args.case is not None:
         seed = args.seed if args.seed is not None else int(os.environ.get("SOAK_SEED", "1"))
         G = F.device_pool(A, torch, ctx, seed)
@@ -61,14 +88,18 @@ def main():
         return 0
     first = args.seed if args.seed is not None else int(os.environ.get("SOAK_SEED", "1"))
     budget = float(os.environ.get("SOAK_SECONDS", "240"))
-    total, per_call, plants = 0, {c: 0 for c in Q.CALLS}, {}
+    page = os.environ.get("SOAK_PAGE", "") not in ("", "0")
+    total, per_call, plants = 0, {c: 0 for c in (Q.PAGE_CALLS if page else Q.CALLS)}, {}
     for seed in (first, first + 1):
         t0 = time.time()
-        G = F.device_pool(A, torch, ctx, seed)
+        G = FP.page_pool(A, torch, ctx, seed) if page else F.device_pool(A, torch, ctx, seed)
         n = 0
         while time.time() - t0 < budget / 2:
             try:
-                B = one_case(ctx, G, n, lambda B: [F.FORMS[B["call"]][(n // len(Q.CALLS)) % len(F.FORMS[B["call"]])]])
+                if page:
+                    B = one_page_case(ctx, G, n, lambda B: [FP.PAGE_FORMS[B["call"]][(n // len(Q.PAGE_CALLS)) % len(FP.PAGE_FORMS[B["call"]])]])
+                else:
+                    B = one_case(ctx, G, n, lambda B: [F.FORMS[B["call"]][(n // len(Q.CALLS)) % len(F.FORMS[B["call"]])]])
             except BaseException as e:  # a mismatch, a HIP error, anything: the first one ends the run
                 print("FAIL seed", seed, "case", n, "->", type(e).__name__, e)
                 print("SOAK stopped: iterations", total, "per call", per_call)
